@@ -49,6 +49,8 @@ HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: 8.0 TB/s spec
 MODE_NAMES = {0: "median", 1: "mean", 2: "sigma-clip", 3: "winsorized sigma-clip",
               4: "MAD sigma-clip", 5: "linear-fit"}
 VALU_ISSUE_PEAK = 256 * 4 * 2.4e9 / 2.0      # wave-instructions/s: 1024 SIMDs, one wave64 VALU instruction per 2 cycles (MI355X_MICROARCH.md), 2.4 GHz
+DUMP_MAX_PIXELS = 1 << 22                    # --dump-outputs: at most 16 MiB of float32 result values
+DUMP_SAMPLE_SEED = 20261015
 TRAFFIC_FILES = ("r06_traffic.json", "r05_traffic.json", "r04_traffic.json", "r03_traffic.json", "r02_traffic.json", "r01_traffic.json")
 
 
@@ -89,7 +91,29 @@ def parse():
                          "device-side counter reduction all the same -- the RCCL code path of the scaling run on one GPU")
     ap.add_argument("--share-device", action="store_true",
                     help="rehearsal on a 1-GPU box: every rank uses device 0 (needs --backend gloo)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step of the headline workload returned: DIR/result.npy (float32, the "
+                         "stacked image in row-major pixel order, or, when it has more than %d pixels, those at a fixed "
+                         "seeded sample of %d sorted pixel indices) and DIR/clip_counters.npy (float64 [low, high])"
+                         % (DUMP_MAX_PIXELS, DUMP_MAX_PIXELS))
     return ap.parse_args()
+
+
+def dump_sample_index(pixels):
+    """Pixel indices --dump-outputs writes: all of them, or a fixed seeded sample of DUMP_MAX_PIXELS, sorted."""
+    import numpy as np
+    if pixels <= DUMP_MAX_PIXELS:
+        return np.arange(pixels, dtype=np.int64)
+    rng = np.random.default_rng(DUMP_SAMPLE_SEED)
+    return np.sort(rng.choice(pixels, DUMP_MAX_PIXELS, replace=False, shuffle=False))
+
+
+def write_outputs(out_dir, image, clip_counters):
+    """--dump-outputs: the stacked image (or its sample, dump_sample_index) and the clip counters of one pass."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "result.npy"), np.ascontiguousarray(image[dump_sample_index(image.size)], np.float32))
+    np.save(os.path.join(out_dir, "clip_counters.npy"), np.array(clip_counters, np.float64))
 
 
 def cpu_info():
@@ -387,10 +411,11 @@ def main():
     # global clip totals (the log line of stack.go:214-218 needs them on every pass)
     totals = torch.zeros(2, dtype=torch.int64, device="cuda" if on_device else "cpu")
 
-    def time_stack(frames, mode, steps, warmup, weights=None, geo=None):
+    def time_stack(frames, mode, steps, warmup, weights=None, geo=None, dump=False):
         """One workload on this rank's row tile: `warmup` untimed passes, then exactly `steps` timed ones
         bracketed by barrier + synchronize.  Returns the handle (still open) and the timings.
-        geo = (width, image_rows, row0, rows) of another geometry than the headline's (1-GPU extras)."""
+        geo = (width, image_rows, row0, rows) of another geometry than the headline's (1-GPU extras).
+        dump: also return what the last timed pass gave its caller -- this rank's result rows and the global clip counters."""
         gw, gh, gr0, grows = geo or (w, image_rows, row0, rows)
         st = StackHandle(frames, gw, gh, row0=gr0, rows=grows, device=device)
         st.fill_synthetic()
@@ -443,11 +468,12 @@ def main():
                             works[k].wait()
                             works[k] = None
                 comm.synchronize()
-            st.finish()
+            counters = st.finish()
             torch.cuda.synchronize()
             if dist is not None:
                 dist.barrier()
                 torch.cuda.synchronize()
+            return counters
 
         for _ in range(args.preheat_steps):                  # device clock ramp, untimed (see --preheat-steps)
             step()
@@ -458,7 +484,7 @@ def main():
         t0 = time.perf_counter()
         for _ in range(steps):
             step()
-        fence()
+        last_counters = fence()
         dt = time.perf_counter() - t0
 
         # HIP-event times of the timed passes, read back from the handle's ring after the fact
@@ -466,6 +492,13 @@ def main():
         times = [st.pass_times(b) for b in range(timed)]
         pass_ms = float(np.mean([t[0] for t in times]))
         k_ms = float(np.mean([t[1] for t in times]))
+        outputs = None
+        if dump:
+            if dist is not None and on_device:
+                last_counters = ring[(seq[0] - 1) % 3][:2].tolist()
+            elif dist is not None:
+                last_counters = totals.tolist()
+            outputs = {"result_rows": st.download_rows(-1, 0, grows), "clip_counters": [int(c) for c in last_counters]}
         # one more pass, synchronous as OpStack.Apply runs it (enqueue, wait, read the counters back)
         if ring is not None:
             st.set_counters_buffer(None)                     # (back to the handle's own counters)
@@ -494,7 +527,8 @@ def main():
                 totals.copy_(torch.tensor([cl, ch], dtype=torch.int64))
             dist.all_reduce(totals)
             cl, ch = int(totals[0].item()), int(totals[1].item())
-        return st, {"dt": dt, "pass_ms": pass_ms, "k_ms": k_ms, "timed": timed, "cl": cl, "ch": ch, "sync_ms": sync_ms, "ranks": ranks}
+        return st, {"dt": dt, "pass_ms": pass_ms, "k_ms": k_ms, "timed": timed, "cl": cl, "ch": ch, "sync_ms": sync_ms, "ranks": ranks,
+                    "outputs": outputs}
 
     def strip_parity(frames, mode, geo, weights_, strip_rows, res, cc):
         """The first strip_rows rows of the tile through the C ABI against the oracle's result `res` / counters `cc`
@@ -564,8 +598,16 @@ def main():
     weights = None
     if args.weighted:
         weights = np.array([0.2 + 0.8 * ((k * 37) % 101) / 100.0 for k in range(n)], np.float32)
-    st, tm = time_stack(n, args.mode, args.steps, args.warmup, weights)
+    st, tm = time_stack(n, args.mode, args.steps, args.warmup, weights, dump=bool(args.dump_outputs))
     dt, pass_ms, k_ms, timed, cl, ch = tm["dt"], tm["pass_ms"], tm["k_ms"], tm["timed"], tm["cl"], tm["ch"]
+    if args.dump_outputs:
+        # the ranks' row tiles, in rank order, are the rows of the image this run stacked
+        parts = [tm["outputs"]["result_rows"]]
+        if world > 1:
+            parts = [None] * world
+            dist.all_gather_object(parts, tm["outputs"]["result_rows"])
+        if rank == 0:
+            write_outputs(args.dump_outputs, np.concatenate(parts), tm["outputs"]["clip_counters"])
 
     if rank == 0:
         pixels_per_step = image_rows * w

@@ -12,6 +12,8 @@ import numpy as np
 _PKG = os.path.dirname(os.path.abspath(__file__))
 # NLSTACK_LIB: another build of the same library (A/B timing of kernel variants)
 LIB_PATH = os.environ.get("NLSTACK_LIB") or os.path.join(_PKG, "libnlstack.so")
+# make -C nightlight_amd/csrc EXPERIMENTS=1: the default library plus the kernels that lost their A/B (tests only)
+EXP_LIB_PATH = os.path.join(_PKG, "libnlstack_exp.so")
 
 ST_MEDIAN, ST_MEAN, ST_SIGMA, ST_WINSOR_SIGMA, ST_MAD_SIGMA, ST_LINEAR_FIT, ST_AUTO = range(7)
 WEIGHT_NONE, WEIGHT_EXPOSURE, WEIGHT_INVERSE_NOISE, WEIGHT_INVERSE_HFR = range(4)
@@ -81,16 +83,22 @@ class FitsHeader(C.Structure):
 def load():
     """Load libnlstack.so (built in-tree by __graft_entry__.build())."""
     global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise NlError(ERR_NO_DEVICE, "libnlstack.so is not built (%s); run "
-                      "`python -c 'import __graft_entry__ as g; g.build()'`" % LIB_PATH)
+    if _lib is None:
+        _lib = open_library(LIB_PATH)
+    return _lib
+
+
+def open_library(path):
+    """Open the build of the library at `path` with every prototype declared (load() opens LIB_PATH this way; the
+    tests of the experiments build open nightlight_amd/libnlstack_exp.so beside it)."""
+    if not os.path.exists(path):
+        raise NlError(ERR_NO_DEVICE, "%s is not built; run "
+                      "`python -c 'import __graft_entry__ as g; g.build()'`" % path)
     try:  # if torch is used in this process, let its bundled HIP runtime load first
         import torch  # noqa: F401
     except Exception:  # pragma: no cover - torch is optional for the C ABI
         pass
-    L = C.CDLL(LIB_PATH)
+    L = C.CDLL(path)
     vp = C.c_void_p
     L.nl_last_error.restype = C.c_char_p
     L.nl_version.restype = C.c_char_p
@@ -205,7 +213,6 @@ def load():
     L.nl_host_set_devices.argtypes = [_intp, C.c_int]
     L.nl_host_op_stack_roundtrip_json.argtypes = [C.c_char_p]
     L.nl_host_op_stack_roundtrip_json.restype = C.c_char_p
-    _lib = L
     return L
 
 

@@ -31,13 +31,22 @@ def nl():
 
 
 @pytest.fixture(scope="session")
-def experiments(nl):
-    """Skips tests of the kernels that only the experiments build carries (make -C nightlight_amd/csrc EXPERIMENTS=1:
-    the four-pixels-per-wave replay, the split / persistent LDS-column pass, chunked passes, the guarded linear fit)."""
-    import ctypes
+def experiments_lib(nl):
+    """The experiments build (make -C nightlight_amd/csrc EXPERIMENTS=1, which build() runs: the four-pixels-per-wave
+    replay, the split / persistent LDS-column pass, chunked passes, the guarded linear fit): the library the suite runs
+    on when that is already this build, else nightlight_amd/libnlstack_exp.so opened beside it."""
     from nightlight_amd import capi
-    lib = ctypes.CDLL(capi.LIB_PATH)
-    lib.nl_version.restype = ctypes.c_char_p
+    lib = capi.load()
     if b"+experiments" not in lib.nl_version():
-        pytest.skip("needs the experiments build of libnlstack.so")
+        lib = capi.open_library(capi.EXP_LIB_PATH)
+        if b"+experiments" not in lib.nl_version():
+            pytest.fail("%s is not the experiments build" % capi.EXP_LIB_PATH)
+    return lib
+
+
+@pytest.fixture
+def experiments(experiments_lib, monkeypatch):
+    """Runs the test on the experiments build: every handle the test creates goes through that library."""
+    from nightlight_amd import capi
+    monkeypatch.setattr(capi, "_lib", experiments_lib)
     return True

@@ -895,11 +895,10 @@ def test_extreme_magnitudes_weighted_dispatch(nl, oracle, mode, n, scale):
 @pytest.mark.parametrize("n", [5, 16, 24, 32, 100, 128, 200, 256, 300, 512])
 @pytest.mark.parametrize("mode", sorted(MODES))
 def test_padded_frame_stride_gives_the_dense_layout_s_bits(nl, oracle, monkeypatch, mode, n, weighted, pad):
-    if weighted and mode in (0, 4, 5):
-        pytest.skip("mode ignores weights / MADSigma with weights is unimplemented in the reference")
     width, height = 131, 9
     frames = make_frames(n, width, height, seed=9100 + 13 * n + mode, nan_frac=0.02)
     w = np.random.default_rng(n + mode).uniform(0.2, 1.0, n).astype(np.float32) if weighted else None
+    ow = None if mode in (0, 5) else w          # median and linear fit ignore the weights (stack.go:158,188)
 
     def run(stride_pad):
         monkeypatch.setenv("NL_STRIDE_PAD", str(stride_pad))
@@ -912,6 +911,15 @@ def test_padded_frame_stride_gives_the_dense_layout_s_bits(nl, oracle, monkeypat
             stats = st.frame_stats(n // 2)
             return out, (cl, ch), back, stats
 
+    if weighted and mode == 4:
+        # MADSigma with weights is unimplemented in the reference (it panics): the pass fails with its message, in
+        # either layout
+        from nightlight_amd import capi
+        for stride_pad in (0, pad):
+            with pytest.raises(capi.NlError) as e:
+                run(stride_pad)
+            assert e.value.code == capi.ERR_WEIGHTED_MAD
+        return
     dense, dc, dback, dstats = run(0)
     padded, pc, pback, pstats = run(pad)
     assert pc == dc and bits_equal(padded, dense), "%s n=%d pad %d: %s" % (MODES[mode], n, pad,
@@ -919,7 +927,7 @@ def test_padded_frame_stride_gives_the_dense_layout_s_bits(nl, oracle, monkeypat
     assert bits_equal(pback, frames[n - 1].reshape(pback.shape)) and bits_equal(dback, pback)
     assert np.array_equal(np.asarray(pstats, dtype=np.float64), np.asarray(dstats, dtype=np.float64), equal_nan=True)
     if mode >= 2:
-        rc, want, wl, wh, _ = oracle.stack_apply(mode, frames, w, 2.75, 2.75, 0.5, num_cpu=4)
+        rc, want, wl, wh, _ = oracle.stack_apply(mode, frames, ow, 2.75, 2.75, 0.5, num_cpu=4)
         assert rc == 0 and pc == (wl, wh)
 
 
