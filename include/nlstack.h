@@ -234,9 +234,9 @@ int nl_stack_order_stream_after(nl_stack_t *h, void *hip_stream);
 /* on != 0: run every mode with the bit-exact kernels only (per-pixel replay
  * of the reference's permutation; slow, used for verification; 1 = one pixel
  * per lane with the column in LDS, 2 = one wavefront per pixel, 3 = one
- * wavefront per 64 consecutive pixels with their columns in LDS, 4 = four
- * pixels per wavefront on 16-lane rows -- 2, 3 and 4 exist for sigma and
- * winsorized clipping, weighted or not; by default the weighted clip modes run 3
+ * wavefront per 64 consecutive pixels with their columns in LDS -- 2 and 3
+ * exist for sigma and winsorized clipping, weighted or not; 4 (four pixels per
+ * wavefront) was removed with the experiments build and fails with NL_ERR_INVALID_ARG; by default the weighted clip modes run 3
  * for shallow stacks, a decision pass + 2 for 33 ... 512 frames, 2 above).  Default 0:
  * sigma clipping uses the register-resident kernel, which keeps the clip
  * counters identical to the reference's and the output within summation-order
@@ -246,23 +246,21 @@ int nl_stack_set_exact(nl_stack_t *h, int on);
  * same either way): bit 0 = plain pass protocol (memset before, reduction kernel after every pass) instead of
  * the fused one, bit 1 = the exact replay of the dominant kernel's hand-overs runs in front of the generic pass
  * on the same stream instead of beside it (kernel traces then show each kernel's own duration), bit 2 = weighted
- * stacks replay every clipping round in full (no decision pass), bit 3 (8) = weighted stacks skip the
- * four-pixels-per-wave replay, bit 4 (16) = they skip the 64-pixels-per-wave tile replay (the next engine of the
+ * stacks replay every clipping round in full (no decision pass), bit 3 (8) = no effect (its replay was removed),
+ * bit 4 (16) = weighted stacks skip the 64-pixels-per-wave tile replay (the next engine of the
  * table in DESIGN.md section 3 runs), bit 5 (32) = a pass records none of its three timing events (start, dominant
  * kernel start / end; nl_stack_pass_times then fails with NL_ERR_INVALID_ARG for that pass.  The event at the END of a
  * pass stays: asynchronous uploads order themselves behind it.  tools/wall_probe.py measures what the events cost),
- * bit 6 (64) = no chunked pass even where the environment variable NL_CHUNKS asks for one,
+ * bit 6 (64) = no effect (chunked passes were removed),
  * bit 7 (128) = winsorized passes of 16 ... 128 frames without the winsorization cascade,
  * bit 9 (512) = the first pass on a handle takes no list-length hints from earlier handles of the same geometry.
- * bit 10 (1024) = sigma clipping of 497 ... 512 frames as TWO kernels (sorting kernel, then a rounds kernel over columns kept in
- * device memory, 352 bytes per pixel; also NL_MLZ_SPLIT=1) -- measured slower than the one-kernel pass, DESIGN.md section 5n.
- * bit 11 (2048) = the same class with persistent workgroups (three per CU looping over blocks of 64 pixels, no barrier: a block's
- * rounds run in one wave while the others sort the next block; also NL_MLZ_PERSIST=1) -- slower as well, same section.
+ * bits 10 (1024) and 11 (2048) selected the split and the persistent LDS-column pass (measured slower), bit 12
+ * (4096) the guarded linear fit: their code was removed with the experiments build.
  * bit 13 (8192) = generic pass and first replay of a short-listed sigma pass on two streams (the protocol of rounds 2 - 4)
  * instead of one launch (stack_tail_fused.hip; also NL_TAIL_FUSED=0), for A/B runs.
- * Default 0.  Bits 10 and 11 (and nl_stack_set_exact(h, 4), and the environment switches NL_CHUNKS, NL_MLZ_SPLIT, NL_MLZ_PERSIST,
- * NL_COOP4, NL_LFG) select code of the EXPERIMENTS build (make EXPERIMENTS=1 -> libnlstack_exp.so): the default library
- * rejects the two bits and the flavour with NL_ERR_INVALID_ARG instead of running its one kernel under another name.
+ * bit 14 (16384) = winsorization loops without the invariant-interval certificate.
+ * Default 0.  Bits 10 and 11 (like nl_stack_set_exact(h, 4)) are rejected with NL_ERR_INVALID_ARG ("removed with the experiments
+ * build") instead of running another kernel under their name.
  * No counterpart in the reference. */
 int nl_stack_set_dev_flags(nl_stack_t *h, unsigned flags);
 /* Pixels of the last pass that were re-done by the exact kernel. */
@@ -272,12 +270,11 @@ int64_t nl_stack_last_fallback_pixels(nl_stack_t *h);
 int64_t nl_stack_last_generic_pixels(nl_stack_t *h);
 /* How the last pass was enqueued (diagnostics; the results do not depend on it): bit 0 = fused protocol (no memset in front, no
  * reduction kernel behind: sigma / winsorized passes once a handle knows its list lengths), bit 1 = generic pass and first
- * replay as one launch (plain sigma, 65 ... 128 frames, short exact lists; stack_tail_fused.hip), bit 2 = chunked (experiments
- * build).  No counterpart in the reference. */
+ * replay as one launch (plain sigma, 65 ... 128 frames, short exact lists; stack_tail_fused.hip).  No counterpart in the
+ * reference. */
 int nl_stack_last_pass_protocol(nl_stack_t *h);
 /* Linear-fit cascade of the last pass (stack_linfit.hip; StackLinearFit stack.go:834-918 has no
- * counterpart, diagnostics only): counts[s] = pixels stage s handed to stage s+1 (4 stages; entries 4 ... 7 belong to the
- * guarded stages of the experiments build and are zero in the default library).  Writes min(n, 8) values -- pass a buffer
+ * counterpart, diagnostics only): counts[s] = pixels stage s handed to stage s+1 (4 stages; entries 4 ... 7 are zero).  Writes min(n, 8) values -- pass a buffer
  * of 8 -- and returns how many, 0 when the last pass ran no cascade. */
 int nl_stack_linfit_stage_counts(nl_stack_t *h, unsigned *counts, int n);
 /* Name of the dominant kernel launched by the last pass (for profiles). */

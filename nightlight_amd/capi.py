@@ -12,8 +12,6 @@ import numpy as np
 _PKG = os.path.dirname(os.path.abspath(__file__))
 # NLSTACK_LIB: another build of the same library (A/B timing of kernel variants)
 LIB_PATH = os.environ.get("NLSTACK_LIB") or os.path.join(_PKG, "libnlstack.so")
-# make -C nightlight_amd/csrc EXPERIMENTS=1: the default library plus the kernels that lost their A/B (tests only)
-EXP_LIB_PATH = os.path.join(_PKG, "libnlstack_exp.so")
 
 ST_MEDIAN, ST_MEAN, ST_SIGMA, ST_WINSOR_SIGMA, ST_MAD_SIGMA, ST_LINEAR_FIT, ST_AUTO = range(7)
 WEIGHT_NONE, WEIGHT_EXPOSURE, WEIGHT_INVERSE_NOISE, WEIGHT_INVERSE_HFR = range(4)
@@ -89,8 +87,8 @@ def load():
 
 
 def open_library(path):
-    """Open the build of the library at `path` with every prototype declared (load() opens LIB_PATH this way; the
-    tests of the experiments build open nightlight_amd/libnlstack_exp.so beside it)."""
+    """Open the build of the library at `path` with every prototype declared (load() opens LIB_PATH this way; another
+    build can be opened beside it for A/B comparisons in one process)."""
     if not os.path.exists(path):
         raise NlError(ERR_NO_DEVICE, "%s is not built; run "
                       "`python -c 'import __graft_entry__ as g; g.build()'`" % path)

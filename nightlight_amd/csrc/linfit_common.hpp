@@ -1,5 +1,4 @@
-// linfit_common.hpp -- helpers shared by the linear-fit kernels: stack_linfit.hip (bit-exact cascade) and
-// stack_linfit_guard.hip (guarded stages in front of it).
+// linfit_common.hpp -- helpers of the linear-fit kernels (stack_linfit.hip, bit-exact cascade).
 #pragma once
 #include "fast_ml_common.hpp"
 

@@ -16,17 +16,6 @@
 
 #include "stack_kernels.h"
 
-// Kernels and pass protocols that were built, tested and measured slower than what is dispatched live in the
-// experiments build (make EXPERIMENTS=1, -DNL_EXPERIMENTS): the four-pixels-per-wave replay (stack_exact_coop4.hip),
-// chunked passes, the split / persistent LDS-column pass, the round-1 multi-lane kernel, the guarded linear fit.
-#ifdef NL_EXPERIMENTS
-#define NL_COOP4_SUPPORTED(mode, weighted, n) (nl::coop4_supported(mode, weighted, n) != 0)
-#define NL_LAUNCH_COOP4(...) nl::launch_stack_sigma_coop4(__VA_ARGS__)
-#else
-#define NL_COOP4_SUPPORTED(mode, weighted, n) false
-#define NL_LAUNCH_COOP4(...) hipErrorNotSupported
-#endif
-
 namespace {
 
 thread_local std::string g_err;
@@ -67,7 +56,6 @@ constexpr int kListLanes = 4;       // pixels per wave there: few pixels, keep d
 constexpr int kOrderRing = 8;              // events nl_stack_order_stream_after cycles through
 constexpr unsigned kFusedMaxList = 512;    // exact-list length up to which a pass runs the fused protocol
 constexpr unsigned kTailFusedMaxList = 512;    // ... up to which generic pass and first replay share one launch (stack_tail_fused.hip)
-constexpr int kMaxChunks = 16;             // pixel ranges of a chunked pass
 // winsorization cascade, "clipping passes : winsorization rounds per pass : regions of the previous stage's list per
 // workgroup" for every stage (the last one runs to the end): measured on 4096^2 -- up to 40 frames
 // 16 / 24 frames 3.68 / 3.94 -> 2.97 / 3.07 ms, 41 ... 96 frames (64: 5.22 -> 4.59 ms); beyond that a continuing stage
@@ -78,6 +66,18 @@ constexpr int kWinsorCascadeMaxFrames = 96;
 // per-pass device scratch, zeroed by one memset (or, in the fused protocol of the sigma / winsorized fast path, by
 // the previous pass's dominant kernel -- two sets alternate): clip accumulators + list lengths + snapshot
 constexpr size_t kScratchBytes = sizeof(unsigned long long) * nl::kScratchWords;
+
+// Developer switches (nl_stack_set_dev_flags, include/nlstack.h): A/B measurements, the results are the same either way
+constexpr unsigned kDevPlainProtocol = 1u;         // memset before, reduction kernel after every pass
+constexpr unsigned kDevReplayInFront = 2u;         // first replay in front of the generic pass, on the same stream
+constexpr unsigned kDevNoDecision = 4u;            // weighted stacks: no decision pass, no recorded rounds
+constexpr unsigned kDevNoTile = 16u;               // weighted stacks skip the 64-pixels-per-wave tile replay
+constexpr unsigned kDevUntimed = 32u;              // a pass records none of its timing events
+constexpr unsigned kDevNoWinsorCascade = 128u;     // winsorized passes without the winsorization cascade
+constexpr unsigned kDevNoSharedHints = 512u;       // no list-length hints from earlier handles of the same geometry
+constexpr unsigned kDevRemovedPasses = 1024u | 2048u;     // split / persistent LDS-column pass: removed, rejected
+constexpr unsigned kDevTwoStreamTail = 8192u;      // generic pass and first replay on two streams, not one launch
+constexpr unsigned kDevNoCertificate = 16384u;     // winsorization loops without the invariant-interval certificate
 
 // ---- device-memory cache ---------------------------------------------------------------------------------------------
 // The cgo drop-in creates a handle per OpStack.Apply (stack.go:131-138 allocates per call as well) and destroys it
@@ -426,10 +426,6 @@ struct nl_stack {
     unsigned *d_fb_list = nullptr;             // [npix] pixels the fast kernel handed to the exact kernel
     unsigned *d_fb_count = nullptr;            // [2]: exact-list length, generic-list length (inside d_partial)
     unsigned *d_gen_list = nullptr;            // [npix] pixels zonal waves handed to the generic pass
-    float *d_cols = nullptr;                   // split LDS-column pass (FastArgs::cols): rows of cols_stride floats, allocated on first use
-    size_t cols_bytes = 0;
-    int64_t cols_stride = 0;
-    bool cols_tried = false;
     bool force_exact = false;
     int exact_flavour = 0;            // nl_stack_set_exact argument: 1 = LDS column kernel, 2 = wave-per-pixel replay
     bool last_used_fast = false;
@@ -437,13 +433,11 @@ struct nl_stack {
     unsigned long long *d_counters_own = nullptr;
     double *d_stat_partial = nullptr;          // [kStatBlocks*3]
     // linear-fit cascade (stack_linfit.hip): ping-pong pixel lists + liveness masks, lazily allocated
-    // (a third list + masks for the guarded stages' hand-overs, stack_linfit_guard.hip: up to 128 frames)
-    unsigned *d_lf_list[3] = {nullptr, nullptr, nullptr};
-    uint4 *d_lf_state[3] = {nullptr, nullptr, nullptr};
+    unsigned *d_lf_list[2] = {nullptr, nullptr};
+    uint4 *d_lf_state[2] = {nullptr, nullptr};
     unsigned *d_lf_count = nullptr;
     int lf_lanes = 0;                          // liveness masks per listed pixel the state arrays were sized for
-    int lf_lists = 0;                          // lists allocated (2, or 3 with the guarded stages)
-    bool lf_tried = false, lf_no_third = false;
+    bool lf_tried = false;
     void *d_ingest = nullptr;                  // raw FITS bytes / unaligned source frame, grown on demand
     size_t ingest_bytes = 0;
     // asynchronous uploads: pinned staging ring + copy stream (nl_stack_upload_frame_async)
@@ -457,14 +451,6 @@ struct nl_stack {
     bool stage_used[kStageSlots] = {false, false, false, false};
     int stage_next = 0;
     bool uploads_pending = false;
-    // chunked passes (sigma / winsorized fast path, see chunk_plan): the dominant kernel runs as a few launches over
-    // consecutive pixel ranges, each range with hand-over lists of its own, and the tail of a range (generic pass,
-    // exact replays) runs on two more streams while the next range's dominant kernel has the device
-    hipStream_t chunk_stream[2] = {nullptr, nullptr};      // [0]: generic pass + replay of its additions, [1]: replay of the dominant kernel's list
-    hipEvent_t ev_chunk[kMaxChunks] = {};                  // behind the dominant kernel of a chunk
-    hipEvent_t ev_chunk_join[2] = {nullptr, nullptr};
-    unsigned *d_chunk_counts = nullptr;                    // [kMaxChunks][4]: exact-list length, generic-list length, snapshot, spare
-    int last_chunks = 0;                                   // chunks of the last pass (0: not chunked)
     int max_grid = 0;
     int last_mode = -1;
     bool last_has_counters = false;
@@ -551,14 +537,7 @@ extern "C" {
 
 const char *nl_last_error(void) { return g_err.c_str(); }
 
-const char *nl_version(void)
-{
-#ifdef NL_EXPERIMENTS
-    return "nlstack 0.2.0 (gfx950) +experiments";
-#else
-    return "nlstack 0.2.0 (gfx950)";
-#endif
-}
+const char *nl_version(void) { return "nlstack 0.2.0 (gfx950)"; }
 
 void nl_release_cached_memory(void) { cache_release_all(); stream_pool_release_all(); pinned_release_all(); }
 
@@ -581,8 +560,6 @@ static int destroy_impl(nl_stack_t *h)
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     if (h->side_stream) (void)hipStreamSynchronize(h->side_stream);
     if (h->copy_stream) (void)hipStreamSynchronize(h->copy_stream);
-    for (int i = 0; i < 2; i++)
-        if (h->chunk_stream[i]) (void)hipStreamSynchronize(h->chunk_stream[i]);
     // (the large create-time buffers are parked for the next handle of the same geometry, see cached_free)
     cached_free(h->d_frames_owned, (size_t)h->fstride_owned * sizeof(float) * (size_t)h->n_capacity, h->device);
     cached_free(h->d_out, (size_t)h->npix * sizeof(float), h->device);
@@ -594,13 +571,12 @@ static int destroy_impl(nl_stack_t *h)
     cached_free(h->d_nrounds, (size_t)h->npix, h->device);
     cached_free(h->d_fb_list, sizeof(unsigned) * (size_t)h->npix, h->device);
     cached_free(h->d_gen_list, sizeof(unsigned) * (size_t)h->npix, h->device);
-    if (h->d_cols) cached_free(h->d_cols, h->cols_bytes, h->device);
     if (h->d_counters_own) (void)hipFree(h->d_counters_own);
     if (h->d_stat_partial) (void)hipFree(h->d_stat_partial);
     if (h->d_ingest) (void)hipFree(h->d_ingest);
     if (h->d_ingest_async) (void)hipFree(h->d_ingest_async);
     if (h->d_stat_partial_async) (void)hipFree(h->d_stat_partial_async);
-    for (int i = 0; i < 3; i++) {          // (parked like the create-time buffers: a handle per Apply pays no hipMalloc for them)
+    for (int i = 0; i < 2; i++) {          // (parked like the create-time buffers: a handle per Apply pays no hipMalloc for them)
         cached_free(h->d_lf_list[i], sizeof(unsigned) * (size_t)h->npix, h->device);
         cached_free(h->d_lf_state[i], sizeof(uint4) * (size_t)h->npix * (size_t)h->lf_lanes, h->device);
     }
@@ -617,13 +593,6 @@ static int destroy_impl(nl_stack_t *h)
         if (h->ring_dom0[i]) (void)hipEventDestroy(h->ring_dom0[i]);
         if (h->ring_dom1[i]) (void)hipEventDestroy(h->ring_dom1[i]);
     }
-    for (int i = 0; i < 2; i++) {
-        if (h->chunk_stream[i]) { (void)hipStreamSynchronize(h->chunk_stream[i]); (void)hipStreamDestroy(h->chunk_stream[i]); }
-        if (h->ev_chunk_join[i]) (void)hipEventDestroy(h->ev_chunk_join[i]);
-    }
-    for (int i = 0; i < kMaxChunks; i++)
-        if (h->ev_chunk[i]) (void)hipEventDestroy(h->ev_chunk[i]);
-    if (h->d_chunk_counts) (void)hipFree(h->d_chunk_counts);
     if (h->side_stream) (void)hipStreamSynchronize(h->side_stream);
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
     if (h->ev_join) (void)hipEventDestroy(h->ev_join);
@@ -866,17 +835,15 @@ int64_t nl_stack_device_bytes(nl_stack_t *h)
     if (h->d_nrounds) b += np;
     if (h->d_fb_list) b += np * 4;
     if (h->d_gen_list) b += np * 4;
-    if (h->d_cols) b += (int64_t)h->cols_bytes;
     if (h->d_counters) b += 32;
     if (h->d_stat_partial) b += 8 * 3 * kStatBlocks;
     if (h->d_stat_partial_async) b += 8 * 3 * kStatBlocks;
     const int lanes = h->n_capacity <= 128 ? 1 : h->n_capacity <= 256 ? 2 : 4;
-    for (int i = 0; i < 3; i++) {
+    for (int i = 0; i < 2; i++) {
         if (h->d_lf_list[i]) b += np * 4;
         if (h->d_lf_state[i]) b += np * 16 * lanes;
     }
     if (h->d_lf_count) b += 4 * nl::kLinfitCounters;
-    if (h->d_chunk_counts) b += 16 * kMaxChunks;
     b += (int64_t)h->ingest_bytes + (int64_t)h->ingest_async_bytes;
     return b;
 }
@@ -991,11 +958,9 @@ int nl_weights_from_scalars(int weighting, const float *per_frame, int n_frames,
     return fail(NL_ERR_INVALID_WEIGHTING, "Invalid weighting mode %d\n", weighting);
 }
 
-// Linear-fit cascade buffers (stack_linfit.hip, stack_linfit_guard.hip): pixel lists and state arrays with
-// lanes_per_pixel liveness masks (16 B) per pixel, allocated on first use -- two for the bit-exact cascade, a third
-// for the guarded stages' hand-overs (up to 128 frames).  Without them (allocation failure) the kernels run as a
-// single bit-exact stage.
-static bool linfit_buffers(nl_stack_t *h, int lists = 2)
+// Linear-fit cascade buffers (stack_linfit.hip): two pixel lists and state arrays with lanes_per_pixel liveness masks
+// (16 B) per pixel, allocated on first use.  nullptr (allocation failure): the kernels run as a single bit-exact stage.
+static const nl::LinfitCascade *linfit_cascade(nl_stack_t *h, nl::LinfitCascade *out)
 {
     if (!h->lf_tried) {
         // sized for the most lanes per pixel any active frame count of this handle can need
@@ -1005,33 +970,18 @@ static bool linfit_buffers(nl_stack_t *h, int lists = 2)
             (void)hipGetLastError();
             h->d_lf_count = nullptr;
         }
-    }
-    if (!h->d_lf_count) return false;
-    const size_t np = (size_t)h->npix;
-    if (lists > 2 && h->lf_no_third) return false;
-    while (h->lf_lists < lists) {                     // (the third list only when a guarded linear fit asks for it)
-        const int i = h->lf_lists;
-        if (cached_malloc((void **)&h->d_lf_list[i], sizeof(unsigned) * np, h->device) != hipSuccess ||
-            cached_malloc((void **)&h->d_lf_state[i], sizeof(uint4) * np * (size_t)h->lf_lanes, h->device) != hipSuccess) {
-            (void)hipGetLastError();
-            if (h->d_lf_list[i]) { (void)hipFree(h->d_lf_list[i]); h->d_lf_list[i] = nullptr; }
-            h->d_lf_state[i] = nullptr;
-            if (i < 2) {                               // no cascade at all on this handle
-                (void)hipFree(h->d_lf_count);
+        const size_t np = (size_t)h->npix;
+        for (int i = 0; h->d_lf_count && i < 2; i++)
+            if (cached_malloc((void **)&h->d_lf_list[i], sizeof(unsigned) * np, h->device) != hipSuccess ||
+                cached_malloc((void **)&h->d_lf_state[i], sizeof(uint4) * np * (size_t)h->lf_lanes, h->device) != hipSuccess) {
+                (void)hipGetLastError();
+                if (h->d_lf_list[i]) { (void)hipFree(h->d_lf_list[i]); h->d_lf_list[i] = nullptr; }
+                h->d_lf_state[i] = nullptr;
+                (void)hipFree(h->d_lf_count);              // no cascade at all on this handle
                 h->d_lf_count = nullptr;
-            } else {
-                h->lf_no_third = true;                 // the bit-exact cascade keeps its two lists
             }
-            return false;
-        }
-        h->lf_lists++;
     }
-    return true;
-}
-
-static const nl::LinfitCascade *linfit_cascade(nl_stack_t *h, int /*lanes_per_pixel*/, nl::LinfitCascade *out)
-{
-    if (!linfit_buffers(h, 2)) return nullptr;
+    if (!h->d_lf_count) return nullptr;
     out->list[0] = h->d_lf_list[0]; out->list[1] = h->d_lf_list[1];
     out->state[0] = h->d_lf_state[0]; out->state[1] = h->d_lf_state[1];
     out->count = h->d_lf_count;
@@ -1039,62 +989,16 @@ static const nl::LinfitCascade *linfit_cascade(nl_stack_t *h, int /*lanes_per_pi
     return out;
 }
 
-#ifdef NL_EXPERIMENTS
-// the guarded stages' buffers (three lists); false: run the bit-exact cascade alone
-static bool linfit_guard_bufs(nl_stack_t *h, nl::LinfitGuardBufs *out)
-{
-    static const bool on = [] { const char *e = getenv("NL_LFG"); return e && e[0] == '1'; }();
-    if (!on || (h->dev_flags & 4096u)) return false;                  // developer switch 4096: bit-exact cascade only (A/B)
-    if (h->n_capacity > 128 || !linfit_buffers(h, 3)) return false;
-    for (int i = 0; i < 3; i++) { out->list[i] = h->d_lf_list[i]; out->state[i] = h->d_lf_state[i]; }
-    out->count = h->d_lf_count;
-    out->capacity = (unsigned)h->npix;
-    return true;
-}
-#endif
-
 // Weighted sigma / winsorized stacks of 33 ... 512 frames run a decision pass in front of the bit-exact replay
 // (33 ... 128 frames: stack_fast_decide.hip, 129 ... 512: the LDS-column kernel of the class, record-only), and
 // unweighted winsorized passes above 128 frames put their decided rounds on record for the list replay: scratch for the
 // thresholds, kBoundRounds * 8 + 1 bytes per pixel of the tile (1.1 GB for 4096^2), allocated by the first pass that
-// wants it and held until the handle is destroyed; nl_stack_device_bytes() reports what a handle holds at any time.  false: off (NL_WDECIDE=0, developer switch 4, allocation failed: those passes then run without it).
-// The split pass of the selected LDS-column kernel (stack_fast_mlz_impl.hpp, FastArgs::cols): 352 bytes per pixel for the
-// columns between the sorting kernel and the rounds kernel.  OFF by default -- measured slower than the one-kernel pass
-// (sigma 512 x 4096^2 10.72 against 10.20 ms); NL_MLZ_SPLIT=1 or developer switch 1024 turn it on.
-static void set_split_cols(nl_stack *h, int mode, int n_frames, nl::FastArgs &f)
-{
-#ifndef NL_EXPERIMENTS
-    (void)h; (void)mode; (void)n_frames; (void)f;          // (the default library carries the one-kernel pass only)
-#else
-    const int rows = nl::mlz_split_rows(mode, n_frames);
-    static const bool on = [] { const char *e = getenv("NL_MLZ_SPLIT"); return e && e[0] == '1'; }();
-    // (the same class as persistent workgroups -- three per CU, no barrier, the rounds of a block behind the sorting of the
-    // next: also built, also slower; NL_MLZ_PERSIST=1 / developer switch 2048)
-    static const bool persist = [] { const char *e = getenv("NL_MLZ_PERSIST"); return e && e[0] == '1'; }();
-    if (rows != 0 && (persist || (h->dev_flags & 2048u)) && !(h->dev_flags & 1024u) && f.fb_count) {
-        f.persistent = 1;
-        f.ticket = f.fb_count + 3;                     // (fourth word of the pass's list counters: zeroed with them)
-    }
-    if (rows == 0 || !(on || (h->dev_flags & 1024u))) return;
-    if (!h->d_cols && !h->cols_tried) {
-        h->cols_tried = true;
-        h->cols_stride = (h->npix + 63) / 64 * 64;
-        h->cols_bytes = (size_t)rows * (size_t)h->cols_stride * sizeof(float);
-        if (cached_malloc((void **)&h->d_cols, h->cols_bytes, h->device) != hipSuccess) {
-            (void)hipGetLastError();
-            h->d_cols = nullptr;
-        }
-    }
-    if (!h->d_cols) return;
-    f.cols = h->d_cols;
-    f.cols_stride = h->cols_stride;
-#endif
-}
-
+// wants it and held until the handle is destroyed; nl_stack_device_bytes() reports what a handle holds at any time.
+// false: off (NL_WDECIDE=0, developer switch kDevNoDecision, allocation failed: those passes then run without it).
 static bool ensure_bounds(nl_stack *h)
 {
     static const bool on = [] { const char *e = getenv("NL_WDECIDE"); return !(e && e[0] == '0'); }();
-    if (!on || (h->dev_flags & 4u)) return false;
+    if (!on || (h->dev_flags & kDevNoDecision)) return false;
     if (h->d_bounds) return true;
     if (h->bounds_tried) return false;
     h->bounds_tried = true;
@@ -1109,85 +1013,15 @@ static bool ensure_bounds(nl_stack *h)
     return true;
 }
 
-// Chunked passes (developer switch NL_CHUNKS; off by default, see chunk_plan).  The tail of a sigma / winsorized fast pass -- generic pass, bit-exact replay of the undecidable
-// pixels -- is latency- and gather-bound and depends on the dominant kernel, which is bound by VALU issue: run one after
-// the other they leave each other's resource idle (sigma 512 x 4096^2: 10.6 ms + 0.76 ms).  A chunked pass launches the
-// dominant kernel over a few consecutive pixel ranges; every range has hand-over lists of its own, and its tail runs
-// on two more streams while the next range's dominant kernel has the device.  Only the tail of the LAST range is
-// exposed, so the ranges shrink towards the end.  The plan: per cent of the tile per range (the last takes the rest).
-struct ChunkPlan {
-    int n = 0;
-    int64_t off[kMaxChunks], len[kMaxChunks];
-};
-
-static void chunk_plan(const nl_stack *h, int mode, bool weighted, int n_frames, ChunkPlan *plan)
+// The sigma / winsorized fast path from 17 frames on (a zonal kernel followed by a generic pass) runs the FUSED protocol
+// (StackArgs::final): no memset in front of the pass -- the previous fused pass's dominant kernel zeroed this pass's
+// scratch set, the two sets alternate -- and no reduction kernel behind it.  NL_FUSED=0 (developer switch) keeps
+// memset + reduce_counters_kernel for A/B runs, and turns off the recorded rounds of winsorized passes above 128 frames.
+static bool fused_protocol_on()
 {
-    plan->n = 0;
-#ifdef NL_EXPERIMENTS
-    // NL_CHUNKS (developer switch): "0" = never, "p1,p2,..." = these ranges whenever the fast path runs
-    static const std::vector<double> env_plan = [] {
-        std::vector<double> v;
-        const char *e = getenv("NL_CHUNKS");
-        if (!e) return v;
-        for (const char *p = e; *p;) {
-            char *end = nullptr;
-            const double x = strtod(p, &end);
-            if (end == p) break;
-            v.push_back(x);
-            p = (*end == ',') ? end + 1 : end;
-            if (*end != ',') break;
-        }
-        if (v.empty()) v.push_back(0.0);
-        return v;
-    }();
-    if (h->dev_flags & 64u) return;                    // developer switch 64: no chunks (A/B inside one process)
-    if (!(mode == NL_ST_SIGMA || mode == NL_ST_WINSOR_SIGMA) || weighted) return;
-    // OFF unless NL_CHUNKS asks for it: measured (round 4), the overlap LOSES -- a replay wave
-    // (64 registers, latency-bound, resident for ~100 us) takes the slot of a dominant-kernel wave (168 registers,
-    // three per SIMD), and the VALU-bound kernel slows down by more than the tail it hides: sigma 512 x 4096^2
-    // 11.47 ms unchunked, 11.97 ms chunked at default stream priority, 13.6 - 14.3 ms with high-priority tails.
-    (void)n_frames;
-    if (env_plan.empty() || (env_plan.size() == 1 && env_plan[0] <= 0.0)) return;
-    const double *pc = env_plan.data();
-    int n = (int)env_plan.size();
-    if (n < 2) return;
-    if (n > kMaxChunks) n = kMaxChunks;
-    int64_t at = 0;
-    for (int k = 0; k < n && at < h->npix; k++) {
-        int64_t len = (int64_t)((double)h->npix * pc[k] / 100.0);
-        len = (len + 1023) & ~(int64_t)1023;           // whole workgroups of every dominant kernel, aligned loads
-        if (len <= 0) continue;
-        if (k == n - 1 || at + len > h->npix) len = h->npix - at;
-        plan->off[plan->n] = at;
-        plan->len[plan->n] = len;
-        plan->n++;
-        at += len;
-    }
-    if (plan->n > 0 && at < h->npix) plan->len[plan->n - 1] += h->npix - at;
-    if (plan->n < 2) plan->n = 0;
-#else
-    (void)h; (void)mode; (void)weighted; (void)n_frames;      // (the default library has no chunked passes: measured slower)
-#endif
+    static const bool on = [] { const char *e = getenv("NL_FUSED"); return !(e && e[0] == '0'); }();
+    return on;
 }
-
-#ifdef NL_EXPERIMENTS
-static int ensure_chunk_resources(nl_stack *h)
-{
-    if (h->d_chunk_counts) return NL_OK;
-    // the tails get the wave slots the dominant kernel's retiring workgroups free BEFORE its own next workgroups do
-    // (NL_CHUNK_PRIO=0: default priority, for A/B runs)
-    static const bool prio = [] { const char *e = getenv("NL_CHUNK_PRIO"); return !(e && e[0] == '0'); }();
-    int least = 0, greatest = 0;
-    NL_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
-    for (int i = 0; i < 2; i++) {
-        NL_HIP(hipStreamCreateWithPriority(&h->chunk_stream[i], hipStreamNonBlocking, prio ? greatest : 0));
-        NL_HIP(hipEventCreateWithFlags(&h->ev_chunk_join[i], hipEventDisableTiming));
-    }
-    for (int i = 0; i < kMaxChunks; i++) NL_HIP(hipEventCreateWithFlags(&h->ev_chunk[i], hipEventDisableTiming));
-    NL_HIP(dev_malloc(&h->d_chunk_counts, sizeof(unsigned) * 4 * kMaxChunks));
-    return NL_OK;
-}
-#endif  // NL_EXPERIMENTS
 
 static int auto_select_mode(int l)   // stack.go:45-55
 {
@@ -1195,6 +1029,411 @@ static int auto_select_mode(int l)   // stack.go:45-55
     if (l >= 15) return NL_ST_WINSOR_SIGMA;
     if (l >= 6) return NL_ST_SIGMA;
     return NL_ST_MEAN;
+}
+
+// ---- one stack pass: run_async_impl sets it up, select_engine picks the engine that runs it ----------------------------
+
+// the engines, in the order select_engine tries them
+enum class Engine {
+    Mean,
+    MedianRegisters,      // register-resident sorting network, up to 128 frames
+    MedianMultiLane,      // 129 ... 512 frames, 2 or 4 lanes per pixel
+    Listed,               // MAD sigma / linear fit, one- or multi-lane: dominant kernel + bit-exact replay of its list
+    SigmaFast,            // sigma / winsorized: dominant kernel + generic pass, replays of the pixels both hand over
+    WeightedTile,         // bit-exact replay, 64 consecutive pixels per wave with their columns in LDS
+    DenseReplay,          // bit-exact wave-per-pixel replay over the whole tile (behind a decision pass where there is one)
+    ExactColumns,         // bit-exact, one pixel per lane with its column in LDS: every mode, any depth
+};
+
+// what the prologue of the pass decided, for the engine
+struct PassSetup {
+    int mode;
+    bool weighted;
+    bool timed;               // the pass records its timing events (not with kDevUntimed)
+    bool fused;               // fused protocol (fused_protocol_on; only the SigmaFast engine runs it)
+    nl::StackArgs a;
+};
+
+// what a pass leaves behind, written into the handle's last_* fields by every pass (and reset by a failed one)
+struct PassFacts {
+    bool has_counters = false;    // d_counters holds the pass's clip counters
+    bool used_fast = false;       // a dominant kernel handed pixels over: the list lengths belong to this pass
+    bool lists = false;           // ... and sit behind the totals (d_counters[2])
+    bool fused = false;           // fused protocol: this pass's scratch set used, the other one zeroed
+    bool tail_fused = false;      // generic pass + first replay ran as one launch (stack_tail_fused.hip)
+    bool zeroed_behind = false;   // the reduction kernel left the scratch set zeroed
+};
+
+static void set_last_pass(nl_stack *h, const PassFacts &f)
+{
+    h->last_has_counters = f.has_counters;
+    h->last_used_fast = f.used_fast;
+    h->last_lists = f.lists;
+    h->last_fused = f.fused;
+    h->last_tail_fused = f.tail_fused;
+    h->sets_clean = f.fused;
+}
+
+// Pure: allocates nothing, enqueues nothing.  The first engine whose condition holds runs the pass.
+static Engine select_engine(const nl_stack *h, int mode, bool weighted, const nl::StackArgs &a)
+{
+    const bool fast = !h->force_exact;
+    const int n = a.n_frames;
+    if (mode == NL_ST_MEAN) return Engine::Mean;
+    if (fast && mode == NL_ST_MEDIAN && nl::fast_supported(mode, weighted, n, a.npix)) return Engine::MedianRegisters;
+    if (fast && mode == NL_ST_MEDIAN && nl::fast_ml_supported(mode, weighted, n, a.npix)) return Engine::MedianMultiLane;
+    if (fast && h->d_fb_list &&
+        (nl::mad_fast_supported(mode, weighted, n, a.npix) || (mode == NL_ST_MAD_SIGMA && nl::fast_ml_supported(mode, weighted, n, a.npix)) ||
+         nl::linfit_ml_supported(mode, n, a.npix) || nl::linfit_fast_supported(mode, n, a.npix)))
+        return Engine::Listed;
+    if (fast && h->d_fb_list && (nl::fast_supported(mode, weighted, n, a.npix) || nl::fast_ml_supported(mode, weighted, n, a.npix)))
+        return Engine::SigmaFast;
+    // nl_stack_set_exact(h, 3) forces the tile replay, 2 the wave-per-pixel one (verification)
+    if ((h->exact_flavour == 3 ||
+         (fast && weighted && !(h->dev_flags & kDevNoTile) &&
+          n <= (mode == NL_ST_WINSOR_SIGMA ? nl::kTileMaxFramesWinsor : nl::kTileMaxFramesSigma))) &&
+        nl::tile_supported(mode, weighted, n))
+        return Engine::WeightedTile;
+    if ((h->exact_flavour == 2 || (fast && (weighted || n > 512))) && nl::coop_supported(mode, weighted, n))
+        return Engine::DenseReplay;
+    return Engine::ExactColumns;
+}
+
+// FastArgs of a dominant kernel that hands pixels to the exact replay (fb_*) and / or to the generic pass (gen_*)
+static nl::FastArgs list_args(const nl_stack *h, bool exact_list, bool generic_list)
+{
+    nl::FastArgs f;
+    memset(&f, 0, sizeof f);
+    if (exact_list) {
+        f.fb_list = h->d_fb_list;
+        f.fb_count = h->d_fb_count;
+        f.fb_capacity = (unsigned)h->npix;
+    }
+    if (generic_list) {
+        f.gen_list = h->d_gen_list;                 // (nullptr for huge tiles: the median kernel then sorts in full everywhere)
+        f.gen_count = h->d_fb_count + 1;
+        f.gen_capacity = (unsigned)h->npix;
+    }
+    return f;
+}
+
+// the exact list (d_fb_list) replayed by the LDS-column kernel, kListLanes pixels per wave
+static int replay_list(nl_stack *h, int mode, bool weighted, const nl::StackArgs &a)
+{
+    int lanes = 0;
+    size_t lds = 0;
+    if (nl::exact_plan(mode, weighted, a.n_frames, a.n_pad, kListLanes, &lanes, &lds) != 0)
+        return fail(NL_ERR_TOO_MANY_FRAMES, "%d frames do not fit the per-pixel LDS column (mode %d)", a.n_frames, mode);
+    nl::StackArgs e = a;
+    e.list = h->d_fb_list;
+    e.list_count = h->d_fb_count;
+    e.list_capacity = (unsigned)h->npix;
+    const char *exact_name = "";
+    NL_HIP(nl::launch_stack_exact(mode, weighted, e, lanes, kListGrid, lds, h->stream, &exact_name));
+    return NL_OK;
+}
+
+// Grids of the wave-per-pixel list replays: one wave per workgroup, grid-stride over a list whose length is only known on
+// the device; launching 16 k workgroups for a few hundred pixels costs more than replaying them, so the length the last
+// finished pass reported (nl_stack_finish) sizes the grid.  grid0: the dominant kernel's hand-overs, grid1: the generic
+// pass's additions.
+static void replay_grids(const nl_stack *h, int *grid0, int *grid1)
+{
+    *grid0 = kCoopGrid;
+    *grid1 = kCoopGrid / 4;
+    if (h->fb_hint) {
+        const int want = next_pow2((int)(2u * (h->fb_hint - 1u) + 64u));
+        *grid0 = want < 1024 ? 1024 : (want > kCoopGrid ? kCoopGrid : want);      // (a 256-workgroup floor measured the same)
+        *grid1 = *grid0 / 4 < 512 ? 512 : *grid0 / 4;
+    }
+}
+
+// The decision pass of a weighted sigma / winsorized stack in front of the whole-tile replay: it leaves the clip bounds of
+// every round it can decide in a.bounds / a.nrounds.  33 ... 128 frames: the register-resident kernel; 129 ... 512: the
+// LDS-column kernel of the frame-count class (FastArgs::record_only: no outputs, lists or counters; a pixel it would hand
+// to the generic pass has no round on record).
+static int decision_pass(nl_stack *h, const PassSetup &p, nl::StackArgs &a)
+{
+    if (!p.weighted || h->exact_flavour != 0 || p.mode == NL_ST_MEDIAN) return NL_OK;
+    const char *ignored = "";
+    if (nl::decide_supported(p.mode, a.n_frames, a.npix) && ensure_bounds(h)) {
+        a.bounds = h->d_bounds;
+        a.nrounds = h->d_nrounds;
+        NL_HIP(nl::launch_stack_sigma_decide(a, h->stream, p.mode == NL_ST_WINSOR_SIGMA, &ignored));
+    } else if (nl::decide_ml_supported(p.mode, a.n_frames, a.npix) && ensure_bounds(h)) {
+        a.bounds = h->d_bounds;
+        a.nrounds = h->d_nrounds;
+        nl::FastArgs f;
+        memset(&f, 0, sizeof f);
+        f.record_only = 1;
+        NL_HIP(nl::launch_stack_sigma_mlz(a, f, h->stream, &ignored, p.mode == NL_ST_WINSOR_SIGMA));
+    }
+    return NL_OK;
+}
+
+static int run_mean(nl_stack *h, const PassSetup &p, PassFacts *)
+{
+    NL_HIP(nl::launch_stack_mean(p.weighted, p.a, h->stream, &h->last_kernel));
+    NL_HIP(hipEventRecord(h->ev_dom1, h->stream));
+    return NL_OK;
+}
+
+// bit-exact: a register-resident sorting network (pixels with many missing samples are handed from the pruned-network
+// kernel to the full-sort one) or, 129 ... 512 frames, 2 or 4 lanes per pixel
+static int run_median(nl_stack *h, const PassSetup &p, bool multi_lane)
+{
+    if (!multi_lane) {
+        NL_HIP(nl::launch_stack_median_fast(p.a, list_args(h, false, true), h->stream, &h->last_kernel, h->ev_dom1));
+    } else {
+        NL_HIP(nl::launch_stack_median_ml(p.a, h->stream, &h->last_kernel));
+        NL_HIP(hipEventRecord(h->ev_dom1, h->stream));
+    }
+    return NL_OK;
+}
+
+// MAD sigma / linear fit: register-resident, the exact kernel replays the pixels the dominant kernel lists
+static int run_listed(nl_stack *h, const PassSetup &p, PassFacts *facts)
+{
+    const nl::StackArgs &a = p.a;
+    if (p.mode == NL_ST_MAD_SIGMA) {
+        // counters exact (the bounds come from two medians); pixels with a non-finite median are replayed; 128 frames:
+        // pixels with too few samples for the selection kernel go to the generic list
+        const nl::FastArgs f = list_args(h, true, true);
+        if (a.n_frames <= 128) NL_HIP(nl::launch_stack_mad_fast(a, f, h->stream, &h->last_kernel));
+        else                   NL_HIP(nl::launch_stack_mad_ml(a, f, h->stream, &h->last_kernel));
+        NL_HIP(hipEventRecord(h->ev_dom1, h->stream));
+    } else {
+        // bit-exact (sums run in sorted order; 129 ... 512 frames: 2 or 4 lanes per pixel, the sums chained through the
+        // lanes); only pixels with an infinite sample are replayed
+        const nl::FastArgs f = list_args(h, true, false);
+        nl::LinfitCascade cascade;
+        const nl::LinfitCascade *cas = linfit_cascade(h, &cascade);
+        if (cas) NL_HIP(hipMemsetAsync(h->d_lf_count, 0, sizeof(unsigned) * nl::kLinfitCounters, h->stream));
+        if (nl::linfit_ml_supported(p.mode, a.n_frames, a.npix))
+            NL_HIP(nl::launch_stack_linfit_ml(a, f, cas, h->stream, &h->last_kernel, h->ev_dom1));
+        else
+            NL_HIP(nl::launch_stack_linfit_fast(a, f, cas, h->stream, &h->last_kernel, h->ev_dom1));
+    }
+    const int rc = replay_list(h, p.mode, p.weighted, a);
+    if (rc != NL_OK) return rc;
+    NL_HIP(nl::launch_reduce_counters(h->d_partial, nl::kClipSlots, h->d_counters, h->stream));
+    facts->has_counters = true;
+    facts->used_fast = true;
+    return NL_OK;
+}
+
+// Winsorized fast passes: how the generic pass and the winsorization loops are budgeted.  true: the winsorization cascade runs.
+static bool winsor_setup(nl_stack *h, int n_frames, nl::FastArgs &f)
+{
+    // winsorized generic passes and the stages of the cascade behind the dominant kernel: a wave runs for its slowest pixel,
+    // and the few pixels whose winsorization loops take dozens of rounds are cheaper in the replay (NL_GEN_ROUND_CAP: rounds per clipping pass; 100 = the limit of every kernel)
+    static const int cap_env = [] { const char *e = getenv("NL_GEN_ROUND_CAP"); return e ? atoi(e) : 0; }();
+    // (measured per frame count on the bench stack; 12 / 13 frames -- the smallest stacks with a zonal kernel -- lose with 40)
+    f.gen_round_cap = cap_env > 0 ? cap_env : (n_frames >= 48 ? 24 : (n_frames > 20 ? 32 : ((n_frames == 12 || n_frames == 13) ? 60 : 40)));
+    // the invariant-interval certificate of the winsorization loops (stack_fast_sigma_impl.hpp): first trial after
+    // cert_first rounds of a loop, then every cert_every; NL_WCERT="first,every" ("0" = off), developer switch kDevNoCertificate: off
+    // (3, 3: measured best at 16 frames and within 2 % of the best at 24, profiles/r05_winsor_cert.txt)
+    static const int cert_env[2] = {[] { const char *e = getenv("NL_WCERT"); return e ? atoi(e) : 3; }(),
+                                    [] { const char *e = getenv("NL_WCERT"); const char *c = e ? strchr(e, ',') : nullptr; const int v = c ? atoi(c + 1) : 3; return v > 0 ? v : 1; }()};
+    f.cert_first = (h->dev_flags & kDevNoCertificate) ? 0 : cert_env[0];
+    f.cert_every = cert_env[1];
+    // winsorized clipping of 16 ... 128 frames: the winsorization cascade (stack_fast_sigma_impl.hpp) -- the dominant
+    // kernel and a second stage stop at a budget of rounds per wave and hand their unfinished pixels on, a third
+    // stage finishes them.  Lists and states live in the buffers of the linear-fit cascade (same sizes, never in
+    // use at the same time); their lengths in the scratch set.  NL_WCAS="b1,b2" sets the budgets, "0" turns it off;
+    // developer switch kDevNoWinsorCascade: off (A/B inside one process)
+    if (n_frames > 128 || n_frames < 12 || (h->dev_flags & kDevNoWinsorCascade)) return false;
+    // plan: "passes:cap[:group]" per stage, comma-separated, the dominant kernel first; the last stage runs to the end
+    struct Plan { int stages; int pass[nl::kCascadeStages], cap[nl::kCascadeStages], group[nl::kCascadeStages]; };
+    auto parse = [](const char *e, Plan *pl) {
+        pl->stages = 0;
+        const char *p = e;
+        while (*p && pl->stages < nl::kCascadeStages) {
+            char *end = nullptr;
+            const long a1 = strtol(p, &end, 10);
+            if (end == p || *end != ':') break;
+            p = end + 1;
+            const long a2 = strtol(p, &end, 10);
+            if (end == p) break;
+            long a3 = 4;
+            if (*end == ':') { p = end + 1; a3 = strtol(p, &end, 10); if (end == p) break; }
+            pl->pass[pl->stages] = (int)a1;
+            pl->cap[pl->stages] = (int)a2;
+            pl->group[pl->stages] = a3 < 1 ? 1 : (a3 > 16 ? 16 : (int)a3);
+            pl->stages++;
+            if (*end != ',') break;
+            p = end + 1;
+        }
+    };
+    static const Plan env_plan = [&] { Plan p0{}; const char *e = getenv("NL_WCAS"); if (e) parse(e, &p0); return p0; }();
+    static const bool env_off = [] { const char *e = getenv("NL_WCAS"); return e && e[0] == '0' && e[1] == 0; }();
+    Plan pl{};
+    if (env_plan.stages >= 2) pl = env_plan;
+    else if (n_frames <= kWinsorCascadeMaxFrames) parse(n_frames <= 40 ? kWinsorPlanShallow : kWinsorPlanDeep, &pl);
+    nl::LinfitCascade cb;
+    // (a list holds at most one entry per pixel of the tile, rounded up to whole workgroups: list and states of a
+    // stage share one of the cascade's state arrays, 4 words per pixel; the region lengths take its pixel lists)
+    if (env_off || pl.stages < 2 || h->npix < 65536 || !linfit_cascade(h, &cb)) return false;
+    for (int i = 0; i < 2; i++) {
+        unsigned *base = reinterpret_cast<unsigned *>(cb.state[i]);
+        f.cas_list[i] = base;
+        f.cas_state[i] = base + 2 * (size_t)h->npix;
+        f.cas_count[i] = cb.list[i];
+    }
+    f.cas_stages = pl.stages;
+    for (int k = 0; k < pl.stages; k++) { f.cas_pass[k] = pl.pass[k]; f.cas_cap[k] = pl.cap[k]; f.cas_group[k] = pl.group[k]; }
+    return true;
+}
+
+// Sigma / winsorized clipping: a register-resident (up to 128 frames) or LDS-column (129 ... 512) dominant kernel, a generic
+// pass over the pixels it hands over, and the bit-exact replay of the pixels either cannot decide: one wave per pixel where
+// available.  The hand-overs of the dominant kernel are replayed on the side stream WHILE the generic pass runs (both only
+// depend on the dominant kernel); what the generic pass adds to the list is replayed after it.
+static int run_sigma_fast(nl_stack *h, const PassSetup &p, PassFacts *facts)
+{
+    const int mode = p.mode;
+    nl::StackArgs a = p.a;
+    // winsorized passes: the fast kernels put the thresholds of every round they decide on record, so that the
+    // replay of a pixel that turns undecidable later skips the winsorization loops of the decided rounds
+    // (from 129 frames on: C3 tile 5.28 -> 5.14 ms; at 128 frames most undecidable pixels are undecidable in
+    // their first round and the stores cost the dominant kernel 0.6 %)
+    if (mode == NL_ST_WINSOR_SIGMA && a.n_frames > 128 && fused_protocol_on() && ensure_bounds(h)) {
+        a.bounds = h->d_bounds;
+        a.nrounds = h->d_nrounds;
+    }
+    nl::FastArgs f = list_args(h, true, true);
+    f.fb_snap = h->d_fb_count + 2;                   // see the replay below
+    f.gen_hint = h->gen_hint;
+    const bool cascade = mode == NL_ST_WINSOR_SIGMA && winsor_setup(h, a.n_frames, f);
+    nl::StackArgs e = a;
+    e.list = h->d_fb_list;
+    e.list_count = h->d_fb_count;
+    e.list_capacity = (unsigned)h->npix;
+    const bool coop = nl::coop_supported(mode, p.weighted, a.n_frames) != 0;
+    unsigned *snap = h->d_fb_count + 2;               // 1 + list length when the first replay started (set on the device)
+    int grid0 = 0, grid1 = 0;
+    replay_grids(h, &grid0, &grid1);
+    struct Fork { nl_stack *h; nl::StackArgs e; int mode; unsigned *snap; int grid0; bool cascade; hipError_t err; } fork{h, e, mode, snap, grid0, cascade, hipSuccess};
+    nl::AfterDominant after = nullptr;
+    if (coop) after = [](void *u) {
+        Fork *k = static_cast<Fork *>(u);
+        nl_stack *hh = k->h;
+        const char *ignored = "";
+        // (ev_dom1: recorded behind the dominant kernel.  With a winsorization cascade two more kernels have filled the
+        // lists since: an event of its own)
+        const bool own = (hh->dev_flags & kDevUntimed) || k->cascade;
+        hipEvent_t fork_ev = own ? hh->ev_fork : hh->ev_dom1;
+        hipError_t err = own ? hipEventRecord(hh->ev_fork, hh->stream) : hipSuccess;
+        // (kDevReplayInFront: the first replay in front of the generic pass, same stream)
+        const bool in_front = (hh->dev_flags & kDevReplayInFront) != 0;
+        const hipStream_t s = in_front ? hh->stream : hh->side_stream;
+        if (!in_front && err == hipSuccess) err = hipStreamWaitEvent(hh->side_stream, fork_ev, 0);
+        nl::StackArgs first = k->e;
+        first.list_snap = k->snap;                    // the list as the dominant kernel left it (snapshot on the device)
+        first.list_part = 0;
+        if (err == hipSuccess) err = nl::launch_stack_sigma_coop(k->mode, first, k->grid0, s, &ignored);
+        if (err == hipSuccess) err = hipEventRecord(hh->ev_join, s);
+        k->err = err;
+    };
+    // Short exact lists (plain sigma, 65 ... 128 frames, fused protocol): generic pass and first replay as the lower and the
+    // upper workgroups of ONE launch (stack_tail_fused.hip) instead of two streams -- no fork, no join: the join alone costs
+    // a 512-row tile 14 us of its 257.  Every workgroup of that launch claims the generic pass's 48 KiB of LDS (three per
+    // CU), hence only while one wave per listed pixel fits the device at that rate.
+    // NL_TAIL_FUSED=0 / developer switch kDevTwoStreamTail: the two-stream protocol (A/B).
+    static const bool tail_fused_on = [] { const char *e = getenv("NL_TAIL_FUSED"); return !(e && e[0] == '0'); }();
+    const bool tail_fused = tail_fused_on && !(h->dev_flags & (kDevTwoStreamTail | kDevReplayInFront)) && p.fused && coop && !cascade &&
+                            nl::tail_fused_supported(mode, p.weighted, a.n_frames) != 0 && h->fb_hint != 0 &&
+                            h->fb_hint - 1u <= kTailFusedMaxList;
+    nl::StackArgs first_replay = e;
+    first_replay.list_snap = snap;                    // the list as the dominant kernel left it (snapshot on the device)
+    first_replay.list_part = 0;
+    unsigned replay_blocks = h->fb_hint + 31u;        // one wave per listed pixel and some: the list's length is last pass's
+    replay_blocks = replay_blocks < 64u ? 64u : replay_blocks > 768u ? 768u : replay_blocks;
+    if (tail_fused) after = nullptr;
+    if (a.n_frames <= 128)
+        NL_HIP(nl::launch_stack_sigma_fast(a, f, h->stream, &h->last_kernel, p.timed ? h->ev_dom1 : nullptr,
+                                           mode == NL_ST_WINSOR_SIGMA, after, &fork,
+                                           tail_fused ? &first_replay : nullptr, replay_blocks));
+    else   // 129..512 frames: 2 or 4 lanes per pixel
+        NL_HIP(nl::launch_stack_sigma_ml(a, f, h->stream, &h->last_kernel, p.timed ? h->ev_dom1 : nullptr,
+                                         mode == NL_ST_WINSOR_SIGMA, after, &fork));
+    NL_HIP(fork.err);
+    if (coop) {
+        const char *exact_name = "";
+        e.list_snap = snap;                           // the generic pass's additions
+        e.list_part = 1;
+        NL_HIP(nl::launch_stack_sigma_coop(mode, e, grid1, h->stream, &exact_name));
+        if (!tail_fused) NL_HIP(hipStreamWaitEvent(h->stream, h->ev_join, 0));
+    } else {
+        const int rc = replay_list(h, mode, p.weighted, a);
+        if (rc != NL_OK) return rc;
+    }
+    if (!p.fused) {              // (a fused pass implies coop: every kernel of the pass is enqueued)
+        // (the reduction zeroes the scratch set behind itself: no memset in front of the next pass)
+        NL_HIP(nl::launch_reduce_counters(h->d_partial, nl::kClipSlots, h->d_counters, h->stream, h->d_fb_count, true));
+        facts->zeroed_behind = true;
+    }
+    facts->has_counters = true;
+    facts->used_fast = true;
+    facts->lists = true;
+    facts->fused = p.fused;
+    facts->tail_fused = tail_fused;
+    return NL_OK;
+}
+
+// Bit-exact replay over the whole tile, 64 consecutive pixels per wave with their columns in LDS, one pixel per lane:
+// the default for weighted sigma / winsorized clipping (their result depends on the reference's permutation, so there
+// is no register-resident shortcut) up to kTileMaxFrames* frames -- the LDS column limits it to one wave per SIMD at
+// 128 frames, where the wave-per-pixel replay is faster (tools/replay_probe.py: 0.5 vs 1.5 ms per Mpixel at 32 frames,
+// 7.7 vs 3.8 at 128)
+static int run_weighted_tile(nl_stack *h, const PassSetup &p, PassFacts *facts)
+{
+    const int64_t tiles = (p.a.npix + 63) / 64;
+    const int64_t g = tiles < (1 << 20) ? tiles : (1 << 20);
+    NL_HIP(nl::launch_stack_sigma_tile(p.mode, p.a, (int)g, h->stream, &h->last_kernel));
+    NL_HIP(hipEventRecord(h->ev_dom1, h->stream));
+    NL_HIP(nl::launch_reduce_counters(h->d_partial, nl::kClipSlots, h->d_counters, h->stream));
+    facts->has_counters = true;
+    return NL_OK;
+}
+
+// The wave-per-pixel exact replay over the whole tile: the default for deeper weighted sigma / winsorized stacks (behind
+// their decision pass) and beyond 512 frames
+static int run_dense_replay(nl_stack *h, const PassSetup &p, PassFacts *facts)
+{
+    nl::StackArgs a = p.a;
+    const int rc = decision_pass(h, p, a);
+    if (rc != NL_OK) return rc;
+    const int per_item = p.mode == NL_ST_MEDIAN ? 1 : nl::coop_group(a);
+    // many short workgroups: neighbours that start together share the sectors they fetch, long-lived workgroups
+    // drift apart (128 frames x 4096^2, weighted sigma: 34.7 ms with 8 192 workgroups, 31.6 with 16 384, 28.0 with
+    // 65 536, 27.2 with 262 144; a 512-row tile of 64 frames: 2.50 / 2.26 / 2.07 / 2.08 ms)
+    const int64_t items = a.npix / per_item;
+    const int64_t most = 262144;
+    const int g = dense_grid(items, most, h->width, per_item);
+    if (p.mode == NL_ST_MEDIAN) NL_HIP(nl::launch_stack_median_coop(a, (int)g, h->stream, &h->last_kernel));
+    else                        NL_HIP(nl::launch_stack_sigma_coop(p.mode, a, (int)g, h->stream, &h->last_kernel));
+    NL_HIP(hipEventRecord(h->ev_dom1, h->stream));
+    NL_HIP(nl::launch_reduce_counters(h->d_partial, nl::kClipSlots, h->d_counters, h->stream));
+    facts->has_counters = p.mode != NL_ST_MEDIAN;
+    return NL_OK;
+}
+
+// one pixel per lane with its column in LDS: every mode at any depth (nl_stack_set_exact(h, 1), and what no other engine takes)
+static int run_exact_columns(nl_stack *h, const PassSetup &p, PassFacts *facts)
+{
+    nl::StackArgs a = p.a;
+    int lanes = 0;
+    size_t lds = 0;
+    if (nl::exact_plan(p.mode, p.weighted, a.n_frames, a.n_pad, 64, &lanes, &lds) != 0)
+        return fail(NL_ERR_TOO_MANY_FRAMES, "%d frames do not fit the per-pixel LDS column (mode %d)", a.n_frames, p.mode);
+    a.tiles = (a.npix + lanes - 1) / lanes;
+    const int grid = (int)(a.tiles < (int64_t)h->max_grid ? a.tiles : (int64_t)h->max_grid);
+    NL_HIP(nl::launch_stack_exact(p.mode, p.weighted, a, lanes, grid, lds, h->stream, &h->last_kernel));
+    NL_HIP(hipEventRecord(h->ev_dom1, h->stream));
+    NL_HIP(nl::launch_reduce_counters(h->d_partial, nl::kClipSlots, h->d_counters, h->stream));
+    facts->has_counters = p.mode != NL_ST_MEDIAN;
+    return NL_OK;
 }
 
 static int run_async_impl(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc);
@@ -1210,16 +1449,9 @@ int nl_stack_run_async(nl_stack_t *h, int mode, float sigma_low, float sigma_hig
         (void)hipSetDevice(h->device);
         (void)hipStreamSynchronize(h->stream);
         if (h->side_stream) (void)hipStreamSynchronize(h->side_stream);
-        for (int i = 0; i < 2; i++)
-            if (h->chunk_stream[i]) (void)hipStreamSynchronize(h->chunk_stream[i]);
         (void)hipGetLastError();
-        h->sets_clean = false;
+        set_last_pass(h, PassFacts{});
         h->partial_clean = false;
-        h->last_lists = false;
-        h->last_fused = false;
-        h->last_has_counters = false;
-        h->last_used_fast = false;
-        h->last_chunks = 0;
         h->pending = false;
         g_err = keep;
     }
@@ -1276,31 +1508,20 @@ static int run_async_impl(nl_stack_t *h, int mode, float sigma_low, float sigma_
         h->ev_start = h->ring_start[slot]; h->ev_stop = h->ring_stop[slot];
         h->ev_dom0 = h->ring_dom0[slot]; h->ev_dom1 = h->ring_dom1[slot];
     }
-    const bool timed = !(h->dev_flags & 32u);         // developer switch 32: a pass without its timing events
+    const bool timed = !(h->dev_flags & kDevUntimed);
     h->ring_timed[h->pass_seq % kTimingRing] = timed;
     if (timed) NL_HIP(hipEventRecord(h->ev_start, h->stream));
-    // The sigma / winsorized fast path from 17 frames on (a zonal kernel followed by a generic pass) runs the
-    // FUSED protocol (StackArgs::final): no memset in front of the pass -- the previous fused pass's dominant
-    // kernel zeroed this pass's scratch set, the two sets alternate -- and no reduction kernel behind it.
-    // NL_FUSED=0 (developer switch) keeps memset + reduce_counters_kernel for A/B runs.
-    static const bool fused_on = [] {
-        for (const char *name : {"NL_FUSED", "NL_MLG", "NL_MLZ"}) { const char *e = getenv(name); if (e && e[0] == '0') return false; }
-        return true;
-    }();
-    const bool sigma_fast = !h->force_exact && h->d_fb_list && (mode == NL_ST_SIGMA || mode == NL_ST_WINSOR_SIGMA) &&
-                            (nl::fast_supported(mode, weighted, a.n_frames, a.npix) ||
-                             nl::fast_ml_supported(mode, weighted, a.n_frames, a.npix));
+    const bool fused_on = fused_protocol_on();
+    const Engine engine = select_engine(h, mode, weighted, a);
+    const bool sigma_fast = engine == Engine::SigmaFast;
     // (only while the exact list is short -- the length the last finished pass reported: its replays add their
     // counts to ONE word, and thousands of workgroups doing that take longer than a reduction kernel)
-    if (sigma_fast && h->fb_hint == 0 && !(h->dev_flags & 512u)) {          // (developer switch 512: no hints from other handles)
+    if (sigma_fast && h->fb_hint == 0 && !(h->dev_flags & kDevNoSharedHints)) {
         unsigned fb = 0, gen = 0;
         if (hints_load({a.n_frames, a.npix, mode, weighted}, &fb, &gen)) { h->fb_hint = fb; h->gen_hint = gen; }
     }
     h->last_weighted = weighted;
-    ChunkPlan plan;
-    if (sigma_fast && a.n_frames > 16 && nl::coop_supported(mode, weighted, a.n_frames) != 0) chunk_plan(h, mode, weighted, a.n_frames, &plan);
-    const bool chunked = plan.n > 1;
-    const bool fused = fused_on && !chunked && !(h->dev_flags & 1u) && sigma_fast && a.n_frames > 8 && h->fb_hint != 0 &&
+    const bool fused = fused_on && !(h->dev_flags & kDevPlainProtocol) && sigma_fast && a.n_frames > 8 && h->fb_hint != 0 &&
                        h->fb_hint - 1u < kFusedMaxList && nl::coop_supported(mode, weighted, a.n_frames) != 0;
     // Every event recorded on the pass's stream costs a few microseconds of it (three of them: 17 us of a 277 us pass on
     // a 512-row tile, tools/wall_probe.py): a fused pass that finds its scratch set clean has nothing between "start" and
@@ -1320,506 +1541,27 @@ static int run_async_impl(nl_stack_t *h, int mode, float sigma_low, float sigma_
         NL_HIP(hipMemsetAsync(h->d_partial, 0, kScratchBytes, h->stream));
     }
     h->sets_clean = false;                       // until this pass is enqueued completely
-    bool zeroed_behind = false;
     const bool keep_clean = h->partial_clean && mode == NL_ST_MEAN;     // (a mean pass does not touch the scratch set)
     h->partial_clean = false;
     if (timed && !one_start) NL_HIP(hipEventRecord(h->ev_dom0, h->stream));
-    if (mode == NL_ST_MEAN) {
-        NL_HIP(nl::launch_stack_mean(weighted, a, h->stream, &h->last_kernel));
-        NL_HIP(hipEventRecord(h->ev_dom1, h->stream));
-        h->last_has_counters = false;
-    } else if (!h->force_exact && mode == NL_ST_MEDIAN && nl::fast_supported(mode, weighted, a.n_frames, a.npix)) {
-        // register-resident sorting network, bit-exact; pixels with many missing samples are
-        // handed from the pruned-network kernel to the full-sort one
-        nl::FastArgs f;
-        memset(&f, 0, sizeof f);
-        f.gen_list = h->d_gen_list;                 // nullptr for huge tiles: full sort everywhere
-        f.gen_count = h->d_fb_count + 1;
-        f.gen_capacity = (unsigned)h->npix;
-        NL_HIP(nl::launch_stack_median_fast(a, f, h->stream, &h->last_kernel, h->ev_dom1));
-        h->last_has_counters = false;
-        h->last_used_fast = false;
-    } else if (!h->force_exact && mode == NL_ST_MEDIAN && nl::fast_ml_supported(mode, weighted, a.n_frames, a.npix)) {
-        // 129..512 frames: 2 or 4 lanes per pixel, bit-exact
-        NL_HIP(nl::launch_stack_median_ml(a, h->stream, &h->last_kernel));
-        NL_HIP(hipEventRecord(h->ev_dom1, h->stream));
-        h->last_has_counters = false;
-        h->last_used_fast = false;
-    } else if (!h->force_exact && h->d_fb_list &&
-               (nl::mad_fast_supported(mode, weighted, a.n_frames, a.npix) ||
-                (mode == NL_ST_MAD_SIGMA && nl::fast_ml_supported(mode, weighted, a.n_frames, a.npix)))) {
-        // register-resident MAD clipping: counters exact (the bounds come from two medians);
-        // pixels with a non-finite median are replayed by the LDS kernel
-        nl::FastArgs f;
-        memset(&f, 0, sizeof f);
-        f.fb_list = h->d_fb_list;
-        f.fb_count = h->d_fb_count;
-        f.fb_capacity = (unsigned)h->npix;
-        f.gen_list = h->d_gen_list;                 // 128 frames: pixels with too few samples for the selection kernel
-        f.gen_count = h->d_fb_count + 1;
-        f.gen_capacity = (unsigned)h->npix;
-        if (a.n_frames <= 128) NL_HIP(nl::launch_stack_mad_fast(a, f, h->stream, &h->last_kernel));
-        else                   NL_HIP(nl::launch_stack_mad_ml(a, f, h->stream, &h->last_kernel));
-        NL_HIP(hipEventRecord(h->ev_dom1, h->stream));
-        {
-            int lanes = 0;
-            size_t lds = 0;
-            if (nl::exact_plan(mode, weighted, a.n_frames, a.n_pad, kListLanes, &lanes, &lds) != 0)
-                return fail(NL_ERR_TOO_MANY_FRAMES,
-                            "%d frames do not fit the per-pixel LDS column (mode %d)", a.n_frames, mode);
-            nl::StackArgs e = a;
-            e.list = h->d_fb_list;
-            e.list_count = h->d_fb_count;
-            e.list_capacity = (unsigned)h->npix;
-            const char *exact_name = "";
-            NL_HIP(nl::launch_stack_exact(mode, weighted, e, lanes, kListGrid, lds, h->stream, &exact_name));
-        }
-        NL_HIP(nl::launch_reduce_counters(h->d_partial, nl::kClipSlots, h->d_counters, h->stream));
-        h->last_has_counters = true;
-        h->last_used_fast = true;
-    } else if (!h->force_exact && h->d_fb_list && nl::linfit_ml_supported(mode, a.n_frames, a.npix)) {
-        // 129..512 frames: 2 or 4 lanes per pixel, the sums chained through the lanes; bit-exact
-        nl::FastArgs f;
-        memset(&f, 0, sizeof f);
-        f.fb_list = h->d_fb_list;
-        f.fb_count = h->d_fb_count;
-        f.fb_capacity = (unsigned)h->npix;
-        nl::LinfitCascade cascade;
-        const nl::LinfitCascade *cas = linfit_cascade(h, a.n_frames <= 256 ? 2 : 4, &cascade);
-        if (cas) NL_HIP(hipMemsetAsync(h->d_lf_count, 0, sizeof(unsigned) * nl::kLinfitCounters, h->stream));
-        NL_HIP(nl::launch_stack_linfit_ml(a, f, cas, h->stream, &h->last_kernel, h->ev_dom1));
-        int lanes = 0;
-        size_t lds = 0;
-        if (nl::exact_plan(mode, weighted, a.n_frames, a.n_pad, kListLanes, &lanes, &lds) != 0)
-            return fail(NL_ERR_TOO_MANY_FRAMES,
-                        "%d frames do not fit the per-pixel LDS column (mode %d)", a.n_frames, mode);
-        nl::StackArgs e = a;
-        e.list = h->d_fb_list;
-        e.list_count = h->d_fb_count;
-        e.list_capacity = (unsigned)h->npix;
-        const char *exact_name = "";
-        NL_HIP(nl::launch_stack_exact(mode, weighted, e, lanes, kListGrid, lds, h->stream, &exact_name));
-        NL_HIP(nl::launch_reduce_counters(h->d_partial, nl::kClipSlots, h->d_counters, h->stream));
-        h->last_has_counters = true;
-        h->last_used_fast = true;
-    } else if (!h->force_exact && h->d_fb_list && nl::linfit_fast_supported(mode, a.n_frames, a.npix)) {
-        // register-resident linear fit: bit-exact (sums run in sorted order);
-        // only pixels with an infinite sample are replayed by the LDS kernel
-        nl::FastArgs f;
-        memset(&f, 0, sizeof f);
-        f.fb_list = h->d_fb_list;
-        f.fb_count = h->d_fb_count;
-        f.fb_capacity = (unsigned)h->npix;
-#ifdef NL_EXPERIMENTS
-        // Guarded stages in front of the bit-exact cascade (stack_linfit_guard.hip; round 5): exact ymean, enclosed slope /
-        // sigma, undecidable pixels continue bit-exactly from their state.  Parity-green, decides 94 % of the pixels --
-        // and issues as many vector instructions as the cascade it replaces (8.32 against 8.37 * 10^9
-        // for the first stage, pass 18.9 against 17.0 ms): experiments build only, NL_LFG=1.
-        nl::LinfitGuardBufs gb;
-        if (nl::linfit_guard_supported(mode, a.n_frames, a.npix) && linfit_guard_bufs(h, &gb)) {
-            NL_HIP(hipMemsetAsync(h->d_lf_count, 0, sizeof(unsigned) * nl::kLinfitCounters, h->stream));
-            NL_HIP(nl::launch_stack_linfit_guarded(a, f, gb, h->stream, &h->last_kernel, h->ev_dom1));
-        } else
-#endif
-        {
-            nl::LinfitCascade cascade;
-            const nl::LinfitCascade *cas = linfit_cascade(h, 1, &cascade);
-            if (cas) NL_HIP(hipMemsetAsync(h->d_lf_count, 0, sizeof(unsigned) * nl::kLinfitCounters, h->stream));
-            NL_HIP(nl::launch_stack_linfit_fast(a, f, cas, h->stream, &h->last_kernel, h->ev_dom1));
-        }
-        int lanes = 0;
-        size_t lds = 0;
-        if (nl::exact_plan(mode, weighted, a.n_frames, a.n_pad, kListLanes, &lanes, &lds) != 0)
-            return fail(NL_ERR_TOO_MANY_FRAMES,
-                        "%d frames do not fit the per-pixel LDS column (mode %d)", a.n_frames, mode);
-        nl::StackArgs e = a;
-        e.list = h->d_fb_list;
-        e.list_count = h->d_fb_count;
-        e.list_capacity = (unsigned)h->npix;
-        const char *exact_name = "";
-        NL_HIP(nl::launch_stack_exact(mode, weighted, e, lanes, kListGrid, lds, h->stream, &exact_name));
-        NL_HIP(nl::launch_reduce_counters(h->d_partial, nl::kClipSlots, h->d_counters, h->stream));
-        h->last_has_counters = true;
-        h->last_used_fast = true;
-#ifdef NL_EXPERIMENTS
-    } else if (chunked) {
-        // the sigma / winsorized fast path as a chunked pass (see chunk_plan): plain protocol (the memset above,
-        // sharded clip counters, a reduction kernel at the end), one set of list lengths per chunk
-        int rc = ensure_chunk_resources(h);
-        if (rc != NL_OK) return rc;
-        NL_HIP(hipMemsetAsync(h->d_chunk_counts, 0, sizeof(unsigned) * 4 * kMaxChunks, h->stream));
-        const bool record = mode == NL_ST_WINSOR_SIGMA && a.n_frames > 128 && fused_on && ensure_bounds(h);     // (as the unchunked pass below)
-        static const bool coop4_env = [] { const char *e = getenv("NL_COOP4"); return e && e[0] == '1'; }();
-        const bool coop4 = coop4_env && NL_COOP4_SUPPORTED(mode, weighted, a.n_frames);
-        struct Fork { nl_stack *h; nl::StackArgs e; int mode; int grid0; bool coop4; hipEvent_t done; hipError_t err; };
-        for (int k = 0; k < plan.n; k++) {
-            const int64_t off = plan.off[k], len = plan.len[k];
-            const double share = (double)len / (double)h->npix;
-            nl::StackArgs ak = a;
-            ak.frames = a.frames + off;
-            ak.out = a.out + off;
-            ak.npix = len;
-            if (record) {
-                ak.bounds = h->d_bounds + (size_t)nl::kBoundRounds * (size_t)off;      // [round][pixel of the chunk]
-                ak.nrounds = h->d_nrounds + off;
-            }
-            unsigned *cc = h->d_chunk_counts + 4 * k;
-            nl::FastArgs f;
-            memset(&f, 0, sizeof f);
-            f.fb_list = h->d_fb_list + off;
-            f.fb_count = cc;
-            f.fb_capacity = (unsigned)len;
-            f.fb_snap = cc + 2;
-            f.gen_list = h->d_gen_list + off;
-            f.gen_count = cc + 1;
-            f.gen_capacity = (unsigned)len;
-            f.gen_hint = h->gen_hint ? (unsigned)((double)(h->gen_hint - 1u) * share * 1.25) + 1u : 0u;
-            if (!weighted) set_split_cols(h, mode, ak.n_frames, f);     // (chunks run one after the other on the pass's stream: one buffer)
-            if (mode == NL_ST_WINSOR_SIGMA) f.gen_round_cap = ak.n_frames >= 48 ? 24 : (ak.n_frames > 20 ? 32 : 40);
-            nl::StackArgs e = ak;
-            e.list = f.fb_list;
-            e.list_count = cc;
-            e.list_capacity = (unsigned)len;
-            int grid0 = kCoopGrid, grid1 = kCoopGrid / 4;
-            if (h->fb_hint) {
-                const int want = next_pow2((int)(2.0 * share * (double)(h->fb_hint - 1u)) + 64);
-                grid0 = want < 1024 ? 1024 : (want > kCoopGrid ? kCoopGrid : want);
-                grid1 = grid0 / 4 < 512 ? 512 : grid0 / 4;
-            }
-            if (coop4) { grid0 = (grid0 + 3) / 4; grid1 = (grid1 + 3) / 4; }
-            const bool last = k == plan.n - 1;
-            hipEvent_t done = (last && timed) ? h->ev_dom1 : h->ev_chunk[k];
-            Fork fork{h, e, mode, grid0, coop4, done, hipSuccess};
-            nl::AfterDominant after = [](void *u) {
-                // behind the chunk's dominant kernel: its hand-overs are replayed on one stream, the generic pass
-                // (launched by the caller of this callback) and the replay of what it adds run on the other
-                Fork *fk = static_cast<Fork *>(u);
-                nl_stack *hh = fk->h;
-                const char *ignored = "";
-                hipError_t err = hipStreamWaitEvent(hh->chunk_stream[1], fk->done, 0);
-                nl::StackArgs first = fk->e;
-                first.list_snap = const_cast<unsigned *>(fk->e.list_count) + 2;
-                first.list_part = 0;
-                if (err == hipSuccess) err = fk->coop4 ? NL_LAUNCH_COOP4(fk->mode, first, fk->grid0, hh->chunk_stream[1], &ignored)
-                                                       : nl::launch_stack_sigma_coop(fk->mode, first, fk->grid0, hh->chunk_stream[1], &ignored);
-                if (err == hipSuccess) err = hipStreamWaitEvent(hh->chunk_stream[0], fk->done, 0);
-                fk->err = err;
-            };
-            const char *name_k = "";
-            if (a.n_frames <= 128)
-                NL_HIP(nl::launch_stack_sigma_fast(ak, f, h->stream, &name_k, done, mode == NL_ST_WINSOR_SIGMA, after, &fork, h->chunk_stream[0]));
-            else
-                NL_HIP(nl::launch_stack_sigma_ml(ak, f, h->stream, &name_k, done, mode == NL_ST_WINSOR_SIGMA, after, &fork, h->chunk_stream[0]));
-            NL_HIP(fork.err);
-            if (k == 0) h->last_kernel = name_k;
-            const char *exact_name = "";
-            e.list_snap = cc + 2;                         // the generic pass's additions
-            e.list_part = 1;
-            if (coop4) NL_HIP(NL_LAUNCH_COOP4(mode, e, grid1, h->chunk_stream[0], &exact_name));
-            else       NL_HIP(nl::launch_stack_sigma_coop(mode, e, grid1, h->chunk_stream[0], &exact_name));
-        }
-        for (int i = 0; i < 2; i++) {
-            NL_HIP(hipEventRecord(h->ev_chunk_join[i], h->chunk_stream[i]));
-            NL_HIP(hipStreamWaitEvent(h->stream, h->ev_chunk_join[i], 0));
-        }
-        NL_HIP(nl::launch_reduce_counters(h->d_partial, nl::kClipSlots, h->d_counters, h->stream, h->d_chunk_counts, plan.n, 4));
-        h->last_lists = true;
-        h->last_fused = false;
-        h->last_has_counters = true;
-        h->last_used_fast = true;
-#endif  // NL_EXPERIMENTS
-    } else if (!h->force_exact && h->d_fb_list &&
-               (nl::fast_supported(mode, weighted, a.n_frames, a.npix) || nl::fast_ml_supported(mode, weighted, a.n_frames, a.npix))) {
-        // register-resident fast kernel; pixels it cannot decide go to the exact kernel
-        nl::FastArgs f;
-        memset(&f, 0, sizeof f);
-        // winsorized passes: the fast kernels put the thresholds of every round they decide on record, so that the
-        // replay of a pixel that turns undecidable later skips the winsorization loops of the decided rounds
-        // (not with the developer switches that bring back round-1 kernels, which write no round counts)
-        // (from 129 frames on: C3 tile 5.28 -> 5.14 ms; at 128 frames most undecidable pixels are undecidable in
-        // their first round and the stores cost the dominant kernel 0.6 %)
-        if (mode == NL_ST_WINSOR_SIGMA && a.n_frames > 128 && fused_on && ensure_bounds(h)) {
-            a.bounds = h->d_bounds;
-            a.nrounds = h->d_nrounds;
-        }
-        f.fb_list = h->d_fb_list;
-        f.fb_count = h->d_fb_count;
-        f.fb_capacity = (unsigned)h->npix;
-        f.fb_snap = h->d_fb_count + 2;               // see the replay below
-        f.gen_list = h->d_gen_list;
-        f.gen_count = h->d_fb_count + 1;
-        f.gen_capacity = (unsigned)h->npix;
-        f.gen_hint = h->gen_hint;
-        f.in_list = nullptr;
-        f.in_count = nullptr;
-        f.in_capacity = 0;
-        if (!weighted) set_split_cols(h, mode, a.n_frames, f);
-        // winsorized generic passes and the stages of the cascade behind the dominant kernel: a wave runs for its slowest pixel,
-        // and the few pixels whose winsorization loops take dozens of rounds are cheaper in the replay (NL_GEN_ROUND_CAP: rounds per clipping pass; 100 = the limit of every kernel)
-        if (mode == NL_ST_WINSOR_SIGMA) {
-            static const int cap_env = [] { const char *e = getenv("NL_GEN_ROUND_CAP"); return e ? atoi(e) : 0; }();
-            // (measured per frame count on the bench stack; 12 / 13 frames -- the smallest stacks with a zonal kernel -- lose with 40)
-            f.gen_round_cap = cap_env > 0 ? cap_env : (a.n_frames >= 48 ? 24 : (a.n_frames > 20 ? 32 : ((a.n_frames == 12 || a.n_frames == 13) ? 60 : 40)));
-        }
-        // the invariant-interval certificate of the winsorization loops (stack_fast_sigma_impl.hpp): first trial after
-        // cert_first rounds of a loop, then every cert_every; NL_WCERT="first,every" ("0" = off), developer switch 16384: off
-        // (3, 3: measured best at 16 frames and within 2 % of the best at 24, profiles/r05_winsor_cert.txt)
-        if (mode == NL_ST_WINSOR_SIGMA) {
-            static const int cert_env[2] = {[] { const char *e = getenv("NL_WCERT"); return e ? atoi(e) : 3; }(),
-                                            [] { const char *e = getenv("NL_WCERT"); const char *c = e ? strchr(e, ',') : nullptr; const int v = c ? atoi(c + 1) : 3; return v > 0 ? v : 1; }()};
-            f.cert_first = (h->dev_flags & 16384u) ? 0 : cert_env[0];
-            f.cert_every = cert_env[1];
-        }
-        // winsorized clipping of 16 ... 128 frames: the winsorization cascade (stack_fast_sigma_impl.hpp) -- the dominant
-        // kernel and a second stage stop at a budget of rounds per wave and hand their unfinished pixels on, a third
-        // stage finishes them.  Lists and states live in the buffers of the linear-fit cascade (same sizes, never in
-        // use at the same time); their lengths in the scratch set.  NL_WCAS="b1,b2" sets the budgets, "0" turns it off;
-        // developer switch 128: off (A/B inside one process)
-        bool cascade = false;
-        if (mode == NL_ST_WINSOR_SIGMA && a.n_frames <= 128 && a.n_frames >= 12 && !(h->dev_flags & 128u)) {
-            // plan: "passes:cap[:group]" per stage, comma-separated, the dominant kernel first; the last stage runs to the end
-            struct Plan { int stages; int pass[nl::kCascadeStages], cap[nl::kCascadeStages], group[nl::kCascadeStages]; };
-            auto parse = [](const char *e, Plan *pl) {
-                pl->stages = 0;
-                const char *p = e;
-                while (*p && pl->stages < nl::kCascadeStages) {
-                    char *end = nullptr;
-                    const long a1 = strtol(p, &end, 10);
-                    if (end == p || *end != ':') break;
-                    p = end + 1;
-                    const long a2 = strtol(p, &end, 10);
-                    if (end == p) break;
-                    long a3 = 4;
-                    if (*end == ':') { p = end + 1; a3 = strtol(p, &end, 10); if (end == p) break; }
-                    pl->pass[pl->stages] = (int)a1;
-                    pl->cap[pl->stages] = (int)a2;
-                    pl->group[pl->stages] = a3 < 1 ? 1 : (a3 > 16 ? 16 : (int)a3);
-                    pl->stages++;
-                    if (*end != ',') break;
-                    p = end + 1;
-                }
-            };
-            static const Plan env_plan = [&] { Plan p0{}; const char *e = getenv("NL_WCAS"); if (e) parse(e, &p0); return p0; }();
-            static const bool env_off = [] { const char *e = getenv("NL_WCAS"); return e && e[0] == '0' && e[1] == 0; }();
-            Plan pl{};
-            if (env_plan.stages >= 2) pl = env_plan;
-            else if (a.n_frames <= kWinsorCascadeMaxFrames) parse(a.n_frames <= 40 ? kWinsorPlanShallow : kWinsorPlanDeep, &pl);
-            nl::LinfitCascade cb;
-            // (a list holds at most one entry per pixel of the tile, rounded up to whole workgroups: list and states of a
-            // stage share one of the cascade's state arrays, 4 words per pixel; the region lengths take its pixel lists)
-            if (!env_off && pl.stages >= 2 && h->npix >= 65536 && linfit_cascade(h, 1, &cb)) {
-                cascade = true;
-                for (int i = 0; i < 2; i++) {
-                    unsigned *base = reinterpret_cast<unsigned *>(cb.state[i]);
-                    f.cas_list[i] = base;
-                    f.cas_state[i] = base + 2 * (size_t)h->npix;
-                    f.cas_count[i] = cb.list[i];
-                }
-                f.cas_stages = pl.stages;
-                for (int k = 0; k < pl.stages; k++) { f.cas_pass[k] = pl.pass[k]; f.cas_cap[k] = pl.cap[k]; f.cas_group[k] = pl.group[k]; }
-            }
-        }
-        // exact replay of the undecidable pixels: one wave per pixel where available.  The
-        // hand-overs of the dominant kernel are replayed on a side stream WHILE the generic
-        // pass runs (both only depend on the dominant kernel); what the generic pass adds
-        // to the list is replayed after it.
-        nl::StackArgs e = a;
-        e.list = h->d_fb_list;
-        e.list_count = h->d_fb_count;
-        e.list_capacity = (unsigned)h->npix;
-        const bool coop = nl::coop_supported(mode, weighted, a.n_frames) != 0;
-        unsigned *snap = h->d_fb_count + 2;               // 1 + list length when the first replay started (set on the device)
-        // replay grids: one wave per workgroup, grid-stride over a list whose length is only known on the device;
-        // launching 16 k workgroups for a few hundred pixels costs more than replaying them, so the length the
-        // last finished pass reported (nl_stack_finish) sizes the grid
-        int grid0 = kCoopGrid, grid1 = kCoopGrid / 4;
-        if (h->fb_hint) {
-            const int want = next_pow2((int)(2u * (h->fb_hint - 1u) + 64u));
-            grid0 = want < 1024 ? 1024 : (want > kCoopGrid ? kCoopGrid : want);      // (a 256-workgroup floor measured the same)
-            grid1 = grid0 / 4 < 512 ? 512 : grid0 / 4;
-        }
-        // NL_COOP4=1 (developer switch): replay the lists four pixels per wave (stack_exact_coop4.hip).  Its
-        // sequential sums cost a third of the instructions, but with a quarter of the waves in flight the replay
-        // turns latency-bound: C3 tile 5.32 -> 6.74 ms, sigma 512 tail 0.82 -> 1.45 ms -- measured, off by default
-        static const bool coop4_env = [] { const char *e = getenv("NL_COOP4"); return e && e[0] == '1'; }();
-        const bool coop4 = coop && coop4_env && NL_COOP4_SUPPORTED(mode, weighted, a.n_frames);
-        if (coop4) { grid0 = (grid0 + 3) / 4; grid1 = (grid1 + 3) / 4; }
-        struct Fork { nl_stack *h; nl::StackArgs e; int mode; unsigned *snap; int grid0; bool coop4; bool cascade; hipError_t err; } fork{h, e, mode, snap, grid0, coop4, cascade, hipSuccess};
-        nl::AfterDominant after = nullptr;
-        if (coop) after = [](void *u) {
-            Fork *k = static_cast<Fork *>(u);
-            nl_stack *hh = k->h;
-            const char *ignored = "";
-            // (ev_dom1: recorded behind the dominant kernel.  With a winsorization cascade two more kernels have filled the
-            // lists since: an event of its own)
-            const bool own = (hh->dev_flags & 32u) || k->cascade;
-            hipEvent_t fork_ev = own ? hh->ev_fork : hh->ev_dom1;
-            hipError_t err = own ? hipEventRecord(hh->ev_fork, hh->stream) : hipSuccess;
-            if (hh->dev_flags & 2u) {            // developer switch: the first replay in front of the generic pass, same stream
-                nl::StackArgs first = k->e;
-                first.list_snap = k->snap;
-                first.list_part = 0;
-                if (err == hipSuccess) err = k->coop4 ? NL_LAUNCH_COOP4(k->mode, first, k->grid0, hh->stream, &ignored)
-                                                      : nl::launch_stack_sigma_coop(k->mode, first, k->grid0, hh->stream, &ignored);
-                if (err == hipSuccess) err = hipEventRecord(hh->ev_join, hh->stream);
-                k->err = err;
-                return;
-            }
-            if (err == hipSuccess) err = hipStreamWaitEvent(hh->side_stream, fork_ev, 0);
-            nl::StackArgs first = k->e;
-            first.list_snap = k->snap;                    // the list as the dominant kernel left it (snapshot on the device)
-            first.list_part = 0;
-            if (err == hipSuccess) err = k->coop4 ? NL_LAUNCH_COOP4(k->mode, first, k->grid0, hh->side_stream, &ignored)
-                                                  : nl::launch_stack_sigma_coop(k->mode, first, k->grid0, hh->side_stream, &ignored);
-            if (err == hipSuccess) err = hipEventRecord(hh->ev_join, hh->side_stream);
-            k->err = err;
-        };
-        // Short exact lists (plain sigma, 65 ... 128 frames, fused protocol): generic pass and first replay as the lower and the
-        // upper workgroups of ONE launch (stack_tail_fused.hip) instead of two streams -- no fork, no join: the join alone costs
-        // a 512-row tile 14 us of its 257.  Every workgroup of that launch claims the generic pass's 48 KiB of LDS (three per
-        // CU), hence only while one wave per listed pixel fits the device at that rate.
-        // NL_TAIL_FUSED=0 / developer switch 8192: the two-stream protocol (A/B).
-        static const bool tail_fused_on = [] { const char *e = getenv("NL_TAIL_FUSED"); return !(e && e[0] == '0'); }();
-        const bool tail_fused = tail_fused_on && !(h->dev_flags & (8192u | 2u)) && fused && coop && !coop4 && !cascade &&
-                                nl::tail_fused_supported(mode, weighted, a.n_frames) != 0 && h->fb_hint != 0 &&
-                                h->fb_hint - 1u <= kTailFusedMaxList;
-        nl::StackArgs first_replay = e;
-        first_replay.list_snap = snap;                    // the list as the dominant kernel left it (snapshot on the device)
-        first_replay.list_part = 0;
-        unsigned replay_blocks = h->fb_hint + 31u;        // one wave per listed pixel and some: the list's length is last pass's
-        replay_blocks = replay_blocks < 64u ? 64u : replay_blocks > 768u ? 768u : replay_blocks;
-        if (tail_fused) after = nullptr;
-        if (a.n_frames <= 128)
-            NL_HIP(nl::launch_stack_sigma_fast(a, f, h->stream, &h->last_kernel, timed ? h->ev_dom1 : nullptr,
-                                               mode == NL_ST_WINSOR_SIGMA, after, &fork, nullptr,
-                                               tail_fused ? &first_replay : nullptr, replay_blocks));
-        else   // 129..512 frames: 2 or 4 lanes per pixel
-            NL_HIP(nl::launch_stack_sigma_ml(a, f, h->stream, &h->last_kernel, timed ? h->ev_dom1 : nullptr,
-                                             mode == NL_ST_WINSOR_SIGMA, after, &fork));
-        NL_HIP(fork.err);
-        const char *exact_name = "";
-        if (coop) {
-            e.list_snap = snap;                           // the generic pass's additions
-            e.list_part = 1;
-            if (coop4) NL_HIP(NL_LAUNCH_COOP4(mode, e, grid1, h->stream, &exact_name));
-            else       NL_HIP(nl::launch_stack_sigma_coop(mode, e, grid1, h->stream, &exact_name));
-            if (!tail_fused) NL_HIP(hipStreamWaitEvent(h->stream, h->ev_join, 0));
-        } else {
-            int lanes = 0;
-            size_t lds = 0;
-            if (nl::exact_plan(mode, weighted, a.n_frames, a.n_pad, kListLanes, &lanes, &lds) != 0)
-                return fail(NL_ERR_TOO_MANY_FRAMES,
-                            "%d frames do not fit the per-pixel LDS column (mode %d)", a.n_frames, mode);
-            NL_HIP(nl::launch_stack_exact(mode, weighted, e, lanes, kListGrid, lds, h->stream, &exact_name));
-        }
-        if (fused) h->sets_clean = true;             // (fused implies coop: every kernel of the pass is enqueued)
-        else {
-            // (the reduction zeroes the scratch set behind itself: no memset in front of the next pass)
-            NL_HIP(nl::launch_reduce_counters(h->d_partial, nl::kClipSlots, h->d_counters, h->stream, h->d_fb_count, 1, 0, true));
-            zeroed_behind = true;
-        }
-        h->last_lists = true;
-        h->last_fused = fused;
-        h->last_tail_fused = tail_fused;
-        h->last_has_counters = true;
-        h->last_used_fast = true;
-    } else if ((h->exact_flavour == 3 ||
-                (!h->force_exact && weighted && !(h->dev_flags & 16u) &&
-                 a.n_frames <= (mode == NL_ST_WINSOR_SIGMA ? nl::kTileMaxFramesWinsor : nl::kTileMaxFramesSigma))) &&
-               nl::tile_supported(mode, weighted, a.n_frames)) {
-        // bit-exact replay over the whole tile, 64 consecutive pixels per wave with their columns in
-        // LDS, one pixel per lane: the default for weighted sigma / winsorized clipping (their result
-        // depends on the reference's permutation, so there is no register-resident shortcut) up to
-        // 64 frames -- the LDS column limits it to one wave per SIMD at 128 frames, where the
-        // wave-per-pixel replay below is faster (tools/replay_probe.py: 0.5 vs 1.5 ms per Mpixel at
-        // 32 frames, 7.7 vs 3.8 at 128); nl_stack_set_exact(h, 3) forces it (verification)
-        h->last_used_fast = false;
-        const int64_t tiles = (a.npix + 63) / 64;
-        const int64_t g = tiles < (1 << 20) ? tiles : (1 << 20);
-        NL_HIP(nl::launch_stack_sigma_tile(mode, a, (int)g, h->stream, &h->last_kernel));
-        NL_HIP(hipEventRecord(h->ev_dom1, h->stream));
-        NL_HIP(nl::launch_reduce_counters(h->d_partial, nl::kClipSlots, h->d_counters, h->stream));
-        h->last_has_counters = true;
-    } else if (NL_COOP4_SUPPORTED(mode, weighted, a.n_frames) &&           // (experiments build only)
-               (h->exact_flavour == 4 ||
-                (!h->force_exact && weighted && !(h->dev_flags & 8u) && mode == NL_ST_WINSOR_SIGMA &&
-                 a.n_frames >= nl::kCoop4MinFrames && a.n_frames <= nl::kCoop4MaxFrames &&
-                 !(nl::decide_ml_supported(mode, a.n_frames, a.npix) && ensure_bounds(h))))) {      // (only without a decision pass)
-        // the four-pixels-per-wave replay over the whole tile: weighted stacks of medium depth (the sequential sums
-        // are a large share of a dense replay, and a row of 16 lanes wastes fewer of them on short ranges);
-        // nl_stack_set_exact(h, 4) forces it (verification)
-        h->last_used_fast = false;
-        if (weighted && h->exact_flavour == 0 && nl::decide_supported(mode, a.n_frames, a.npix) && ensure_bounds(h)) {
-            // decision pass: the register-resident kernel leaves the clip bounds of every round it can decide
-            a.bounds = h->d_bounds;
-            a.nrounds = h->d_nrounds;
-            const char *ignored = "";
-            NL_HIP(nl::launch_stack_sigma_decide(a, h->stream, mode == NL_ST_WINSOR_SIGMA, &ignored));
-        }
-        const int g = dense_grid((a.npix + 3) / 4, 65536, h->width, 4);
-        (void)g;
-        NL_HIP(NL_LAUNCH_COOP4(mode, a, (int)g, h->stream, &h->last_kernel));
-        NL_HIP(hipEventRecord(h->ev_dom1, h->stream));
-        NL_HIP(nl::launch_reduce_counters(h->d_partial, nl::kClipSlots, h->d_counters, h->stream));
-        h->last_has_counters = true;
-    } else if ((h->exact_flavour == 2 || (!h->force_exact && (weighted || a.n_frames > 512))) &&
-               nl::coop_supported(mode, weighted, a.n_frames)) {
-        // the wave-per-pixel exact replay over the whole tile: the default for weighted sigma /
-        // winsorized clipping (their result depends on the reference's permutation, so there is
-        // no register-resident shortcut) and beyond 512 frames; with nl_stack_set_exact(h, 2) a
-        // verification path
-        h->last_used_fast = false;
-        if (weighted && h->exact_flavour == 0 && mode != NL_ST_MEDIAN && nl::decide_supported(mode, a.n_frames, a.npix) &&
-            ensure_bounds(h)) {
-            a.bounds = h->d_bounds;                    // decision pass, see the four-pixels-per-wave branch above
-            a.nrounds = h->d_nrounds;
-            const char *ignored = "";
-            NL_HIP(nl::launch_stack_sigma_decide(a, h->stream, mode == NL_ST_WINSOR_SIGMA, &ignored));
-        } else if (weighted && h->exact_flavour == 0 && mode != NL_ST_MEDIAN && nl::decide_ml_supported(mode, a.n_frames, a.npix) &&
-                   ensure_bounds(h)) {
-            // 129 ... 512 frames: the LDS-column kernel of the frame-count class decides (FastArgs::record_only: no
-            // outputs, lists or counters; a pixel it would hand to the generic pass has no round on record)
-            a.bounds = h->d_bounds;
-            a.nrounds = h->d_nrounds;
-            nl::FastArgs f;
-            memset(&f, 0, sizeof f);
-            f.record_only = 1;
-            set_split_cols(h, mode, a.n_frames, f);
-            const char *ignored = "";
-            NL_HIP(nl::launch_stack_sigma_mlz(a, f, h->stream, &ignored, mode == NL_ST_WINSOR_SIGMA));
-        }
-        const int per_item = mode == NL_ST_MEDIAN ? 1 : nl::coop_group(a);
-        // many short workgroups: neighbours that start together share the sectors they fetch, long-lived workgroups
-        // drift apart (128 frames x 4096^2, weighted sigma: 34.7 ms with 8 192 workgroups, 31.6 with 16 384, 28.0 with
-        // 65 536, 27.2 with 262 144; a 512-row tile of 64 frames: 2.50 / 2.26 / 2.07 / 2.08 ms)
-        const int64_t items = a.npix / per_item;
-        const int64_t most = 262144;
-        const int g = dense_grid(items, most, h->width, per_item);
-        if (mode == NL_ST_MEDIAN) NL_HIP(nl::launch_stack_median_coop(a, (int)g, h->stream, &h->last_kernel));
-        else                      NL_HIP(nl::launch_stack_sigma_coop(mode, a, (int)g, h->stream, &h->last_kernel));
-        NL_HIP(hipEventRecord(h->ev_dom1, h->stream));
-        NL_HIP(nl::launch_reduce_counters(h->d_partial, nl::kClipSlots, h->d_counters, h->stream));
-        h->last_has_counters = (mode != NL_ST_MEDIAN);
-    } else {
-        h->last_used_fast = false;
-        int lanes = 0;
-        size_t lds = 0;
-        if (nl::exact_plan(mode, weighted, a.n_frames, a.n_pad, 64, &lanes, &lds) != 0)
-            return fail(NL_ERR_TOO_MANY_FRAMES,
-                        "%d frames do not fit the per-pixel LDS column (mode %d)", a.n_frames, mode);
-        a.tiles = (a.npix + lanes - 1) / lanes;
-        int grid = (int)(a.tiles < (int64_t)h->max_grid ? a.tiles : (int64_t)h->max_grid);
-        NL_HIP(nl::launch_stack_exact(mode, weighted, a, lanes, grid, lds, h->stream, &h->last_kernel));
-        NL_HIP(hipEventRecord(h->ev_dom1, h->stream));
-        NL_HIP(nl::launch_reduce_counters(h->d_partial, nl::kClipSlots, h->d_counters, h->stream));
-        h->last_has_counters = (mode != NL_ST_MEDIAN);
+
+    const PassSetup p{mode, weighted, timed, fused, a};
+    PassFacts facts;
+    int rc = NL_OK;
+    switch (engine) {
+    case Engine::Mean:            rc = run_mean(h, p, &facts); break;
+    case Engine::MedianRegisters: rc = run_median(h, p, false); break;
+    case Engine::MedianMultiLane: rc = run_median(h, p, true); break;
+    case Engine::Listed:          rc = run_listed(h, p, &facts); break;
+    case Engine::SigmaFast:       rc = run_sigma_fast(h, p, &facts); break;
+    case Engine::WeightedTile:    rc = run_weighted_tile(h, p, &facts); break;
+    case Engine::DenseReplay:     rc = run_dense_replay(h, p, &facts); break;
+    case Engine::ExactColumns:    rc = run_exact_columns(h, p, &facts); break;
     }
+    if (rc != NL_OK) return rc;
     NL_HIP(hipEventRecord(h->ev_stop, h->stream));
-    h->partial_clean = zeroed_behind || keep_clean;
-    if (!fused) h->last_fused = false;
-    if (!fused || !sigma_fast) h->last_tail_fused = false;
-    if (!sigma_fast) h->last_lists = false;
-    h->last_chunks = chunked ? plan.n : 0;
+    set_last_pass(h, facts);
+    h->partial_clean = facts.zeroed_behind || keep_clean;
     h->pass_seq++;
     h->last_mode = mode;
     h->pending = true;
@@ -1870,12 +1612,10 @@ int nl_stack_set_exact(nl_stack_t *h, int on)
 {
     NL_CHECK_HANDLE(h);
     if (on < 0 || on > 4) return fail(NL_ERR_INVALID_ARG, "set_exact: unknown flavour %d (0 ... 4)", on);
-#ifndef NL_EXPERIMENTS
-    // (a switch this build does not carry must not fall through to another kernel silently: an A/B run would time the same
+    // (a switch whose code was removed must not fall through to another kernel silently: an A/B run would time the same
     // kernel twice)
     if (on == 4)
-        return fail(NL_ERR_INVALID_ARG, "set_exact: flavour 4 (four pixels per wave) is in the experiments build only (make EXPERIMENTS=1)");
-#endif
+        return fail(NL_ERR_INVALID_ARG, "set_exact: flavour 4 (four pixels per wave) was removed with the experiments build");
     h->force_exact = on != 0;
     h->exact_flavour = on;
     return NL_OK;
@@ -1884,11 +1624,9 @@ int nl_stack_set_exact(nl_stack_t *h, int on)
 int nl_stack_set_dev_flags(nl_stack_t *h, unsigned flags)
 {
     NL_CHECK_HANDLE(h);
-#ifndef NL_EXPERIMENTS
-    if (flags & (1024u | 2048u))
-        return fail(NL_ERR_INVALID_ARG, "set_dev_flags: switches 1024 / 2048 (split / persistent LDS-column pass) are in the experiments "
-                                        "build only (make EXPERIMENTS=1)");
-#endif
+    if (flags & kDevRemovedPasses)
+        return fail(NL_ERR_INVALID_ARG, "set_dev_flags: switches 1024 / 2048 (split / persistent LDS-column pass) were removed with the "
+                                        "experiments build");
     h->dev_flags = flags;
     return NL_OK;
 }
@@ -1919,7 +1657,7 @@ int64_t nl_stack_last_fallback_pixels(nl_stack_t *h)
 int nl_stack_last_pass_protocol(nl_stack_t *h)
 {
     if (!h) return 0;
-    return (h->last_fused ? 1 : 0) | (h->last_tail_fused ? 2 : 0) | (h->last_chunks > 0 ? 4 : 0);
+    return (h->last_fused ? 1 : 0) | (h->last_tail_fused ? 2 : 0);
 }
 
 int64_t nl_stack_last_generic_pixels(nl_stack_t *h)

@@ -501,10 +501,10 @@ hipError_t launch_stack_exact(int mode, bool weighted, StackArgs &args, int lane
 
 hipError_t launch_reduce_counters(unsigned long long *partial, int n_blocks,
                                   unsigned long long *counters, hipStream_t stream, const unsigned *list_counts,
-                                  int n_lists, int list_stride, bool zero_after)
+                                  bool zero_after)
 {
     hipLaunchKernelGGL(reduce_counters_kernel, dim3(1), dim3(256), 0, stream, partial, n_blocks,
-                       counters, list_counts, n_lists, list_stride, zero_after ? 1 : 0);
+                       counters, list_counts, 1, 0, zero_after ? 1 : 0);
     return hipGetLastError();
 }
 

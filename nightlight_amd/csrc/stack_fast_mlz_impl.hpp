@@ -128,35 +128,14 @@ struct MlzLayout {
     static_assert(!SELECT || (KL <= KE && KH == KE && TOPW <= 14 && BOTW <= 10 && PADS < KE), "selection sizes");
 };
 
-// The split pass of the SELECT class: which LDS rows travel from the sorting kernel to the rounds kernel (FastArgs::cols:
-// one block of N rows x 64 pixels per workgroup, contiguous): the low column's KL ranks, the high column, the per-pixel scalars, the median window.
-template <class L>
-struct MlzSplit {
-    static constexpr int N = L::KL + L::KH + 8 + L::MW;
-    static constexpr int row(int g)
-    {
-        return g < L::KL ? L::XL + g : (g < L::KL + L::KH ? L::XH + (g - L::KL) : (g < L::KL + L::KH + 8 ? L::PS + (g - L::KL - L::KH) : L::XW + (g - L::KL - L::KH - 8)));
-    }
-    __device__ static __forceinline__ int row_rt(int g) { return row(g); }
-};
-
 // Where the rounds phase finds its rows.  MlzRows: the layout above, tables beside the columns (`tab` = `col`).
-// MlzRowsPersistent (PHASE 3, the SELECT class): a compact buffer per block -- the KL / KH ranks of the columns the rounds
-// read, the median window, the scalars and one TRASH row for what the selection stores beyond them (ranks KL .. KE-1 of the
-// low end, the spare window slots) -- of which a workgroup holds TWO, and one table area shared by its rounds.
 template <class L>
 struct MlzRows {
     static constexpr int XL = L::XL, XH = L::XH, XW = L::XW, PS = L::PS, SL1 = L::SL1, SL2 = L::SL2, SH1 = L::SH1, SH2 = L::SH2;
-    static constexpr int TRASH = -1, ROWS = L::ROWS, TROWS = 0;
+    // TRASH: the row a compact layout would take the spare stores of the selection into (none here).  The two discarded
+    // branches that use it stay: without them the compiler schedules the selected class's kernel differently.
+    static constexpr int TRASH = -1, ROWS = L::ROWS;
 };
-template <class L>
-struct MlzRowsPersistent {
-    // (TRASH: the seventh scalar row -- only the winsorized kernels have a seventh scalar.  LDS is handed out in granules
-    // of 1 280 bytes: with one more row per buffer a workgroup took 43 instead of 42 of them and a CU held two workgroups, not three)
-    static constexpr int XL = 0, XH = XL + L::KL, XW = XH + L::KH, PS = XW + L::MW, TRASH = PS + 6, ROWS = PS + 8;
-    static constexpr int SL1 = 0, SL2 = SL1 + L::GL, SH1 = SL2 + L::GL, SH2 = SH1 + L::GH, TROWS = SH2 + L::GH;
-};
-
 // ---- DPP minima / maxima: "mine" against the partner lane's "theirs" in ONE instruction ----
 // (inline asm: the compiler's hazard recognizer does not look inside -- a VALU write of a register needs two
 // wait states before a DPP read of it.  Every stage below starts with dpp_stage_begin() and only reads, through
@@ -371,36 +350,19 @@ __device__ __forceinline__ void lds_settle() { asm volatile("s_waitcnt lgkmcnt(0
 #ifndef NL_MLZ_WINSOR_WAVES
 #define NL_MLZ_WINSOR_WAVES 2
 #endif
-// PHASE (the SELECT class only, see MlzSplit below): 0 = the whole pass in one kernel; 1 = the sorting phase, whose
-// columns go to FastArgs::cols instead of staying in LDS; 2 = the rounds phase over those columns, one wave per workgroup.
-// PHASE 3: a wave waits for a flag of its workgroup.  (In practice the flag is long set; a wait that never ends -- a bug --
-// traps instead of hanging the device.)
-__device__ __forceinline__ void mlz_spin_until(unsigned *flag, unsigned target)
-{
-    for (int i = 0; i < (1 << 22); i++) {
-        if (__hip_atomic_load(flag, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) >= target) return;
-        __builtin_amdgcn_s_sleep(2);
-    }
-    __builtin_trap();
-}
-
+// (PHASE is always 0: the rocprofv3 name stack_sigma_mlz_kernel<L, W, N, 0> keys the measured traffic of profiles/r0*_traffic.json in bench.py)
 template <int LPP, bool WINSOR, int NTOP, int PHASE = 0>
-__global__ __launch_bounds__(PHASE == 2 ? 64 : mlz_block<LPP>)
-__attribute__((amdgpu_waves_per_eu(PHASE == 2 ? 1 : (WINSOR ? NL_MLZ_WINSOR_WAVES : 3), 8)))
+__global__ __launch_bounds__(mlz_block<LPP>)
+__attribute__((amdgpu_waves_per_eu(WINSOR ? NL_MLZ_WINSOR_WAVES : 3, 8)))
 void stack_sigma_mlz_kernel(StackArgs p, FastArgs q)
 {
+    static_assert(PHASE == 0, "one kernel per pass");
     using L = MlzLayout<LPP, WINSOR, NTOP>;
-    using SP = MlzSplit<L>;
-    using V = std::conditional_t<PHASE == 3, MlzRowsPersistent<L>, MlzRows<L>>;
-    static_assert(PHASE == 0 || (L::SELECT && L::PACK && L::PW == 64), "the split and the persistent pass exist for the SELECT class");
-    static_assert(PHASE != 3 || (!WINSOR && (2 * V::ROWS + V::TROWS) * L::PW * 4 + 64 <= 42 * 1280), "persistent pass: three workgroups per CU");
+    using V = MlzRows<L>;
     constexpr int NS = L::NS, PW = L::PW, KL = L::KL, KH = L::KH, CR = L::CR, H0 = L::H0, W0 = L::W0;
-    // (PHASE 3: two column buffers and one table area)
-    __shared__ float lds[(PHASE == 3 ? 2 * V::ROWS + V::TROWS : L::ROWS) * PW];
-    __shared__ unsigned s_done[2], s_freed[2];             // PHASE 3: waves that wrote / rounds that finished, per buffer
-    __shared__ unsigned s_blk[4], s_seq;                   // PHASE 3: the workgroup's block of trip k (slot k & 3), trips published
+    __shared__ float lds[L::ROWS * PW];
     __shared__ int s_lo[4], s_hi[4];                       // (kernels whose rounds run in every wave: their clip counts)
-    if constexpr (PHASE != 2) fused_prologue_dominant(p);
+    fused_prologue_dominant(p);
 
     // Two phases.  SORTING: LPP lanes per pixel, every wave of the workgroup -- gather, in-lane sort, merge / selection,
     // columns + median window + the moments between the columns to LDS.  ROUNDS: ONE lane per pixel, i.e. one wave for
@@ -409,25 +371,14 @@ void stack_sigma_mlz_kernel(StackArgs p, FastArgs q)
     // LDS reads at data-dependent rows plus scalar-like arithmetic, nothing the lanes of a pixel could share out);
     // a fifth (sigma) to a half (winsorized) of the kernel's instructions were those.  The wave that stays is picked
     // by the workgroup index so that a CU's SIMDs share the rounds evenly.
-    const int lane = threadIdx.x & 63;
-    // ---- sorting phase of block `blk` (PW pixels); its rows go to `colbase`; `before_store` runs in front of the first store ----
-    auto sorting_phase = [&](const int64_t blk, float *const colbase, auto &&before_store) NL_INL {
-    // (PHASE 3 runs this in a loop: everything derived from the thread index would be hoisted out of it -- some thirty
-    // registers, i.e. spills to scratch and their reloads on the waves' critical path (measured: 17.9 instead of 10.1 ms) --
-    // so the index goes through an opaque register per trip and the few shifts and masks are redone)
+    // ---- sorting phase of block `blk` (PW pixels); its rows go to `colbase` ----
+    auto sorting_phase = [&](const int64_t blk, float *const colbase) NL_INL {
     int tid = (int)threadIdx.x;
-    if constexpr (PHASE == 3) asm volatile("" : "+v"(tid));
     const int role = tid % LPP;
     float *col = colbase + tid / LPP;                      // element r of this pixel: col[r * PW]
     const int64_t pix = blk * PW + tid / LPP;
-    // (PHASE 3: the wait for the buffer -- over long before -- stands HERE, not in front of the first store: a loop in the
-    // middle of the sorting phase cuts its one basic block in two and cost 14 more spilled registers)
-    if constexpr (L::SELECT) before_store();
     const bool on = pix < p.npix;
     int N = p.n_frames;
-    // (PHASE 3 calls this in a loop: re-read through an opaque register, or the per-frame scalar selects that depend on the
-    // frame count are hoisted out of the loop and spilled)
-    if constexpr (PHASE == 3) asm volatile("" : "+s"(N));
     float v[NS];
     // a stack that fills its lanes: the last merge orders the 32 lowest / highest ranks of every lane
     // (columns of the plain sigma kernel, median window); the winsorized columns are longer, and the
@@ -503,7 +454,6 @@ void stack_sigma_mlz_kernel(StackArgs p, FastArgs q)
         }
         select_window<L, LPP, NS, V>(v, role, col, window_ok);
     } else {
-    before_store();
     static_range<0, KL>([&](auto K) NL_INL {
         constexpr int k = decltype(K)::value;
         col[(V::XL + k) * PW] = bcast_f(std::integral_constant<int, 0>{}, v[k]);
@@ -574,7 +524,6 @@ void stack_sigma_mlz_kernel(StackArgs p, FastArgs q)
     auto rounds_phase = [&](const int64_t blk, float *const colbase, float *const tabbase) NL_INL {
     int c_lo_total = 0, c_hi_total = 0;
     int tid = (int)threadIdx.x;
-    if constexpr (PHASE == 3) asm volatile("" : "+v"(tid));        // (see the sorting phase)
     const int lane = tid & 63;
 #if defined(NL_ROUND_STATS) && defined(NL_MLZ_EXP_TIMING)
     const unsigned long long exp_t0 = __builtin_readcyclecounter();      // (timing experiment: cycles of the rounds phase)
@@ -941,107 +890,8 @@ void stack_sigma_mlz_kernel(StackArgs p, FastArgs q)
     }
     };   // ---- end of the rounds phase ----
 
-    if constexpr (PHASE == 3) {
-        // ---- persistent workgroups: block k of this workgroup is blockIdx.x + k * gridDim.x.  No barrier: wave (k mod 4)
-        // runs the rounds of block k AFTER it has sorted its share of block k + 1 -- by then the other waves' rows of
-        // block k have long been there, and its own lag (one rounds phase in four blocks, every wave in turn) never makes
-        // another wave wait: nobody idles, nobody retires.  Two column buffers (a block's rows are overwritten two blocks
-        // later, when its rounds are long over); the flags below only make that certain.
-        // Blocks are handed out in order through a device counter (FastArgs::ticket): with a fixed stride per workgroup the
-        // workgroups drift apart over hundreds of trips and the 512 frames are read at ever more scattered places.
-        if (threadIdx.x < 2) { s_done[threadIdx.x] = 0u; s_freed[threadIdx.x] = 0u; }
-        if (threadIdx.x == 0) { s_blk[0] = atomicAdd(q.ticket, 1u); s_seq = 1u; }
-        __syncthreads();
-        // All workgroups start together and every block takes the same time: without a stagger the three waves of a SIMD
-        // would gather at the same time and sort at the same time for the whole launch -- nothing to hide the loads behind.
-        // The k-th third of the grid (the dispatcher fills the CUs once per third) starts a third of a block's time later.
-        {
-            // (HW_ID[3:0]: the wave's slot on its SIMD)
-            const int third = (int)((__builtin_amdgcn_s_getreg(63492) & 15u) % 3u);
-            for (int i = 0; i < NL_MLZ_STAGGER * third; i++) __builtin_amdgcn_s_sleep(127);
-        }
-        // (a real call: inlined, the rounds phase's loop invariants -- lane masks, addresses, constants -- are kept in registers
-        // across the sorting phase of every trip, which has none to spare: 55 spilled registers instead of 4, their reloads
-        // on the waves' critical path)
-        auto rounds_call = [&](const int64_t rblk, float *const rcol, float *const rtab) NL_INL {
-            rounds_phase(rblk, rcol, rtab);
-        };
-        const int wave = (int)(threadIdx.x >> 6);
-        const int64_t nblk = (p.npix + PW - 1) / PW;
-        float *const tabbase = lds + 2 * V::ROWS * PW;
-        int64_t prev_blk = 0;
-        for (int k = 0;; k++) {
-            mlz_spin_until(&s_seq, (unsigned)k + 1u);      // (wave 0 published this trip's block while sorting the last one)
-            const int64_t blk = (int64_t)__builtin_amdgcn_readfirstlane((int)s_blk[k & 3]);
-            const bool has = blk < nblk;                   // (the same for every wave of the workgroup)
-            unsigned next_ticket = 0u;
-            if (has && threadIdx.x == 0) next_ticket = atomicAdd(q.ticket, 1u);     // (returns behind the gather's loads)
-#if defined(NL_ROUND_STATS) && defined(NL_MLZ_EXP_TIMING)
-            const unsigned long long tt0 = __builtin_readcyclecounter();
-#endif
-            if (has) {
-                float *const buf = lds + (k & 1) * (V::ROWS * PW);
-                sorting_phase(blk, buf, [&]() NL_INL {
-#if defined(NL_ROUND_STATS) && defined(NL_MLZ_EXP_TIMING)
-                    const unsigned long long ts0 = __builtin_readcyclecounter();
-#endif
-                    if (k >= 2) mlz_spin_until(&s_freed[k & 1], (unsigned)(k >> 1));      // rounds of block k - 2 are over
-#if defined(NL_ROUND_STATS) && defined(NL_MLZ_EXP_TIMING)
-                    if (threadIdx.x == 0) NL_STAT(3, __builtin_readcyclecounter() - ts0);
-#endif
-                });
-                lds_settle();
-                if (lane == 0) __hip_atomic_fetch_add(&s_done[k & 1], 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-                if (threadIdx.x == 0) {
-                    s_blk[(k + 1) & 3] = next_ticket;
-                    __hip_atomic_store(&s_seq, (unsigned)k + 2u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-                }
-#if defined(NL_ROUND_STATS) && defined(NL_MLZ_EXP_TIMING)
-                if (threadIdx.x == 0) { NL_STAT(5, __builtin_readcyclecounter() - tt0); NL_STAT(4, 1); }
-#endif
-            }
-            const int j = k - 1;
-            if (j >= 0 && (j & 3) == wave) {
-#if defined(NL_ROUND_STATS) && defined(NL_MLZ_EXP_TIMING)
-                const unsigned long long ts1 = __builtin_readcyclecounter();
-#endif
-                mlz_spin_until(&s_done[j & 1], 4u * (unsigned)((j >> 1) + 1));             // every wave's rows of block j
-                if (j >= 1) mlz_spin_until(&s_freed[(j - 1) & 1], (unsigned)(((j - 1) >> 1) + 1));      // the table area is free
-#if defined(NL_ROUND_STATS) && defined(NL_MLZ_EXP_TIMING)
-                if (lane == 0) NL_STAT(2, __builtin_readcyclecounter() - ts1);
-#endif
-                rounds_call(prev_blk, lds + (j & 1) * (V::ROWS * PW), tabbase);
-                lds_settle();
-                if (lane == 0) __hip_atomic_fetch_add(&s_freed[j & 1], 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-            }
-            if (!has) break;
-            prev_blk = blk;
-        }
-        return;
-    } else {
-    if constexpr (PHASE == 2) {
-        // ---- the columns the sorting kernel left: rows of 64 pixels, back to their places in LDS ----
-        const float *src = q.cols + (size_t)blockIdx.x * (size_t)(SP::N * PW) + lane;
-        static_range<0, SP::N>([&](auto G) NL_INL {
-            constexpr int g = decltype(G)::value;
-            lds[SP::row(g) * PW + lane] = src[g * PW];
-        });
-        lds_settle();
-    } else {
-        sorting_phase((int64_t)blockIdx.x, lds, []() NL_INL {});
-    }
-    if constexpr (PHASE == 1) {
-        // the columns, the window and the scalars of the workgroup's 64 pixels: 256-byte rows, every wave its share
-        __syncthreads();
-        float *dst = q.cols + (size_t)blockIdx.x * (size_t)(SP::N * PW) + lane;
-        static_range<0, (SP::N + 3) / 4>([&](auto G) NL_INL {
-            const int g = 4 * decltype(G)::value + (int)(threadIdx.x >> 6);
-            if (g < SP::N) dst[g * PW] = lds[SP::row_rt(g) * PW + lane];
-        });
-        return;
-    } else if constexpr (PHASE == 2) {
-        // (one wave: nothing to meet)
-    } else if constexpr (L::PACK) {
+    sorting_phase((int64_t)blockIdx.x, lds);
+    if constexpr (L::PACK) {
         __syncthreads();
 #ifdef NL_MLZ_EXP_SORTONLY
         if (p.npix > 0) return;                            // (timing experiment: the sorting phase alone)
@@ -1061,7 +911,6 @@ void stack_sigma_mlz_kernel(StackArgs p, FastArgs q)
         lds_settle();
     }
     rounds_phase((int64_t)blockIdx.x, lds, lds);
-    }
 }
 
 
@@ -1077,31 +926,6 @@ static bool launch_mlz_classes(int ntop, bool winsor, const StackArgs &args, con
         using L = MlzLayout<LPP, false, NTOP>;
         using LW = MlzLayout<LPP, true, NTOP>;
         if (winsor) hipLaunchKernelGGL((stack_sigma_mlz_kernel<LPP, true, NTOP>), dim3((unsigned)((args.npix + LW::PW - 1) / LW::PW)), dim3(LW::BLOCK), 0, stream, args, f);
-        else if constexpr (L::SELECT) {
-            const dim3 grid((unsigned)((args.npix + L::PW - 1) / L::PW));
-#ifdef NL_EXPERIMENTS
-            // (both measured slower than the one-kernel pass, DESIGN.md section 5n: instantiated in the experiments build only)
-            if (f.cols) {
-                // split pass: the sorting kernel's workgroups retire as a whole (in the one-kernel pass three of a
-                // workgroup's four wave slots idle while its fourth wave runs the rounds), then one wave per 64 pixels
-                hipLaunchKernelGGL((stack_sigma_mlz_kernel<LPP, false, NTOP, 1>), grid, dim3(L::BLOCK), 0, stream, args, f);
-                hipLaunchKernelGGL((stack_sigma_mlz_kernel<LPP, false, NTOP, 2>), grid, dim3(64), 0, stream, args, f);
-            } else if (f.persistent) {
-                // persistent workgroups, three per CU (168 registers: three waves per SIMD), each looping over blocks of 64 pixels
-                static const int cus = [] {
-                    int dev = 0, n = 0;
-                    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-                    return n;
-                }();
-                static const int per_cu = [] { const char *e = getenv("NL_MLZ_WGS_PER_CU"); const int v = e ? atoi(e) : 3; return v >= 1 && v <= 8 ? v : 3; }();      // (experiments)
-                const unsigned wgs = (unsigned)(per_cu * cus);
-                hipLaunchKernelGGL((stack_sigma_mlz_kernel<LPP, false, NTOP, 3>), dim3(grid.x < wgs ? grid.x : wgs), dim3(L::BLOCK), 0, stream, args, f);
-            } else
-#endif
-            {
-                hipLaunchKernelGGL((stack_sigma_mlz_kernel<LPP, false, NTOP>), grid, dim3(L::BLOCK), 0, stream, args, f);
-            }
-        }
         else        hipLaunchKernelGGL((stack_sigma_mlz_kernel<LPP, false, NTOP>), dim3((unsigned)((args.npix + L::PW - 1) / L::PW)), dim3(L::BLOCK), 0, stream, args, f);
         done = true;
     };

@@ -106,19 +106,9 @@ struct FastArgs {
     int pass_budget, round_cap;   // clipping passes a wave may run in this stage / winsorization rounds per pass (0 = no limit)
     int record_only = 0;          // LDS-column kernels as the DECISION pass of a weighted stack (129 ... 512 frames): no outputs, no
                                   // lists, no counters -- only StackArgs::bounds / nrounds (0 rounds for a pixel they would hand over)
-    // The split pass of the LDS-column kernel whose columns are selected (497 ... 512 frames, plain sigma; stack_fast_mlz_impl.hpp):
-    // the sorting kernel leaves mlz_split_rows() rows x 64 pixels per workgroup here (blocks of 64 pixels, contiguous; cols_stride =
-    // pixels the buffer holds, a multiple of 64) and a second kernel, one wave per block, runs the clipping rounds over them.
-    // nullptr: one kernel does both.
-    float *cols = nullptr;
-    long long cols_stride = 0;
-    // The same class as PERSISTENT workgroups (three per CU, each looping over blocks of 64 pixels; the rounds of a block run in one
-    // of its waves while the others are sorting the next block -- stack_fast_mlz_impl.hpp, PHASE 3).  0: one workgroup per block.
     int cert_first = 0, cert_every = 1;      // invariant-interval certificate of the winsorization loops (stack_fast_sigma_impl.hpp): first trial after this many rounds of a loop (0: off), then every so many
     int gen_round_cap = 0;        // generic pass of the one-lane winsorized kernels: winsorization rounds per clipping pass before a pixel
                                   // is handed to the exact replay instead (0: 100, the limit of every kernel)
-    int persistent = 0;
-    unsigned *ticket = nullptr;   // persistent workgroups: the next block to hand out (zero at the start of the pass)
 };
 
 // sets what nl_last_error() returns on this thread (nlstack_api.hip)
@@ -211,13 +201,11 @@ int exact_plan(int mode, bool weighted, int n_frames, int n_pad, int max_lanes, 
                size_t *lds_bytes);
 hipError_t launch_stack_exact(int mode, bool weighted, StackArgs &args, int lanes, int grid,
                               size_t lds_bytes, hipStream_t stream, const char **name);
-// list_counts (optional): {exact-list length, generic-list length} of the pass, left in counters[2] (low | high << 32);
-// a chunked pass has n_lists such pairs, list_stride words apart, and leaves their sums
+// list_counts (optional): {exact-list length, generic-list length} of the pass, left in counters[2] (low | high << 32)
 // zero_after: the kernel leaves the scratch set (kScratchWords words at `partial`) zeroed for the next pass
 hipError_t launch_reduce_counters(unsigned long long *partial, int n_blocks,
                                   unsigned long long *counters, hipStream_t stream,
-                                  const unsigned *list_counts = nullptr, int n_lists = 1, int list_stride = 0,
-                                  bool zero_after = false);
+                                  const unsigned *list_counts = nullptr, bool zero_after = false);
 
 // ---- stack_fast.hip ----
 // one-lane register kernels address a group of 4 frames through one buffer descriptor with
@@ -238,18 +226,14 @@ typedef void (*AfterDominant)(void *user);
 hipError_t launch_stack_sigma_mlg(const StackArgs &args, const FastArgs &fargs, unsigned grid, hipStream_t stream,
                                   bool winsor);
 int fast_mlz_supported(int mode, bool weighted, int n_frames);
-// rows per pixel the split pass of this mode / frame count keeps in FastArgs::cols (0: the pass is not split)
-int mlz_split_rows(int mode, int n_frames);
 hipError_t launch_stack_sigma_mlz(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name,
                                   bool winsor);
-// tail (optional): the stream the generic pass is launched on instead of `stream` -- chunked passes
-// (nlstack_api.hip), whose after_dominant callback orders it behind the dominant kernel
 // fused_replay (optional; tail_fused_supported): the generic pass and the replay of the exact list as the dominant kernel left
 // it run as ONE launch (stack_tail_fused.hip) -- *fused_replay are the replay's arguments (list part 0), in fused_replay_blocks
 // workgroups; after_dominant is then not needed for the replay
 hipError_t launch_stack_sigma_fast(const StackArgs &args, const FastArgs &fargs, hipStream_t stream,
                                    const char **name, hipEvent_t dominant_done,
-                                   bool winsor, AfterDominant after_dominant, void *user, hipStream_t tail = nullptr,
+                                   bool winsor, AfterDominant after_dominant, void *user,
                                    const StackArgs *fused_replay = nullptr, unsigned fused_replay_blocks = 0);
 // ---- stack_tail_fused.hip: generic pass (one lane per pixel, LDS columns) + first replay in one grid; plain sigma, 65 ... 128 frames
 int tail_fused_supported(int mode, bool weighted, int n_frames);
@@ -272,18 +256,13 @@ hipError_t launch_stack_median_ml(const StackArgs &args, hipStream_t stream, con
 hipError_t launch_stack_mad_ml(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name);
 hipError_t launch_stack_sigma_ml(const StackArgs &args, const FastArgs &fargs, hipStream_t stream,
                                  const char **name, hipEvent_t dominant_done, bool winsor,
-                                 AfterDominant after_dominant, void *user, hipStream_t tail = nullptr);
+                                 AfterDominant after_dominant, void *user);
 
 // ---- stack_exact_coop.hip (bit-exact sigma replay, one wave per pixel) ----
 int coop_supported(int mode, bool weighted, int n_frames);
 hipError_t launch_stack_median_coop(const StackArgs &args, int grid, hipStream_t stream, const char **name);
 hipError_t launch_stack_sigma_coop(int mode, const StackArgs &args, int grid, hipStream_t stream, const char **name);
 int coop_group(const StackArgs &args);      // pixels per work item of that launch (4: whole-tile replay with aligned 16-byte loads)
-
-// ---- stack_exact_coop4.hip (the same replay, four pixels per wave on 16-lane rows: the sequential sums cost a
-// third of the instructions per pixel) ----
-int coop4_supported(int mode, bool weighted, int n_frames);
-hipError_t launch_stack_sigma_coop4(int mode, const StackArgs &args, int grid, hipStream_t stream, const char **name);
 
 // ---- stack_exact_tile.hip (bit-exact sigma / winsorized clipping over whole tiles: one wave = 64
 // consecutive pixels, columns in LDS, one pixel per lane; the weighted modes' default path) ----
@@ -298,11 +277,7 @@ constexpr int kTileMaxFramesSigma = 40, kTileMaxFramesWinsor = 32;
 // frames 9.3 (tile) vs 11.5, 44: 13.7 vs 13.7, 56: 21.7 vs 16.9, 64: 21.2 (four pixels per wave) vs 18.9, 96: 30.6
 // vs 26.0; winsorized 36 frames 27.2 (tile) vs 16.6, 44: 36.2 vs 17.4, 96: 35.5 (four) vs 28.9, 128: 52.6 vs 38.3;
 // with four pixels per work item (stack_exact_coop.hip, GROUP): sigma 34 frames 8.5 (tile) vs 11.1, 40: 11.4 vs 11.7,
-// 44: 13.7 vs 12.0.)  Four pixels per wave stays for winsorized stacks WITHOUT a decision pass (since the LDS-column
-// kernels decide 129 ... 512 frames: only with developer switch 4 or without memory for the bounds), for
-// kCoop4MinFrames ... kCoop4MaxFrames frames (ms per 2048 x 4096 pixels, four pixels per wave vs one: 136 frames 65 vs 89,
-// 160 frames 79 vs 93, 192 frames 115 vs 98).
-constexpr int kCoop4MinFrames = 129, kCoop4MaxFrames = 176;
+// 44: 13.7 vs 12.0.)
 int tile_supported(int mode, bool weighted, int n_frames);
 hipError_t launch_stack_sigma_tile(int mode, const StackArgs &args, int grid, hipStream_t stream, const char **name);
 
@@ -320,27 +295,6 @@ constexpr int kLinfitStages = 4;
 constexpr int kLinfitCounters = 8;  // device list lengths of one pass (the bit-exact cascade uses the first kLinfitStages)
 int linfit_fast_supported(int mode, int n_frames, int64_t npix);
 int linfit_ml_supported(int mode, int n_frames, int64_t npix);
-
-// ---- stack_linfit_guard.hip (guarded stages in front of the bit-exact cascade, 17 ... 128 frames) ----
-// Three pixel lists with liveness masks (npix entries each) and kLinfitCounters list lengths, zeroed per pass:
-// two continuation lists ping-pong between the guarded stages, the third collects the pixels a guarded stage cannot
-// decide; the bit-exact stages over it reuse the first two.
-struct LinfitGuardBufs {
-    unsigned *list[3];
-    uint4 *state[3];
-    unsigned *count;              // device: [kLinfitCounters]
-    unsigned capacity;
-};
-struct LinfitGuardLists {          // where a guarded stage hands its undecidable pixels over
-    unsigned *x_list; unsigned *x_count; uint4 *x_state; unsigned x_capacity;
-};
-struct LinfitStage;
-int linfit_guard_supported(int mode, int n_frames, int64_t npix);
-hipError_t launch_stack_linfit_guarded(const StackArgs &args, const FastArgs &fargs, const LinfitGuardBufs &bufs,
-                                       hipStream_t stream, const char **name, hipEvent_t dominant_done);
-// one continuation stage of the bit-exact one-lane kernel over stage.in_list (stack_linfit.hip)
-void launch_linfit_exact_stage(const StackArgs &args, const FastArgs &fargs, const LinfitStage &stage, unsigned blocks,
-                               hipStream_t stream);
 
 hipError_t launch_stack_linfit_fast(const StackArgs &args, const FastArgs &fargs, const LinfitCascade *cascade,
                                     hipStream_t stream, const char **name, hipEvent_t dominant_done);

@@ -822,20 +822,6 @@ static void launch_lf(const StackArgs &args, const FastArgs &f, const LinfitCasc
     }
 }
 
-// one continuation stage of the one-lane kernel over stage.in_list (the bit-exact tail of other cascades)
-void launch_linfit_exact_stage(const StackArgs &args, const FastArgs &fargs, const LinfitStage &stage, unsigned blocks,
-                               hipStream_t stream)
-{
-    const int n = args.n_frames;
-    if (n <= 8)        hipLaunchKernelGGL((stack_linfit_fast_kernel<8, true>), dim3(blocks), dim3(256), 0, stream, args, fargs, stage);
-    else if (n <= 16)  hipLaunchKernelGGL((stack_linfit_fast_kernel<16, true>), dim3(blocks), dim3(256), 0, stream, args, fargs, stage);
-    else if (n <= 32)  hipLaunchKernelGGL((stack_linfit_fast_kernel<32, true>), dim3(blocks), dim3(256), 0, stream, args, fargs, stage);
-    else if (n <= 48)  hipLaunchKernelGGL((stack_linfit_fast_kernel<48, true>), dim3(blocks), dim3(256), 0, stream, args, fargs, stage);
-    else if (n <= 64)  hipLaunchKernelGGL((stack_linfit_fast_kernel<64, true>), dim3(blocks), dim3(256), 0, stream, args, fargs, stage);
-    else if (n <= 96)  hipLaunchKernelGGL((stack_linfit_fast_kernel<96, true>), dim3(blocks), dim3(256), 0, stream, args, fargs, stage);
-    else               hipLaunchKernelGGL((stack_linfit_fast_kernel<128, true>), dim3(blocks), dim3(256), 0, stream, args, fargs, stage);
-}
-
 hipError_t launch_stack_linfit_fast(const StackArgs &args, const FastArgs &fargs, const LinfitCascade *cascade,
                                     hipStream_t stream, const char **name, hipEvent_t dominant_done)
 {

@@ -174,7 +174,7 @@ class StackHandle:
 
     @property
     def last_pass_protocol(self):
-        """Bit 0: fused protocol, bit 1: generic pass + first replay in one launch, bit 2: chunked (diagnostics)."""
+        """Bit 0: fused protocol, bit 1: generic pass + first replay in one launch (diagnostics)."""
         return int(self._lib.nl_stack_last_pass_protocol(self._h))
 
     @property

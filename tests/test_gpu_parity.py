@@ -206,22 +206,6 @@ def test_wave_per_pixel_exact_replay_is_bit_exact(nl, oracle, n):
                 assert gc == wc
 
 
-@pytest.mark.parametrize("n", [1, 2, 3, 7, 15, 16, 17, 33, 64, 65, 128, 130, 300, 512])
-def test_four_pixels_per_wave_exact_replay_is_bit_exact(nl, oracle, experiments, n):
-    # stack_exact_coop4.hip: the same replay with four pixels per wave on 16-lane rows (row_shr chains); forced
-    # for every pixel (37 x 5 = 185 pixels: the last wave holds one pixel, rows with different sample counts,
-    # NaN borders, ties)
-    width, height = 37, 5
-    frames = make_frames(n, width, height, seed=1900 + n, ties=(n % 2 == 1))
-    weights = np.random.default_rng(n).uniform(0.2, 1.0, n).astype(np.float32)
-    for mode in (2, 3):
-        for kappa in (2.75, 1.0):
-            for w in (None, weights):
-                got, gc, want, wc = run_both(nl, oracle, mode, frames, width, height, w, kappa, kappa, exact=4)
-                assert same_values(got, want), "coop4 %s n=%d: %s" % (MODES[mode], n, describe_mismatch(got, want))
-                assert gc == wc
-
-
 @pytest.mark.parametrize("n", [1, 2, 3, 5, 8, 9, 25, 31, 33, 64, 65, 100, 128])
 def test_register_resident_linear_fit_is_bit_exact(nl, oracle, n):
     # default dispatch for linear fit (stack_linfit.hip): one sort, then every sum
@@ -761,38 +745,6 @@ def test_developer_switches_do_not_change_results(nl, oracle, mode, n, weighted)
             assert np.array_equal(got.view(np.uint32), ref[0].view(np.uint32)), flags
 
 
-@pytest.mark.parametrize("n,weighted,height", [(512, False, 12), (500, False, 9), (512, True, 6)])
-def test_split_lds_column_pass_gives_the_bits_of_the_one_kernel_pass(nl, oracle, experiments, n, weighted, height):
-    # developer switch 1024: the selected LDS-column kernel (497 ... 512 frames, plain sigma) as a sorting kernel plus a
-    # rounds kernel over columns kept in device memory (FastArgs::cols); 2048: as persistent workgroups that loop over
-    # blocks of 64 pixels without a barrier -- same code for the rounds, so the same bits, counters and hand-over lists;
-    # a ragged last workgroup (height * width not a multiple of 64) included
-    width = 4096 if height != 9 else 1000
-    with nl.StackHandle(n, width, 4096, row0=0, rows=height) as st:
-        st.fill_synthetic(9)
-        if weighted:
-            st.set_weights(np.random.default_rng(n).uniform(0.2, 1.0, n).astype(np.float32))
-        ref = None
-        b0 = None
-        for flags in (0, 1024, 1024 | 1, 2048, 2048 | 1, 0):
-            st.set_dev_flags(flags)
-            got, cl, ch = st.run(2, 3.0, 2.5)
-            got = got[:height * width]
-            if ref is None:
-                ref = (got.copy(), cl, ch, st.last_generic_pixels, st.last_fallback_pixels)
-                b0 = st.device_bytes
-            assert (cl, ch) == ref[1:3], (flags, cl, ch, ref[1:3])
-            assert np.array_equal(got.view(np.uint32), ref[0].view(np.uint32)), flags
-            if not weighted:
-                assert (st.last_generic_pixels, st.last_fallback_pixels) == ref[3:], flags
-        assert st.device_bytes >= b0 + 88 * 4 * height * width          # the columns' buffer is on the books
-        if not weighted:
-            frames = [st.download_tile(i) for i in range(n)]
-            rc, want, wl, wh, _ = oracle.stack_apply(2, frames, None, 3.0, 2.5)
-            assert (wl, wh) == ref[1:3]
-            assert np.allclose(ref[0], want[:height * width], rtol=1e-5, atol=0)
-
-
 def test_device_bytes_reports_the_lazily_allocated_scratch(nl):
     # nl_stack_device_bytes: create-time buffers, then the decision-pass thresholds a weighted clip mode allocates
     # on its first pass (65 bytes per pixel) and keeps until destroy
@@ -1100,3 +1052,70 @@ def test_winsor_certificate_on_and_off_give_identical_counters(nl, oracle, n):
         rc, want, wl, wh, _ = oracle.stack_apply(3, frames, None, sl, sh, 0.0, num_cpu=4)
         assert rc == 0 and (al, ah) == (wl, wh), "n=%d sigma %r: counters %r vs oracle %r" % (n, (sl, sh), (al, ah), (wl, wh))
         assert close_values(a, want), "n=%d sigma %r: %s" % (n, (sl, sh), describe_mismatch(a, want))
+
+
+# The engine every pass runs, pinned per row: mode, frames, weighted, nl_stack_set_exact, developer switches ->
+# nl_stack_last_kernel_name, nl_stack_last_pass_protocol of the second pass on one handle (the first one leaves the
+# list-length hints the second sizes its replay grids and picks its protocol from).
+DISPATCH_TABLE = [
+    # mode, n, weighted, exact, flags, kernel, protocol
+    (1, 16, False, 0, 0, "stack_mean_vec4_kernel", 0),
+    (0, 64, False, 0, 0, "stack_median_fast_kernel<64, true>", 0),
+    (0, 300, False, 0, 0, "stack_median_ml_kernel<4>", 0),
+    (0, 600, False, 0, 0, "stack_median_coop_kernel", 0),
+    (4, 64, False, 0, 0, "stack_mad_fast_kernel<64>", 0),
+    (4, 300, False, 0, 0, "stack_mad_ml_kernel<4>", 0),
+    (5, 64, False, 0, 0, "stack_linfit_fast_kernel<64, false>", 0),
+    (5, 300, False, 0, 0, "stack_linfit_ml_kernel<4, false>", 0),
+    (2, 32, False, 0, 0, "stack_sigma_fast_kernel<32, true, false, true, false, false>", 1),
+    (2, 128, False, 0, 0, "stack_sigma_fast_kernel<128, true, false, true, false, false>", 3),
+    (2, 300, False, 0, 0, "stack_sigma_mlz_kernel<4, false, 304, 0>", 1),
+    (2, 600, False, 0, 0, "stack_sigma_coop_kernel<false, false, 4, 2>", 0),
+    (3, 16, False, 0, 0, "stack_sigma_fast_kernel<16, true, true, true, false, false>", 1),
+    (3, 24, False, 0, 0, "stack_sigma_fast_kernel<24, true, true, true, false, false>", 1),
+    (3, 128, False, 0, 0, "stack_sigma_fast_kernel<128, true, true, true, false, false>", 1),
+    (3, 300, False, 0, 0, "stack_sigma_mlz_kernel<4, true, 304, 0>", 1),
+    (2, 32, True, 0, 0, "stack_sigma_tile_kernel<sigma,weighted>", 0),
+    (2, 100, True, 0, 0, "stack_sigma_coop_kernel<false, true, 4, 2>", 0),
+    (2, 300, True, 0, 0, "stack_sigma_coop_kernel<false, true, 4, 2>", 0),
+    (3, 64, True, 0, 0, "stack_sigma_coop_kernel<true, true, 4, 2>", 0),
+    (2, 32, False, 1, 0, "stack_exact_kernel<sigma>", 0),
+    (2, 32, False, 2, 0, "stack_sigma_coop_kernel<false, false, 4, 2>", 0),
+    (2, 32, False, 3, 0, "stack_sigma_tile_kernel<sigma>", 0),
+    (2, 128, False, 0, 1, "stack_sigma_fast_kernel<128, true, false, true, false, false>", 0),
+    (2, 128, False, 0, 2, "stack_sigma_fast_kernel<128, true, false, true, false, false>", 1),
+    (2, 32, True, 0, 16, "stack_sigma_coop_kernel<false, true, 4, 2>", 0),
+    (2, 128, False, 0, 8192, "stack_sigma_fast_kernel<128, true, false, true, false, false>", 1),
+]
+
+
+def _dispatch_second_pass(nl, mode, n, weighted, exact, flags):
+    with nl.StackHandle(n, 4096, 4096, row0=0, rows=16) as st:
+        st.fill_synthetic(3)
+        if weighted:
+            st.set_weights(np.linspace(0.2, 1.0, n).astype(np.float32))
+        st.set_exact(exact)
+        st.set_dev_flags(flags)
+        for _ in range(2):
+            st.run(mode, 3.0, 2.5, fetch=False)
+        return st.last_kernel_name, st.last_pass_protocol, st.last_mode
+
+
+@pytest.mark.parametrize("mode,n,weighted,exact,flags,kernel,protocol", DISPATCH_TABLE)
+def test_dispatch_table(nl, mode, n, weighted, exact, flags, kernel, protocol):
+    assert _dispatch_second_pass(nl, mode, n, weighted, exact, flags) == (kernel, protocol, mode)
+
+
+def test_mean_pass_reports_no_hand_over_lists(nl):
+    # a mean pass hands no pixels over: after a sigma fast pass that listed pixels (infinite samples go to the exact
+    # kernel), a mean pass on the same handle reports empty lists, not the lists of the pass before it
+    width, height = 64, 8
+    frames = make_frames(64, width, height, seed=31, nan_frac=0.0, nan_border=False, all_nan_patch=False)
+    frames[2, 5] = np.inf
+    frames[7, 100] = np.inf
+    with nl.StackHandle(64, width, height) as st:
+        st.upload_frames(frames)
+        st.run(2, 2.75, 2.75)
+        assert st.last_fallback_pixels > 0
+        st.run(1)
+        assert (st.last_fallback_pixels, st.last_generic_pixels) == (0, 0)
