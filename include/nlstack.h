@@ -414,6 +414,46 @@ int nl_median_filter_3x3(const float *in_host, float *out_host, int width, int h
 int nl_median_filter_mask(const float *in_host, float *out_host, int64_t n, const int32_t *mask,
                           int mask_len, int device);
 
+/* ---- OpCalibrate and OpBadPixel, mono (internal/ops/pre/preprocess.go:68-195) ----
+ * The per-frame steps of the reference's `stack` command in front of debayering and star detection
+ * (cmd/nightlight/main.go:285-293).  Bit-exact: Subtract c = a - b (badpixels.go:107-111), Divide
+ * c = b <= 0 ? a : (a*bMax)/b in fp32 (badpixels.go:114-123); bad pixels as BadPixelMap
+ * (badpixels.go:32-51) finds them and MedianFilterSparse (badpixels.go:81-88) replaces them, in index
+ * order and in place.  No CPU path: without a device every entry fails with NL_ERR_NO_DEVICE.
+ *
+ * nl_calib_create: OpCalibrate's masters resident on one device (dark / flat: width*height fp32 of
+ * their own shape, either may be NULL but not both); the flat's Stats.Max() (stats.go:112-121) is
+ * taken here over the whole flat.  Dark and flat of different shapes: NULL, nl_last_error() =
+ * "dark dimensions [w h] differ from flat dimensions [w h]" (preprocess.go:144-147).  Read-only
+ * afterwards: any number of threads may share one.  NULL on failure (message in nl_last_error()). */
+typedef struct nl_calib nl_calib_t;
+nl_calib_t *nl_calib_create(int device, const float *dark_host, int dark_width, int dark_height,
+                            const float *flat_host, int flat_width, int flat_height);
+void nl_calib_destroy(nl_calib_t *c);
+int nl_calib_flat_max(const nl_calib_t *c, float *out);
+/* OpCalibrate.Apply (preprocess.go:68-99) then OpBadPixel.Apply, mono branch (preprocess.go:180-195),
+ * on one host frame of width x height, one device round trip.  c may be NULL (no masters).  A light
+ * whose shape differs from the masters' fails with "<frame_id>: Light dimensions [w h] differ from
+ * dark dimensions [w h]" (or "flat"), unless the pixel counts are equal: then the masters apply 1-D
+ * (the reference's Seestar case, where it prints a warning the caller may print too).
+ * sigma_low == 0 || sigma_high == 0: no bad-pixel step (removed 0, diff stats NaN).  A negative sigma
+ * fails with NL_ERR_INVALID_ARG: the reference would flag the zero differences of the border -- the
+ * one deviation.  removed_out: number of bad pixels (len(bpm)); diff_stats_out[2]: mean and
+ * StdDev() of the local-median differences (Image.MedianDiffStats, which FindStars reads).
+ * out_host may equal in_host.  frame_id only for the error strings.  Safe to call from several host
+ * threads at once (each call has a stream and scratch of its own). */
+int nl_preprocess_frame(const nl_calib_t *c, int frame_id, const float *in_host, float *out_host,
+                        int width, int height, float sigma_low, float sigma_high,
+                        int64_t *removed_out, float *diff_stats_out, int device);
+/* The same steps on a resident frame slot.  Calibrate works on any row tile (the tile's 1-D range of
+ * the masters; c on the handle's device; the slot index is the frame id of the error strings).  The
+ * bad-pixel step needs a whole-image handle (3x3 stencil and a whole-frame std), like
+ * nl_stack_frame_noise; a tile handle fails with NL_ERR_INVALID_ARG.  Thresholds are computed on the
+ * device: the only host round trip is the read-back of removed_out / diff_stats_out at the end. */
+int nl_stack_frame_calibrate(nl_stack_t *h, int idx, const nl_calib_t *c);
+int nl_stack_frame_badpixel(nl_stack_t *h, int idx, float sigma_low, float sigma_high,
+                            int64_t *removed_out, float *diff_stats_out);
+
 /* ---- host-side operator mirror (nightlight_amd/host/, C++) ----
  * The reference's stack operator decoded from its JSON form and run through
  * MakePromises/Apply exactly as OpSequence would drive it

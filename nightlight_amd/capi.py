@@ -52,6 +52,8 @@ EXPORTS = [
     "nl_stack_download_result_fits", "nl_fits_decode", "nl_project_bilinear",
     "nl_host_op_stack_apply_json", "nl_host_op_stack_roundtrip_json", "nl_host_set_devices",
     "nl_host_op_stack_batches_apply_json",
+    "nl_calib_create", "nl_calib_destroy", "nl_calib_flat_max", "nl_preprocess_frame",
+    "nl_stack_frame_calibrate", "nl_stack_frame_badpixel",
 ]
 
 
@@ -211,6 +213,15 @@ def open_library(path):
     L.nl_host_set_devices.argtypes = [_intp, C.c_int]
     L.nl_host_op_stack_roundtrip_json.argtypes = [C.c_char_p]
     L.nl_host_op_stack_roundtrip_json.restype = C.c_char_p
+    L.nl_calib_create.argtypes = [C.c_int, _f32p, C.c_int, C.c_int, _f32p, C.c_int, C.c_int]
+    L.nl_calib_create.restype = vp
+    L.nl_calib_destroy.argtypes = [vp]
+    L.nl_calib_destroy.restype = None
+    L.nl_calib_flat_max.argtypes = [vp, _f32p]
+    L.nl_preprocess_frame.argtypes = [vp, C.c_int, _f32p, _f32p, C.c_int, C.c_int, C.c_float, C.c_float, _i64p,
+                                      _f32p, C.c_int]
+    L.nl_stack_frame_calibrate.argtypes = [vp, C.c_int, vp]
+    L.nl_stack_frame_badpixel.argtypes = [vp, C.c_int, C.c_float, C.c_float, _i64p, _f32p]
     return L
 
 

@@ -6,6 +6,7 @@
 // All are single-pass HBM streams (4 B read per sample): 16-byte loads,
 // grid-stride, wave shuffle + LDS block reduction, one fp64 partial per
 // workgroup, summed on the host (a few thousand values).
+#include "median9.hpp"
 #include "stack_kernels.h"
 
 namespace nl {
@@ -144,12 +145,7 @@ __global__ __launch_bounds__(256) void noise_kernel(const float *data, int width
     if (threadIdx.x == 0) partial[blockIdx.x] = s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];
 }
 
-// 19-step median-of-9 exchange network (median3x3.go:85-110); min/max only,
-// so results are bit-exact for NaN-free input.
-#define NL_CE(i, j) { const float lo_ = fminf(a##i, a##j); a##j = fmaxf(a##i, a##j); a##i = lo_; }
-#define NL_MAXTO(i, j) { a##j = fmaxf(a##i, a##j); }
-#define NL_MINTO(i, j) { a##i = fminf(a##i, a##j); }
-
+// MedianFilter3x3 (median3x3.go:26-110) through the shared network of median9.hpp.
 __global__ __launch_bounds__(256) void median3x3_kernel(const float *in, float *out, int width,
                                                          int height)
 {
@@ -162,23 +158,7 @@ __global__ __launch_bounds__(256) void median3x3_kernel(const float *in, float *
             continue;
         }
         const float *r0 = in + t - width, *r1 = in + t, *r2 = in + t + width;
-        float a0 = r0[-1], a1 = r0[0], a2 = r0[1];
-        float a3 = r1[-1], a4 = r1[0], a5 = r1[1];
-        float a6 = r2[-1], a7 = r2[0], a8 = r2[1];
-        NL_CE(0, 1) NL_CE(3, 4) NL_CE(6, 7)
-        NL_CE(1, 2) NL_CE(4, 5) NL_CE(7, 8)
-        NL_CE(0, 1) NL_CE(3, 4) NL_CE(6, 7)
-        NL_MAXTO(0, 3)
-        NL_MAXTO(3, 6)
-        NL_CE(1, 4)
-        NL_MINTO(4, 7)
-        NL_MAXTO(1, 4)
-        NL_MINTO(5, 8)
-        NL_MINTO(2, 5)
-        NL_CE(2, 4)
-        NL_MINTO(4, 6)
-        NL_MAXTO(2, 4)
-        out[t] = a4;
+        out[t] = median9(r0[-1], r0[0], r0[1], r1[-1], r1[0], r1[1], r2[-1], r2[0], r2[1]);
     }
 }
 

@@ -14,6 +14,7 @@
 #include <thread>
 #include <vector>
 
+#include "preprocess.hpp"
 #include "stack_kernels.h"
 
 namespace {
@@ -451,6 +452,12 @@ struct nl_stack {
     bool stage_used[kStageSlots] = {false, false, false, false};
     int stage_next = 0;
     bool uploads_pending = false;
+    // bad-pixel step (nl_stack_frame_badpixel), lazily allocated: diff, per-workgroup lists, ordered list,
+    // nl::BpParams + per-workgroup list lengths, offsets, bad-pixel counts
+    float *d_bp_diff = nullptr;
+    unsigned *d_bp_seg = nullptr;
+    unsigned *d_bp_list = nullptr;
+    unsigned *d_bp_small = nullptr;
     int max_grid = 0;
     int last_mode = -1;
     bool last_has_counters = false;
@@ -581,6 +588,10 @@ static int destroy_impl(nl_stack_t *h)
         cached_free(h->d_lf_state[i], sizeof(uint4) * (size_t)h->npix * (size_t)h->lf_lanes, h->device);
     }
     if (h->d_lf_count) (void)hipFree(h->d_lf_count);
+    cached_free(h->d_bp_diff, sizeof(float) * (size_t)h->npix, h->device);
+    cached_free(h->d_bp_seg, sizeof(unsigned) * (size_t)nl::bp_blocks(h->npix) * nl::kBpChunk, h->device);
+    cached_free(h->d_bp_list, sizeof(unsigned) * (size_t)h->npix, h->device);
+    if (h->d_bp_small) (void)hipFree(h->d_bp_small);
     if (h->copy_stream) (void)hipStreamSynchronize(h->copy_stream);
     for (int i = 0; i < kStageSlots; i++) {
         pinned_free(h->h_stage[i], h->stage_cap[i]);
@@ -2194,6 +2205,204 @@ int nl_median_filter_3x3(const float *in_host, float *out_host, int width, int h
     if (e != hipSuccess) rc = fail(NL_ERR_HIP, "median_filter_3x3: %s", hipGetErrorString(e));
     (void)hipFree(d_in);
     (void)hipFree(d_out);
+    return rc;
+}
+
+// ---- OpCalibrate / OpBadPixel, mono (internal/ops/pre/preprocess.go:68-195; kernels in preprocess.hip) ----------
+
+// OpCalibrate's masters on one device (read-only after nl_calib_create: any number of threads may share one)
+struct nl_calib {
+    int device = 0;
+    int width = 0, height = 0;             // Naxisn of the masters
+    float *d_dark = nullptr, *d_flat = nullptr;
+    float flat_max = 0.0f;                 // FlatFrame.Stats.Max()
+};
+
+static int select_device(int device)
+{
+    int ndev = 0;
+    hipError_t e = hipGetDeviceCount(&ndev);
+    if (e != hipSuccess || ndev <= 0)
+        return fail(NL_ERR_NO_DEVICE, "no HIP device available (%s); libnlstack has no CPU path", hipGetErrorString(e));
+    if (device < 0 || device >= ndev) return fail(NL_ERR_INVALID_ARG, "device %d out of range (have %d)", device, ndev);
+    NL_HIP(hipSetDevice(device));
+    return NL_OK;
+}
+
+// Stats.Max() (stats.go:112-121) of the flat through the min / sum / max reduction of nl_stack_frame_stats
+static int flat_max_impl(const float *d_flat, int64_t n, float *out)
+{
+    double *d_part = nullptr;
+    NL_HIP(dev_malloc(&d_part, sizeof(double) * 3 * kStatBlocks));
+    std::vector<double> part(3 * kStatBlocks);
+    hipError_t e = nl::launch_min_sum_max(d_flat, n, d_part, kStatBlocks, nullptr);
+    if (e == hipSuccess) e = hipMemcpy(part.data(), d_part, sizeof(double) * part.size(), hipMemcpyDeviceToHost);
+    (void)hipFree(d_part);
+    if (e != hipSuccess) return fail(NL_ERR_HIP, "calib_create: flat maximum: %s", hipGetErrorString(e));
+    float hi = (float)part[2];
+    for (int b = 0; b < kStatBlocks; b++) {
+        const float bh = (float)part[3 * b + 2];
+        if (bh > hi) hi = bh;
+    }
+    *out = hi;
+    return NL_OK;
+}
+
+static int calib_create_impl(nl_calib *c, const float *dark_host, const float *flat_host)
+{
+    int rc = select_device(c->device);
+    if (rc != NL_OK) return rc;
+    const int64_t n = (int64_t)c->width * c->height;
+    const size_t bytes = (size_t)n * sizeof(float);
+    if (dark_host) {
+        NL_HIP(dev_malloc(&c->d_dark, bytes));
+        NL_HIP(hipMemcpy(c->d_dark, dark_host, bytes, hipMemcpyHostToDevice));
+    }
+    if (flat_host) {
+        NL_HIP(dev_malloc(&c->d_flat, bytes));
+        NL_HIP(hipMemcpy(c->d_flat, flat_host, bytes, hipMemcpyHostToDevice));
+        return flat_max_impl(c->d_flat, n, &c->flat_max);
+    }
+    return NL_OK;
+}
+
+nl_calib_t *nl_calib_create(int device, const float *dark_host, int dark_width, int dark_height,
+                            const float *flat_host, int flat_width, int flat_height)
+{
+    if (!dark_host && !flat_host) { fail(NL_ERR_INVALID_ARG, "calib_create: neither a dark nor a flat"); return nullptr; }
+    if ((dark_host && (dark_width < 1 || dark_height < 1)) || (flat_host && (flat_width < 1 || flat_height < 1))) {
+        fail(NL_ERR_INVALID_ARG, "calib_create: bad master dimensions");
+        return nullptr;
+    }
+    if (dark_host && flat_host && (dark_width != flat_width || dark_height != flat_height)) {      // preprocess.go:144-147
+        fail(NL_ERR_INVALID_ARG, "dark dimensions [%d %d] differ from flat dimensions [%d %d]", dark_width, dark_height,
+             flat_width, flat_height);
+        return nullptr;
+    }
+    nl_calib *c = new nl_calib();
+    c->device = device;
+    c->width = dark_host ? dark_width : flat_width;
+    c->height = dark_host ? dark_height : flat_height;
+    if (calib_create_impl(c, dark_host, flat_host) != NL_OK) {
+        std::string keep = g_err;
+        nl_calib_destroy(c);
+        g_err = keep;
+        return nullptr;
+    }
+    return c;
+}
+
+void nl_calib_destroy(nl_calib_t *c)
+{
+    if (!c) return;
+    if (c->d_dark || c->d_flat) {
+        (void)hipSetDevice(c->device);
+        if (c->d_dark) (void)hipFree(c->d_dark);
+        if (c->d_flat) (void)hipFree(c->d_flat);
+    }
+    delete c;
+}
+
+int nl_calib_flat_max(const nl_calib_t *c, float *out)
+{
+    if (!c || !out) return fail(NL_ERR_INVALID_ARG, "calib_flat_max: null argument");
+    if (!c->d_flat) return fail(NL_ERR_INVALID_ARG, "calib_flat_max: the calibration has no flat");
+    *out = c->flat_max;
+    return NL_OK;
+}
+
+// preprocess.go:73-93: the masters' shape, or another one with the same pixel count (the Seestar case: the data is
+// taken as 1-D, the reference prints a warning), else the reference's error (the dark is checked first)
+static int calib_check_light(const nl_calib *c, int frame_id, int width, int height)
+{
+    if ((width == c->width && height == c->height) || (int64_t)width * height == (int64_t)c->width * c->height)
+        return NL_OK;
+    return fail(NL_ERR_INVALID_ARG, "%d: Light dimensions [%d %d] differ from %s dimensions [%d %d]", frame_id, width,
+                height, c->d_dark ? "dark" : "flat", c->width, c->height);
+}
+
+int nl_stack_frame_calibrate(nl_stack_t *h, int idx, const nl_calib_t *c)
+{
+    NL_CHECK_HANDLE(h);
+    NL_SETTLE_UPLOADS(h);
+    if (idx < 0 || idx >= h->n_frames || !c)
+        return fail(NL_ERR_INVALID_ARG, "frame_calibrate: bad index %d or null calibration", idx);
+    if (c->device != h->device)
+        return fail(NL_ERR_INVALID_ARG, "frame_calibrate: calibration on device %d, handle on device %d", c->device,
+                    h->device);
+    int rc = calib_check_light(c, idx, h->width, h->height);
+    if (rc != NL_OK) return rc;
+    const int64_t off = (int64_t)h->row0 * h->width;          // the tile's 1-D range of the masters
+    float *d = h->d_frames + (int64_t)idx * h->fstride;
+    NL_HIP(nl::launch_calibrate(d, d, h->npix, c->d_dark ? c->d_dark + off : nullptr,
+                                c->d_flat ? c->d_flat + off : nullptr, c->flat_max, h->stream));
+    NL_HIP(hipStreamSynchronize(h->stream));
+    return NL_OK;
+}
+
+int nl_stack_frame_badpixel(nl_stack_t *h, int idx, float sigma_low, float sigma_high, int64_t *removed_out,
+                            float *diff_stats_out)
+{
+    NL_CHECK_HANDLE(h);
+    NL_SETTLE_UPLOADS(h);
+    if (idx < 0 || idx >= h->n_frames) return fail(NL_ERR_INVALID_ARG, "frame_badpixel: bad index %d", idx);
+    if (sigma_low == 0.0f || sigma_high == 0.0f) {         // preprocess.go:181-183: nothing to do
+        if (removed_out) *removed_out = 0;
+        if (diff_stats_out) diff_stats_out[0] = diff_stats_out[1] = NAN;
+        return NL_OK;
+    }
+    if (sigma_low < 0.0f || sigma_high < 0.0f)             // (the reference would flag the border: not supported)
+        return fail(NL_ERR_INVALID_ARG, "frame_badpixel: negative sigma (low %g, high %g)", sigma_low, sigma_high);
+    if (h->row0 != 0 || h->rows != h->height)
+        return fail(NL_ERR_INVALID_ARG, "frame_badpixel needs a whole-image handle (3x3 stencil, whole-frame std)");
+    if (h->npix >= ((int64_t)1 << 31)) return fail(NL_ERR_INVALID_ARG, "frame_badpixel: frame of 2^31 pixels or more");
+    const int blocks = nl::bp_blocks(h->npix);
+    if (!h->d_bp_diff) NL_HIP(cached_malloc((void **)&h->d_bp_diff, sizeof(float) * (size_t)h->npix, h->device));
+    if (!h->d_bp_seg)
+        NL_HIP(cached_malloc((void **)&h->d_bp_seg, sizeof(unsigned) * (size_t)blocks * nl::kBpChunk, h->device));
+    if (!h->d_bp_list) NL_HIP(cached_malloc((void **)&h->d_bp_list, sizeof(unsigned) * (size_t)h->npix, h->device));
+    if (!h->d_bp_small) NL_HIP(dev_malloc(&h->d_bp_small, sizeof(nl::BpParams) + 3 * sizeof(unsigned) * (size_t)blocks));
+    nl::BpScratch s;
+    s.diff = h->d_bp_diff;
+    s.seg = h->d_bp_seg;
+    s.list = h->d_bp_list;
+    s.params = reinterpret_cast<nl::BpParams *>(h->d_bp_small);
+    s.count = h->d_bp_small + sizeof(nl::BpParams) / sizeof(unsigned);
+    s.offset = s.count + blocks;
+    s.removed = s.offset + blocks;
+    s.partial = h->d_stat_partial;
+    s.stat_blocks = kStatBlocks;
+    NL_HIP(nl::launch_badpixel(h->d_frames + (int64_t)idx * h->fstride, h->width, h->height, sigma_low, sigma_high, s,
+                               h->stream));
+    nl::BpParams p;
+    NL_HIP(hipMemcpyAsync(&p, s.params, sizeof p, hipMemcpyDeviceToHost, h->stream));
+    NL_HIP(hipStreamSynchronize(h->stream));
+    if (removed_out) *removed_out = (int64_t)p.removed;
+    if (diff_stats_out) { diff_stats_out[0] = p.mean; diff_stats_out[1] = p.std; }
+    return NL_OK;
+}
+
+int nl_preprocess_frame(const nl_calib_t *c, int frame_id, const float *in_host, float *out_host, int width, int height,
+                        float sigma_low, float sigma_high, int64_t *removed_out, float *diff_stats_out, int device)
+{
+    if (!in_host || !out_host || width < 1 || height < 1)
+        return fail(NL_ERR_INVALID_ARG, "preprocess_frame: bad argument");
+    int rc = select_device(device);
+    if (rc != NL_OK) return rc;
+    if (c && c->device != device)
+        return fail(NL_ERR_INVALID_ARG, "preprocess_frame: calibration on device %d, frame on device %d", c->device,
+                    device);
+    if (c && (rc = calib_check_light(c, frame_id, width, height)) != NL_OK) return rc;
+    // a one-frame handle of its own per call carries stream and scratch: concurrent calls share nothing but c
+    nl_stack_t *h = nl_stack_create(1, width, height, 0, height, device);
+    if (!h) return NL_ERR_HIP;
+    rc = nl_stack_upload_tile(h, 0, in_host);
+    if (rc == NL_OK && c) rc = nl_stack_frame_calibrate(h, 0, c);
+    if (rc == NL_OK) rc = nl_stack_frame_badpixel(h, 0, sigma_low, sigma_high, removed_out, diff_stats_out);
+    if (rc == NL_OK) rc = nl_stack_download_tile(h, 0, out_host);
+    std::string keep = g_err;
+    nl_stack_destroy(h);
+    g_err = keep;
     return rc;
 }
 

@@ -323,6 +323,18 @@ class StackHandle:
     def frame_affine(self, idx, multiplier, offset):
         capi.check(self._lib.nl_stack_frame_affine(self._h, int(idx), float(multiplier), float(offset)))
 
+    def frame_calibrate(self, idx, calib):
+        """OpCalibrate.Apply on resident slot idx (any row tile; calib on the handle's device)."""
+        capi.check(self._lib.nl_stack_frame_calibrate(self._h, int(idx), calib._c))
+
+    def frame_badpixel(self, idx, sigma_low=3.0, sigma_high=5.0):
+        """OpBadPixel.Apply (mono) on resident slot idx of a whole-image handle.
+        Returns (removed, (diff_mean, diff_std))."""
+        removed, stats = C.c_int64(0), (C.c_float * 2)()
+        capi.check(self._lib.nl_stack_frame_badpixel(self._h, int(idx), float(sigma_low), float(sigma_high),
+                                                     C.byref(removed), stats))
+        return int(removed.value), (np.float32(stats[0]), np.float32(stats[1]))
+
     def download_result_fits(self):
         raw = np.empty(self.tile_pixels * 4, np.uint8)
         capi.check(self._lib.nl_stack_download_result_fits(self._h, raw.ctypes.data_as(C.c_void_p)))
@@ -498,6 +510,69 @@ def weights_from_scalars(weighting, per_frame):
     if rc != capi.OK:
         raise capi.NlError(rc, capi.last_error())
     return None if weighting == capi.WEIGHT_NONE else w
+
+
+class Calibration:
+    """OpCalibrate's dark and / or flat master resident on one device (nl_calib_t).  The flat's
+    shape defaults to (width, height); flat_width / flat_height give it another one (the reference
+    then fails with "dark dimensions ... differ from flat dimensions ...")."""
+
+    def __init__(self, device, width, height, dark=None, flat=None, flat_width=None, flat_height=None):
+        self._lib = capi.load()
+        self._c = None
+        fw = int(width if flat_width is None else flat_width)
+        fh = int(height if flat_height is None else flat_height)
+        d = None if dark is None else np.ascontiguousarray(dark, dtype=np.float32).reshape(-1)
+        f = None if flat is None else np.ascontiguousarray(flat, dtype=np.float32).reshape(-1)
+        assert d is None or d.size == int(width) * int(height)
+        assert f is None or f.size == fw * fh
+        c = self._lib.nl_calib_create(int(device), None if d is None else capi.fptr(d), int(width), int(height),
+                                      None if f is None else capi.fptr(f), fw, fh)
+        if not c:
+            msg = capi.last_error()
+            raise capi.NlError(capi.ERR_NO_DEVICE if "no HIP device" in msg else capi.ERR_INVALID_ARG, msg)
+        self._c = c
+        self.device, self.width, self.height = int(device), int(width), int(height)
+
+    @property
+    def flat_max(self):
+        """FlatFrame.Stats.Max() as taken when the masters were set."""
+        out = C.c_float()
+        capi.check(self._lib.nl_calib_flat_max(self._c, C.byref(out)))
+        return np.float32(out.value)
+
+    def close(self):
+        if self._c:
+            self._lib.nl_calib_destroy(self._c)
+            self._c = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def preprocess_frame(frame, width, height, calib=None, sigma_low=3.0, sigma_high=5.0, frame_id=0, device=None):
+    """OpCalibrate then OpBadPixel (mono) on one host frame, on calib's device (else `device`, default 0).
+    Returns (out, removed, (diff_mean, diff_std))."""
+    frame = np.ascontiguousarray(frame, dtype=np.float32).reshape(-1)
+    assert frame.size == int(width) * int(height)
+    if device is None:
+        device = calib.device if calib is not None else 0
+    out = np.empty_like(frame)
+    removed, stats = C.c_int64(0), (C.c_float * 2)()
+    lib = capi.load()
+    capi.check(lib.nl_preprocess_frame(None if calib is None else calib._c, int(frame_id), capi.fptr(frame),
+                                       capi.fptr(out), int(width), int(height), float(sigma_low), float(sigma_high),
+                                       C.byref(removed), stats, int(device)))
+    return out, int(removed.value), (np.float32(stats[0]), np.float32(stats[1]))
 
 
 def median_filter_3x3(image, width, height, device=0):
