@@ -454,6 +454,46 @@ int nl_stack_frame_calibrate(nl_stack_t *h, int idx, const nl_calib_t *c);
 int nl_stack_frame_badpixel(nl_stack_t *h, int idx, float sigma_low, float sigma_high,
                             int64_t *removed_out, float *diff_stats_out);
 
+/* ---- OpBadPixel, Bayer branch, and OpDebayer (internal/ops/pre/preprocess.go:180-251) ----
+ * The colour-camera front of the `stack -debayer R|G|B -cfa ...` command: OpCalibrate, then
+ * CosmeticCorrectionBayer (badpixels_bayer.go:26-351) on the chosen channel's pixels, then
+ * DebayerBilinear (debayer.go:41-263) to one interpolated plane of (width - xOff) &~ 1 by
+ * (height - yOff) &~ 1.  Bit-exact, the delta mean / std included.  CFA "RGGB" / "GRBG" / "GBRG" /
+ * "BGGR" (or lower case), channel "R" / "G" / "B" (or lower case); the CFA is checked first.  Errors
+ * are the reference's: "Unknown CFA value <cfa>", "Unknown debayering value <channel>".  A debayered
+ * shape of 0 pixels fails with NL_ERR_INVALID_ARG (the reference divides by zero): the one deviation.
+ *
+ * nl_debayer_shape: the shape OpDebayer.Apply gives a width x height frame (preprocess.go:239-251,
+ * debayer.go:26-66).  Host only, needs no device.  channel or cfa "" (or NULL): no debayer, the shape
+ * is unchanged. */
+int nl_debayer_shape(int width, int height, const char *channel, const char *cfa, int *out_width,
+                     int *out_height);
+/* OpCalibrate.Apply, OpBadPixel.Apply, OpDebayer.Apply (preprocess.go:68-99, 180-251) on one host
+ * frame, one device round trip.  out_host holds nl_debayer_shape(width, height, channel, cfa) pixels;
+ * *out_width / *out_height receive that shape.  Every branch of the operators applies:
+ * sigma_low == 0 || sigma_high == 0: no bad-pixel step; channel "": the mono branch, and the result is
+ * exactly nl_preprocess_frame's (its negative-sigma rejection included); channel set: the Bayer branch
+ * (a negative sigma is well defined there and accepted), which needs a valid CFA even when OpDebayer
+ * would not run; cfa "": no debayer.  removed_out: numRemoved (or the mono bad-pixel count);
+ * stats_out[2]: mean and std of data - median over the channel (the Bayer branch leaves the image's
+ * MedianDiffStats unset), the mono MedianDiffStats on the mono branch, NaN when no step ran.
+ * Calibration errors as nl_preprocess_frame.  Safe to call from several host threads sharing c. */
+int nl_preprocess_frame_cfa(const nl_calib_t *c, int frame_id, const float *in_host, int width,
+                            int height, const char *channel, const char *cfa, float sigma_low,
+                            float sigma_high, float *out_host, int *out_width, int *out_height,
+                            int64_t *removed_out, float *stats_out, int device);
+/* The same into resident slot idx: the raw mosaic goes to per-handle scratch (allocated on first use,
+ * freed by nl_stack_destroy), is calibrated (c may be NULL; the slot index is the frame id of the error
+ * strings) and corrected there, and the debayered plane is written into the slot at the handle's frame
+ * stride: it never crosses PCIe.  Needs a whole-image handle whose shape is nl_debayer_shape(raw_width,
+ * raw_height, channel, cfa) and a non-empty channel and CFA; anything else fails with
+ * NL_ERR_INVALID_ARG (mono frames take nl_stack_upload_tile + nl_stack_frame_calibrate +
+ * nl_stack_frame_badpixel).  The only device-to-host copy is removed_out / stats_out at the end. */
+int nl_stack_upload_frame_cfa(nl_stack_t *h, int idx, const float *raw_host, int raw_width,
+                              int raw_height, const nl_calib_t *c, const char *channel,
+                              const char *cfa, float sigma_low, float sigma_high,
+                              int64_t *removed_out, float *stats_out);
+
 /* ---- host-side operator mirror (nightlight_amd/host/, C++) ----
  * The reference's stack operator decoded from its JSON form and run through
  * MakePromises/Apply exactly as OpSequence would drive it

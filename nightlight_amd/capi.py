@@ -54,6 +54,7 @@ EXPORTS = [
     "nl_host_op_stack_batches_apply_json",
     "nl_calib_create", "nl_calib_destroy", "nl_calib_flat_max", "nl_preprocess_frame",
     "nl_stack_frame_calibrate", "nl_stack_frame_badpixel",
+    "nl_debayer_shape", "nl_preprocess_frame_cfa", "nl_stack_upload_frame_cfa",
 ]
 
 
@@ -222,6 +223,11 @@ def open_library(path):
                                       _f32p, C.c_int]
     L.nl_stack_frame_calibrate.argtypes = [vp, C.c_int, vp]
     L.nl_stack_frame_badpixel.argtypes = [vp, C.c_int, C.c_float, C.c_float, _i64p, _f32p]
+    L.nl_debayer_shape.argtypes = [C.c_int, C.c_int, C.c_char_p, C.c_char_p, _intp, _intp]
+    L.nl_preprocess_frame_cfa.argtypes = [vp, C.c_int, _f32p, C.c_int, C.c_int, C.c_char_p, C.c_char_p, C.c_float,
+                                          C.c_float, _f32p, _intp, _intp, _i64p, _f32p, C.c_int]
+    L.nl_stack_upload_frame_cfa.argtypes = [vp, C.c_int, _f32p, C.c_int, C.c_int, vp, C.c_char_p, C.c_char_p,
+                                            C.c_float, C.c_float, _i64p, _f32p]
     return L
 
 

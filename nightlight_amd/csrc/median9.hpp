@@ -34,4 +34,33 @@ __device__ __forceinline__ float median9(float a0, float a1, float a2, float a3,
 #undef NL_MAXTO
 #undef NL_MINTO
 
+// The same network with the reference's own steps, `if a[i] > a[j] { ... }` (median3x3.go:85-110): also exact where a
+// NaN or a +0 / -0 tie takes part (a false comparison leaves both in place; fminf / fmaxf would pick one).
+#define NL_CE(i, j) { const bool g_ = a##i > a##j; const float lo_ = g_ ? a##j : a##i; a##j = g_ ? a##i : a##j; a##i = lo_; }
+#define NL_MAXTO(i, j) { if (a##i > a##j) a##j = a##i; }
+#define NL_MINTO(i, j) { if (a##i > a##j) a##i = a##j; }
+
+__device__ __forceinline__ float median9_cmp(float a0, float a1, float a2, float a3, float a4, float a5,
+                                             float a6, float a7, float a8)
+{
+    NL_CE(0, 1) NL_CE(3, 4) NL_CE(6, 7)
+    NL_CE(1, 2) NL_CE(4, 5) NL_CE(7, 8)
+    NL_CE(0, 1) NL_CE(3, 4) NL_CE(6, 7)
+    NL_MAXTO(0, 3)
+    NL_MAXTO(3, 6)
+    NL_CE(1, 4)
+    NL_MINTO(4, 7)
+    NL_MAXTO(1, 4)
+    NL_MINTO(5, 8)
+    NL_MINTO(2, 5)
+    NL_CE(2, 4)
+    NL_MINTO(4, 6)
+    NL_MAXTO(2, 4)
+    return a4;
+}
+
+#undef NL_CE
+#undef NL_MAXTO
+#undef NL_MINTO
+
 }  // namespace nl

@@ -14,6 +14,7 @@
 #include <thread>
 #include <vector>
 
+#include "bayer.hpp"
 #include "preprocess.hpp"
 #include "stack_kernels.h"
 
@@ -458,6 +459,10 @@ struct nl_stack {
     unsigned *d_bp_seg = nullptr;
     unsigned *d_bp_list = nullptr;
     unsigned *d_bp_small = nullptr;
+    // colour-camera front (nl_stack_upload_frame_cfa), lazily allocated and grown: the raw mosaic, the compact
+    // delta / median of one channel, row sums, per-workgroup counts, nl::BayerParams
+    void *d_cfa = nullptr;
+    size_t cfa_bytes = 0;
     int max_grid = 0;
     int last_mode = -1;
     bool last_has_counters = false;
@@ -592,6 +597,7 @@ static int destroy_impl(nl_stack_t *h)
     cached_free(h->d_bp_seg, sizeof(unsigned) * (size_t)nl::bp_blocks(h->npix) * nl::kBpChunk, h->device);
     cached_free(h->d_bp_list, sizeof(unsigned) * (size_t)h->npix, h->device);
     if (h->d_bp_small) (void)hipFree(h->d_bp_small);
+    if (h->d_cfa) (void)hipFree(h->d_cfa);
     if (h->copy_stream) (void)hipStreamSynchronize(h->copy_stream);
     for (int i = 0; i < kStageSlots; i++) {
         pinned_free(h->h_stage[i], h->stage_cap[i]);
@@ -2406,4 +2412,173 @@ int nl_preprocess_frame(const nl_calib_t *c, int frame_id, const float *in_host,
     return rc;
 }
 
+// ---- OpBadPixel, Bayer branch, and OpDebayer (internal/ops/pre/preprocess.go:180-251; kernels in bayer.hip) -------
+
+// getOffsets (debayer.go:26-37)
+static int cfa_offsets(const char *cfa, int *xo, int *yo)
+{
+    const std::string c = cfa;
+    if (c == "RGGB" || c == "rggb") { *xo = 0; *yo = 0; }
+    else if (c == "GRBG" || c == "grbg") { *xo = 1; *yo = 0; }
+    else if (c == "GBRG" || c == "gbrg") { *xo = 0; *yo = 1; }
+    else if (c == "BGGR" || c == "bggr") { *xo = 1; *yo = 1; }
+    else return fail(NL_ERR_INVALID_ARG, "Unknown CFA value %s", cfa);
+    return NL_OK;
+}
+
+// the channel switch of CosmeticCorrectionBayer / DebayerBilinear (badpixels_bayer.go:36-45, debayer.go:47-59)
+static int cfa_channel(const char *channel, int *ch)
+{
+    const std::string c = channel;
+    if (c == "R" || c == "r") *ch = nl::kBayerR;
+    else if (c == "G" || c == "g") *ch = nl::kBayerG;
+    else if (c == "B" || c == "b") *ch = nl::kBayerB;
+    else return fail(NL_ERR_INVALID_ARG, "Unknown debayering value %s", channel);
+    return NL_OK;
+}
+
+// the CFA, then the channel, as the reference checks them; the output shape of DebayerBilinear (debayer.go:65-66)
+static int cfa_parse(const char *channel, const char *cfa, int width, int height, int *ch, int *xo, int *yo,
+                     int *out_w, int *out_h)
+{
+    int rc = cfa_offsets(cfa, xo, yo);
+    if (rc == NL_OK) rc = cfa_channel(channel, ch);
+    if (rc != NL_OK) return rc;
+    *out_w = (width - *xo) & ~1;
+    *out_h = (height - *yo) & ~1;
+    if ((int64_t)*out_w * *out_h == 0)        // (the reference divides by the width 0 at preprocess.go:245)
+        return fail(NL_ERR_INVALID_ARG, "debayer: %dx%d mosaic with cfa %s gives an empty %dx%d image", width, height,
+                    cfa, *out_w, *out_h);
+    return NL_OK;
+}
+
+int nl_debayer_shape(int width, int height, const char *channel, const char *cfa, int *out_width, int *out_height)
+{
+    if (width < 1 || height < 1 || !out_width || !out_height)
+        return fail(NL_ERR_INVALID_ARG, "debayer_shape: bad argument");
+    if (!channel || !cfa || !*channel || !*cfa) {            // OpDebayer.Apply is a no-op (preprocess.go:240-242)
+        *out_width = width;
+        *out_height = height;
+        return NL_OK;
+    }
+    int ch, xo, yo;
+    return cfa_parse(channel, cfa, width, height, &ch, &xo, &yo, out_width, out_height);
+}
+
+static size_t cfa_align(size_t b) { return (b + 255) & ~(size_t)255; }
+
+int nl_stack_upload_frame_cfa(nl_stack_t *h, int idx, const float *raw_host, int raw_width, int raw_height,
+                              const nl_calib_t *c, const char *channel, const char *cfa, float sigma_low,
+                              float sigma_high, int64_t *removed_out, float *stats_out)
+{
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(NL_ERR_NO_DEVICE, "no HIP device available; libnlstack has no CPU path");
+    NL_CHECK_HANDLE(h);
+    NL_SETTLE_UPLOADS(h);
+    if (idx < 0 || idx >= h->n_frames || !raw_host || raw_width < 1 || raw_height < 1)
+        return fail(NL_ERR_INVALID_ARG, "upload_frame_cfa: bad index %d, null frame or bad raw size %dx%d", idx,
+                    raw_width, raw_height);
+    if (!channel || !cfa || !*channel || !*cfa)
+        return fail(NL_ERR_INVALID_ARG, "upload_frame_cfa needs a channel and a CFA (mono frames: nl_stack_upload_tile, "
+                    "nl_stack_frame_calibrate, nl_stack_frame_badpixel)");
+    int ch, xo, yo, out_w, out_h;
+    int rc = cfa_parse(channel, cfa, raw_width, raw_height, &ch, &xo, &yo, &out_w, &out_h);
+    if (rc != NL_OK) return rc;
+    if (h->row0 != 0 || h->rows != h->height)
+        return fail(NL_ERR_INVALID_ARG, "upload_frame_cfa needs a whole-image handle (3x3 stencil, whole-frame std)");
+    if (h->width != out_w || h->height != out_h)
+        return fail(NL_ERR_INVALID_ARG, "upload_frame_cfa: a %dx%d mosaic debayers to %dx%d, the handle is %dx%d",
+                    raw_width, raw_height, out_w, out_h, h->width, h->height);
+    const int64_t n = (int64_t)raw_width * raw_height;
+    if (n >= ((int64_t)1 << 31)) return fail(NL_ERR_INVALID_ARG, "upload_frame_cfa: mosaic of 2^31 pixels or more");
+    if (c) {
+        if (c->device != h->device)
+            return fail(NL_ERR_INVALID_ARG, "upload_frame_cfa: calibration on device %d, handle on device %d",
+                        c->device, h->device);
+        if ((rc = calib_check_light(c, idx, raw_width, raw_height)) != NL_OK) return rc;
+    }
+    const nl::BayerGeom g = nl::bayer_geom(raw_width, raw_height, ch, xo, yo);
+    const size_t compact = cfa_align(sizeof(float) * (size_t)g.rows * g.cstride);
+    const size_t o_delta = cfa_align(sizeof(float) * (size_t)n), o_median = o_delta + compact;
+    const size_t o_rowsum = o_median + compact, o_removed = o_rowsum + cfa_align(sizeof(float) * (size_t)g.rows);
+    const size_t o_params = o_removed + cfa_align(sizeof(unsigned) * (size_t)nl::bayer_replace_blocks(g));
+    const size_t bytes = o_params + sizeof(nl::BayerParams);
+    if (bytes > h->cfa_bytes) {
+        if (h->d_cfa) {
+            NL_HIP(hipStreamSynchronize(h->stream));
+            (void)hipFree(h->d_cfa);
+            h->d_cfa = nullptr;
+            h->cfa_bytes = 0;
+        }
+        NL_HIP(dev_malloc(&h->d_cfa, bytes));
+        h->cfa_bytes = bytes;
+    }
+    char *base = static_cast<char *>(h->d_cfa);
+    float *raw = reinterpret_cast<float *>(base);
+    NL_HIP(hipMemcpyAsync(raw, raw_host, sizeof(float) * (size_t)n, hipMemcpyHostToDevice, h->stream));
+    if (c)
+        NL_HIP(nl::launch_calibrate(raw, raw, n, c->d_dark, c->d_flat, c->flat_max, h->stream));
+    const bool correct = sigma_low != 0.0f && sigma_high != 0.0f;     // preprocess.go:181-183
+    nl::BayerScratch s;
+    s.delta = reinterpret_cast<float *>(base + o_delta);
+    s.median = reinterpret_cast<float *>(base + o_median);
+    s.rowsum = reinterpret_cast<float *>(base + o_rowsum);
+    s.removed = reinterpret_cast<unsigned *>(base + o_removed);
+    s.params = reinterpret_cast<nl::BayerParams *>(base + o_params);
+    if (correct) NL_HIP(nl::launch_bayer_correct(raw, g, sigma_low, sigma_high, s, h->stream));
+    NL_HIP(nl::launch_debayer(raw, raw_width, raw_height, ch, xo, yo, h->d_frames + (int64_t)idx * h->fstride,
+                              h->width, h->stream));
+    nl::BayerParams p;
+    p.mean = p.std = NAN;
+    p.removed = 0;
+    if (correct) NL_HIP(hipMemcpyAsync(&p, s.params, sizeof p, hipMemcpyDeviceToHost, h->stream));
+    NL_HIP(hipStreamSynchronize(h->stream));   // (raw_host must not be retained)
+    if (removed_out) *removed_out = (int64_t)p.removed;
+    if (stats_out) { stats_out[0] = p.mean; stats_out[1] = p.std; }
+    return NL_OK;
+}
+
+int nl_preprocess_frame_cfa(const nl_calib_t *c, int frame_id, const float *in_host, int width, int height,
+                            const char *channel, const char *cfa, float sigma_low, float sigma_high, float *out_host,
+                            int *out_width, int *out_height, int64_t *removed_out, float *stats_out, int device)
+{
+    if (!in_host || !out_host || width < 1 || height < 1)
+        return fail(NL_ERR_INVALID_ARG, "preprocess_frame_cfa: bad argument");
+    int rc = select_device(device);
+    if (rc != NL_OK) return rc;
+    if (c && c->device != device)
+        return fail(NL_ERR_INVALID_ARG, "preprocess_frame_cfa: calibration on device %d, frame on device %d",
+                    c->device, device);
+    if (c && (rc = calib_check_light(c, frame_id, width, height)) != NL_OK) return rc;        // OpCalibrate first
+    const char *chan = channel ? channel : "", *pattern = cfa ? cfa : "";
+    const bool correct = sigma_low != 0.0f && sigma_high != 0.0f;
+    int ch, xo, yo, ow = width, oh = height;
+    if (*chan && correct && (rc = cfa_parse(chan, pattern, width, height, &ch, &xo, &yo, &ow, &oh)) != NL_OK)
+        return rc;                                              // OpBadPixel's Bayer branch: CFA, then channel
+    if (!*chan || !*pattern) {
+        // the mono branch of OpBadPixel (or none) and no OpDebayer: nl_preprocess_frame's result
+        if (out_width) *out_width = width;
+        if (out_height) *out_height = height;
+        return nl_preprocess_frame(c, frame_id, in_host, out_host, width, height, *chan ? 0.0f : sigma_low,
+                                   *chan ? 0.0f : sigma_high, removed_out, stats_out, device);
+    }
+    if ((rc = cfa_parse(chan, pattern, width, height, &ch, &xo, &yo, &ow, &oh)) != NL_OK) return rc;   // OpDebayer
+    // a one-frame handle of the debayered shape per call carries stream and scratch: concurrent calls share only c
+    nl_stack_t *h = nl_stack_create(1, ow, oh, 0, oh, device);
+    if (!h) return NL_ERR_HIP;
+    rc = nl_stack_upload_frame_cfa(h, 0, in_host, width, height, c, chan, pattern, sigma_low, sigma_high, removed_out,
+                                   stats_out);
+    if (rc == NL_OK) rc = nl_stack_download_tile(h, 0, out_host);
+    if (rc == NL_OK) {
+        if (out_width) *out_width = ow;
+        if (out_height) *out_height = oh;
+    }
+    std::string keep = g_err;
+    nl_stack_destroy(h);
+    g_err = keep;
+    return rc;
+}
+
 }  // extern "C"
+

@@ -335,6 +335,20 @@ class StackHandle:
                                                      C.byref(removed), stats))
         return int(removed.value), (np.float32(stats[0]), np.float32(stats[1]))
 
+    def upload_frame_cfa(self, idx, raw, raw_width, raw_height, channel, cfa="RGGB", calib=None, sigma_low=3.0,
+                         sigma_high=5.0):
+        """OpCalibrate, OpBadPixel (Bayer branch) and OpDebayer of a raw raw_width x raw_height mosaic into
+        resident slot idx of a whole-image handle of the debayered shape (debayer_shape).
+        Returns (removed, (delta_mean, delta_std))."""
+        raw = np.ascontiguousarray(raw, dtype=np.float32).reshape(-1)
+        assert raw.size == int(raw_width) * int(raw_height)
+        removed, stats = C.c_int64(0), (C.c_float * 2)()
+        capi.check(self._lib.nl_stack_upload_frame_cfa(self._h, int(idx), capi.fptr(raw), int(raw_width),
+                                                       int(raw_height), None if calib is None else calib._c,
+                                                       _cstr(channel), _cstr(cfa), float(sigma_low),
+                                                       float(sigma_high), C.byref(removed), stats))
+        return int(removed.value), (np.float32(stats[0]), np.float32(stats[1]))
+
     def download_result_fits(self):
         raw = np.empty(self.tile_pixels * 4, np.uint8)
         capi.check(self._lib.nl_stack_download_result_fits(self._h, raw.ctypes.data_as(C.c_void_p)))
@@ -573,6 +587,41 @@ def preprocess_frame(frame, width, height, calib=None, sigma_low=3.0, sigma_high
                                        capi.fptr(out), int(width), int(height), float(sigma_low), float(sigma_high),
                                        C.byref(removed), stats, int(device)))
     return out, int(removed.value), (np.float32(stats[0]), np.float32(stats[1]))
+
+
+def _cstr(s):
+    return (s or "").encode("utf-8")
+
+
+def debayer_shape(width, height, channel, cfa):
+    """The (width, height) OpDebayer gives a frame: unchanged when channel or cfa is "" (host only)."""
+    w, h = C.c_int(0), C.c_int(0)
+    capi.check(capi.load().nl_debayer_shape(int(width), int(height), _cstr(channel), _cstr(cfa), C.byref(w),
+                                            C.byref(h)))
+    return int(w.value), int(h.value)
+
+
+def preprocess_frame_cfa(frame, width, height, channel, cfa="RGGB", calib=None, sigma_low=3.0, sigma_high=5.0,
+                         frame_id=0, device=None):
+    """OpCalibrate, OpBadPixel and OpDebayer on one host frame, on calib's device (else `device`, default 0).
+    Returns (out, out_width, out_height, removed, (mean, std)): the Bayer branch's delta statistics, or the mono
+    MedianDiffStats when channel is ""."""
+    frame = np.ascontiguousarray(frame, dtype=np.float32).reshape(-1)
+    assert frame.size == int(width) * int(height)
+    if device is None:
+        device = calib.device if calib is not None else 0
+    lib = capi.load()
+    ow, oh = C.c_int(0), C.c_int(0)
+    # (an unknown CFA or channel is reported by the entry point itself, in the reference's order)
+    rc = lib.nl_debayer_shape(int(width), int(height), _cstr(channel), _cstr(cfa), C.byref(ow), C.byref(oh))
+    out = np.empty(max(ow.value * oh.value, 1) if rc == capi.OK else 1, np.float32)
+    removed, stats = C.c_int64(0), (C.c_float * 2)()
+    capi.check(lib.nl_preprocess_frame_cfa(None if calib is None else calib._c, int(frame_id), capi.fptr(frame),
+                                           int(width), int(height), _cstr(channel), _cstr(cfa), float(sigma_low),
+                                           float(sigma_high), capi.fptr(out), C.byref(ow), C.byref(oh),
+                                           C.byref(removed), stats, int(device)))
+    return (out[:ow.value * oh.value], int(ow.value), int(oh.value), int(removed.value),
+            (np.float32(stats[0]), np.float32(stats[1])))
 
 
 def median_filter_3x3(image, width, height, device=0):
