@@ -297,6 +297,60 @@ __device__ __forceinline__ void pick_pair(const float (&v)[NS], int idx, float &
     lower = lo;
 }
 
+// ---- branch-free lookups for the zonal clipping pass (no compare -> mask -> select chain through VCC) ----
+constexpr int ilog2_ceil(int n) { return n <= 1 ? 0 : 1 + ilog2_ceil((n + 1) / 2); }
+constexpr int ilog2_exact(int n) { return (1 << ilog2_ceil(n)) == n ? ilog2_ceil(n) : -1; }
+
+// mux_tree<NB, LO>(bit, leaf): leaf(BASE + sum of the selected bits' weights), over bits [LO, LO+NB) of a
+// per-lane index given as lane masks (bit[i] has weight 2^i): a tree of 2^NB - 1 selects whose root is bit LO,
+// whose leaves are bit LO+NB-1 -- the selects on the higher bits do not wait for the lower ones.
+template <int NB, int LO, int BASE = 0, int M, class F>
+__device__ __forceinline__ float mux_tree(const bool (&bit)[M], F &&leaf)
+{
+    if constexpr (NB == 0) {
+        return leaf(std::integral_constant<int, BASE>{});
+    } else {
+        const float hi = mux_tree<NB - 1, LO + 1, BASE + (1 << LO)>(bit, leaf);
+        const float lo = mux_tree<NB - 1, LO + 1, BASE>(bit, leaf);
+        return bit[LO] ? hi : lo;
+    }
+}
+
+// the bits of idx in [0, 2^M) as lane masks (the top one as a compare: one instruction instead of two)
+template <int M>
+__device__ __forceinline__ void index_bits(int idx, bool (&bit)[M])
+{
+    static_range<0, M>([&](auto I) NL_INL {
+        constexpr int i = decltype(I)::value;
+        bit[i] = i == M - 1 ? idx >= (1 << i) : (idx & (1 << i)) != 0;
+    });
+}
+
+// Rank of a threshold in a sorted zone of Z = 2^M values, as a branch-free binary search.  z(j) (j in [0, Z)) is
+// the zone in the order in which pred holds for a prefix (pred(x): x < t on an ascending zone, x > t on a
+// descending one).  Returns r = #{j < Z-1 : pred(z(j))} in [0, Z-1] -- M compares, each on a candidate selected by
+// the masks already known (step l: 2^l - 1 selects) -- and sets full = pred(z(Z-1)) (then r = Z-1 and the true count
+// is Z) and last = z(r-1), the last value for which pred holds (meaningless for r = 0).
+template <int M, class Z, class P>
+__device__ __forceinline__ int zone_rank(Z &&z, P &&pred, bool &full, float &last)
+{
+    bool bit[M];
+    float lst = 0.0f;
+    int r = 0;
+    static_range<0, M>([&](auto L) NL_INL {
+        constexpr int l = decltype(L)::value;
+        // candidate z(BASE + 2^(M-1-l) - 1), BASE = the bits M-1 ... M-l decided so far
+        const float x = mux_tree<l, M - l>(bit, [&](auto B) NL_INL { return z(std::integral_constant<int, decltype(B)::value + (1 << (M - 1 - l)) - 1>{}); });
+        const bool hit = pred(x);
+        bit[M - 1 - l] = hit;
+        lst = hit ? x : lst;
+        r += hit ? (1 << (M - 1 - l)) : 0;
+    });
+    full = pred(z(std::integral_constant<int, (1 << M) - 1>{}));
+    last = lst;
+    return r;
+}
+
 // min / max as the instructions themselves: fminf / fmaxf put a canonicalising v_max_f32 x, x, x
 // in front of every operand that comes out of the (asm) sorting network.  No NaN reaches these.
 __device__ __forceinline__ float max_raw(float a, float b)

@@ -182,6 +182,35 @@ void stack_sigma_fast_kernel(StackArgs p, FastArgs q)
             d_mid = (d0 + d1) + (d2 + d3);
             q_mid = (q0 + q1) + (q2 + q3);
         }
+        // Zonal plain sigma (ZT): the zones' shares of D and Q for every pair (a, b) a pass can meet, built once here
+        // and looked up by a and NS - b in each pass (round 7; they were re-summed under rank masks every pass).  Low
+        // zone: suffix sums from ZL-1 down to a; high zone: prefix sums from ZH up to b-1 -- running sums over the
+        // same positions as the masked sums they replace (DESIGN.md section 5 "Guard": every zone term still passes
+        // through at most ZL resp. NS-ZH additions).  Entries below lo_pads hold -Inf padding and are never read.
+        constexpr bool ZT = ZONAL && !WINSOR;
+        constexpr int ZHW = NS - ZH;                                     // high zone width (KZ + KP)
+        constexpr int ML = ZT ? ilog2_exact(ZL) : 0, MH = ZT ? ilog2_exact(ZHW) : 0;
+        float tdl[ZT ? ZL : 1], tql[ZT ? ZL : 1], tdh[ZT ? ZHW : 1], tqh[ZT ? ZHW : 1];
+        if constexpr (ZT) {
+            float sd = 0.0f, sq = 0.0f;
+            static_range<0, ZL>([&](auto K) NL_INL {
+                constexpr int k = ZL - 1 - decltype(K)::value;
+                const float e = v[k] - c;
+                sd += e;
+                sq = __builtin_fmaf(e, e, sq);
+                tdl[k] = sd;                                             // sum over [k, ZL)
+                tql[k] = sq;
+            });
+            sd = 0.0f; sq = 0.0f;
+            static_range<ZH, NS>([&](auto K) NL_INL {
+                constexpr int k = decltype(K)::value;
+                const float e = v[k] - c;
+                sd += e;
+                sq = __builtin_fmaf(e, e, sq);
+                tdh[NS - 1 - k] = sd;                                    // sum over [ZH, b), b = k + 1: index NS - b
+                tqh[NS - 1 - k] = sq;
+            });
+        }
 
         // winsorization (stack.go:646-672) clamps at median -/+ 1.5 sigma: in the zonal
         // passes only sorted positions outside [WL, WH) are allowed to reach a clamp,
@@ -243,7 +272,16 @@ void stack_sigma_fast_kernel(StackArgs p, FastArgs q)
             const int cnt = b - a;
             const float fcnt = (float)cnt;
             float dz0 = 0.0f, dz1 = 0.0f, qz0 = 0.0f, qz1 = 0.0f;
-            if constexpr (ZONAL) {
+            if constexpr (ZT) {
+                // the zones' sums: two table lookups per side (a in [0, ZL), NS - b in [0, NS - ZH))
+                bool ba[ML], bb[MH];
+                index_bits(a, ba);
+                index_bits(NS - b, bb);
+                dz0 = mux_tree<ML, 0>(ba, [&](auto J) NL_INL { return tdl[decltype(J)::value]; });
+                qz0 = mux_tree<ML, 0>(ba, [&](auto J) NL_INL { return tql[decltype(J)::value]; });
+                dz1 = mux_tree<MH, 0>(bb, [&](auto J) NL_INL { return tdh[decltype(J)::value]; });
+                qz1 = mux_tree<MH, 0>(bb, [&](auto J) NL_INL { return tqh[decltype(J)::value]; });
+            } else if constexpr (ZONAL) {
                 static_range<0, ZL>([&](auto K) NL_INL {
                     constexpr int k = decltype(K)::value;
                     const float e = (k >= a) ? v[k] - cz : 0.0f;
@@ -297,14 +335,17 @@ void stack_sigma_fast_kernel(StackArgs p, FastArgs q)
             // ---- bracket the reference's stddev ----
             // ours: aa carries <= NS/4+8 roundings per term; bb = delta^2 with delta off by
             // <= (NS/4+7) u mean|e|, and 2|delta| mean|e| <= aa + bb: together <= (NS/2+17) u (aa+bb)
+            // (ZT: the zone tables are running sums over the same positions -- a zone term passes through at most ZL resp.
+            // NS-ZH additions there as under the rank masks, which only added exact zeros -- so the constant is unchanged)
 #ifdef NL_IEEE_PASS
             const float err_o = ((float)(NS / 2 + 24)) * kU * (aa + bb);
 #else
             const float err_o = ((float)(NS / 2 + 32)) * kU * (aa + bb);     // (+8: the reciprocal's ulp in delta, delta^2 and aa)
 #endif
             // reference: relative gamma_(n+3) on its variance, its mean off by <= e_m
-            const float eps_r = 1.02f * (fcnt + 8.0f) * kU;
-            const float e_m = 1.02f * (fcnt + 2.0f) * kU * amax;
+            // (the scaling by kU = 2^-24 is exact, so these are 1.02f * (fcnt + 8) * kU etc. bit for bit, one multiply fewer)
+            const float eps_r = (fcnt + 8.0f) * (1.02f * kU);
+            const float e_m = (fcnt + 2.0f) * (1.02f * kU) * amax;
             const float v_up = var + err_o;
             const float v_dn = fmaxf(var - err_o, 0.0f);
             const float v_hi = v_up + v_up * eps_r + e_m * e_m;
@@ -323,7 +364,17 @@ void stack_sigma_fast_kernel(StackArgs p, FastArgs q)
             // zonal: a in [0,ZL), b in (ZH,NS]  =>  kk in [ZH/2, ZL-1+NS/2]
             const int kk = a + (cnt >> 1);
             float upper, lower;
-            pick_pair<W0, W1>(v, kk, lower, upper);
+            if constexpr (ZT) {
+                // kk = floor((a + b) / 2) in [K0, K1] (a < ZL, b > ZH): a select tree on the bits of kk - K0
+                constexpr int K0 = (ZH + 1) / 2, K1 = (ZL - 1 + NS) / 2, MK = ilog2_ceil(K1 - K0 + 1);
+                static_assert(K0 - 1 >= W0 && K1 < W1, "the median window holds exact ranks");
+                bool bk[MK];
+                index_bits(kk - K0, bk);
+                upper = mux_tree<MK, 0>(bk, [&](auto J) NL_INL { constexpr int j = decltype(J)::value; return v[K0 + (j < K1 - K0 ? j : K1 - K0)]; });
+                lower = mux_tree<MK, 0>(bk, [&](auto J) NL_INL { constexpr int j = decltype(J)::value; return v[K0 - 1 + (j < K1 - K0 ? j : K1 - K0)]; });
+            } else {
+                pick_pair<W0, W1>(v, kk, lower, upper);
+            }
             const float median = (cnt & 1) ? upper : 0.5f * (lower + upper);
 
             // ---- the reference's bound expressions at both ends of an interval [smin, smax] of its stddev (stack.go:408-409;
@@ -331,13 +382,16 @@ void stack_sigma_fast_kernel(StackArgs p, FastArgs q)
             // column is sorted, so the samples below a threshold are a prefix and those above it a suffix (pads are
             // +Inf): counted over the whole zone without rank masks, minus what is already excluded ----
             float lo_min, lo_max, hi_min, hi_max;
-            auto clip_counts = [&](const float smin, const float smax, int &c1, int &c2, int &d1, int &d2) NL_INL {
+            auto thresholds = [&](const float smin, const float smax) NL_INL {
                 const float tl0 = __fmul_rn(p.sig_lo, smin), tl1 = __fmul_rn(p.sig_lo, smax);
                 const float th0 = __fmul_rn(p.sig_hi, smin), th1 = __fmul_rn(p.sig_hi, smax);
                 const float la = __fsub_rn(median, tl0), lb = __fsub_rn(median, tl1);
                 const float ha = __fadd_rn(median, th0), hb = __fadd_rn(median, th1);
                 lo_min = fminf(la, lb); lo_max = fmaxf(la, lb);
                 hi_min = fminf(ha, hb); hi_max = fmaxf(ha, hb);
+            };
+            auto clip_counts = [&](const float smin, const float smax, int &c1, int &c2, int &d1, int &d2) NL_INL {
+                thresholds(smin, smax);
                 c1 = 0; c2 = 0; d1 = 0; d2 = 0;
                 if constexpr (ZONAL) {
                     static_range<0, ZL>([&](auto K) NL_INL {
@@ -570,13 +624,66 @@ void stack_sigma_fast_kernel(StackArgs p, FastArgs q)
             }
 
             // ---- count certain clips (c1,d1) and possible clips (c2,d2) over the interval of the stddev ----
-            int c1, c2, d1, d2;
-            clip_counts(s_min, s_max, c1, c2, d1, d2);
+            int c1, d1;
+            bool overflow, undecided;                    // a zone would run empty / c1 != c2 or d1 != d2
+            if constexpr (ZT) {
+                // The zones are sorted, so each count is a rank: a branch-free binary search for lo_max in the low zone
+                // and for hi_min in the high zone read from the top, which also yields the last sample on the clipped
+                // side.  c1 = c2 unless a survivor lies in [lo_min, lo_max), i.e. unless the largest survivor below
+                // lo_max is not below lo_min (likewise d1, d2 with the smallest survivor above hi_min); the other two
+                // counts need no search of their own.  A zone that is clipped entirely is the overflow of old.
+                {
+                    // (thresholds(), with the minima / maxima as the instructions: the operands are results of arithmetic,
+                    // never signalling NaNs, so nothing needs canonicalising)
+                    const float la = __fsub_rn(median, __fmul_rn(p.sig_lo, s_min)), lb = __fsub_rn(median, __fmul_rn(p.sig_lo, s_max));
+                    const float ha = __fadd_rn(median, __fmul_rn(p.sig_hi, s_min)), hb = __fadd_rn(median, __fmul_rn(p.sig_hi, s_max));
+                    lo_min = min_raw(la, lb); lo_max = max_raw(la, lb);
+                    hi_min = min_raw(ha, hb); hi_max = max_raw(ha, hb);
+                }
+                const int u = NS - b;                    // dead positions at the top of the high zone
+                bool full_lo, full_hi;
+                float last_lo, last_hi;
+                const int r_lo = zone_rank<ML>([&](auto J) NL_INL { return v[decltype(J)::value]; },
+                                               [&](float x) NL_INL { return x < lo_max; }, full_lo, last_lo);
+                const int r_hi = zone_rank<MH>([&](auto J) NL_INL { return v[NS - 1 - decltype(J)::value]; },
+                                               [&](float x) NL_INL { return x > hi_min; }, full_hi, last_hi);
+                overflow = full_lo || full_hi;
+                c1 = max(r_lo - a, 0);
+                d1 = max(r_hi - u, 0);
+                undecided = (c1 > 0 && !(last_lo < lo_min)) || (d1 > 0 && !(last_hi > hi_max));
+            } else {
+                int c2, d2;
+                clip_counts(s_min, s_max, c1, c2, d1, d2);
+                overflow = ZONAL && ((a + c2 >= ZL) || (b - d2 <= ZH));
+                undecided = (c1 != c2) || (d1 != d2);
+            }
+            if constexpr (ZT) {
+                // the same decisions as below, as selects: no divergent branches, whose joins cost a register copy of
+                // every value the pass carries
+                const bool gen = active && overflow;
+                const bool exact = active && !overflow && (bail || undecided || (lo_max > hi_min && (c1 + d1) > 0));
+                const bool step = active && !gen && !exact;
+                if constexpr (RECORD) {
+                    if (step && rnd < kBoundRounds) p.bounds[(size_t)rnd * (size_t)p.npix + (size_t)pix] = make_float2(lo_max, hi_min);
+                    rnd += step ? 1 : 0;
+                }
+                c1 = step ? c1 : 0;                      // (the clip counters are a - lo_pads and lo_pads + n - b, see below)
+                d1 = step ? d1 : 0;
+                a += c1;
+                b -= d1;
+                amax = min_raw(amax, max_raw(fabsf(lo_min), fabsf(hi_max)));     // (only read while the lane is active)
+                const bool done = step && ((c1 + d1) == 0 || (b - a) <= 1);    // stack.go:427-430: mean BEFORE this pass
+                res = done ? m : res;
+                to_generic = to_generic || gen;
+                to_exact = to_exact || exact;
+                active = step && !done;
+                return;
+            }
             if constexpr (ZONAL) {
                 // the zones must still hold a survivor on each side, otherwise the
                 // next sorted position (outside the zone) might be clipped as well:
                 // such a lane restarts in the generic pass
-                if (active && ((a + c2 >= ZL) || (b - d2 <= ZH))) {
+                if (active && overflow) {
                     to_generic = true;
                     active = false;
                 }
@@ -584,7 +691,7 @@ void stack_sigma_fast_kernel(StackArgs p, FastArgs q)
             if (active) {
                 // a sample inside the window, or (negative sigma) inverted bounds where the
                 // reference's "low first" order matters: let the exact kernel decide
-                bail |= (c1 != c2) || (d1 != d2) || (lo_max > hi_min && (c1 + d1) > 0);
+                bail |= undecided || (lo_max > hi_min && (c1 + d1) > 0);
                 if (bail) {
                     to_exact = true;
                     active = false;
@@ -685,6 +792,10 @@ void stack_sigma_fast_kernel(StackArgs p, FastArgs q)
             const bool decided = on && !to_generic && !to_exact && n > 0 && rnd <= kBoundRounds;
             if (on) p.nrounds[pix] = (unsigned char)(decided ? rnd : 0);
         } else {
+            if constexpr (ZT) {
+                c_lo = a - lo_pads;
+                c_hi = lo_pads + n - b;
+            }
             flush();
         }
     }
