@@ -494,6 +494,56 @@ int nl_stack_upload_frame_cfa(nl_stack_t *h, int idx, const float *raw_host, int
                               const char *cfa, float sigma_low, float sigma_high,
                               int64_t *removed_out, float *stats_out);
 
+/* ---- OpStarDetect: star.FindStars (internal/star/findstars.go:59-103) ----
+ * Bit-exact: the star list, sumOfShifts and avgHFR are the reference's bits wherever the reference
+ * returns.  nl_star_t is star.Star (findstars.go:30-37): same field order and size, so a cgo caller can
+ * copy it straight into a []star.Star.
+ *
+ * location, scale: the caller's f.Stats.Location() / Scale(), as OpStarDetect.Apply passes them
+ * (pre/preprocess.go:448); this library does not estimate them.  diff_std: f.MedianDiffStats.StdDev()
+ * (nl_stack_frame_badpixel's diff_stats_out[1]); NaN means MedianDiffStats == nil.  At most capacity
+ * stars are written to stars_out; *n_stars always receives the full count.  sum_of_shifts, avg_hfr:
+ * FindStars' other two results (avg_hfr is NaN when no star is left, 0/0 as there).  n_stars,
+ * sum_of_shifts, avg_hfr may be NULL.  Without a device every entry fails with NL_ERR_NO_DEVICE.
+ * Deviations, all NL_ERR_INVALID_ARG unless stated:
+ *   1. diff_std NaN with bp_sigma > 0: the reference estimates the std from a random 1 % sample drawn with
+ *      an unseeded generator (findstars.go:139-149).  Here every pixel whose whole 3x3 mask lies inside
+ *      the data gives data[i] - MedianFloat32Slice9(gather), reduced by Stats.StdDev's arithmetic (fp64
+ *      sums, float32 mean and std); the candidate loop starts from a zeroed buffer as with given stats.
+ *   2. radius < 0 or radius > 1024 (radius 0 is well defined and finds no star).
+ *   3. +-Inf anywhere in the frame.
+ *   4. where the reference panics, with a message naming the site: a NaN Mass as the pivot of
+ *      QPartitionStarsDesc (qsort.go:37-57), and a star whose bin lies outside filterOutOverlaps' grid
+ *      (findstars.go:250-256: a NaN centroid after a NaN pixel in its window, or a centroid the 1-D wrap
+ *      pulled past the last cell row). */
+typedef struct nl_star {
+    int32_t index;                 /* int32(x) + width*int32(y) */
+    float value, x, y, mass, hfr;
+} nl_star_t;
+#ifdef __cplusplus
+static_assert(sizeof(nl_star_t) == 24, "nl_star_t is star.Star: 24 bytes");
+#else
+_Static_assert(sizeof(nl_star_t) == 24, "nl_star_t is star.Star: 24 bytes");
+#endif
+/* One host frame of width x height, one device round trip for the frame plus three short ones for the
+ * star lists.  Safe to call from several host threads at once (each call has a stream and scratch of its
+ * own). */
+int nl_find_stars(const float *data_host, int width, int height, float location, float scale,
+                  float star_sig, float bp_sigma, float star_in_out, int radius, float diff_std,
+                  nl_star_t *stars_out, int capacity, int *n_stars, float *sum_of_shifts,
+                  float *avg_hfr, int device);
+/* The same on resident slot idx, or on the last pass's result still on the device; both need a
+ * whole-image handle (FindStars indexes the data 1-D), and the result form a handle that has run a
+ * pass.  The frame never crosses PCIe. */
+int nl_stack_frame_find_stars(nl_stack_t *h, int idx, float location, float scale, float star_sig,
+                              float bp_sigma, float star_in_out, int radius, float diff_std,
+                              nl_star_t *stars_out, int capacity, int *n_stars, float *sum_of_shifts,
+                              float *avg_hfr);
+int nl_stack_result_find_stars(nl_stack_t *h, float location, float scale, float star_sig,
+                               float bp_sigma, float star_in_out, int radius, float diff_std,
+                               nl_star_t *stars_out, int capacity, int *n_stars, float *sum_of_shifts,
+                               float *avg_hfr);
+
 /* ---- host-side operator mirror (nightlight_amd/host/, C++) ----
  * The reference's stack operator decoded from its JSON form and run through
  * MakePromises/Apply exactly as OpSequence would drive it

@@ -55,7 +55,13 @@ EXPORTS = [
     "nl_calib_create", "nl_calib_destroy", "nl_calib_flat_max", "nl_preprocess_frame",
     "nl_stack_frame_calibrate", "nl_stack_frame_badpixel",
     "nl_debayer_shape", "nl_preprocess_frame_cfa", "nl_stack_upload_frame_cfa",
+    "nl_find_stars", "nl_stack_frame_find_stars", "nl_stack_result_find_stars",
 ]
+
+# nl_star_t = star.Star (findstars.go:30-37), 24 bytes
+STAR_DTYPE = np.dtype([("index", "<i4"), ("value", "<f4"), ("x", "<f4"), ("y", "<f4"), ("mass", "<f4"),
+                       ("hfr", "<f4")])
+assert STAR_DTYPE.itemsize == 24
 
 
 class NlError(RuntimeError):
@@ -228,6 +234,11 @@ def open_library(path):
                                           C.c_float, _f32p, _intp, _intp, _i64p, _f32p, C.c_int]
     L.nl_stack_upload_frame_cfa.argtypes = [vp, C.c_int, _f32p, C.c_int, C.c_int, vp, C.c_char_p, C.c_char_p,
                                             C.c_float, C.c_float, _i64p, _f32p]
+    _star_args = [C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_float, vp, C.c_int, _intp,
+                  _f32p, _f32p]
+    L.nl_find_stars.argtypes = [_f32p, C.c_int, C.c_int] + _star_args + [C.c_int]
+    L.nl_stack_frame_find_stars.argtypes = [vp, C.c_int] + _star_args
+    L.nl_stack_result_find_stars.argtypes = [vp] + _star_args
     return L
 
 

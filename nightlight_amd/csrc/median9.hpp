@@ -63,4 +63,33 @@ __device__ __forceinline__ float median9_cmp(float a0, float a1, float a2, float
 #undef NL_MAXTO
 #undef NL_MINTO
 
+// median9_cmp on a buffer, in place, as MedianFloat32Slice9 leaves it (median3x3.go:85-110): GatherAndMedian
+// (gather.go:26-38) reuses one 9-slot buffer, so where a mask leaves the data the slots it does not fill keep what the
+// network left there for the previous call (star detection's bad-pixel test, stars.hip).
+#define NL_CE(i, j) { const bool g_ = a[i] > a[j]; const float lo_ = g_ ? a[j] : a[i]; a[j] = g_ ? a[i] : a[j]; a[i] = lo_; }
+#define NL_MAXTO(i, j) { if (a[i] > a[j]) a[j] = a[i]; }
+#define NL_MINTO(i, j) { if (a[i] > a[j]) a[i] = a[j]; }
+
+__host__ __device__ inline float median9_cmp_buf(float (&a)[9])
+{
+    NL_CE(0, 1) NL_CE(3, 4) NL_CE(6, 7)
+    NL_CE(1, 2) NL_CE(4, 5) NL_CE(7, 8)
+    NL_CE(0, 1) NL_CE(3, 4) NL_CE(6, 7)
+    NL_MAXTO(0, 3)
+    NL_MAXTO(3, 6)
+    NL_CE(1, 4)
+    NL_MINTO(4, 7)
+    NL_MAXTO(1, 4)
+    NL_MINTO(5, 8)
+    NL_MINTO(2, 5)
+    NL_CE(2, 4)
+    NL_MINTO(4, 6)
+    NL_MAXTO(2, 4)
+    return a[4];
+}
+
+#undef NL_CE
+#undef NL_MAXTO
+#undef NL_MINTO
+
 }  // namespace nl

@@ -16,6 +16,7 @@
 
 #include "bayer.hpp"
 #include "preprocess.hpp"
+#include "stars.hpp"
 #include "stack_kernels.h"
 
 namespace {
@@ -463,6 +464,8 @@ struct nl_stack {
     // delta / median of one channel, row sums, per-workgroup counts, nl::BayerParams
     void *d_cfa = nullptr;
     size_t cfa_bytes = 0;
+    // star detection (nl_stack_frame_find_stars / nl_stack_result_find_stars), lazily allocated and grown
+    nl::StarWork star_work;
     int max_grid = 0;
     int last_mode = -1;
     bool last_has_counters = false;
@@ -598,6 +601,7 @@ static int destroy_impl(nl_stack_t *h)
     cached_free(h->d_bp_list, sizeof(unsigned) * (size_t)h->npix, h->device);
     if (h->d_bp_small) (void)hipFree(h->d_bp_small);
     if (h->d_cfa) (void)hipFree(h->d_cfa);
+    h->star_work.free();
     if (h->copy_stream) (void)hipStreamSynchronize(h->copy_stream);
     for (int i = 0; i < kStageSlots; i++) {
         pinned_free(h->h_stage[i], h->stage_cap[i]);
@@ -2406,6 +2410,77 @@ int nl_preprocess_frame(const nl_calib_t *c, int frame_id, const float *in_host,
     if (rc == NL_OK && c) rc = nl_stack_frame_calibrate(h, 0, c);
     if (rc == NL_OK) rc = nl_stack_frame_badpixel(h, 0, sigma_low, sigma_high, removed_out, diff_stats_out);
     if (rc == NL_OK) rc = nl_stack_download_tile(h, 0, out_host);
+    std::string keep = g_err;
+    nl_stack_destroy(h);
+    g_err = keep;
+    return rc;
+}
+
+// ---- OpStarDetect: star.FindStars (internal/star/findstars.go:59-103; kernels and host steps in stars.hip) ---------
+
+static int find_stars_impl(nl_stack_t *h, const float *d_data, const char *who, float location, float scale,
+                           float star_sig, float bp_sigma, float star_in_out, int radius, float diff_std,
+                           nl_star_t *stars_out, int capacity, int *n_stars, float *sum_of_shifts, float *avg_hfr)
+{
+    if (radius < 0 || radius > 1024)      // (deviation 2; radius 0 finds no star)
+        return fail(NL_ERR_INVALID_ARG, "%s: radius %d not in [0, 1024]", who, radius);
+    if (capacity < 0 || (capacity > 0 && !stars_out))
+        return fail(NL_ERR_INVALID_ARG, "%s: capacity %d with %s output", who, capacity, stars_out ? "an" : "no");
+    if (h->row0 != 0 || h->rows != h->height)
+        return fail(NL_ERR_INVALID_ARG, "%s needs a whole-image handle (FindStars indexes the data 1-D)", who);
+    if (h->npix >= ((int64_t)1 << 31)) return fail(NL_ERR_INVALID_ARG, "%s: frame of 2^31 pixels or more", who);
+    if (!h->d_stat_partial) NL_HIP(dev_malloc(&h->d_stat_partial, sizeof(double) * 3 * kStatBlocks));
+    const nl::StarParams p{location, scale, star_sig, bp_sigma, star_in_out, radius, diff_std};
+    std::vector<nl_star_t> stars;
+    float sum = 0.0f, avg = 0.0f;
+    std::string msg;
+    const int rc = nl::find_stars_run(d_data, h->width, h->height, p, h->star_work, h->d_stat_partial, kStatBlocks,
+                                      h->stream, stars, &sum, &avg, &msg);
+    if (rc != NL_OK) return fail(rc, "%s: %s", who, msg.c_str());
+    const size_t k = std::min(stars.size(), (size_t)capacity);
+    if (k) memcpy(stars_out, stars.data(), k * sizeof(nl_star_t));
+    if (n_stars) *n_stars = (int)stars.size();
+    if (sum_of_shifts) *sum_of_shifts = sum;
+    if (avg_hfr) *avg_hfr = avg;
+    return NL_OK;
+}
+
+int nl_stack_frame_find_stars(nl_stack_t *h, int idx, float location, float scale, float star_sig, float bp_sigma,
+                              float star_in_out, int radius, float diff_std, nl_star_t *stars_out, int capacity,
+                              int *n_stars, float *sum_of_shifts, float *avg_hfr)
+{
+    NL_CHECK_HANDLE(h);
+    NL_SETTLE_UPLOADS(h);
+    if (idx < 0 || idx >= h->n_frames) return fail(NL_ERR_INVALID_ARG, "frame_find_stars: bad index %d", idx);
+    return find_stars_impl(h, h->d_frames + (int64_t)idx * h->fstride, "frame_find_stars", location, scale, star_sig,
+                           bp_sigma, star_in_out, radius, diff_std, stars_out, capacity, n_stars, sum_of_shifts,
+                           avg_hfr);
+}
+
+int nl_stack_result_find_stars(nl_stack_t *h, float location, float scale, float star_sig, float bp_sigma,
+                               float star_in_out, int radius, float diff_std, nl_star_t *stars_out, int capacity,
+                               int *n_stars, float *sum_of_shifts, float *avg_hfr)
+{
+    NL_CHECK_HANDLE(h);
+    if (h->last_mode < 0) return fail(NL_ERR_INVALID_ARG, "result_find_stars: the handle has not run a pass");
+    return find_stars_impl(h, h->d_out, "result_find_stars", location, scale, star_sig, bp_sigma, star_in_out, radius,
+                           diff_std, stars_out, capacity, n_stars, sum_of_shifts, avg_hfr);
+}
+
+int nl_find_stars(const float *data_host, int width, int height, float location, float scale, float star_sig,
+                  float bp_sigma, float star_in_out, int radius, float diff_std, nl_star_t *stars_out, int capacity,
+                  int *n_stars, float *sum_of_shifts, float *avg_hfr, int device)
+{
+    if (!data_host || width < 1 || height < 1) return fail(NL_ERR_INVALID_ARG, "find_stars: bad argument");
+    int rc = select_device(device);
+    if (rc != NL_OK) return rc;
+    // a one-frame handle of its own per call carries stream and scratch: concurrent calls share nothing
+    nl_stack_t *h = nl_stack_create(1, width, height, 0, height, device);
+    if (!h) return NL_ERR_HIP;
+    rc = nl_stack_upload_tile(h, 0, data_host);
+    if (rc == NL_OK)
+        rc = find_stars_impl(h, h->d_frames, "find_stars", location, scale, star_sig, bp_sigma, star_in_out, radius,
+                             diff_std, stars_out, capacity, n_stars, sum_of_shifts, avg_hfr);
     std::string keep = g_err;
     nl_stack_destroy(h);
     g_err = keep;

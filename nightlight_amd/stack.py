@@ -349,6 +349,18 @@ class StackHandle:
                                                        float(sigma_high), C.byref(removed), stats))
         return int(removed.value), (np.float32(stats[0]), np.float32(stats[1]))
 
+    def frame_find_stars(self, idx, location, scale, star_sig=15.0, bp_sigma=5.0, star_in_out=1.4, radius=16,
+                         diff_std=None):
+        """star.FindStars on resident slot idx of a whole-image handle (see find_stars)."""
+        return _find_stars(lambda *a: self._lib.nl_stack_frame_find_stars(self._h, int(idx), *a), location, scale,
+                           star_sig, bp_sigma, star_in_out, radius, diff_std)
+
+    def result_find_stars(self, location, scale, star_sig=15.0, bp_sigma=5.0, star_in_out=1.4, radius=16,
+                          diff_std=None):
+        """star.FindStars on the last pass's result, still on the device (see find_stars)."""
+        return _find_stars(lambda *a: self._lib.nl_stack_result_find_stars(self._h, *a), location, scale, star_sig,
+                           bp_sigma, star_in_out, radius, diff_std)
+
     def download_result_fits(self):
         raw = np.empty(self.tile_pixels * 4, np.uint8)
         capi.check(self._lib.nl_stack_download_result_fits(self._h, raw.ctypes.data_as(C.c_void_p)))
@@ -587,6 +599,35 @@ def preprocess_frame(frame, width, height, calib=None, sigma_low=3.0, sigma_high
                                        capi.fptr(out), int(width), int(height), float(sigma_low), float(sigma_high),
                                        C.byref(removed), stats, int(device)))
     return out, int(removed.value), (np.float32(stats[0]), np.float32(stats[1]))
+
+
+def _find_stars(call, location, scale, star_sig, bp_sigma, star_in_out, radius, diff_std, capacity=16384):
+    """One nl_*find_stars call through `call(<parameters from location on>)`; retried once with the reported count
+    when `capacity` was short."""
+    args = (float(location), float(scale), float(star_sig), float(bp_sigma), float(star_in_out), int(radius),
+            float("nan") if diff_std is None else float(diff_std))
+    n, shifts, hfr = C.c_int(0), C.c_float(0.0), C.c_float(0.0)
+    for _ in range(2):
+        out = np.zeros(max(capacity, 1), capi.STAR_DTYPE)
+        capi.check(call(*args, out.ctypes.data_as(C.c_void_p), int(capacity), C.byref(n), C.byref(shifts),
+                        C.byref(hfr)))
+        if n.value <= capacity:
+            break
+        capacity = n.value
+    return out[:n.value].copy(), np.float32(shifts.value), np.float32(hfr.value)
+
+
+def find_stars(frame, width, height, location, scale, star_sig=15.0, bp_sigma=5.0, star_in_out=1.4, radius=16,
+               diff_std=None, device=None):
+    """star.FindStars (internal/star/findstars.go:59-103) on one host frame on `device` (default 0).
+    location / scale: the frame's Stats.Location() / Scale(); diff_std: MedianDiffStats.StdDev() or None (nil).
+    Returns (stars, sum_of_shifts, avg_hfr): stars a structured array with the fields index value x y mass hfr."""
+    frame = np.ascontiguousarray(frame, dtype=np.float32).reshape(-1)
+    assert frame.size == int(width) * int(height)
+    lib = capi.load()
+    return _find_stars(lambda *a: lib.nl_find_stars(capi.fptr(frame), int(width), int(height), *a,
+                                                    0 if device is None else int(device)),
+                       location, scale, star_sig, bp_sigma, star_in_out, radius, diff_std)
 
 
 def _cstr(s):
