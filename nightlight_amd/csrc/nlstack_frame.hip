@@ -1,0 +1,573 @@
+// nlstack_frame.hip -- steps on one frame resident in a handle, and their host forms: statistics and noise,
+// median filters, OpCalibrate / OpBadPixel, star detection, the colour-camera front.  Kernels in frame_stats.hip,
+// preprocess.hip, stars.hip and bayer.hip.
+#include <math.h>
+
+#include <algorithm>
+
+#include "bayer.hpp"
+#include "preprocess.hpp"
+#include "nlstack_internal.hpp"
+
+namespace {
+
+// the per-block {min, sum, max} partials of launch_min_sum_max folded from block 0 on: compared in fp32, summed in
+// fp64 in block order (the results are bit-exact against the reference)
+struct MinSumMax { float lo; double sum; float hi; };
+MinSumMax fold_min_sum_max(const std::vector<double> &part)
+{
+    MinSumMax f{(float)part[0], 0.0, (float)part[2]};
+    for (int b = 0; b < kStatBlocks; b++) {
+        const float bl = (float)part[3 * b], bh = (float)part[3 * b + 2];
+        if (bl < f.lo) f.lo = bl;
+        if (bh > f.hi) f.hi = bh;
+        f.sum += part[3 * b + 1];
+    }
+    return f;
+}
+
+// one whole frame through a filter kernel, launch(d_in, d_out), on `device`: buffers of its own, no handle
+template <class Launch>
+int median_filter_run(const char *who, const float *in_host, float *out_host, int64_t n, int device, Launch launch)
+{
+    int rc = select_device(device);
+    if (rc != NL_OK) return rc;
+    const size_t bytes = (size_t)n * sizeof(float);
+    float *d_in = nullptr, *d_out = nullptr;
+    NL_HIP(dev_malloc(&d_in, bytes));
+    hipError_t e = dev_malloc(&d_out, bytes);
+    if (e != hipSuccess) { (void)hipFree(d_in); return fail(NL_ERR_HIP, "hipMalloc: %s", hipGetErrorString(e)); }
+    do {
+        if ((e = hipMemcpy(d_in, in_host, bytes, hipMemcpyHostToDevice)) != hipSuccess) break;
+        if ((e = launch(d_in, d_out)) != hipSuccess) break;
+        if ((e = hipMemcpy(out_host, d_out, bytes, hipMemcpyDeviceToHost)) != hipSuccess) break;
+    } while (0);
+    (void)hipFree(d_in);
+    (void)hipFree(d_out);
+    if (e != hipSuccess) return fail(NL_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    return NL_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// ---- per-frame statistics ---------------------------------------------------
+
+static int frame_stats_impl(nl_stack_t *h, const float *d, int64_t n, float *mn, float *mean,
+                            float *mx, double *variance)
+{
+    std::vector<double> part(3 * kStatBlocks);
+    NL_HIP(nl::launch_min_sum_max(d, n, h->d_stat_partial, kStatBlocks, h->stream));
+    NL_HIP(hipMemcpyAsync(part.data(), h->d_stat_partial, sizeof(double) * 3 * kStatBlocks,
+                          hipMemcpyDeviceToHost, h->stream));
+    NL_HIP(hipStreamSynchronize(h->stream));
+    const MinSumMax f = fold_min_sum_max(part);
+    const float m = (float)(f.sum / (double)n);
+    if (mn) *mn = f.lo;
+    if (mx) *mx = f.hi;
+    if (mean) *mean = m;
+    if (variance) {
+        NL_HIP(nl::launch_variance(d, n, m, h->d_stat_partial, kStatBlocks, h->stream));
+        NL_HIP(hipMemcpyAsync(part.data(), h->d_stat_partial, sizeof(double) * kStatBlocks,
+                              hipMemcpyDeviceToHost, h->stream));
+        NL_HIP(hipStreamSynchronize(h->stream));
+        double s = 0.0;
+        for (int b = 0; b < kStatBlocks; b++) s += part[b];
+        *variance = s / (double)n;
+    }
+    return NL_OK;
+}
+
+int nl_stack_frame_stats(nl_stack_t *h, int idx, float *mn, float *mean, float *mx,
+                         double *variance)
+{
+    NL_CHECK_HANDLE(h);
+    NL_SETTLE_UPLOADS(h);
+    if (idx < 0 || idx >= h->n_frames) return fail(NL_ERR_INVALID_ARG, "frame_stats: bad index %d", idx);
+    return frame_stats_impl(h, h->d_frames + (int64_t)idx * h->fstride, h->npix, mn, mean, mx, variance);
+}
+
+static int frame_noise_impl(nl_stack_t *h, const float *d, float *noise)
+{
+    std::vector<double> part(kStatBlocks);
+    NL_HIP(nl::launch_noise(d, h->width, h->height, h->d_stat_partial, kStatBlocks, h->stream));
+    NL_HIP(hipMemcpyAsync(part.data(), h->d_stat_partial, sizeof(double) * kStatBlocks,
+                          hipMemcpyDeviceToHost, h->stream));
+    NL_HIP(hipStreamSynchronize(h->stream));
+    double s = 0.0;
+    for (int b = 0; b < kStatBlocks; b++) s += part[b];
+    // noise.go:53: factor = float32(sqrt(pi/2)) / (6*float32(w-2)*float32(h-2)), fp32
+    const float c = (float)sqrt(0.5 * M_PI);
+    volatile float den = 6.0f * (float)(h->width - 2);
+    den = den * (float)(h->height - 2);
+    const float factor = c / den;
+    *noise = (float)s * factor;
+    return NL_OK;
+}
+
+int nl_stack_frame_noise(nl_stack_t *h, int idx, float *noise)
+{
+    NL_CHECK_HANDLE(h);
+    NL_SETTLE_UPLOADS(h);
+    if (idx < 0 || idx >= h->n_frames || !noise)
+        return fail(NL_ERR_INVALID_ARG, "frame_noise: bad index %d or null output", idx);
+    if (h->row0 != 0 || h->rows != h->height)
+        return fail(NL_ERR_INVALID_ARG, "frame_noise needs a whole-image handle (3x3 stencil)");
+    if (h->width < 3 || h->height < 3) return fail(NL_ERR_INVALID_ARG, "frame_noise: image too small");
+    return frame_noise_impl(h, h->d_frames + (int64_t)idx * h->fstride, noise);
+}
+
+int nl_stack_weights_from_noise(nl_stack_t *h, float *noise_out)
+{
+    NL_CHECK_HANDLE(h);
+    std::vector<float> noise((size_t)h->n_frames), w((size_t)h->n_frames);
+    for (int i = 0; i < h->n_frames; i++) {
+        int rc = nl_stack_frame_noise(h, i, &noise[(size_t)i]);
+        if (rc != NL_OK) return rc;
+    }
+    if (noise_out) memcpy(noise_out, noise.data(), sizeof(float) * noise.size());
+    int rc = nl_weights_from_scalars(NL_WEIGHT_INVERSE_NOISE, noise.data(), h->n_frames, w.data(), nullptr);
+    if (rc != NL_OK) return rc;
+    return nl_stack_set_weights(h, w.data());
+}
+
+int nl_stack_frame_affine(nl_stack_t *h, int idx, float multiplier, float offset)
+{
+    NL_CHECK_HANDLE(h);
+    NL_SETTLE_UPLOADS(h);
+    if (idx < 0 || idx >= h->n_frames) return fail(NL_ERR_INVALID_ARG, "frame_affine: bad index %d", idx);
+    NL_HIP(nl::launch_affine(h->d_frames + (int64_t)idx * h->fstride, h->npix, multiplier, offset, h->stream));
+    NL_HIP(hipStreamSynchronize(h->stream));
+    return NL_OK;
+}
+
+// MedianFilter / GatherAndMedian, ops/pre/badpixels.go:54-77 and internal/median/gather.go:26-38
+int nl_median_filter_mask(const float *in_host, float *out_host, int64_t n, const int32_t *mask, int mask_len, int device)
+{
+    if (!in_host || !out_host || n < 1 || !mask || mask_len < 1 || mask_len > nl::kMedianMaskMax)
+        return fail(NL_ERR_INVALID_ARG, "median_filter_mask: bad argument (mask of 1..%d offsets)", nl::kMedianMaskMax);
+    return median_filter_run("median_filter_mask", in_host, out_host, n, device, [&](const float *d_in, float *d_out) {
+        return nl::launch_median_mask(d_in, d_out, n, mask, mask_len, nullptr);
+    });
+}
+
+int nl_median_filter_3x3(const float *in_host, float *out_host, int width, int height, int device)
+{
+    if (!in_host || !out_host || width < 1 || height < 1)
+        return fail(NL_ERR_INVALID_ARG, "median_filter_3x3: bad argument");
+    return median_filter_run("median_filter_3x3", in_host, out_host, (int64_t)width * height, device,
+                             [&](const float *d_in, float *d_out) {
+                                 return nl::launch_median3x3(d_in, d_out, width, height, nullptr);
+                             });
+}
+
+// ---- OpCalibrate / OpBadPixel, mono (internal/ops/pre/preprocess.go:68-195; kernels in preprocess.hip) ----------
+
+// OpCalibrate's masters on one device (read-only after nl_calib_create: any number of threads may share one)
+struct nl_calib {
+    int device = 0;
+    int width = 0, height = 0;             // Naxisn of the masters
+    float *d_dark = nullptr, *d_flat = nullptr;
+    float flat_max = 0.0f;                 // FlatFrame.Stats.Max()
+};
+
+// Stats.Max() (stats.go:112-121) of the flat through the min / sum / max reduction of nl_stack_frame_stats
+static int flat_max_impl(const float *d_flat, int64_t n, float *out)
+{
+    double *d_part = nullptr;
+    NL_HIP(dev_malloc(&d_part, sizeof(double) * 3 * kStatBlocks));
+    std::vector<double> part(3 * kStatBlocks);
+    hipError_t e = nl::launch_min_sum_max(d_flat, n, d_part, kStatBlocks, nullptr);
+    if (e == hipSuccess) e = hipMemcpy(part.data(), d_part, sizeof(double) * part.size(), hipMemcpyDeviceToHost);
+    (void)hipFree(d_part);
+    if (e != hipSuccess) return fail(NL_ERR_HIP, "calib_create: flat maximum: %s", hipGetErrorString(e));
+    *out = fold_min_sum_max(part).hi;
+    return NL_OK;
+}
+
+static int calib_create_impl(nl_calib *c, const float *dark_host, const float *flat_host)
+{
+    int rc = select_device(c->device);
+    if (rc != NL_OK) return rc;
+    const int64_t n = (int64_t)c->width * c->height;
+    const size_t bytes = (size_t)n * sizeof(float);
+    if (dark_host) {
+        NL_HIP(dev_malloc(&c->d_dark, bytes));
+        NL_HIP(hipMemcpy(c->d_dark, dark_host, bytes, hipMemcpyHostToDevice));
+    }
+    if (flat_host) {
+        NL_HIP(dev_malloc(&c->d_flat, bytes));
+        NL_HIP(hipMemcpy(c->d_flat, flat_host, bytes, hipMemcpyHostToDevice));
+        return flat_max_impl(c->d_flat, n, &c->flat_max);
+    }
+    return NL_OK;
+}
+
+nl_calib_t *nl_calib_create(int device, const float *dark_host, int dark_width, int dark_height,
+                            const float *flat_host, int flat_width, int flat_height)
+{
+    if (!dark_host && !flat_host) { fail(NL_ERR_INVALID_ARG, "calib_create: neither a dark nor a flat"); return nullptr; }
+    if ((dark_host && (dark_width < 1 || dark_height < 1)) || (flat_host && (flat_width < 1 || flat_height < 1))) {
+        fail(NL_ERR_INVALID_ARG, "calib_create: bad master dimensions");
+        return nullptr;
+    }
+    if (dark_host && flat_host && (dark_width != flat_width || dark_height != flat_height)) {      // preprocess.go:144-147
+        fail(NL_ERR_INVALID_ARG, "dark dimensions [%d %d] differ from flat dimensions [%d %d]", dark_width, dark_height,
+             flat_width, flat_height);
+        return nullptr;
+    }
+    nl_calib *c = new nl_calib();
+    c->device = device;
+    c->width = dark_host ? dark_width : flat_width;
+    c->height = dark_host ? dark_height : flat_height;
+    if (calib_create_impl(c, dark_host, flat_host) != NL_OK) {
+        std::string keep = g_err;
+        nl_calib_destroy(c);
+        g_err = keep;
+        return nullptr;
+    }
+    return c;
+}
+
+void nl_calib_destroy(nl_calib_t *c)
+{
+    if (!c) return;
+    if (c->d_dark || c->d_flat) {
+        (void)hipSetDevice(c->device);
+        if (c->d_dark) (void)hipFree(c->d_dark);
+        if (c->d_flat) (void)hipFree(c->d_flat);
+    }
+    delete c;
+}
+
+int nl_calib_flat_max(const nl_calib_t *c, float *out)
+{
+    if (!c || !out) return fail(NL_ERR_INVALID_ARG, "calib_flat_max: null argument");
+    if (!c->d_flat) return fail(NL_ERR_INVALID_ARG, "calib_flat_max: the calibration has no flat");
+    *out = c->flat_max;
+    return NL_OK;
+}
+
+// preprocess.go:73-93: the masters' shape, or another one with the same pixel count (the Seestar case: the data is
+// taken as 1-D, the reference prints a warning), else the reference's error (the dark is checked first)
+static int calib_check_light(const nl_calib *c, int frame_id, int width, int height)
+{
+    if ((width == c->width && height == c->height) || (int64_t)width * height == (int64_t)c->width * c->height)
+        return NL_OK;
+    return fail(NL_ERR_INVALID_ARG, "%d: Light dimensions [%d %d] differ from %s dimensions [%d %d]", frame_id, width,
+                height, c->d_dark ? "dark" : "flat", c->width, c->height);
+}
+
+int nl_stack_frame_calibrate(nl_stack_t *h, int idx, const nl_calib_t *c)
+{
+    NL_CHECK_HANDLE(h);
+    NL_SETTLE_UPLOADS(h);
+    if (idx < 0 || idx >= h->n_frames || !c)
+        return fail(NL_ERR_INVALID_ARG, "frame_calibrate: bad index %d or null calibration", idx);
+    if (c->device != h->device)
+        return fail(NL_ERR_INVALID_ARG, "frame_calibrate: calibration on device %d, handle on device %d", c->device,
+                    h->device);
+    int rc = calib_check_light(c, idx, h->width, h->height);
+    if (rc != NL_OK) return rc;
+    const int64_t off = (int64_t)h->row0 * h->width;          // the tile's 1-D range of the masters
+    float *d = h->d_frames + (int64_t)idx * h->fstride;
+    NL_HIP(nl::launch_calibrate(d, d, h->npix, c->d_dark ? c->d_dark + off : nullptr,
+                                c->d_flat ? c->d_flat + off : nullptr, c->flat_max, h->stream));
+    NL_HIP(hipStreamSynchronize(h->stream));
+    return NL_OK;
+}
+
+int nl_stack_frame_badpixel(nl_stack_t *h, int idx, float sigma_low, float sigma_high, int64_t *removed_out,
+                            float *diff_stats_out)
+{
+    NL_CHECK_HANDLE(h);
+    NL_SETTLE_UPLOADS(h);
+    if (idx < 0 || idx >= h->n_frames) return fail(NL_ERR_INVALID_ARG, "frame_badpixel: bad index %d", idx);
+    if (sigma_low == 0.0f || sigma_high == 0.0f) {         // preprocess.go:181-183: nothing to do
+        if (removed_out) *removed_out = 0;
+        if (diff_stats_out) diff_stats_out[0] = diff_stats_out[1] = NAN;
+        return NL_OK;
+    }
+    if (sigma_low < 0.0f || sigma_high < 0.0f)             // (the reference would flag the border: not supported)
+        return fail(NL_ERR_INVALID_ARG, "frame_badpixel: negative sigma (low %g, high %g)", sigma_low, sigma_high);
+    if (h->row0 != 0 || h->rows != h->height)
+        return fail(NL_ERR_INVALID_ARG, "frame_badpixel needs a whole-image handle (3x3 stencil, whole-frame std)");
+    if (h->npix >= ((int64_t)1 << 31)) return fail(NL_ERR_INVALID_ARG, "frame_badpixel: frame of 2^31 pixels or more");
+    const int blocks = nl::bp_blocks(h->npix);
+    nl_stack::FrameScratch &fs = h->frame_scratch;
+    if (!fs.d_bp_diff) NL_HIP(cached_malloc((void **)&fs.d_bp_diff, sizeof(float) * (size_t)h->npix, h->device));
+    if (!fs.d_bp_seg)
+        NL_HIP(cached_malloc((void **)&fs.d_bp_seg, sizeof(unsigned) * (size_t)blocks * nl::kBpChunk, h->device));
+    if (!fs.d_bp_list) NL_HIP(cached_malloc((void **)&fs.d_bp_list, sizeof(unsigned) * (size_t)h->npix, h->device));
+    if (!fs.d_bp_small) NL_HIP(dev_malloc(&fs.d_bp_small, sizeof(nl::BpParams) + 3 * sizeof(unsigned) * (size_t)blocks));
+    nl::BpScratch s;
+    s.diff = fs.d_bp_diff;
+    s.seg = fs.d_bp_seg;
+    s.list = fs.d_bp_list;
+    s.params = reinterpret_cast<nl::BpParams *>(fs.d_bp_small);
+    s.count = fs.d_bp_small + sizeof(nl::BpParams) / sizeof(unsigned);
+    s.offset = s.count + blocks;
+    s.removed = s.offset + blocks;
+    s.partial = h->d_stat_partial;
+    s.stat_blocks = kStatBlocks;
+    NL_HIP(nl::launch_badpixel(h->d_frames + (int64_t)idx * h->fstride, h->width, h->height, sigma_low, sigma_high, s,
+                               h->stream));
+    nl::BpParams p;
+    NL_HIP(hipMemcpyAsync(&p, s.params, sizeof p, hipMemcpyDeviceToHost, h->stream));
+    NL_HIP(hipStreamSynchronize(h->stream));
+    if (removed_out) *removed_out = (int64_t)p.removed;
+    if (diff_stats_out) { diff_stats_out[0] = p.mean; diff_stats_out[1] = p.std; }
+    return NL_OK;
+}
+
+// what both preprocess host forms check first: the arguments, the device, the calibration's device and shape
+static int preprocess_check(const char *who, const nl_calib *c, int frame_id, const float *in_host, const float *out_host,
+                            int width, int height, int device)
+{
+    if (!in_host || !out_host || width < 1 || height < 1) return fail(NL_ERR_INVALID_ARG, "%s: bad argument", who);
+    const int rc = select_device(device);
+    if (rc != NL_OK) return rc;
+    if (c && c->device != device)
+        return fail(NL_ERR_INVALID_ARG, "%s: calibration on device %d, frame on device %d", who, c->device, device);
+    return c ? calib_check_light(c, frame_id, width, height) : NL_OK;
+}
+
+int nl_preprocess_frame(const nl_calib_t *c, int frame_id, const float *in_host, float *out_host, int width, int height,
+                        float sigma_low, float sigma_high, int64_t *removed_out, float *diff_stats_out, int device)
+{
+    const int rc = preprocess_check("preprocess_frame", c, frame_id, in_host, out_host, width, height, device);
+    if (rc != NL_OK) return rc;
+    return with_scratch_handle(width, height, device, [&](nl_stack_t *h) {
+        int r = nl_stack_upload_tile(h, 0, in_host);
+        if (r == NL_OK && c) r = nl_stack_frame_calibrate(h, 0, c);
+        if (r == NL_OK) r = nl_stack_frame_badpixel(h, 0, sigma_low, sigma_high, removed_out, diff_stats_out);
+        return r == NL_OK ? nl_stack_download_tile(h, 0, out_host) : r;
+    });
+}
+
+// ---- OpStarDetect: star.FindStars (internal/star/findstars.go:59-103; kernels and host steps in stars.hip) ---------
+
+static int find_stars_impl(nl_stack_t *h, const float *d_data, const char *who, float location, float scale,
+                           float star_sig, float bp_sigma, float star_in_out, int radius, float diff_std,
+                           nl_star_t *stars_out, int capacity, int *n_stars, float *sum_of_shifts, float *avg_hfr)
+{
+    if (radius < 0 || radius > 1024)      // (deviation 2; radius 0 finds no star)
+        return fail(NL_ERR_INVALID_ARG, "%s: radius %d not in [0, 1024]", who, radius);
+    if (capacity < 0 || (capacity > 0 && !stars_out))
+        return fail(NL_ERR_INVALID_ARG, "%s: capacity %d with %s output", who, capacity, stars_out ? "an" : "no");
+    if (h->row0 != 0 || h->rows != h->height)
+        return fail(NL_ERR_INVALID_ARG, "%s needs a whole-image handle (FindStars indexes the data 1-D)", who);
+    if (h->npix >= ((int64_t)1 << 31)) return fail(NL_ERR_INVALID_ARG, "%s: frame of 2^31 pixels or more", who);
+    if (!h->d_stat_partial) NL_HIP(dev_malloc(&h->d_stat_partial, sizeof(double) * 3 * kStatBlocks));
+    const nl::StarParams p{location, scale, star_sig, bp_sigma, star_in_out, radius, diff_std};
+    std::vector<nl_star_t> stars;
+    float sum = 0.0f, avg = 0.0f;
+    std::string msg;
+    const int rc = nl::find_stars_run(d_data, h->width, h->height, p, h->frame_scratch.star_work, h->d_stat_partial, kStatBlocks,
+                                      h->stream, stars, &sum, &avg, &msg);
+    if (rc != NL_OK) return fail(rc, "%s: %s", who, msg.c_str());
+    const size_t k = std::min(stars.size(), (size_t)capacity);
+    if (k) memcpy(stars_out, stars.data(), k * sizeof(nl_star_t));
+    if (n_stars) *n_stars = (int)stars.size();
+    if (sum_of_shifts) *sum_of_shifts = sum;
+    if (avg_hfr) *avg_hfr = avg;
+    return NL_OK;
+}
+
+int nl_stack_frame_find_stars(nl_stack_t *h, int idx, float location, float scale, float star_sig, float bp_sigma,
+                              float star_in_out, int radius, float diff_std, nl_star_t *stars_out, int capacity,
+                              int *n_stars, float *sum_of_shifts, float *avg_hfr)
+{
+    NL_CHECK_HANDLE(h);
+    NL_SETTLE_UPLOADS(h);
+    if (idx < 0 || idx >= h->n_frames) return fail(NL_ERR_INVALID_ARG, "frame_find_stars: bad index %d", idx);
+    return find_stars_impl(h, h->d_frames + (int64_t)idx * h->fstride, "frame_find_stars", location, scale, star_sig,
+                           bp_sigma, star_in_out, radius, diff_std, stars_out, capacity, n_stars, sum_of_shifts,
+                           avg_hfr);
+}
+
+int nl_stack_result_find_stars(nl_stack_t *h, float location, float scale, float star_sig, float bp_sigma,
+                               float star_in_out, int radius, float diff_std, nl_star_t *stars_out, int capacity,
+                               int *n_stars, float *sum_of_shifts, float *avg_hfr)
+{
+    NL_CHECK_HANDLE(h);
+    if (h->last_mode < 0) return fail(NL_ERR_INVALID_ARG, "result_find_stars: the handle has not run a pass");
+    return find_stars_impl(h, h->d_out, "result_find_stars", location, scale, star_sig, bp_sigma, star_in_out, radius,
+                           diff_std, stars_out, capacity, n_stars, sum_of_shifts, avg_hfr);
+}
+
+int nl_find_stars(const float *data_host, int width, int height, float location, float scale, float star_sig,
+                  float bp_sigma, float star_in_out, int radius, float diff_std, nl_star_t *stars_out, int capacity,
+                  int *n_stars, float *sum_of_shifts, float *avg_hfr, int device)
+{
+    if (!data_host || width < 1 || height < 1) return fail(NL_ERR_INVALID_ARG, "find_stars: bad argument");
+    const int rc = select_device(device);
+    if (rc != NL_OK) return rc;
+    return with_scratch_handle(width, height, device, [&](nl_stack_t *h) {
+        const int r = nl_stack_upload_tile(h, 0, data_host);
+        if (r != NL_OK) return r;
+        return find_stars_impl(h, h->d_frames, "find_stars", location, scale, star_sig, bp_sigma, star_in_out, radius,
+                               diff_std, stars_out, capacity, n_stars, sum_of_shifts, avg_hfr);
+    });
+}
+
+// ---- OpBadPixel, Bayer branch, and OpDebayer (internal/ops/pre/preprocess.go:180-251; kernels in bayer.hip) -------
+
+// getOffsets (debayer.go:26-37)
+static int cfa_offsets(const char *cfa, int *xo, int *yo)
+{
+    const std::string c = cfa;
+    if (c == "RGGB" || c == "rggb") { *xo = 0; *yo = 0; }
+    else if (c == "GRBG" || c == "grbg") { *xo = 1; *yo = 0; }
+    else if (c == "GBRG" || c == "gbrg") { *xo = 0; *yo = 1; }
+    else if (c == "BGGR" || c == "bggr") { *xo = 1; *yo = 1; }
+    else return fail(NL_ERR_INVALID_ARG, "Unknown CFA value %s", cfa);
+    return NL_OK;
+}
+
+// the channel switch of CosmeticCorrectionBayer / DebayerBilinear (badpixels_bayer.go:36-45, debayer.go:47-59)
+static int cfa_channel(const char *channel, int *ch)
+{
+    const std::string c = channel;
+    if (c == "R" || c == "r") *ch = nl::kBayerR;
+    else if (c == "G" || c == "g") *ch = nl::kBayerG;
+    else if (c == "B" || c == "b") *ch = nl::kBayerB;
+    else return fail(NL_ERR_INVALID_ARG, "Unknown debayering value %s", channel);
+    return NL_OK;
+}
+
+// the CFA, then the channel, as the reference checks them; the output shape of DebayerBilinear (debayer.go:65-66)
+static int cfa_parse(const char *channel, const char *cfa, int width, int height, int *ch, int *xo, int *yo,
+                     int *out_w, int *out_h)
+{
+    int rc = cfa_offsets(cfa, xo, yo);
+    if (rc == NL_OK) rc = cfa_channel(channel, ch);
+    if (rc != NL_OK) return rc;
+    *out_w = (width - *xo) & ~1;
+    *out_h = (height - *yo) & ~1;
+    if ((int64_t)*out_w * *out_h == 0)        // (the reference divides by the width 0 at preprocess.go:245)
+        return fail(NL_ERR_INVALID_ARG, "debayer: %dx%d mosaic with cfa %s gives an empty %dx%d image", width, height,
+                    cfa, *out_w, *out_h);
+    return NL_OK;
+}
+
+int nl_debayer_shape(int width, int height, const char *channel, const char *cfa, int *out_width, int *out_height)
+{
+    if (width < 1 || height < 1 || !out_width || !out_height)
+        return fail(NL_ERR_INVALID_ARG, "debayer_shape: bad argument");
+    if (!channel || !cfa || !*channel || !*cfa) {            // OpDebayer.Apply is a no-op (preprocess.go:240-242)
+        *out_width = width;
+        *out_height = height;
+        return NL_OK;
+    }
+    int ch, xo, yo;
+    return cfa_parse(channel, cfa, width, height, &ch, &xo, &yo, out_width, out_height);
+}
+
+static size_t cfa_align(size_t b) { return (b + 255) & ~(size_t)255; }
+
+int nl_stack_upload_frame_cfa(nl_stack_t *h, int idx, const float *raw_host, int raw_width, int raw_height,
+                              const nl_calib_t *c, const char *channel, const char *cfa, float sigma_low,
+                              float sigma_high, int64_t *removed_out, float *stats_out)
+{
+    int rc = nl::require_device();            // (before the handle: without a device a null handle is NL_ERR_NO_DEVICE)
+    if (rc != NL_OK) return rc;
+    NL_CHECK_HANDLE(h);
+    NL_SETTLE_UPLOADS(h);
+    if (idx < 0 || idx >= h->n_frames || !raw_host || raw_width < 1 || raw_height < 1)
+        return fail(NL_ERR_INVALID_ARG, "upload_frame_cfa: bad index %d, null frame or bad raw size %dx%d", idx,
+                    raw_width, raw_height);
+    if (!channel || !cfa || !*channel || !*cfa)
+        return fail(NL_ERR_INVALID_ARG, "upload_frame_cfa needs a channel and a CFA (mono frames: nl_stack_upload_tile, "
+                    "nl_stack_frame_calibrate, nl_stack_frame_badpixel)");
+    int ch, xo, yo, out_w, out_h;
+    if ((rc = cfa_parse(channel, cfa, raw_width, raw_height, &ch, &xo, &yo, &out_w, &out_h)) != NL_OK) return rc;
+    if (h->row0 != 0 || h->rows != h->height)
+        return fail(NL_ERR_INVALID_ARG, "upload_frame_cfa needs a whole-image handle (3x3 stencil, whole-frame std)");
+    if (h->width != out_w || h->height != out_h)
+        return fail(NL_ERR_INVALID_ARG, "upload_frame_cfa: a %dx%d mosaic debayers to %dx%d, the handle is %dx%d",
+                    raw_width, raw_height, out_w, out_h, h->width, h->height);
+    const int64_t n = (int64_t)raw_width * raw_height;
+    if (n >= ((int64_t)1 << 31)) return fail(NL_ERR_INVALID_ARG, "upload_frame_cfa: mosaic of 2^31 pixels or more");
+    if (c) {
+        if (c->device != h->device)
+            return fail(NL_ERR_INVALID_ARG, "upload_frame_cfa: calibration on device %d, handle on device %d",
+                        c->device, h->device);
+        if ((rc = calib_check_light(c, idx, raw_width, raw_height)) != NL_OK) return rc;
+    }
+    const nl::BayerGeom g = nl::bayer_geom(raw_width, raw_height, ch, xo, yo);
+    const size_t compact = cfa_align(sizeof(float) * (size_t)g.rows * g.cstride);
+    const size_t o_delta = cfa_align(sizeof(float) * (size_t)n), o_median = o_delta + compact;
+    const size_t o_rowsum = o_median + compact, o_removed = o_rowsum + cfa_align(sizeof(float) * (size_t)g.rows);
+    const size_t o_params = o_removed + cfa_align(sizeof(unsigned) * (size_t)nl::bayer_replace_blocks(g));
+    const size_t bytes = o_params + sizeof(nl::BayerParams);
+    NL_HIP(h->frame_scratch.cfa.reserve(bytes, h->stream));
+    char *base = static_cast<char *>(h->frame_scratch.cfa.ptr);
+    float *raw = reinterpret_cast<float *>(base);
+    NL_HIP(hipMemcpyAsync(raw, raw_host, sizeof(float) * (size_t)n, hipMemcpyHostToDevice, h->stream));
+    if (c)
+        NL_HIP(nl::launch_calibrate(raw, raw, n, c->d_dark, c->d_flat, c->flat_max, h->stream));
+    const bool correct = sigma_low != 0.0f && sigma_high != 0.0f;     // preprocess.go:181-183
+    nl::BayerScratch s;
+    s.delta = reinterpret_cast<float *>(base + o_delta);
+    s.median = reinterpret_cast<float *>(base + o_median);
+    s.rowsum = reinterpret_cast<float *>(base + o_rowsum);
+    s.removed = reinterpret_cast<unsigned *>(base + o_removed);
+    s.params = reinterpret_cast<nl::BayerParams *>(base + o_params);
+    if (correct) NL_HIP(nl::launch_bayer_correct(raw, g, sigma_low, sigma_high, s, h->stream));
+    NL_HIP(nl::launch_debayer(raw, raw_width, raw_height, ch, xo, yo, h->d_frames + (int64_t)idx * h->fstride,
+                              h->width, h->stream));
+    nl::BayerParams p;
+    p.mean = p.std = NAN;
+    p.removed = 0;
+    if (correct) NL_HIP(hipMemcpyAsync(&p, s.params, sizeof p, hipMemcpyDeviceToHost, h->stream));
+    NL_HIP(hipStreamSynchronize(h->stream));   // (raw_host must not be retained)
+    if (removed_out) *removed_out = (int64_t)p.removed;
+    if (stats_out) { stats_out[0] = p.mean; stats_out[1] = p.std; }
+    return NL_OK;
+}
+
+int nl_preprocess_frame_cfa(const nl_calib_t *c, int frame_id, const float *in_host, int width, int height,
+                            const char *channel, const char *cfa, float sigma_low, float sigma_high, float *out_host,
+                            int *out_width, int *out_height, int64_t *removed_out, float *stats_out, int device)
+{
+    int rc = preprocess_check("preprocess_frame_cfa", c, frame_id, in_host, out_host, width, height, device);
+    if (rc != NL_OK) return rc;                                 // (OpCalibrate first)
+    const char *chan = channel ? channel : "", *pattern = cfa ? cfa : "";
+    const bool correct = sigma_low != 0.0f && sigma_high != 0.0f;
+    int ch, xo, yo, ow = width, oh = height;
+    if (*chan && correct && (rc = cfa_parse(chan, pattern, width, height, &ch, &xo, &yo, &ow, &oh)) != NL_OK)
+        return rc;                                              // OpBadPixel's Bayer branch: CFA, then channel
+    if (!*chan || !*pattern) {
+        // the mono branch of OpBadPixel (or none) and no OpDebayer: nl_preprocess_frame's result
+        if (out_width) *out_width = width;
+        if (out_height) *out_height = height;
+        return nl_preprocess_frame(c, frame_id, in_host, out_host, width, height, *chan ? 0.0f : sigma_low,
+                                   *chan ? 0.0f : sigma_high, removed_out, stats_out, device);
+    }
+    if ((rc = cfa_parse(chan, pattern, width, height, &ch, &xo, &yo, &ow, &oh)) != NL_OK) return rc;   // OpDebayer
+    // (a handle of the debayered shape)
+    rc = with_scratch_handle(ow, oh, device, [&](nl_stack_t *h) {
+        const int r = nl_stack_upload_frame_cfa(h, 0, in_host, width, height, c, chan, pattern, sigma_low, sigma_high,
+                                                removed_out, stats_out);
+        return r == NL_OK ? nl_stack_download_tile(h, 0, out_host) : r;
+    });
+    if (rc == NL_OK) {
+        if (out_width) *out_width = ow;
+        if (out_height) *out_height = oh;
+    }
+    return rc;
+}
+
+}  // extern "C"
+
+void nl_stack::FrameScratch::release(int device, int64_t npix)
+{
+    cached_free(d_bp_diff, sizeof(float) * (size_t)npix, device);
+    cached_free(d_bp_seg, sizeof(unsigned) * (size_t)nl::bp_blocks(npix) * nl::kBpChunk, device);
+    cached_free(d_bp_list, sizeof(unsigned) * (size_t)npix, device);
+    if (d_bp_small) (void)hipFree(d_bp_small);
+    cfa.release();
+    star_work.free();
+}

@@ -1,0 +1,180 @@
+// nlstack_internal.hpp -- what the three units of the C ABI (nlstack_api.hip, nlstack_pass.hip, nlstack_frame.hip)
+// share: the handle, the error state, the device-memory helpers.  Private: no kernel source includes it, not installed.
+#pragma once
+
+#include <string.h>
+
+#include <string>
+#include <vector>
+
+#include "stars.hpp"
+#include "stack_kernels.h"
+
+namespace nl {
+
+extern thread_local std::string g_err;     // what nl_last_error() returns on this thread
+int fail(int code, const char *fmt, ...);   // g_err = the formatted message; returns code
+
+// NL_ERR_NO_DEVICE unless HIP sees a device (*count: how many); select_device: that, a range check, hipSetDevice
+int require_device(int *count = nullptr);
+int select_device(int device);
+
+// EVERY device allocation of the library goes through dev_malloc (it hands parked blocks back when HIP runs out);
+// cached_malloc / cached_free park large blocks for the next handle of the same sizes (the caller has selected `device`)
+hipError_t dev_malloc(void **p, size_t bytes);
+template <class T>
+hipError_t dev_malloc(T **p, size_t bytes) { return dev_malloc(reinterpret_cast<void **>(p), bytes); }
+hipError_t cached_malloc(void **p, size_t bytes, int device);
+void cached_free(void *p, size_t bytes, int device);
+
+// device scratch grown on demand, never shrunk: the old buffer goes only once `stream`, its last user, is idle
+struct DevBuffer {
+    void *ptr = nullptr;
+    size_t bytes = 0;
+    hipError_t reserve(size_t want, hipStream_t stream);
+    void release() { if (ptr) (void)hipFree(ptr); ptr = nullptr; bytes = 0; }
+};
+
+// The host forms of the frame steps (nl_fits_decode, nl_find_stars, ...): a one-frame width x height handle of their
+// own per call carries stream and scratch, so concurrent calls share nothing.  run(h) runs on it; its error message
+// outlives the handle.  A handle that cannot be created gives NL_ERR_HIP with nl_stack_create's message.
+template <class Run>
+int with_scratch_handle(int width, int height, int device, Run run)
+{
+    nl_stack_t *h = nl_stack_create(1, width, height, 0, height, device);
+    if (!h) return NL_ERR_HIP;
+    const int rc = run(h);
+    const std::string keep = g_err;
+    nl_stack_destroy(h);
+    g_err = keep;
+    return rc;
+}
+
+}  // namespace nl
+
+using nl::cached_free, nl::cached_malloc, nl::dev_malloc, nl::fail, nl::g_err, nl::select_device, nl::with_scratch_handle;
+
+#define NL_HIP(call)                                                                        \
+    do {                                                                                    \
+        hipError_t e_ = (call);                                                             \
+        if (e_ != hipSuccess)                                                               \
+            return fail(NL_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), \
+                        __FILE__, __LINE__);                                                \
+    } while (0)
+
+constexpr int kTimingRing = 64;     // passes whose HIP-event times can be read back after the fact
+constexpr int kStageSlots = 4;      // pinned staging buffers of the asynchronous upload
+constexpr int kStatBlocks = 2048;
+constexpr int kOrderRing = 8;              // events nl_stack_order_stream_after cycles through
+// per-pass device scratch, zeroed by one memset (or, in the fused protocol of the sigma / winsorized fast path, by
+// the previous pass's dominant kernel -- two sets alternate): clip accumulators + list lengths + snapshot
+constexpr size_t kScratchBytes = sizeof(unsigned long long) * nl::kScratchWords;
+
+struct nl_stack {
+    int device = 0;
+    int n_frames = 0, width = 0, height = 0, row0 = 0, rows = 0;
+    int n_capacity = 0;               // frame slots allocated; n_frames <= n_capacity are in use (nl_stack_set_active_frames)
+    int64_t npix = 0;                 // rows*width
+    int64_t fstride = 0;              // floats between consecutive frames of the buffer d_frames points at
+    int64_t fstride_owned = 0;        // ... of the owned buffer (padded_frame_stride); a lent buffer brings its own
+    hipStream_t stream = nullptr;
+    // HIP events of the last kTimingRing passes (whole pass; dominant kernel only), so a caller can
+    // queue many passes without a host sync and read every pass's GPU time afterwards
+    hipEvent_t ring_start[kTimingRing] = {}, ring_stop[kTimingRing] = {};
+    hipEvent_t ring_dom0[kTimingRing] = {}, ring_dom1[kTimingRing] = {};
+    bool ring_dom0_is_start[kTimingRing] = {};            // the pass recorded one event for both (nothing ran in between)
+    bool ring_timed[kTimingRing] = {};                    // the pass in this slot recorded its timing events (not with developer switch 32)
+    int64_t pass_seq = 0;                                  // passes enqueued so far
+    int64_t copy_waits_pass = 0;                           // pass the copy stream has been ordered behind
+    hipEvent_t ev_start = nullptr, ev_stop = nullptr;      // = the ring slot of the current / last pass
+    hipEvent_t ev_dom0 = nullptr, ev_dom1 = nullptr;
+    hipStream_t side_stream = nullptr;                     // replay of the dominant kernel's hand-overs,
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;        // concurrent with the generic pass
+    hipEvent_t ev_order[kOrderRing] = {};                   // nl_stack_order_stream_after
+    int order_seq = 0;
+    unsigned ev_rel = 0;                                   // creation flag of the pass's events (hipEventDisableSystemFence or 0)
+    float *d_frames_owned = nullptr;  // [n_capacity][fstride_owned], the first npix floats of a slot in use
+    float *d_frames = nullptr;        // owned or lent
+    float *d_out = nullptr;           // [npix]
+    float *d_acc = nullptr;           // stack-of-stacks accumulator, lazily allocated
+    float *d_weights = nullptr;       // [n_frames]
+    bool has_weights = false;
+    float *d_xstat = nullptr;         // [(n_frames+1)*2]
+    unsigned long long *d_sets = nullptr;      // two scratch sets of kScratchWords; d_partial = the current one
+    int cur_set = 0;
+    bool sets_clean = false;                   // both sets as a fused pass leaves them: the current one used, the other zeroed
+    bool partial_clean = false;                // the current set is all zeros: the last pass's reduction kernel left it so (plain protocol of the sigma fast path)
+    unsigned long long *d_partial = nullptr;   // [kClipSlots][2] clip accumulators + 2 words of list lengths
+    float2 *d_bounds = nullptr;                // decision pass of weighted stacks: [kBoundRounds][npix] thresholds, lazily allocated
+    unsigned char *d_nrounds = nullptr;        // [npix]
+    bool bounds_tried = false;
+    unsigned fb_hint = 0;                      // exact-list length of the last finished fast pass + 1 (0 = unknown)
+    unsigned gen_hint = 0;                     // same for the generic list
+    bool last_weighted = false;                // the last pass ran with weights (key of the hints it leaves)
+    bool last_fused = false;
+    bool last_tail_fused = false;              // generic pass + first replay ran as one launch (stack_tail_fused.hip)
+    bool last_lists = false;                   // the last pass left its list lengths behind the totals (d_counters[2])
+    unsigned dev_flags = 0;                    // nl_stack_set_dev_flags (A/B measurements)
+    unsigned *d_fb_list = nullptr;             // [npix] pixels the fast kernel handed to the exact kernel
+    unsigned *d_fb_count = nullptr;            // [2]: exact-list length, generic-list length (inside d_partial)
+    unsigned *d_gen_list = nullptr;            // [npix] pixels zonal waves handed to the generic pass
+    bool force_exact = false;
+    int exact_flavour = 0;            // nl_stack_set_exact argument: 1 = LDS column kernel, 2 = wave-per-pixel replay
+    bool last_used_fast = false;
+    unsigned long long *d_counters = nullptr;  // [4]: where a pass leaves {clip_low, clip_high, list lengths, -}: the handle's own buffer or the caller's (nl_stack_set_counters_buffer)
+    unsigned long long *d_counters_own = nullptr;
+    double *d_stat_partial = nullptr;          // [kStatBlocks*3]
+    // linear-fit cascade (stack_linfit.hip): ping-pong pixel lists + liveness masks, lazily allocated
+    unsigned *d_lf_list[2] = {nullptr, nullptr};
+    uint4 *d_lf_state[2] = {nullptr, nullptr};
+    unsigned *d_lf_count = nullptr;
+    int lf_lanes = 0;                          // liveness masks per listed pixel the state arrays were sized for
+    bool lf_tried = false;
+    nl::DevBuffer ingest;                      // raw FITS bytes / unaligned source frame
+    // asynchronous uploads: pinned staging ring + copy stream (nl_stack_upload_frame_async)
+    hipStream_t copy_stream = nullptr;
+    size_t stage_cap[kStageSlots] = {0, 0, 0, 0};
+    nl::DevBuffer ingest_async;                // raw bytes / source frame of the overlapped ingest (copy stream)
+    double *d_stat_partial_async = nullptr;
+    void *h_stage[kStageSlots] = {nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t stage_done[kStageSlots] = {nullptr, nullptr, nullptr, nullptr};
+    bool stage_used[kStageSlots] = {false, false, false, false};
+    int stage_next = 0;
+    bool uploads_pending = false;
+    // scratch of the steps on one resident frame (nlstack_frame.hip), lazily allocated; release() is defined there
+    struct FrameScratch {
+        // bad-pixel step (nl_stack_frame_badpixel): diff, per-workgroup lists, ordered list,
+        // nl::BpParams + per-workgroup list lengths, offsets, bad-pixel counts
+        float *d_bp_diff = nullptr;
+        unsigned *d_bp_seg = nullptr;
+        unsigned *d_bp_list = nullptr;
+        unsigned *d_bp_small = nullptr;
+        // colour-camera front (nl_stack_upload_frame_cfa): the raw mosaic, the compact delta / median of one
+        // channel, row sums, per-workgroup counts, nl::BayerParams
+        nl::DevBuffer cfa;
+        // star detection (nl_stack_frame_find_stars / nl_stack_result_find_stars), grown
+        nl::StarWork star_work;
+        void release(int device, int64_t npix);
+    } frame_scratch;
+    int max_grid = 0;
+    int last_mode = -1;
+    bool last_has_counters = false;
+    bool pending = false;
+    const char *last_kernel = "";
+};
+
+#define NL_CHECK_HANDLE(h)                                              \
+    do {                                                                \
+        if (!(h)) return fail(NL_ERR_INVALID_ARG, "null handle");       \
+        NL_HIP(hipSetDevice((h)->device));                              \
+    } while (0)
+
+// entry points that read frames on h->stream outside a stack pass first let pending
+// asynchronous uploads land
+#define NL_SETTLE_UPLOADS(h)                                            \
+    do {                                                                \
+        if ((h)->uploads_pending) {                                     \
+            NL_HIP(hipStreamSynchronize((h)->copy_stream));             \
+            (h)->uploads_pending = false;                               \
+        }                                                               \
+    } while (0)

@@ -1,0 +1,953 @@
+// nlstack_pass.hip -- one stack pass of the C ABI, and what runs passes: goal-seek, the stack of stacks.
+// run_async_impl sets a pass up, select_engine picks the engine that runs it; all pixel arithmetic runs in the kernels.
+#include <mutex>
+
+#include "nlstack_internal.hpp"
+
+namespace {
+
+constexpr int kListGrid = 2048;     // workgroups of the exact kernel in fallback-list mode
+constexpr int kCoopGrid = 16384;    // workgroups (one wave each) of the wave-per-pixel exact replay
+constexpr int kListLanes = 4;       // pixels per wave there: few pixels, keep divergence low
+constexpr unsigned kFusedMaxList = 512;    // exact-list length up to which a pass runs the fused protocol
+constexpr unsigned kTailFusedMaxList = 512;    // ... up to which generic pass and first replay share one launch (stack_tail_fused.hip)
+// winsorization cascade, "clipping passes : winsorization rounds per pass : regions of the previous stage's list per
+// workgroup" for every stage (the last one runs to the end): measured on 4096^2 -- up to 40 frames
+// 16 / 24 frames 3.68 / 3.94 -> 2.97 / 3.07 ms, 41 ... 96 frames (64: 5.22 -> 4.59 ms); beyond that a continuing stage
+// re-reads every cache line of the stack for an eighth of its pixels and the cascade loses (128 frames: 5.43 -> 5.83 ms)
+constexpr const char *kWinsorPlanShallow = "1:6,1:12:4,0:0:4";   // (round 5, with the certificate: first stage 8 -> 6 rounds, three stages instead of four: 16 / 24 / 32 frames 2.34 / 2.78 / 2.97 -> 2.17 / 2.71 / 2.80 ms)
+constexpr const char *kWinsorPlanDeep = "2:12,2:16:8,3:24:4,0:0:4";
+constexpr int kWinsorCascadeMaxFrames = 96;
+
+// Developer switches (nl_stack_set_dev_flags, include/nlstack.h): A/B measurements, the results are the same either way
+constexpr unsigned kDevPlainProtocol = 1u;         // memset before, reduction kernel after every pass
+constexpr unsigned kDevReplayInFront = 2u;         // first replay in front of the generic pass, on the same stream
+constexpr unsigned kDevNoDecision = 4u;            // weighted stacks: no decision pass, no recorded rounds
+constexpr unsigned kDevNoTile = 16u;               // weighted stacks skip the 64-pixels-per-wave tile replay
+constexpr unsigned kDevUntimed = 32u;              // a pass records none of its timing events
+constexpr unsigned kDevNoWinsorCascade = 128u;     // winsorized passes without the winsorization cascade
+constexpr unsigned kDevNoSharedHints = 512u;       // no list-length hints from earlier handles of the same geometry
+constexpr unsigned kDevRemovedPasses = 1024u | 2048u;     // split / persistent LDS-column pass: removed, rejected
+constexpr unsigned kDevTwoStreamTail = 8192u;      // generic pass and first replay on two streams, not one launch
+constexpr unsigned kDevNoCertificate = 16384u;     // winsorization loops without the invariant-interval certificate
+
+// ---- list-length hints across handles ---------------------------------------------------------------------------------
+// A pass sizes its replay grids and picks its protocol from the list lengths the last FINISHED pass on the handle
+// reported.  A handle that lives for one Apply never has one: its pass ran with 16 384-workgroup replay grids and the
+// plain protocol (headline stack: 2.04 instead of 1.73 ms).  The lengths are therefore also remembered per geometry --
+// frames, tile pixels, mode, weighted -- in a small process-wide table: the next handle of that geometry starts from
+// what the last one saw (stacks of one session resemble each other; a wrong hint costs time, never correctness).
+struct HintKey { int frames; int64_t npix; int mode; bool weighted; };
+struct HintEntry { HintKey key; unsigned fb, gen; };
+std::mutex g_hint_mu;
+std::vector<HintEntry> g_hints;
+constexpr size_t kHintEntries = 32;
+
+void hints_store(const HintKey &k, unsigned fb, unsigned gen)
+{
+    std::lock_guard<std::mutex> lk(g_hint_mu);
+    for (HintEntry &e : g_hints)
+        if (e.key.frames == k.frames && e.key.npix == k.npix && e.key.mode == k.mode && e.key.weighted == k.weighted) {
+            e.fb = fb; e.gen = gen;
+            return;
+        }
+    if (g_hints.size() >= kHintEntries) g_hints.erase(g_hints.begin());
+    g_hints.push_back({k, fb, gen});
+}
+
+bool hints_load(const HintKey &k, unsigned *fb, unsigned *gen)
+{
+    std::lock_guard<std::mutex> lk(g_hint_mu);
+    for (const HintEntry &e : g_hints)
+        if (e.key.frames == k.frames && e.key.npix == k.npix && e.key.mode == k.mode && e.key.weighted == k.weighted) {
+            *fb = e.fb; *gen = e.gen;
+            return true;
+        }
+    return false;
+}
+
+int next_pow2(int n)
+{
+    int p = 1;
+    while (p < n) p <<= 1;
+    return p;
+}
+
+}  // namespace
+
+// Grid of a dense replay whose workgroups stride through the pixels (item = workgroup + i * grid): with a grid that
+// is a multiple of the image width a workgroup would visit ONE image column throughout, and the few workgroups of the
+// alignment borders -- NaN columns, every pixel a full replay -- would run three times as long as the rest with the
+// device draining around them (measured: 5 400 of 8 192 waves in flight on average).  A multiple of 8 (the
+// XCD-contiguous mapping wants whole sweeps) that shares no large factor with the width walks through the columns
+// (at least 64 of them per workgroup).
+static int dense_grid(int64_t items, int64_t max_grid, int width, int pixels_per_item)
+{
+    int64_t g = items < max_grid ? items : max_grid;
+    if (g <= 8 || items <= g) return (int)g;                 // no second sweep: nothing to align with
+    g &= ~(int64_t)7;
+    auto gcd = [](int64_t x, int64_t y) { while (y) { const int64_t t = x % y; x = y; y = t; } return x; };
+    const int64_t most = (int64_t)width / 64 > 8 * pixels_per_item ? (int64_t)width / 64 : 8 * pixels_per_item;       // >= 64 columns per workgroup
+    for (int tries = 0; tries < 64 && g > 8 && gcd(g * pixels_per_item, (int64_t)width) > most; tries++) g -= 8;
+    return (int)g;
+}
+
+extern "C" {
+
+// Linear-fit cascade buffers (stack_linfit.hip): two pixel lists and state arrays with lanes_per_pixel liveness masks
+// (16 B) per pixel, allocated on first use.  nullptr (allocation failure): the kernels run as a single bit-exact stage.
+static const nl::LinfitCascade *linfit_cascade(nl_stack_t *h, nl::LinfitCascade *out)
+{
+    if (!h->lf_tried) {
+        // sized for the most lanes per pixel any active frame count of this handle can need
+        h->lf_lanes = h->n_capacity <= 128 ? 1 : h->n_capacity <= 256 ? 2 : 4;
+        h->lf_tried = true;
+        if (dev_malloc(&h->d_lf_count, sizeof(unsigned) * nl::kLinfitCounters) != hipSuccess) {
+            (void)hipGetLastError();
+            h->d_lf_count = nullptr;
+        }
+        const size_t np = (size_t)h->npix;
+        for (int i = 0; h->d_lf_count && i < 2; i++)
+            if (cached_malloc((void **)&h->d_lf_list[i], sizeof(unsigned) * np, h->device) != hipSuccess ||
+                cached_malloc((void **)&h->d_lf_state[i], sizeof(uint4) * np * (size_t)h->lf_lanes, h->device) != hipSuccess) {
+                (void)hipGetLastError();
+                if (h->d_lf_list[i]) { (void)hipFree(h->d_lf_list[i]); h->d_lf_list[i] = nullptr; }
+                h->d_lf_state[i] = nullptr;
+                (void)hipFree(h->d_lf_count);              // no cascade at all on this handle
+                h->d_lf_count = nullptr;
+            }
+    }
+    if (!h->d_lf_count) return nullptr;
+    out->list[0] = h->d_lf_list[0]; out->list[1] = h->d_lf_list[1];
+    out->state[0] = h->d_lf_state[0]; out->state[1] = h->d_lf_state[1];
+    out->count = h->d_lf_count;
+    out->capacity = (unsigned)h->npix;
+    return out;
+}
+
+// Weighted sigma / winsorized stacks of 33 ... 512 frames run a decision pass in front of the bit-exact replay
+// (33 ... 128 frames: stack_fast_decide.hip, 129 ... 512: the LDS-column kernel of the class, record-only), and
+// unweighted winsorized passes above 128 frames put their decided rounds on record for the list replay: scratch for the
+// thresholds, kBoundRounds * 8 + 1 bytes per pixel of the tile (1.1 GB for 4096^2), allocated by the first pass that
+// wants it and held until the handle is destroyed; nl_stack_device_bytes() reports what a handle holds at any time.
+// false: off (NL_WDECIDE=0, developer switch kDevNoDecision, allocation failed: those passes then run without it).
+static bool ensure_bounds(nl_stack *h)
+{
+    static const bool on = [] { const char *e = getenv("NL_WDECIDE"); return !(e && e[0] == '0'); }();
+    if (!on || (h->dev_flags & kDevNoDecision)) return false;
+    if (h->d_bounds) return true;
+    if (h->bounds_tried) return false;
+    h->bounds_tried = true;
+    // (through the cache: a handle per Apply of a weighted stack pays no hipMalloc / hipFree of 1.1 GB at 4096^2)
+    if (cached_malloc((void **)&h->d_bounds, (size_t)nl::kBoundRounds * (size_t)h->npix * sizeof(float2), h->device) != hipSuccess ||
+        cached_malloc((void **)&h->d_nrounds, (size_t)h->npix, h->device) != hipSuccess) {
+        (void)hipGetLastError();
+        if (h->d_bounds) { (void)hipFree(h->d_bounds); h->d_bounds = nullptr; }
+        h->d_nrounds = nullptr;
+        return false;
+    }
+    return true;
+}
+
+// The sigma / winsorized fast path from 17 frames on (a zonal kernel followed by a generic pass) runs the FUSED protocol
+// (StackArgs::final): no memset in front of the pass -- the previous fused pass's dominant kernel zeroed this pass's
+// scratch set, the two sets alternate -- and no reduction kernel behind it.  NL_FUSED=0 (developer switch) keeps
+// memset + reduce_counters_kernel for A/B runs, and turns off the recorded rounds of winsorized passes above 128 frames.
+static bool fused_protocol_on()
+{
+    static const bool on = [] { const char *e = getenv("NL_FUSED"); return !(e && e[0] == '0'); }();
+    return on;
+}
+
+static int auto_select_mode(int l)   // stack.go:45-55
+{
+    if (l >= 25) return NL_ST_LINEAR_FIT;
+    if (l >= 15) return NL_ST_WINSOR_SIGMA;
+    if (l >= 6) return NL_ST_SIGMA;
+    return NL_ST_MEAN;
+}
+
+// ---- one stack pass: run_async_impl sets it up, select_engine picks the engine that runs it ----------------------------
+
+// the engines, in the order select_engine tries them
+enum class Engine {
+    Mean,
+    MedianRegisters,      // register-resident sorting network, up to 128 frames
+    MedianMultiLane,      // 129 ... 512 frames, 2 or 4 lanes per pixel
+    Listed,               // MAD sigma / linear fit, one- or multi-lane: dominant kernel + bit-exact replay of its list
+    SigmaFast,            // sigma / winsorized: dominant kernel + generic pass, replays of the pixels both hand over
+    WeightedTile,         // bit-exact replay, 64 consecutive pixels per wave with their columns in LDS
+    DenseReplay,          // bit-exact wave-per-pixel replay over the whole tile (behind a decision pass where there is one)
+    ExactColumns,         // bit-exact, one pixel per lane with its column in LDS: every mode, any depth
+};
+
+// what the prologue of the pass decided, for the engine
+struct PassSetup {
+    int mode;
+    bool weighted;
+    bool timed;               // the pass records its timing events (not with kDevUntimed)
+    bool fused;               // fused protocol (fused_protocol_on; only the SigmaFast engine runs it)
+    nl::StackArgs a;
+};
+
+// what a pass leaves behind, written into the handle's last_* fields by every pass (and reset by a failed one)
+struct PassFacts {
+    bool has_counters = false;    // d_counters holds the pass's clip counters
+    bool used_fast = false;       // a dominant kernel handed pixels over: the list lengths belong to this pass
+    bool lists = false;           // ... and sit behind the totals (d_counters[2])
+    bool fused = false;           // fused protocol: this pass's scratch set used, the other one zeroed
+    bool tail_fused = false;      // generic pass + first replay ran as one launch (stack_tail_fused.hip)
+    bool zeroed_behind = false;   // the reduction kernel left the scratch set zeroed
+};
+
+static void set_last_pass(nl_stack *h, const PassFacts &f)
+{
+    h->last_has_counters = f.has_counters;
+    h->last_used_fast = f.used_fast;
+    h->last_lists = f.lists;
+    h->last_fused = f.fused;
+    h->last_tail_fused = f.tail_fused;
+    h->sets_clean = f.fused;
+}
+
+// Pure: allocates nothing, enqueues nothing.  The first engine whose condition holds runs the pass.
+static Engine select_engine(const nl_stack *h, int mode, bool weighted, const nl::StackArgs &a)
+{
+    const bool fast = !h->force_exact;
+    const int n = a.n_frames;
+    if (mode == NL_ST_MEAN) return Engine::Mean;
+    if (fast && mode == NL_ST_MEDIAN && nl::fast_supported(mode, weighted, n, a.npix)) return Engine::MedianRegisters;
+    if (fast && mode == NL_ST_MEDIAN && nl::fast_ml_supported(mode, weighted, n, a.npix)) return Engine::MedianMultiLane;
+    if (fast && h->d_fb_list &&
+        (nl::mad_fast_supported(mode, weighted, n, a.npix) || (mode == NL_ST_MAD_SIGMA && nl::fast_ml_supported(mode, weighted, n, a.npix)) ||
+         nl::linfit_ml_supported(mode, n, a.npix) || nl::linfit_fast_supported(mode, n, a.npix)))
+        return Engine::Listed;
+    if (fast && h->d_fb_list && (nl::fast_supported(mode, weighted, n, a.npix) || nl::fast_ml_supported(mode, weighted, n, a.npix)))
+        return Engine::SigmaFast;
+    // nl_stack_set_exact(h, 3) forces the tile replay, 2 the wave-per-pixel one (verification)
+    if ((h->exact_flavour == 3 ||
+         (fast && weighted && !(h->dev_flags & kDevNoTile) &&
+          n <= (mode == NL_ST_WINSOR_SIGMA ? nl::kTileMaxFramesWinsor : nl::kTileMaxFramesSigma))) &&
+        nl::tile_supported(mode, weighted, n))
+        return Engine::WeightedTile;
+    if ((h->exact_flavour == 2 || (fast && (weighted || n > 512))) && nl::coop_supported(mode, weighted, n))
+        return Engine::DenseReplay;
+    return Engine::ExactColumns;
+}
+
+// FastArgs of a dominant kernel that hands pixels to the exact replay (fb_*) and / or to the generic pass (gen_*)
+static nl::FastArgs list_args(const nl_stack *h, bool exact_list, bool generic_list)
+{
+    nl::FastArgs f;
+    memset(&f, 0, sizeof f);
+    if (exact_list) {
+        f.fb_list = h->d_fb_list;
+        f.fb_count = h->d_fb_count;
+        f.fb_capacity = (unsigned)h->npix;
+    }
+    if (generic_list) {
+        f.gen_list = h->d_gen_list;                 // (nullptr for huge tiles: the median kernel then sorts in full everywhere)
+        f.gen_count = h->d_fb_count + 1;
+        f.gen_capacity = (unsigned)h->npix;
+    }
+    return f;
+}
+
+// the exact list (d_fb_list) replayed by the LDS-column kernel, kListLanes pixels per wave
+static int replay_list(nl_stack *h, int mode, bool weighted, const nl::StackArgs &a)
+{
+    int lanes = 0;
+    size_t lds = 0;
+    if (nl::exact_plan(mode, weighted, a.n_frames, a.n_pad, kListLanes, &lanes, &lds) != 0)
+        return fail(NL_ERR_TOO_MANY_FRAMES, "%d frames do not fit the per-pixel LDS column (mode %d)", a.n_frames, mode);
+    nl::StackArgs e = a;
+    e.list = h->d_fb_list;
+    e.list_count = h->d_fb_count;
+    e.list_capacity = (unsigned)h->npix;
+    const char *exact_name = "";
+    NL_HIP(nl::launch_stack_exact(mode, weighted, e, lanes, kListGrid, lds, h->stream, &exact_name));
+    return NL_OK;
+}
+
+// Grids of the wave-per-pixel list replays: one wave per workgroup, grid-stride over a list whose length is only known on
+// the device; launching 16 k workgroups for a few hundred pixels costs more than replaying them, so the length the last
+// finished pass reported (nl_stack_finish) sizes the grid.  grid0: the dominant kernel's hand-overs, grid1: the generic
+// pass's additions.
+static void replay_grids(const nl_stack *h, int *grid0, int *grid1)
+{
+    *grid0 = kCoopGrid;
+    *grid1 = kCoopGrid / 4;
+    if (h->fb_hint) {
+        const int want = next_pow2((int)(2u * (h->fb_hint - 1u) + 64u));
+        *grid0 = want < 1024 ? 1024 : (want > kCoopGrid ? kCoopGrid : want);      // (a 256-workgroup floor measured the same)
+        *grid1 = *grid0 / 4 < 512 ? 512 : *grid0 / 4;
+    }
+}
+
+// The decision pass of a weighted sigma / winsorized stack in front of the whole-tile replay: it leaves the clip bounds of
+// every round it can decide in a.bounds / a.nrounds.  33 ... 128 frames: the register-resident kernel; 129 ... 512: the
+// LDS-column kernel of the frame-count class (FastArgs::record_only: no outputs, lists or counters; a pixel it would hand
+// to the generic pass has no round on record).
+static int decision_pass(nl_stack *h, const PassSetup &p, nl::StackArgs &a)
+{
+    if (!p.weighted || h->exact_flavour != 0 || p.mode == NL_ST_MEDIAN) return NL_OK;
+    const char *ignored = "";
+    if (nl::decide_supported(p.mode, a.n_frames, a.npix) && ensure_bounds(h)) {
+        a.bounds = h->d_bounds;
+        a.nrounds = h->d_nrounds;
+        NL_HIP(nl::launch_stack_sigma_decide(a, h->stream, p.mode == NL_ST_WINSOR_SIGMA, &ignored));
+    } else if (nl::decide_ml_supported(p.mode, a.n_frames, a.npix) && ensure_bounds(h)) {
+        a.bounds = h->d_bounds;
+        a.nrounds = h->d_nrounds;
+        nl::FastArgs f;
+        memset(&f, 0, sizeof f);
+        f.record_only = 1;
+        NL_HIP(nl::launch_stack_sigma_mlz(a, f, h->stream, &ignored, p.mode == NL_ST_WINSOR_SIGMA));
+    }
+    return NL_OK;
+}
+
+static int run_mean(nl_stack *h, const PassSetup &p, PassFacts *)
+{
+    NL_HIP(nl::launch_stack_mean(p.weighted, p.a, h->stream, &h->last_kernel));
+    NL_HIP(hipEventRecord(h->ev_dom1, h->stream));
+    return NL_OK;
+}
+
+// bit-exact: a register-resident sorting network (pixels with many missing samples are handed from the pruned-network
+// kernel to the full-sort one) or, 129 ... 512 frames, 2 or 4 lanes per pixel
+static int run_median(nl_stack *h, const PassSetup &p, bool multi_lane)
+{
+    if (!multi_lane) {
+        NL_HIP(nl::launch_stack_median_fast(p.a, list_args(h, false, true), h->stream, &h->last_kernel, h->ev_dom1));
+    } else {
+        NL_HIP(nl::launch_stack_median_ml(p.a, h->stream, &h->last_kernel));
+        NL_HIP(hipEventRecord(h->ev_dom1, h->stream));
+    }
+    return NL_OK;
+}
+
+// MAD sigma / linear fit: register-resident, the exact kernel replays the pixels the dominant kernel lists
+static int run_listed(nl_stack *h, const PassSetup &p, PassFacts *facts)
+{
+    const nl::StackArgs &a = p.a;
+    if (p.mode == NL_ST_MAD_SIGMA) {
+        // counters exact (the bounds come from two medians); pixels with a non-finite median are replayed; 128 frames:
+        // pixels with too few samples for the selection kernel go to the generic list
+        const nl::FastArgs f = list_args(h, true, true);
+        if (a.n_frames <= 128) NL_HIP(nl::launch_stack_mad_fast(a, f, h->stream, &h->last_kernel));
+        else                   NL_HIP(nl::launch_stack_mad_ml(a, f, h->stream, &h->last_kernel));
+        NL_HIP(hipEventRecord(h->ev_dom1, h->stream));
+    } else {
+        // bit-exact (sums run in sorted order; 129 ... 512 frames: 2 or 4 lanes per pixel, the sums chained through the
+        // lanes); only pixels with an infinite sample are replayed
+        const nl::FastArgs f = list_args(h, true, false);
+        nl::LinfitCascade cascade;
+        const nl::LinfitCascade *cas = linfit_cascade(h, &cascade);
+        if (cas) NL_HIP(hipMemsetAsync(h->d_lf_count, 0, sizeof(unsigned) * nl::kLinfitCounters, h->stream));
+        if (nl::linfit_ml_supported(p.mode, a.n_frames, a.npix))
+            NL_HIP(nl::launch_stack_linfit_ml(a, f, cas, h->stream, &h->last_kernel, h->ev_dom1));
+        else
+            NL_HIP(nl::launch_stack_linfit_fast(a, f, cas, h->stream, &h->last_kernel, h->ev_dom1));
+    }
+    const int rc = replay_list(h, p.mode, p.weighted, a);
+    if (rc != NL_OK) return rc;
+    NL_HIP(nl::launch_reduce_counters(h->d_partial, nl::kClipSlots, h->d_counters, h->stream));
+    facts->has_counters = true;
+    facts->used_fast = true;
+    return NL_OK;
+}
+
+// Winsorized fast passes: how the generic pass and the winsorization loops are budgeted.  true: the winsorization cascade runs.
+static bool winsor_setup(nl_stack *h, int n_frames, nl::FastArgs &f)
+{
+    // winsorized generic passes and the stages of the cascade behind the dominant kernel: a wave runs for its slowest pixel,
+    // and the few pixels whose winsorization loops take dozens of rounds are cheaper in the replay (NL_GEN_ROUND_CAP: rounds per clipping pass; 100 = the limit of every kernel)
+    static const int cap_env = [] { const char *e = getenv("NL_GEN_ROUND_CAP"); return e ? atoi(e) : 0; }();
+    // (measured per frame count on the bench stack; 12 / 13 frames -- the smallest stacks with a zonal kernel -- lose with 40)
+    f.gen_round_cap = cap_env > 0 ? cap_env : (n_frames >= 48 ? 24 : (n_frames > 20 ? 32 : ((n_frames == 12 || n_frames == 13) ? 60 : 40)));
+    // the invariant-interval certificate of the winsorization loops (stack_fast_sigma_impl.hpp): first trial after
+    // cert_first rounds of a loop, then every cert_every; NL_WCERT="first,every" ("0" = off), developer switch kDevNoCertificate: off
+    // (3, 3: measured best at 16 frames and within 2 % of the best at 24, profiles/r05_winsor_cert.txt)
+    static const int cert_env[2] = {[] { const char *e = getenv("NL_WCERT"); return e ? atoi(e) : 3; }(),
+                                    [] { const char *e = getenv("NL_WCERT"); const char *c = e ? strchr(e, ',') : nullptr; const int v = c ? atoi(c + 1) : 3; return v > 0 ? v : 1; }()};
+    f.cert_first = (h->dev_flags & kDevNoCertificate) ? 0 : cert_env[0];
+    f.cert_every = cert_env[1];
+    // winsorized clipping of 16 ... 128 frames: the winsorization cascade (stack_fast_sigma_impl.hpp) -- the dominant
+    // kernel and a second stage stop at a budget of rounds per wave and hand their unfinished pixels on, a third
+    // stage finishes them.  Lists and states live in the buffers of the linear-fit cascade (same sizes, never in
+    // use at the same time); their lengths in the scratch set.  NL_WCAS="b1,b2" sets the budgets, "0" turns it off;
+    // developer switch kDevNoWinsorCascade: off (A/B inside one process)
+    if (n_frames > 128 || n_frames < 12 || (h->dev_flags & kDevNoWinsorCascade)) return false;
+    // plan: "passes:cap[:group]" per stage, comma-separated, the dominant kernel first; the last stage runs to the end
+    struct Plan { int stages; int pass[nl::kCascadeStages], cap[nl::kCascadeStages], group[nl::kCascadeStages]; };
+    auto parse = [](const char *e, Plan *pl) {
+        pl->stages = 0;
+        const char *p = e;
+        while (*p && pl->stages < nl::kCascadeStages) {
+            char *end = nullptr;
+            const long a1 = strtol(p, &end, 10);
+            if (end == p || *end != ':') break;
+            p = end + 1;
+            const long a2 = strtol(p, &end, 10);
+            if (end == p) break;
+            long a3 = 4;
+            if (*end == ':') { p = end + 1; a3 = strtol(p, &end, 10); if (end == p) break; }
+            pl->pass[pl->stages] = (int)a1;
+            pl->cap[pl->stages] = (int)a2;
+            pl->group[pl->stages] = a3 < 1 ? 1 : (a3 > 16 ? 16 : (int)a3);
+            pl->stages++;
+            if (*end != ',') break;
+            p = end + 1;
+        }
+    };
+    static const Plan env_plan = [&] { Plan p0{}; const char *e = getenv("NL_WCAS"); if (e) parse(e, &p0); return p0; }();
+    static const bool env_off = [] { const char *e = getenv("NL_WCAS"); return e && e[0] == '0' && e[1] == 0; }();
+    Plan pl{};
+    if (env_plan.stages >= 2) pl = env_plan;
+    else if (n_frames <= kWinsorCascadeMaxFrames) parse(n_frames <= 40 ? kWinsorPlanShallow : kWinsorPlanDeep, &pl);
+    nl::LinfitCascade cb;
+    // (a list holds at most one entry per pixel of the tile, rounded up to whole workgroups: list and states of a
+    // stage share one of the cascade's state arrays, 4 words per pixel; the region lengths take its pixel lists)
+    if (env_off || pl.stages < 2 || h->npix < 65536 || !linfit_cascade(h, &cb)) return false;
+    for (int i = 0; i < 2; i++) {
+        unsigned *base = reinterpret_cast<unsigned *>(cb.state[i]);
+        f.cas_list[i] = base;
+        f.cas_state[i] = base + 2 * (size_t)h->npix;
+        f.cas_count[i] = cb.list[i];
+    }
+    f.cas_stages = pl.stages;
+    for (int k = 0; k < pl.stages; k++) { f.cas_pass[k] = pl.pass[k]; f.cas_cap[k] = pl.cap[k]; f.cas_group[k] = pl.group[k]; }
+    return true;
+}
+
+// Sigma / winsorized clipping: a register-resident (up to 128 frames) or LDS-column (129 ... 512) dominant kernel, a generic
+// pass over the pixels it hands over, and the bit-exact replay of the pixels either cannot decide: one wave per pixel where
+// available.  The hand-overs of the dominant kernel are replayed on the side stream WHILE the generic pass runs (both only
+// depend on the dominant kernel); what the generic pass adds to the list is replayed after it.
+static int run_sigma_fast(nl_stack *h, const PassSetup &p, PassFacts *facts)
+{
+    const int mode = p.mode;
+    nl::StackArgs a = p.a;
+    // winsorized passes: the fast kernels put the thresholds of every round they decide on record, so that the
+    // replay of a pixel that turns undecidable later skips the winsorization loops of the decided rounds
+    // (from 129 frames on: C3 tile 5.28 -> 5.14 ms; at 128 frames most undecidable pixels are undecidable in
+    // their first round and the stores cost the dominant kernel 0.6 %)
+    if (mode == NL_ST_WINSOR_SIGMA && a.n_frames > 128 && fused_protocol_on() && ensure_bounds(h)) {
+        a.bounds = h->d_bounds;
+        a.nrounds = h->d_nrounds;
+    }
+    nl::FastArgs f = list_args(h, true, true);
+    f.fb_snap = h->d_fb_count + 2;                   // see the replay below
+    f.gen_hint = h->gen_hint;
+    const bool cascade = mode == NL_ST_WINSOR_SIGMA && winsor_setup(h, a.n_frames, f);
+    nl::StackArgs e = a;
+    e.list = h->d_fb_list;
+    e.list_count = h->d_fb_count;
+    e.list_capacity = (unsigned)h->npix;
+    const bool coop = nl::coop_supported(mode, p.weighted, a.n_frames) != 0;
+    unsigned *snap = h->d_fb_count + 2;               // 1 + list length when the first replay started (set on the device)
+    int grid0 = 0, grid1 = 0;
+    replay_grids(h, &grid0, &grid1);
+    struct Fork { nl_stack *h; nl::StackArgs e; int mode; unsigned *snap; int grid0; bool cascade; hipError_t err; } fork{h, e, mode, snap, grid0, cascade, hipSuccess};
+    nl::AfterDominant after = nullptr;
+    if (coop) after = [](void *u) {
+        Fork *k = static_cast<Fork *>(u);
+        nl_stack *hh = k->h;
+        const char *ignored = "";
+        // (ev_dom1: recorded behind the dominant kernel.  With a winsorization cascade two more kernels have filled the
+        // lists since: an event of its own)
+        const bool own = (hh->dev_flags & kDevUntimed) || k->cascade;
+        hipEvent_t fork_ev = own ? hh->ev_fork : hh->ev_dom1;
+        hipError_t err = own ? hipEventRecord(hh->ev_fork, hh->stream) : hipSuccess;
+        // (kDevReplayInFront: the first replay in front of the generic pass, same stream)
+        const bool in_front = (hh->dev_flags & kDevReplayInFront) != 0;
+        const hipStream_t s = in_front ? hh->stream : hh->side_stream;
+        if (!in_front && err == hipSuccess) err = hipStreamWaitEvent(hh->side_stream, fork_ev, 0);
+        nl::StackArgs first = k->e;
+        first.list_snap = k->snap;                    // the list as the dominant kernel left it (snapshot on the device)
+        first.list_part = 0;
+        if (err == hipSuccess) err = nl::launch_stack_sigma_coop(k->mode, first, k->grid0, s, &ignored);
+        if (err == hipSuccess) err = hipEventRecord(hh->ev_join, s);
+        k->err = err;
+    };
+    // Short exact lists (plain sigma, 65 ... 128 frames, fused protocol): generic pass and first replay as the lower and the
+    // upper workgroups of ONE launch (stack_tail_fused.hip) instead of two streams -- no fork, no join: the join alone costs
+    // a 512-row tile 14 us of its 257.  Every workgroup of that launch claims the generic pass's 48 KiB of LDS (three per
+    // CU), hence only while one wave per listed pixel fits the device at that rate.
+    // NL_TAIL_FUSED=0 / developer switch kDevTwoStreamTail: the two-stream protocol (A/B).
+    static const bool tail_fused_on = [] { const char *e = getenv("NL_TAIL_FUSED"); return !(e && e[0] == '0'); }();
+    const bool tail_fused = tail_fused_on && !(h->dev_flags & (kDevTwoStreamTail | kDevReplayInFront)) && p.fused && coop && !cascade &&
+                            nl::tail_fused_supported(mode, p.weighted, a.n_frames) != 0 && h->fb_hint != 0 &&
+                            h->fb_hint - 1u <= kTailFusedMaxList;
+    nl::StackArgs first_replay = e;
+    first_replay.list_snap = snap;                    // the list as the dominant kernel left it (snapshot on the device)
+    first_replay.list_part = 0;
+    unsigned replay_blocks = h->fb_hint + 31u;        // one wave per listed pixel and some: the list's length is last pass's
+    replay_blocks = replay_blocks < 64u ? 64u : replay_blocks > 768u ? 768u : replay_blocks;
+    if (tail_fused) after = nullptr;
+    if (a.n_frames <= 128)
+        NL_HIP(nl::launch_stack_sigma_fast(a, f, h->stream, &h->last_kernel, p.timed ? h->ev_dom1 : nullptr,
+                                           mode == NL_ST_WINSOR_SIGMA, after, &fork,
+                                           tail_fused ? &first_replay : nullptr, replay_blocks));
+    else   // 129..512 frames: 2 or 4 lanes per pixel
+        NL_HIP(nl::launch_stack_sigma_ml(a, f, h->stream, &h->last_kernel, p.timed ? h->ev_dom1 : nullptr,
+                                         mode == NL_ST_WINSOR_SIGMA, after, &fork));
+    NL_HIP(fork.err);
+    if (coop) {
+        const char *exact_name = "";
+        e.list_snap = snap;                           // the generic pass's additions
+        e.list_part = 1;
+        NL_HIP(nl::launch_stack_sigma_coop(mode, e, grid1, h->stream, &exact_name));
+        if (!tail_fused) NL_HIP(hipStreamWaitEvent(h->stream, h->ev_join, 0));
+    } else {
+        const int rc = replay_list(h, mode, p.weighted, a);
+        if (rc != NL_OK) return rc;
+    }
+    if (!p.fused) {              // (a fused pass implies coop: every kernel of the pass is enqueued)
+        // (the reduction zeroes the scratch set behind itself: no memset in front of the next pass)
+        NL_HIP(nl::launch_reduce_counters(h->d_partial, nl::kClipSlots, h->d_counters, h->stream, h->d_fb_count, true));
+        facts->zeroed_behind = true;
+    }
+    facts->has_counters = true;
+    facts->used_fast = true;
+    facts->lists = true;
+    facts->fused = p.fused;
+    facts->tail_fused = tail_fused;
+    return NL_OK;
+}
+
+// Bit-exact replay over the whole tile, 64 consecutive pixels per wave with their columns in LDS, one pixel per lane:
+// the default for weighted sigma / winsorized clipping (their result depends on the reference's permutation, so there
+// is no register-resident shortcut) up to kTileMaxFrames* frames -- the LDS column limits it to one wave per SIMD at
+// 128 frames, where the wave-per-pixel replay is faster (tools/replay_probe.py: 0.5 vs 1.5 ms per Mpixel at 32 frames,
+// 7.7 vs 3.8 at 128)
+static int run_weighted_tile(nl_stack *h, const PassSetup &p, PassFacts *facts)
+{
+    const int64_t tiles = (p.a.npix + 63) / 64;
+    const int64_t g = tiles < (1 << 20) ? tiles : (1 << 20);
+    NL_HIP(nl::launch_stack_sigma_tile(p.mode, p.a, (int)g, h->stream, &h->last_kernel));
+    NL_HIP(hipEventRecord(h->ev_dom1, h->stream));
+    NL_HIP(nl::launch_reduce_counters(h->d_partial, nl::kClipSlots, h->d_counters, h->stream));
+    facts->has_counters = true;
+    return NL_OK;
+}
+
+// The wave-per-pixel exact replay over the whole tile: the default for deeper weighted sigma / winsorized stacks (behind
+// their decision pass) and beyond 512 frames
+static int run_dense_replay(nl_stack *h, const PassSetup &p, PassFacts *facts)
+{
+    nl::StackArgs a = p.a;
+    const int rc = decision_pass(h, p, a);
+    if (rc != NL_OK) return rc;
+    const int per_item = p.mode == NL_ST_MEDIAN ? 1 : nl::coop_group(a);
+    // many short workgroups: neighbours that start together share the sectors they fetch, long-lived workgroups
+    // drift apart (128 frames x 4096^2, weighted sigma: 34.7 ms with 8 192 workgroups, 31.6 with 16 384, 28.0 with
+    // 65 536, 27.2 with 262 144; a 512-row tile of 64 frames: 2.50 / 2.26 / 2.07 / 2.08 ms)
+    const int64_t items = a.npix / per_item;
+    const int64_t most = 262144;
+    const int g = dense_grid(items, most, h->width, per_item);
+    if (p.mode == NL_ST_MEDIAN) NL_HIP(nl::launch_stack_median_coop(a, (int)g, h->stream, &h->last_kernel));
+    else                        NL_HIP(nl::launch_stack_sigma_coop(p.mode, a, (int)g, h->stream, &h->last_kernel));
+    NL_HIP(hipEventRecord(h->ev_dom1, h->stream));
+    NL_HIP(nl::launch_reduce_counters(h->d_partial, nl::kClipSlots, h->d_counters, h->stream));
+    facts->has_counters = p.mode != NL_ST_MEDIAN;
+    return NL_OK;
+}
+
+// one pixel per lane with its column in LDS: every mode at any depth (nl_stack_set_exact(h, 1), and what no other engine takes)
+static int run_exact_columns(nl_stack *h, const PassSetup &p, PassFacts *facts)
+{
+    nl::StackArgs a = p.a;
+    int lanes = 0;
+    size_t lds = 0;
+    if (nl::exact_plan(p.mode, p.weighted, a.n_frames, a.n_pad, 64, &lanes, &lds) != 0)
+        return fail(NL_ERR_TOO_MANY_FRAMES, "%d frames do not fit the per-pixel LDS column (mode %d)", a.n_frames, p.mode);
+    a.tiles = (a.npix + lanes - 1) / lanes;
+    const int grid = (int)(a.tiles < (int64_t)h->max_grid ? a.tiles : (int64_t)h->max_grid);
+    NL_HIP(nl::launch_stack_exact(p.mode, p.weighted, a, lanes, grid, lds, h->stream, &h->last_kernel));
+    NL_HIP(hipEventRecord(h->ev_dom1, h->stream));
+    NL_HIP(nl::launch_reduce_counters(h->d_partial, nl::kClipSlots, h->d_counters, h->stream));
+    facts->has_counters = p.mode != NL_ST_MEDIAN;
+    return NL_OK;
+}
+
+static int run_async_impl(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc);
+
+// A pass that fails half-way (a launch or an event call after the first kernel) must not hand control back with work in
+// flight on the handle's streams and its bookkeeping half-updated: whatever was enqueued is waited for, the scratch
+// sets count as dirty, no list lengths or hints are taken from the broken pass.  The error of the failing call is kept.
+int nl_stack_run_async(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc)
+{
+    const int rc = run_async_impl(h, mode, sigma_low, sigma_high, ref_loc);
+    if (rc != NL_OK && h && h->stream) {
+        const std::string keep = g_err;
+        (void)hipSetDevice(h->device);
+        (void)hipStreamSynchronize(h->stream);
+        if (h->side_stream) (void)hipStreamSynchronize(h->side_stream);
+        (void)hipGetLastError();
+        set_last_pass(h, PassFacts{});
+        h->partial_clean = false;
+        h->pending = false;
+        g_err = keep;
+    }
+    return rc;
+}
+
+static int run_async_impl(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc)
+{
+    NL_CHECK_HANDLE(h);
+    if (mode < NL_ST_MEDIAN || mode > NL_ST_AUTO) return fail(NL_ERR_INVALID_MODE, "invalid stacking mode");
+    if (mode == NL_ST_AUTO) mode = auto_select_mode(h->n_frames);
+    bool weighted = h->has_weights;
+    if (mode == NL_ST_MAD_SIGMA && weighted)
+        return fail(NL_ERR_WEIGHTED_MAD, "MADSigma stacking with weights is still unimplemented");
+    if (mode == NL_ST_LINEAR_FIT || mode == NL_ST_MEDIAN) weighted = false;  // stack.go:158,188-189
+
+    if (h->uploads_pending) {
+        // asynchronous uploads: the pass waits for the last DMA on the device
+        const int last = (h->stage_next + kStageSlots - 1) % kStageSlots;
+        NL_HIP(hipStreamWaitEvent(h->stream, h->stage_done[last], 0));
+        h->uploads_pending = false;
+    }
+
+    nl::StackArgs a{};                  // (no list, no final counters, no bounds: the engines set what they use)
+    a.frames = h->d_frames;
+    a.stride = h->fstride;
+    a.npix = h->npix;
+    a.n_frames = h->n_frames;
+    a.n_pad = next_pow2(h->n_frames);
+    a.weights = weighted ? h->d_weights : nullptr;
+    a.xstat = h->d_xstat;
+    a.sig_lo = sigma_low; a.sig_hi = sigma_high; a.ref_loc = ref_loc;
+    a.out = h->d_out;
+    a.partial = h->d_partial;
+
+    {
+        const int slot = (int)(h->pass_seq % kTimingRing);
+        if (!h->ring_start[slot]) {
+            NL_HIP(hipEventCreateWithFlags(&h->ring_start[slot], hipEventDefault | h->ev_rel));
+            NL_HIP(hipEventCreateWithFlags(&h->ring_stop[slot], hipEventDefault | h->ev_rel));
+            NL_HIP(hipEventCreateWithFlags(&h->ring_dom0[slot], hipEventDefault | h->ev_rel));
+            NL_HIP(hipEventCreateWithFlags(&h->ring_dom1[slot], hipEventDefault | h->ev_rel));
+        }
+        h->ev_start = h->ring_start[slot]; h->ev_stop = h->ring_stop[slot];
+        h->ev_dom0 = h->ring_dom0[slot]; h->ev_dom1 = h->ring_dom1[slot];
+    }
+    const bool timed = !(h->dev_flags & kDevUntimed);
+    h->ring_timed[h->pass_seq % kTimingRing] = timed;
+    if (timed) NL_HIP(hipEventRecord(h->ev_start, h->stream));
+    const bool fused_on = fused_protocol_on();
+    const Engine engine = select_engine(h, mode, weighted, a);
+    const bool sigma_fast = engine == Engine::SigmaFast;
+    // (only while the exact list is short -- the length the last finished pass reported: its replays add their
+    // counts to ONE word, and thousands of workgroups doing that take longer than a reduction kernel)
+    if (sigma_fast && h->fb_hint == 0 && !(h->dev_flags & kDevNoSharedHints)) {
+        unsigned fb = 0, gen = 0;
+        if (hints_load({a.n_frames, a.npix, mode, weighted}, &fb, &gen)) { h->fb_hint = fb; h->gen_hint = gen; }
+    }
+    h->last_weighted = weighted;
+    const bool fused = fused_on && !(h->dev_flags & kDevPlainProtocol) && sigma_fast && a.n_frames > 8 && h->fb_hint != 0 &&
+                       h->fb_hint - 1u < kFusedMaxList && nl::coop_supported(mode, weighted, a.n_frames) != 0;
+    // Every event recorded on the pass's stream costs a few microseconds of it (three of them: 17 us of a 277 us pass on
+    // a 512-row tile, tools/wall_probe.py): a fused pass that finds its scratch set clean has nothing between "start" and
+    // "dominant kernel starts", and the event behind the dominant kernel is also the fork of the side stream.
+    const bool one_start = timed && fused && h->sets_clean;
+    h->ring_dom0_is_start[h->pass_seq % kTimingRing] = one_start;
+    if (one_start) h->ev_dom0 = h->ev_start;
+    if (fused) {
+        if (h->sets_clean) h->cur_set ^= 1;
+        else NL_HIP(hipMemsetAsync(h->d_sets, 0, 2 * kScratchBytes, h->stream));
+        h->d_partial = h->d_sets + (size_t)h->cur_set * nl::kScratchWords;
+        h->d_fb_count = reinterpret_cast<unsigned *>(h->d_partial + 2 * nl::kClipSlots);
+        a.partial = h->d_partial;
+        a.final = h->d_counters;
+        a.zero_next = h->d_sets + (size_t)(h->cur_set ^ 1) * nl::kScratchWords;
+    } else if (!h->partial_clean) {
+        NL_HIP(hipMemsetAsync(h->d_partial, 0, kScratchBytes, h->stream));
+    }
+    h->sets_clean = false;                       // until this pass is enqueued completely
+    const bool keep_clean = h->partial_clean && mode == NL_ST_MEAN;     // (a mean pass does not touch the scratch set)
+    h->partial_clean = false;
+    if (timed && !one_start) NL_HIP(hipEventRecord(h->ev_dom0, h->stream));
+
+    const PassSetup p{mode, weighted, timed, fused, a};
+    PassFacts facts;
+    int rc = NL_OK;
+    switch (engine) {
+    case Engine::Mean:            rc = run_mean(h, p, &facts); break;
+    case Engine::MedianRegisters: rc = run_median(h, p, false); break;
+    case Engine::MedianMultiLane: rc = run_median(h, p, true); break;
+    case Engine::Listed:          rc = run_listed(h, p, &facts); break;
+    case Engine::SigmaFast:       rc = run_sigma_fast(h, p, &facts); break;
+    case Engine::WeightedTile:    rc = run_weighted_tile(h, p, &facts); break;
+    case Engine::DenseReplay:     rc = run_dense_replay(h, p, &facts); break;
+    case Engine::ExactColumns:    rc = run_exact_columns(h, p, &facts); break;
+    }
+    if (rc != NL_OK) return rc;
+    NL_HIP(hipEventRecord(h->ev_stop, h->stream));
+    set_last_pass(h, facts);
+    h->partial_clean = facts.zeroed_behind || keep_clean;
+    h->pass_seq++;
+    h->last_mode = mode;
+    h->pending = true;
+    return NL_OK;
+}
+
+int nl_stack_finish(nl_stack_t *h, float *out_host, int64_t *clip_low, int64_t *clip_high)
+{
+    NL_CHECK_HANDLE(h);
+    unsigned long long c[4] = {0, 0, 0, 0};
+    // (a fast sigma / winsorized pass leaves its list lengths behind the totals: c[2] = exact list | generic list << 32)
+    if (h->last_has_counters && (clip_low || clip_high || h->last_lists))
+        NL_HIP(hipMemcpyAsync(c, h->d_counters, h->last_lists ? 3 * sizeof c[0] : 2 * sizeof c[0], hipMemcpyDeviceToHost, h->stream));
+    if (out_host)
+        NL_HIP(hipMemcpyAsync(out_host + (int64_t)h->row0 * h->width, h->d_out,
+                              (size_t)h->npix * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    NL_HIP(hipStreamSynchronize(h->stream));
+    h->pending = false;
+    if (h->last_has_counters && h->last_lists) {
+        h->fb_hint = (unsigned)(c[2] & 0xffffffffull) + 1u;
+        h->gen_hint = (unsigned)(c[2] >> 32) + 1u;
+        hints_store({h->n_frames, h->npix, h->last_mode, h->last_weighted}, h->fb_hint, h->gen_hint);
+    }
+    if (clip_low) *clip_low = (int64_t)c[0];
+    if (clip_high) *clip_high = (int64_t)c[1];
+    return NL_OK;
+}
+
+int nl_stack_run(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc,
+                 float *out_host, int64_t *clip_low, int64_t *clip_high)
+{
+    int rc = nl_stack_run_async(h, mode, sigma_low, sigma_high, ref_loc);
+    if (rc != NL_OK) return rc;
+    return nl_stack_finish(h, out_host, clip_low, clip_high);
+}
+
+// GPU time from event `from` to event `to` of the last pass, once `to` has completed; -1 where unavailable
+static float elapsed_ms(nl_stack_t *h, hipEvent_t from, hipEvent_t to)
+{
+    float ms = -1.0f;
+    if (hipSetDevice(h->device) != hipSuccess || hipEventSynchronize(to) != hipSuccess ||
+        hipEventElapsedTime(&ms, from, to) != hipSuccess)
+        return -1.0f;
+    return ms;
+}
+
+float nl_stack_last_dominant_kernel_ms(nl_stack_t *h) { return h && h->ev_dom0 ? elapsed_ms(h, h->ev_dom0, h->ev_dom1) : -1.0f; }
+
+int nl_stack_set_exact(nl_stack_t *h, int on)
+{
+    NL_CHECK_HANDLE(h);
+    if (on < 0 || on > 4) return fail(NL_ERR_INVALID_ARG, "set_exact: unknown flavour %d (0 ... 4)", on);
+    // (a switch whose code was removed must not fall through to another kernel silently: an A/B run would time the same
+    // kernel twice)
+    if (on == 4)
+        return fail(NL_ERR_INVALID_ARG, "set_exact: flavour 4 (four pixels per wave) was removed with the experiments build");
+    h->force_exact = on != 0;
+    h->exact_flavour = on;
+    return NL_OK;
+}
+
+int nl_stack_set_dev_flags(nl_stack_t *h, unsigned flags)
+{
+    NL_CHECK_HANDLE(h);
+    if (flags & kDevRemovedPasses)
+        return fail(NL_ERR_INVALID_ARG, "set_dev_flags: switches 1024 / 2048 (split / persistent LDS-column pass) were removed with the "
+                                        "experiments build");
+    h->dev_flags = flags;
+    return NL_OK;
+}
+
+// list lengths of the last fast pass: a sigma / winsorized pass leaves them behind its totals (d_counters[2] = exact list |
+// generic list << 32 -- its own counters may be zeroed again by then), the other fast passes keep them in the scratch set
+static int64_t last_list_length(nl_stack_t *h, int which)
+{
+    if (hipSetDevice(h->device) != hipSuccess) return -1;
+    if (h->last_lists) {
+        unsigned long long c = 0;
+        if (hipMemcpyAsync(&c, h->d_counters + 2, sizeof c, hipMemcpyDeviceToHost, h->stream) != hipSuccess) return -1;
+        if (hipStreamSynchronize(h->stream) != hipSuccess) return -1;
+        return which == 0 ? (int64_t)(c & 0xffffffffull) : (int64_t)(c >> 32);
+    }
+    unsigned c = 0;
+    if (hipMemcpyAsync(&c, h->d_fb_count + which, sizeof c, hipMemcpyDeviceToHost, h->stream) != hipSuccess) return -1;
+    if (hipStreamSynchronize(h->stream) != hipSuccess) return -1;
+    return (int64_t)c;
+}
+
+int64_t nl_stack_last_fallback_pixels(nl_stack_t *h)
+{
+    if (!h || !h->last_used_fast || !h->d_fb_count) return 0;
+    return last_list_length(h, 0);
+}
+
+int nl_stack_last_pass_protocol(nl_stack_t *h)
+{
+    if (!h) return 0;
+    return (h->last_fused ? 1 : 0) | (h->last_tail_fused ? 2 : 0);
+}
+
+int64_t nl_stack_last_generic_pixels(nl_stack_t *h)
+{
+    if (!h || !h->last_used_fast || !h->d_fb_count || !h->d_gen_list) return 0;
+    return last_list_length(h, 1);
+}
+
+int nl_stack_linfit_stage_counts(nl_stack_t *h, unsigned *counts, int n)
+{
+    if (!h || !counts || n <= 0 || !h->d_lf_count || h->last_mode != NL_ST_LINEAR_FIT || !h->last_used_fast) return 0;
+    if (hipSetDevice(h->device) != hipSuccess) return -1;
+    unsigned c[nl::kLinfitCounters] = {};
+    if (hipMemcpyAsync(c, h->d_lf_count, sizeof c, hipMemcpyDeviceToHost, h->stream) != hipSuccess) return -1;
+    if (hipStreamSynchronize(h->stream) != hipSuccess) return -1;
+    const int m = n < nl::kLinfitCounters ? n : nl::kLinfitCounters;
+    for (int i = 0; i < m; i++) counts[i] = c[i];
+    return m;
+}
+
+// GPU times of a pass that is `back` passes old (0 = the last one enqueued); -1 where unavailable
+int nl_stack_pass_times(nl_stack_t *h, int back, float *pass_ms, float *dominant_ms)
+{
+    NL_CHECK_HANDLE(h);
+    if (back < 0 || back >= kTimingRing || (int64_t)back >= h->pass_seq)
+        return fail(NL_ERR_INVALID_ARG, "pass_times: pass %d back is not in the ring of %d", back, kTimingRing);
+    const int slot = (int)((h->pass_seq - 1 - back) % kTimingRing);
+    if (!h->ring_timed[slot])
+        return fail(NL_ERR_INVALID_ARG, "pass_times: pass %d back ran without timing events (developer switch 32)", back);
+    NL_HIP(hipEventSynchronize(h->ring_stop[slot]));
+    float ms = -1.0f;
+    if (pass_ms) {
+        NL_HIP(hipEventElapsedTime(&ms, h->ring_start[slot], h->ring_stop[slot]));
+        *pass_ms = ms;
+    }
+    if (dominant_ms) {
+        NL_HIP(hipEventElapsedTime(&ms, h->ring_dom0_is_start[slot] ? h->ring_start[slot] : h->ring_dom0[slot], h->ring_dom1[slot]));
+        *dominant_ms = ms;
+    }
+    return NL_OK;
+}
+
+// enqueues, behind the last pass on the handle's stream, a 16-byte device-to-device copy of its
+// {clip_low, clip_high} totals into a caller-owned device buffer (e.g. the tensor an RCCL
+// all-reduce runs on): no host round trip between the pass and the reduction
+int nl_stack_copy_counters_async(nl_stack_t *h, void *device_dst)
+{
+    NL_CHECK_HANDLE(h);
+    if (!device_dst) return fail(NL_ERR_INVALID_ARG, "copy_counters_async: null destination");
+    if (h->last_has_counters)
+        NL_HIP(hipMemcpyAsync(device_dst, h->d_counters, 2 * sizeof(unsigned long long), hipMemcpyDeviceToDevice, h->stream));
+    else
+        NL_HIP(hipMemsetAsync(device_dst, 0, 2 * sizeof(unsigned long long), h->stream));
+    return NL_OK;
+}
+
+void *nl_stack_stream(nl_stack_t *h) { return h ? (void *)h->stream : nullptr; }
+void *nl_stack_counters_device_ptr(nl_stack_t *h) { return h ? (void *)h->d_counters : nullptr; }
+
+int nl_stack_set_counters_buffer(nl_stack_t *h, void *device_buf)
+{
+    NL_CHECK_HANDLE(h);
+    h->d_counters = device_buf ? static_cast<unsigned long long *>(device_buf) : h->d_counters_own;
+    return NL_OK;
+}
+
+int nl_stack_order_stream_after(nl_stack_t *h, void *hip_stream)
+{
+    NL_CHECK_HANDLE(h);
+    if (!hip_stream) return fail(NL_ERR_INVALID_ARG, "order_stream_after: null stream");
+    // a ring of events: the waiting stream may still be working off an older one when the next pass is enqueued
+    const int slot = h->order_seq++ % kOrderRing;
+    if (!h->ev_order[slot]) NL_HIP(hipEventCreateWithFlags(&h->ev_order[slot], hipEventDisableTiming | h->ev_rel));
+    NL_HIP(hipEventRecord(h->ev_order[slot], h->stream));
+    NL_HIP(hipStreamWaitEvent(static_cast<hipStream_t>(hip_stream), h->ev_order[slot], 0));
+    return NL_OK;
+}
+
+float nl_stack_last_kernel_ms(nl_stack_t *h) { return h && h->ev_start ? elapsed_ms(h, h->ev_start, h->ev_stop) : -1.0f; }
+
+// stackfindsigma.go:48-98 (commented-out reference code = the spec)
+int nl_stack_find_sigmas(nl_stack_t *h, int mode, float ref_loc,
+                         float clip_perc_low, float clip_perc_high,
+                         nl_reduce_fn reduce, void *user,
+                         float *out_host, int64_t *clip_low, int64_t *clip_high,
+                         float *sigma_low, float *sigma_high, int *passes)
+{
+    NL_CHECK_HANDLE(h);
+    if (mode == NL_ST_AUTO) mode = auto_select_mode(h->n_frames);
+    if (mode < NL_ST_MEDIAN || mode > NL_ST_LINEAR_FIT) return fail(NL_ERR_INVALID_MODE, "invalid stacking mode");
+    // the counters cover the samples the percentages are taken of: with a reducer the whole
+    // image (every tile contributes), without one only this handle's tile
+    const int64_t total = reduce ? (int64_t)h->width * h->height * (int64_t)h->n_frames
+                                 : h->npix * (int64_t)h->n_frames;
+    int n_pass = 0;
+    // one pass with the given sigmas; c = its clip counters (with a reducer: over every tile)
+    auto counted_pass = [&](float lo, float hi, int64_t c[2]) {
+        int rc = nl_stack_run(h, mode, lo, hi, ref_loc, nullptr, &c[0], &c[1]);
+        if (rc != NL_OK) return rc;
+        n_pass++;
+        if (reduce && (rc = reduce(c, user)) != 0)
+            return fail(NL_ERR_INVALID_ARG, "counter reduction callback failed (%d)", rc);
+        return NL_OK;
+    };
+    // the outcome: the counters and sigmas of the pass whose result the handle holds
+    auto report = [&](int64_t lo, int64_t hi, float sig_lo, float sig_hi) {
+        if (clip_low) *clip_low = lo;
+        if (clip_high) *clip_high = hi;
+        if (sigma_low) *sigma_low = sig_lo;
+        if (sigma_high) *sigma_high = sig_hi;
+        if (passes) *passes = n_pass;
+        return out_host ? nl_stack_finish(h, out_host, nullptr, nullptr) : NL_OK;
+    };
+    if (mode != NL_ST_SIGMA && mode != NL_ST_WINSOR_SIGMA) {
+        // stackfindsigma.go:40-46: Newton's method for the linear fit; the other modes "do not support
+        // sigmas" and are stacked once with 0, 0
+        nl::SigmaNewton nw(clip_perc_low, total);
+        const bool newton = mode == NL_ST_LINEAR_FIT;
+        for (;;) {
+            int64_t c[2] = {0, 0};
+            int rc = counted_pass(newton ? nw.next_low() : 0.0f, newton ? nw.next_high() : 0.0f, c);
+            if (rc != NL_OK) return rc;
+            const int st = newton ? nw.step(c[0], c[1]) : 1;
+            if (st == 0) continue;
+            if (st == 2) {                       // a probe pass overwrote the result: re-make the base pass
+                rc = nl_stack_run(h, mode, nw.sig_low, nw.sig_high, ref_loc, nullptr, nullptr, nullptr);
+                if (rc != NL_OK) return rc;
+            }
+            if (!newton) return report(c[0], c[1], 0.0f, 0.0f);
+            return report(nw.base_lo, nw.base_hi, nw.sig_low, nw.sig_high);
+        }
+    }
+    nl::SigmaBisection bis(clip_perc_low, clip_perc_high, total);
+    for (;;) {
+        int64_t c[2] = {0, 0};
+        const int rc = counted_pass(bis.low_mid, bis.high_mid, c);
+        if (rc != NL_OK) return rc;
+        if (bis.step(c[0], c[1])) return report(c[0], c[1], bis.low_mid, bis.high_mid);
+    }
+}
+
+// StackIncremental / StackIncrementalFinalize, stack.go:924-944
+int nl_stack_accumulate(nl_stack_t *h, float weight, int first)
+{
+    NL_CHECK_HANDLE(h);
+    if (!h->d_acc) NL_HIP(dev_malloc(&h->d_acc, (size_t)h->npix * sizeof(float)));
+    NL_HIP(nl::launch_axpy(h->d_acc, h->d_out, weight, first, h->npix, h->stream));
+    NL_HIP(hipStreamSynchronize(h->stream));
+    return NL_OK;
+}
+
+int nl_stack_accumulate_finalize(nl_stack_t *h, float weight_sum, float *out_host)
+{
+    NL_CHECK_HANDLE(h);
+    if (!h->d_acc) return fail(NL_ERR_INVALID_ARG, "accumulate_finalize before accumulate");
+    volatile float factor = 1.0f / weight_sum;
+    NL_HIP(nl::launch_scale(h->d_acc, factor, h->npix, h->stream));
+    if (out_host)
+        NL_HIP(hipMemcpyAsync(out_host + (int64_t)h->row0 * h->width, h->d_acc,
+                              (size_t)h->npix * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    NL_HIP(hipStreamSynchronize(h->stream));
+    return NL_OK;
+}
+
+}  // extern "C"

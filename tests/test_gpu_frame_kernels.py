@@ -336,3 +336,16 @@ def test_median_filter_mask_argument_errors(nl):
         nl.median_filter_mask(img, np.arange(40, dtype=np.int32))          # more than 32 offsets
     with pytest.raises(capi.NlError):
         nl.median_filter_mask(img, np.zeros(0, np.int32))
+
+
+def test_median_filters_reject_an_out_of_range_device(nl):
+    # the device ordinal is checked like every other entry point's (not handed to hipSetDevice as it is)
+    from nightlight_amd import capi
+    bad = capi.device_count()
+    img = np.zeros(64, np.float32)
+    with pytest.raises(capi.NlError) as e:
+        nl.median_filter_mask(img, np.array([-1, 0, 1], np.int32), device=bad)
+    assert e.value.code == capi.ERR_INVALID_ARG and "device %d out of range" % bad in e.value.message
+    with pytest.raises(capi.NlError) as e:
+        nl.median_filter_3x3(img, 8, 8, device=bad)
+    assert e.value.code == capi.ERR_INVALID_ARG and "device %d out of range" % bad in e.value.message
