@@ -8,8 +8,6 @@
 
 namespace nl {
 
-constexpr int kMlNS = 128;     // samples per lane
-
 template <int CTRL>
 __device__ __forceinline__ float dpp_f(float x)
 {

@@ -20,7 +20,7 @@
 // sample read exactly once with 256-byte coalesced rows per frame); in this
 // exact form the kernel is limited by per-lane LDS latency and VALU issue,
 // see DESIGN.md section 4.
-#include "stack_kernels.h"
+#include "launch_common.hpp"
 
 namespace nl {
 
@@ -423,30 +423,13 @@ __global__ __launch_bounds__(256) void reduce_counters_kernel(unsigned long long
 }
 
 // ---- host-side launcher ----------------------------------------------------
-template <int MODE, bool W, int LANES>
-static hipError_t launch_exact(const StackArgs &args, int grid, size_t lds_bytes, hipStream_t stream)
-{
-    auto kern = stack_exact_kernel<MODE, W, LANES>;
-    if (lds_bytes > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)lds_bytes);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64), lds_bytes, stream, args);
-    return hipGetLastError();
-}
-
 template <int MODE, bool W>
-static hipError_t launch_exact_lanes(StackArgs &args, int lanes, int grid, size_t lds_bytes,
-                                     hipStream_t stream)
+static hipError_t launch_exact(const StackArgs &args, int lanes, int grid, size_t lds_bytes, hipStream_t stream)
 {
-    switch (lanes) {
-    case 64: return launch_exact<MODE, W, 64>(args, grid, lds_bytes, stream);
-    case 32: return launch_exact<MODE, W, 32>(args, grid, lds_bytes, stream);
-    case 16: return launch_exact<MODE, W, 16>(args, grid, lds_bytes, stream);
-    default: return launch_exact<MODE, W, 4>(args, grid, lds_bytes, stream);
-    }
+    Launcher L(stream);
+    L(lanes == 64 ? stack_exact_kernel<MODE, W, 64> : lanes == 32 ? stack_exact_kernel<MODE, W, 32>
+      : lanes == 16 ? stack_exact_kernel<MODE, W, 16> : stack_exact_kernel<MODE, W, 4>, grid, 64, lds_bytes, args);
+    return L.err;
 }
 
 int exact_plan(int mode, bool weighted, int n_frames, int n_pad, int max_lanes, int *lanes,
@@ -467,33 +450,33 @@ int exact_plan(int mode, bool weighted, int n_frames, int n_pad, int max_lanes, 
     return -1;
 }
 
-hipError_t launch_stack_exact(int mode, bool weighted, StackArgs &args, int lanes, int grid,
+hipError_t launch_stack_exact(int mode, bool weighted, const StackArgs &args, int lanes, int grid,
                               size_t lds_bytes, hipStream_t stream, const char **name)
 {
     switch (mode) {
     case NL_ST_MEDIAN:
         *name = "stack_exact_kernel<median>";
-        return launch_exact_lanes<NL_ST_MEDIAN, false>(args, lanes, grid, lds_bytes, stream);
+        return launch_exact<NL_ST_MEDIAN, false>(args, lanes, grid, lds_bytes, stream);
     case NL_ST_SIGMA:
         if (weighted) {
             *name = "stack_exact_kernel<sigma,weighted>";
-            return launch_exact_lanes<NL_ST_SIGMA, true>(args, lanes, grid, lds_bytes, stream);
+            return launch_exact<NL_ST_SIGMA, true>(args, lanes, grid, lds_bytes, stream);
         }
         *name = "stack_exact_kernel<sigma>";
-        return launch_exact_lanes<NL_ST_SIGMA, false>(args, lanes, grid, lds_bytes, stream);
+        return launch_exact<NL_ST_SIGMA, false>(args, lanes, grid, lds_bytes, stream);
     case NL_ST_WINSOR_SIGMA:
         if (weighted) {
             *name = "stack_exact_kernel<winsor,weighted>";
-            return launch_exact_lanes<NL_ST_WINSOR_SIGMA, true>(args, lanes, grid, lds_bytes, stream);
+            return launch_exact<NL_ST_WINSOR_SIGMA, true>(args, lanes, grid, lds_bytes, stream);
         }
         *name = "stack_exact_kernel<winsor>";
-        return launch_exact_lanes<NL_ST_WINSOR_SIGMA, false>(args, lanes, grid, lds_bytes, stream);
+        return launch_exact<NL_ST_WINSOR_SIGMA, false>(args, lanes, grid, lds_bytes, stream);
     case NL_ST_MAD_SIGMA:
         *name = "stack_exact_kernel<mad>";
-        return launch_exact_lanes<NL_ST_MAD_SIGMA, false>(args, lanes, grid, lds_bytes, stream);
+        return launch_exact<NL_ST_MAD_SIGMA, false>(args, lanes, grid, lds_bytes, stream);
     case NL_ST_LINEAR_FIT:
         *name = "stack_exact_kernel<linearfit>";
-        return launch_exact_lanes<NL_ST_LINEAR_FIT, false>(args, lanes, grid, lds_bytes, stream);
+        return launch_exact<NL_ST_LINEAR_FIT, false>(args, lanes, grid, lds_bytes, stream);
     default:
         return hipErrorInvalidValue;
     }

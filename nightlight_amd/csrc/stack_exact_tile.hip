@@ -27,7 +27,7 @@
 //                                      the clip swaps
 // Same fp32 operations in the same order as the reference (no FMA contraction): every output
 // bit and both counters equal the oracle's.
-#include "stack_kernels.h"
+#include "launch_common.hpp"
 
 namespace nl {
 
@@ -353,36 +353,24 @@ int tile_supported(int mode, bool weighted, int n_frames)
     return tile_lds_bytes(n_frames, weighted) != 0 ? 1 : 0;
 }
 
-template <bool WINSOR, bool W, class IDX>
-static hipError_t launch_tile(const StackArgs &args, int grid, size_t lds, hipStream_t stream)
-{
-    auto kern = stack_sigma_tile_kernel<WINSOR, W, IDX>;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64), lds, stream, args);
-    return hipGetLastError();
-}
-
 hipError_t launch_stack_sigma_tile(int mode, const StackArgs &args, int grid, hipStream_t stream, const char **name)
 {
     const bool weighted = args.weights != nullptr;
     const size_t lds = tile_lds_bytes(args.n_frames, weighted);
     if (!lds) return hipErrorInvalidValue;
     const bool winsor = mode == NL_ST_WINSOR_SIGMA;
-    if (!weighted) {
+    if (!weighted)
         *name = winsor ? "stack_sigma_tile_kernel<winsor>" : "stack_sigma_tile_kernel<sigma>";
-        return winsor ? launch_tile<true, false, unsigned char>(args, grid, lds, stream)
-                      : launch_tile<false, false, unsigned char>(args, grid, lds, stream);
-    }
-    *name = winsor ? "stack_sigma_tile_kernel<winsor,weighted>" : "stack_sigma_tile_kernel<sigma,weighted>";
-    if (args.n_frames <= 256)
-        return winsor ? launch_tile<true, true, unsigned char>(args, grid, lds, stream)
-                      : launch_tile<false, true, unsigned char>(args, grid, lds, stream);
-    return winsor ? launch_tile<true, true, unsigned short>(args, grid, lds, stream)
-                  : launch_tile<false, true, unsigned short>(args, grid, lds, stream);
+    else
+        *name = winsor ? "stack_sigma_tile_kernel<winsor,weighted>" : "stack_sigma_tile_kernel<sigma,weighted>";
+    Launcher L(stream);
+    with_bool(winsor, [&](auto WS) {
+        constexpr bool WINSOR = decltype(WS)::value;
+        L(!weighted ? stack_sigma_tile_kernel<WINSOR, false, unsigned char>
+          : args.n_frames <= 256 ? stack_sigma_tile_kernel<WINSOR, true, unsigned char>
+          : stack_sigma_tile_kernel<WINSOR, true, unsigned short>, grid, 64, lds, args);
+    });
+    return L.err;
 }
 
 }  // namespace nl

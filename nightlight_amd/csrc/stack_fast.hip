@@ -32,9 +32,10 @@
 // mask.  A wave that leaves this regime (NaN borders, heavy clipping) puts its
 // pixels on the "generic" list; the GENERIC instantiation re-does those from
 // the list with every position masked by its rank.
-#include <string>
+#include <algorithm>
 
 #include "fast_common.hpp"
+#include "launch_common.hpp"
 
 namespace nl {
 
@@ -392,60 +393,32 @@ int fast_supported(int mode, bool weighted, int n_frames, int64_t npix)
     return ((mode == NL_ST_SIGMA || mode == NL_ST_WINSOR_SIGMA) && !weighted) ? 1 : 0;
 }
 
-template <int NS>
-static void launch_median(const StackArgs &args, const FastArgs &fargs, unsigned blocks, hipStream_t stream,
-                          const char **name, hipEvent_t dominant_done)
-{
-    static const std::string names[2] = {"stack_median_fast_kernel<" + std::to_string(NS) + ", false>",
-                                         "stack_median_fast_kernel<" + std::to_string(NS) + ", true>"};
-    FastArgs f = fargs;
-    f.in_list = nullptr;
-    f.in_count = nullptr;
-    f.in_capacity = 0;
-    const bool window = NS >= 32 && args.n_frames > NS - kMedianPad && fargs.gen_list != nullptr &&
-                        args.npix < ((int64_t)1 << 29);
-    if constexpr (NS >= 32) {
-        if (window) {
-            *name = names[1].c_str();
-            hipLaunchKernelGGL((stack_median_fast_kernel<NS, true>), dim3(blocks), dim3(256), 0, stream, args, f);
-            if (dominant_done) (void)hipEventRecord(dominant_done, stream);
-            f.in_list = fargs.gen_list;
-            f.in_count = fargs.gen_count;
-            f.in_capacity = fargs.gen_capacity;
-            const unsigned gblocks = blocks < kGenericGrid ? blocks : kGenericGrid;
-            hipLaunchKernelGGL((stack_median_fast_kernel<NS, false>), dim3(gblocks), dim3(256), 0, stream, args, f);
-            return;
-        }
-    }
-    *name = names[0].c_str();
-    hipLaunchKernelGGL((stack_median_fast_kernel<NS, false>), dim3(blocks), dim3(256), 0, stream, args, f);
-    if (dominant_done) (void)hipEventRecord(dominant_done, stream);
-}
+constexpr char kMedianFastName[] = "stack_median_fast_kernel";
+constexpr char kMadFastName[] = "stack_mad_fast_kernel";
+constexpr char kSigmaFastName[] = "stack_sigma_fast_kernel";
 
 hipError_t launch_stack_median_fast(const StackArgs &args, const FastArgs &fargs, hipStream_t stream,
                                     const char **name, hipEvent_t dominant_done)
 {
-    const unsigned blocks = (unsigned)((args.npix + 255) / 256);
-    const int n = args.n_frames;
-    if (n <= 8)        launch_median<8>(args, fargs, blocks, stream, name, dominant_done);
-    else if (n <= 16)  launch_median<16>(args, fargs, blocks, stream, name, dominant_done);
-    else if (n <= 32)  launch_median<32>(args, fargs, blocks, stream, name, dominant_done);
-    else if (n <= 48)  launch_median<48>(args, fargs, blocks, stream, name, dominant_done);
-    else if (n <= 64)  launch_median<64>(args, fargs, blocks, stream, name, dominant_done);
-    else if (n <= 80)  launch_median<80>(args, fargs, blocks, stream, name, dominant_done);
-    else if (n <= 96)  launch_median<96>(args, fargs, blocks, stream, name, dominant_done);
-    else if (n <= 112) launch_median<112>(args, fargs, blocks, stream, name, dominant_done);
-    else               launch_median<128>(args, fargs, blocks, stream, name, dominant_done);
-    return hipGetLastError();
-}
-
-
-template <int NS>
-static void launch_mad(const StackArgs &args, const FastArgs &f, unsigned blocks, hipStream_t stream, const char **name)
-{
-    static const std::string nm = "stack_mad_fast_kernel<" + std::to_string(NS) + ">";
-    *name = nm.c_str();
-    hipLaunchKernelGGL(stack_mad_fast_kernel<NS>, dim3(blocks), dim3(256), 0, stream, args, f);
+    Launcher L(stream);
+    const unsigned blocks = pixel_grid(args.npix);
+    const FastArgs f = whole_tile(fargs);
+    with_class<8, 16, 32, 48, 64, 80, 96, 112, 128>(args.n_frames, [&](auto C) {
+        constexpr int NS = decltype(C)::value;
+        if constexpr (NS >= 32) {
+            if (args.n_frames > NS - kMedianPad && fargs.gen_list != nullptr && args.npix < ((int64_t)1 << 29)) {
+                *name = kernel_name<kMedianFastName, NS, true>();
+                L(stack_median_fast_kernel<NS, true>, blocks, 256, 0, args, f);
+                L.record(dominant_done);
+                L(stack_median_fast_kernel<NS, false>, std::min(blocks, kGenericGrid), 256, 0, args, over_generic_list(f));
+                return;
+            }
+        }
+        *name = kernel_name<kMedianFastName, NS, false>();
+        L(stack_median_fast_kernel<NS, false>, blocks, 256, 0, args, f);
+        L.record(dominant_done);
+    });
+    return L.err;
 }
 
 int mad_fast_supported(int mode, bool weighted, int n_frames, int64_t npix)
@@ -455,63 +428,34 @@ int mad_fast_supported(int mode, bool weighted, int n_frames, int64_t npix)
 
 hipError_t launch_stack_mad_fast(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name)
 {
-    const unsigned blocks = (unsigned)((args.npix + 255) / 256);
-    const int n = args.n_frames;
-    if (n <= 8)        launch_mad<8>(args, fargs, blocks, stream, name);
-    else if (n <= 16)  launch_mad<16>(args, fargs, blocks, stream, name);
-    else if (n <= 32)  launch_mad<32>(args, fargs, blocks, stream, name);
-    else if (n <= 48)  launch_mad<48>(args, fargs, blocks, stream, name);
-    else if (n <= 64)  launch_mad<64>(args, fargs, blocks, stream, name);
-    else if (n <= 80)  launch_mad<80>(args, fargs, blocks, stream, name);
-    else if (n <= 96)  launch_mad<96>(args, fargs, blocks, stream, name);
-    else if (n <= 112) launch_mad<112>(args, fargs, blocks, stream, name);
-    else if (n < 114 || !fargs.gen_list) launch_mad<128>(args, fargs, blocks, stream, name);
-    else {
+    Launcher L(stream);
+    const unsigned blocks = pixel_grid(args.npix);
+    if (args.n_frames >= 114 && fargs.gen_list) {
         *name = "stack_mad_bitonic_kernel";
-        FastArgs f = fargs;
-        f.in_list = nullptr;
-        f.in_count = nullptr;
-        f.in_capacity = 0;
-        hipLaunchKernelGGL(stack_mad_bitonic_kernel, dim3(blocks), dim3(256), 0, stream, args, f);
+        L(stack_mad_bitonic_kernel, blocks, 256, 0, args, whole_tile(fargs));
         // the pixels with fewer than 114 samples (aligned frames' borders): two sorts, second read
-        f.in_list = fargs.gen_list;
-        f.in_count = fargs.gen_count;
-        f.in_capacity = fargs.gen_capacity;
-        const unsigned gblocks = blocks < kGenericGrid ? blocks : kGenericGrid;
-        hipLaunchKernelGGL(stack_mad_fast_kernel<128>, dim3(gblocks), dim3(256), 0, stream, args, f);
+        L(stack_mad_fast_kernel<128>, std::min(blocks, kGenericGrid), 256, 0, args, over_generic_list(fargs));
+        return L.err;
     }
-    return hipGetLastError();
+    with_class<8, 16, 32, 48, 64, 80, 96, 112, 128>(args.n_frames, [&](auto C) {
+        constexpr int NS = decltype(C)::value;
+        *name = kernel_name<kMadFastName, NS>();
+        L(stack_mad_fast_kernel<NS>, blocks, 256, 0, args, fargs);
+    });
+    return L.err;
 }
 
 // smallest network size with a zonal instantiation
 constexpr int kZonalMinSize = 16;
 
-// kernel names as rocprofv3 prints them (template arguments: NS, ZONAL, WINSOR, TIGHT, RECORD)
-template <int NS, bool ZONAL, bool WINSOR, bool TIGHT>
-static const char *sigma_kernel_name()
-{
-    static const std::string name = std::string("stack_sigma_fast_kernel<") + std::to_string(NS) + ", " +
-                                    (ZONAL ? "true" : "false") + ", " + (WINSOR ? "true" : "false") + ", " +
-                                    (TIGHT ? "true" : "false") + ", false, false>";
-    return name.c_str();
-}
-
-// The nested launchers (stack_fast_mlg.hip, stack_fast_mlz.hip) end in hipGetLastError(), which CLEARS
-// the pending error: their result is kept here (first error wins) so that a failed launch of the
-// dominant kernel or of the generic pass reaches nl_stack_run instead of being erased.
-static inline void keep_first(hipError_t &acc, hipError_t e) { if (acc == hipSuccess) acc = e; }
-
 template <int NS, bool WINSOR>
-static hipError_t launch_pair(const StackArgs &args, const FastArgs &fargs, unsigned tile_blocks,
-                              hipStream_t stream, const char **name, hipEvent_t dominant_done,
-                              AfterDominant after, void *user,
+static hipError_t launch_pair(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name,
+                              hipEvent_t dominant_done, AfterDominant after, void *user,
                               const StackArgs *fused_replay, unsigned fused_replay_blocks)
 {
-    hipError_t err = hipSuccess;
-    FastArgs f = fargs;
-    f.in_list = nullptr;
-    f.in_count = nullptr;
-    f.in_capacity = 0;
+    Launcher L(stream);
+    const unsigned tile_blocks = pixel_grid(args.npix);
+    FastArgs f = whole_tile(fargs);
     if constexpr (NS >= kZonalMinSize) {
         f.cont_list = nullptr; f.cont_state = nullptr; f.cont_count = nullptr; f.cont_region = 0; f.in_state = nullptr;
         f.in_region = f.in_regions = f.in_group = 0;
@@ -526,17 +470,12 @@ static hipError_t launch_pair(const StackArgs &args, const FastArgs &fargs, unsi
         }
         // (workgroups of 64 or 128 threads instead of 256 -- no wave waits for its workgroup's slowest at the barriers of the
         // hand-over lists -- measured the same within the noise at 32 and 128 frames, round 4)
-        if (args.n_frames == NS) {
-            *name = sigma_kernel_name<NS, true, WINSOR, true>();
-            hipLaunchKernelGGL((stack_sigma_fast_kernel<NS, true, WINSOR, true>), dim3(tile_blocks), dim3(256), 0,
-                               stream, args, f);
-        } else {
-            *name = sigma_kernel_name<NS, true, WINSOR, false>();
-            hipLaunchKernelGGL((stack_sigma_fast_kernel<NS, true, WINSOR, false>), dim3(tile_blocks), dim3(256), 0,
-                               stream, args, f);
-        }
-        keep_first(err, hipGetLastError());
-        if (dominant_done) keep_first(err, hipEventRecord(dominant_done, stream));
+        with_bool(args.n_frames == NS, [&](auto T) {
+            constexpr bool TIGHT = decltype(T)::value;
+            *name = kernel_name<kSigmaFastName, NS, true, WINSOR, TIGHT, false, false>();
+            L(stack_sigma_fast_kernel<NS, true, WINSOR, TIGHT>, tile_blocks, 256, 0, args, f);
+        });
+        L.record(dominant_done);
         if constexpr (WINSOR) {
             // winsorization cascade (stack_fast_sigma_impl.hpp): the dominant kernel above stopped at its budget; two more
             // stages over the continuation lists, in freshly packed waves, the last one without a budget
@@ -560,11 +499,9 @@ static hipError_t launch_pair(const StackArgs &args, const FastArgs &fargs, unsi
                     g.cont_region = region * group;                   // (a workgroup cannot hand on more than it was given)
                     g.pass_budget = last ? 0 : fargs.cas_pass[st];
                     g.round_cap = last ? 0 : fargs.cas_cap[st];
-                    if (args.n_frames == NS)
-                        hipLaunchKernelGGL((stack_sigma_fast_kernel<NS, true, WINSOR, true, false, true>), dim3(blocks), dim3(256), 0, stream, args, g);
-                    else
-                        hipLaunchKernelGGL((stack_sigma_fast_kernel<NS, true, WINSOR, false, false, true>), dim3(blocks), dim3(256), 0, stream, args, g);
-                    keep_first(err, hipGetLastError());
+                    with_bool(args.n_frames == NS, [&](auto T) {
+                        L(stack_sigma_fast_kernel<NS, true, WINSOR, decltype(T)::value, false, true>, blocks, 256, 0, args, g);
+                    });
                     regions = blocks;
                     region = region * group;
                 }
@@ -573,55 +510,28 @@ static hipError_t launch_pair(const StackArgs &args, const FastArgs &fargs, unsi
         if (after) after(user);
         // generic pass over the pixels the zonal waves handed over (its length
         // is only known on the device: fixed grid, grid-stride loop)
-        f.in_list = fargs.gen_list;
-        f.in_count = fargs.gen_count;
-        f.in_capacity = fargs.gen_capacity;
-        const unsigned gblocks = generic_grid(fargs.gen_hint, 256, tile_blocks < kGenericGrid ? tile_blocks : kGenericGrid);
+        const FastArgs fg = over_generic_list(f);
         if constexpr (NS > 64) {
             // whole columns + prefix sums in LDS (stack_fast_mlg.hip): a clipping or winsorization round
             // is a few LDS reads instead of a pass over 128 masked registers -- this pass is pure
             // latency (a few hundred waves at most), and it sits on every pass's critical path
-            const unsigned lblocks = generic_grid(fargs.gen_hint, 64, 4 * tile_blocks < 4 * kGenericGrid ? 4 * tile_blocks : 4 * kGenericGrid);
+            const unsigned lblocks = generic_grid(fargs.gen_hint, 64, 4 * std::min(tile_blocks, kGenericGrid));
             if (!WINSOR && fused_replay)      // generic pass + first replay in one grid (stack_tail_fused.hip)
-                keep_first(err, launch_stack_sigma_tail(args, f, lblocks, *fused_replay, fused_replay_blocks, stream));
+                L.keep(launch_stack_sigma_tail(args, fg, lblocks, *fused_replay, fused_replay_blocks, stream));
             else
-                keep_first(err, launch_stack_sigma_mlg(args, f, lblocks, stream, WINSOR));
+                L.keep(launch_stack_sigma_mlg(args, fg, lblocks, stream, WINSOR));
         } else {
-            hipLaunchKernelGGL((stack_sigma_fast_kernel<NS, false, WINSOR, false>), dim3(gblocks), dim3(256), 0,
-                               stream, args, f);
-            keep_first(err, hipGetLastError());
+            L(stack_sigma_fast_kernel<NS, false, WINSOR, false>, generic_grid(fargs.gen_hint, 256, std::min(tile_blocks, kGenericGrid)),
+              256, 0, args, fg);
         }
     } else {
         // small stacks: generic passes are cheap, run them over the whole tile
-        *name = sigma_kernel_name<NS, false, WINSOR, false>();
-        hipLaunchKernelGGL((stack_sigma_fast_kernel<NS, false, WINSOR, false>), dim3(tile_blocks), dim3(256), 0,
-                           stream, args, f);
-        keep_first(err, hipGetLastError());
-        if (dominant_done) keep_first(err, hipEventRecord(dominant_done, stream));
+        *name = kernel_name<kSigmaFastName, NS, false, WINSOR, false, false, false>();
+        L(stack_sigma_fast_kernel<NS, false, WINSOR, false>, tile_blocks, 256, 0, args, f);
+        L.record(dominant_done);
         if (after) after(user);
     }
-    return err;
-}
-
-template <bool WINSOR>
-static hipError_t launch_sized(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name,
-                         hipEvent_t dominant_done, AfterDominant after, void *user,
-                         const StackArgs *fused_replay, unsigned fused_replay_blocks)
-{
-    const unsigned blocks = (unsigned)((args.npix + 255) / 256);
-    const int n = args.n_frames;
-    // network sizes: the frame count rounded up to the next instantiated size;
-    // unused positions count as missing samples
-    if (n <= 8)        return launch_pair<8, WINSOR>(args, fargs, blocks, stream, name, dominant_done, after, user, fused_replay, fused_replay_blocks);
-    else if (n <= 16)  return launch_pair<16, WINSOR>(args, fargs, blocks, stream, name, dominant_done, after, user, fused_replay, fused_replay_blocks);
-    else if (n <= 24)  return launch_pair<24, WINSOR>(args, fargs, blocks, stream, name, dominant_done, after, user, fused_replay, fused_replay_blocks);
-    else if (n <= 32)  return launch_pair<32, WINSOR>(args, fargs, blocks, stream, name, dominant_done, after, user, fused_replay, fused_replay_blocks);
-    else if (n <= 48)  return launch_pair<48, WINSOR>(args, fargs, blocks, stream, name, dominant_done, after, user, fused_replay, fused_replay_blocks);
-    else if (n <= 64)  return launch_pair<64, WINSOR>(args, fargs, blocks, stream, name, dominant_done, after, user, fused_replay, fused_replay_blocks);
-    else if (n <= 80)  return launch_pair<80, WINSOR>(args, fargs, blocks, stream, name, dominant_done, after, user, fused_replay, fused_replay_blocks);
-    else if (n <= 96)  return launch_pair<96, WINSOR>(args, fargs, blocks, stream, name, dominant_done, after, user, fused_replay, fused_replay_blocks);
-    else if (n <= 112) return launch_pair<112, WINSOR>(args, fargs, blocks, stream, name, dominant_done, after, user, fused_replay, fused_replay_blocks);
-    else               return launch_pair<128, WINSOR>(args, fargs, blocks, stream, name, dominant_done, after, user, fused_replay, fused_replay_blocks);
+    return L.err;
 }
 
 hipError_t launch_stack_sigma_fast(const StackArgs &args, const FastArgs &fargs, hipStream_t stream,
@@ -629,10 +539,14 @@ hipError_t launch_stack_sigma_fast(const StackArgs &args, const FastArgs &fargs,
                                    bool winsor, AfterDominant after, void *user,
                                    const StackArgs *fused_replay, unsigned fused_replay_blocks)
 {
-    hipError_t err = winsor ? launch_sized<true>(args, fargs, stream, name, dominant_done, after, user, fused_replay, fused_replay_blocks)
-                            : launch_sized<false>(args, fargs, stream, name, dominant_done, after, user, fused_replay, fused_replay_blocks);
-    keep_first(err, hipGetLastError());
-    return err;
+    // network sizes: the frame count rounded up to the next instantiated size;
+    // unused positions count as missing samples
+    return with_bool(winsor, [&](auto W) {
+        return with_class<8, 16, 24, 32, 48, 64, 80, 96, 112, 128>(args.n_frames, [&](auto C) {
+            return launch_pair<decltype(C)::value, decltype(W)::value>(args, fargs, stream, name, dominant_done, after, user,
+                                                                       fused_replay, fused_replay_blocks);
+        });
+    });
 }
 
 }  // namespace nl

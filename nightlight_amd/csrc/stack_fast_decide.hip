@@ -11,10 +11,9 @@
 // (1e-4 .. 1e-2 of them), the NaN borders and pixels that clip more than the zones hold are replayed in full.
 #include <string.h>
 
-#include <string>
-
 #define NL_STAT(i, x) ((void)0)
 #include "stack_fast_sigma_impl.hpp"
+#include "launch_common.hpp"
 
 namespace nl {
 
@@ -24,41 +23,24 @@ int decide_supported(int mode, int n_frames, int64_t npix)
     return (n_frames >= 33 && n_frames <= 128 && npix < kFastMaxPixels) ? 1 : 0;
 }
 
-template <int NS, bool WINSOR>
-static void launch_decide(const StackArgs &args, unsigned blocks, hipStream_t stream, const char **name)
-{
-    static const std::string names[2] = {
-        std::string("stack_sigma_fast_kernel<") + std::to_string(NS) + ", true, " + (WINSOR ? "true" : "false") + ", false, true, false>",
-        std::string("stack_sigma_fast_kernel<") + std::to_string(NS) + ", true, " + (WINSOR ? "true" : "false") + ", true, true, false>"};
-    FastArgs f;
-    memset(&f, 0, sizeof f);
-    if (args.n_frames == NS) {
-        *name = names[1].c_str();
-        hipLaunchKernelGGL((stack_sigma_fast_kernel<NS, true, WINSOR, true, true>), dim3(blocks), dim3(256), 0, stream, args, f);
-    } else {
-        *name = names[0].c_str();
-        hipLaunchKernelGGL((stack_sigma_fast_kernel<NS, true, WINSOR, false, true>), dim3(blocks), dim3(256), 0, stream, args, f);
-    }
-}
-
-template <bool WINSOR>
-static void launch_decide_sized(const StackArgs &args, hipStream_t stream, const char **name)
-{
-    const unsigned blocks = (unsigned)((args.npix + 255) / 256);
-    const int n = args.n_frames;
-    if (n <= 48)       launch_decide<48, WINSOR>(args, blocks, stream, name);
-    else if (n <= 64)  launch_decide<64, WINSOR>(args, blocks, stream, name);
-    else if (n <= 80)  launch_decide<80, WINSOR>(args, blocks, stream, name);
-    else if (n <= 96)  launch_decide<96, WINSOR>(args, blocks, stream, name);
-    else if (n <= 112) launch_decide<112, WINSOR>(args, blocks, stream, name);
-    else               launch_decide<128, WINSOR>(args, blocks, stream, name);
-}
+constexpr char kSigmaFastName[] = "stack_sigma_fast_kernel";
 
 hipError_t launch_stack_sigma_decide(const StackArgs &args, hipStream_t stream, bool winsor, const char **name)
 {
-    if (winsor) launch_decide_sized<true>(args, stream, name);
-    else        launch_decide_sized<false>(args, stream, name);
-    return hipGetLastError();
+    Launcher L(stream);
+    FastArgs f;
+    memset(&f, 0, sizeof f);
+    with_bool(winsor, [&](auto W) {
+        with_class<48, 64, 80, 96, 112, 128>(args.n_frames, [&](auto C) {
+            with_bool(args.n_frames == decltype(C)::value, [&](auto T) {
+                constexpr int NS = decltype(C)::value;
+                constexpr bool WINSOR = decltype(W)::value, TIGHT = decltype(T)::value;
+                *name = kernel_name<kSigmaFastName, NS, true, WINSOR, TIGHT, true, false>();
+                L(stack_sigma_fast_kernel<NS, true, WINSOR, TIGHT, true>, pixel_grid(args.npix), 256, 0, args, f);
+            });
+        });
+    });
+    return L.err;
 }
 
 }  // namespace nl

@@ -19,9 +19,9 @@
 // StackSigma: internal/ops/stack/stack.go:372-436.  HBM traffic: every sample is
 // read once; a wave instruction covers 64/LPP consecutive pixels of LPP frames.
 #include <cstdlib>
-#include <string>
 
 #include "fast_ml_common.hpp"
+#include "launch_common.hpp"
 
 namespace nl {
 
@@ -64,18 +64,17 @@ void stack_median_ml_kernel(StackArgs p)
     if (on && role == 0) NL_STORE_RESULT(&p.out[item], res);
 }
 
+constexpr char kMedianMlName[] = "stack_median_ml_kernel";
+constexpr char kMadMlName[] = "stack_mad_ml_kernel";
+
 hipError_t launch_stack_median_ml(const StackArgs &args, hipStream_t stream, const char **name)
 {
-    if (args.n_frames <= 2 * kMlNS) {
-        *name = "stack_median_ml_kernel<2>";
-        const unsigned blocks = (unsigned)((args.npix + 127) / 128);
-        hipLaunchKernelGGL(stack_median_ml_kernel<2>, dim3(blocks), dim3(256), 0, stream, args);
-    } else {
-        *name = "stack_median_ml_kernel<4>";
-        const unsigned blocks = (unsigned)((args.npix + 63) / 64);
-        hipLaunchKernelGGL(stack_median_ml_kernel<4>, dim3(blocks), dim3(256), 0, stream, args);
-    }
-    return hipGetLastError();
+    Launcher L(stream);
+    with_ml_lanes(args.n_frames, [&](auto LPP) {
+        *name = kernel_name<kMedianMlName, decltype(LPP)::value>();
+        L(stack_median_ml_kernel<decltype(LPP)::value>, pixel_grid(args.npix, LPP), 256, 0, args);
+    });
+    return L.err;
 }
 
 // StackMADSigma (stack.go:536-605) for 129..512 frames, as stack_mad_fast_kernel: merged
@@ -180,70 +179,39 @@ void stack_mad_ml_kernel(StackArgs p, FastArgs q)
 
 hipError_t launch_stack_mad_ml(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name)
 {
-    if (args.n_frames <= 2 * kMlNS) {
-        *name = "stack_mad_ml_kernel<2>";
-        hipLaunchKernelGGL(stack_mad_ml_kernel<2>, dim3((unsigned)((args.npix + 127) / 128)), dim3(256), 0, stream, args,
-                           fargs);
-    } else {
-        *name = "stack_mad_ml_kernel<4>";
-        hipLaunchKernelGGL(stack_mad_ml_kernel<4>, dim3((unsigned)((args.npix + 63) / 64)), dim3(256), 0, stream, args,
-                           fargs);
-    }
-    return hipGetLastError();
+    Launcher L(stream);
+    with_ml_lanes(args.n_frames, [&](auto LPP) {
+        *name = kernel_name<kMadMlName, decltype(LPP)::value>();
+        L(stack_mad_ml_kernel<decltype(LPP)::value>, pixel_grid(args.npix, LPP), 256, 0, args, fargs);
+    });
+    return L.err;
 }
 
 int fast_ml_supported(int mode, bool weighted, int n_frames, int64_t npix)
 {
     // 4 frames of the tile must be addressable with a 31-bit buffer offset
-    if (n_frames <= 128 || n_frames > 512 || npix >= ((int64_t)1 << 27)) return 0;
+    if (n_frames <= 128 || n_frames > 512 || npix >= kFastMaxPixels) return 0;
     if (mode == NL_ST_MEDIAN) return 1;
     if (mode == NL_ST_MAD_SIGMA) return weighted ? 0 : 1;
     return ((mode == NL_ST_SIGMA || mode == NL_ST_WINSOR_SIGMA) && !weighted) ? 1 : 0;
 }
 
-// the nested launchers end in hipGetLastError(), which clears the pending error: keep the first one
-static inline void keep_first(hipError_t &acc, hipError_t e) { if (acc == hipSuccess) acc = e; }
-
 // Dominant kernel = the LDS-column kernel of the frame-count class (stack_fast_mlz*.hip), generic pass = whole columns in
 // LDS (stack_fast_mlg.hip).
-template <int LPP, bool WINSOR>
-static hipError_t launch_ml(const StackArgs &args, const FastArgs &fargs, hipStream_t stream,
-                            hipEvent_t dominant_done, AfterDominant after, void *user, const char **name)
-{
-    hipError_t err = hipSuccess;
-    FastArgs f = fargs;
-    f.in_list = nullptr;
-    f.in_count = nullptr;
-    f.in_capacity = 0;
-    // every position in use: the clipping rounds run on LDS columns (stack_fast_mlz.hip), which sets *name
-    keep_first(err, launch_stack_sigma_mlz(args, f, stream, name, WINSOR));
-    if (dominant_done) keep_first(err, hipEventRecord(dominant_done, stream));
-    if (after) after(user);
-    f.in_list = fargs.gen_list;
-    f.in_count = fargs.gen_count;
-    f.in_capacity = fargs.gen_capacity;
-    // generic pass over the hand-over list: whole columns in LDS (stack_fast_mlg.hip)
-    keep_first(err, launch_stack_sigma_mlg(args, f, generic_grid(fargs.gen_hint, 64 / LPP, 4 * kGenericGrid), stream, WINSOR));
-    return err;
-}
-
-template <int LPP>
-static hipError_t launch_ml_variant(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name,
-                                    hipEvent_t dominant_done, bool winsor, AfterDominant after, void *user)
-{
-    if (winsor) return launch_ml<LPP, true>(args, fargs, stream, dominant_done, after, user, name);
-    return launch_ml<LPP, false>(args, fargs, stream, dominant_done, after, user, name);
-}
-
 hipError_t launch_stack_sigma_ml(const StackArgs &args, const FastArgs &fargs, hipStream_t stream,
                                  const char **name, hipEvent_t dominant_done, bool winsor,
                                  AfterDominant after, void *user)
 {
-    hipError_t err = args.n_frames <= 2 * kMlNS
-        ? launch_ml_variant<2>(args, fargs, stream, name, dominant_done, winsor, after, user)
-        : launch_ml_variant<4>(args, fargs, stream, name, dominant_done, winsor, after, user);
-    keep_first(err, hipGetLastError());
-    return err;
+    Launcher L(stream);
+    const FastArgs f = whole_tile(fargs);
+    // every position in use: the clipping rounds run on LDS columns (stack_fast_mlz.hip), which sets *name
+    L.keep(launch_stack_sigma_mlz(args, f, stream, name, winsor));
+    L.record(dominant_done);
+    if (after) after(user);
+    // generic pass over the hand-over list: whole columns in LDS (stack_fast_mlg.hip)
+    const unsigned grid = with_ml_lanes(args.n_frames, [&](auto LPP) { return generic_grid(fargs.gen_hint, 64 / LPP, 4 * kGenericGrid); });
+    L.keep(launch_stack_sigma_mlg(args, over_generic_list(f), grid, stream, winsor));
+    return L.err;
 }
 
 }  // namespace nl

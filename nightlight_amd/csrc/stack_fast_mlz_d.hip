@@ -4,9 +4,9 @@
 
 namespace nl {
 
-bool launch_mlz_part_d(int ntop, bool winsor, const StackArgs &args, const FastArgs &f, hipStream_t stream)
+bool launch_mlz_part_d(int ntop, bool winsor, const StackArgs &args, const FastArgs &f, Launcher &L, const char **name)
 {
-    return launch_mlz_classes<4>(ntop, winsor, args, f, stream, std::integer_sequence<int, 448, 464, 480, 496, 512>{});
+    return launch_mlz_classes<4, 448, 464, 480, 496, 512>(ntop, winsor, args, f, L, name);
 }
 
 }  // namespace nl

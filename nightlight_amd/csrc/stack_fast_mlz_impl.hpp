@@ -24,9 +24,10 @@
 // replay, pixels whose clips or clamps leave the columns go to the generic pass.
 // StackSigma: stack.go:372-436, StackWinsorSigma: stack.go:611-705.
 #pragma once
-#include <string>
+#include <algorithm>
 
 #include "fast_ml_common.hpp"
+#include "launch_common.hpp"
 
 namespace nl {
 
@@ -914,23 +915,23 @@ void stack_sigma_mlz_kernel(StackArgs p, FastArgs q)
 }
 
 
-// launches the kernel of frame-count class `ntop` if this translation unit instantiates it
-template <int LPP, int... NTOPS>
-static bool launch_mlz_classes(int ntop, bool winsor, const StackArgs &args, const FastArgs &f, hipStream_t stream,
-                               std::integer_sequence<int, NTOPS...>)
+constexpr char kMlzName[] = "stack_sigma_mlz_kernel";
+
+// launches the kernel of frame-count class `ntop` if it is one of this translation unit's (consecutive multiples of 16)
+template <int LPP, int FIRST, int... MORE>
+static bool launch_mlz_classes(int ntop, bool winsor, const StackArgs &args, const FastArgs &f, Launcher &L, const char **name)
 {
-    bool done = false;
-    auto one = [&](auto C) {
-        constexpr int NTOP = decltype(C)::value;
-        if (done || ntop != NTOP) return;
-        using L = MlzLayout<LPP, false, NTOP>;
-        using LW = MlzLayout<LPP, true, NTOP>;
-        if (winsor) hipLaunchKernelGGL((stack_sigma_mlz_kernel<LPP, true, NTOP>), dim3((unsigned)((args.npix + LW::PW - 1) / LW::PW)), dim3(LW::BLOCK), 0, stream, args, f);
-        else        hipLaunchKernelGGL((stack_sigma_mlz_kernel<LPP, false, NTOP>), dim3((unsigned)((args.npix + L::PW - 1) / L::PW)), dim3(L::BLOCK), 0, stream, args, f);
-        done = true;
-    };
-    (one(std::integral_constant<int, NTOPS>{}), ...);
-    return done;
+    if (ntop < FIRST || ntop > std::max({FIRST, MORE...})) return false;
+    with_bool(winsor, [&](auto W) {
+        with_class<FIRST, MORE...>(ntop, [&](auto C) {
+            constexpr bool WINSOR = decltype(W)::value;
+            constexpr int NTOP = decltype(C)::value;
+            using LY = MlzLayout<LPP, WINSOR, NTOP>;
+            *name = kernel_name<kMlzName, LPP, WINSOR, NTOP, 0>();
+            L(stack_sigma_mlz_kernel<LPP, WINSOR, NTOP>, (unsigned)((args.npix + LY::PW - 1) / LY::PW), LY::BLOCK, 0, args, f);
+        });
+    });
+    return true;
 }
 
 }  // namespace nl

@@ -199,7 +199,7 @@ struct SigmaNewton {
 // Picks lanes-per-wave and LDS bytes for the exact kernel; -1 if it cannot fit.
 int exact_plan(int mode, bool weighted, int n_frames, int n_pad, int max_lanes, int *lanes,
                size_t *lds_bytes);
-hipError_t launch_stack_exact(int mode, bool weighted, StackArgs &args, int lanes, int grid,
+hipError_t launch_stack_exact(int mode, bool weighted, const StackArgs &args, int lanes, int grid,
                               size_t lds_bytes, hipStream_t stream, const char **name);
 // list_counts (optional): {exact-list length, generic-list length} of the pass, left in counters[2] (low | high << 32)
 // zero_after: the kernel leaves the scratch set (kScratchWords words at `partial`) zeroed for the next pass
@@ -251,6 +251,7 @@ int decide_ml_supported(int mode, int n_frames, int64_t npix);      // 129 ... 5
 hipError_t launch_stack_sigma_decide(const StackArgs &args, hipStream_t stream, bool winsor, const char **name);
 
 // ---- stack_fast_ml.hip (129..512 frames, 2 or 4 lanes per pixel) ----
+constexpr int kMlNS = 128;     // samples per lane of the multi-lane kernels
 int fast_ml_supported(int mode, bool weighted, int n_frames, int64_t npix);
 hipError_t launch_stack_median_ml(const StackArgs &args, hipStream_t stream, const char **name);
 hipError_t launch_stack_mad_ml(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name);

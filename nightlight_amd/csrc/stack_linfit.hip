@@ -15,9 +15,12 @@
 // One pixel per lane, samples in VGPRs, no LDS, no hand-over lists (a pixel
 // with a +-Inf sample is replayed by the LDS kernel: its pads are +Inf too).
 // MeanStdDev of xs = 0..m-1 depends on m only and comes from the host table.
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+
 #include "linfit_common.hpp"
+#include "launch_common.hpp"
 
 namespace nl {
 
@@ -707,7 +710,7 @@ void stack_linfit_ml_kernel(StackArgs p, FastArgs q, LinfitStage g)
 
 int linfit_ml_supported(int mode, int n_frames, int64_t npix)
 {
-    return (mode == NL_ST_LINEAR_FIT && n_frames > 128 && n_frames <= 512 && npix < ((int64_t)1 << 27)) ? 1 : 0;
+    return (mode == NL_ST_LINEAR_FIT && n_frames > 128 && n_frames <= 512 && npix < kFastMaxPixels) ? 1 : 0;
 }
 
 // fit iterations per cascade stage (the last stage runs to the end); NL_LF_QUOTA="a,b,c" overrides.
@@ -736,66 +739,16 @@ static const int *linfit_quota(int n_frames)
     return q668;
 }
 
-template <int LPP>
-static void launch_lf_ml(const StackArgs &args, const FastArgs &f, const LinfitCascade *c, hipStream_t stream,
-                         hipEvent_t dominant_done)
-{
-    const unsigned per_wg = 256 / LPP;
-    const unsigned blocks = (unsigned)((args.npix + per_wg - 1) / per_wg);
-    LinfitStage g = {};
-    if (!c) {
-        hipLaunchKernelGGL((stack_linfit_ml_kernel<LPP, false>), dim3(blocks), dim3(256), 0, stream, args, f, g);
-        if (dominant_done) (void)hipEventRecord(dominant_done, stream);
-        return;
-    }
-    const int *quota = linfit_quota(args.n_frames);             // as the one-lane kernel
-    for (int s = 0; s < kLinfitStages; s++) {
-        g.max_iters = quota[s];
-        g.in_list = s ? c->list[(s - 1) & 1] : nullptr;
-        g.in_state = s ? c->state[(s - 1) & 1] : nullptr;
-        g.in_count = s ? c->count + (s - 1) : nullptr;
-        g.in_capacity = c->capacity;
-        g.out_list = c->list[s & 1];
-        g.out_state = c->state[s & 1];
-        g.out_count = c->count + s;
-        g.out_capacity = c->capacity;
-        if (s == 0) {
-            hipLaunchKernelGGL((stack_linfit_ml_kernel<LPP, false>), dim3(blocks), dim3(256), 0, stream, args, f, g);
-            if (dominant_done) (void)hipEventRecord(dominant_done, stream);
-        } else {
-            const unsigned gblocks = blocks < 16384u ? blocks : 16384u;
-            hipLaunchKernelGGL((stack_linfit_ml_kernel<LPP, true>), dim3(gblocks), dim3(256), 0, stream, args, f, g);
-        }
-    }
-}
-
-// cascade->state must hold LPP entries per listed pixel (2 up to 256 frames, else 4)
-hipError_t launch_stack_linfit_ml(const StackArgs &args, const FastArgs &fargs, const LinfitCascade *cascade,
-                                  hipStream_t stream, const char **name, hipEvent_t dominant_done)
-{
-    if (args.n_frames <= 2 * kMlNS) {
-        *name = "stack_linfit_ml_kernel<2, false>";
-        launch_lf_ml<2>(args, fargs, cascade, stream, dominant_done);
-    } else {
-        *name = "stack_linfit_ml_kernel<4, false>";
-        launch_lf_ml<4>(args, fargs, cascade, stream, dominant_done);
-    }
-    return hipGetLastError();
-}
-
-int linfit_fast_supported(int mode, int n_frames, int64_t npix)
-{
-    return (mode == NL_ST_LINEAR_FIT && n_frames >= 1 && n_frames <= 128 && npix < kFastMaxPixels) ? 1 : 0;
-}
-
-template <int NS>
-static void launch_lf(const StackArgs &args, const FastArgs &f, const LinfitCascade *c, unsigned blocks,
-                      hipStream_t stream, hipEvent_t dominant_done)
+// The cascade of a fit: `first` (the dominant kernel) over the whole tile, then `cont` over what the stage before left, in at
+// most max_cont_grid workgroups of 256 threads
+static void launch_lf_cascade(Launcher &L, void (*first)(StackArgs, FastArgs, LinfitStage),
+                              void (*cont)(StackArgs, FastArgs, LinfitStage), unsigned blocks, unsigned max_cont_grid,
+                              const StackArgs &args, const FastArgs &f, const LinfitCascade *c, hipEvent_t dominant_done)
 {
     LinfitStage g = {};
     if (!c) {                                    // no cascade buffers: one stage, run to completion
-        hipLaunchKernelGGL((stack_linfit_fast_kernel<NS, false>), dim3(blocks), dim3(256), 0, stream, args, f, g);
-        if (dominant_done) (void)hipEventRecord(dominant_done, stream);
+        L(first, blocks, 256, 0, args, f, g);
+        L.record(dominant_done);
         return;
     }
     // Fit iterations per stage.  The number a pixel needs varies a lot (8 on average, 20-26
@@ -813,28 +766,47 @@ static void launch_lf(const StackArgs &args, const FastArgs &f, const LinfitCasc
         g.out_count = c->count + s;
         g.out_capacity = c->capacity;
         if (s == 0) {
-            hipLaunchKernelGGL((stack_linfit_fast_kernel<NS, false>), dim3(blocks), dim3(256), 0, stream, args, f, g);
-            if (dominant_done) (void)hipEventRecord(dominant_done, stream);
+            L(first, blocks, 256, 0, args, f, g);
+            L.record(dominant_done);
         } else {
-            const unsigned gblocks = blocks < 8192u ? blocks : 8192u;
-            hipLaunchKernelGGL((stack_linfit_fast_kernel<NS, true>), dim3(gblocks), dim3(256), 0, stream, args, f, g);
+            L(cont, std::min(blocks, max_cont_grid), 256, 0, args, f, g);
         }
     }
+}
+
+constexpr char kLinfitMlName[] = "stack_linfit_ml_kernel";
+constexpr char kLinfitFastName[] = "stack_linfit_fast_kernel";
+
+// cascade->state must hold LPP entries per listed pixel (2 up to 256 frames, else 4)
+hipError_t launch_stack_linfit_ml(const StackArgs &args, const FastArgs &fargs, const LinfitCascade *cascade,
+                                  hipStream_t stream, const char **name, hipEvent_t dominant_done)
+{
+    Launcher L(stream);
+    with_ml_lanes(args.n_frames, [&](auto C) {
+        constexpr int LPP = decltype(C)::value;
+        *name = kernel_name<kLinfitMlName, LPP, false>();
+        launch_lf_cascade(L, stack_linfit_ml_kernel<LPP, false>, stack_linfit_ml_kernel<LPP, true>, pixel_grid(args.npix, LPP),
+                          16384u, args, fargs, cascade, dominant_done);
+    });
+    return L.err;
+}
+
+int linfit_fast_supported(int mode, int n_frames, int64_t npix)
+{
+    return (mode == NL_ST_LINEAR_FIT && n_frames >= 1 && n_frames <= 128 && npix < kFastMaxPixels) ? 1 : 0;
 }
 
 hipError_t launch_stack_linfit_fast(const StackArgs &args, const FastArgs &fargs, const LinfitCascade *cascade,
                                     hipStream_t stream, const char **name, hipEvent_t dominant_done)
 {
-    const unsigned blocks = (unsigned)((args.npix + 255) / 256);
-    const int n = args.n_frames;
-    if (n <= 8)        { *name = "stack_linfit_fast_kernel<8, false>";   launch_lf<8>(args, fargs, cascade, blocks, stream, dominant_done); }
-    else if (n <= 16)  { *name = "stack_linfit_fast_kernel<16, false>";  launch_lf<16>(args, fargs, cascade, blocks, stream, dominant_done); }
-    else if (n <= 32)  { *name = "stack_linfit_fast_kernel<32, false>";  launch_lf<32>(args, fargs, cascade, blocks, stream, dominant_done); }
-    else if (n <= 48)  { *name = "stack_linfit_fast_kernel<48, false>";  launch_lf<48>(args, fargs, cascade, blocks, stream, dominant_done); }
-    else if (n <= 64)  { *name = "stack_linfit_fast_kernel<64, false>";  launch_lf<64>(args, fargs, cascade, blocks, stream, dominant_done); }
-    else if (n <= 96)  { *name = "stack_linfit_fast_kernel<96, false>";  launch_lf<96>(args, fargs, cascade, blocks, stream, dominant_done); }
-    else               { *name = "stack_linfit_fast_kernel<128, false>"; launch_lf<128>(args, fargs, cascade, blocks, stream, dominant_done); }
-    return hipGetLastError();
+    Launcher L(stream);
+    with_class<8, 16, 32, 48, 64, 96, 128>(args.n_frames, [&](auto C) {
+        constexpr int NS = decltype(C)::value;
+        *name = kernel_name<kLinfitFastName, NS, false>();
+        launch_lf_cascade(L, stack_linfit_fast_kernel<NS, false>, stack_linfit_fast_kernel<NS, true>, pixel_grid(args.npix),
+                          8192u, args, fargs, cascade, dominant_done);
+    });
+    return L.err;
 }
 
 }  // namespace nl

@@ -5,7 +5,7 @@
 // wave instruction), walks the frames in frame order -- the reference's
 // summation order, so results are bit-exact -- with 8 frames of loads in
 // flight.  No LDS, no reduction across lanes.  HBM-bound: 4*(N+1) bytes/pixel.
-#include "stack_kernels.h"
+#include "launch_common.hpp"
 
 namespace nl {
 
@@ -106,28 +106,20 @@ hipError_t launch_stack_mean(bool weighted, const StackArgs &args, hipStream_t s
     const bool vec_ok = (args.stride % 4 == 0) &&
                         ((reinterpret_cast<uintptr_t>(args.frames) & 15) == 0) &&
                         ((reinterpret_cast<uintptr_t>(args.out) & 15) == 0);
-    int64_t done = 0;
     *name = weighted ? "stack_mean_vec4_kernel<weighted>" : "stack_mean_vec4_kernel";
-    if (vec_ok && args.npix >= 4) {
-        const int64_t quads = args.npix >> 2;
-        const int grid = grid_for(quads, 256, 256 * 64);
-        if (weighted)
-            hipLaunchKernelGGL(stack_mean_vec4_kernel<true>, dim3(grid), dim3(256), 0, stream, args);
-        else
-            hipLaunchKernelGGL(stack_mean_vec4_kernel<false>, dim3(grid), dim3(256), 0, stream, args);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        done = quads << 2;
-    }
-    if (done < args.npix) {
-        const int grid = grid_for(args.npix - done, 256, 256 * 64);
-        if (weighted)
-            hipLaunchKernelGGL(stack_mean_scalar_kernel<true>, dim3(grid), dim3(256), 0, stream, args, done);
-        else
-            hipLaunchKernelGGL(stack_mean_scalar_kernel<false>, dim3(grid), dim3(256), 0, stream, args, done);
-        return hipGetLastError();
-    }
-    return hipSuccess;
+    Launcher L(stream);
+    with_bool(weighted, [&](auto W) {
+        int64_t done = 0;
+        if (vec_ok && args.npix >= 4) {
+            const int64_t quads = args.npix >> 2;
+            L(stack_mean_vec4_kernel<decltype(W)::value>, grid_for(quads, 256, 256 * 64), 256, 0, args);
+            if (L.err != hipSuccess) return;
+            done = quads << 2;
+        }
+        if (done < args.npix)
+            L(stack_mean_scalar_kernel<decltype(W)::value>, grid_for(args.npix - done, 256, 256 * 64), 256, 0, args, done);
+    });
+    return L.err;
 }
 
 // StackIncremental (stack.go:924-937): acc = x*w (first) or acc += x*w

@@ -13,11 +13,11 @@
 // care who looks first).  The replay of what the generic pass adds to the list follows as before.  Every workgroup claims the
 // generic pass's 48 KiB of LDS, so three replay workgroups fit a CU: dispatched only while the exact list is short
 // (nlstack_api.hip: kTailFusedMaxList), which is where the join weighs most.
-#undef NL_ROUND_STATS
-#undef NL_PROBE
-#define NL_TAIL_FUSED_TU
-#include "stack_fast_mlg.hip"
-#include "stack_exact_coop.hip"
+#undef NL_ROUND_STATS                 // (the generic pass's round statistics are stack_fast_mlg.hip's)
+#define NL_STAT(i, x) ((void)0)
+#include "stack_fast_mlg_impl.hpp"
+#include "stack_exact_coop_impl.hpp"
+#include "launch_common.hpp"
 
 namespace nl {
 
@@ -42,9 +42,9 @@ hipError_t launch_stack_sigma_tail(const StackArgs &generic, const FastArgs &far
 {
     // LDS of the replay part: samples + 2 scratch columns of 16 bits (coop_columns(NL_ST_SIGMA, false) in stack_exact_coop.hip)
     const size_t lds = (size_t)replay.n_frames * sizeof(float) * 2;
-    hipLaunchKernelGGL(stack_sigma_tail_kernel, dim3(gen_blocks + replay_blocks), dim3(64), lds, stream, generic, fargs, replay,
-                       gen_blocks);
-    return hipGetLastError();
+    Launcher L(stream);
+    L(stack_sigma_tail_kernel, gen_blocks + replay_blocks, 64, lds, generic, fargs, replay, gen_blocks);
+    return L.err;
 }
 
 }  // namespace nl

@@ -1086,6 +1086,32 @@ DISPATCH_TABLE = [
     (2, 128, False, 0, 2, "stack_sigma_fast_kernel<128, true, false, true, false, false>", 1),
     (2, 32, True, 0, 16, "stack_sigma_coop_kernel<false, true, 4, 2>", 0),
     (2, 128, False, 0, 8192, "stack_sigma_fast_kernel<128, true, false, true, false, false>", 1),
+    # one row per name path of the stack-pass launchers
+    (0, 8, False, 0, 0, "stack_median_fast_kernel<8, false>", 0),
+    (0, 200, False, 0, 0, "stack_median_ml_kernel<2>", 0),
+    (0, 32, False, 1, 0, "stack_exact_kernel<median>", 0),
+    (0, 32, False, 2, 0, "stack_median_coop_kernel", 0),
+    (1, 16, True, 0, 0, "stack_mean_vec4_kernel<weighted>", 0),
+    (4, 8, False, 0, 0, "stack_mad_fast_kernel<8>", 0),
+    (4, 120, False, 0, 0, "stack_mad_bitonic_kernel", 0),
+    (4, 200, False, 0, 0, "stack_mad_ml_kernel<2>", 0),
+    (4, 32, False, 1, 0, "stack_exact_kernel<mad>", 0),
+    (5, 8, False, 0, 0, "stack_linfit_fast_kernel<8, false>", 0),
+    (5, 200, False, 0, 0, "stack_linfit_ml_kernel<2, false>", 0),
+    (5, 32, False, 1, 0, "stack_exact_kernel<linearfit>", 0),
+    (2, 5, False, 0, 0, "stack_sigma_fast_kernel<8, false, false, false, false, false>", 0),
+    (2, 100, False, 0, 0, "stack_sigma_fast_kernel<112, true, false, false, false, false>", 3),
+    (2, 200, False, 0, 0, "stack_sigma_mlz_kernel<2, false, 208, 0>", 1),
+    (3, 8, False, 0, 0, "stack_sigma_fast_kernel<8, false, true, false, false, false>", 0),
+    (3, 48, False, 0, 0, "stack_sigma_fast_kernel<48, true, true, true, false, false>", 0),
+    (3, 100, False, 0, 0, "stack_sigma_fast_kernel<112, true, true, false, false, false>", 1),
+    (3, 500, False, 0, 0, "stack_sigma_mlz_kernel<4, true, 512, 0>", 0),
+    (3, 32, False, 1, 0, "stack_exact_kernel<winsor>", 0),
+    (2, 32, True, 1, 0, "stack_exact_kernel<sigma,weighted>", 0),
+    (2, 300, True, 3, 0, "stack_sigma_tile_kernel<sigma,weighted>", 0),
+    (3, 300, True, 3, 0, "stack_sigma_tile_kernel<winsor,weighted>", 0),
+    (3, 300, True, 0, 0, "stack_sigma_coop_kernel<true, true, 4, 8>", 0),
+    (2, 300, False, 2, 0, "stack_sigma_coop_kernel<false, false, 4, 2>", 0),
 ]
 
 
