@@ -15,10 +15,18 @@ range).  The only exchange is the sum of the two clip counters per pass
 copied device-to-device behind the pass and reduced on the handle's own stream,
 no host round trip per pass.  --weak keeps the tile per GPU fixed instead.
 
-Prints ONE JSON line on rank 0 (contract in the task description) including
+A plain run does only what the headline needs: it sets up the stack, runs the
+untimed preheat and --warmup passes, times the --steps passes, writes
+--dump-outputs if asked and prints ONE JSON line on rank 0 (metric, value,
+unit, higher_is_better, dtype, ms_per_step, config) including
   roofline     algorithmic HBM bytes of one launch (4*tile_pixels*(N+1)) / the
                dominant kernel's mean duration over the TIMED passes (HIP events
                on the stream the kernel runs on, read back after the timed region)
+  ranks        (--gpus N) every rank's wall clock per step, pass and dominant-kernel GPU time, and their min / max.
+
+--full measures everything else as well, each in runs of its own after the timed steps (--no-cpu, --no-apply, --apply and
+--no-also choose among these legs):
+  ms_per_step_synchronous  one more pass, enqueued and waited for as OpStack.Apply runs it.
   cpu_baseline the CPU oracle (C restatement of the Go reference) on a bounded
                strip of the same stack: 1 warm-up + median of 3, N separately
                allocated host frames, all host threads.
@@ -32,7 +40,7 @@ Prints ONE JSON line on rank 0 (contract in the task description) including
                create, first pass, destroy -- wall-clock milliseconds; with the grid hints the library carries over from
                the last handle of the geometry, and ("without_inherited_hints") without them; a winsorized and a weighted
                pass on the same frames as well (their scratch goes through the same buffer cache).
-  ranks        (--gpus N) every rank's wall clock per step, pass and dominant-kernel GPU time, and their min / max.
+  apply_from_host  OpStack.Apply from frames in host memory (default workload on one GPU, or --apply).
 """
 import argparse
 import json
@@ -71,17 +79,20 @@ def parse():
                     help="1-GPU runs only: first image row of the tile (with --image-height: one GPU's share of a larger image)")
     ap.add_argument("--image-height", type=int, default=0,
                     help="1-GPU runs only: height of the whole image the --height rows tile is cut from")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure everything else too: the synchronous pass, cpu_baseline, fresh_handle, "
+                         "apply_from_host and the other workloads under \"also\" (a plain run times the headline only)")
     ap.add_argument("--cpu-rows", type=int, default=0,
-                    help="rows of the stack timed on the CPU (0 = auto, about 3 s per run)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the host-side legs: cpu_baseline and apply_from_host")
-    ap.add_argument("--apply", action="store_true", help="run the apply_from_host leg even with --no-cpu")
-    ap.add_argument("--no-apply", action="store_true", help="skip the apply_from_host leg (OpStack.Apply from host memory)")
+                    help="--full: rows of the stack timed on the CPU (0 = auto, about 3 s per run)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the host-side legs: cpu_baseline and apply_from_host")
+    ap.add_argument("--apply", action="store_true", help="--full: run the apply_from_host leg for any geometry, even with --no-cpu")
+    ap.add_argument("--no-apply", action="store_true", help="--full: skip the apply_from_host leg (OpStack.Apply from host memory)")
     ap.add_argument("--preheat-steps", type=int, default=64,
                     help="untimed passes in front of the W warm-up steps (the same number on every rank): a box fresh from idle "
                          "runs its first ~30 ms of work at a lower clock and 5 warm-up passes are 9 ms -- measured 1.91 ms per pass "
                          "with --steps 5 --warmup 2, 1.81 with 10 / 3, 1.76 with 20 / 5, 1.74 from 100 passes on; reported in config")
     ap.add_argument("--no-also", action="store_true",
-                    help="default workload only: skip the 32- and 512-frame stacks reported under \"also\"")
+                    help="--full: skip the other workloads reported under \"also\"")
     ap.add_argument("--weighted", action="store_true",
                     help="per-frame weights in [0.2, 1] (the shape of inverse-noise weights, stack.go:246-253)")
     ap.add_argument("--backend", default="nccl",
@@ -96,7 +107,10 @@ def parse():
                          "stacked image in row-major pixel order, or, when it has more than %d pixels, those at a fixed "
                          "seeded sample of %d sorted pixel indices) and DIR/clip_counters.npy (float64 [low, high])"
                          % (DUMP_MAX_PIXELS, DUMP_MAX_PIXELS))
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.apply and not args.full:
+        ap.error("--apply asks for a leg of --full")
+    return args
 
 
 def dump_sample_index(pixels):
@@ -411,11 +425,13 @@ def main():
     # global clip totals (the log line of stack.go:214-218 needs them on every pass)
     totals = torch.zeros(2, dtype=torch.int64, device="cuda" if on_device else "cpu")
 
-    def time_stack(frames, mode, steps, warmup, weights=None, geo=None, dump=False):
+    def time_stack(frames, mode, steps, warmup, weights=None, geo=None, dump=False, sync=False):
         """One workload on this rank's row tile: `warmup` untimed passes, then exactly `steps` timed ones
-        bracketed by barrier + synchronize.  Returns the handle (still open) and the timings.
+        bracketed by barrier + synchronize.  Returns the handle (still open) and the timings; cl / ch are the
+        global clip counters of the last timed pass.
         geo = (width, image_rows, row0, rows) of another geometry than the headline's (1-GPU extras).
-        dump: also return what the last timed pass gave its caller -- this rank's result rows and the global clip counters."""
+        dump: also return what the last timed pass gave its caller -- this rank's result rows and the global clip counters.
+        sync: also time one more pass run synchronously (sync_ms; None without)."""
         gw, gh, gr0, grows = geo or (w, image_rows, row0, rows)
         st = StackHandle(frames, gw, gh, row0=gr0, rows=grows, device=device)
         st.fill_synthetic()
@@ -492,20 +508,23 @@ def main():
         times = [st.pass_times(b) for b in range(timed)]
         pass_ms = float(np.mean([t[0] for t in times]))
         k_ms = float(np.mean([t[1] for t in times]))
+        if dist is not None and on_device:
+            last_counters = ring[(seq[0] - 1) % 3][:2].tolist()
+        elif dist is not None:
+            last_counters = totals.tolist()
+        cl, ch = (int(c) for c in last_counters)
         outputs = None
         if dump:
-            if dist is not None and on_device:
-                last_counters = ring[(seq[0] - 1) % 3][:2].tolist()
-            elif dist is not None:
-                last_counters = totals.tolist()
-            outputs = {"result_rows": st.download_rows(-1, 0, grows), "clip_counters": [int(c) for c in last_counters]}
-        # one more pass, synchronous as OpStack.Apply runs it (enqueue, wait, read the counters back)
+            outputs = {"result_rows": st.download_rows(-1, 0, grows), "clip_counters": [cl, ch]}
         if ring is not None:
             st.set_counters_buffer(None)                     # (back to the handle's own counters)
-        t1 = time.perf_counter()
-        st.run_async(mode, args.kappa, args.kappa, 0.0)
-        cl, ch = st.finish()
-        sync_ms = (time.perf_counter() - t1) * 1e3
+        sync_ms = None
+        if sync:
+            # one more pass, synchronous as OpStack.Apply runs it (enqueue, wait, read the counters back)
+            t1 = time.perf_counter()
+            st.run_async(mode, args.kappa, args.kappa, 0.0)
+            st.finish()
+            sync_ms = (time.perf_counter() - t1) * 1e3
         ranks = None
         if dist is not None:
             t = torch.tensor([dt], dtype=torch.float64, device="cuda" if on_device else "cpu")
@@ -520,13 +539,6 @@ def main():
                      "pass_ms_min": round(min(r[1] for r in rows_), 4), "pass_ms_max": round(max(r[1] for r in rows_), 4),
                      "kernel_ms_min": round(min(r[2] for r in rows_), 4), "kernel_ms_max": round(max(r[2] for r in rows_), 4)}
             dt = float(t.item())
-            if on_device:
-                st.copy_counters_async(totals.data_ptr())
-                torch.cuda.synchronize()
-            else:
-                totals.copy_(torch.tensor([cl, ch], dtype=torch.int64))
-            dist.all_reduce(totals)
-            cl, ch = int(totals[0].item()), int(totals[1].item())
         return st, {"dt": dt, "pass_ms": pass_ms, "k_ms": k_ms, "timed": timed, "cl": cl, "ch": ch, "sync_ms": sync_ms, "ranks": ranks,
                     "outputs": outputs}
 
@@ -593,12 +605,12 @@ def main():
                            " -- the first pass ran WITH the hints the previous handle left") +
                         "; the timed steps above re-use one handle"}
 
-    default_workload_early = (args.frames == 128 and args.mode == 2 and args.width == 4096 and args.height == 4096 and
-                              not args.weak and not args.weighted and not args.image_height)
+    default_workload = (args.frames == 128 and args.mode == 2 and args.width == 4096 and args.height == 4096 and
+                        not args.weak and not args.weighted and not args.image_height)
     weights = None
     if args.weighted:
         weights = np.array([0.2 + 0.8 * ((k * 37) % 101) / 100.0 for k in range(n)], np.float32)
-    st, tm = time_stack(n, args.mode, args.steps, args.warmup, weights, dump=bool(args.dump_outputs))
+    st, tm = time_stack(n, args.mode, args.steps, args.warmup, weights, dump=bool(args.dump_outputs), sync=args.full)
     dt, pass_ms, k_ms, timed, cl, ch = tm["dt"], tm["pass_ms"], tm["k_ms"], tm["timed"], tm["cl"], tm["ch"]
     if args.dump_outputs:
         # the ranks' row tiles, in rank order, are the rows of the image this run stacked
@@ -646,13 +658,15 @@ def main():
                          "pass_frac": round(alg_bytes / (pass_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
                          "pixels_redone_by_exact_kernel": st.last_fallback_pixels,
                          "issue": issue_roofline(st.last_kernel_name, n, w, rows, args.mode, k_ms)},
+        }
+        if args.full:
             # ms_per_step times passes queued back to back (one host sync at the end of the timed region);
             # this is one pass run the way OpStack.Apply runs it: enqueue, wait, read the counters back
-            "ms_per_step_synchronous": round(tm["sync_ms"], 4),
-        }
+            out["ms_per_step_synchronous"] = round(tm["sync_ms"], 4)
         if tm["ranks"] is not None:
             out["ranks"] = tm["ranks"]            # per rank: wall clock per step, pass and dominant-kernel GPU time (HIP events)
-        if world == 1 and not args.no_cpu:
+        # everything below up to the JSON line is --full: runs of their own beside the headline
+        if args.full and world == 1 and not args.no_cpu:
             cpu_rows = args.cpu_rows
             if cpu_rows <= 0:
                 # about 2 s per run at the usable threads (several cgroup quota periods): the oracle does ~50e6 samples/s
@@ -664,12 +678,12 @@ def main():
             # parity in the same run: the same strip through the C ABI vs the oracle
             base["parity_with_gpu"] = strip_parity(n, args.mode, (w, image_rows, row0, rows), weights, cpu_rows, res, cc)
             out["cpu_baseline"] = base
-        if world == 1 and dist is None:
+        if args.full and world == 1 and dist is None:
             out["fresh_handle"] = fresh_handle_cost(st, n, args.mode, weights)
             out["fresh_handle"]["without_inherited_hints"] = {
                 k: v for k, v in fresh_handle_cost(st, n, args.mode, weights, no_hints=True).items()
                 if k in ("ms_create", "ms_first_pass_fresh_handle", "ms_second_pass_synchronous", "ms_destroy", "note")}
-            if default_workload_early:
+            if default_workload:
                 # the scratch of the other pass protocols goes through the same buffer cache: a winsorized stack (the
                 # cascade's lists) and a weighted one (the decision pass's thresholds) on the same resident frames
                 w_ = np.array([0.2 + 0.8 * ((k * 37) % 101) / 100.0 for k in range(n)], np.float32)
@@ -677,16 +691,14 @@ def main():
                     c = fresh_handle_cost(st, n, m_, wt_)
                     out["fresh_handle"][tag] = {k: c[k] for k in ("ms_create", "ms_first_pass_fresh_handle", "ms_destroy", "ms_create_destroy")}
 
-    if rank == 0 and world == 1 and dist is None and weights is None and (
-            args.apply or (default_workload_early and not (args.no_apply or args.no_cpu))):     # (--no-cpu skips both host-side legs; --apply: any geometry)
+    if args.full and rank == 0 and world == 1 and dist is None and weights is None and (
+            args.apply or (default_workload and not (args.no_apply or args.no_cpu))):     # (--no-cpu skips both host-side legs; --apply: any geometry)
         want = st.download_rows(-1, 0, rows)          # result of the last resident pass (same frames, same kappa)
         out["apply_from_host"] = apply_from_host(st, n, w, image_rows, args.mode, args.kappa, device, want, (cl, ch))
     st.close()
     # The other stack depths the north star names (4096 x 4096 x {32, 512} fp32, sigma clipping), same protocol
     # and the same row tiles, reported beside the headline (which stays what `value` is).
-    default_workload = (args.frames == 128 and args.mode == 2 and args.width == 4096 and args.height == 4096 and
-                        not args.weak and not args.weighted and not args.image_height)
-    if default_workload and not args.no_also:
+    if args.full and default_workload and not args.no_also:
         w128 = np.array([0.2 + 0.8 * ((k * 37) % 101) / 100.0 for k in range(128)], np.float32)
         # (tag, frames, mode, weights, geometry (width, image rows, first row, rows) or None = the headline's tile, goal-seek)
         extras = [("sigma32", 32, 2, None, None, False), ("sigma512", 512, 2, None, None, False)]
@@ -707,7 +719,7 @@ def main():
                        ("linfit32", 32, 5, None, None, False)]
         also = []
         for tag, frames, mode, wts, geo, goal_seek in extras:
-            st2, t2 = time_stack(frames, mode, args.steps, args.warmup, wts, geo)
+            st2, t2 = time_stack(frames, mode, args.steps, args.warmup, wts, geo, sync=True)
             if rank == 0:
                 gw, gh, gr0, grows = geo or (w, image_rows, row0, rows)
                 alg = 4.0 * grows * gw * (frames + 1)

@@ -36,6 +36,18 @@ def test_dump_sample_is_fixed_and_bounded(tmp_path):
     assert cc.dtype == np.float64 and cc.tolist() == [3.0, 4.0]
 
 
+def test_full_is_off_by_default_and_apply_needs_it(monkeypatch, capsys):
+    b = _bench_module()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "5"])
+    assert b.parse().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--apply"])
+    assert b.parse().full is True
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--apply"])
+    with pytest.raises(SystemExit):
+        b.parse()
+    assert "--full" in capsys.readouterr().err
+
+
 def _bench(extra, out_dir):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--frames", "16", "--width", "256", "--height", "96",
            "--steps", "3", "--warmup", "1", "--preheat-steps", "1", "--no-cpu", "--no-also",
@@ -51,6 +63,8 @@ def _bench(extra, out_dir):
 def test_dump_holds_what_the_timed_pass_returned(nl, tmp_path):
     one, res1, cc1 = _bench([], str(tmp_path / "one"))
     assert one["steps"] == 3 and one["roofline"]["timed_passes_averaged"] == 3 and one["ms_per_step"] > 0
+    # a plain run measures the headline only: every other leg is --full's
+    assert not {"ms_per_step_synchronous", "cpu_baseline", "fresh_handle", "apply_from_host", "also"} & set(one)
     # the same synthetic stack through the C ABI in this process
     with nl.StackHandle(16, 256, 96) as st:
         st.fill_synthetic()

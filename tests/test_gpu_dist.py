@@ -325,21 +325,22 @@ def test_bench_force_dist_reports_the_rccl_protocol_on_one_gpu():
     doc = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][0])
     assert doc["n_gpus"] == 1
     assert "on the device (RCCL, the pass's own stream)" in doc["config"]["sharding"]
-    p1 = subprocess.run(base, env=env, capture_output=True, text=True, timeout=280)
+    p1 = subprocess.run(base + ["--full"], env=env, capture_output=True, text=True, timeout=280)
     assert p1.returncode == 0, p1.stderr[-2000:]
     one = json.loads([ln for ln in p1.stdout.splitlines() if ln.startswith("{")][0])
     assert "RCCL" not in one["config"]["sharding"]
     assert (one["config"]["clip_low"], one["config"]["clip_high"]) == (doc["config"]["clip_low"], doc["config"]["clip_high"])
     assert "fresh_handle" in one and one["fresh_handle"]["ms_first_pass_fresh_handle"] > 0
     assert one["fresh_handle"]["clip_counters"] == [one["config"]["clip_low"], one["config"]["clip_high"]]
+    assert one["ms_per_step_synchronous"] > 0
 
 
 def test_bench_apply_from_host_leg_matches_the_resident_pass():
     # bench.py apply_from_host (round 6): OpStack.Apply from pageable host frames through nl_group_create /
     # nl_group_upload_frame[_fits] / nl_group_run / nl_group_destroy, as go/stackhip/stack_hip.go calls them -- here on a small
-    # stack (--apply runs the leg for any geometry): the fp32 leg must reproduce the resident pass's result and counters
+    # stack (--full --apply runs the leg for any geometry): the fp32 leg must reproduce the resident pass's result and counters
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--frames", "12", "--width", "512", "--height", "96",
-           "--steps", "2", "--warmup", "1", "--preheat-steps", "1", "--no-cpu", "--no-also", "--apply"]
+           "--steps", "2", "--warmup", "1", "--preheat-steps", "1", "--full", "--no-cpu", "--no-also", "--apply"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     doc = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][0])

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Round 6, item 1 of VERDICT r05: which of the buffer-cache / stream-pool commits grew the pass tail of the C3 tile and of
-# winsor 24?  Default bench line (--no-cpu) under each variant, interleaved, twice, on ONE box:
+# winsor 24?  Default bench line (--full --no-cpu) under each variant, interleaved, twice, on ONE box:
 #   pre     library of d9feae8 (before 2da1693 / d720fce / 5b852c3 / ec3beb3), build/pre/libnlstack_pre.so
 #   head    this tree
 #   nopool  this tree, NL_STREAM_POOL=0            (5b852c3 off)
@@ -15,7 +15,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=${1:-gpurun_out/bisect}; mkdir -p $O
 run() {  # tag, env...
   tag=$1; shift
-  env "$@" timeout 600 python bench.py --steps 20 --warmup 5 --no-cpu > $O/$tag.json 2> $O/$tag.err
+  env "$@" timeout 600 python bench.py --full --steps 20 --warmup 5 --no-cpu > $O/$tag.json 2> $O/$tag.err
   python3 - $O/$tag.json $tag <<'PY'
 import json, sys
 for l in open(sys.argv[1]):

@@ -34,5 +34,6 @@ doc = {"_comment": "HBM traffic per launch of the dominant kernel from rocprofv3
                    "is taken as is.",
        "entries": entries}
 json.dump(doc, open("profiles/%s_traffic.json" % rnd, "w"), indent=1)
-if os.path.exists("gpurun_out/bench_default.json"):
-    shutil.copy("gpurun_out/bench_default.json", "profiles/%s_bench_default_with_cpu_baseline.json" % rnd)
+BENCH_DEFAULT = os.path.join("build", "bench", "bench_default.json")       # tools/profile_all.sh: bench.py --full
+if os.path.exists(BENCH_DEFAULT):
+    shutil.copy(BENCH_DEFAULT, "profiles/%s_bench_default_with_cpu_baseline.json" % rnd)

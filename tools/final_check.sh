@@ -1,7 +1,7 @@
 #!/bin/bash
 # The gate a library commit has to pass (ON THE GPU BOX, from the repo root; rule since round 6: no library commit after the
 # last run of this script that ended "ok"):   tools/final_check.sh [out-dir]
-#   1. the -m gpu suite through the C ABI   2. smoke()   3. the default bench line   4. tools/check_bench.py on it
+#   1. the -m gpu suite through the C ABI   2. smoke()   3. the default bench line with --full   4. tools/check_bench.py on it
 # Stops at the first step that fails, faults or runs out of time.  The suite runs in ONE pytest process: parallel workers
 # plus the ranks the distributed tests start would put more than six processes on the shared device.
 cd "$(dirname "$0")/.." && export TMPDIR=/tmp
@@ -11,6 +11,6 @@ timeout -k 10 3000 python -m pytest tests -m gpu -x -q > $O/tests_gpu.log 2>&1; 
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; rc=$?; echo "rc=$rc" >> $O/smoke.log; tail -2 $O/smoke.log
 [ $rc -eq 0 ] || exit $rc
 t0=$(date +%s)
-timeout -k 10 900 python bench.py --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err || exit $?
+timeout -k 10 900 python bench.py --full --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err || exit $?
 echo "bench: $(( $(date +%s) - t0 )) s"
 python tools/check_bench.py $O/bench_default.json | tee $O/check_bench.txt

@@ -3,6 +3,7 @@
 # tools/collect_profiles.py <tags> copies the summaries.
 set -u
 P=tools/gpu_profile.sh
+BENCH_OUT=${1:-build/bench}
 timeout 300 $P sigma128
 timeout 300 $P sigma128tile --height 512 --row0 1536 --image-height 4096
 timeout 300 $P sigma32 --frames 32
@@ -26,5 +27,7 @@ timeout 300 $P wwinsor128 --weighted --mode 3
 timeout 300 $P sigma384 --frames 384
 timeout 300 $P sigma160 --frames 160
 timeout 300 $P sigma100 --frames 100
-timeout 600 python bench.py --steps 20 --warmup 5 > gpurun_out/bench_default.json 2> gpurun_out/bench_default.err
-tail -c 400 gpurun_out/bench_default.json
+# the default bench line with every leg (--full) into the directory collect_profiles.py copies it from
+mkdir -p "$BENCH_OUT"
+timeout 600 python bench.py --full --steps 20 --warmup 5 > "$BENCH_OUT/bench_default.json" 2> "$BENCH_OUT/bench_default.err"
+tail -c 400 "$BENCH_OUT/bench_default.json"

@@ -2,6 +2,7 @@
 # Round-6 profile set (run on the GPU box from the repo root), then tools/collect_profiles.py r06 <tags>.
 set -u
 P=tools/gpu_profile.sh
+BENCH_OUT=${1:-build/bench}
 timeout 300 $P sigma128
 timeout 300 $P sigma128tile --height 512 --row0 1536 --image-height 4096
 timeout 300 $P sigma32 --frames 32
@@ -22,5 +23,7 @@ timeout 300 $P wsigma128 --weighted
 timeout 300 $P wwinsor128 --weighted --mode 3
 timeout 600 $P wsigma512 --weighted --frames 512 --height 1024 --preheat-steps 8
 timeout 600 $P wwinsor512 --weighted --mode 3 --frames 512 --height 1024 --preheat-steps 8
-timeout 600 python bench.py --steps 20 --warmup 5 > gpurun_out/bench_default.json 2> gpurun_out/bench_default.err
-tail -c 300 gpurun_out/bench_default.json
+# the default bench line with every leg (--full) into the directory collect_profiles.py copies it from
+mkdir -p "$BENCH_OUT"
+timeout 600 python bench.py --full --steps 20 --warmup 5 > "$BENCH_OUT/bench_default.json" 2> "$BENCH_OUT/bench_default.err"
+tail -c 300 "$BENCH_OUT/bench_default.json"
