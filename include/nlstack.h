@@ -544,6 +544,42 @@ int nl_stack_result_find_stars(nl_stack_t *h, float location, float scale, float
                                nl_star_t *stars_out, int capacity, int *n_stars, float *sum_of_shifts,
                                float *avg_hfr);
 
+/* ---- OpBackExtract: pre.NewBackground + Background.Subtract / Render ----
+ * (internal/ops/pre/preprocess.go:372-398, internal/ops/pre/background.go:68-462)
+ * Bit-exact wherever the reference returns: the smoothed grid (cells_out), the info fields, the
+ * subtracted frame and the rendered background.  grid_size <= 0 is OpBackExtract's no-op: NL_OK, every
+ * bit of the frame unchanged, *info zeroed.  stars / n_stars: exactly what nl_*find_stars returned
+ * (f.Stars).  background_out (NULL or width*height floats, host): Render(), as the op.Save branch needs
+ * it; the subtracted frame is the same either way.  cells_out: the first min(cells_x*cells_y,
+ * cells_capacity) cells, row-major.  info: what Background.String() prints, plus the geometry; may be
+ * NULL.  Without a device both entries fail with NL_ERR_NO_DEVICE.
+ * Deviations, all NL_ERR_INVALID_ARG with a message naming the site:
+ *   1. where the reference panics: a cell with no sample after star masking, or with no sample below
+ *      the trimming bound (QSelectFloat32 on an empty slice); a cell index outside [0, cells) in
+ *      Subtract / Render (every grid one cell wide or tall); a cell larger than FitCell's buffer; a NaN
+ *      pivot in one of the literal selects the host runs for cells holding a NaN.
+ *   2. cells_x or cells_y is 0 (the image is smaller than half a grid cell): the reference divides by 0.
+ *   3. clip leaves cells that stay NaN on every pass of interpolate (e.g. clip >= cells): the reference
+ *      loops forever.
+ *   4. where a cell's median rank is tied between -0 and +0, the device may return the other zero;
+ *      cells and pixels then differ only in the sign of a zero (integer camera data hold no -0). */
+typedef struct nl_background {
+    int32_t cells_x, cells_y, outlier_cells;
+    float spacing_x, spacing_y, min, max;
+} nl_background_t;
+/* One host frame, in place (data_host in and out), on a handle of its own per call: safe to call from
+ * several host threads at once, like nl_find_stars. */
+int nl_back_extract(float *data_host, int width, int height, int grid_size, float hfr_factor,
+                    float sigma, int clip, const nl_star_t *stars, int n_stars,
+                    float *background_out, float *cells_out, int cells_capacity,
+                    nl_background_t *info, int device);
+/* The same on resident slot idx of a whole-image handle (row tiles: NL_ERR_INVALID_ARG), in place:
+ * the frame never crosses PCIe, only the cell grid and the Subtract tables do. */
+int nl_stack_frame_back_extract(nl_stack_t *h, int idx, int grid_size, float hfr_factor, float sigma,
+                                int clip, const nl_star_t *stars, int n_stars,
+                                float *background_out, float *cells_out, int cells_capacity,
+                                nl_background_t *info);
+
 /* ---- host-side operator mirror (nightlight_amd/host/, C++) ----
  * The reference's stack operator decoded from its JSON form and run through
  * MakePromises/Apply exactly as OpSequence would drive it

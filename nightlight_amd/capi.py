@@ -56,12 +56,21 @@ EXPORTS = [
     "nl_stack_frame_calibrate", "nl_stack_frame_badpixel",
     "nl_debayer_shape", "nl_preprocess_frame_cfa", "nl_stack_upload_frame_cfa",
     "nl_find_stars", "nl_stack_frame_find_stars", "nl_stack_result_find_stars",
+    "nl_back_extract", "nl_stack_frame_back_extract",
 ]
 
 # nl_star_t = star.Star (findstars.go:30-37), 24 bytes
 STAR_DTYPE = np.dtype([("index", "<i4"), ("value", "<f4"), ("x", "<f4"), ("y", "<f4"), ("mass", "<f4"),
                        ("hfr", "<f4")])
 assert STAR_DTYPE.itemsize == 24
+
+
+
+
+class Background(C.Structure):
+    """nl_background_t: what Background.String() prints (background.go:48-52), plus the geometry."""
+    _fields_ = [("cells_x", C.c_int32), ("cells_y", C.c_int32), ("outlier_cells", C.c_int32),
+                ("spacing_x", C.c_float), ("spacing_y", C.c_float), ("min", C.c_float), ("max", C.c_float)]
 
 
 class NlError(RuntimeError):
@@ -239,6 +248,9 @@ def open_library(path):
     L.nl_find_stars.argtypes = [_f32p, C.c_int, C.c_int] + _star_args + [C.c_int]
     L.nl_stack_frame_find_stars.argtypes = [vp, C.c_int] + _star_args
     L.nl_stack_result_find_stars.argtypes = [vp] + _star_args
+    _back_args = [C.c_int, C.c_float, C.c_float, C.c_int, vp, C.c_int, _f32p, _f32p, C.c_int, C.POINTER(Background)]
+    L.nl_back_extract.argtypes = [_f32p, C.c_int, C.c_int] + _back_args + [C.c_int]
+    L.nl_stack_frame_back_extract.argtypes = [vp, C.c_int] + _back_args
     return L
 
 

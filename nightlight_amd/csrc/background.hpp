@@ -1,0 +1,37 @@
+// background.hpp -- background extraction (OpBackExtract: pre.NewBackground + Background.Subtract / Render,
+// internal/ops/pre/background.go:68-462) for the C ABI in nlstack_frame.hip.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <string>
+
+#include "../../include/nlstack.h"
+
+namespace nl {
+
+struct BackParams {
+    int grid;                        // GridSize > 0 (GridSize <= 0 is the caller's no-op)
+    float hfr_factor, sigma;
+    int clip;                        // Clip; <= 0: no clipping
+};
+
+// per-handle device scratch, grown on demand, released by free()
+struct BackWork {
+    void *buf = nullptr;             // cell rectangles, star lists, cell results, grid, Subtract tables
+    size_t bytes = 0;
+    void *stage = nullptr;           // the large-cell path's star-masked samples (one float per pixel at most)
+    size_t stage_bytes = 0;
+    void *render = nullptr;          // the rendered background of background_host
+    size_t render_bytes = 0;
+    void free();
+};
+
+// NewBackground + Subtract on one whole width x height frame resident at d_data (width * height < 2^31), in place on
+// `stream`.  background_host (NULL or width * height floats): the Render() image; cells_out: the first
+// min(cells, cells_capacity) smoothed cell values.  Returns NL_OK or an NL_ERR_* code with the message in *msg.
+int back_extract_run(float *d_data, int width, int height, const BackParams &p, const nl_star_t *stars, int n_stars,
+                     BackWork &w, hipStream_t stream, float *background_host, float *cells_out, int cells_capacity,
+                     nl_background_t *info, std::string *msg);
+
+}  // namespace nl

@@ -412,6 +412,61 @@ int nl_find_stars(const float *data_host, int width, int height, float location,
     });
 }
 
+// ---- OpBackExtract: pre.NewBackground + Subtract / Render (internal/ops/pre/background.go:68-462; background.hip) --
+
+static int back_extract_impl(nl_stack_t *h, float *d_data, const char *who, int grid_size, float hfr_factor,
+                             float sigma, int clip, const nl_star_t *stars, int n_stars, float *background_out,
+                             float *cells_out, int cells_capacity, nl_background_t *info)
+{
+    if (n_stars < 0 || (n_stars > 0 && !stars)) return fail(NL_ERR_INVALID_ARG, "%s: %d stars", who, n_stars);
+    if (cells_capacity < 0 || (cells_capacity > 0 && !cells_out))
+        return fail(NL_ERR_INVALID_ARG, "%s: capacity %d with %s output", who, cells_capacity, cells_out ? "an" : "no");
+    if (h->row0 != 0 || h->rows != h->height)
+        return fail(NL_ERR_INVALID_ARG, "%s needs a whole-image handle (the grid spans the whole frame)", who);
+    if (h->npix >= ((int64_t)1 << 31)) return fail(NL_ERR_INVALID_ARG, "%s: frame of 2^31 pixels or more", who);
+    if (grid_size <= 0) {                  // OpBackExtract.Apply is a no-op (preprocess.go:373-375)
+        if (info) memset(info, 0, sizeof *info);
+        return NL_OK;
+    }
+    const nl::BackParams p{grid_size, hfr_factor, sigma, clip};
+    std::string msg;
+    const int rc = nl::back_extract_run(d_data, h->width, h->height, p, stars, n_stars, h->frame_scratch.back_work,
+                                        h->stream, background_out, cells_out, cells_capacity, info, &msg);
+    return rc == NL_OK ? NL_OK : fail(rc, "%s: %s", who, msg.c_str());
+}
+
+int nl_stack_frame_back_extract(nl_stack_t *h, int idx, int grid_size, float hfr_factor, float sigma, int clip,
+                                const nl_star_t *stars, int n_stars, float *background_out, float *cells_out,
+                                int cells_capacity, nl_background_t *info)
+{
+    NL_CHECK_HANDLE(h);
+    NL_SETTLE_UPLOADS(h);
+    if (idx < 0 || idx >= h->n_frames) return fail(NL_ERR_INVALID_ARG, "frame_back_extract: bad index %d", idx);
+    return back_extract_impl(h, h->d_frames + (int64_t)idx * h->fstride, "frame_back_extract", grid_size, hfr_factor,
+                             sigma, clip, stars, n_stars, background_out, cells_out, cells_capacity, info);
+}
+
+int nl_back_extract(float *data_host, int width, int height, int grid_size, float hfr_factor, float sigma, int clip,
+                    const nl_star_t *stars, int n_stars, float *background_out, float *cells_out, int cells_capacity,
+                    nl_background_t *info, int device)
+{
+    if (!data_host || width < 1 || height < 1) return fail(NL_ERR_INVALID_ARG, "back_extract: bad argument");
+    const int rc = select_device(device);
+    if (rc != NL_OK) return rc;
+    if (grid_size <= 0)                    // no-op: the frame is not even uploaded
+        return with_scratch_handle(1, 1, device, [&](nl_stack_t *h) {
+            return back_extract_impl(h, h->d_frames, "back_extract", grid_size, hfr_factor, sigma, clip, stars,
+                                     n_stars, background_out, cells_out, cells_capacity, info);
+        });
+    return with_scratch_handle(width, height, device, [&](nl_stack_t *h) {
+        int r = nl_stack_upload_tile(h, 0, data_host);
+        if (r == NL_OK)
+            r = back_extract_impl(h, h->d_frames, "back_extract", grid_size, hfr_factor, sigma, clip, stars, n_stars,
+                                  background_out, cells_out, cells_capacity, info);
+        return r == NL_OK ? nl_stack_download_tile(h, 0, data_host) : r;
+    });
+}
+
 // ---- OpBadPixel, Bayer branch, and OpDebayer (internal/ops/pre/preprocess.go:180-251; kernels in bayer.hip) -------
 
 // getOffsets (debayer.go:26-37)
@@ -570,4 +625,5 @@ void nl_stack::FrameScratch::release(int device, int64_t npix)
     if (d_bp_small) (void)hipFree(d_bp_small);
     cfa.release();
     star_work.free();
+    back_work.free();
 }

@@ -7,6 +7,7 @@
 #include <string>
 #include <vector>
 
+#include "background.hpp"
 #include "stars.hpp"
 #include "stack_kernels.h"
 
@@ -154,6 +155,8 @@ struct nl_stack {
         nl::DevBuffer cfa;
         // star detection (nl_stack_frame_find_stars / nl_stack_result_find_stars), grown
         nl::StarWork star_work;
+        // background extraction (nl_stack_frame_back_extract), grown
+        nl::BackWork back_work;
         void release(int device, int64_t npix);
     } frame_scratch;
     int max_grid = 0;

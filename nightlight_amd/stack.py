@@ -361,6 +361,14 @@ class StackHandle:
         return _find_stars(lambda *a: self._lib.nl_stack_result_find_stars(self._h, *a), location, scale, star_sig,
                            bp_sigma, star_in_out, radius, diff_std)
 
+    def frame_back_extract(self, idx, stars, grid_size, hfr_factor=4.0, sigma=1.5, clip=0, render=False):
+        """OpBackExtract on resident slot idx of a whole-image handle, in place (see back_extract).
+        Returns (None, background or None, cells, info)."""
+        _, bg, cells, info = _back_extract(lambda *a: self._lib.nl_stack_frame_back_extract(self._h, int(idx), *a),
+                                           self.width, self.height, stars, grid_size, hfr_factor, sigma, clip,
+                                           render)
+        return None, bg, cells, info
+
     def download_result_fits(self):
         raw = np.empty(self.tile_pixels * 4, np.uint8)
         capi.check(self._lib.nl_stack_download_result_fits(self._h, raw.ctypes.data_as(C.c_void_p)))
@@ -628,6 +636,37 @@ def find_stars(frame, width, height, location, scale, star_sig=15.0, bp_sigma=5.
     return _find_stars(lambda *a: lib.nl_find_stars(capi.fptr(frame), int(width), int(height), *a,
                                                     0 if device is None else int(device)),
                        location, scale, star_sig, bp_sigma, star_in_out, radius, diff_std)
+
+
+def _back_extract(call, width, height, stars, grid_size, hfr_factor, sigma, clip, render):
+    """One nl_*back_extract call through `call(<parameters from grid_size on>)`."""
+    stars = np.ascontiguousarray(np.zeros(0, capi.STAR_DTYPE) if stars is None else stars, dtype=capi.STAR_DTYPE)
+    g = int(grid_size)
+    n_cells = ((int(width) + g // 2) // g) * ((int(height) + g // 2) // g) if g > 0 else 0
+    cells = np.zeros(max(n_cells, 1), np.float32)
+    bg = np.empty(int(width) * int(height), np.float32) if render else None
+    info = capi.Background()
+    capi.check(call(g, float(hfr_factor), float(sigma), int(clip), stars.ctypes.data_as(C.c_void_p), int(stars.size),
+                    None if bg is None else capi.fptr(bg), capi.fptr(cells), int(n_cells), C.byref(info)))
+    info = {name: getattr(info, name) for name, _ in capi.Background._fields_}
+    for k in ("spacing_x", "spacing_y", "min", "max"):
+        info[k] = np.float32(info[k])
+    return None, bg, cells[:n_cells].copy(), info
+
+
+def back_extract(frame, width, height, stars, grid_size, hfr_factor=4.0, sigma=1.5, clip=0, render=False,
+                 device=None):
+    """OpBackExtract (internal/ops/pre/preprocess.go:372-398): pre.NewBackground over the frame with the star list
+    find_stars returned, then Subtract (render=False) or Render + subtract (render=True), on `device` (default 0).
+    Returns (out, background or None, cells, info): out the subtracted frame (None when grid_size <= 0, the
+    reference's no-op), cells the smoothed grid, info the dict of nl_background_t."""
+    out = np.array(frame, dtype=np.float32, copy=True).reshape(-1)
+    assert out.size == int(width) * int(height)
+    lib = capi.load()
+    _, bg, cells, info = _back_extract(
+        lambda *a: lib.nl_back_extract(capi.fptr(out), int(width), int(height), *a, 0 if device is None else int(device)),
+        width, height, stars, grid_size, hfr_factor, sigma, clip, render)
+    return (out if int(grid_size) > 0 else None), bg, cells, info
 
 
 def _cstr(s):
