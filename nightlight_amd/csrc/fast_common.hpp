@@ -379,37 +379,65 @@ __device__ __forceinline__ float nan_to_inf(float x)
 // the number of valid samples n (they occupy v[0..n), +Inf above).
 // NaN = no data (stack.go:380-387): NaNs and unused positions (k >= N) become
 // +Inf and sort last.  All loads are issued first (independent, 256 B per wave
-// each); the frame pointer advances by one frame per position and stops at the
-// last frame, so unused positions re-read a valid address.
+// each); unused positions re-read the last frame, a valid address.
 // GAP: the caller guarantees N > NS - GAP (distance to its next smaller network size).
 // SORT: FullSort, or ZonalSort<...> where only part of the order is needed.
 // PADDED = false: the caller knows N == NS (no unused positions).
-template <int NS, int GAP = 16, class SORT = FullSort, bool NT = false, bool PADDED = true>
+// RUN (opt-in per caller: it moves the register count by a few either way, and only the kernels that were looked at
+// take it): positions the caller guarantees to hold a frame are addressed from a running descriptor base, see below.
+// A caller that breaks its guarantee (N > NS - GAP; N == NS without padding) then reads past the last frame
+// instead of re-reading it.
+// clean (optional): set to whether the wave took no NaN count -- every sample of every lane is finite, n == min(N, NS)
+// on every lane (wave-uniform).
+template <int NS, int GAP = 16, class SORT = FullSort, bool NT = false, bool PADDED = true, bool RUN = false>
 __device__ __forceinline__ int gather_sorted(const float *frames, int64_t stride, int N,
-                                             unsigned boff, float (&v)[NS], int lo_pads = 0)
+                                             unsigned boff, float (&v)[NS], int lo_pads = 0, bool *clean = nullptr)
 {
     // Buffer loads: the address is (scalar descriptor base) + (scalar offset) +
     // (one per-lane byte offset), so the 128 loads need neither per-load VGPR
-    // address pairs nor branches.  Four frames share a descriptor; the frame
-    // index is clamped to the last frame (positions k >= N re-read it and are
-    // turned into missing samples below).
+    // address pairs nor branches.  Four frames share a descriptor.
+    // RUN: positions below PC hold a frame by the caller's guarantee (all of them without padding): the descriptor's base
+    // advances by four frames per chunk -- one 64-bit scalar add, written as the two instructions: left to the
+    // compiler, a running pointer turns back into c0 * frame_bytes afresh per chunk -- and the three non-zero scalar
+    // offsets are formed once (int products of the frame's bytes, as the clamped path forms them per position: the
+    // launchers admit no stride beyond that).  (Base and offset as a product per position cost the headline kernel 662 scalar
+    // instructions in front of and between its 128 loads, now 108: each delays the moment the wave's last load is out.)
+    // From PC on the frame index is clamped to the last frame (positions k >= N re-read it and are turned into missing
+    // samples below).
     const int64_t frame_bytes = stride * (int64_t)sizeof(float);
     const int last = N - 1;
+    constexpr int PC = !RUN ? 0 : (!PADDED ? NS : (NS > GAP ? (NS - GAP) / 4 * 4 : 0));
+    const int o1 = (int)frame_bytes, o2 = 2 * o1, o3 = 3 * o1;
+    const uint64_t chunk_bytes = 4 * (uint64_t)frame_bytes;
+    const unsigned step_lo = (unsigned)chunk_bytes, step_hi = (unsigned)(chunk_bytes >> 32);
+    unsigned base_lo = (unsigned)reinterpret_cast<uint64_t>(frames), base_hi = (unsigned)(reinterpret_cast<uint64_t>(frames) >> 32);
     // NT: cache policy nt (aux = 2) for kernels that read every frame byte exactly once per pass --
     // the lines need not stay in L2 / MALL: the median kernel gains 6 % (80 % of the 8 TB/s peak).
     // Not for the MAD kernel (its second read of the column hits the MALL) nor for the multi-lane
     // gathers (neighbouring waves share 128-byte lines through L2): both measured slower with nt.
     static_chunks<0, NS / 4, 4>([&](auto C) NL_INL {
         constexpr int c0 = 4 * decltype(C)::value;
-        const int f0 = min(c0, last);
-        const char *gb = reinterpret_cast<const char *>(frames) + (int64_t)f0 * frame_bytes;
-        const __amdgpu_buffer_rsrc_t rs =
-            __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(gb), 0, -1, 0x00020000);
-        static_range<0, 4>([&](auto U) NL_INL {
-            constexpr int k = c0 + decltype(U)::value;
-            const int soff = (min(k, last) - f0) * (int)frame_bytes;
-            v[k] = __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, (int)boff, soff, NT ? 2 : 0));
-        });
+        if constexpr (c0 < PC) {
+            char *gb = reinterpret_cast<char *>(((uint64_t)base_hi << 32) | base_lo);
+            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(gb, 0, -1, 0x00020000);
+            v[c0 + 0] = __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, (int)boff, 0, NT ? 2 : 0));
+            v[c0 + 1] = __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, (int)boff, o1, NT ? 2 : 0));
+            v[c0 + 2] = __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, (int)boff, o2, NT ? 2 : 0));
+            v[c0 + 3] = __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, (int)boff, o3, NT ? 2 : 0));
+            if constexpr (c0 + 4 < PC)
+                asm volatile("s_add_u32 %0, %0, %2\n\ts_addc_u32 %1, %1, %3"
+                             : "+s"(base_lo), "+s"(base_hi) : "s"(step_lo), "s"(step_hi) : "scc");
+        } else {
+            const int f0 = min(c0, last);
+            const char *gb = reinterpret_cast<const char *>(frames) + (int64_t)f0 * frame_bytes;
+            const __amdgpu_buffer_rsrc_t rs =
+                __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(gb), 0, -1, 0x00020000);
+            static_range<0, 4>([&](auto U) NL_INL {
+                constexpr int k = c0 + decltype(U)::value;
+                const int soff = (min(k, last) - f0) * (int)frame_bytes;
+                v[k] = __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, (int)boff, soff, NT ? 2 : 0));
+            });
+        }
     });
     // Unused positions k >= N (N > NS - GAP by the choice of NS) hold no frame: +Inf (they sort last), and they stay
     // out of the finiteness test below -- otherwise every wave of a stack whose frame count is not a network size
@@ -434,7 +462,9 @@ __device__ __forceinline__ int gather_sorted(const float *frames, int64_t stride
     static_range<P0 / 4 * 4, P0>([&](auto K) NL_INL { t1 += v[decltype(K)::value]; });
     const float total = (t0 + t1) + (t2 + t3);
     int nan_cnt = 0;
-    if (__any(!(__builtin_fabsf(total) < __builtin_inff()))) {
+    const bool dirty = __any(!(__builtin_fabsf(total) < __builtin_inff()));
+    if (clean) *clean = !dirty;
+    if (dirty) {
         // NaN <=> (bits & 0x7fffffff) > 0x7f800000; counted with integer arithmetic
         // (a compare would park a lane mask in SGPRs per element), then NaN -> +Inf in
         // place (tied asm operand: the column keeps its registers across the branch)

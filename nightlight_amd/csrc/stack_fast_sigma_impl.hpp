@@ -38,6 +38,16 @@ namespace nl {
 #ifndef NL_CERT_ON
 #define NL_CERT_ON(ns) true
 #endif
+// Round 8, both for the 128-position kernels only, where they were measured to pay.  The same
+// source costs the smaller exact-size kernels registers -- 64 positions 86 -> 100 and a wave per SIMD, 96: 114 -> 132,
+// 112: 141 -> 148 -- and at 112 frames, the one of them that was timed with both, it gained nothing.
+// NL_GATHER_RUN: the gather's running descriptor base.  NL_PEEL_FIRST: the peeled first pass.
+#ifndef NL_GATHER_RUN
+#define NL_GATHER_RUN(ns) ((ns) >= 128)
+#endif
+#ifndef NL_PEEL_FIRST
+#define NL_PEEL_FIRST(ns) ((ns) >= 128)
+#endif
 #ifndef NL_WINSOR_WL
 #define NL_WINSOR_WL(ns) ((ns) >= 112 ? 20 : ((ns) >= 80 ? 16 : ((ns) / 4 + 3) / 4 * 4))
 #endif
@@ -147,7 +157,8 @@ void stack_sigma_fast_kernel(StackArgs p, FastArgs q)
             // pass -- 1.1 % of them at 25 frames, 187 k, and the appends alone cost the kernel 0.3 ms)
             lo_pads = min(max(KZ / 2 + 1 - (N - ZH), 0), KZ == 4 ? KZ / 2 : KZ / 2 - 1);     // (N is wave-uniform)
         }
-        const int n = gather_sorted<NS, 16, Sorter, true, !TIGHT>(p.frames, p.stride, N, boff, v, lo_pads);
+        bool clean = false;                                   // wave-uniform: no lane holds a NaN or an infinite sample
+        const int n = gather_sorted<NS, 16, Sorter, true, !TIGHT, NL_GATHER_RUN(NS) && !RECORD>(p.frames, p.stride, N, boff, v, lo_pads, &clean);
         bool to_exact = false;
 
         float res = p.ref_loc;
@@ -249,7 +260,23 @@ void stack_sigma_fast_kernel(StackArgs p, FastArgs q)
         // max|x| over the survivors (only enters the reference-mean error term):
         // first pass from the two ends of the sorted column, afterwards from the
         // bounds every survivor passed
-        float amax = fmaxf(fabsf(pick<0, ZONAL ? ZL : 1>(v, a)), fabsf(pick<ZONAL ? ZH : 0, NS>(v, b - 1)));
+        // A clean wave of a stack of exactly NS frames (wave-uniform: the gather took no NaN count) has a = 0, b = NS on
+        // every lane, so what the first clipping pass looks up by a and b sits at constant positions: the pass is peeled
+        // off the loop under that condition with b = NS spelled out, and the compiler folds the selects of index_bits and
+        // mux_tree and the picks of amax away -- the same floating-point operations on the same operands in the same
+        // order, 115 VALU fewer per clean wave (measured, 128 frames).  (The flag goes through a scalar that the compiler cannot see through and
+        // that waits for the zone tables: a branch it can place divides the block behind the sorting network, and the
+        // kernel then takes 191 - 199 registers instead of 164 -- two waves per SIMD; tools/final_check.sh checks the headline's count.  For the same reason c above stays
+        // a pick: a branch of its own for v[NS / 2] cost 27 registers more than the 26 instructions were worth.)
+        constexpr bool PEEL = NL_PEEL_FIRST(NS) && ZT && TIGHT && !RECORD;
+        int peel_s = 0;
+        if constexpr (PEEL) {
+            peel_s = __builtin_amdgcn_readfirstlane(clean ? 1 : 0);
+            asm volatile("" : "+s"(peel_s) : "v"(q_mid), "v"(tql[0]), "v"(tqh[ZHW - 1]));
+        }
+        const bool peel = PEEL && peel_s != 0;
+        float amax;                            // (a peeled wave sets it in front of its peeled pass, below)
+        if (!peel) amax = fmaxf(fabsf(pick<0, ZONAL ? ZL : 1>(v, a)), fabsf(pick<ZONAL ? ZH : 0, NS>(v, b - 1)));
 
         int rnd = 0;                           // RECORD: clipping rounds decided so far
         if (ZONAL && lane == 0) NL_STAT(4, 1);
@@ -786,6 +813,11 @@ void stack_sigma_fast_kernel(StackArgs p, FastArgs q)
         // 3.4 passes and 28 winsorization rounds against 1.8 and 9.6), yet plain sigma clipping LOST 6 % at 100 and 128
         // frames (headline kernel 1.55 - 1.59 -> 1.67 ms; a pass is only 430 instructions) and the winsorized kernels
         // gained nothing (4.59 -> 4.60 ms).  Removed; profiles/r04_sigma512_experiments.txt.)
+        if (peel) {
+            b = NS;                                            // (what it is: n == NS on every lane)
+            amax = fmaxf(fabsf(v[0]), fabsf(v[NS - 1]));
+            one_pass();
+        }
         while (__any(active)) one_pass();
         if constexpr (RECORD) {
             // (a pixel without data is left to the full replay, which writes RefFrameLoc)
