@@ -27,6 +27,8 @@
 #include <vector>
 
 #include "background.hpp"
+#include "frame_common.hpp"
+#include "launch_common.hpp"
 
 namespace nl {
 
@@ -39,9 +41,6 @@ constexpr size_t kLdsCap = 80 * 1024;  // LDS of one cell's workgroup: two workg
 
 enum CellStatus : int { kCellOk = 0, kCellHost = 1, kCellEmpty = 2, kCellEmptyTrim = 3 };
 
-// Go's float -> int32 conversion is CVTTSS2SL on amd64: truncation, and 0x80000000 for NaN or out of range
-inline int32_t go_i32(float f) { return (f >= -2147483648.0f && f < 2147483648.0f) ? (int32_t)f : INT32_MIN; }
-
 __device__ inline uint32_t f2key(float f)
 {
     const uint32_t u = __float_as_uint(f);
@@ -52,18 +51,16 @@ __device__ inline float key2f(uint32_t k) { return __uint_as_float(k ^ ((k >> 31
 // block-wide reductions of kFitThreads lanes through red[4] (LDS); every lane gets the result
 __device__ inline unsigned block_sum(unsigned v, unsigned *red)
 {
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return red[0] + red[1] + red[2] + red[3];
+    v = wave_sum(v);
+    __syncthreads();                   // (red may still be read from the reduction before)
+    wave_values(v, red);
+    return sum_in_order<kFitThreads / 64>(red);
 }
 __device__ inline unsigned block_max(unsigned v, unsigned *red)
 {
-    for (int d = 32; d > 0; d >>= 1) v = max(v, (unsigned)__shfl_xor(v, d, 64));
+    v = wave_max(v);
     __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
+    wave_values(v, red);
     return max(max(red[0], red[1]), max(red[2], red[3]));
 }
 
@@ -251,32 +248,6 @@ __global__ __launch_bounds__(kSubThreads) void back_subtract_kernel(float *data,
     }
 }
 
-#define BACK_HIP(call)                                                                                  \
-    do {                                                                                                \
-        hipError_t e_ = (call);                                                                         \
-        if (e_ != hipSuccess) {                                                                         \
-            *msg = std::string(#call " failed: ") + hipGetErrorString(e_);                              \
-            return NL_ERR_HIP;                                                                          \
-        }                                                                                               \
-    } while (0)
-
-static size_t align_up(size_t b) { return (b + 255) & ~(size_t)255; }
-
-static hipError_t grow(void **p, size_t *have, size_t want, hipStream_t stream)
-{
-    if (want <= *have) return hipSuccess;
-    if (*p) {
-        hipError_t e = hipStreamSynchronize(stream);
-        if (e != hipSuccess) return e;
-        (void)hipFree(*p);
-        *p = nullptr;
-        *have = 0;
-    }
-    hipError_t e = hipMalloc(p, want);
-    if (e == hipSuccess) *have = want;
-    return e;
-}
-
 static int invalid(std::string *msg, const std::string &m)
 {
     *msg = m;
@@ -400,15 +371,6 @@ static void axis_table(int32_t n, float sp, int32_t cells, int *lo, float *frac)
 
 }  // namespace
 
-void BackWork::free()
-{
-    if (buf) (void)hipFree(buf);
-    if (stage) (void)hipFree(stage);
-    if (render) (void)hipFree(render);
-    buf = stage = render = nullptr;
-    bytes = stage_bytes = render_bytes = 0;
-}
-
 int back_extract_run(float *d_data, int width, int height, const BackParams &p, const nl_star_t *stars, int n_stars,
                      BackWork &w, hipStream_t stream, float *background_host, float *cells_out, int cells_capacity,
                      nl_background_t *info, std::string *msg)
@@ -478,56 +440,55 @@ int back_extract_run(float *d_data, int width, int height, const BackParams &p, 
         }
     }
 
-    // device scratch: rect | star_off | mstar | cell_val | cell_n | cell_status | cells | col_xl | col_xr | row_base | row_yr
-    const size_t o_rect = 0;
-    const size_t o_off = align_up(o_rect + sizeof(int) * rect.size());
-    const size_t o_mstar = align_up(o_off + sizeof(int) * star_off.size());
-    const size_t o_val = align_up(o_mstar + sizeof(float) * mstar.size());
-    const size_t o_n = align_up(o_val + sizeof(float) * ncell);
-    const size_t o_status = align_up(o_n + sizeof(int) * ncell);
-    const size_t o_cells = align_up(o_status + sizeof(int) * ncell);
-    const size_t o_colxl = align_up(o_cells + sizeof(float) * ncell);
-    const size_t o_colxr = align_up(o_colxl + sizeof(int) * width);
-    const size_t o_rowb = align_up(o_colxr + sizeof(float) * width);
-    const size_t o_rowyr = align_up(o_rowb + sizeof(int) * height);
-    const size_t total = align_up(o_rowyr + sizeof(float) * height);
-    BACK_HIP(grow(&w.buf, &w.bytes, total, stream));
-    unsigned char *b = static_cast<unsigned char *>(w.buf);
-    BACK_HIP(hipMemcpyAsync(b + o_rect, rect.data(), sizeof(int) * rect.size(), hipMemcpyHostToDevice, stream));
-    BACK_HIP(hipMemcpyAsync(b + o_off, star_off.data(), sizeof(int) * star_off.size(), hipMemcpyHostToDevice, stream));
-    BACK_HIP(hipMemcpyAsync(b + o_mstar, mstar.data(), sizeof(float) * mstar.size(), hipMemcpyHostToDevice, stream));
+    // device scratch
+    int4 *d_rect;
+    int *d_off, *d_n, *d_status, *cxl, *rbs;
+    float4 *d_mstar;
+    float *d_val, *dcells, *cxr, *ryr;
+    auto carve = [&](void *base) {
+        Carver c(base);
+        d_rect = c.take<int4>(ncell);
+        d_off = c.take<int>(star_off.size());
+        d_mstar = c.take<float4>(mstar.size() / 4);
+        d_val = c.take<float>(ncell);
+        d_n = c.take<int>(ncell);
+        d_status = c.take<int>(ncell);
+        dcells = c.take<float>(ncell);
+        cxl = c.take<int>(width);
+        cxr = c.take<float>(width);
+        rbs = c.take<int>(height);
+        ryr = c.take<float>(height);
+        return align_up(c.bytes());
+    };
+    NL_RUN_HIP(w.buf.reserve(carve(nullptr), stream));
+    carve(w.buf.ptr);
+    NL_RUN_HIP(hipMemcpyAsync(d_rect, rect.data(), sizeof(int) * rect.size(), hipMemcpyHostToDevice, stream));
+    NL_RUN_HIP(hipMemcpyAsync(d_off, star_off.data(), sizeof(int) * star_off.size(), hipMemcpyHostToDevice, stream));
+    NL_RUN_HIP(hipMemcpyAsync(d_mstar, mstar.data(), sizeof(float) * mstar.size(), hipMemcpyHostToDevice, stream));
 
     // FitCell on the device: LDS when the largest cell fits the budget, else the global staging area
     int dev = 0, lds_max = 0;
-    BACK_HIP(hipGetDevice(&dev));
-    BACK_HIP(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
+    NL_RUN_HIP(hipGetDevice(&dev));
+    NL_RUN_HIP(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
     const size_t sh_head = (sizeof(FitShared) + 15) & ~(size_t)15;
     const size_t lds_bytes = sh_head + sizeof(float) * (size_t)max_area;
     const bool use_lds = lds_bytes <= std::min(kLdsCap, (size_t)lds_max);
-    float *d_val = reinterpret_cast<float *>(b + o_val);
-    int *d_n = reinterpret_cast<int *>(b + o_n);
-    int *d_status = reinterpret_cast<int *>(b + o_status);
+    Launcher L(stream);
     if (use_lds) {
-        if (lds_bytes > 64 * 1024)
-            BACK_HIP(hipFuncSetAttribute((const void *)back_fit_kernel<true>,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-        hipLaunchKernelGGL(back_fit_kernel<true>, dim3(ncell), dim3(kFitThreads), lds_bytes, stream, d_data, width,
-                           reinterpret_cast<const int4 *>(b + o_rect), reinterpret_cast<const int *>(b + o_off),
-                           reinterpret_cast<const float4 *>(b + o_mstar), p.sigma, nullptr, d_val, d_n, d_status);
+        L(back_fit_kernel<true>, ncell, kFitThreads, lds_bytes, d_data, width, d_rect, d_off, d_mstar, p.sigma, nullptr,
+          d_val, d_n, d_status);
     } else {
-        BACK_HIP(grow(&w.stage, &w.stage_bytes, sizeof(float) * (size_t)width * height, stream));
-        hipLaunchKernelGGL(back_fit_kernel<false>, dim3(ncell), dim3(kFitThreads), sh_head, stream, d_data, width,
-                           reinterpret_cast<const int4 *>(b + o_rect), reinterpret_cast<const int *>(b + o_off),
-                           reinterpret_cast<const float4 *>(b + o_mstar), p.sigma, static_cast<float *>(w.stage),
-                           d_val, d_n, d_status);
+        NL_RUN_HIP(w.stage.reserve(sizeof(float) * (size_t)width * height, stream));
+        L(back_fit_kernel<false>, ncell, kFitThreads, sh_head, d_data, width, d_rect, d_off, d_mstar, p.sigma,
+          static_cast<float *>(w.stage.ptr), d_val, d_n, d_status);
     }
-    BACK_HIP(hipGetLastError());
+    NL_RUN_LAUNCHED(L);
     std::vector<float> cells(ncell);
     std::vector<int> cnt(ncell), status(ncell);
-    BACK_HIP(hipMemcpyAsync(cells.data(), d_val, sizeof(float) * ncell, hipMemcpyDeviceToHost, stream));
-    BACK_HIP(hipMemcpyAsync(cnt.data(), d_n, sizeof(int) * ncell, hipMemcpyDeviceToHost, stream));
-    BACK_HIP(hipMemcpyAsync(status.data(), d_status, sizeof(int) * ncell, hipMemcpyDeviceToHost, stream));
-    BACK_HIP(hipStreamSynchronize(stream));
+    NL_RUN_HIP(hipMemcpyAsync(cells.data(), d_val, sizeof(float) * ncell, hipMemcpyDeviceToHost, stream));
+    NL_RUN_HIP(hipMemcpyAsync(cnt.data(), d_n, sizeof(int) * ncell, hipMemcpyDeviceToHost, stream));
+    NL_RUN_HIP(hipMemcpyAsync(status.data(), d_status, sizeof(int) * ncell, hipMemcpyDeviceToHost, stream));
+    NL_RUN_HIP(hipStreamSynchronize(stream));
 
     // the reference's panics in cell order; the flagged cells literally on the host
     std::vector<float> rectbuf, med, mad;
@@ -544,9 +505,9 @@ int back_extract_run(float *d_data, int width, int height, const BackParams &p, 
         const int *r = &rect[4 * (size_t)c];
         const int cw = r[1] - r[0], ch = r[3] - r[2];
         rectbuf.resize((size_t)cw * ch);
-        BACK_HIP(hipMemcpy2DAsync(rectbuf.data(), sizeof(float) * cw, d_data + (int64_t)r[2] * width + r[0],
+        NL_RUN_HIP(hipMemcpy2DAsync(rectbuf.data(), sizeof(float) * cw, d_data + (int64_t)r[2] * width + r[0],
                                   sizeof(float) * width, sizeof(float) * cw, ch, hipMemcpyDeviceToHost, stream));
-        BACK_HIP(hipStreamSynchronize(stream));
+        NL_RUN_HIP(hipStreamSynchronize(stream));
         med.clear();
         for (int y = r[2]; y < r[3]; y++)
             for (int x = r[0]; x < r[1]; x++) {
@@ -638,39 +599,29 @@ int back_extract_run(float *d_data, int width, int height, const BackParams &p, 
     std::vector<int> row_base(height);
     for (int y = 0; y < height; y++) row_base[y] = row_yl[y] * g.cells_x;
 
-    BACK_HIP(hipMemcpyAsync(b + o_cells, smooth.data(), sizeof(float) * ncell, hipMemcpyHostToDevice, stream));
-    BACK_HIP(hipMemcpyAsync(b + o_colxl, col_xl.data(), sizeof(int) * width, hipMemcpyHostToDevice, stream));
-    BACK_HIP(hipMemcpyAsync(b + o_colxr, col_xr.data(), sizeof(float) * width, hipMemcpyHostToDevice, stream));
-    BACK_HIP(hipMemcpyAsync(b + o_rowb, row_base.data(), sizeof(int) * height, hipMemcpyHostToDevice, stream));
-    BACK_HIP(hipMemcpyAsync(b + o_rowyr, row_yr.data(), sizeof(float) * height, hipMemcpyHostToDevice, stream));
+    NL_RUN_HIP(hipMemcpyAsync(dcells, smooth.data(), sizeof(float) * ncell, hipMemcpyHostToDevice, stream));
+    NL_RUN_HIP(hipMemcpyAsync(cxl, col_xl.data(), sizeof(int) * width, hipMemcpyHostToDevice, stream));
+    NL_RUN_HIP(hipMemcpyAsync(cxr, col_xr.data(), sizeof(float) * width, hipMemcpyHostToDevice, stream));
+    NL_RUN_HIP(hipMemcpyAsync(rbs, row_base.data(), sizeof(int) * height, hipMemcpyHostToDevice, stream));
+    NL_RUN_HIP(hipMemcpyAsync(ryr, row_yr.data(), sizeof(float) * height, hipMemcpyHostToDevice, stream));
     float *d_bg = nullptr;
     if (background_host) {
-        BACK_HIP(grow(&w.render, &w.render_bytes, sizeof(float) * (size_t)width * height, stream));
-        d_bg = static_cast<float *>(w.render);
+        NL_RUN_HIP(w.render.reserve(sizeof(float) * (size_t)width * height, stream));
+        d_bg = static_cast<float *>(w.render.ptr);
     }
     const int col_blocks = (width + kSubThreads * kSubCols - 1) / (kSubThreads * kSubCols);
     const bool vec = width % kSubCols == 0 && ((uintptr_t)d_data & 15) == 0;
-    const dim3 grid((unsigned)col_blocks * (unsigned)height), block(kSubThreads);
-    const int *cxl = reinterpret_cast<const int *>(b + o_colxl), *rbs = reinterpret_cast<const int *>(b + o_rowb);
-    const float *cxr = reinterpret_cast<const float *>(b + o_colxr), *ryr = reinterpret_cast<const float *>(b + o_rowyr);
-    const float *dcells = reinterpret_cast<const float *>(b + o_cells);
-    if (vec && d_bg)
-        hipLaunchKernelGGL((back_subtract_kernel<true, true>), grid, block, 0, stream, d_data, d_bg, width, col_blocks,
-                           cxl, cxr, rbs, ryr, dcells, g.cells_x);
-    else if (vec)
-        hipLaunchKernelGGL((back_subtract_kernel<true, false>), grid, block, 0, stream, d_data, d_bg, width, col_blocks,
-                           cxl, cxr, rbs, ryr, dcells, g.cells_x);
-    else if (d_bg)
-        hipLaunchKernelGGL((back_subtract_kernel<false, true>), grid, block, 0, stream, d_data, d_bg, width, col_blocks,
-                           cxl, cxr, rbs, ryr, dcells, g.cells_x);
-    else
-        hipLaunchKernelGGL((back_subtract_kernel<false, false>), grid, block, 0, stream, d_data, d_bg, width, col_blocks,
-                           cxl, cxr, rbs, ryr, dcells, g.cells_x);
-    BACK_HIP(hipGetLastError());
+    with_bool(vec, [&](auto V) {
+        with_bool(d_bg != nullptr, [&](auto R) {
+            L(back_subtract_kernel<decltype(V)::value, decltype(R)::value>, (unsigned)col_blocks * (unsigned)height,
+              kSubThreads, 0, d_data, d_bg, width, col_blocks, cxl, cxr, rbs, ryr, dcells, g.cells_x);
+        });
+    });
+    NL_RUN_LAUNCHED(L);
     if (d_bg)
-        BACK_HIP(hipMemcpyAsync(background_host, d_bg, sizeof(float) * (size_t)width * height, hipMemcpyDeviceToHost,
+        NL_RUN_HIP(hipMemcpyAsync(background_host, d_bg, sizeof(float) * (size_t)width * height, hipMemcpyDeviceToHost,
                                 stream));
-    BACK_HIP(hipStreamSynchronize(stream));
+    NL_RUN_HIP(hipStreamSynchronize(stream));
 
     if (cells_out && cells_capacity > 0)
         memcpy(cells_out, smooth.data(), sizeof(float) * (size_t)std::min<int64_t>(ncell, cells_capacity));

@@ -7,6 +7,7 @@
 #include <string>
 
 #include "../../include/nlstack.h"
+#include "dev_memory.hpp"
 
 namespace nl {
 
@@ -16,15 +17,13 @@ struct BackParams {
     int clip;                        // Clip; <= 0: no clipping
 };
 
-// per-handle device scratch, grown on demand, released by free()
+// per-handle device scratch, grown on demand
 struct BackWork {
-    void *buf = nullptr;             // cell rectangles, star lists, cell results, grid, Subtract tables
-    size_t bytes = 0;
-    void *stage = nullptr;           // the large-cell path's star-masked samples (one float per pixel at most)
-    size_t stage_bytes = 0;
-    void *render = nullptr;          // the rendered background of background_host
-    size_t render_bytes = 0;
-    void free();
+    DevBuffer buf;                   // cell rectangles, star lists, cell results, grid, Subtract tables
+    DevBuffer stage;                 // the large-cell path's star-masked samples (one float per pixel at most)
+    DevBuffer render;                // the rendered background of background_host
+    size_t bytes() const { return buf.bytes + stage.bytes + render.bytes; }
+    void release() { buf.release(); stage.release(); render.release(); }
 };
 
 // NewBackground + Subtract on one whole width x height frame resident at d_data (width * height < 2^31), in place on

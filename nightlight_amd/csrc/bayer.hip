@@ -18,6 +18,8 @@
 // No fused multiply-add anywhere (-ffp-contract=off, as the reference's amd64 build).
 // The debayer is one launch, one lane per 2x2 output box, in the reference's expression order.
 #include "bayer.hpp"
+#include "frame_common.hpp"
+#include "launch_common.hpp"
 #include "median9.hpp"
 
 namespace nl {
@@ -258,14 +260,8 @@ __global__ __launch_bounds__(kBayerThreads) void bayer_replace_kernel(float *dat
             count++;
         }
     }
-    for (int off = 32; off > 0; off >>= 1) count += __shfl_xor(count, off, 64);
-    if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = count;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned total = 0;
-        for (int w = 0; w < kBayerThreads / 64; w++) total += s_wave[w];
-        removed[j] = total;
-    }
+    wave_values(wave_sum(count), s_wave);
+    if (threadIdx.x == 0) removed[j] = sum_in_order<kBayerThreads / 64>(s_wave);
 }
 
 __global__ __launch_bounds__(kCountThreads) void bayer_count_kernel(const unsigned *removed, int64_t blocks,
@@ -274,14 +270,8 @@ __global__ __launch_bounds__(kCountThreads) void bayer_count_kernel(const unsign
     __shared__ unsigned long long s_wave[kCountThreads / 64];
     unsigned long long sum = 0;
     for (int64_t b = threadIdx.x; b < blocks; b += kCountThreads) sum += removed[b];
-    for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 64);
-    if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = sum;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long total = 0;
-        for (int w = 0; w < kCountThreads / 64; w++) total += s_wave[w];
-        p->removed = total;
-    }
+    wave_values(wave_sum(sum), s_wave);
+    if (threadIdx.x == 0) p->removed = sum_in_order<kCountThreads / 64>(s_wave);
 }
 
 // DebayerBilinearRGGBTo{Red,Green,Blue} (debayer.go:63-263), one lane per 2x2 box of the output; box rows * blocks
@@ -358,18 +348,6 @@ __global__ __launch_bounds__(kBayerThreads) void debayer_kernel(const float *dat
     }
 }
 
-template <int CH>
-void launch_debayer_t(bool v2, dim3 grid, const float *data, int width, int height, int xo, int yo, int adj_w,
-                      float *out, int64_t out_stride, hipStream_t stream)
-{
-    if (v2)
-        hipLaunchKernelGGL((debayer_kernel<CH, true>), grid, dim3(kBayerThreads), 0, stream, data, width, height, xo,
-                           yo, adj_w, out, out_stride);
-    else
-        hipLaunchKernelGGL((debayer_kernel<CH, false>), grid, dim3(kBayerThreads), 0, stream, data, width, height, xo,
-                           yo, adj_w, out, out_stride);
-}
-
 }  // namespace
 
 BayerGeom bayer_geom(int width, int height, int channel, int xo, int yo)
@@ -400,26 +378,18 @@ int64_t bayer_replace_blocks(const BayerGeom &g) { return g.rows; }
 hipError_t launch_bayer_correct(float *data, const BayerGeom &g, float sigma_low, float sigma_high,
                                 const BayerScratch &s, hipStream_t stream)
 {
-    const dim3 grid((unsigned)(g.rows * ((g.cols + kBayerThreads - 1) / kBayerThreads)));
+    const unsigned grid = (unsigned)(g.rows * ((g.cols + kBayerThreads - 1) / kBayerThreads));
     const bool any = g.rows > 0 && g.cols > 0;         // (a row without a channel pixel still sums to +0)
-    if (any) hipLaunchKernelGGL(bayer_median_kernel, grid, dim3(kBayerThreads), 0, stream, data, g, s.delta, s.median);
     const unsigned sum_blocks = (unsigned)((g.rows + kSumRows - 1) / kSumRows);
-    if (g.rows > 0)
-        hipLaunchKernelGGL(bayer_rowsum_kernel<false>, dim3(sum_blocks), dim3(kBayerThreads), 0, stream, s.delta, g,
-                           s.params, s.rowsum);
-    hipLaunchKernelGGL(bayer_total_kernel<false>, dim3(1), dim3(kBayerThreads), 0, stream, s.rowsum, g, sigma_low,
-                       sigma_high, s.params);
-    if (g.rows > 0)
-        hipLaunchKernelGGL(bayer_rowsum_kernel<true>, dim3(sum_blocks), dim3(kBayerThreads), 0, stream, s.delta, g,
-                           s.params, s.rowsum);
-    hipLaunchKernelGGL(bayer_total_kernel<true>, dim3(1), dim3(kBayerThreads), 0, stream, s.rowsum, g, sigma_low,
-                       sigma_high, s.params);
-    if (any)
-        hipLaunchKernelGGL(bayer_replace_kernel, dim3((unsigned)g.rows), dim3(kBayerThreads), 0, stream, data,
-                           s.delta, s.median, g, s.params, s.removed);
-    hipLaunchKernelGGL(bayer_count_kernel, dim3(1), dim3(kCountThreads), 0, stream, s.removed,
-                       any ? bayer_replace_blocks(g) : (int64_t)0, s.params);
-    return hipGetLastError();
+    Launcher L(stream);
+    if (any) L(bayer_median_kernel, grid, kBayerThreads, 0, data, g, s.delta, s.median);
+    if (g.rows > 0) L(bayer_rowsum_kernel<false>, sum_blocks, kBayerThreads, 0, s.delta, g, s.params, s.rowsum);
+    L(bayer_total_kernel<false>, 1, kBayerThreads, 0, s.rowsum, g, sigma_low, sigma_high, s.params);
+    if (g.rows > 0) L(bayer_rowsum_kernel<true>, sum_blocks, kBayerThreads, 0, s.delta, g, s.params, s.rowsum);
+    L(bayer_total_kernel<true>, 1, kBayerThreads, 0, s.rowsum, g, sigma_low, sigma_high, s.params);
+    if (any) L(bayer_replace_kernel, (unsigned)g.rows, kBayerThreads, 0, data, s.delta, s.median, g, s.params, s.removed);
+    L(bayer_count_kernel, 1, kCountThreads, 0, s.removed, any ? bayer_replace_blocks(g) : (int64_t)0, s.params);
+    return L.err;
 }
 
 hipError_t launch_debayer(const float *data, int width, int height, int channel, int xo, int yo, float *out,
@@ -427,12 +397,16 @@ hipError_t launch_debayer(const float *data, int width, int height, int channel,
 {
     const int adj_w = (width - xo) & ~1, adj_h = (height - yo) & ~1;
     if (adj_w <= 0 || adj_h <= 0) return hipSuccess;
-    const dim3 grid((unsigned)((adj_h >> 1) * (((adj_w >> 1) + kBayerThreads - 1) / kBayerThreads)));
+    const unsigned grid = (unsigned)((adj_h >> 1) * (((adj_w >> 1) + kBayerThreads - 1) / kBayerThreads));
     const bool v2 = ((uintptr_t)out & 7) == 0 && (out_stride & 1) == 0;
-    if (channel == kBayerR) launch_debayer_t<kBayerR>(v2, grid, data, width, height, xo, yo, adj_w, out, out_stride, stream);
-    else if (channel == kBayerG) launch_debayer_t<kBayerG>(v2, grid, data, width, height, xo, yo, adj_w, out, out_stride, stream);
-    else launch_debayer_t<kBayerB>(v2, grid, data, width, height, xo, yo, adj_w, out, out_stride, stream);
-    return hipGetLastError();
+    Launcher L(stream);
+    with_class<kBayerR, kBayerG, kBayerB>(channel, [&](auto CH) {          // (channel is one of the three)
+        with_bool(v2, [&](auto V2) {
+            L(debayer_kernel<decltype(CH)::value, decltype(V2)::value>, grid, kBayerThreads, 0, data, width, height, xo,
+              yo, adj_w, out, out_stride);
+        });
+    });
+    return L.err;
 }
 
 }  // namespace nl

@@ -6,29 +6,11 @@
 // All are single-pass HBM streams (4 B read per sample): 16-byte loads,
 // grid-stride, wave shuffle + LDS block reduction, one fp64 partial per
 // workgroup, summed on the host (a few thousand values).
+#include "frame_common.hpp"
+#include "launch_common.hpp"
 #include "median9.hpp"
-#include "stack_kernels.h"
 
 namespace nl {
-
-__device__ __forceinline__ double wave_sum_d(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-__device__ __forceinline__ float wave_min_f(float v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fminf(v, __shfl_xor(v, off, 64));
-    return v;
-}
-__device__ __forceinline__ float wave_max_f(float v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-    return v;
-}
 
 // min / max in fp32, sum in fp64 (stats.go:264-277, stats_amd64.s:28-92).
 // A comparison with NaN is false in the reference, so NaN never becomes
@@ -61,9 +43,9 @@ __global__ __launch_bounds__(256) void min_sum_max_kernel(const float *data, int
     }
     __shared__ float s_mn[4], s_mx[4];
     __shared__ double s_sum[4];
-    mn = wave_min_f(mn);
-    mx = wave_max_f(mx);
-    sum = wave_sum_d(sum);
+    mn = wave_min(mn);
+    mx = wave_max(mx);
+    sum = wave_sum(sum);
     const int wave = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0) { s_mn[wave] = mn; s_mx[wave] = mx; s_sum[wave] = sum; }
     __syncthreads();
@@ -103,10 +85,8 @@ __global__ __launch_bounds__(256) void variance_kernel(const float *data, int64_
         }
     }
     __shared__ double s_sum[4];
-    sum = wave_sum_d(sum);
-    if ((threadIdx.x & 63) == 0) s_sum[threadIdx.x >> 6] = sum;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];
+    wave_values(wave_sum(sum), s_sum);
+    if (threadIdx.x == 0) partial[blockIdx.x] = sum_in_order<4>(s_sum);
 }
 
 // Immerkaer noise estimate (noise.go:32-55): per interior pixel the fp32
@@ -139,10 +119,8 @@ __global__ __launch_bounds__(256) void noise_kernel(const float *data, int width
         sum += (double)fabsf(conv);
     }
     __shared__ double s_sum[4];
-    sum = wave_sum_d(sum);
-    if ((threadIdx.x & 63) == 0) s_sum[threadIdx.x >> 6] = sum;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];
+    wave_values(wave_sum(sum), s_sum);
+    if (threadIdx.x == 0) partial[blockIdx.x] = sum_in_order<4>(s_sum);
 }
 
 // MedianFilter3x3 (median3x3.go:26-110) through the shared network of median9.hpp.
@@ -216,30 +194,33 @@ hipError_t launch_median_mask(const float *in, float *out, int64_t n, const int 
 {
     MaskArg m;
     for (int j = 0; j < kMaskMax; j++) m.off[j] = j < len ? mask[j] : 0;
-    hipLaunchKernelGGL(median_mask_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, in, out, n, m, len);
-    return hipGetLastError();
+    Launcher L(stream);
+    L(median_mask_kernel, (unsigned)((n + 255) / 256), 256, 0, in, out, n, m, len);
+    return L.err;
 }
 
 hipError_t launch_min_sum_max(const float *data, int64_t n, double *partial, int blocks,
                               hipStream_t stream)
 {
-    hipLaunchKernelGGL(min_sum_max_kernel, dim3(blocks), dim3(256), 0, stream, data, n, partial);
-    return hipGetLastError();
+    Launcher L(stream);
+    L(min_sum_max_kernel, blocks, 256, 0, data, n, partial);
+    return L.err;
 }
 
 hipError_t launch_variance(const float *data, int64_t n, float mean, double *partial, int blocks,
                            hipStream_t stream)
 {
-    hipLaunchKernelGGL(variance_kernel, dim3(blocks), dim3(256), 0, stream, data, n, mean, partial);
-    return hipGetLastError();
+    Launcher L(stream);
+    L(variance_kernel, blocks, 256, 0, data, n, mean, partial);
+    return L.err;
 }
 
 hipError_t launch_noise(const float *data, int width, int height, double *partial, int blocks,
                         hipStream_t stream)
 {
-    hipLaunchKernelGGL(noise_kernel, dim3(blocks), dim3(256), 0, stream, data, width, height,
-                       partial);
-    return hipGetLastError();
+    Launcher L(stream);
+    L(noise_kernel, blocks, 256, 0, data, width, height, partial);
+    return L.err;
 }
 
 hipError_t launch_median3x3(const float *in, float *out, int width, int height, hipStream_t stream)
@@ -247,8 +228,9 @@ hipError_t launch_median3x3(const float *in, float *out, int width, int height, 
     const int64_t total = (int64_t)width * height;
     int64_t g = (total + 255) / 256;
     if (g > 256 * 32) g = 256 * 32;
-    hipLaunchKernelGGL(median3x3_kernel, dim3((int)g), dim3(256), 0, stream, in, out, width, height);
-    return hipGetLastError();
+    Launcher L(stream);
+    L(median3x3_kernel, (unsigned)g, 256, 0, in, out, width, height);
+    return L.err;
 }
 
 }  // namespace nl

@@ -12,7 +12,8 @@
 // -ffp-contract=off), hence bit-exact; all of it is HBM-bound.
 #include <float.h>
 
-#include "stack_kernels.h"
+#include "frame_common.hpp"
+#include "launch_common.hpp"
 
 namespace nl {
 
@@ -74,17 +75,15 @@ __device__ __forceinline__ void decode_four(const unsigned char *raw, int64_t i4
     }
 }
 
-// partial[3*b + {0,1,2}] = {min, max, sum} of block b, as doubles (min / max are exact floats)
+// partial[3*b + {0,1,2}] = {min, max, sum} of block b, as doubles (min / max are exact floats); the four wave sums
+// pairwise, unlike everywhere else
 __device__ __forceinline__ void block_min_max_sum(float mn, float mx, double sum, double *partial)
 {
     __shared__ float s_mn[4], s_mx[4];
     __shared__ double s_sum[4];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        mn = fminf(mn, __shfl_xor(mn, o, 64));
-        mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-        sum += __shfl_xor(sum, o, 64);
-    }
+    mn = wave_min(mn);
+    mx = wave_max(mx);
+    sum = wave_sum(sum);
     if ((threadIdx.x & 63) == 0) {
         s_mn[threadIdx.x >> 6] = mn; s_mx[threadIdx.x >> 6] = mx; s_sum[threadIdx.x >> 6] = sum;
     }
@@ -198,17 +197,19 @@ __global__ __launch_bounds__(256) void project_kernel(const float *src, int src_
 
 }  // namespace
 
-template <int BITPIX>
-static void launch_decode_t(const void *raw, int64_t n, float bscale, float bzero, bool affine, float mult,
-                            float off, float *out, double *partial, int blocks, hipStream_t stream)
+// f(std::integral_constant<int, BITPIX>) for a BITPIX of FITS; false for any other value
+template <class F>
+static bool with_bitpix(int bitpix, F &&f)
 {
-    const unsigned char *r = static_cast<const unsigned char *>(raw);
-    if (affine)
-        hipLaunchKernelGGL((fits_decode_kernel<BITPIX, true>), dim3(blocks), dim3(256), 0, stream, r, n, bscale,
-                           bzero, mult, off, out, partial);
-    else
-        hipLaunchKernelGGL((fits_decode_kernel<BITPIX, false>), dim3(blocks), dim3(256), 0, stream, r, n, bscale,
-                           bzero, mult, off, out, partial);
+    switch (bitpix) {
+    case 8:   f(std::integral_constant<int, 8>{}); return true;
+    case 16:  f(std::integral_constant<int, 16>{}); return true;
+    case 32:  f(std::integral_constant<int, 32>{}); return true;
+    case 64:  f(std::integral_constant<int, 64>{}); return true;
+    case -32: f(std::integral_constant<int, -32>{}); return true;
+    case -64: f(std::integral_constant<int, -64>{}); return true;
+    default:  return false;
+    }
 }
 
 int fits_bytes_per_value(int bitpix)
@@ -226,33 +227,32 @@ hipError_t launch_fits_decode(const void *raw, int bitpix, int64_t n, float bsca
                               float mult, float off, float *out, double *partial, int blocks,
                               hipStream_t stream)
 {
-    switch (bitpix) {
-    case 8:   launch_decode_t<8>(raw, n, bscale, bzero, affine, mult, off, out, partial, blocks, stream); break;
-    case 16:  launch_decode_t<16>(raw, n, bscale, bzero, affine, mult, off, out, partial, blocks, stream); break;
-    case 32:  launch_decode_t<32>(raw, n, bscale, bzero, affine, mult, off, out, partial, blocks, stream); break;
-    case 64:  launch_decode_t<64>(raw, n, bscale, bzero, affine, mult, off, out, partial, blocks, stream); break;
-    case -32: launch_decode_t<-32>(raw, n, bscale, bzero, affine, mult, off, out, partial, blocks, stream); break;
-    case -64: launch_decode_t<-64>(raw, n, bscale, bzero, affine, mult, off, out, partial, blocks, stream); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    Launcher L(stream);
+    const bool known = with_bitpix(bitpix, [&](auto B) {
+        with_bool(affine, [&](auto A) {
+            L(fits_decode_kernel<decltype(B)::value, decltype(A)::value>, blocks, 256, 0,
+              static_cast<const unsigned char *>(raw), n, bscale, bzero, mult, off, out, partial);
+        });
+    });
+    return known ? L.err : hipErrorInvalidValue;
 }
 
 hipError_t launch_fits_encode(const float *data, int64_t n, int replace_nans, void *raw, hipStream_t stream)
 {
     const int64_t want = (n + 255) / 256;
     const int blocks = (int)(want < 1 ? 1 : (want > 16384 ? 16384 : want));
-    hipLaunchKernelGGL(fits_encode_kernel, dim3(blocks), dim3(256), 0, stream, data, n, replace_nans,
-                       static_cast<unsigned *>(raw));
-    return hipGetLastError();
+    Launcher L(stream);
+    L(fits_encode_kernel, blocks, 256, 0, data, n, replace_nans, static_cast<unsigned *>(raw));
+    return L.err;
 }
 
 hipError_t launch_affine(float *data, int64_t n, float mult, float off, hipStream_t stream)
 {
     const int64_t want = ((n >> 2) + 255) / 256;
     const int blocks = (int)(want < 1 ? 1 : (want > 16384 ? 16384 : want));
-    hipLaunchKernelGGL(affine_kernel, dim3(blocks), dim3(256), 0, stream, data, n, mult, off);
-    return hipGetLastError();
+    Launcher L(stream);
+    L(affine_kernel, blocks, 256, 0, data, n, mult, off);
+    return L.err;
 }
 
 hipError_t launch_project(const float *src, int src_w, int src_h, float *dst, int dst_w, int row0, int rows,
@@ -260,13 +260,12 @@ hipError_t launch_project(const float *src, int src_w, int src_h, float *dst, in
                           hipStream_t stream)
 {
     const dim3 grid((unsigned)((dst_w + 255) / 256), (unsigned)rows);
-    if (affine)
-        hipLaunchKernelGGL((project_kernel<true>), grid, dim3(256), 0, stream, src, src_w, src_h, dst, dst_w, row0,
-                           rows, inv[0], inv[1], inv[2], inv[3], inv[4], inv[5], oob, mult, off);
-    else
-        hipLaunchKernelGGL((project_kernel<false>), grid, dim3(256), 0, stream, src, src_w, src_h, dst, dst_w, row0,
-                           rows, inv[0], inv[1], inv[2], inv[3], inv[4], inv[5], oob, mult, off);
-    return hipGetLastError();
+    Launcher L(stream);
+    with_bool(affine, [&](auto A) {
+        L(project_kernel<decltype(A)::value>, grid, 256, 0, src, src_w, src_h, dst, dst_w, row0, rows, inv[0], inv[1],
+          inv[2], inv[3], inv[4], inv[5], oob, mult, off);
+    });
+    return L.err;
 }
 
 }  // namespace nl

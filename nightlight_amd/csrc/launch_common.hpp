@@ -1,6 +1,7 @@
-// launch_common.hpp -- what the stack-pass launchers (the launch_* functions of stack_*.hip) share: the frame-count
-// class dispatch, one error path for everything a launcher enqueues, kernel names as rocprofv3 prints them, the lanes
-// per pixel of the 129 ... 512-frame kernels, and the two inputs of a FastArgs pass.  Host code only.
+// launch_common.hpp -- what everything that launches a kernel shares (the launch_* functions of the stack passes and of
+// the per-frame operators, find_stars_run, back_extract_run): the run-time -> template dispatch, one error path for
+// everything a launcher enqueues, kernel names as rocprofv3 prints them, the lanes per pixel of the 129 ... 512-frame
+// kernels, and the two inputs of a FastArgs pass.  Host code only.
 #pragma once
 #include <string>
 #include <type_traits>
@@ -55,18 +56,31 @@ struct Launcher {
     void keep(hipError_t e) { if (err == hipSuccess) err = e; }
     // dynamic LDS above 64 KiB needs the kernel's attribute raised first
     template <class... P, class... A>
-    void operator()(void (*kernel)(P...), unsigned grid, unsigned block, size_t lds, A &&... args)
+    void operator()(void (*kernel)(P...), dim3 grid, unsigned block, size_t lds, A &&... args)
     {
         if (lds > 64 * 1024) {
             const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             if (e != hipSuccess) { keep(e); return; }
         }
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, stream, std::forward<A>(args)...);
+        hipLaunchKernelGGL(kernel, grid, dim3(block), lds, stream, std::forward<A>(args)...);
         keep(hipGetLastError());
     }
     void record(hipEvent_t event) { if (event) keep(hipEventRecord(event, stream)); }
 };
+
+// In a function that returns an NL_* code and reports through std::string *msg (find_stars_run, back_extract_run):
+// leave with NL_ERR_HIP when a HIP call -- or, as NL_RUN_LAUNCHED(L), anything Launcher L enqueued -- failed
+#define NL_RUN_CHECK(e, what)                                                                           \
+    do {                                                                                                \
+        hipError_t e_ = (e);                                                                            \
+        if (e_ != hipSuccess) {                                                                         \
+            *msg = std::string(what " failed: ") + hipGetErrorString(e_);                               \
+            return NL_ERR_HIP;                                                                          \
+        }                                                                                               \
+    } while (0)
+#define NL_RUN_HIP(call) NL_RUN_CHECK(call, #call)
+#define NL_RUN_LAUNCHED(L) NL_RUN_CHECK((L).err, "hipGetLastError()")
 
 template <class T>
 std::string name_arg(T v)

@@ -430,7 +430,7 @@ static int destroy_impl(nl_stack_t *h)
         cached_free(h->d_lf_state[i], sizeof(uint4) * (size_t)h->npix * (size_t)h->lf_lanes, h->device);
     }
     if (h->d_lf_count) (void)hipFree(h->d_lf_count);
-    h->frame_scratch.release(h->device, h->npix);
+    h->frame_scratch.release(h->device);
     for (int i = 0; i < kStageSlots; i++) {
         pinned_free(h->h_stage[i], h->stage_cap[i]);
         if (h->stage_done[i]) (void)hipEventDestroy(h->stage_done[i]);
@@ -640,8 +640,8 @@ int nl_stack_download_rows(nl_stack_t *h, int idx, int first_row, int n_rows, fl
 
 // Device memory the handle holds right now: the buffers of nl_stack_create plus everything a pass, an upload path or
 // the stack of stacks has allocated since (decision-pass thresholds, linear-fit cascade lists, accumulator, ingest
-// staging) -- those stay until nl_stack_destroy, so a caller that sizes batches to the device (OpStackBatches,
-// stackbatches.go:121-187 does it for host memory) can see what is left.
+// staging, the scratch of the steps on one frame) -- those stay until nl_stack_destroy, so a caller that sizes batches
+// to the device (OpStackBatches, stackbatches.go:121-187 does it for host memory) can see what is left.
 int64_t nl_stack_device_bytes(nl_stack_t *h)
 {
     if (!h) return 0;
@@ -666,7 +666,7 @@ int64_t nl_stack_device_bytes(nl_stack_t *h)
         if (h->d_lf_state[i]) b += np * 16 * lanes;
     }
     if (h->d_lf_count) b += 4 * nl::kLinfitCounters;
-    b += (int64_t)h->ingest.bytes + (int64_t)h->ingest_async.bytes;
+    b += (int64_t)h->ingest.bytes + (int64_t)h->ingest_async.bytes + (int64_t)h->frame_scratch.bytes();
     return b;
 }
 

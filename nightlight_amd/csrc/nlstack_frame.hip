@@ -1,6 +1,6 @@
 // nlstack_frame.hip -- steps on one frame resident in a handle, and their host forms: statistics and noise,
-// median filters, OpCalibrate / OpBadPixel, star detection, the colour-camera front.  Kernels in frame_stats.hip,
-// preprocess.hip, stars.hip and bayer.hip.
+// median filters, OpCalibrate / OpBadPixel, star detection, background extraction, the colour-camera front.  Kernels
+// in frame_stats.hip, preprocess.hip, stars.hip, background.hip and bayer.hip.
 #include <math.h>
 
 #include <algorithm>
@@ -48,6 +48,32 @@ int median_filter_run(const char *who, const float *in_host, float *out_host, in
     return NL_OK;
 }
 
+// ---- what the entry points ask of the handle first (h is checked) ----
+
+// frame idx of the handle; without one nullptr, and "<who>: bad index <idx>" is the thread's error
+float *frame_or_fail(nl_stack_t *h, int idx, const char *who)
+{
+    if (idx < 0 || idx >= h->n_frames) {
+        fail(NL_ERR_INVALID_ARG, "%s: bad index %d", who, idx);
+        return nullptr;
+    }
+    return h->d_frames + (int64_t)idx * h->fstride;
+}
+
+// a step that looks beyond its own pixel (why) cannot run on a tile of rows
+int need_whole_image(const nl_stack_t *h, const char *who, const char *why)
+{
+    if (h->row0 == 0 && h->rows == h->height) return NL_OK;
+    return fail(NL_ERR_INVALID_ARG, "%s needs a whole-image handle (%s)", who, why);
+}
+
+// the kernels of these steps index pixels with 32 bits
+int need_int32_pixels(int64_t n, const char *who, const char *what = "frame")
+{
+    if (n < ((int64_t)1 << 31)) return NL_OK;
+    return fail(NL_ERR_INVALID_ARG, "%s: %s of 2^31 pixels or more", who, what);
+}
+
 }  // namespace
 
 extern "C" {
@@ -84,8 +110,8 @@ int nl_stack_frame_stats(nl_stack_t *h, int idx, float *mn, float *mean, float *
 {
     NL_CHECK_HANDLE(h);
     NL_SETTLE_UPLOADS(h);
-    if (idx < 0 || idx >= h->n_frames) return fail(NL_ERR_INVALID_ARG, "frame_stats: bad index %d", idx);
-    return frame_stats_impl(h, h->d_frames + (int64_t)idx * h->fstride, h->npix, mn, mean, mx, variance);
+    const float *d = frame_or_fail(h, idx, "frame_stats");
+    return d ? frame_stats_impl(h, d, h->npix, mn, mean, mx, variance) : NL_ERR_INVALID_ARG;
 }
 
 static int frame_noise_impl(nl_stack_t *h, const float *d, float *noise)
@@ -112,8 +138,8 @@ int nl_stack_frame_noise(nl_stack_t *h, int idx, float *noise)
     NL_SETTLE_UPLOADS(h);
     if (idx < 0 || idx >= h->n_frames || !noise)
         return fail(NL_ERR_INVALID_ARG, "frame_noise: bad index %d or null output", idx);
-    if (h->row0 != 0 || h->rows != h->height)
-        return fail(NL_ERR_INVALID_ARG, "frame_noise needs a whole-image handle (3x3 stencil)");
+    const int rc = need_whole_image(h, "frame_noise", "3x3 stencil");
+    if (rc != NL_OK) return rc;
     if (h->width < 3 || h->height < 3) return fail(NL_ERR_INVALID_ARG, "frame_noise: image too small");
     return frame_noise_impl(h, h->d_frames + (int64_t)idx * h->fstride, noise);
 }
@@ -136,8 +162,9 @@ int nl_stack_frame_affine(nl_stack_t *h, int idx, float multiplier, float offset
 {
     NL_CHECK_HANDLE(h);
     NL_SETTLE_UPLOADS(h);
-    if (idx < 0 || idx >= h->n_frames) return fail(NL_ERR_INVALID_ARG, "frame_affine: bad index %d", idx);
-    NL_HIP(nl::launch_affine(h->d_frames + (int64_t)idx * h->fstride, h->npix, multiplier, offset, h->stream));
+    float *d = frame_or_fail(h, idx, "frame_affine");
+    if (!d) return NL_ERR_INVALID_ARG;
+    NL_HIP(nl::launch_affine(d, h->npix, multiplier, offset, h->stream));
     NL_HIP(hipStreamSynchronize(h->stream));
     return NL_OK;
 }
@@ -283,7 +310,8 @@ int nl_stack_frame_badpixel(nl_stack_t *h, int idx, float sigma_low, float sigma
 {
     NL_CHECK_HANDLE(h);
     NL_SETTLE_UPLOADS(h);
-    if (idx < 0 || idx >= h->n_frames) return fail(NL_ERR_INVALID_ARG, "frame_badpixel: bad index %d", idx);
+    float *d = frame_or_fail(h, idx, "frame_badpixel");
+    if (!d) return NL_ERR_INVALID_ARG;
     if (sigma_low == 0.0f || sigma_high == 0.0f) {         // preprocess.go:181-183: nothing to do
         if (removed_out) *removed_out = 0;
         if (diff_stats_out) diff_stats_out[0] = diff_stats_out[1] = NAN;
@@ -291,28 +319,26 @@ int nl_stack_frame_badpixel(nl_stack_t *h, int idx, float sigma_low, float sigma
     }
     if (sigma_low < 0.0f || sigma_high < 0.0f)             // (the reference would flag the border: not supported)
         return fail(NL_ERR_INVALID_ARG, "frame_badpixel: negative sigma (low %g, high %g)", sigma_low, sigma_high);
-    if (h->row0 != 0 || h->rows != h->height)
-        return fail(NL_ERR_INVALID_ARG, "frame_badpixel needs a whole-image handle (3x3 stencil, whole-frame std)");
-    if (h->npix >= ((int64_t)1 << 31)) return fail(NL_ERR_INVALID_ARG, "frame_badpixel: frame of 2^31 pixels or more");
+    int rc = need_whole_image(h, "frame_badpixel", "3x3 stencil, whole-frame std");
+    if (rc == NL_OK) rc = need_int32_pixels(h->npix, "frame_badpixel");
+    if (rc != NL_OK) return rc;
     const int blocks = nl::bp_blocks(h->npix);
     nl_stack::FrameScratch &fs = h->frame_scratch;
-    if (!fs.d_bp_diff) NL_HIP(cached_malloc((void **)&fs.d_bp_diff, sizeof(float) * (size_t)h->npix, h->device));
-    if (!fs.d_bp_seg)
-        NL_HIP(cached_malloc((void **)&fs.d_bp_seg, sizeof(unsigned) * (size_t)blocks * nl::kBpChunk, h->device));
-    if (!fs.d_bp_list) NL_HIP(cached_malloc((void **)&fs.d_bp_list, sizeof(unsigned) * (size_t)h->npix, h->device));
-    if (!fs.d_bp_small) NL_HIP(dev_malloc(&fs.d_bp_small, sizeof(nl::BpParams) + 3 * sizeof(unsigned) * (size_t)blocks));
+    NL_HIP(fs.bp_diff.reserve(sizeof(float) * (size_t)h->npix, h->device));
+    NL_HIP(fs.bp_seg.reserve(sizeof(unsigned) * (size_t)blocks * nl::kBpChunk, h->device));
+    NL_HIP(fs.bp_list.reserve(sizeof(unsigned) * (size_t)h->npix, h->device));
+    NL_HIP(fs.bp_small.reserve(sizeof(nl::BpParams) + 3 * sizeof(unsigned) * (size_t)blocks, h->stream));
     nl::BpScratch s;
-    s.diff = fs.d_bp_diff;
-    s.seg = fs.d_bp_seg;
-    s.list = fs.d_bp_list;
-    s.params = reinterpret_cast<nl::BpParams *>(fs.d_bp_small);
-    s.count = fs.d_bp_small + sizeof(nl::BpParams) / sizeof(unsigned);
+    s.diff = static_cast<float *>(fs.bp_diff.ptr);
+    s.seg = static_cast<unsigned *>(fs.bp_seg.ptr);
+    s.list = static_cast<unsigned *>(fs.bp_list.ptr);
+    s.params = static_cast<nl::BpParams *>(fs.bp_small.ptr);
+    s.count = reinterpret_cast<unsigned *>(s.params + 1);
     s.offset = s.count + blocks;
     s.removed = s.offset + blocks;
     s.partial = h->d_stat_partial;
     s.stat_blocks = kStatBlocks;
-    NL_HIP(nl::launch_badpixel(h->d_frames + (int64_t)idx * h->fstride, h->width, h->height, sigma_low, sigma_high, s,
-                               h->stream));
+    NL_HIP(nl::launch_badpixel(d, h->width, h->height, sigma_low, sigma_high, s, h->stream));
     nl::BpParams p;
     NL_HIP(hipMemcpyAsync(&p, s.params, sizeof p, hipMemcpyDeviceToHost, h->stream));
     NL_HIP(hipStreamSynchronize(h->stream));
@@ -356,9 +382,9 @@ static int find_stars_impl(nl_stack_t *h, const float *d_data, const char *who, 
         return fail(NL_ERR_INVALID_ARG, "%s: radius %d not in [0, 1024]", who, radius);
     if (capacity < 0 || (capacity > 0 && !stars_out))
         return fail(NL_ERR_INVALID_ARG, "%s: capacity %d with %s output", who, capacity, stars_out ? "an" : "no");
-    if (h->row0 != 0 || h->rows != h->height)
-        return fail(NL_ERR_INVALID_ARG, "%s needs a whole-image handle (FindStars indexes the data 1-D)", who);
-    if (h->npix >= ((int64_t)1 << 31)) return fail(NL_ERR_INVALID_ARG, "%s: frame of 2^31 pixels or more", who);
+    int pre = need_whole_image(h, who, "FindStars indexes the data 1-D");
+    if (pre == NL_OK) pre = need_int32_pixels(h->npix, who);
+    if (pre != NL_OK) return pre;
     if (!h->d_stat_partial) NL_HIP(dev_malloc(&h->d_stat_partial, sizeof(double) * 3 * kStatBlocks));
     const nl::StarParams p{location, scale, star_sig, bp_sigma, star_in_out, radius, diff_std};
     std::vector<nl_star_t> stars;
@@ -381,10 +407,10 @@ int nl_stack_frame_find_stars(nl_stack_t *h, int idx, float location, float scal
 {
     NL_CHECK_HANDLE(h);
     NL_SETTLE_UPLOADS(h);
-    if (idx < 0 || idx >= h->n_frames) return fail(NL_ERR_INVALID_ARG, "frame_find_stars: bad index %d", idx);
-    return find_stars_impl(h, h->d_frames + (int64_t)idx * h->fstride, "frame_find_stars", location, scale, star_sig,
-                           bp_sigma, star_in_out, radius, diff_std, stars_out, capacity, n_stars, sum_of_shifts,
-                           avg_hfr);
+    const float *d = frame_or_fail(h, idx, "frame_find_stars");
+    if (!d) return NL_ERR_INVALID_ARG;
+    return find_stars_impl(h, d, "frame_find_stars", location, scale, star_sig, bp_sigma, star_in_out, radius, diff_std,
+                           stars_out, capacity, n_stars, sum_of_shifts, avg_hfr);
 }
 
 int nl_stack_result_find_stars(nl_stack_t *h, float location, float scale, float star_sig, float bp_sigma,
@@ -421,9 +447,9 @@ static int back_extract_impl(nl_stack_t *h, float *d_data, const char *who, int 
     if (n_stars < 0 || (n_stars > 0 && !stars)) return fail(NL_ERR_INVALID_ARG, "%s: %d stars", who, n_stars);
     if (cells_capacity < 0 || (cells_capacity > 0 && !cells_out))
         return fail(NL_ERR_INVALID_ARG, "%s: capacity %d with %s output", who, cells_capacity, cells_out ? "an" : "no");
-    if (h->row0 != 0 || h->rows != h->height)
-        return fail(NL_ERR_INVALID_ARG, "%s needs a whole-image handle (the grid spans the whole frame)", who);
-    if (h->npix >= ((int64_t)1 << 31)) return fail(NL_ERR_INVALID_ARG, "%s: frame of 2^31 pixels or more", who);
+    int pre = need_whole_image(h, who, "the grid spans the whole frame");
+    if (pre == NL_OK) pre = need_int32_pixels(h->npix, who);
+    if (pre != NL_OK) return pre;
     if (grid_size <= 0) {                  // OpBackExtract.Apply is a no-op (preprocess.go:373-375)
         if (info) memset(info, 0, sizeof *info);
         return NL_OK;
@@ -441,9 +467,10 @@ int nl_stack_frame_back_extract(nl_stack_t *h, int idx, int grid_size, float hfr
 {
     NL_CHECK_HANDLE(h);
     NL_SETTLE_UPLOADS(h);
-    if (idx < 0 || idx >= h->n_frames) return fail(NL_ERR_INVALID_ARG, "frame_back_extract: bad index %d", idx);
-    return back_extract_impl(h, h->d_frames + (int64_t)idx * h->fstride, "frame_back_extract", grid_size, hfr_factor,
-                             sigma, clip, stars, n_stars, background_out, cells_out, cells_capacity, info);
+    float *d = frame_or_fail(h, idx, "frame_back_extract");
+    if (!d) return NL_ERR_INVALID_ARG;
+    return back_extract_impl(h, d, "frame_back_extract", grid_size, hfr_factor, sigma, clip, stars, n_stars,
+                             background_out, cells_out, cells_capacity, info);
 }
 
 int nl_back_extract(float *data_host, int width, int height, int grid_size, float hfr_factor, float sigma, int clip,
@@ -520,8 +547,6 @@ int nl_debayer_shape(int width, int height, const char *channel, const char *cfa
     return cfa_parse(channel, cfa, width, height, &ch, &xo, &yo, out_width, out_height);
 }
 
-static size_t cfa_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
 int nl_stack_upload_frame_cfa(nl_stack_t *h, int idx, const float *raw_host, int raw_width, int raw_height,
                               const nl_calib_t *c, const char *channel, const char *cfa, float sigma_low,
                               float sigma_high, int64_t *removed_out, float *stats_out)
@@ -538,13 +563,12 @@ int nl_stack_upload_frame_cfa(nl_stack_t *h, int idx, const float *raw_host, int
                     "nl_stack_frame_calibrate, nl_stack_frame_badpixel)");
     int ch, xo, yo, out_w, out_h;
     if ((rc = cfa_parse(channel, cfa, raw_width, raw_height, &ch, &xo, &yo, &out_w, &out_h)) != NL_OK) return rc;
-    if (h->row0 != 0 || h->rows != h->height)
-        return fail(NL_ERR_INVALID_ARG, "upload_frame_cfa needs a whole-image handle (3x3 stencil, whole-frame std)");
+    if ((rc = need_whole_image(h, "upload_frame_cfa", "3x3 stencil, whole-frame std")) != NL_OK) return rc;
     if (h->width != out_w || h->height != out_h)
         return fail(NL_ERR_INVALID_ARG, "upload_frame_cfa: a %dx%d mosaic debayers to %dx%d, the handle is %dx%d",
                     raw_width, raw_height, out_w, out_h, h->width, h->height);
     const int64_t n = (int64_t)raw_width * raw_height;
-    if (n >= ((int64_t)1 << 31)) return fail(NL_ERR_INVALID_ARG, "upload_frame_cfa: mosaic of 2^31 pixels or more");
+    if ((rc = need_int32_pixels(n, "upload_frame_cfa", "mosaic")) != NL_OK) return rc;
     if (c) {
         if (c->device != h->device)
             return fail(NL_ERR_INVALID_ARG, "upload_frame_cfa: calibration on device %d, handle on device %d",
@@ -552,24 +576,24 @@ int nl_stack_upload_frame_cfa(nl_stack_t *h, int idx, const float *raw_host, int
         if ((rc = calib_check_light(c, idx, raw_width, raw_height)) != NL_OK) return rc;
     }
     const nl::BayerGeom g = nl::bayer_geom(raw_width, raw_height, ch, xo, yo);
-    const size_t compact = cfa_align(sizeof(float) * (size_t)g.rows * g.cstride);
-    const size_t o_delta = cfa_align(sizeof(float) * (size_t)n), o_median = o_delta + compact;
-    const size_t o_rowsum = o_median + compact, o_removed = o_rowsum + cfa_align(sizeof(float) * (size_t)g.rows);
-    const size_t o_params = o_removed + cfa_align(sizeof(unsigned) * (size_t)nl::bayer_replace_blocks(g));
-    const size_t bytes = o_params + sizeof(nl::BayerParams);
-    NL_HIP(h->frame_scratch.cfa.reserve(bytes, h->stream));
-    char *base = static_cast<char *>(h->frame_scratch.cfa.ptr);
-    float *raw = reinterpret_cast<float *>(base);
+    float *raw;
+    nl::BayerScratch s;
+    auto carve = [&](void *base) {
+        nl::Carver cv(base);
+        raw = cv.take<float>((size_t)n);
+        s.delta = cv.take<float>((size_t)g.rows * g.cstride);
+        s.median = cv.take<float>((size_t)g.rows * g.cstride);
+        s.rowsum = cv.take<float>((size_t)g.rows);
+        s.removed = cv.take<unsigned>((size_t)nl::bayer_replace_blocks(g));
+        s.params = cv.take<nl::BayerParams>(1);
+        return cv.bytes();
+    };
+    NL_HIP(h->frame_scratch.cfa.reserve(carve(nullptr), h->stream));
+    carve(h->frame_scratch.cfa.ptr);
     NL_HIP(hipMemcpyAsync(raw, raw_host, sizeof(float) * (size_t)n, hipMemcpyHostToDevice, h->stream));
     if (c)
         NL_HIP(nl::launch_calibrate(raw, raw, n, c->d_dark, c->d_flat, c->flat_max, h->stream));
     const bool correct = sigma_low != 0.0f && sigma_high != 0.0f;     // preprocess.go:181-183
-    nl::BayerScratch s;
-    s.delta = reinterpret_cast<float *>(base + o_delta);
-    s.median = reinterpret_cast<float *>(base + o_median);
-    s.rowsum = reinterpret_cast<float *>(base + o_rowsum);
-    s.removed = reinterpret_cast<unsigned *>(base + o_removed);
-    s.params = reinterpret_cast<nl::BayerParams *>(base + o_params);
     if (correct) NL_HIP(nl::launch_bayer_correct(raw, g, sigma_low, sigma_high, s, h->stream));
     NL_HIP(nl::launch_debayer(raw, raw_width, raw_height, ch, xo, yo, h->d_frames + (int64_t)idx * h->fstride,
                               h->width, h->stream));
@@ -616,14 +640,3 @@ int nl_preprocess_frame_cfa(const nl_calib_t *c, int frame_id, const float *in_h
 }
 
 }  // extern "C"
-
-void nl_stack::FrameScratch::release(int device, int64_t npix)
-{
-    cached_free(d_bp_diff, sizeof(float) * (size_t)npix, device);
-    cached_free(d_bp_seg, sizeof(unsigned) * (size_t)nl::bp_blocks(npix) * nl::kBpChunk, device);
-    cached_free(d_bp_list, sizeof(unsigned) * (size_t)npix, device);
-    if (d_bp_small) (void)hipFree(d_bp_small);
-    cfa.release();
-    star_work.free();
-    back_work.free();
-}

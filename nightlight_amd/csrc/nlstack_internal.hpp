@@ -1,5 +1,6 @@
 // nlstack_internal.hpp -- what the three units of the C ABI (nlstack_api.hip, nlstack_pass.hip, nlstack_frame.hip)
-// share: the handle, the error state, the device-memory helpers.  Private: no kernel source includes it, not installed.
+// share: the handle and the error state (the allocator and the scratch types: dev_memory.hpp).  Private: no kernel
+// source includes it, not installed.
 #pragma once
 
 #include <string.h>
@@ -8,6 +9,7 @@
 #include <vector>
 
 #include "background.hpp"
+#include "dev_memory.hpp"
 #include "stars.hpp"
 #include "stack_kernels.h"
 
@@ -19,22 +21,6 @@ int fail(int code, const char *fmt, ...);   // g_err = the formatted message; re
 // NL_ERR_NO_DEVICE unless HIP sees a device (*count: how many); select_device: that, a range check, hipSetDevice
 int require_device(int *count = nullptr);
 int select_device(int device);
-
-// EVERY device allocation of the library goes through dev_malloc (it hands parked blocks back when HIP runs out);
-// cached_malloc / cached_free park large blocks for the next handle of the same sizes (the caller has selected `device`)
-hipError_t dev_malloc(void **p, size_t bytes);
-template <class T>
-hipError_t dev_malloc(T **p, size_t bytes) { return dev_malloc(reinterpret_cast<void **>(p), bytes); }
-hipError_t cached_malloc(void **p, size_t bytes, int device);
-void cached_free(void *p, size_t bytes, int device);
-
-// device scratch grown on demand, never shrunk: the old buffer goes only once `stream`, its last user, is idle
-struct DevBuffer {
-    void *ptr = nullptr;
-    size_t bytes = 0;
-    hipError_t reserve(size_t want, hipStream_t stream);
-    void release() { if (ptr) (void)hipFree(ptr); ptr = nullptr; bytes = 0; }
-};
 
 // The host forms of the frame steps (nl_fits_decode, nl_find_stars, ...): a one-frame width x height handle of their
 // own per call carries stream and scratch, so concurrent calls share nothing.  run(h) runs on it; its error message
@@ -142,22 +128,34 @@ struct nl_stack {
     bool stage_used[kStageSlots] = {false, false, false, false};
     int stage_next = 0;
     bool uploads_pending = false;
-    // scratch of the steps on one resident frame (nlstack_frame.hip), lazily allocated; release() is defined there
+    // scratch of the steps on one resident frame (nlstack_frame.hip), lazily allocated
     struct FrameScratch {
-        // bad-pixel step (nl_stack_frame_badpixel): diff, per-workgroup lists, ordered list,
+        // bad-pixel step (nl_stack_frame_badpixel): diff, per-workgroup lists, ordered list (parked between handles);
         // nl::BpParams + per-workgroup list lengths, offsets, bad-pixel counts
-        float *d_bp_diff = nullptr;
-        unsigned *d_bp_seg = nullptr;
-        unsigned *d_bp_list = nullptr;
-        unsigned *d_bp_small = nullptr;
+        nl::ParkedBuffer bp_diff, bp_seg, bp_list;
+        nl::DevBuffer bp_small;
         // colour-camera front (nl_stack_upload_frame_cfa): the raw mosaic, the compact delta / median of one
         // channel, row sums, per-workgroup counts, nl::BayerParams
         nl::DevBuffer cfa;
-        // star detection (nl_stack_frame_find_stars / nl_stack_result_find_stars), grown
+        // star detection (nl_stack_frame_find_stars / nl_stack_result_find_stars)
         nl::StarWork star_work;
-        // background extraction (nl_stack_frame_back_extract), grown
+        // background extraction (nl_stack_frame_back_extract)
         nl::BackWork back_work;
-        void release(int device, int64_t npix);
+        size_t bytes() const
+        {
+            return bp_diff.bytes + bp_seg.bytes + bp_list.bytes + bp_small.bytes + cfa.bytes + star_work.bytes() +
+                   back_work.bytes();
+        }
+        void release(int device)
+        {
+            bp_diff.release(device);
+            bp_seg.release(device);
+            bp_list.release(device);
+            bp_small.release();
+            cfa.release();
+            star_work.release();
+            back_work.release();
+        }
     } frame_scratch;
     int max_grid = 0;
     int last_mode = -1;

@@ -20,6 +20,8 @@
 // unchained pixels are never neighbours, so their writes do not race.  The chained pixels are then walked in
 // rounds: a chained pixel's earlier neighbours lie in the row above (final once an earlier round wrote them) or to
 // its left in the same run of chained pixels, which one lane walks left to right.
+#include "frame_common.hpp"
+#include "launch_common.hpp"
 #include "median9.hpp"
 #include "preprocess.hpp"
 
@@ -30,25 +32,6 @@ namespace {
 constexpr int kBpThreads = 256;
 constexpr int kWalkThreads = 1024;
 constexpr int kScanThreads = 1024;
-
-__device__ __forceinline__ double bp_wave_sum(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-// one fp64 value per workgroup of kBpThreads (4 waves)
-__device__ __forceinline__ double bp_block_sum(double v)
-{
-    __shared__ double s[kBpThreads / 64];
-    v = bp_wave_sum(v);
-    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double t = 0.0;
-    for (int w = 0; w < kBpThreads / 64; w++) t += s[w];
-    return t;
-}
 
 __device__ __forceinline__ float calib_one(float x, float d, float f, float flat_max, bool dark, bool flat)
 {
@@ -107,7 +90,7 @@ __global__ __launch_bounds__(kBpThreads) void bp_diff_kernel(const float *data, 
             sum += (double)d;
         }
     }
-    sum = bp_block_sum(sum);
+    sum = block_sum<kBpThreads>(sum);
     if (threadIdx.x == 0) partial[blockIdx.x] = sum;
 }
 
@@ -117,7 +100,7 @@ __global__ __launch_bounds__(kBpThreads) void bp_mean_kernel(const double *parti
 {
     double s = 0.0;
     for (int b = threadIdx.x; b < blocks; b += kBpThreads) s += partial[b];
-    s = bp_block_sum(s);
+    s = block_sum<kBpThreads>(s);
     if (threadIdx.x == 0) {
         p->mean = (float)(s / (double)n);
     }
@@ -144,7 +127,7 @@ __global__ __launch_bounds__(kBpThreads) void bp_variance_kernel(const float *di
         const double d = (double)(diff[(quads << 2) + threadIdx.x] - mean);
         sum += d * d;
     }
-    sum = bp_block_sum(sum);
+    sum = block_sum<kBpThreads>(sum);
     if (threadIdx.x == 0) partial[blockIdx.x] = sum;
 }
 
@@ -154,7 +137,7 @@ __global__ __launch_bounds__(kBpThreads) void bp_threshold_kernel(const double *
 {
     double s = 0.0;
     for (int b = threadIdx.x; b < blocks; b += kBpThreads) s += partial[b];
-    s = bp_block_sum(s);
+    s = block_sum<kBpThreads>(s);
     if (threadIdx.x == 0) {
         const float std = (float)sqrt(s / (double)n);
         p->std = std;
@@ -265,7 +248,7 @@ __global__ __launch_bounds__(kScanThreads) void bp_scan_kernel(const unsigned *c
         carry += total;
         __syncthreads();
     }
-    for (int off = 32; off > 0; off >>= 1) removed += __shfl_xor(removed, off, 64);
+    removed = wave_sum(removed);
     if (lane == 0) atomicAdd(&s_removed, removed);        // (LDS, 16 waves)
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -329,18 +312,6 @@ __global__ __launch_bounds__(kWalkThreads) void bp_walk_kernel(float *data, int 
     }
 }
 
-template <bool DARK, bool FLAT>
-void launch_calibrate_t(bool vec, int64_t grid, const float *in, float *out, int64_t n, const float *dark,
-                        const float *flat, float flat_max, hipStream_t stream)
-{
-    if (vec)
-        hipLaunchKernelGGL((calibrate_kernel<DARK, FLAT, true>), dim3((unsigned)grid), dim3(256), 0, stream, in, out, n,
-                           dark, flat, flat_max);
-    else
-        hipLaunchKernelGGL((calibrate_kernel<DARK, FLAT, false>), dim3((unsigned)grid), dim3(256), 0, stream, in, out,
-                           n, dark, flat, flat_max);
-}
-
 }  // namespace
 
 hipError_t launch_calibrate(const float *in, float *out, int64_t n, const float *dark, const float *flat,
@@ -352,11 +323,16 @@ hipError_t launch_calibrate(const float *in, float *out, int64_t n, const float 
     int64_t grid = (items + 255) / 256;
     if (grid > 8192) grid = 8192;
     if (grid < 1) grid = 1;
-    if (dark && flat) launch_calibrate_t<true, true>(vec, grid, in, out, n, dark, flat, flat_max, stream);
-    else if (dark) launch_calibrate_t<true, false>(vec, grid, in, out, n, dark, flat, flat_max, stream);
-    else if (flat) launch_calibrate_t<false, true>(vec, grid, in, out, n, dark, flat, flat_max, stream);
-    else launch_calibrate_t<false, false>(vec, grid, in, out, n, dark, flat, flat_max, stream);
-    return hipGetLastError();
+    Launcher L(stream);
+    with_bool(dark != nullptr, [&](auto D) {
+        with_bool(flat != nullptr, [&](auto F) {
+            with_bool(vec, [&](auto V) {
+                L(calibrate_kernel<decltype(D)::value, decltype(F)::value, decltype(V)::value>, (unsigned)grid, 256, 0,
+                  in, out, n, dark, flat, flat_max);
+            });
+        });
+    });
+    return L.err;
 }
 
 int bp_blocks(int64_t n) { return (int)((n + kBpChunk - 1) / kBpChunk); }
@@ -366,20 +342,16 @@ hipError_t launch_badpixel(float *data, int width, int height, float sigma_low, 
 {
     const int64_t n = (int64_t)width * height;
     const int blocks = bp_blocks(n);
-    hipLaunchKernelGGL(bp_diff_kernel, dim3(s.stat_blocks), dim3(kBpThreads), 0, stream, data, s.diff, width, height,
-                       s.partial);
-    hipLaunchKernelGGL(bp_mean_kernel, dim3(1), dim3(kBpThreads), 0, stream, s.partial, s.stat_blocks, n, s.params);
-    hipLaunchKernelGGL(bp_variance_kernel, dim3(s.stat_blocks), dim3(kBpThreads), 0, stream, s.diff, n, s.params,
-                       s.partial);
-    hipLaunchKernelGGL(bp_threshold_kernel, dim3(1), dim3(kBpThreads), 0, stream, s.partial, s.stat_blocks, n,
-                       sigma_low, sigma_high, s.params);
-    hipLaunchKernelGGL(bp_classify_kernel, dim3(blocks), dim3(kBpThreads), 0, stream, data, s.diff, width, height,
-                       s.params, s.seg, s.count, s.removed);
-    hipLaunchKernelGGL(bp_scan_kernel, dim3(1), dim3(kScanThreads), 0, stream, s.count, s.removed, s.offset, blocks,
-                       s.params);
-    hipLaunchKernelGGL(bp_gather_kernel, dim3(blocks), dim3(kBpThreads), 0, stream, s.seg, s.count, s.offset, s.list);
-    hipLaunchKernelGGL(bp_walk_kernel, dim3(1), dim3(kWalkThreads), 0, stream, data, width, s.list, s.params);
-    return hipGetLastError();
+    Launcher L(stream);
+    L(bp_diff_kernel, s.stat_blocks, kBpThreads, 0, data, s.diff, width, height, s.partial);
+    L(bp_mean_kernel, 1, kBpThreads, 0, s.partial, s.stat_blocks, n, s.params);
+    L(bp_variance_kernel, s.stat_blocks, kBpThreads, 0, s.diff, n, s.params, s.partial);
+    L(bp_threshold_kernel, 1, kBpThreads, 0, s.partial, s.stat_blocks, n, sigma_low, sigma_high, s.params);
+    L(bp_classify_kernel, blocks, kBpThreads, 0, data, s.diff, width, height, s.params, s.seg, s.count, s.removed);
+    L(bp_scan_kernel, 1, kScanThreads, 0, s.count, s.removed, s.offset, blocks, s.params);
+    L(bp_gather_kernel, blocks, kBpThreads, 0, s.seg, s.count, s.offset, s.list);
+    L(bp_walk_kernel, 1, kWalkThreads, 0, data, width, s.list, s.params);
+    return L.err;
 }
 
 }  // namespace nl

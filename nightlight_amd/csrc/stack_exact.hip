@@ -486,9 +486,9 @@ hipError_t launch_reduce_counters(unsigned long long *partial, int n_blocks,
                                   unsigned long long *counters, hipStream_t stream, const unsigned *list_counts,
                                   bool zero_after)
 {
-    hipLaunchKernelGGL(reduce_counters_kernel, dim3(1), dim3(256), 0, stream, partial, n_blocks,
-                       counters, list_counts, 1, 0, zero_after ? 1 : 0);
-    return hipGetLastError();
+    Launcher L(stream);
+    L(reduce_counters_kernel, 1, 256, 0, partial, n_blocks, counters, list_counts, 1, 0, zero_after ? 1 : 0);
+    return L.err;
 }
 
 }  // namespace nl

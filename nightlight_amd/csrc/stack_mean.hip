@@ -144,16 +144,16 @@ __global__ __launch_bounds__(256) void scale_kernel(float *acc, float factor, in
 hipError_t launch_axpy(float *acc, const float *x, float weight, int first, int64_t n,
                        hipStream_t stream)
 {
-    hipLaunchKernelGGL(axpy_kernel, dim3(grid_for(n, 256, 256 * 32)), dim3(256), 0, stream, acc, x,
-                       weight, first, n);
-    return hipGetLastError();
+    Launcher L(stream);
+    L(axpy_kernel, grid_for(n, 256, 256 * 32), 256, 0, acc, x, weight, first, n);
+    return L.err;
 }
 
 hipError_t launch_scale(float *acc, float factor, int64_t n, hipStream_t stream)
 {
-    hipLaunchKernelGGL(scale_kernel, dim3(grid_for(n, 256, 256 * 32)), dim3(256), 0, stream, acc,
-                       factor, n);
-    return hipGetLastError();
+    Launcher L(stream);
+    L(scale_kernel, grid_for(n, 256, 256 * 32), 256, 0, acc, factor, n);
+    return L.err;
 }
 
 }  // namespace nl

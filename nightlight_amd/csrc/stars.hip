@@ -25,6 +25,8 @@
 
 #include <algorithm>
 
+#include "frame_common.hpp"
+#include "launch_common.hpp"
 #include "median9.hpp"
 #include "stars.hpp"
 
@@ -37,14 +39,6 @@ constexpr int kRejectThreads = 256;
 constexpr int kStarThreads = 64;
 constexpr int kStdThreads = 256;
 
-__host__ __device__ inline int32_t go_i32(float f)
-{
-    return (f >= -2147483648.0f && f < 2147483648.0f) ? (int32_t)f : INT32_MIN;
-}
-__host__ __device__ inline int32_t go_i32(double d)
-{
-    return (d > -2147483649.0 && d < 2147483648.0) ? (int32_t)d : INT32_MIN;
-}
 __host__ __device__ inline int32_t wrap_add(int32_t a, int32_t b) { return (int32_t)((uint32_t)a + (uint32_t)b); }
 __host__ __device__ inline int32_t wrap_mul(int32_t a, int32_t b) { return (int32_t)((uint32_t)a * (uint32_t)b); }
 
@@ -147,18 +141,6 @@ __device__ __forceinline__ float star_med(const float *d, int64_t i, int w)
 }
 __device__ __forceinline__ float star_med_diff(const float *d, int64_t i, int w) { return d[i] - star_med(d, i, w); }
 
-__device__ __forceinline__ double star_block_sum(double v)
-{
-    __shared__ double s[kStdThreads / 64];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double t = 0.0;
-    for (int w = 0; w < kStdThreads / 64; w++) t += s[w];
-    return t;
-}
-
 // Stats.Mean (stats.go:264-277): the fp64 sum of the differences over [lo, hi)
 __global__ __launch_bounds__(kStdThreads) void star_std_sum_kernel(const float *data, int width, int64_t lo, int64_t hi,
                                                                     double *partial)
@@ -166,7 +148,7 @@ __global__ __launch_bounds__(kStdThreads) void star_std_sum_kernel(const float *
     double s = 0.0;
     for (int64_t i = lo + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < hi; i += (int64_t)gridDim.x * blockDim.x)
         s += (double)star_med_diff(data, i, width);
-    s = star_block_sum(s);
+    s = block_sum<kStdThreads>(s);
     if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
@@ -180,7 +162,7 @@ __global__ __launch_bounds__(kStdThreads) void star_std_var_kernel(const float *
         const double d = (double)(star_med_diff(data, i, width) - mean);
         s += d * d;
     }
-    s = star_block_sum(s);
+    s = block_sum<kStdThreads>(s);
     if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
@@ -191,7 +173,7 @@ __global__ __launch_bounds__(kStdThreads) void star_std_final_kernel(const doubl
 {
     double s = 0.0;
     for (int b = threadIdx.x; b < blocks; b += kStdThreads) s += partial[b];
-    s = star_block_sum(s);
+    s = block_sum<kStdThreads>(s);
     if (threadIdx.x == 0) {
         if (step == 0) {
             params[0] = (float)(s / (double)m);
@@ -457,45 +439,11 @@ static bool filter_overlaps(std::vector<nl_star_t> &stars, int32_t width, int32_
     return true;
 }
 
-#define STAR_HIP(call)                                                                                  \
-    do {                                                                                                \
-        hipError_t e_ = (call);                                                                         \
-        if (e_ != hipSuccess) {                                                                         \
-            *msg = std::string(#call " failed: ") + hipGetErrorString(e_);                              \
-            return NL_ERR_HIP;                                                                          \
-        }                                                                                               \
-    } while (0)
-
-static size_t align_up(size_t b) { return (b + 255) & ~(size_t)255; }
-
-static hipError_t grow(void **p, size_t *have, size_t want, hipStream_t stream)
-{
-    if (want <= *have) return hipSuccess;
-    if (*p) {
-        hipError_t e = hipStreamSynchronize(stream);
-        if (e != hipSuccess) return e;
-        (void)hipFree(*p);
-        *p = nullptr;
-        *have = 0;
-    }
-    hipError_t e = hipMalloc(p, want);
-    if (e == hipSuccess) *have = want;
-    return e;
-}
-
 static const char *kPanicSort = "QPartitionStarsDesc (qsort.go:37-57) would index past the slice: a star's Mass is NaN";
 static const char *kPanicBins = "filterOutOverlaps (findstars.go:250-256) would index bins out of range: a star's "
                                 "centroid lies outside the bin grid (NaN position, or pulled past the last cell)";
 
 }  // namespace
-
-void StarWork::free()
-{
-    if (buf) (void)hipFree(buf);
-    if (stars) (void)hipFree(stars);
-    buf = stars = nullptr;
-    bytes = star_bytes = 0;
-}
 
 int find_stars_run(const float *d_data, int width, int height, const StarParams &p, StarWork &w, double *d_partial,
                    int stat_blocks, hipStream_t stream, std::vector<nl_star_t> &stars, float *sum_of_shifts,
@@ -505,28 +453,32 @@ int find_stars_run(const float *d_data, int width, int height, const StarParams 
     const int r = p.radius;
     const int cap = (int)(((int64_t)width + r) / ((int64_t)r + 1));       // ceil(width / (radius + 1)) >= 1
     const size_t maxc = (size_t)height * (size_t)cap;
-    const size_t o_list = align_up(sizeof(uint2) * maxc);
-    const size_t o_keep = o_list + align_up(sizeof(uint2) * maxc);
-    const size_t o_rowcnt = o_keep + align_up(maxc);
-    const size_t o_flags = o_rowcnt + align_up(sizeof(unsigned) * ((size_t)height + 1));
-    const size_t o_params = o_flags + 256;
-    STAR_HIP(grow(&w.buf, &w.bytes, o_params + 256, stream));
-    char *base = static_cast<char *>(w.buf);
-    uint2 *seg = reinterpret_cast<uint2 *>(base);
-    uint2 *list = reinterpret_cast<uint2 *>(base + o_list);
-    unsigned char *keep = reinterpret_cast<unsigned char *>(base + o_keep);
-    unsigned *rowcnt = reinterpret_cast<unsigned *>(base + o_rowcnt);
-    unsigned *flags = reinterpret_cast<unsigned *>(base + o_flags);
-    float *params = reinterpret_cast<float *>(base + o_params);
+    uint2 *seg, *list;
+    unsigned char *keep;
+    unsigned *rowcnt, *flags;
+    float *params;
+    auto carve = [&](void *base) {
+        Carver c(base);
+        seg = c.take<uint2>(maxc);
+        list = c.take<uint2>(maxc);
+        keep = c.take<unsigned char>(maxc);
+        rowcnt = c.take<unsigned>((size_t)height + 1);
+        flags = c.take<unsigned>(1);
+        params = c.take<float>(3);
+        return align_up(c.bytes());
+    };
+    NL_RUN_HIP(w.buf.reserve(carve(nullptr), stream));
+    carve(w.buf.ptr);
 
     // findBrightPixels (:105-131), threshold location + scale*starSig in fp32 (:61)
     const float thr = p.location + p.scale * p.star_sig;
-    STAR_HIP(hipMemsetAsync(flags, 0, sizeof(unsigned), stream));
+    NL_RUN_HIP(hipMemsetAsync(flags, 0, sizeof(unsigned), stream));
     const int rows_grid = (height + kScanThreads / 64 - 1) / (kScanThreads / 64);
-    star_scan_kernel<<<rows_grid, kScanThreads, 0, stream>>>(d_data, width, height, thr, r, cap, seg, rowcnt, flags);
-    star_offsets_kernel<<<1, 1024, 0, stream>>>(rowcnt, height);
-    star_compact_kernel<<<rows_grid, kScanThreads, 0, stream>>>(seg, rowcnt, height, cap, list);
-    STAR_HIP(hipGetLastError());
+    Launcher L(stream);
+    L(star_scan_kernel, rows_grid, kScanThreads, 0, d_data, width, height, thr, r, cap, seg, rowcnt, flags);
+    L(star_offsets_kernel, 1, 1024, 0, rowcnt, height);
+    L(star_compact_kernel, rows_grid, kScanThreads, 0, seg, rowcnt, height, cap, list);
+    NL_RUN_LAUNCHED(L);
 
     // rejectBadPixels (:134-168)
     const bool bp = p.bp_sigma > 0.0f;
@@ -538,23 +490,23 @@ int find_stars_run(const float *d_data, int width, int height, const StarParams 
             const int64_t lo = (int64_t)width + 1, hi = std::max(lo, n - width - 1), m = hi - lo;
             const int64_t want = (m + kStdThreads - 1) / kStdThreads;
             const int g = (int)std::max<int64_t>(1, std::min<int64_t>(want, stat_blocks));
-            star_std_sum_kernel<<<g, kStdThreads, 0, stream>>>(d_data, width, lo, hi, d_partial);
-            star_std_final_kernel<<<1, kStdThreads, 0, stream>>>(d_partial, g, m, p.bp_sigma, 0, params);
-            star_std_var_kernel<<<g, kStdThreads, 0, stream>>>(d_data, width, lo, hi, params, d_partial);
-            star_std_final_kernel<<<1, kStdThreads, 0, stream>>>(d_partial, g, m, p.bp_sigma, 1, params);
+            L(star_std_sum_kernel, g, kStdThreads, 0, d_data, width, lo, hi, d_partial);
+            L(star_std_final_kernel, 1, kStdThreads, 0, d_partial, g, m, p.bp_sigma, 0, params);
+            L(star_std_var_kernel, g, kStdThreads, 0, d_data, width, lo, hi, params, d_partial);
+            L(star_std_final_kernel, 1, kStdThreads, 0, d_partial, g, m, p.bp_sigma, 1, params);
             tp = params;
         } else {
             t_given = p.diff_std * p.bp_sigma;
         }
         const int g = (int)std::min<size_t>((maxc + kRejectThreads - 1) / kRejectThreads, 4096);
-        star_reject_kernel<<<g, kRejectThreads, 0, stream>>>(d_data, width, n, list, total, tp, t_given, keep);
-        star_reject_edge_kernel<<<1, 64, 0, stream>>>(d_data, width, n, list, total, tp, t_given, keep);
-        STAR_HIP(hipGetLastError());
+        L(star_reject_kernel, g, kRejectThreads, 0, d_data, width, n, list, total, tp, t_given, keep);
+        L(star_reject_edge_kernel, 1, 64, 0, d_data, width, n, list, total, tp, t_given, keep);
+        NL_RUN_LAUNCHED(L);
     }
     unsigned head[2] = {0, 0};
-    STAR_HIP(hipMemcpyAsync(&head[0], total, sizeof(unsigned), hipMemcpyDeviceToHost, stream));
-    STAR_HIP(hipMemcpyAsync(&head[1], flags, sizeof(unsigned), hipMemcpyDeviceToHost, stream));
-    STAR_HIP(hipStreamSynchronize(stream));
+    NL_RUN_HIP(hipMemcpyAsync(&head[0], total, sizeof(unsigned), hipMemcpyDeviceToHost, stream));
+    NL_RUN_HIP(hipMemcpyAsync(&head[1], flags, sizeof(unsigned), hipMemcpyDeviceToHost, stream));
+    NL_RUN_HIP(hipStreamSynchronize(stream));
     if (head[1] & 1u) {
         *msg = "find_stars: the frame holds +-Inf (not supported)";
         return NL_ERR_INVALID_ARG;
@@ -563,9 +515,9 @@ int find_stars_run(const float *d_data, int width, int height, const StarParams 
     std::vector<uint2> cand(cnt);
     std::vector<unsigned char> kept(bp ? cnt : 0);
     if (cnt) {
-        STAR_HIP(hipMemcpyAsync(cand.data(), list, sizeof(uint2) * cnt, hipMemcpyDeviceToHost, stream));
-        if (bp) STAR_HIP(hipMemcpyAsync(kept.data(), keep, cnt, hipMemcpyDeviceToHost, stream));
-        STAR_HIP(hipStreamSynchronize(stream));
+        NL_RUN_HIP(hipMemcpyAsync(cand.data(), list, sizeof(uint2) * cnt, hipMemcpyDeviceToHost, stream));
+        if (bp) NL_RUN_HIP(hipMemcpyAsync(kept.data(), keep, cnt, hipMemcpyDeviceToHost, stream));
+        NL_RUN_HIP(hipStreamSynchronize(stream));
     }
     stars.clear();
     stars.reserve(cnt);
@@ -584,22 +536,29 @@ int find_stars_run(const float *d_data, int width, int height, const StarParams 
 
     // shiftToCenterOfMass (:79), threshold location + scale*starSig*0.5
     const int m1 = (int)stars.size();
-    const size_t o_out = align_up(sizeof(DevStar) * (size_t)m1), o_shift = 2 * o_out;
-    STAR_HIP(grow(&w.stars, &w.star_bytes, o_shift + align_up(sizeof(float) * (size_t)m1) + 256, stream));
-    DevStar *d_in = static_cast<DevStar *>(w.stars);
-    DevStar *d_out = reinterpret_cast<DevStar *>(static_cast<char *>(w.stars) + o_out);
-    float *d_shift = reinterpret_cast<float *>(static_cast<char *>(w.stars) + o_shift);
+    DevStar *d_in, *d_out;
+    float *d_shift;
+    auto carve_stars = [&](void *base) {
+        Carver c(base);
+        d_in = c.take<DevStar>((size_t)m1);
+        d_out = c.take<DevStar>((size_t)m1);
+        d_shift = c.take<float>((size_t)m1);
+        c.take<char>(1);                  // (no star: still an allocation)
+        return align_up(c.bytes());
+    };
+    NL_RUN_HIP(w.stars.reserve(carve_stars(nullptr), stream));
+    carve_stars(w.stars.ptr);
     float sum = 0.0f;
     if (m1) {
         const float thr2 = p.location + p.scale * p.star_sig * 0.5f;
-        STAR_HIP(hipMemcpyAsync(d_in, stars.data(), sizeof(DevStar) * (size_t)m1, hipMemcpyHostToDevice, stream));
-        star_centroid_kernel<<<(m1 + kStarThreads - 1) / kStarThreads, kStarThreads, 0, stream>>>(
-            d_data, width, n, thr2, r, d_in, m1, d_out, d_shift);
-        STAR_HIP(hipGetLastError());
+        NL_RUN_HIP(hipMemcpyAsync(d_in, stars.data(), sizeof(DevStar) * (size_t)m1, hipMemcpyHostToDevice, stream));
+        L(star_centroid_kernel, (m1 + kStarThreads - 1) / kStarThreads, kStarThreads, 0, d_data, width, n, thr2, r, d_in,
+          m1, d_out, d_shift);
+        NL_RUN_LAUNCHED(L);
         std::vector<float> shift((size_t)m1);
-        STAR_HIP(hipMemcpyAsync(stars.data(), d_out, sizeof(DevStar) * (size_t)m1, hipMemcpyDeviceToHost, stream));
-        STAR_HIP(hipMemcpyAsync(shift.data(), d_shift, sizeof(float) * (size_t)m1, hipMemcpyDeviceToHost, stream));
-        STAR_HIP(hipStreamSynchronize(stream));
+        NL_RUN_HIP(hipMemcpyAsync(stars.data(), d_out, sizeof(DevStar) * (size_t)m1, hipMemcpyDeviceToHost, stream));
+        NL_RUN_HIP(hipMemcpyAsync(shift.data(), d_shift, sizeof(float) * (size_t)m1, hipMemcpyDeviceToHost, stream));
+        NL_RUN_HIP(hipStreamSynchronize(stream));
         for (int i = 0; i < m1; i++) sum += shift[(size_t)i];      // sumOfShifts, in list order (:322)
     }
 
@@ -616,14 +575,14 @@ int find_stars_run(const float *d_data, int width, int height, const StarParams 
         const float re = rf + 1e-8f;
         const int lim = go_i32(ceil((double)re * (double)re));
         unsigned char *d_keep = reinterpret_cast<unsigned char *>(d_out);
-        STAR_HIP(hipMemcpyAsync(d_in, stars.data(), sizeof(DevStar) * (size_t)m2, hipMemcpyHostToDevice, stream));
-        star_hfr_kernel<<<(m2 + kStarThreads - 1) / kStarThreads, kStarThreads, 0, stream>>>(
-            d_data, width, n, rf, rad, lim, p.location, p.star_in_out, d_in, m2, d_keep);
-        STAR_HIP(hipGetLastError());
+        NL_RUN_HIP(hipMemcpyAsync(d_in, stars.data(), sizeof(DevStar) * (size_t)m2, hipMemcpyHostToDevice, stream));
+        L(star_hfr_kernel, (m2 + kStarThreads - 1) / kStarThreads, kStarThreads, 0, d_data, width, n, rf, rad, lim,
+          p.location, p.star_in_out, d_in, m2, d_keep);
+        NL_RUN_LAUNCHED(L);
         std::vector<unsigned char> hk((size_t)m2);
-        STAR_HIP(hipMemcpyAsync(stars.data(), d_in, sizeof(DevStar) * (size_t)m2, hipMemcpyDeviceToHost, stream));
-        STAR_HIP(hipMemcpyAsync(hk.data(), d_keep, (size_t)m2, hipMemcpyDeviceToHost, stream));
-        STAR_HIP(hipStreamSynchronize(stream));
+        NL_RUN_HIP(hipMemcpyAsync(stars.data(), d_in, sizeof(DevStar) * (size_t)m2, hipMemcpyDeviceToHost, stream));
+        NL_RUN_HIP(hipMemcpyAsync(hk.data(), d_keep, (size_t)m2, hipMemcpyDeviceToHost, stream));
+        NL_RUN_HIP(hipStreamSynchronize(stream));
         for (int i = 0; i < m2; i++) {
             if (!hk[(size_t)i]) continue;
             stars[nk++] = stars[(size_t)i];

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/nlstack.h"
+#include "dev_memory.hpp"
 
 namespace nl {
 
@@ -17,13 +18,12 @@ struct StarParams {
     float diff_std;                  // f.MedianDiffStats.StdDev(); NaN: MedianDiffStats == nil
 };
 
-// per-handle device scratch, grown on demand, released by free()
+// per-handle device scratch, grown on demand
 struct StarWork {
-    void *buf = nullptr;             // candidate segments, list, flags, thresholds
-    size_t bytes = 0;
-    void *stars = nullptr;           // star lists of the centroid and HFR stages
-    size_t star_bytes = 0;
-    void free();
+    DevBuffer buf;                   // candidate segments, list, flags, thresholds
+    DevBuffer stars;                 // star lists of the centroid and HFR stages
+    size_t bytes() const { return buf.bytes + stars.bytes; }
+    void release() { buf.release(); stars.release(); }
 };
 
 // FindStars on one whole width x height frame resident at d_data (width * height < 2^31), on `stream`.  d_partial:

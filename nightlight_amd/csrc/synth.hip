@@ -2,7 +2,7 @@
 // (SURVEY.md section 8d), so that 8-32 GiB benchmark inputs never cross PCIe.
 // Counter-based RNG keyed by (seed, frame, pixel-of-the-full-image): a row tile
 // holds exactly the rows of the whole image's stack, whatever the sharding.
-#include "stack_kernels.h"
+#include "launch_common.hpp"
 
 namespace nl {
 
@@ -65,9 +65,9 @@ hipError_t launch_fill_synthetic(float *frames, int64_t stride, int n_frames, in
                                  int height, int row0, int rows, uint64_t seed,
                                  hipStream_t stream)
 {
-    hipLaunchKernelGGL(fill_synthetic_kernel, dim3(256 * 16), dim3(256), 0, stream, frames, stride,
-                       n_frames, width, height, row0, rows, seed);
-    return hipGetLastError();
+    Launcher L(stream);
+    L(fill_synthetic_kernel, 256 * 16, 256, 0, frames, stride, n_frames, width, height, row0, rows, seed);
+    return L.err;
 }
 
 }  // namespace nl

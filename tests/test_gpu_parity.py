@@ -760,6 +760,33 @@ def test_device_bytes_reports_the_lazily_allocated_scratch(nl):
         assert st.device_bytes >= b0 + 65 * w * h
 
 
+def test_device_bytes_reports_the_scratch_of_the_frame_operators(nl):
+    # nl_stack_device_bytes counts what the steps on one resident frame allocate on first use and keep until destroy.
+    # The bounds are buffer sizes of the code: the bad-pixel step holds diff (4 B / pixel), the per-workgroup list
+    # segments (4 B / pixel, rounded up to whole workgroups) and the ordered list (4 B / pixel); background
+    # extraction with a rendered background holds that image (4 B / pixel)
+    w, h = 256, 128
+    frame = (1000.0 + np.random.default_rng(11).normal(0.0, 20.0, w * h)).astype(np.float32)
+    with nl.StackHandle(1, w, h) as st:
+        st.upload_frame(0, frame)
+        b0 = st.device_bytes
+        st.frame_badpixel(0, 3.0, 5.0)
+        b1 = st.device_bytes
+        assert b1 >= b0 + 3 * 4 * w * h
+        st.frame_badpixel(0, 3.0, 5.0)
+        assert st.device_bytes == b1
+        stars, _, _ = st.frame_find_stars(0, 1000.0, 20.0)
+        b2 = st.device_bytes
+        assert b2 > b1
+        st.frame_find_stars(0, 1000.0, 20.0)
+        assert st.device_bytes == b2
+        st.frame_back_extract(0, stars, 32, render=True)
+        b3 = st.device_bytes
+        assert b3 >= b2 + 4 * w * h
+        st.frame_back_extract(0, stars, 32, render=True)
+        assert st.device_bytes == b3
+
+
 def test_destroyed_handles_park_their_buffers_for_the_next_one(nl, oracle):
     # nl_stack_destroy parks the large buffers, the next handle of the same geometry takes them over (stale contents:
     # every pass must overwrite what it reads back); nl_release_cached_memory hands them back to HIP
