@@ -57,6 +57,16 @@ constexpr int kOrderRing = 8;              // events nl_stack_order_stream_after
 // the previous pass's dominant kernel -- two sets alternate): clip accumulators + list lengths + snapshot
 constexpr size_t kScratchBytes = sizeof(unsigned long long) * nl::kScratchWords;
 
+// what a pass leaves behind: filled in by its engine, kept on the handle as `last`
+struct PassFacts {
+    bool has_counters = false;    // d_counters holds the pass's clip counters
+    bool used_fast = false;       // a dominant kernel handed pixels over: the list lengths belong to this pass
+    bool lists = false;           // ... and sit behind the totals (d_counters[2])
+    bool fused = false;           // fused protocol: this pass's scratch set used, the other one zeroed
+    bool tail_fused = false;      // generic pass + first replay ran as one launch (stack_tail_fused.hip)
+    bool zeroed_behind = false;   // the reduction kernel left the scratch set zeroed
+};
+
 struct nl_stack {
     int device = 0;
     int n_frames = 0, width = 0, height = 0, row0 = 0, rows = 0;
@@ -98,16 +108,13 @@ struct nl_stack {
     unsigned fb_hint = 0;                      // exact-list length of the last finished fast pass + 1 (0 = unknown)
     unsigned gen_hint = 0;                     // same for the generic list
     bool last_weighted = false;                // the last pass ran with weights (key of the hints it leaves)
-    bool last_fused = false;
-    bool last_tail_fused = false;              // generic pass + first replay ran as one launch (stack_tail_fused.hip)
-    bool last_lists = false;                   // the last pass left its list lengths behind the totals (d_counters[2])
+    PassFacts last;                            // what the last pass left behind (all false after a failed one)
     unsigned dev_flags = 0;                    // nl_stack_set_dev_flags (A/B measurements)
     unsigned *d_fb_list = nullptr;             // [npix] pixels the fast kernel handed to the exact kernel
     unsigned *d_fb_count = nullptr;            // [2]: exact-list length, generic-list length (inside d_partial)
     unsigned *d_gen_list = nullptr;            // [npix] pixels zonal waves handed to the generic pass
     bool force_exact = false;
     int exact_flavour = 0;            // nl_stack_set_exact argument: 1 = LDS column kernel, 2 = wave-per-pixel replay
-    bool last_used_fast = false;
     unsigned long long *d_counters = nullptr;  // [4]: where a pass leaves {clip_low, clip_high, list lengths, -}: the handle's own buffer or the caller's (nl_stack_set_counters_buffer)
     unsigned long long *d_counters_own = nullptr;
     double *d_stat_partial = nullptr;          // [kStatBlocks*3]
@@ -159,7 +166,6 @@ struct nl_stack {
     } frame_scratch;
     int max_grid = 0;
     int last_mode = -1;
-    bool last_has_counters = false;
     bool pending = false;
     const char *last_kernel = "";
 };

@@ -2,6 +2,7 @@
 // run_async_impl sets a pass up, select_engine picks the engine that runs it; all pixel arithmetic runs in the kernels.
 #include <mutex>
 
+#include "launch_common.hpp"
 #include "nlstack_internal.hpp"
 
 namespace {
@@ -190,26 +191,6 @@ struct PassSetup {
     nl::StackArgs a;
 };
 
-// what a pass leaves behind, written into the handle's last_* fields by every pass (and reset by a failed one)
-struct PassFacts {
-    bool has_counters = false;    // d_counters holds the pass's clip counters
-    bool used_fast = false;       // a dominant kernel handed pixels over: the list lengths belong to this pass
-    bool lists = false;           // ... and sit behind the totals (d_counters[2])
-    bool fused = false;           // fused protocol: this pass's scratch set used, the other one zeroed
-    bool tail_fused = false;      // generic pass + first replay ran as one launch (stack_tail_fused.hip)
-    bool zeroed_behind = false;   // the reduction kernel left the scratch set zeroed
-};
-
-static void set_last_pass(nl_stack *h, const PassFacts &f)
-{
-    h->last_has_counters = f.has_counters;
-    h->last_used_fast = f.used_fast;
-    h->last_lists = f.lists;
-    h->last_fused = f.fused;
-    h->last_tail_fused = f.tail_fused;
-    h->sets_clean = f.fused;
-}
-
 // Pure: allocates nothing, enqueues nothing.  The first engine whose condition holds runs the pass.
 static Engine select_engine(const nl_stack *h, int mode, bool weighted, const nl::StackArgs &a)
 {
@@ -358,6 +339,34 @@ static int run_listed(nl_stack *h, const PassSetup &p, PassFacts *facts)
     return NL_OK;
 }
 
+// A winsorization cascade plan (kWinsorPlan*, NL_WCAS), the dominant kernel first, the last stage runs to the end:
+//   plan  := stage { "," stage }          at most nl::kCascadeStages stages
+//   stage := passes ":" cap [ ":" group ]  clipping passes per wave, winsorization rounds per pass, regions of the previous
+//                                          stage's list per workgroup (1 ... 16, default 4)
+// Parsing stops at the first thing that is not a stage; the stages before it stand.
+struct CascadePlan { int stages; int pass[nl::kCascadeStages], cap[nl::kCascadeStages], group[nl::kCascadeStages]; };
+static CascadePlan parse_cascade_plan(const char *p)
+{
+    CascadePlan pl{};
+    while (*p && pl.stages < nl::kCascadeStages) {
+        char *end = nullptr;
+        const long a1 = strtol(p, &end, 10);
+        if (end == p || *end != ':') break;
+        p = end + 1;
+        const long a2 = strtol(p, &end, 10);
+        if (end == p) break;
+        long a3 = 4;
+        if (*end == ':') { p = end + 1; a3 = strtol(p, &end, 10); if (end == p) break; }
+        pl.pass[pl.stages] = (int)a1;
+        pl.cap[pl.stages] = (int)a2;
+        pl.group[pl.stages] = a3 < 1 ? 1 : (a3 > 16 ? 16 : (int)a3);
+        pl.stages++;
+        if (*end != ',') break;
+        p = end + 1;
+    }
+    return pl;
+}
+
 // Winsorized fast passes: how the generic pass and the winsorization loops are budgeted.  true: the winsorization cascade runs.
 static bool winsor_setup(nl_stack *h, int n_frames, nl::FastArgs &f)
 {
@@ -379,33 +388,11 @@ static bool winsor_setup(nl_stack *h, int n_frames, nl::FastArgs &f)
     // use at the same time); their lengths in the scratch set.  NL_WCAS="b1,b2" sets the budgets, "0" turns it off;
     // developer switch kDevNoWinsorCascade: off (A/B inside one process)
     if (n_frames > 128 || n_frames < 12 || (h->dev_flags & kDevNoWinsorCascade)) return false;
-    // plan: "passes:cap[:group]" per stage, comma-separated, the dominant kernel first; the last stage runs to the end
-    struct Plan { int stages; int pass[nl::kCascadeStages], cap[nl::kCascadeStages], group[nl::kCascadeStages]; };
-    auto parse = [](const char *e, Plan *pl) {
-        pl->stages = 0;
-        const char *p = e;
-        while (*p && pl->stages < nl::kCascadeStages) {
-            char *end = nullptr;
-            const long a1 = strtol(p, &end, 10);
-            if (end == p || *end != ':') break;
-            p = end + 1;
-            const long a2 = strtol(p, &end, 10);
-            if (end == p) break;
-            long a3 = 4;
-            if (*end == ':') { p = end + 1; a3 = strtol(p, &end, 10); if (end == p) break; }
-            pl->pass[pl->stages] = (int)a1;
-            pl->cap[pl->stages] = (int)a2;
-            pl->group[pl->stages] = a3 < 1 ? 1 : (a3 > 16 ? 16 : (int)a3);
-            pl->stages++;
-            if (*end != ',') break;
-            p = end + 1;
-        }
-    };
-    static const Plan env_plan = [&] { Plan p0{}; const char *e = getenv("NL_WCAS"); if (e) parse(e, &p0); return p0; }();
+    static const CascadePlan env_plan = [] { const char *e = getenv("NL_WCAS"); return e ? parse_cascade_plan(e) : CascadePlan{}; }();
     static const bool env_off = [] { const char *e = getenv("NL_WCAS"); return e && e[0] == '0' && e[1] == 0; }();
-    Plan pl{};
+    CascadePlan pl{};
     if (env_plan.stages >= 2) pl = env_plan;
-    else if (n_frames <= kWinsorCascadeMaxFrames) parse(n_frames <= 40 ? kWinsorPlanShallow : kWinsorPlanDeep, &pl);
+    else if (n_frames <= kWinsorCascadeMaxFrames) pl = parse_cascade_plan(n_frames <= 40 ? kWinsorPlanShallow : kWinsorPlanDeep);
     nl::LinfitCascade cb;
     // (a list holds at most one entry per pixel of the tile, rounded up to whole workgroups: list and states of a
     // stage share one of the cascade's state arrays, 4 words per pixel; the region lengths take its pixel lists)
@@ -421,6 +408,22 @@ static bool winsor_setup(nl_stack *h, int n_frames, nl::FastArgs &f)
     return true;
 }
 
+// The first replay of a pass (list part 0) beside the generic part: on the side stream behind the fork event, with ev_join
+// for the pass to wait on.  The fork event is ev_dom1, recorded behind the dominant kernel, unless the pass is untimed or
+// cascade stages have filled the lists since: then ev_fork, recorded here.  kDevReplayInFront: on the pass's own stream.
+static int fork_first_replay(nl_stack *h, int mode, const nl::StackArgs &first, int grid, bool cascade)
+{
+    const char *ignored = "";
+    const bool own = (h->dev_flags & kDevUntimed) || cascade;
+    if (own) NL_HIP(hipEventRecord(h->ev_fork, h->stream));
+    const bool in_front = (h->dev_flags & kDevReplayInFront) != 0;
+    const hipStream_t s = in_front ? h->stream : h->side_stream;
+    if (!in_front) NL_HIP(hipStreamWaitEvent(h->side_stream, own ? h->ev_fork : h->ev_dom1, 0));
+    NL_HIP(nl::launch_stack_sigma_coop(mode, first, grid, s, &ignored));
+    NL_HIP(hipEventRecord(h->ev_join, s));
+    return NL_OK;
+}
+
 // Sigma / winsorized clipping: a register-resident (up to 128 frames) or LDS-column (129 ... 512) dominant kernel, a generic
 // pass over the pixels it hands over, and the bit-exact replay of the pixels either cannot decide: one wave per pixel where
 // available.  The hand-overs of the dominant kernel are replayed on the side stream WHILE the generic pass runs (both only
@@ -428,49 +431,34 @@ static bool winsor_setup(nl_stack *h, int n_frames, nl::FastArgs &f)
 static int run_sigma_fast(nl_stack *h, const PassSetup &p, PassFacts *facts)
 {
     const int mode = p.mode;
+    const bool winsor = mode == NL_ST_WINSOR_SIGMA;
     nl::StackArgs a = p.a;
     // winsorized passes: the fast kernels put the thresholds of every round they decide on record, so that the
     // replay of a pixel that turns undecidable later skips the winsorization loops of the decided rounds
     // (from 129 frames on: C3 tile 5.28 -> 5.14 ms; at 128 frames most undecidable pixels are undecidable in
     // their first round and the stores cost the dominant kernel 0.6 %)
-    if (mode == NL_ST_WINSOR_SIGMA && a.n_frames > 128 && fused_protocol_on() && ensure_bounds(h)) {
+    if (winsor && a.n_frames > 128 && fused_protocol_on() && ensure_bounds(h)) {
         a.bounds = h->d_bounds;
         a.nrounds = h->d_nrounds;
     }
+    // the wave-per-pixel replays of the exact list: the first of them to start stores 1 + the list's length in `snap`
+    // (StackArgs::list_snap); part 0 is the list as the dominant part left it, part 1 the generic pass's additions
+    unsigned *const snap = h->d_fb_count + 2;
     nl::FastArgs f = list_args(h, true, true);
-    f.fb_snap = h->d_fb_count + 2;                   // see the replay below
+    f.fb_snap = snap;
     f.gen_hint = h->gen_hint;
-    const bool cascade = mode == NL_ST_WINSOR_SIGMA && winsor_setup(h, a.n_frames, f);
-    nl::StackArgs e = a;
-    e.list = h->d_fb_list;
-    e.list_count = h->d_fb_count;
-    e.list_capacity = (unsigned)h->npix;
+    const bool cascade = winsor && winsor_setup(h, a.n_frames, f);
     const bool coop = nl::coop_supported(mode, p.weighted, a.n_frames) != 0;
-    unsigned *snap = h->d_fb_count + 2;               // 1 + list length when the first replay started (set on the device)
+    nl::StackArgs first = a;
+    first.list = h->d_fb_list;
+    first.list_count = h->d_fb_count;
+    first.list_capacity = (unsigned)h->npix;
+    first.list_snap = snap;
+    first.list_part = 0;
+    nl::StackArgs second = first;
+    second.list_part = 1;
     int grid0 = 0, grid1 = 0;
     replay_grids(h, &grid0, &grid1);
-    struct Fork { nl_stack *h; nl::StackArgs e; int mode; unsigned *snap; int grid0; bool cascade; hipError_t err; } fork{h, e, mode, snap, grid0, cascade, hipSuccess};
-    nl::AfterDominant after = nullptr;
-    if (coop) after = [](void *u) {
-        Fork *k = static_cast<Fork *>(u);
-        nl_stack *hh = k->h;
-        const char *ignored = "";
-        // (ev_dom1: recorded behind the dominant kernel.  With a winsorization cascade two more kernels have filled the
-        // lists since: an event of its own)
-        const bool own = (hh->dev_flags & kDevUntimed) || k->cascade;
-        hipEvent_t fork_ev = own ? hh->ev_fork : hh->ev_dom1;
-        hipError_t err = own ? hipEventRecord(hh->ev_fork, hh->stream) : hipSuccess;
-        // (kDevReplayInFront: the first replay in front of the generic pass, same stream)
-        const bool in_front = (hh->dev_flags & kDevReplayInFront) != 0;
-        const hipStream_t s = in_front ? hh->stream : hh->side_stream;
-        if (!in_front && err == hipSuccess) err = hipStreamWaitEvent(hh->side_stream, fork_ev, 0);
-        nl::StackArgs first = k->e;
-        first.list_snap = k->snap;                    // the list as the dominant kernel left it (snapshot on the device)
-        first.list_part = 0;
-        if (err == hipSuccess) err = nl::launch_stack_sigma_coop(k->mode, first, k->grid0, s, &ignored);
-        if (err == hipSuccess) err = hipEventRecord(hh->ev_join, s);
-        k->err = err;
-    };
     // Short exact lists (plain sigma, 65 ... 128 frames, fused protocol): generic pass and first replay as the lower and the
     // upper workgroups of ONE launch (stack_tail_fused.hip) instead of two streams -- no fork, no join: the join alone costs
     // a 512-row tile 14 us of its 257.  Every workgroup of that launch claims the generic pass's 48 KiB of LDS (three per
@@ -480,25 +468,22 @@ static int run_sigma_fast(nl_stack *h, const PassSetup &p, PassFacts *facts)
     const bool tail_fused = tail_fused_on && !(h->dev_flags & (kDevTwoStreamTail | kDevReplayInFront)) && p.fused && coop && !cascade &&
                             nl::tail_fused_supported(mode, p.weighted, a.n_frames) != 0 && h->fb_hint != 0 &&
                             h->fb_hint - 1u <= kTailFusedMaxList;
-    nl::StackArgs first_replay = e;
-    first_replay.list_snap = snap;                    // the list as the dominant kernel left it (snapshot on the device)
-    first_replay.list_part = 0;
     unsigned replay_blocks = h->fb_hint + 31u;        // one wave per listed pixel and some: the list's length is last pass's
     replay_blocks = replay_blocks < 64u ? 64u : replay_blocks > 768u ? 768u : replay_blocks;
-    if (tail_fused) after = nullptr;
-    if (a.n_frames <= 128)
-        NL_HIP(nl::launch_stack_sigma_fast(a, f, h->stream, &h->last_kernel, p.timed ? h->ev_dom1 : nullptr,
-                                           mode == NL_ST_WINSOR_SIGMA, after, &fork,
-                                           tail_fused ? &first_replay : nullptr, replay_blocks));
-    else   // 129..512 frames: 2 or 4 lanes per pixel
-        NL_HIP(nl::launch_stack_sigma_ml(a, f, h->stream, &h->last_kernel, p.timed ? h->ev_dom1 : nullptr,
-                                         mode == NL_ST_WINSOR_SIGMA, after, &fork));
-    NL_HIP(fork.err);
+    const hipEvent_t dominant_done = p.timed ? h->ev_dom1 : nullptr;
+    const bool one_lane = a.n_frames <= 128;          // 129 ... 512 frames: 2 or 4 lanes per pixel, the LDS-column kernels
+    if (one_lane) NL_HIP(nl::launch_stack_sigma_fast_dominant(a, f, h->stream, &h->last_kernel, dominant_done, winsor));
+    else          NL_HIP(nl::launch_stack_sigma_mlz(a, nl::whole_tile(f), h->stream, &h->last_kernel, winsor));
+    if (!one_lane && dominant_done) NL_HIP(hipEventRecord(dominant_done, h->stream));
+    if (coop && !tail_fused) {
+        const int rc = fork_first_replay(h, mode, first, grid0, cascade);
+        if (rc != NL_OK) return rc;
+    }
+    if (one_lane) NL_HIP(nl::launch_stack_sigma_fast_generic(a, f, h->stream, winsor, tail_fused ? &first : nullptr, replay_blocks));
+    else          NL_HIP(nl::launch_stack_sigma_mlg(a, nl::over_generic_list(nl::whole_tile(f)), nl::ml_generic_grid(a.n_frames, f.gen_hint), h->stream, winsor));
     if (coop) {
         const char *exact_name = "";
-        e.list_snap = snap;                           // the generic pass's additions
-        e.list_part = 1;
-        NL_HIP(nl::launch_stack_sigma_coop(mode, e, grid1, h->stream, &exact_name));
+        NL_HIP(nl::launch_stack_sigma_coop(mode, second, grid1, h->stream, &exact_name));
         if (!tail_fused) NL_HIP(hipStreamWaitEvent(h->stream, h->ev_join, 0));
     } else {
         const int rc = replay_list(h, mode, p.weighted, a);
@@ -509,9 +494,7 @@ static int run_sigma_fast(nl_stack *h, const PassSetup &p, PassFacts *facts)
         NL_HIP(nl::launch_reduce_counters(h->d_partial, nl::kClipSlots, h->d_counters, h->stream, h->d_fb_count, true));
         facts->zeroed_behind = true;
     }
-    facts->has_counters = true;
-    facts->used_fast = true;
-    facts->lists = true;
+    facts->has_counters = facts->used_fast = facts->lists = true;
     facts->fused = p.fused;
     facts->tail_fused = tail_fused;
     return NL_OK;
@@ -586,7 +569,8 @@ int nl_stack_run_async(nl_stack_t *h, int mode, float sigma_low, float sigma_hig
         (void)hipStreamSynchronize(h->stream);
         if (h->side_stream) (void)hipStreamSynchronize(h->side_stream);
         (void)hipGetLastError();
-        set_last_pass(h, PassFacts{});
+        h->last = PassFacts{};
+        h->sets_clean = false;
         h->partial_clean = false;
         h->pending = false;
         g_err = keep;
@@ -686,7 +670,8 @@ static int run_async_impl(nl_stack_t *h, int mode, float sigma_low, float sigma_
     }
     if (rc != NL_OK) return rc;
     NL_HIP(hipEventRecord(h->ev_stop, h->stream));
-    set_last_pass(h, facts);
+    h->last = facts;
+    h->sets_clean = facts.fused;
     h->partial_clean = facts.zeroed_behind || keep_clean;
     h->pass_seq++;
     h->last_mode = mode;
@@ -699,14 +684,14 @@ int nl_stack_finish(nl_stack_t *h, float *out_host, int64_t *clip_low, int64_t *
     NL_CHECK_HANDLE(h);
     unsigned long long c[4] = {0, 0, 0, 0};
     // (a fast sigma / winsorized pass leaves its list lengths behind the totals: c[2] = exact list | generic list << 32)
-    if (h->last_has_counters && (clip_low || clip_high || h->last_lists))
-        NL_HIP(hipMemcpyAsync(c, h->d_counters, h->last_lists ? 3 * sizeof c[0] : 2 * sizeof c[0], hipMemcpyDeviceToHost, h->stream));
+    if (h->last.has_counters && (clip_low || clip_high || h->last.lists))
+        NL_HIP(hipMemcpyAsync(c, h->d_counters, h->last.lists ? 3 * sizeof c[0] : 2 * sizeof c[0], hipMemcpyDeviceToHost, h->stream));
     if (out_host)
         NL_HIP(hipMemcpyAsync(out_host + (int64_t)h->row0 * h->width, h->d_out,
                               (size_t)h->npix * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     NL_HIP(hipStreamSynchronize(h->stream));
     h->pending = false;
-    if (h->last_has_counters && h->last_lists) {
+    if (h->last.has_counters && h->last.lists) {
         h->fb_hint = (unsigned)(c[2] & 0xffffffffull) + 1u;
         h->gen_hint = (unsigned)(c[2] >> 32) + 1u;
         hints_store({h->n_frames, h->npix, h->last_mode, h->last_weighted}, h->fb_hint, h->gen_hint);
@@ -764,7 +749,7 @@ int nl_stack_set_dev_flags(nl_stack_t *h, unsigned flags)
 static int64_t last_list_length(nl_stack_t *h, int which)
 {
     if (hipSetDevice(h->device) != hipSuccess) return -1;
-    if (h->last_lists) {
+    if (h->last.lists) {
         unsigned long long c = 0;
         if (hipMemcpyAsync(&c, h->d_counters + 2, sizeof c, hipMemcpyDeviceToHost, h->stream) != hipSuccess) return -1;
         if (hipStreamSynchronize(h->stream) != hipSuccess) return -1;
@@ -778,25 +763,25 @@ static int64_t last_list_length(nl_stack_t *h, int which)
 
 int64_t nl_stack_last_fallback_pixels(nl_stack_t *h)
 {
-    if (!h || !h->last_used_fast || !h->d_fb_count) return 0;
+    if (!h || !h->last.used_fast || !h->d_fb_count) return 0;
     return last_list_length(h, 0);
 }
 
 int nl_stack_last_pass_protocol(nl_stack_t *h)
 {
     if (!h) return 0;
-    return (h->last_fused ? 1 : 0) | (h->last_tail_fused ? 2 : 0);
+    return (h->last.fused ? 1 : 0) | (h->last.tail_fused ? 2 : 0);
 }
 
 int64_t nl_stack_last_generic_pixels(nl_stack_t *h)
 {
-    if (!h || !h->last_used_fast || !h->d_fb_count || !h->d_gen_list) return 0;
+    if (!h || !h->last.used_fast || !h->d_fb_count || !h->d_gen_list) return 0;
     return last_list_length(h, 1);
 }
 
 int nl_stack_linfit_stage_counts(nl_stack_t *h, unsigned *counts, int n)
 {
-    if (!h || !counts || n <= 0 || !h->d_lf_count || h->last_mode != NL_ST_LINEAR_FIT || !h->last_used_fast) return 0;
+    if (!h || !counts || n <= 0 || !h->d_lf_count || h->last_mode != NL_ST_LINEAR_FIT || !h->last.used_fast) return 0;
     if (hipSetDevice(h->device) != hipSuccess) return -1;
     unsigned c[nl::kLinfitCounters] = {};
     if (hipMemcpyAsync(c, h->d_lf_count, sizeof c, hipMemcpyDeviceToHost, h->stream) != hipSuccess) return -1;
@@ -835,7 +820,7 @@ int nl_stack_copy_counters_async(nl_stack_t *h, void *device_dst)
 {
     NL_CHECK_HANDLE(h);
     if (!device_dst) return fail(NL_ERR_INVALID_ARG, "copy_counters_async: null destination");
-    if (h->last_has_counters)
+    if (h->last.has_counters)
         NL_HIP(hipMemcpyAsync(device_dst, h->d_counters, 2 * sizeof(unsigned long long), hipMemcpyDeviceToDevice, h->stream));
     else
         NL_HIP(hipMemsetAsync(device_dst, 0, 2 * sizeof(unsigned long long), h->stream));

@@ -448,26 +448,65 @@ hipError_t launch_stack_mad_fast(const StackArgs &args, const FastArgs &fargs, h
 // smallest network size with a zonal instantiation
 constexpr int kZonalMinSize = 16;
 
+// FastArgs of the zonal dominant kernel (network sizes from kZonalMinSize on): the whole tile; with a winsorization cascade
+// the dominant kernel is its stage 0, one region per workgroup.  The generic part runs over_generic_list() of the same.
+static FastArgs zonal_args(const FastArgs &fargs, bool winsor)
+{
+    FastArgs f = whole_tile(fargs);
+    f.cont_list = nullptr; f.cont_state = nullptr; f.cont_count = nullptr; f.cont_region = 0; f.in_state = nullptr;
+    f.in_region = f.in_regions = f.in_group = 0;
+    f.pass_budget = f.round_cap = 0;
+    if (winsor && fargs.cas_list[0]) {
+        f.cont_list = fargs.cas_list[0];
+        f.cont_state = fargs.cas_state[0];
+        f.cont_count = fargs.cas_count[0];
+        f.cont_region = 256;
+        f.pass_budget = fargs.cas_pass[0];
+        f.round_cap = fargs.cas_cap[0];
+    }
+    return f;
+}
+
+// Continuation stages of the winsorization cascade (stack_fast_sigma_impl.hpp): the dominant kernel stopped at its budget
+// and left its unfinished pixels in list 0, one region of 256 entries per workgroup.  Stage st = 1, 2, ... reads list
+// (st - 1) % 2 -- in_group consecutive regions per workgroup, in freshly packed waves -- and writes list st % 2, one region
+// of in_region * in_group entries per workgroup; the last stage has no budget and writes no list.
+template <int NS>
+static void launch_cascade_stages(Launcher &L, const StackArgs &args, const FastArgs &fargs, FastArgs g, unsigned tile_blocks)
+{
+    unsigned regions = tile_blocks, region = 256;          // of the list the stage reads
+    for (int st = 1; st < fargs.cas_stages; st++) {
+        const bool last = st == fargs.cas_stages - 1;
+        const unsigned group = (unsigned)fargs.cas_group[st];
+        const unsigned blocks = (regions + group - 1) / group;
+        g.in_list = fargs.cas_list[(st - 1) & 1];
+        g.in_state = fargs.cas_state[(st - 1) & 1];
+        g.in_count = fargs.cas_count[(st - 1) & 1];
+        g.in_capacity = 0;
+        g.in_region = region;
+        g.in_regions = regions;
+        g.in_group = group;
+        g.cont_list = last ? nullptr : fargs.cas_list[st & 1];
+        g.cont_state = last ? nullptr : fargs.cas_state[st & 1];
+        g.cont_count = last ? nullptr : fargs.cas_count[st & 1];
+        g.cont_region = region * group;                   // (a workgroup cannot hand on more than it was given)
+        g.pass_budget = last ? 0 : fargs.cas_pass[st];
+        g.round_cap = last ? 0 : fargs.cas_cap[st];
+        with_bool(args.n_frames == NS, [&](auto T) {
+            L(stack_sigma_fast_kernel<NS, true, true, decltype(T)::value, false, true>, blocks, 256, 0, args, g);
+        });
+        regions = blocks;
+        region = region * group;
+    }
+}
+
 template <int NS, bool WINSOR>
-static hipError_t launch_pair(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name,
-                              hipEvent_t dominant_done, AfterDominant after, void *user,
-                              const StackArgs *fused_replay, unsigned fused_replay_blocks)
+static hipError_t launch_dominant(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name, hipEvent_t dominant_done)
 {
     Launcher L(stream);
     const unsigned tile_blocks = pixel_grid(args.npix);
-    FastArgs f = whole_tile(fargs);
     if constexpr (NS >= kZonalMinSize) {
-        f.cont_list = nullptr; f.cont_state = nullptr; f.cont_count = nullptr; f.cont_region = 0; f.in_state = nullptr;
-        f.in_region = f.in_regions = f.in_group = 0;
-        f.pass_budget = f.round_cap = 0;
-        if (WINSOR && fargs.cas_list[0]) {            // first stage of the winsorization cascade: one region per workgroup
-            f.cont_list = fargs.cas_list[0];
-            f.cont_state = fargs.cas_state[0];
-            f.cont_count = fargs.cas_count[0];
-            f.cont_region = 256;
-            f.pass_budget = fargs.cas_pass[0];
-            f.round_cap = fargs.cas_cap[0];
-        }
+        const FastArgs f = zonal_args(fargs, WINSOR);
         // (workgroups of 64 or 128 threads instead of 256 -- no wave waits for its workgroup's slowest at the barriers of the
         // hand-over lists -- measured the same within the noise at 32 and 128 frames, round 4)
         with_bool(args.n_frames == NS, [&](auto T) {
@@ -477,75 +516,63 @@ static hipError_t launch_pair(const StackArgs &args, const FastArgs &fargs, hipS
         });
         L.record(dominant_done);
         if constexpr (WINSOR) {
-            // winsorization cascade (stack_fast_sigma_impl.hpp): the dominant kernel above stopped at its budget; two more
-            // stages over the continuation lists, in freshly packed waves, the last one without a budget
-            if (fargs.cas_list[0]) {
-                FastArgs g = f;
-                unsigned regions = tile_blocks, region = 256;          // of the list the stage reads
-                for (int st = 1; st < fargs.cas_stages; st++) {
-                    const bool last = st == fargs.cas_stages - 1;
-                    const unsigned group = (unsigned)fargs.cas_group[st];
-                    const unsigned blocks = (regions + group - 1) / group;
-                    g.in_list = fargs.cas_list[(st - 1) & 1];
-                    g.in_state = fargs.cas_state[(st - 1) & 1];
-                    g.in_count = fargs.cas_count[(st - 1) & 1];
-                    g.in_capacity = 0;
-                    g.in_region = region;
-                    g.in_regions = regions;
-                    g.in_group = group;
-                    g.cont_list = last ? nullptr : fargs.cas_list[st & 1];
-                    g.cont_state = last ? nullptr : fargs.cas_state[st & 1];
-                    g.cont_count = last ? nullptr : fargs.cas_count[st & 1];
-                    g.cont_region = region * group;                   // (a workgroup cannot hand on more than it was given)
-                    g.pass_budget = last ? 0 : fargs.cas_pass[st];
-                    g.round_cap = last ? 0 : fargs.cas_cap[st];
-                    with_bool(args.n_frames == NS, [&](auto T) {
-                        L(stack_sigma_fast_kernel<NS, true, WINSOR, decltype(T)::value, false, true>, blocks, 256, 0, args, g);
-                    });
-                    regions = blocks;
-                    region = region * group;
-                }
-            }
+            if (fargs.cas_list[0]) launch_cascade_stages<NS>(L, args, fargs, f, tile_blocks);
         }
-        if (after) after(user);
-        // generic pass over the pixels the zonal waves handed over (its length
-        // is only known on the device: fixed grid, grid-stride loop)
-        const FastArgs fg = over_generic_list(f);
+    } else {
+        // small stacks: generic passes are cheap, run them over the whole tile
+        *name = kernel_name<kSigmaFastName, NS, false, WINSOR, false, false, false>();
+        L(stack_sigma_fast_kernel<NS, false, WINSOR, false>, tile_blocks, 256, 0, args, whole_tile(fargs));
+        L.record(dominant_done);
+    }
+    return L.err;
+}
+
+// generic pass over the pixels the zonal waves handed over (its length is only known on the device: fixed grid, grid-stride loop)
+template <int NS, bool WINSOR>
+static hipError_t launch_generic(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const StackArgs *first_replay, unsigned replay_blocks)
+{
+    Launcher L(stream);
+    if constexpr (NS >= kZonalMinSize) {
+        const unsigned tile_blocks = pixel_grid(args.npix);
+        const FastArgs fg = over_generic_list(zonal_args(fargs, WINSOR));
         if constexpr (NS > 64) {
-            // whole columns + prefix sums in LDS (stack_fast_mlg.hip): a clipping or winsorization round
-            // is a few LDS reads instead of a pass over 128 masked registers -- this pass is pure
-            // latency (a few hundred waves at most), and it sits on every pass's critical path
+            // whole columns + prefix sums in LDS (stack_fast_mlg.hip): a clipping or winsorization round is a few LDS reads instead of a
+            // pass over 128 masked registers -- this pass is pure latency (a few hundred waves at most), on every pass's critical path
             const unsigned lblocks = generic_grid(fargs.gen_hint, 64, 4 * std::min(tile_blocks, kGenericGrid));
-            if (!WINSOR && fused_replay)      // generic pass + first replay in one grid (stack_tail_fused.hip)
-                L.keep(launch_stack_sigma_tail(args, fg, lblocks, *fused_replay, fused_replay_blocks, stream));
+            if (!WINSOR && first_replay)      // generic pass + first replay in one grid (stack_tail_fused.hip)
+                L.keep(launch_stack_sigma_tail(args, fg, lblocks, *first_replay, replay_blocks, stream));
             else
                 L.keep(launch_stack_sigma_mlg(args, fg, lblocks, stream, WINSOR));
         } else {
             L(stack_sigma_fast_kernel<NS, false, WINSOR, false>, generic_grid(fargs.gen_hint, 256, std::min(tile_blocks, kGenericGrid)),
               256, 0, args, fg);
         }
-    } else {
-        // small stacks: generic passes are cheap, run them over the whole tile
-        *name = kernel_name<kSigmaFastName, NS, false, WINSOR, false, false, false>();
-        L(stack_sigma_fast_kernel<NS, false, WINSOR, false>, tile_blocks, 256, 0, args, f);
-        L.record(dominant_done);
-        if (after) after(user);
     }
     return L.err;
 }
 
-hipError_t launch_stack_sigma_fast(const StackArgs &args, const FastArgs &fargs, hipStream_t stream,
-                                   const char **name, hipEvent_t dominant_done,
-                                   bool winsor, AfterDominant after, void *user,
-                                   const StackArgs *fused_replay, unsigned fused_replay_blocks)
+// f(network size, winsorized): the frame count rounded up to the next instantiated size; unused positions count as missing samples
+template <class F>
+static hipError_t with_sigma_network(bool winsor, int n_frames, F &&f)
 {
-    // network sizes: the frame count rounded up to the next instantiated size;
-    // unused positions count as missing samples
     return with_bool(winsor, [&](auto W) {
-        return with_class<8, 16, 24, 32, 48, 64, 80, 96, 112, 128>(args.n_frames, [&](auto C) {
-            return launch_pair<decltype(C)::value, decltype(W)::value>(args, fargs, stream, name, dominant_done, after, user,
-                                                                       fused_replay, fused_replay_blocks);
-        });
+        return with_class<8, 16, 24, 32, 48, 64, 80, 96, 112, 128>(n_frames, [&](auto C) { return f(C, W); });
+    });
+}
+
+hipError_t launch_stack_sigma_fast_dominant(const StackArgs &args, const FastArgs &fargs, hipStream_t stream,
+                                            const char **name, hipEvent_t dominant_done, bool winsor)
+{
+    return with_sigma_network(winsor, args.n_frames, [&](auto C, auto W) {
+        return launch_dominant<decltype(C)::value, decltype(W)::value>(args, fargs, stream, name, dominant_done);
+    });
+}
+
+hipError_t launch_stack_sigma_fast_generic(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, bool winsor,
+                                           const StackArgs *first_replay, unsigned replay_blocks)
+{
+    return with_sigma_network(winsor, args.n_frames, [&](auto C, auto W) {
+        return launch_generic<decltype(C)::value, decltype(W)::value>(args, fargs, stream, first_replay, replay_blocks);
     });
 }
 

@@ -196,22 +196,10 @@ int fast_ml_supported(int mode, bool weighted, int n_frames, int64_t npix)
     return ((mode == NL_ST_SIGMA || mode == NL_ST_WINSOR_SIGMA) && !weighted) ? 1 : 0;
 }
 
-// Dominant kernel = the LDS-column kernel of the frame-count class (stack_fast_mlz*.hip), generic pass = whole columns in
-// LDS (stack_fast_mlg.hip).
-hipError_t launch_stack_sigma_ml(const StackArgs &args, const FastArgs &fargs, hipStream_t stream,
-                                 const char **name, hipEvent_t dominant_done, bool winsor,
-                                 AfterDominant after, void *user)
+// workgroups of the generic pass behind an LDS-column dominant kernel (launch_stack_sigma_mlg): generic_grid at 64 / LPP pixels each
+unsigned ml_generic_grid(int n_frames, unsigned gen_hint)
 {
-    Launcher L(stream);
-    const FastArgs f = whole_tile(fargs);
-    // every position in use: the clipping rounds run on LDS columns (stack_fast_mlz.hip), which sets *name
-    L.keep(launch_stack_sigma_mlz(args, f, stream, name, winsor));
-    L.record(dominant_done);
-    if (after) after(user);
-    // generic pass over the hand-over list: whole columns in LDS (stack_fast_mlg.hip)
-    const unsigned grid = with_ml_lanes(args.n_frames, [&](auto LPP) { return generic_grid(fargs.gen_hint, 64 / LPP, 4 * kGenericGrid); });
-    L.keep(launch_stack_sigma_mlg(args, over_generic_list(f), grid, stream, winsor));
-    return L.err;
+    return with_ml_lanes(n_frames, [&](auto LPP) { return generic_grid(gen_hint, 64 / LPP, 4 * kGenericGrid); });
 }
 
 }  // namespace nl

@@ -217,9 +217,6 @@ hipError_t launch_stack_median_fast(const StackArgs &args, const FastArgs &fargs
 // dominant_done (optional) is recorded right after the first, dominant kernel
 int mad_fast_supported(int mode, bool weighted, int n_frames, int64_t npix);
 hipError_t launch_stack_mad_fast(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name);
-// after_dominant(user) is called between the launch of the dominant (zonal) kernel and
-// the generic pass, so the caller can start work that only depends on the former
-typedef void (*AfterDominant)(void *user);
 // 249..256 / 505..512 frames: zonal sigma / winsorized sigma pass with the clipping rounds on LDS
 // columns (stack_fast_mlz.hip); hand-over lists as the other fast kernels
 // generic pass of the multi-lane sigma / winsor kernels over fargs.in_list, whole columns in LDS (stack_fast_mlg.hip)
@@ -228,13 +225,15 @@ hipError_t launch_stack_sigma_mlg(const StackArgs &args, const FastArgs &fargs, 
 int fast_mlz_supported(int mode, bool weighted, int n_frames);
 hipError_t launch_stack_sigma_mlz(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name,
                                   bool winsor);
-// fused_replay (optional; tail_fused_supported): the generic pass and the replay of the exact list as the dominant kernel left
-// it run as ONE launch (stack_tail_fused.hip) -- *fused_replay are the replay's arguments (list part 0), in fused_replay_blocks
-// workgroups; after_dominant is then not needed for the replay
-hipError_t launch_stack_sigma_fast(const StackArgs &args, const FastArgs &fargs, hipStream_t stream,
-                                   const char **name, hipEvent_t dominant_done,
-                                   bool winsor, AfterDominant after_dominant, void *user,
-                                   const StackArgs *fused_replay = nullptr, unsigned fused_replay_blocks = 0);
+// sigma / winsorized clipping of 2 ... 128 frames, in the two parts a pass enqueues them.  Dominant part: the zonal kernel
+// (network size 8: the generic kernel over the whole tile), dominant_done (optional) recorded behind it, and for winsorized
+// stacks the continuation stages of the cascade.  Generic part: the pass over the generic list (network size 8: nothing);
+// with first_replay (tail_fused_supported) it shares ONE launch with the replay of the exact list as the dominant part left
+// it (stack_tail_fused.hip) -- *first_replay are that replay's arguments (list part 0), in replay_blocks workgroups
+hipError_t launch_stack_sigma_fast_dominant(const StackArgs &args, const FastArgs &fargs, hipStream_t stream,
+                                            const char **name, hipEvent_t dominant_done, bool winsor);
+hipError_t launch_stack_sigma_fast_generic(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, bool winsor,
+                                           const StackArgs *first_replay = nullptr, unsigned replay_blocks = 0);
 // ---- stack_tail_fused.hip: generic pass (one lane per pixel, LDS columns) + first replay in one grid; plain sigma, 65 ... 128 frames
 int tail_fused_supported(int mode, bool weighted, int n_frames);
 hipError_t launch_stack_sigma_tail(const StackArgs &generic, const FastArgs &fargs, unsigned gen_blocks,
@@ -255,9 +254,7 @@ constexpr int kMlNS = 128;     // samples per lane of the multi-lane kernels
 int fast_ml_supported(int mode, bool weighted, int n_frames, int64_t npix);
 hipError_t launch_stack_median_ml(const StackArgs &args, hipStream_t stream, const char **name);
 hipError_t launch_stack_mad_ml(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name);
-hipError_t launch_stack_sigma_ml(const StackArgs &args, const FastArgs &fargs, hipStream_t stream,
-                                 const char **name, hipEvent_t dominant_done, bool winsor,
-                                 AfterDominant after_dominant, void *user);
+unsigned ml_generic_grid(int n_frames, unsigned gen_hint);      // workgroups of launch_stack_sigma_mlg behind launch_stack_sigma_mlz
 
 // ---- stack_exact_coop.hip (bit-exact sigma replay, one wave per pixel) ----
 int coop_supported(int mode, bool weighted, int n_frames);

@@ -1159,6 +1159,54 @@ def test_dispatch_table(nl, mode, n, weighted, exact, flags, kernel, protocol):
     assert _dispatch_second_pass(nl, mode, n, weighted, exact, flags) == (kernel, protocol, mode)
 
 
+# The orders in which the tail of a sigma / winsorized fast pass may be enqueued -- first replay forked to the side stream
+# from the event behind the dominant kernel or from one of its own (untimed pass, 32; cascade stages), in front of the
+# generic pass (2), sharing its launch or not (8192), plain protocol (1) -- on the smallest tile on which the winsorization
+# cascade runs (65 536 pixels): one row per path through run_sigma_fast.
+# fill_synthetic leaves no hand-over list of these rows empty (asserted below).  Every row is bit-stable: the library from
+# before run_sigma_fast was written as one sequence passes the same bar, none needs values within RTOL instead of bits.
+TAIL_ORDER_ROWS = [
+    (2, 8),        # no generic pass
+    (3, 24),       # shallow cascade plan, register generic pass
+    (3, 48),       # deep plan
+    (3, 96),       # deep plan, LDS-column generic pass, fork from an event of its own
+    (2, 100),      # padded network, one-launch tail
+    (2, 128),      # headline
+    (3, 128),      # no cascade
+    (2, 300),      # multi-lane
+    (3, 300),
+]
+
+
+@pytest.mark.parametrize("mode,n", TAIL_ORDER_ROWS)
+def test_tail_enqueue_orders_give_the_default_bits_and_counters(nl, oracle, mode, n):
+    width, rows = 4096, 16
+    pinned = {(m, k): proto for m, k, weighted, exact, flags, _, proto in DISPATCH_TABLE if not weighted and exact == 0 and flags == 0}
+    with nl.StackHandle(n, width, 4096, row0=0, rows=rows) as st:
+        st.fill_synthetic(3)
+        ref = None
+        for k, flags in enumerate((0, 0, 2, 32, 8192, 8192 | 32, 1, 0)):
+            st.set_dev_flags(flags)
+            got, cl, ch = st.run(mode, 3.0, 2.5)
+            got = got[:rows * width]
+            if ref is None:
+                ref = (got.copy(), cl, ch)
+            lists = (st.last_generic_pixels, st.last_fallback_pixels)
+            print("mode %d n %d flags %d: protocol %d, generic / exact list %r, counters %r" % (mode, n, flags, st.last_pass_protocol, lists, (cl, ch)))
+            if k == 1 and (mode, n) in pinned:        # the first pass with list-length hints
+                assert st.last_pass_protocol == pinned[(mode, n)], (st.last_pass_protocol, lists)
+            if n >= 16:
+                assert lists[0] > 0, "no pixel went through the generic pass"
+            if mode == 2 and n in (100, 128):
+                assert lists[1] > 0, "no pixel was replayed"
+            assert (cl, ch) == ref[1:], (flags, cl, ch, ref[1:])
+            assert np.array_equal(got.view(np.uint32), ref[0].view(np.uint32)), flags
+        if mode == 2 and n in (100, 128):
+            frames = np.stack([st.download_tile(i) for i in range(n)])
+            rc, _, wl, wh, _ = oracle.stack_apply(2, frames, None, 3.0, 2.5, 0.0, num_cpu=4)
+            assert rc == 0 and ref[1:] == (wl, wh), (ref[1:], wl, wh)
+
+
 def test_mean_pass_reports_no_hand_over_lists(nl):
     # a mean pass hands no pixels over: after a sigma fast pass that listed pixels (infinite samples go to the exact
     # kernel), a mean pass on the same handle reports empty lists, not the lists of the pass before it

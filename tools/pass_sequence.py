@@ -1,0 +1,27 @@
+"""The kernels a stack pass enqueues, in enqueue order (run on the GPU box):
+    rocprofv3 --kernel-trace --stats -d DIR -o seq --output-format csv -- python tools/pass_sequence.py run
+    python tools/pass_sequence.py list DIR > profiles/<name>.txt
+`run`: two passes each, on one handle each, of sigma 128 frames, winsorized 24 and winsorized 300 on a 512-row tile.
+`list`: kernel name, grid and workgroup size and queue (numbered by first appearance) of every dispatch of the trace,
+in dispatch order -- two libraries that enqueue the same work in the same order give the same listing."""
+import csv
+import glob
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+if sys.argv[1] == "run":
+    from nightlight_amd import StackHandle
+    for mode, n in ((2, 128), (3, 24), (3, 300)):
+        with StackHandle(n, 4096, 4096, device=0, row0=1536, rows=512) as st:
+            st.fill_synthetic(seed=1)
+            for _ in range(2):
+                st.run(mode, 3.0, 3.0, fetch=False)
+else:
+    path, = glob.glob(os.path.join(sys.argv[2], "**", "*kernel_trace.csv"), recursive=True)
+    rows = sorted(csv.DictReader(open(path)), key=lambda r: int(r["Dispatch_Id"]))
+    queues = {}
+    for r in rows:
+        q = queues.setdefault(r["Queue_Id"], len(queues))
+        print("q%d  grid %8d  wg %4d  %s" % (q, int(r["Grid_Size_X"]), int(r["Workgroup_Size_X"]), r["Kernel_Name"]))
