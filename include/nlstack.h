@@ -580,6 +580,61 @@ int nl_stack_frame_back_extract(nl_stack_t *h, int idx, int grid_size, float hfr
                                 float *background_out, float *cells_out, int cells_capacity,
                                 nl_background_t *info);
 
+/* ---- OpDebandHoriz / OpDebandVert (internal/ops/pre/banding.go:61-132, :197-270) ----
+ * Bit-exact wherever the reference returns: the frame, threshold and the factors' range.  Per row (horiz)
+ * or column (vert) the percentile-th percentile of the samples <= threshold (QSelectFloat32 with
+ * k = int(float32(n) * percentile * 0.01), :82-93) is selected on the device; the windows over those
+ * percentiles, fixWindowEdge (:134-162), the window medians and the factors median / percentile run on
+ * the host literally; then every pixel is multiplied by its row's / column's factor on the device.
+ * threshold is MaxFloat32 when sigma == 0, else location + sigma * scale with the caller's
+ * f.Stats.Location() / Scale() (as for nl_find_stars; this library does not estimate them).
+ * info (may be NULL): what the reference's log line prints, "... threshold %.2f, factors in [%.3f, %.3f]".
+ * The operators' own guards -- percentile <= 0 or >= 100, and for horiz window <= 0 (:62, :198) -- are
+ * no-ops: NL_OK, every bit of the frame unchanged, info = {threshold, 1, 0}.  Without a device every
+ * entry fails with NL_ERR_NO_DEVICE.
+ * Deviations, all NL_ERR_INVALID_ARG with a message naming the site:
+ *   1. where the reference panics: a row / column with no sample <= threshold (QSelectFloat32 on an empty
+ *      slice; a NaN threshold, a line of NaN, or of +Inf with sigma == 0); window <= 0 in vert (make with a
+ *      negative length, QSelectMedianFloat32 of no element); an out-of-bounds index in one of the literal
+ *      selects over a window (a NaN among the interpolated edge values).
+ *   2. where the selected rank is tied between -0 and +0, the device may return the other zero: the factor
+ *      is then the other infinity. */
+typedef struct nl_deband {
+    float threshold, lowest, highest;
+} nl_deband_t;
+/* One host frame, in place (data_host in and out), on a handle of its own per call: safe to call from
+ * several host threads at once, like nl_preprocess_frame. */
+int nl_deband_horiz(float *data_host, int width, int height, float percentile, int window, float sigma,
+                    float location, float scale, nl_deband_t *info, int device);
+int nl_deband_vert(float *data_host, int width, int height, float percentile, int window, float sigma,
+                   float location, float scale, nl_deband_t *info, int device);
+/* The same on resident slot idx of a whole-image handle, in place (the window needs every row's
+ * percentile: row tiles fail with NL_ERR_INVALID_ARG, like nl_stack_frame_badpixel).  The frame never
+ * crosses PCIe, only the percentiles (down) and the factors (up) do. */
+int nl_stack_frame_deband_horiz(nl_stack_t *h, int idx, float percentile, int window, float sigma,
+                                float location, float scale, nl_deband_t *info);
+int nl_stack_frame_deband_vert(nl_stack_t *h, int idx, float percentile, int window, float sigma,
+                               float location, float scale, nl_deband_t *info);
+
+/* ---- OpBin: fits.NewImageBinNxN (internal/ops/pre/preprocess.go:324-331, internal/fits/fits.go:163-195) ----
+ * Bit-exact: every output pixel is the reference's fp32 sum over yoff then xoff, times
+ * 1.0 / float32(n * n).  The output is width / n by height / n (the remainder columns and rows are
+ * dropped); n <= 1 is OpBin's no-op.  (OpScaleOffset, which precedes OpBin in the reference's sequence,
+ * is nl_stack_frame_affine.)
+ * Deviation: a binned shape of 0 pixels (n > width or n > height) fails with NL_ERR_INVALID_ARG.
+ *
+ * nl_bin_shape: the shape OpBin gives a width x height frame.  Host only, needs no device. */
+int nl_bin_shape(int width, int height, int n, int *out_width, int *out_height);
+/* One host frame into out_host of nl_bin_shape pixels (n <= 1: a copy), on handles of its own per call:
+ * safe to call from several host threads at once. */
+int nl_bin_nxn(const float *in_host, int width, int height, int n, float *out_host, int device);
+/* Resident slot src_idx of one whole-image handle binned into slot dst_idx of another on the same device,
+ * whose shape is nl_bin_shape of the source's (n <= 1: a device copy); neither frame crosses PCIe.  The
+ * destination's stream waits on the source's.  Intended use: a one-frame staging handle of the raw shape
+ * (calibrate, bad pixels, deband) binned into the stack handle.  Row tiles, handles on different devices,
+ * a shape mismatch and a destination whose frames are attached, not owned, fail with NL_ERR_INVALID_ARG. */
+int nl_stack_frame_bin_from(nl_stack_t *dst, int dst_idx, nl_stack_t *src, int src_idx, int n);
+
 /* ---- host-side operator mirror (nightlight_amd/host/, C++) ----
  * The reference's stack operator decoded from its JSON form and run through
  * MakePromises/Apply exactly as OpSequence would drive it

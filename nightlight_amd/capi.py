@@ -57,6 +57,8 @@ EXPORTS = [
     "nl_debayer_shape", "nl_preprocess_frame_cfa", "nl_stack_upload_frame_cfa",
     "nl_find_stars", "nl_stack_frame_find_stars", "nl_stack_result_find_stars",
     "nl_back_extract", "nl_stack_frame_back_extract",
+    "nl_deband_horiz", "nl_deband_vert", "nl_stack_frame_deband_horiz", "nl_stack_frame_deband_vert",
+    "nl_bin_shape", "nl_bin_nxn", "nl_stack_frame_bin_from",
 ]
 
 # nl_star_t = star.Star (findstars.go:30-37), 24 bytes
@@ -71,6 +73,11 @@ class Background(C.Structure):
     """nl_background_t: what Background.String() prints (background.go:48-52), plus the geometry."""
     _fields_ = [("cells_x", C.c_int32), ("cells_y", C.c_int32), ("outlier_cells", C.c_int32),
                 ("spacing_x", C.c_float), ("spacing_y", C.c_float), ("min", C.c_float), ("max", C.c_float)]
+
+
+class Deband(C.Structure):
+    """nl_deband_t: what the debanding operators' log lines print (banding.go:129, :267)."""
+    _fields_ = [("threshold", C.c_float), ("lowest", C.c_float), ("highest", C.c_float)]
 
 
 class NlError(RuntimeError):
@@ -251,6 +258,14 @@ def open_library(path):
     _back_args = [C.c_int, C.c_float, C.c_float, C.c_int, vp, C.c_int, _f32p, _f32p, C.c_int, C.POINTER(Background)]
     L.nl_back_extract.argtypes = [_f32p, C.c_int, C.c_int] + _back_args + [C.c_int]
     L.nl_stack_frame_back_extract.argtypes = [vp, C.c_int] + _back_args
+    _deband_args = [C.c_float, C.c_int, C.c_float, C.c_float, C.c_float, C.POINTER(Deband)]
+    for name in ("nl_deband_horiz", "nl_deband_vert"):
+        getattr(L, name).argtypes = [_f32p, C.c_int, C.c_int] + _deband_args + [C.c_int]
+    for name in ("nl_stack_frame_deband_horiz", "nl_stack_frame_deband_vert"):
+        getattr(L, name).argtypes = [vp, C.c_int] + _deband_args
+    L.nl_bin_shape.argtypes = [C.c_int, C.c_int, C.c_int, _intp, _intp]
+    L.nl_bin_nxn.argtypes = [_f32p, C.c_int, C.c_int, C.c_int, _f32p, C.c_int]
+    L.nl_stack_frame_bin_from.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int]
     return L
 
 

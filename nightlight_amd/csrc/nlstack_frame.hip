@@ -1,6 +1,7 @@
 // nlstack_frame.hip -- steps on one frame resident in a handle, and their host forms: statistics and noise,
-// median filters, OpCalibrate / OpBadPixel, star detection, background extraction, the colour-camera front.  Kernels
-// in frame_stats.hip, preprocess.hip, stars.hip, background.hip and bayer.hip.
+// median filters, OpCalibrate / OpBadPixel, star detection, background extraction, debanding and binning, the
+// colour-camera front.  Kernels in frame_stats.hip, preprocess.hip, stars.hip, background.hip, deband.hip and bayer.hip.
+#include <float.h>
 #include <math.h>
 
 #include <algorithm>
@@ -491,6 +492,158 @@ int nl_back_extract(float *data_host, int width, int height, int grid_size, floa
             r = back_extract_impl(h, h->d_frames, "back_extract", grid_size, hfr_factor, sigma, clip, stars, n_stars,
                                   background_out, cells_out, cells_capacity, info);
         return r == NL_OK ? nl_stack_download_tile(h, 0, data_host) : r;
+    });
+}
+
+// ---- OpDebandHoriz / OpDebandVert (internal/ops/pre/banding.go:61-270; kernels and host steps in deband.hip) -------
+
+// the operators' own guards (:62, :198)
+static bool deband_is_noop(bool cols, float percentile, int window)
+{
+    return percentile <= 0.0f || percentile >= 100.0f || (!cols && window <= 0);
+}
+
+static int deband_impl(nl_stack_t *h, float *d_data, const char *who, bool cols, float percentile, int window,
+                       float sigma, float location, float scale, nl_deband_t *info)
+{
+    int pre = need_whole_image(h, who, "the window needs every row's percentile");
+    if (pre == NL_OK) pre = need_int32_pixels(h->npix, who);
+    if (pre != NL_OK) return pre;
+    float threshold = FLT_MAX;                 // :75-79, :211-215
+    if (sigma != 0.0f) threshold = location + sigma * scale;
+    nl_deband_t out{threshold, 1.0f, 0.0f};
+    if (!deband_is_noop(cols, percentile, window)) {
+        const nl::DebandParams p{percentile, window, threshold};
+        std::string msg;
+        const int rc = nl::deband_run(d_data, h->width, h->height, cols, p, h->frame_scratch.deband_work, h->stream,
+                                      &out.lowest, &out.highest, &msg);
+        if (rc != NL_OK) return fail(rc, "%s: %s", who, msg.c_str());
+    }
+    if (info) *info = out;
+    return NL_OK;
+}
+
+static int frame_deband(nl_stack_t *h, int idx, const char *who, bool cols, float percentile, int window, float sigma,
+                        float location, float scale, nl_deband_t *info)
+{
+    NL_CHECK_HANDLE(h);
+    NL_SETTLE_UPLOADS(h);
+    float *d = frame_or_fail(h, idx, who);
+    if (!d) return NL_ERR_INVALID_ARG;
+    return deband_impl(h, d, who, cols, percentile, window, sigma, location, scale, info);
+}
+
+int nl_stack_frame_deband_horiz(nl_stack_t *h, int idx, float percentile, int window, float sigma, float location,
+                                float scale, nl_deband_t *info)
+{
+    return frame_deband(h, idx, "frame_deband_horiz", false, percentile, window, sigma, location, scale, info);
+}
+
+int nl_stack_frame_deband_vert(nl_stack_t *h, int idx, float percentile, int window, float sigma, float location,
+                               float scale, nl_deband_t *info)
+{
+    return frame_deband(h, idx, "frame_deband_vert", true, percentile, window, sigma, location, scale, info);
+}
+
+static int host_deband(float *data_host, int width, int height, const char *who, bool cols, float percentile,
+                       int window, float sigma, float location, float scale, nl_deband_t *info, int device)
+{
+    if (!data_host || width < 1 || height < 1) return fail(NL_ERR_INVALID_ARG, "%s: bad argument", who);
+    const int rc = select_device(device);
+    if (rc != NL_OK) return rc;
+    if (deband_is_noop(cols, percentile, window))      // no-op: the frame is not even uploaded
+        return with_scratch_handle(1, 1, device, [&](nl_stack_t *h) {
+            return deband_impl(h, h->d_frames, who, cols, percentile, window, sigma, location, scale, info);
+        });
+    return with_scratch_handle(width, height, device, [&](nl_stack_t *h) {
+        int r = nl_stack_upload_tile(h, 0, data_host);
+        if (r == NL_OK) r = deband_impl(h, h->d_frames, who, cols, percentile, window, sigma, location, scale, info);
+        return r == NL_OK ? nl_stack_download_tile(h, 0, data_host) : r;
+    });
+}
+
+int nl_deband_horiz(float *data_host, int width, int height, float percentile, int window, float sigma,
+                    float location, float scale, nl_deband_t *info, int device)
+{
+    return host_deband(data_host, width, height, "deband_horiz", false, percentile, window, sigma, location, scale,
+                       info, device);
+}
+
+int nl_deband_vert(float *data_host, int width, int height, float percentile, int window, float sigma, float location,
+                   float scale, nl_deband_t *info, int device)
+{
+    return host_deband(data_host, width, height, "deband_vert", true, percentile, window, sigma, location, scale,
+                       info, device);
+}
+
+// ---- OpBin: fits.NewImageBinNxN (internal/ops/pre/preprocess.go:324-331, internal/fits/fits.go:163-195; deband.hip) -
+
+int nl_bin_shape(int width, int height, int n, int *out_width, int *out_height)
+{
+    if (width < 1 || height < 1 || !out_width || !out_height) return fail(NL_ERR_INVALID_ARG, "bin_shape: bad argument");
+    if (n <= 1) {                              // OpBin.Apply is a no-op (preprocess.go:325-327)
+        *out_width = width;
+        *out_height = height;
+        return NL_OK;
+    }
+    *out_width = width / n;                    // fits.go:167-171
+    *out_height = height / n;
+    if (*out_width == 0 || *out_height == 0)   // (deviation)
+        return fail(NL_ERR_INVALID_ARG, "NewImageBinNxN (fits.go:163-195): %dx%d binned by %d gives an empty %dx%d image",
+                    width, height, n, *out_width, *out_height);
+    return NL_OK;
+}
+
+int nl_stack_frame_bin_from(nl_stack_t *dst, int dst_idx, nl_stack_t *src, int src_idx, int n)
+{
+    NL_CHECK_HANDLE(src);
+    NL_CHECK_HANDLE(dst);
+    if (src->device != dst->device)
+        return fail(NL_ERR_INVALID_ARG, "frame_bin_from: source on device %d, destination on device %d", src->device,
+                    dst->device);
+    NL_SETTLE_UPLOADS(src);
+    NL_SETTLE_UPLOADS(dst);
+    const float *s = frame_or_fail(src, src_idx, "frame_bin_from (source)");
+    float *d = s ? frame_or_fail(dst, dst_idx, "frame_bin_from (destination)") : nullptr;
+    if (!d) return NL_ERR_INVALID_ARG;
+    int rc = need_whole_image(src, "frame_bin_from (source)", "a bin spans rows");
+    if (rc == NL_OK) rc = need_whole_image(dst, "frame_bin_from (destination)", "a bin spans rows");
+    if (rc == NL_OK) rc = need_int32_pixels(src->npix, "frame_bin_from");
+    if (rc != NL_OK) return rc;
+    if (dst->d_frames != dst->d_frames_owned)
+        return fail(NL_ERR_INVALID_ARG, "frame_bin_from: the destination's frames are attached, not owned");
+    int ow, oh;
+    if ((rc = nl_bin_shape(src->width, src->height, n, &ow, &oh)) != NL_OK) return rc;
+    if (dst->width != ow || dst->height != oh)
+        return fail(NL_ERR_INVALID_ARG, "frame_bin_from: %dx%d binned by %d is %dx%d, the destination is %dx%d",
+                    src->width, src->height, n, ow, oh, dst->width, dst->height);
+    if (src != dst && (rc = nl_stack_order_stream_after(src, dst->stream)) != NL_OK) return rc;
+    if (n > 1)
+        NL_HIP(nl::launch_bin(s, src->width, src->height, n, d, dst->stream));
+    else if (s != d)
+        NL_HIP(hipMemcpyAsync(d, s, sizeof(float) * (size_t)src->npix, hipMemcpyDeviceToDevice, dst->stream));
+    NL_HIP(hipStreamSynchronize(dst->stream));
+    return NL_OK;
+}
+
+int nl_bin_nxn(const float *in_host, int width, int height, int n, float *out_host, int device)
+{
+    if (!in_host || !out_host || width < 1 || height < 1) return fail(NL_ERR_INVALID_ARG, "bin_nxn: bad argument");
+    int rc = select_device(device);
+    if (rc != NL_OK) return rc;
+    int ow, oh;
+    if ((rc = nl_bin_shape(width, height, n, &ow, &oh)) != NL_OK) return rc;
+    if (n <= 1) {
+        if (out_host != in_host) memmove(out_host, in_host, sizeof(float) * (size_t)width * height);
+        return NL_OK;
+    }
+    return with_scratch_handle(width, height, device, [&](nl_stack_t *src) {
+        const int r = nl_stack_upload_tile(src, 0, in_host);
+        if (r != NL_OK) return r;
+        return with_scratch_handle(ow, oh, device, [&](nl_stack_t *dst) {
+            const int rb = nl_stack_frame_bin_from(dst, 0, src, 0, n);
+            return rb == NL_OK ? nl_stack_download_tile(dst, 0, out_host) : rb;
+        });
     });
 }
 

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "background.hpp"
+#include "deband.hpp"
 #include "dev_memory.hpp"
 #include "stars.hpp"
 #include "stack_kernels.h"
@@ -148,10 +149,12 @@ struct nl_stack {
         nl::StarWork star_work;
         // background extraction (nl_stack_frame_back_extract)
         nl::BackWork back_work;
+        // debanding (nl_stack_frame_deband_horiz / _vert)
+        nl::DebandWork deband_work;
         size_t bytes() const
         {
             return bp_diff.bytes + bp_seg.bytes + bp_list.bytes + bp_small.bytes + cfa.bytes + star_work.bytes() +
-                   back_work.bytes();
+                   back_work.bytes() + deband_work.bytes();
         }
         void release(int device)
         {
@@ -162,6 +165,7 @@ struct nl_stack {
             cfa.release();
             star_work.release();
             back_work.release();
+            deband_work.release();
         }
     } frame_scratch;
     int max_grid = 0;

@@ -369,6 +369,21 @@ class StackHandle:
                                            render)
         return None, bg, cells, info
 
+    def frame_deband_horiz(self, idx, percentile=50.0, window=128, sigma=3.0, location=0.0, scale=0.0):
+        """OpDebandHoriz on resident slot idx of a whole-image handle, in place (see deband_horiz).  Returns info."""
+        return _deband(lambda *a: self._lib.nl_stack_frame_deband_horiz(self._h, int(idx), *a), percentile, window,
+                       sigma, location, scale)
+
+    def frame_deband_vert(self, idx, percentile=50.0, window=128, sigma=3.0, location=0.0, scale=0.0):
+        """OpDebandVert on resident slot idx of a whole-image handle, in place (see deband_vert).  Returns info."""
+        return _deband(lambda *a: self._lib.nl_stack_frame_deband_vert(self._h, int(idx), *a), percentile, window,
+                       sigma, location, scale)
+
+    def frame_bin_from(self, idx, src, src_idx, n):
+        """NewImageBinNxN of resident slot src_idx of the whole-image handle `src` into slot idx of this one, whose
+        shape is bin_shape of the source's (n <= 1: a device copy)."""
+        capi.check(self._lib.nl_stack_frame_bin_from(self._h, int(idx), src._h, int(src_idx), int(n)))
+
     def download_result_fits(self):
         raw = np.empty(self.tile_pixels * 4, np.uint8)
         capi.check(self._lib.nl_stack_download_result_fits(self._h, raw.ctypes.data_as(C.c_void_p)))
@@ -667,6 +682,56 @@ def back_extract(frame, width, height, stars, grid_size, hfr_factor=4.0, sigma=1
         lambda *a: lib.nl_back_extract(capi.fptr(out), int(width), int(height), *a, 0 if device is None else int(device)),
         width, height, stars, grid_size, hfr_factor, sigma, clip, render)
     return (out if int(grid_size) > 0 else None), bg, cells, info
+
+
+def _deband(call, percentile, window, sigma, location, scale):
+    """One nl_*deband_* call through `call(<parameters from percentile on>)`: the dict of nl_deband_t."""
+    info = capi.Deband()
+    capi.check(call(float(percentile), int(window), float(sigma), float(location), float(scale), C.byref(info)))
+    return {name: np.float32(getattr(info, name)) for name, _ in capi.Deband._fields_}
+
+
+def _deband_host(entry, frame, width, height, percentile, window, sigma, location, scale, device):
+    out = np.array(frame, dtype=np.float32, copy=True).reshape(-1)
+    assert out.size == int(width) * int(height)
+    info = _deband(lambda *a: entry(capi.fptr(out), int(width), int(height), *a, 0 if device is None else int(device)),
+                   percentile, window, sigma, location, scale)
+    return out, info
+
+
+def deband_horiz(frame, width, height, percentile=50.0, window=128, sigma=3.0, location=0.0, scale=0.0, device=None):
+    """OpDebandHoriz (internal/ops/pre/banding.go:61-132) on one host frame on `device` (default 0): every row is
+    scaled so that its percentile (over the samples <= location + sigma * scale; sigma 0: all finite ones) meets the
+    median of the percentiles in a window of rows.  location / scale: the frame's Stats.Location() / Scale().
+    Returns (out, info): info the dict of nl_deband_t (threshold, lowest, highest); under the operator's own guards
+    out is the frame unchanged and info (threshold, 1, 0)."""
+    return _deband_host(capi.load().nl_deband_horiz, frame, width, height, percentile, window, sigma, location, scale,
+                        device)
+
+
+def deband_vert(frame, width, height, percentile=50.0, window=128, sigma=3.0, location=0.0, scale=0.0, device=None):
+    """OpDebandVert (internal/ops/pre/banding.go:197-270): deband_horiz over columns."""
+    return _deband_host(capi.load().nl_deband_vert, frame, width, height, percentile, window, sigma, location, scale,
+                        device)
+
+
+def bin_shape(width, height, n):
+    """The (width, height) OpBin gives a frame: (width // n, height // n), unchanged for n <= 1 (host only)."""
+    w, h = C.c_int(0), C.c_int(0)
+    capi.check(capi.load().nl_bin_shape(int(width), int(height), int(n), C.byref(w), C.byref(h)))
+    return int(w.value), int(h.value)
+
+
+def bin_nxn(frame, width, height, n, device=None):
+    """fits.NewImageBinNxN (internal/fits/fits.go:163-195) of one host frame on `device` (default 0); n <= 1 copies.
+    Returns (out, out_width, out_height)."""
+    frame = np.ascontiguousarray(frame, dtype=np.float32).reshape(-1)
+    assert frame.size == int(width) * int(height)
+    ow, oh = bin_shape(width, height, n)
+    out = np.empty(ow * oh, np.float32)
+    capi.check(capi.load().nl_bin_nxn(capi.fptr(frame), int(width), int(height), int(n), capi.fptr(out),
+                                      0 if device is None else int(device)))
+    return out, ow, oh
 
 
 def _cstr(s):
