@@ -42,6 +42,31 @@ var Devices []int
 // runs under runtime.LockOSThread (see Apply).
 func lastError() error { return errors.New(C.GoString(C.nl_last_error())) }
 
+// ProjectFrom is the f.Project call of OpAlign.Apply (internal/ops/post/postprocess.go:185) for a frame that is
+// resident on the device: slot srcIdx of the whole-image staging handle src, resampled through the forward
+// transform {A,B,C,D,E,F} into slot dstIdx of the stack handle dst (any row tile).  The handles are the
+// *C.nl_stack_t of nl_stack_create as unsafe.Pointer.  The source slot stays as it is and may be overwritten on return.
+func ProjectFrom(dst unsafe.Pointer, dstIdx int, src unsafe.Pointer, srcIdx int, trans [6]float32, outOfBounds float32) error {
+	runtime.LockOSThread() // nl_last_error() is per OS thread
+	defer runtime.UnlockOSThread()
+	if rc := C.nl_stack_frame_project_from((*C.nl_stack_t)(dst), C.int(dstIdx), (*C.nl_stack_t)(src), C.int(srcIdx),
+		(*C.float)(unsafe.Pointer(&trans[0])), C.float(outOfBounds)); rc != C.NL_OK {
+		return lastError()
+	}
+	return nil
+}
+
+// GroupProjectFrom is ProjectFrom into slot idx of every tile of a group (*C.nl_group_t): each tile projects its own rows.
+func GroupProjectFrom(g unsafe.Pointer, idx int, src unsafe.Pointer, srcIdx int, trans [6]float32, outOfBounds float32) error {
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	if rc := C.nl_group_frame_project_from((*C.nl_group_t)(g), C.int(idx), (*C.nl_stack_t)(src), C.int(srcIdx),
+		(*C.float)(unsafe.Pointer(&trans[0])), C.float(outOfBounds)); rc != C.NL_OK {
+		return lastError()
+	}
+	return nil
+}
+
 // Apply stacks a set of light frames on the GPUs.  Same contract as
 // internal/ops/stack/stack.go:115-227: mode validation and auto selection,
 // weights from getWeights (kept in Go, stack.go:231-270), one result image with

@@ -635,6 +635,32 @@ int nl_bin_nxn(const float *in_host, int width, int height, int n, float *out_ho
  * a shape mismatch and a destination whose frames are attached, not owned, fail with NL_ERR_INVALID_ARG. */
 int nl_stack_frame_bin_from(nl_stack_t *dst, int dst_idx, nl_stack_t *src, int src_idx, int n);
 
+/* ---- OpAlign's projection from a resident frame (internal/ops/post/postprocess.go:185) ----
+ * OpAlign's f.Project (post/postprocess.go:185, fits/project.go:26-76) from a resident frame:
+ * slot src_idx of the whole-image handle src, resampled through trans into slot dst_idx of dst
+ * (any row tile: only dst's rows are produced).  out_of_bounds as OpAlign chooses it
+ * (NaN / reference location / own location).  No multiplier/offset: MatchHistogram precedes
+ * Align in the reference, so call nl_stack_frame_affine on the source slot first.
+ * trans is the forward Transform2D, inverted as for nl_stack_upload_frame_projected (a singular one fails with
+ * "Matrix has no inverse"); the result is bit-identical to that call's on the same source (another kernel, the same arithmetic).  Synchronous: on return
+ * the source slot may be overwritten.  The source stays as it is.  NL_ERR_INVALID_ARG: a row-tile source, handles
+ * on different devices (nl_stack_ form), the same slot of the same handle (a projection cannot run in place), a
+ * destination whose frames are attached, not owned, a null trans, an index out of range.
+ * The group form fans out over the tiles: a tile on the source's device projects straight from the source slot, a
+ * tile on another device first receives the source rows it can tap by a peer-to-peer copy into its ingest buffer.
+ * Nothing goes through host memory. */
+int nl_stack_frame_project_from(nl_stack_t *dst, int dst_idx, nl_stack_t *src, int src_idx,
+                                const float trans[6], float out_of_bounds);
+int nl_group_frame_project_from(nl_group_t *g, int idx, nl_stack_t *src, int src_idx,
+                                const float trans[6], float out_of_bounds);
+/* Developer query: of the workgroup tiles that nl_stack_frame_project_from(dst, ., src, src_idx, trans, .) launches, how
+ * many stage their source box in LDS and how many take their taps from global memory.  Host
+ * arithmetic only, the kernel's own.  Developer switches of nl_stack_set_dev_flags on dst, for A/B runs (the results
+ * are the same either way): bit 15 (32768) = no tile stages, bit 16 (65536) = plain instead of nontemporal result
+ * stores; they hold for the resident projections into dst.  No counterpart in the reference. */
+int nl_stack_project_tile_paths(nl_stack_t *dst, nl_stack_t *src, int src_idx, const float trans[6],
+                                int64_t *staged, int64_t *direct);
+
 /* ---- host-side operator mirror (nightlight_amd/host/, C++) ----
  * The reference's stack operator decoded from its JSON form and run through
  * MakePromises/Apply exactly as OpSequence would drive it

@@ -59,6 +59,7 @@ EXPORTS = [
     "nl_back_extract", "nl_stack_frame_back_extract",
     "nl_deband_horiz", "nl_deband_vert", "nl_stack_frame_deband_horiz", "nl_stack_frame_deband_vert",
     "nl_bin_shape", "nl_bin_nxn", "nl_stack_frame_bin_from",
+    "nl_stack_frame_project_from", "nl_group_frame_project_from", "nl_stack_project_tile_paths",
 ]
 
 # nl_star_t = star.Star (findstars.go:30-37), 24 bytes
@@ -266,6 +267,9 @@ def open_library(path):
     L.nl_bin_shape.argtypes = [C.c_int, C.c_int, C.c_int, _intp, _intp]
     L.nl_bin_nxn.argtypes = [_f32p, C.c_int, C.c_int, C.c_int, _f32p, C.c_int]
     L.nl_stack_frame_bin_from.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int]
+    L.nl_stack_frame_project_from.argtypes = [vp, C.c_int, vp, C.c_int, _f32p, C.c_float]
+    L.nl_group_frame_project_from.argtypes = [vp, C.c_int, vp, C.c_int, _f32p, C.c_float]
+    L.nl_stack_project_tile_paths.argtypes = [vp, vp, C.c_int, _f32p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     return L
 
 

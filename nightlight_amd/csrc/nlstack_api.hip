@@ -382,6 +382,28 @@ int nl::select_device(int device)
     return NL_OK;
 }
 
+namespace nl {
+
+// internal/star/coord.go:159-199, fp32 as written there
+int invert_transform(const float t[6], float inv[6])
+{
+    const volatile float bd = t[1] * t[3], ae = t[0] * t[4];
+    const float eps = bd - ae;
+    if (eps < 1e-8f && -eps < 1e-8f) return fail(NL_ERR_INVALID_ARG, "Matrix has no inverse, epsilon=%g", eps);
+    const volatile float den1 = bd - ae, den2 = ae - bd;
+    const volatile float ce = t[2] * t[4], bf = t[1] * t[5], cd = t[2] * t[3], af = t[0] * t[5];
+    const volatile float n1 = ce - bf, n2 = cd - af;
+    inv[0] = -t[4] / den1;
+    inv[1] = t[1] / den1;
+    inv[2] = n1 / den1;
+    inv[3] = -t[3] / den2;
+    inv[4] = t[0] / den2;
+    inv[5] = n2 / den2;
+    return NL_OK;
+}
+
+}  // namespace nl
+
 extern "C" {
 
 const char *nl_last_error(void) { return g_err.c_str(); }
@@ -799,24 +821,6 @@ static int decode_stats(nl_stack_t *h, int64_t n, float *stats_out)
     stats_out[0] = lo;
     stats_out[1] = hi;
     stats_out[2] = (float)(sum / (double)n);
-    return NL_OK;
-}
-
-// internal/star/coord.go:159-199, fp32 as written there
-static int invert_transform(const float t[6], float inv[6])
-{
-    const volatile float bd = t[1] * t[3], ae = t[0] * t[4];
-    const float eps = bd - ae;
-    if (eps < 1e-8f && -eps < 1e-8f) return fail(NL_ERR_INVALID_ARG, "Matrix has no inverse, epsilon=%g", eps);
-    const volatile float den1 = bd - ae, den2 = ae - bd;
-    const volatile float ce = t[2] * t[4], bf = t[1] * t[5], cd = t[2] * t[3], af = t[0] * t[5];
-    const volatile float n1 = ce - bf, n2 = cd - af;
-    inv[0] = -t[4] / den1;
-    inv[1] = t[1] / den1;
-    inv[2] = n1 / den1;
-    inv[3] = -t[3] / den2;
-    inv[4] = t[0] / den2;
-    inv[5] = n2 / den2;
     return NL_OK;
 }
 

@@ -626,6 +626,121 @@ int nl_stack_frame_bin_from(nl_stack_t *dst, int dst_idx, nl_stack_t *src, int s
     return NL_OK;
 }
 
+// ---- OpAlign's f.Project from a resident frame (post/postprocess.go:185, fits/project.go:26-76; kernel in project.hip) ----
+
+}  // extern "C"
+
+namespace {
+
+// the checks both forms share; *s = the source slot, *d = the destination slot, inv = the inverse transform
+int project_from_check(const char *who, nl_stack_t *dst, int dst_idx, nl_stack_t *src, int src_idx, const float *trans,
+                       const float **s, float **d, float inv[6])
+{
+    char part[96];
+    snprintf(part, sizeof part, "%s (source)", who);
+    *s = frame_or_fail(src, src_idx, part);
+    if (!*s) return NL_ERR_INVALID_ARG;
+    snprintf(part, sizeof part, "%s (destination)", who);
+    *d = frame_or_fail(dst, dst_idx, part);
+    if (!*d) return NL_ERR_INVALID_ARG;
+    if (!trans) return fail(NL_ERR_INVALID_ARG, "%s: null transform", who);
+    snprintf(part, sizeof part, "%s (source)", who);
+    int rc = need_whole_image(src, part, "a projection reads any row of the source");
+    if (rc == NL_OK) rc = need_int32_pixels(src->npix, who, "source frame");
+    if (rc == NL_OK) rc = need_int32_pixels(dst->npix, who, "destination tile");
+    if (rc != NL_OK) return rc;
+    if (dst->d_frames != dst->d_frames_owned)
+        return fail(NL_ERR_INVALID_ARG, "%s: the destination's frames are attached, not owned", who);
+    if (*s == *d) return fail(NL_ERR_INVALID_ARG, "%s: slot %d of one handle is source and destination (a projection cannot run in place)", who, src_idx);
+    return invert_transform(trans, inv);
+}
+
+// the source rows [*y0, *y1] that the destination rows of dst can tap (project.hpp: the corners of a rectangle bound
+// every pixel's coordinates); false: none
+bool project_source_rows(const nl_stack_t *dst, const nl_stack_t *src, const float inv[6], int *y0, int *y1)
+{
+    const nl::ProjInv t = {inv[0], inv[1], inv[2], inv[3], inv[4], inv[5]};
+    const float px[2] = {0.0f, (float)(dst->width - 1)}, py[2] = {(float)dst->row0, (float)(dst->row0 + dst->rows - 1)};
+    float lo = INFINITY, hi = -INFINITY;
+    for (int i = 0; i < 4; i++) {
+        const float y = nl::proj_y(t, px[i & 1], py[i >> 1]);
+        if (y != y || !isfinite(inv[3]) || !isfinite(inv[4]) || !isfinite(inv[5])) { lo = -INFINITY; hi = INFINITY; break; }
+        lo = fminf(lo, y);
+        hi = fmaxf(hi, y);
+    }
+    *y0 = std::max(nl::proj_floor_clamped(lo), 0);
+    *y1 = std::min(nl::proj_floor_clamped(hi) + 1, src->height - 1);
+    return *y0 <= *y1;
+}
+
+}  // namespace
+
+// everything enqueued on the handle so far has finished (the group settles the source once, before its tiles' threads)
+int nl::stack_settle(nl_stack_t *h)
+{
+    NL_CHECK_HANDLE(h);
+    NL_SETTLE_UPLOADS(h);
+    NL_HIP(hipStreamSynchronize(h->stream));
+    return NL_OK;
+}
+
+// Both C-ABI forms.  The group's (from_group): the source is settled and is only read here, since the tiles run on
+// threads of their own; a destination on another device than the source first receives the source rows it can tap,
+// peer to peer, at their place in its ingest buffer.
+int nl::stack_project_from(nl_stack_t *dst, int dst_idx, nl_stack_t *src, int src_idx, const float trans[6],
+                           float out_of_bounds, const char *who, bool from_group)
+{
+    NL_CHECK_HANDLE(src);
+    NL_CHECK_HANDLE(dst);
+    if (src->device != dst->device && !from_group)
+        return fail(NL_ERR_INVALID_ARG, "%s: source on device %d, destination on device %d", who, src->device, dst->device);
+    if (!from_group) NL_SETTLE_UPLOADS(src);
+    NL_SETTLE_UPLOADS(dst);
+    const float *s = nullptr;
+    float *d = nullptr;
+    float inv[6];
+    int rc = project_from_check(who, dst, dst_idx, src, src_idx, trans, &s, &d, inv);
+    if (rc != NL_OK) return rc;
+    if (src != dst && !from_group && (rc = nl_stack_order_stream_after(src, dst->stream)) != NL_OK) return rc;
+    NL_HIP(hipSetDevice(dst->device));
+    if (src->device != dst->device) {
+        NL_HIP(dst->ingest.reserve((size_t)src->npix * sizeof(float), dst->stream));
+        int y0 = 0, y1 = 0;
+        if (project_source_rows(dst, src, inv, &y0, &y1)) {
+            const size_t at = (size_t)y0 * (size_t)src->width;
+            NL_HIP(hipMemcpyPeerAsync(static_cast<float *>(dst->ingest.ptr) + at, dst->device, s + at, src->device,
+                                      sizeof(float) * (size_t)(y1 - y0 + 1) * (size_t)src->width, dst->stream));
+        }
+        s = static_cast<const float *>(dst->ingest.ptr);
+    }
+    NL_HIP(nl::launch_project_tiled(s, src->width, src->height, d, dst->width, dst->row0, dst->rows, inv, out_of_bounds,
+                                    project_switches(dst), dst->stream));
+    NL_HIP(hipStreamSynchronize(dst->stream));                 // the caller may overwrite the source slot at once
+    return NL_OK;
+}
+
+extern "C" {
+
+int nl_stack_frame_project_from(nl_stack_t *dst, int dst_idx, nl_stack_t *src, int src_idx, const float trans[6],
+                                float out_of_bounds)
+{
+    return nl::stack_project_from(dst, dst_idx, src, src_idx, trans, out_of_bounds, "frame_project_from", false);
+}
+
+int nl_stack_project_tile_paths(nl_stack_t *dst, nl_stack_t *src, int src_idx, const float trans[6], int64_t *staged,
+                                int64_t *direct)
+{
+    if (!dst || !src || !trans || !staged || !direct) return fail(NL_ERR_INVALID_ARG, "project_tile_paths: null argument");
+    const float *s = frame_or_fail(src, src_idx, "project_tile_paths");
+    if (!s) return NL_ERR_INVALID_ARG;
+    float inv[6];
+    const int rc = invert_transform(trans, inv);
+    if (rc != NL_OK) return rc;
+    nl::project_tile_paths(s, src->width, src->height, dst->width, dst->row0, dst->rows, inv, project_switches(dst),
+                           staged, direct);
+    return NL_OK;
+}
+
 int nl_bin_nxn(const float *in_host, int width, int height, int n, float *out_host, int device)
 {
     if (!in_host || !out_host || width < 1 || height < 1) return fail(NL_ERR_INVALID_ARG, "bin_nxn: bad argument");

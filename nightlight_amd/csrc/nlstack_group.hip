@@ -152,6 +152,19 @@ int nl_group_upload_frame_projected(nl_group_t *g, int idx, const float *src_hos
     });
 }
 
+// OpAlign's f.Project on the group: every tile projects its own rows from the resident source slot -- straight from
+// it on the source's device, from a peer copy of the rows it needs on another one; nothing goes through host memory
+int nl_group_frame_project_from(nl_group_t *g, int idx, nl_stack_t *src, int src_idx, const float trans[6],
+                                float out_of_bounds)
+{
+    if (!g || !src) return NL_ERR_INVALID_ARG;
+    const int rc = nl::stack_settle(src);                  // once, here: the tiles' threads only read the source
+    if (rc != NL_OK) return rc;
+    return for_each_tile(g, [&](size_t t) {
+        return nl::stack_project_from(g->tiles[t], idx, src, src_idx, trans, out_of_bounds, "group_frame_project_from", true);
+    });
+}
+
 int nl_group_fill_synthetic(nl_group_t *g, uint64_t seed)
 {
     if (!g) return NL_ERR_INVALID_ARG;

@@ -11,6 +11,7 @@
 #include "background.hpp"
 #include "deband.hpp"
 #include "dev_memory.hpp"
+#include "project.hpp"
 #include "stars.hpp"
 #include "stack_kernels.h"
 
@@ -38,9 +39,13 @@ int with_scratch_handle(int width, int height, int device, Run run)
     return rc;
 }
 
+// the inverse of the forward Transform2D t (internal/star/coord.go:159-199, fp32 as written there); a singular one is
+// NL_ERR_INVALID_ARG "Matrix has no inverse" (nlstack_api.hip)
+int invert_transform(const float t[6], float inv[6]);
+
 }  // namespace nl
 
-using nl::cached_free, nl::cached_malloc, nl::dev_malloc, nl::fail, nl::g_err, nl::select_device, nl::with_scratch_handle;
+using nl::cached_free, nl::cached_malloc, nl::dev_malloc, nl::fail, nl::g_err, nl::invert_transform, nl::select_device, nl::with_scratch_handle;
 
 #define NL_HIP(call)                                                                        \
     do {                                                                                    \
@@ -173,6 +178,15 @@ struct nl_stack {
     bool pending = false;
     const char *last_kernel = "";
 };
+
+// developer switches of the projection (nl_stack_set_dev_flags; the others: nlstack_pass.hip) as launch_project takes them
+constexpr unsigned kDevProjectDirect = 32768u;       // no tile stages its source box in LDS
+constexpr unsigned kDevProjectPlainStores = 65536u;  // plain instead of nontemporal result stores
+inline unsigned project_switches(const nl_stack *h)
+{
+    return ((h->dev_flags & kDevProjectDirect) ? nl::kProjDirectOnly : 0u) |
+           ((h->dev_flags & kDevProjectPlainStores) ? nl::kProjPlainStores : 0u);
+}
 
 #define NL_CHECK_HANDLE(h)                                              \
     do {                                                                \

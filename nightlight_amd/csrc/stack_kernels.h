@@ -113,6 +113,10 @@ struct FastArgs {
 
 // sets what nl_last_error() returns on this thread (nlstack_api.hip)
 void set_last_error(const char *msg);
+// nl_stack_frame_project_from / nl_group_frame_project_from (nlstack_frame.hip); who = the call's name in messages
+int stack_project_from(nl_stack_t *dst, int dst_idx, nl_stack_t *src, int src_idx, const float trans[6],
+                       float out_of_bounds, const char *who, bool from_group);
+int stack_settle(nl_stack_t *h);
 
 // Bisection of the goal-seek (spec: internal/ops/stack/stackfindsigma.go:48-98): sigma_low and
 // sigma_high in [1,11], percentages in the reference's fp32 arithmetic, 21 passes at most.
@@ -306,7 +310,7 @@ hipError_t launch_axpy(float *acc, const float *x, float weight, int first, int6
                        hipStream_t stream);
 hipError_t launch_scale(float *acc, float factor, int64_t n, hipStream_t stream);
 
-// ---- ingest.hip (FITS payload decode / encode, MatchHistogram, Project) ----
+// ---- ingest.hip (FITS payload decode / encode, MatchHistogram, Project from a frame that was just uploaded) ----
 int fits_bytes_per_value(int bitpix);
 hipError_t launch_fits_decode(const void *raw, int bitpix, int64_t n, float bscale, float bzero, bool affine,
                               float mult, float off, float *out, double *partial /*[blocks][3]*/, int blocks,
@@ -316,6 +320,13 @@ hipError_t launch_affine(float *data, int64_t n, float mult, float off, hipStrea
 hipError_t launch_project(const float *src, int src_w, int src_h, float *dst, int dst_w, int row0, int rows,
                           const float inv[6], float oob, bool affine, float mult, float off,
                           hipStream_t stream);
+
+// ---- project.hip (Project from a resident frame; switches: kProjDirectOnly | kProjPlainStores of project.hpp) ----
+hipError_t launch_project_tiled(const float *src, int src_w, int src_h, float *dst, int dst_w, int row0, int rows,
+                                const float inv[6], float oob, unsigned switches, hipStream_t stream);
+// how many tiles of that launch stage their source box in LDS, how many tap global memory (host arithmetic, the kernel's own)
+void project_tile_paths(const float *src, int src_w, int src_h, int dst_w, int row0, int rows, const float inv[6],
+                        unsigned switches, int64_t *staged, int64_t *direct);
 
 // ---- synth.hip ----
 hipError_t launch_fill_synthetic(float *frames, int64_t stride, int n_frames, int width,

@@ -384,6 +384,23 @@ class StackHandle:
         shape is bin_shape of the source's (n <= 1: a device copy)."""
         capi.check(self._lib.nl_stack_frame_bin_from(self._h, int(idx), src._h, int(src_idx), int(n)))
 
+    def frame_project_from(self, idx, src, src_idx, trans, out_of_bounds=float("nan")):
+        """OpAlign's Project of resident slot src_idx of the whole-image handle `src` through the forward transform
+        `trans` into slot idx of this handle (any row tile).  Bit-identical to upload_frame_projected of the same
+        source; the source slot stays as it is."""
+        t = np.ascontiguousarray(trans, dtype=np.float32).reshape(6)
+        capi.check(self._lib.nl_stack_frame_project_from(self._h, int(idx), src._h, int(src_idx), capi.fptr(t),
+                                                         float(out_of_bounds)))
+
+    def project_tile_paths(self, src, src_idx, trans):
+        """(staged, direct): how many workgroup tiles of frame_project_from(., src, src_idx, trans) stage their source
+        box in LDS, and how many take their taps from global memory (developer query)."""
+        t = np.ascontiguousarray(trans, dtype=np.float32).reshape(6)
+        staged, direct = C.c_int64(0), C.c_int64(0)
+        capi.check(self._lib.nl_stack_project_tile_paths(self._h, src._h, int(src_idx), capi.fptr(t),
+                                                         C.byref(staged), C.byref(direct)))
+        return int(staged.value), int(direct.value)
+
     def download_result_fits(self):
         raw = np.empty(self.tile_pixels * 4, np.uint8)
         capi.check(self._lib.nl_stack_download_result_fits(self._h, raw.ctypes.data_as(C.c_void_p)))
@@ -451,6 +468,12 @@ class StackGroup:
         capi.check(self._lib.nl_group_upload_frame_projected(
             self._g, int(idx), capi.fptr(src), int(src_w), int(src_h), capi.fptr(t), float(out_of_bounds),
             float(multiplier), float(offset)))
+
+    def frame_project_from(self, idx, src, src_idx, trans, out_of_bounds=float("nan")):
+        """StackHandle.frame_project_from on the group: every tile projects its own rows from the resident slot."""
+        t = np.ascontiguousarray(trans, dtype=np.float32).reshape(6)
+        capi.check(self._lib.nl_group_frame_project_from(self._g, int(idx), src._h, int(src_idx), capi.fptr(t),
+                                                         float(out_of_bounds)))
 
     def fill_synthetic(self, seed=0x4E4C5354):
         capi.check(self._lib.nl_group_fill_synthetic(self._g, C.c_uint64(seed)))
