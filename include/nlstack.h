@@ -661,6 +661,59 @@ int nl_group_frame_project_from(nl_group_t *g, int idx, nl_stack_t *src, int src
 int nl_stack_project_tile_paths(nl_stack_t *dst, nl_stack_t *src, int src_idx, const float trans[6],
                                 int64_t *staged, int64_t *direct);
 
+/* ---- OpGaussianBlur / OpUnsharpMask / OpHSLUnsharpMask's UnsharpMask ----
+ * (internal/ops/stretch/stretch.go:339-424, internal/ops/stretch/usm.go, internal/ops/hsl/hsl.go:538-551)
+ * The two passes of GaussFilter2D (usm.go:118-122): Convolve1DX (usm.go:85-98) into a scratch frame of the
+ * handle, Convolve1DY (usm.go:101-114) back, every output sum = 0, then sum = sum + data[reflect(. + i)] *
+ * kernel[i + k] for i = -k .. k in fp32, one multiply and one add each; the unsharp mask adds
+ * ApplyUnsharpMask (usm.go:134-149) to the second pass: d < abs_threshold copies d, else
+ * r = d + (d - blurred) * gain, then r < min, then r > max, in that order (NaN falls through every test).
+ * Bit-exact given the taps.  One reservation for the sigma forms: their taps go through the C library's
+ * fp64 erf, which may differ from Go's math.Erf in the last place, so a tap may differ by one fp32 ulp from
+ * the Go binary's; everything after the taps is bit-exact, and nl_convolve_separable has no reservation.
+ * min, max and abs_threshold are the caller's scalars (OpUnsharpMask: f.Stats.Min(), f.Stats.Max(),
+ * Location() + Scale() * Threshold; OpHSLUnsharpMask: the luminance plane's), as location / scale are for
+ * nl_find_stars.  The operators' own guards -- sigma == 0 in the blur and unsharp-mask entries, gain == 0 in
+ * the unsharp-mask entries (stretch.go:369, :414) -- are no-ops: NL_OK, every bit unchanged (the host
+ * unsharp mask copies in to out).
+ * Deviations, all NL_ERR_INVALID_ARG with a message naming the site:
+ *   1. a sigma GaussianKernel1D cannot handle: NaN, negative or +Inf (its radius search never ends; the
+ *      search here stops at a radius of 65536, more than any frame of < 2^31 pixels holds), one below the
+ *      value at which the radius comes out -1 (about 0.215: make with a negative length panics), and
+ *      sigma == 0 in nl_gaussian_kernel_1d itself.
+ *   2. a radius above width or above height: one reflect (usm.go:25-33) leaves the range, the reference
+ *      reads a neighbouring row or panics.
+ *   3. an even or non-positive n_taps in nl_convolve_separable: the reference indexes past the kernel.
+ *   4. a capacity below the tap count in nl_gaussian_kernel_1d (*n_taps_out still receives the count).
+ *   5. a row-tile handle: the column pass needs every row (like nl_stack_frame_deband_horiz).
+ *   6. the result forms on a handle that has not run a pass (like nl_stack_result_find_stars).
+ *
+ * GaussianKernel1D (usm.go:41-82): erf in fp64 on float64((x - mu) / (sqrt2 * sigma)), everything else in
+ * fp32; the left half summed, the right half mirrored, every tap times 1.0 / sum.  Host only, needs no
+ * device.  taps_out may be NULL with capacity 0 to ask for the count. */
+int nl_gaussian_kernel_1d(float sigma, float *taps_out, int capacity, int *n_taps_out);
+/* Convolve1DX then Convolve1DY (usm.go:85-114) of one host frame with the caller's n_taps taps, in place.
+ * The host forms run on handles of their own per call: safe to call from several host threads at once. */
+int nl_convolve_separable(float *data_host, int width, int height, const float *taps, int n_taps, int device);
+/* GaussianBlur (usm.go:126-130) of one host frame, in place. */
+int nl_gaussian_blur(float *data_host, int width, int height, float sigma, int device);
+/* UnsharpMask (usm.go:153-159) of one host frame into out_host (which may be in_host). */
+int nl_unsharp_mask(const float *in_host, float *out_host, int width, int height, float sigma, float gain,
+                    float min, float max, float abs_threshold, int device);
+/* The same on resident slot idx of a whole-image handle, in place: only the taps cross PCIe. */
+int nl_stack_frame_gaussian_blur(nl_stack_t *h, int idx, float sigma);
+int nl_stack_frame_unsharp_mask(nl_stack_t *h, int idx, float sigma, float gain, float min, float max,
+                                float abs_threshold);
+/* ... and on the last pass's result still on the device, in place (nl_stack_finish / a download after it
+ * returns the filtered result). */
+int nl_stack_result_gaussian_blur(nl_stack_t *h, float sigma);
+int nl_stack_result_unsharp_mask(nl_stack_t *h, float sigma, float gain, float min, float max,
+                                 float abs_threshold);
+/* Developer query: whether the row pass and the column pass of a kernel of n_taps taps stage their source
+ * tile in LDS (1) or take every tap from global memory (0).  Host arithmetic only,
+ * the launcher's own; the results are the same either way.  No counterpart in the reference. */
+int nl_blur_tap_paths(int n_taps, int *row_staged, int *col_staged);
+
 /* ---- host-side operator mirror (nightlight_amd/host/, C++) ----
  * The reference's stack operator decoded from its JSON form and run through
  * MakePromises/Apply exactly as OpSequence would drive it

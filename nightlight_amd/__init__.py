@@ -8,9 +8,9 @@ from . import capi  # noqa: F401
 from .capi import (NlError, ST_AUTO, ST_LINEAR_FIT, ST_MAD_SIGMA, ST_MEAN, ST_MEDIAN,  # noqa: F401
                    ST_SIGMA, ST_WINSOR_SIGMA, WEIGHT_EXPOSURE, WEIGHT_INVERSE_HFR,
                    WEIGHT_INVERSE_NOISE, WEIGHT_NONE, device_count)
-from .stack import (Calibration, StackGroup, StackHandle, back_extract, bin_nxn, bin_shape, debayer_shape,  # noqa: F401
-                    deband_horiz, deband_vert, find_stars, fits_padded_bytes, fits_parse_header, fits_write_header,
-                    median_filter_3x3, median_filter_mask, preprocess_frame, preprocess_frame_cfa,
-                    weights_from_scalars)
+from .stack import (Calibration, StackGroup, StackHandle, back_extract, bin_nxn, bin_shape, blur_tap_paths,  # noqa: F401
+                    convolve_separable, debayer_shape, deband_horiz, deband_vert, find_stars, fits_padded_bytes,
+                    fits_parse_header, fits_write_header, gaussian_blur, gaussian_kernel_1d, median_filter_3x3,
+                    median_filter_mask, preprocess_frame, preprocess_frame_cfa, unsharp_mask, weights_from_scalars)
 
 __version__ = "0.2.0"

@@ -59,6 +59,9 @@ EXPORTS = [
     "nl_back_extract", "nl_stack_frame_back_extract",
     "nl_deband_horiz", "nl_deband_vert", "nl_stack_frame_deband_horiz", "nl_stack_frame_deband_vert",
     "nl_bin_shape", "nl_bin_nxn", "nl_stack_frame_bin_from",
+    "nl_gaussian_kernel_1d", "nl_convolve_separable", "nl_gaussian_blur", "nl_unsharp_mask",
+    "nl_stack_frame_gaussian_blur", "nl_stack_frame_unsharp_mask", "nl_stack_result_gaussian_blur",
+    "nl_stack_result_unsharp_mask", "nl_blur_tap_paths",
     "nl_stack_frame_project_from", "nl_group_frame_project_from", "nl_stack_project_tile_paths",
 ]
 
@@ -267,6 +270,16 @@ def open_library(path):
     L.nl_bin_shape.argtypes = [C.c_int, C.c_int, C.c_int, _intp, _intp]
     L.nl_bin_nxn.argtypes = [_f32p, C.c_int, C.c_int, C.c_int, _f32p, C.c_int]
     L.nl_stack_frame_bin_from.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int]
+    _usm_args = [C.c_float] * 5                          # sigma, gain, min, max, abs_threshold
+    L.nl_gaussian_kernel_1d.argtypes = [C.c_float, _f32p, C.c_int, _intp]
+    L.nl_convolve_separable.argtypes = [_f32p, C.c_int, C.c_int, _f32p, C.c_int, C.c_int]
+    L.nl_gaussian_blur.argtypes = [_f32p, C.c_int, C.c_int, C.c_float, C.c_int]
+    L.nl_unsharp_mask.argtypes = [_f32p, _f32p, C.c_int, C.c_int] + _usm_args + [C.c_int]
+    L.nl_stack_frame_gaussian_blur.argtypes = [vp, C.c_int, C.c_float]
+    L.nl_stack_frame_unsharp_mask.argtypes = [vp, C.c_int] + _usm_args
+    L.nl_stack_result_gaussian_blur.argtypes = [vp, C.c_float]
+    L.nl_stack_result_unsharp_mask.argtypes = [vp] + _usm_args
+    L.nl_blur_tap_paths.argtypes = [C.c_int, _intp, _intp]
     L.nl_stack_frame_project_from.argtypes = [vp, C.c_int, vp, C.c_int, _f32p, C.c_float]
     L.nl_group_frame_project_from.argtypes = [vp, C.c_int, vp, C.c_int, _f32p, C.c_float]
     L.nl_stack_project_tile_paths.argtypes = [vp, vp, C.c_int, _f32p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]

@@ -1,6 +1,7 @@
 // nlstack_frame.hip -- steps on one frame resident in a handle, and their host forms: statistics and noise,
-// median filters, OpCalibrate / OpBadPixel, star detection, background extraction, debanding and binning, the
-// colour-camera front.  Kernels in frame_stats.hip, preprocess.hip, stars.hip, background.hip, deband.hip and bayer.hip.
+// median filters, OpCalibrate / OpBadPixel, star detection, background extraction, debanding and binning, Gaussian blur
+// and unsharp mask, the colour-camera front.  Kernels in frame_stats.hip, preprocess.hip, stars.hip, background.hip,
+// deband.hip, blur.hip and bayer.hip.
 #include <float.h>
 #include <math.h>
 
@@ -624,6 +625,157 @@ int nl_stack_frame_bin_from(nl_stack_t *dst, int dst_idx, nl_stack_t *src, int s
         NL_HIP(hipMemcpyAsync(d, s, sizeof(float) * (size_t)src->npix, hipMemcpyDeviceToDevice, dst->stream));
     NL_HIP(hipStreamSynchronize(dst->stream));
     return NL_OK;
+}
+
+// ---- OpGaussianBlur / OpUnsharpMask (internal/ops/stretch/stretch.go:339-424, usm.go; kernels in blur.hip) ---------
+
+int nl_gaussian_kernel_1d(float sigma, float *taps_out, int capacity, int *n_taps_out)
+{
+    if (capacity < 0 || (capacity > 0 && !taps_out))
+        return fail(NL_ERR_INVALID_ARG, "gaussian_kernel_1d: capacity %d with %s output", capacity, taps_out ? "an" : "no");
+    std::vector<float> taps;
+    std::string msg;
+    const int rc = nl::gaussian_kernel_1d(sigma, taps, &msg);
+    if (rc != NL_OK) return fail(rc, "gaussian_kernel_1d: %s", msg.c_str());
+    if (n_taps_out) *n_taps_out = (int)taps.size();
+    if ((size_t)capacity < taps.size())
+        return fail(NL_ERR_INVALID_ARG, "gaussian_kernel_1d: sigma %g gives %zu taps, capacity %d", sigma, taps.size(), capacity);
+    memcpy(taps_out, taps.data(), sizeof(float) * taps.size());
+    return NL_OK;
+}
+
+int nl_blur_tap_paths(int n_taps, int *row_staged, int *col_staged)
+{
+    if (n_taps < 1 || n_taps % 2 == 0 || !row_staged || !col_staged)
+        return fail(NL_ERR_INVALID_ARG, "blur_tap_paths: bad argument");
+    *row_staged = n_taps / 2 <= nl::kBlurRowStagedRadius;
+    *col_staged = n_taps / 2 <= nl::kBlurColStagedRadius;
+    return NL_OK;
+}
+
+// what every sigma form decides before it touches a device: the operator's own guard (*noop), else the taps of sigma
+static int blur_taps(const char *who, float sigma, const nl::UsmParams *usm, std::vector<float> &taps, bool *noop)
+{
+    *noop = sigma == 0.0f || (usm && usm->gain == 0.0f);      // stretch.go:369, :414
+    if (*noop) return NL_OK;
+    std::string msg;
+    const int rc = nl::gaussian_kernel_1d(sigma, taps, &msg);
+    if (rc != NL_OK) return fail(rc, "%s: %s", who, msg.c_str());
+    return NL_OK;
+}
+
+// deviations 2 and 3, before any device work
+static int blur_check_taps(const char *who, const float *taps, int n_taps, int width, int height)
+{
+    if (!taps || n_taps < 1 || n_taps % 2 == 0)
+        return fail(NL_ERR_INVALID_ARG, "%s: %d taps: Convolve1DX / Convolve1DY (usm.go:85-114) index kernel[i + k] for "
+                    "i = -k .. k, an odd positive count", who, n_taps);
+    if (n_taps / 2 > width || n_taps / 2 > height)
+        return fail(NL_ERR_INVALID_ARG, "%s: a radius of %d on a %dx%d frame: one reflect (usm.go:25-33) leaves the range",
+                    who, n_taps / 2, width, height);
+    return NL_OK;
+}
+
+// the two passes on a frame or result resident in h, in place
+static int blur_impl(nl_stack_t *h, float *d_data, const char *who, const float *taps, int n_taps,
+                     const nl::UsmParams *usm)
+{
+    int pre = need_whole_image(h, who, "the column pass needs every row");
+    if (pre == NL_OK) pre = need_int32_pixels(h->npix, who);
+    if (pre == NL_OK) pre = blur_check_taps(who, taps, n_taps, h->width, h->height);
+    if (pre != NL_OK) return pre;
+    std::string msg;
+    const int rc = nl::blur_run(d_data, h->width, h->height, taps, n_taps, usm, h->frame_scratch.blur_work, h->stream, &msg);
+    return rc == NL_OK ? NL_OK : fail(rc, "%s: %s", who, msg.c_str());
+}
+
+// the resident sigma forms: idx >= 0 a frame slot, idx < 0 the last pass's result
+static int resident_blur(nl_stack_t *h, int idx, const char *who, float sigma, const nl::UsmParams *usm)
+{
+    NL_CHECK_HANDLE(h);
+    float *d = h->d_out;
+    if (idx >= 0) {
+        NL_SETTLE_UPLOADS(h);
+        if (!(d = frame_or_fail(h, idx, who))) return NL_ERR_INVALID_ARG;
+    } else if (h->last_mode < 0) {
+        return fail(NL_ERR_INVALID_ARG, "%s: the handle has not run a pass", who);
+    }
+    std::vector<float> taps;
+    bool noop;
+    const int rc = blur_taps(who, sigma, usm, taps, &noop);
+    if (rc != NL_OK || noop) return rc;
+    return blur_impl(h, d, who, taps.data(), (int)taps.size(), usm);
+}
+
+int nl_stack_frame_gaussian_blur(nl_stack_t *h, int idx, float sigma)
+{
+    if (h && idx < 0) return fail(NL_ERR_INVALID_ARG, "frame_gaussian_blur: bad index %d", idx);
+    return resident_blur(h, idx, "frame_gaussian_blur", sigma, nullptr);
+}
+
+int nl_stack_frame_unsharp_mask(nl_stack_t *h, int idx, float sigma, float gain, float min, float max,
+                                float abs_threshold)
+{
+    if (h && idx < 0) return fail(NL_ERR_INVALID_ARG, "frame_unsharp_mask: bad index %d", idx);
+    const nl::UsmParams p{gain, min, max, abs_threshold};
+    return resident_blur(h, idx, "frame_unsharp_mask", sigma, &p);
+}
+
+int nl_stack_result_gaussian_blur(nl_stack_t *h, float sigma)
+{
+    return resident_blur(h, -1, "result_gaussian_blur", sigma, nullptr);
+}
+
+int nl_stack_result_unsharp_mask(nl_stack_t *h, float sigma, float gain, float min, float max, float abs_threshold)
+{
+    const nl::UsmParams p{gain, min, max, abs_threshold};
+    return resident_blur(h, -1, "result_unsharp_mask", sigma, &p);
+}
+
+// the host forms: the frame up, the two passes on a handle of the call's own, the frame down into out_host
+static int host_blur(const char *who, const float *in_host, float *out_host, int width, int height, const float *taps,
+                     int n_taps, const nl::UsmParams *usm, int device)
+{
+    int rc = blur_check_taps(who, taps, n_taps, width, height);
+    if (rc == NL_OK) rc = select_device(device);
+    if (rc != NL_OK) return rc;
+    return with_scratch_handle(width, height, device, [&](nl_stack_t *h) {
+        int r = nl_stack_upload_tile(h, 0, in_host);
+        if (r == NL_OK) r = blur_impl(h, h->d_frames, who, taps, n_taps, usm);
+        return r == NL_OK ? nl_stack_download_tile(h, 0, out_host) : r;
+    });
+}
+
+int nl_convolve_separable(float *data_host, int width, int height, const float *taps, int n_taps, int device)
+{
+    if (!data_host || width < 1 || height < 1) return fail(NL_ERR_INVALID_ARG, "convolve_separable: bad argument");
+    return host_blur("convolve_separable", data_host, data_host, width, height, taps, n_taps, nullptr, device);
+}
+
+int nl_gaussian_blur(float *data_host, int width, int height, float sigma, int device)
+{
+    if (!data_host || width < 1 || height < 1) return fail(NL_ERR_INVALID_ARG, "gaussian_blur: bad argument");
+    std::vector<float> taps;
+    bool noop;
+    const int rc = blur_taps("gaussian_blur", sigma, nullptr, taps, &noop);
+    if (rc != NL_OK || noop) return rc;
+    return host_blur("gaussian_blur", data_host, data_host, width, height, taps.data(), (int)taps.size(), nullptr, device);
+}
+
+int nl_unsharp_mask(const float *in_host, float *out_host, int width, int height, float sigma, float gain, float min,
+                    float max, float abs_threshold, int device)
+{
+    if (!in_host || !out_host || width < 1 || height < 1) return fail(NL_ERR_INVALID_ARG, "unsharp_mask: bad argument");
+    const nl::UsmParams p{gain, min, max, abs_threshold};
+    std::vector<float> taps;
+    bool noop;
+    const int rc = blur_taps("unsharp_mask", sigma, &p, taps, &noop);
+    if (rc != NL_OK) return rc;
+    if (noop) {
+        if (out_host != in_host) memmove(out_host, in_host, sizeof(float) * (size_t)width * height);
+        return NL_OK;
+    }
+    return host_blur("unsharp_mask", in_host, out_host, width, height, taps.data(), (int)taps.size(), &p, device);
 }
 
 // ---- OpAlign's f.Project from a resident frame (post/postprocess.go:185, fits/project.go:26-76; kernel in project.hip) ----

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "background.hpp"
+#include "blur.hpp"
 #include "deband.hpp"
 #include "dev_memory.hpp"
 #include "project.hpp"
@@ -156,10 +157,12 @@ struct nl_stack {
         nl::BackWork back_work;
         // debanding (nl_stack_frame_deband_horiz / _vert)
         nl::DebandWork deband_work;
+        // Gaussian blur / unsharp mask (nl_stack_frame_gaussian_blur, nl_stack_result_unsharp_mask, ...)
+        nl::BlurWork blur_work;
         size_t bytes() const
         {
             return bp_diff.bytes + bp_seg.bytes + bp_list.bytes + bp_small.bytes + cfa.bytes + star_work.bytes() +
-                   back_work.bytes() + deband_work.bytes();
+                   back_work.bytes() + deband_work.bytes() + blur_work.bytes();
         }
         void release(int device)
         {
@@ -171,6 +174,7 @@ struct nl_stack {
             star_work.release();
             back_work.release();
             deband_work.release();
+            blur_work.release();
         }
     } frame_scratch;
     int max_grid = 0;

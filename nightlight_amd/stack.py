@@ -379,6 +379,24 @@ class StackHandle:
         return _deband(lambda *a: self._lib.nl_stack_frame_deband_vert(self._h, int(idx), *a), percentile, window,
                        sigma, location, scale)
 
+    def frame_gaussian_blur(self, idx, sigma):
+        """OpGaussianBlur on resident slot idx of a whole-image handle, in place (see gaussian_blur)."""
+        capi.check(self._lib.nl_stack_frame_gaussian_blur(self._h, int(idx), float(sigma)))
+
+    def frame_unsharp_mask(self, idx, sigma, gain, min, max, abs_threshold):
+        """OpUnsharpMask on resident slot idx of a whole-image handle, in place (see unsharp_mask)."""
+        capi.check(self._lib.nl_stack_frame_unsharp_mask(self._h, int(idx), float(sigma), float(gain), float(min),
+                                                         float(max), float(abs_threshold)))
+
+    def result_gaussian_blur(self, sigma):
+        """OpGaussianBlur on the last pass's result, still on the device, in place (download_rows(-1, ...) reads it)."""
+        capi.check(self._lib.nl_stack_result_gaussian_blur(self._h, float(sigma)))
+
+    def result_unsharp_mask(self, sigma, gain, min, max, abs_threshold):
+        """OpUnsharpMask on the last pass's result, still on the device, in place."""
+        capi.check(self._lib.nl_stack_result_unsharp_mask(self._h, float(sigma), float(gain), float(min), float(max),
+                                                          float(abs_threshold)))
+
     def frame_bin_from(self, idx, src, src_idx, n):
         """NewImageBinNxN of resident slot src_idx of the whole-image handle `src` into slot idx of this one, whose
         shape is bin_shape of the source's (n <= 1: a device copy)."""
@@ -755,6 +773,65 @@ def bin_nxn(frame, width, height, n, device=None):
     capi.check(capi.load().nl_bin_nxn(capi.fptr(frame), int(width), int(height), int(n), capi.fptr(out),
                                       0 if device is None else int(device)))
     return out, ow, oh
+
+
+def gaussian_kernel_1d(sigma, capacity=None):
+    """GaussianKernel1D (internal/ops/stretch/usm.go:41-82): the taps for `sigma` as float32 (host only).  capacity:
+    the room offered to the library (default: the tap count, asked for first)."""
+    lib = capi.load()
+    n = C.c_int(0)
+    if capacity is None:
+        rc = lib.nl_gaussian_kernel_1d(float(sigma), None, 0, C.byref(n))
+        if rc != capi.OK and n.value == 0:
+            capi.check(rc)
+        capacity = n.value
+    taps = np.empty(max(int(capacity), 1), np.float32)
+    capi.check(lib.nl_gaussian_kernel_1d(float(sigma), capi.fptr(taps), int(capacity), C.byref(n)))
+    return taps[:n.value].copy()
+
+
+def blur_tap_paths(n_taps):
+    """(row_staged, col_staged): whether the row and the column pass of an n_taps kernel stage their tile in LDS or
+    take every tap from global memory (developer query)."""
+    row, col = C.c_int(0), C.c_int(0)
+    capi.check(capi.load().nl_blur_tap_paths(int(n_taps), C.byref(row), C.byref(col)))
+    return bool(row.value), bool(col.value)
+
+
+def _host_frame(frame, width, height):
+    out = np.array(frame, dtype=np.float32, copy=True).reshape(-1)
+    assert out.size == int(width) * int(height)
+    return out
+
+
+def convolve_separable(frame, width, height, taps, device=None):
+    """Convolve1DX then Convolve1DY (usm.go:85-114) of one host frame with the caller's taps on `device` (default 0);
+    bit-exact.  Returns the filtered frame."""
+    out = _host_frame(frame, width, height)
+    t = np.ascontiguousarray(taps, dtype=np.float32).reshape(-1)
+    capi.check(capi.load().nl_convolve_separable(capi.fptr(out), int(width), int(height), capi.fptr(t) if t.size else None,
+                                                 int(t.size), 0 if device is None else int(device)))
+    return out
+
+
+def gaussian_blur(frame, width, height, sigma, device=None):
+    """OpGaussianBlur (internal/ops/stretch/stretch.go:368-376) of one host frame; sigma 0 returns it unchanged."""
+    out = _host_frame(frame, width, height)
+    capi.check(capi.load().nl_gaussian_blur(capi.fptr(out), int(width), int(height), float(sigma),
+                                            0 if device is None else int(device)))
+    return out
+
+
+def unsharp_mask(frame, width, height, sigma, gain, min, max, abs_threshold, device=None):
+    """UnsharpMask (usm.go:153-159) of one host frame: pixels below abs_threshold stay, the others become
+    d + (d - blurred) * gain clipped to min, then max; sigma 0 or gain 0 returns the frame unchanged."""
+    src = np.ascontiguousarray(frame, dtype=np.float32).reshape(-1)
+    assert src.size == int(width) * int(height)
+    out = np.empty_like(src)
+    capi.check(capi.load().nl_unsharp_mask(capi.fptr(src), capi.fptr(out), int(width), int(height), float(sigma),
+                                           float(gain), float(min), float(max), float(abs_threshold),
+                                           0 if device is None else int(device)))
+    return out
 
 
 def _cstr(s):
