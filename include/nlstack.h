@@ -714,6 +714,76 @@ int nl_stack_result_unsharp_mask(nl_stack_t *h, float sigma, float gain, float m
  * the launcher's own; the results are the same either way.  No counterpart in the reference. */
 int nl_blur_tap_paths(int n_taps, int *row_staged, int *col_staged);
 
+/* ---- the tone curves of the stretch command, and OpSave's quantisation ----
+ * (internal/ops/stretch/stretch.go:40-335 over internal/fits/pixelops.go; internal/fits/tiff16.go:108-135,
+ * internal/fits/writejpg.go:106-131)
+ * OpNormalizeRange, the two pixel passes OpStretchIterative chooses between, OpMidtones, OpGamma, OpGammaPP and
+ * OpScaleBlack -- and the Apply...ToChannel calls of the OpHSL... operators on a luminance plane in a slot -- are one
+ * per-pixel curve each, in place.  The caller passes what Go passes to the pixel function; the library derives the
+ * loop constants as the reference does in front of its loop, in fp32 (and float64(1.0f / g) for the exponent):
+ *   kind                     p[0], p[1], p[2]   per pixel d
+ *   NL_TONE_SCALE_OFFSET     scale, offset      d * scale + offset                             (pixelops.go:123-128)
+ *   NL_TONE_NORMALIZE        min, max           the same with scale = 1.0 / (max - min), offset = -min * scale
+ *                                                                                              (:143-147)
+ *   NL_TONE_GAMMA            g                  float32(pow(float64(d), gg)), gg = float64(1.0 / g)   (:151-157)
+ *   NL_TONE_PARTIAL_GAMMA    from, to, g        where d > from && d < to: dd = (d - from) * rescale1,
+ *                                               from + float32(pow(float64(dd), gg)) * rescale2 with rescale2 =
+ *                                               to - from, rescale1 = 1.0 / rescale2; every other pixel, a NaN
+ *                                               included, keeps its bits                       (:179-191)
+ *   NL_TONE_MIDTONES         mid, black         value = d * (mid - 1) / ((2 * mid - 1) * d - mid); value < clipLow
+ *                                               gives 0, else value > 1 gives 1; (value - clipLow) * scaler, with
+ *                                               clipLow the same expression of black and scaler = 1 / (1 - clipLow);
+ *                                               a NaN falls through both tests                 (:214-229)
+ *   NL_TONE_SHIFT_BLACK      before, after      math.Max(0, (d - black) * scale) with black = (after - before) /
+ *                                               (after - 1), scale = 1 / (1 - black): NaN for a NaN, +0 for -0 and
+ *                                               for every negative product                     (:649-660)
+ * fp32 without FMA, IEEE division; pow is the device's fp64 pow with C99's special cases, which Go documents
+ * identically for everything these curves can reach (a negative base with a fractional exponent is NaN, +-0 to a
+ * positive power 0 and to a negative one +Inf, an exponent of +Inf for g == 0).  Nothing the reference computes is
+ * rejected.  One reservation: neither Go's math.Pow nor the device's pow is correctly rounded, so a pixel whose exact
+ * power lies within a few fp64 ulps of the midpoint between two fp32 values may come out one fp32 ulp away from the Go
+ * binary's; everything else is bit-exact.
+ * Guards: g == 1 of NL_TONE_GAMMA (OpGamma.Apply, stretch.go:240) is a no-op that leaves every bit.  The g == 1 guard
+ * of OpGammaPP (:279) and the guards of OpStretchIterative, OpMidtones and OpScaleBlack (:104, :196, :323) act on the
+ * operator's fields, not on the pixel function's arguments: they stay with the caller.  Location() / Scale() are the
+ * caller's scalars as everywhere else.
+ * Statistics: every one of these curves ends in Stats.Clear(), and the next operator asks for Min() / Mean() / Max()
+ * again.  mn, mean, mx are optional; when any is non-NULL the kernel also reduces what it writes, and the three
+ * values are bit for bit what nl_stack_frame_stats would return on the slot immediately afterwards (a no-op fills
+ * them too).  With all three NULL nothing is reduced.
+ * Per-pixel steps: they run on row-tile handles as well and cover the tile only.
+ * Errors, NL_ERR_INVALID_ARG with a message naming the site: an unknown kind, a NULL curve / frame / output, bits
+ * other than 8 or 16, a result form on a handle that has not run a pass; and one deviation: a gamma of the export
+ * that is NaN or <= 0 (the reference would convert an infinite value to an integer, which Go leaves to the
+ * implementation).  Without a device every entry fails with NL_ERR_NO_DEVICE. */
+#define NL_TONE_SCALE_OFFSET   0
+#define NL_TONE_NORMALIZE      1
+#define NL_TONE_GAMMA          2
+#define NL_TONE_PARTIAL_GAMMA  3
+#define NL_TONE_MIDTONES       4
+#define NL_TONE_SHIFT_BLACK    5
+typedef struct nl_tone {
+    int32_t kind;   /* NL_TONE_* */
+    float p[3];     /* the pixel function's arguments in the table's order; unused ones are ignored */
+} nl_tone_t;
+/* the curve on resident slot idx, in place */
+int nl_stack_frame_tone(nl_stack_t *h, int idx, const nl_tone_t *tone, float *mn, float *mean, float *mx);
+/* ... on the last pass's result still on the device, in place */
+int nl_stack_result_tone(nl_stack_t *h, const nl_tone_t *tone, float *mn, float *mean, float *mx);
+/* ... on n floats of host memory (n < 2^31), in place, on a handle of the call's own */
+int nl_tone(float *data_host, int64_t n, const nl_tone_t *tone, float *mn, float *mean, float *mx, int device);
+/* OpSave's pixel loop (WriteMonoTIFF16 / WriteMonoJPG): gray = (d - min) * scale with scale = 1 / (max - min) in
+ * fp32; NaN or < 0 gives 0, > 1 gives 1; if gammaInv = float64(1.0 / gamma) != 1.0, float32(pow(float64(gray),
+ * gammaInv)); then uint16(gray * 65535) (bits 16) or uint8(gray * 255) (bits 8) by truncation.  out_host receives
+ * one count per pixel of the slot (of the tile, on a row-tile handle): bits 16 two bytes each, high byte first --
+ * the layout of Go's image.Gray16.Pix, which tiff.Encode takes as it is -- bits 8 one byte each, image.Gray.Pix.
+ * The frame stays as it is; 2 or 1 bytes per pixel cross PCIe instead of 4.  The pow reservation above applies:
+ * such a pixel may be one count away. */
+int nl_stack_frame_export_gray(nl_stack_t *h, int idx, float min, float max, float gamma, int bits, void *out_host);
+int nl_stack_result_export_gray(nl_stack_t *h, float min, float max, float gamma, int bits, void *out_host);
+int nl_export_gray(const float *data_host, int64_t n, float min, float max, float gamma, int bits, void *out_host,
+                   int device);
+
 /* ---- host-side operator mirror (nightlight_amd/host/, C++) ----
  * The reference's stack operator decoded from its JSON form and run through
  * MakePromises/Apply exactly as OpSequence would drive it

@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("NLSTACK_LIB") or os.path.join(_PKG, "libnlstack.so")
 
 ST_MEDIAN, ST_MEAN, ST_SIGMA, ST_WINSOR_SIGMA, ST_MAD_SIGMA, ST_LINEAR_FIT, ST_AUTO = range(7)
 WEIGHT_NONE, WEIGHT_EXPOSURE, WEIGHT_INVERSE_NOISE, WEIGHT_INVERSE_HFR = range(4)
+TONE_SCALE_OFFSET, TONE_NORMALIZE, TONE_GAMMA, TONE_PARTIAL_GAMMA, TONE_MIDTONES, TONE_SHIFT_BLACK = range(6)
 
 OK = 0
 ERR_INVALID_MODE = -1
@@ -62,6 +63,8 @@ EXPORTS = [
     "nl_gaussian_kernel_1d", "nl_convolve_separable", "nl_gaussian_blur", "nl_unsharp_mask",
     "nl_stack_frame_gaussian_blur", "nl_stack_frame_unsharp_mask", "nl_stack_result_gaussian_blur",
     "nl_stack_result_unsharp_mask", "nl_blur_tap_paths",
+    "nl_stack_frame_tone", "nl_stack_result_tone", "nl_tone",
+    "nl_stack_frame_export_gray", "nl_stack_result_export_gray", "nl_export_gray",
     "nl_stack_frame_project_from", "nl_group_frame_project_from", "nl_stack_project_tile_paths",
 ]
 
@@ -82,6 +85,11 @@ class Background(C.Structure):
 class Deband(C.Structure):
     """nl_deband_t: what the debanding operators' log lines print (banding.go:129, :267)."""
     _fields_ = [("threshold", C.c_float), ("lowest", C.c_float), ("highest", C.c_float)]
+
+
+class Tone(C.Structure):
+    """nl_tone_t: one curve of the stretch command, the kind and the pixel function's arguments."""
+    _fields_ = [("kind", C.c_int32), ("p", C.c_float * 3)]
 
 
 class NlError(RuntimeError):
@@ -280,6 +288,14 @@ def open_library(path):
     L.nl_stack_result_gaussian_blur.argtypes = [vp, C.c_float]
     L.nl_stack_result_unsharp_mask.argtypes = [vp] + _usm_args
     L.nl_blur_tap_paths.argtypes = [C.c_int, _intp, _intp]
+    _tone_args = [C.POINTER(Tone), _f32p, _f32p, _f32p]      # the curve, mn, mean, mx
+    _gray_args = [C.c_float, C.c_float, C.c_float, C.c_int, vp]     # min, max, gamma, bits, out_host
+    L.nl_stack_frame_tone.argtypes = [vp, C.c_int] + _tone_args
+    L.nl_stack_result_tone.argtypes = [vp] + _tone_args
+    L.nl_tone.argtypes = [_f32p, C.c_int64] + _tone_args + [C.c_int]
+    L.nl_stack_frame_export_gray.argtypes = [vp, C.c_int] + _gray_args
+    L.nl_stack_result_export_gray.argtypes = [vp] + _gray_args
+    L.nl_export_gray.argtypes = [_f32p, C.c_int64] + _gray_args + [C.c_int]
     L.nl_stack_frame_project_from.argtypes = [vp, C.c_int, vp, C.c_int, _f32p, C.c_float]
     L.nl_group_frame_project_from.argtypes = [vp, C.c_int, vp, C.c_int, _f32p, C.c_float]
     L.nl_stack_project_tile_paths.argtypes = [vp, vp, C.c_int, _f32p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]

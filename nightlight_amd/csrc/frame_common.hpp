@@ -1,5 +1,5 @@
 // frame_common.hpp -- what the kernels of the per-frame operators (preprocess.hip, bayer.hip, stars.hip,
-// background.hip, frame_stats.hip, ingest.hip) share: the wave reductions, the block sum, Go's float -> int32.
+// background.hip, frame_stats.hip, ingest.hip, tone.hip) share: the wave reductions, the block sum, Go's float -> int32.
 // Summation order is part of the results (fp64 partials feed bit-exact fp32 statistics): the butterfly runs over the
 // xor distances 32, 16, ... 1, the wave values are added left to right.
 #pragma once
@@ -61,6 +61,31 @@ __device__ __forceinline__ T block_sum(T v)
     __shared__ T s[THREADS / 64];
     wave_values(wave_sum(v), s);
     return sum_in_order<THREADS / 64>(s);
+}
+
+// The end of a {min, sum, max} reduction over a workgroup of 256 (min_sum_max_kernel and the tone kernels that reduce
+// what they write): the waves' butterflies, then wave 0's lane 0 folds the four wave values in order and writes the
+// workgroup's partial[3 * blockIdx.x + {0, 1, 2}].  The statistics are bit-exact against the reference in this order.
+__device__ __forceinline__ void block_min_sum_max(float mn, double sum, float mx, double *partial)
+{
+    __shared__ float s_mn[4], s_mx[4];
+    __shared__ double s_sum[4];
+    mn = wave_min(mn);
+    mx = wave_max(mx);
+    sum = wave_sum(sum);
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { s_mn[wave] = mn; s_mx[wave] = mx; s_sum[wave] = sum; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 4; w++) {
+            mn = fminf(mn, s_mn[w]);
+            mx = fmaxf(mx, s_mx[w]);
+            sum += s_sum[w];
+        }
+        partial[3 * (size_t)blockIdx.x + 0] = (double)mn;
+        partial[3 * (size_t)blockIdx.x + 1] = sum;
+        partial[3 * (size_t)blockIdx.x + 2] = (double)mx;
+    }
 }
 
 // Go's float -> int32 conversion is CVTTSS2SL / CVTTSD2SL on amd64: truncation, and 0x80000000 for NaN or out of range

@@ -41,24 +41,7 @@ __global__ __launch_bounds__(256) void min_sum_max_kernel(const float *data, int
             sum += (double)e;
         }
     }
-    __shared__ float s_mn[4], s_mx[4];
-    __shared__ double s_sum[4];
-    mn = wave_min(mn);
-    mx = wave_max(mx);
-    sum = wave_sum(sum);
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { s_mn[wave] = mn; s_mx[wave] = mx; s_sum[wave] = sum; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; w++) {
-            mn = fminf(mn, s_mn[w]);
-            mx = fmaxf(mx, s_mx[w]);
-            sum += s_sum[w];
-        }
-        partial[3 * (size_t)blockIdx.x + 0] = (double)mn;
-        partial[3 * (size_t)blockIdx.x + 1] = sum;
-        partial[3 * (size_t)blockIdx.x + 2] = (double)mx;
-    }
+    block_min_sum_max(mn, sum, mx, partial);
 }
 
 // sum of (double)(x - mean_fp32)^2 (stats.go:280-287, stats_amd64.s:102-143)

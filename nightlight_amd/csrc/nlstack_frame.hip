@@ -1,7 +1,7 @@
 // nlstack_frame.hip -- steps on one frame resident in a handle, and their host forms: statistics and noise,
 // median filters, OpCalibrate / OpBadPixel, star detection, background extraction, debanding and binning, Gaussian blur
-// and unsharp mask, the colour-camera front.  Kernels in frame_stats.hip, preprocess.hip, stars.hip, background.hip,
-// deband.hip, blur.hip and bayer.hip.
+// and unsharp mask, the tone curves and the gray export, the colour-camera front.  Kernels in frame_stats.hip,
+// preprocess.hip, stars.hip, background.hip, deband.hip, blur.hip, tone.hip and bayer.hip.
 #include <float.h>
 #include <math.h>
 
@@ -82,18 +82,29 @@ extern "C" {
 
 // ---- per-frame statistics ---------------------------------------------------
 
-static int frame_stats_impl(nl_stack_t *h, const float *d, int64_t n, float *mn, float *mean,
-                            float *mx, double *variance)
+// min / mean / max of n values from the {min, sum, max} partials a kernel enqueued on h->stream leaves in
+// h->d_stat_partial (launch_min_sum_max, or a tone curve that reduces what it writes); waits for the stream
+static int min_mean_max_from_partials(nl_stack_t *h, int64_t n, float *mn, float *mean, float *mx)
 {
     std::vector<double> part(3 * kStatBlocks);
-    NL_HIP(nl::launch_min_sum_max(d, n, h->d_stat_partial, kStatBlocks, h->stream));
     NL_HIP(hipMemcpyAsync(part.data(), h->d_stat_partial, sizeof(double) * 3 * kStatBlocks,
                           hipMemcpyDeviceToHost, h->stream));
     NL_HIP(hipStreamSynchronize(h->stream));
     const MinSumMax f = fold_min_sum_max(part);
-    const float m = (float)(f.sum / (double)n);
     if (mn) *mn = f.lo;
     if (mx) *mx = f.hi;
+    if (mean) *mean = (float)(f.sum / (double)n);
+    return NL_OK;
+}
+
+static int frame_stats_impl(nl_stack_t *h, const float *d, int64_t n, float *mn, float *mean,
+                            float *mx, double *variance)
+{
+    std::vector<double> part(kStatBlocks);
+    float m = 0.0f;
+    NL_HIP(nl::launch_min_sum_max(d, n, h->d_stat_partial, kStatBlocks, h->stream));
+    const int rc = min_mean_max_from_partials(h, n, mn, &m, mx);
+    if (rc != NL_OK) return rc;
     if (mean) *mean = m;
     if (variance) {
         NL_HIP(nl::launch_variance(d, n, m, h->d_stat_partial, kStatBlocks, h->stream));
@@ -776,6 +787,147 @@ int nl_unsharp_mask(const float *in_host, float *out_host, int width, int height
         return NL_OK;
     }
     return host_blur("unsharp_mask", in_host, out_host, width, height, taps.data(), (int)taps.size(), &p, device);
+}
+
+// ---- the tone curves of the stretch command and OpSave's quantisation (stretch.go:40-335, pixelops.go, tiff16.go,
+// writejpg.go; kernels in tone.hip).  Per-pixel steps: a row-tile handle is served, its tile only. ------------------
+
+// the curve over the npix floats at d (a slot or the result of h), in place
+static int tone_impl(nl_stack_t *h, float *d, const char *who, const nl_tone_t *tone, float *mn, float *mean, float *mx)
+{
+    nl::ToneArgs args;
+    bool noop;
+    std::string msg;
+    const int rc = nl::tone_args(*tone, &args, &noop, &msg);
+    if (rc != NL_OK) return fail(rc, "%s: %s", who, msg.c_str());
+    const bool stats = mn || mean || mx;
+    if (noop) return stats ? frame_stats_impl(h, d, h->npix, mn, mean, mx, nullptr) : NL_OK;
+    if (!stats) {
+        NL_HIP(nl::launch_tone(d, h->npix, args, nullptr, nullptr, 0, h->stream));
+        NL_HIP(hipStreamSynchronize(h->stream));
+        return NL_OK;
+    }
+    nl::DevBuffer &seed = h->frame_scratch.tone_seed;
+    NL_HIP(seed.reserve(sizeof(float), h->stream));
+    NL_HIP(nl::launch_tone(d, h->npix, args, static_cast<float *>(seed.ptr), h->d_stat_partial, kStatBlocks, h->stream));
+    return min_mean_max_from_partials(h, h->npix, mn, mean, mx);
+}
+
+// the counts of the npix floats at d into out_host, through the handle's ingest buffer like nl_stack_download_result_fits
+static int export_gray_impl(nl_stack_t *h, const float *d, float min, float max, float gamma, int bits, void *out_host)
+{
+    const float scale = 1.0f / (max - min);                    // tiff16.go:112-113
+    const double gamma_inv = (double)(1.0f / gamma);
+    const size_t bytes = (size_t)h->npix * (size_t)(bits / 8);
+    NL_HIP(h->ingest.reserve(bytes, h->stream));
+    NL_HIP(nl::launch_export_gray(d, h->npix, min, scale, gamma_inv != 1.0, gamma_inv, bits, h->ingest.ptr, h->stream));
+    NL_HIP(hipMemcpyAsync(out_host, h->ingest.ptr, bytes, hipMemcpyDeviceToHost, h->stream));
+    NL_HIP(hipStreamSynchronize(h->stream));
+    return NL_OK;
+}
+
+// what needs no device: the curve's kind (and *noop: the operator's own guard holds)
+static int tone_check(const char *who, const nl_tone_t *tone, bool *noop)
+{
+    if (!tone) return fail(NL_ERR_INVALID_ARG, "%s: null curve", who);
+    nl::ToneArgs args;
+    std::string msg;
+    const int rc = nl::tone_args(*tone, &args, noop, &msg);
+    return rc == NL_OK ? NL_OK : fail(rc, "%s: %s", who, msg.c_str());
+}
+
+static int export_gray_check(const char *who, float gamma, int bits, const void *out_host)
+{
+    if (!out_host) return fail(NL_ERR_INVALID_ARG, "%s: null output", who);
+    if (bits != 8 && bits != 16) return fail(NL_ERR_INVALID_ARG, "%s: %d bits (8: image.Gray, 16: image.Gray16)", who, bits);
+    if (!(gamma > 0.0f))                       // (deviation: gray becomes infinite or NaN in front of the conversion)
+        return fail(NL_ERR_INVALID_ARG, "%s: gamma %g (tiff16.go:113, writejpg.go:111: a positive number)", who, gamma);
+    return NL_OK;
+}
+
+// idx >= 0 a frame slot, idx < 0 the last pass's result (as resident_blur); nullptr with the thread's error set
+static float *resident_pixels(nl_stack_t *h, int idx, const char *who, int *rc)
+{
+    *rc = NL_ERR_INVALID_ARG;
+    if (idx >= 0) return frame_or_fail(h, idx, who);
+    if (h->last_mode < 0) {
+        fail(NL_ERR_INVALID_ARG, "%s: the handle has not run a pass", who);
+        return nullptr;
+    }
+    return h->d_out;
+}
+
+static int resident_tone(nl_stack_t *h, int idx, const char *who, const nl_tone_t *tone, float *mn, float *mean, float *mx)
+{
+    NL_CHECK_HANDLE(h);
+    bool noop;
+    int rc = tone_check(who, tone, &noop);
+    if (rc != NL_OK) return rc;
+    if (idx >= 0) NL_SETTLE_UPLOADS(h);
+    float *d = resident_pixels(h, idx, who, &rc);
+    return d ? tone_impl(h, d, who, tone, mn, mean, mx) : rc;
+}
+
+static int resident_export_gray(nl_stack_t *h, int idx, const char *who, float min, float max, float gamma, int bits,
+                                void *out_host)
+{
+    NL_CHECK_HANDLE(h);
+    int rc = export_gray_check(who, gamma, bits, out_host);
+    if (rc != NL_OK) return rc;
+    if (idx >= 0) NL_SETTLE_UPLOADS(h);
+    const float *d = resident_pixels(h, idx, who, &rc);
+    return d ? export_gray_impl(h, d, min, max, gamma, bits, out_host) : rc;
+}
+
+int nl_stack_frame_tone(nl_stack_t *h, int idx, const nl_tone_t *tone, float *mn, float *mean, float *mx)
+{
+    if (h && idx < 0) return fail(NL_ERR_INVALID_ARG, "frame_tone: bad index %d", idx);
+    return resident_tone(h, idx, "frame_tone", tone, mn, mean, mx);
+}
+
+int nl_stack_result_tone(nl_stack_t *h, const nl_tone_t *tone, float *mn, float *mean, float *mx)
+{
+    return resident_tone(h, -1, "result_tone", tone, mn, mean, mx);
+}
+
+int nl_stack_frame_export_gray(nl_stack_t *h, int idx, float min, float max, float gamma, int bits, void *out_host)
+{
+    if (h && idx < 0) return fail(NL_ERR_INVALID_ARG, "frame_export_gray: bad index %d", idx);
+    return resident_export_gray(h, idx, "frame_export_gray", min, max, gamma, bits, out_host);
+}
+
+int nl_stack_result_export_gray(nl_stack_t *h, float min, float max, float gamma, int bits, void *out_host)
+{
+    return resident_export_gray(h, -1, "result_export_gray", min, max, gamma, bits, out_host);
+}
+
+// the host forms: n floats as an n x 1 frame of a handle of the call's own (like nl_fits_decode)
+int nl_tone(float *data_host, int64_t n, const nl_tone_t *tone, float *mn, float *mean, float *mx, int device)
+{
+    if (!data_host || n < 1 || n > 0x7fffffff) return fail(NL_ERR_INVALID_ARG, "tone: bad argument");
+    bool noop;
+    int rc = tone_check("tone", tone, &noop);
+    if (rc != NL_OK) return rc;
+    if (noop && !mn && !mean && !mx) return NL_OK;             // nothing to compute: the frame is not even uploaded
+    if ((rc = select_device(device)) != NL_OK) return rc;
+    return with_scratch_handle((int)n, 1, device, [&](nl_stack_t *h) {
+        int r = nl_stack_upload_tile(h, 0, data_host);
+        if (r == NL_OK) r = tone_impl(h, h->d_frames, "tone", tone, mn, mean, mx);
+        return r == NL_OK ? nl_stack_download_tile(h, 0, data_host) : r;
+    });
+}
+
+int nl_export_gray(const float *data_host, int64_t n, float min, float max, float gamma, int bits, void *out_host,
+                   int device)
+{
+    if (!data_host || n < 1 || n > 0x7fffffff) return fail(NL_ERR_INVALID_ARG, "export_gray: bad argument");
+    int rc = export_gray_check("export_gray", gamma, bits, out_host);
+    if (rc == NL_OK) rc = select_device(device);
+    if (rc != NL_OK) return rc;
+    return with_scratch_handle((int)n, 1, device, [&](nl_stack_t *h) {
+        const int r = nl_stack_upload_tile(h, 0, data_host);
+        return r == NL_OK ? export_gray_impl(h, h->d_frames, min, max, gamma, bits, out_host) : r;
+    });
 }
 
 // ---- OpAlign's f.Project from a resident frame (post/postprocess.go:185, fits/project.go:26-76; kernel in project.hip) ----

@@ -14,6 +14,7 @@
 #include "dev_memory.hpp"
 #include "project.hpp"
 #include "stars.hpp"
+#include "tone.hpp"
 #include "stack_kernels.h"
 
 namespace nl {
@@ -159,10 +160,12 @@ struct nl_stack {
         nl::DebandWork deband_work;
         // Gaussian blur / unsharp mask (nl_stack_frame_gaussian_blur, nl_stack_result_unsharp_mask, ...)
         nl::BlurWork blur_work;
+        // the tone curves with statistics (nl_stack_frame_tone, ...): the transformed element 0, one float
+        nl::DevBuffer tone_seed;
         size_t bytes() const
         {
             return bp_diff.bytes + bp_seg.bytes + bp_list.bytes + bp_small.bytes + cfa.bytes + star_work.bytes() +
-                   back_work.bytes() + deband_work.bytes() + blur_work.bytes();
+                   back_work.bytes() + deband_work.bytes() + blur_work.bytes() + tone_seed.bytes;
         }
         void release(int device)
         {
@@ -175,6 +178,7 @@ struct nl_stack {
             back_work.release();
             deband_work.release();
             blur_work.release();
+            tone_seed.release();
         }
     } frame_scratch;
     int max_grid = 0;

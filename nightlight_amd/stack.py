@@ -397,6 +397,26 @@ class StackHandle:
         capi.check(self._lib.nl_stack_result_unsharp_mask(self._h, float(sigma), float(gain), float(min), float(max),
                                                           float(abs_threshold)))
 
+    def frame_tone(self, idx, kind, *p, stats=False):
+        """One tone curve of the stretch command (capi.TONE_*, see tone) on resident slot idx, in place; any row tile.
+        stats=True: returns (min, mean, max) of the transformed slot from the same pass, the bits frame_stats would
+        return afterwards."""
+        return _tone(lambda *a: self._lib.nl_stack_frame_tone(self._h, int(idx), *a), kind, p, stats)
+
+    def result_tone(self, kind, *p, stats=False):
+        """One tone curve on the last pass's result, still on the device, in place (download_rows(-1, ...) reads it)."""
+        return _tone(lambda *a: self._lib.nl_stack_result_tone(self._h, *a), kind, p, stats)
+
+    def frame_export_gray(self, idx, min, max, gamma=1.0, bits=16):
+        """OpSave's quantisation of resident slot idx (see export_gray); the slot stays as it is."""
+        return _export_gray(lambda *a: self._lib.nl_stack_frame_export_gray(self._h, int(idx), *a), self.tile_pixels,
+                            min, max, gamma, bits)
+
+    def result_export_gray(self, min, max, gamma=1.0, bits=16):
+        """OpSave's quantisation of the last pass's result, still on the device."""
+        return _export_gray(lambda *a: self._lib.nl_stack_result_export_gray(self._h, *a), self.tile_pixels, min, max,
+                            gamma, bits)
+
     def frame_bin_from(self, idx, src, src_idx, n):
         """NewImageBinNxN of resident slot src_idx of the whole-image handle `src` into slot idx of this one, whose
         shape is bin_shape of the source's (n <= 1: a device copy)."""
@@ -832,6 +852,47 @@ def unsharp_mask(frame, width, height, sigma, gain, min, max, abs_threshold, dev
                                            float(gain), float(min), float(max), float(abs_threshold),
                                            0 if device is None else int(device)))
     return out
+
+
+def _tone(call, kind, p, stats):
+    """call(curve, mn, mean, mx) with the nl_tone_t of kind and its arguments p; the statistics when asked for."""
+    assert len(p) <= 3
+    t = capi.Tone(int(kind), (C.c_float * 3)(*[float(v) for v in p]))
+    if not stats:
+        capi.check(call(C.byref(t), None, None, None))
+        return None
+    mn, mean, mx = C.c_float(), C.c_float(), C.c_float()
+    capi.check(call(C.byref(t), C.byref(mn), C.byref(mean), C.byref(mx)))
+    return np.float32(mn.value), np.float32(mean.value), np.float32(mx.value)
+
+
+def tone(frame, kind, *p, stats=False, device=None):
+    """One per-pixel curve of the reference's stretch command (internal/fits/pixelops.go) over a host frame on
+    `device` (default 0).  kind and p, the pixel function's own arguments: capi.TONE_SCALE_OFFSET (scale, offset),
+    TONE_NORMALIZE (min, max), TONE_GAMMA (g), TONE_PARTIAL_GAMMA (from, to, g), TONE_MIDTONES (mid, black),
+    TONE_SHIFT_BLACK (before, after).  Bit-exact but for pixels whose power falls on a rounding boundary (one fp32 ulp).
+    Returns the transformed frame; with stats=True (frame, (min, mean, max)) from the same pass."""
+    out = np.array(frame, dtype=np.float32, copy=True).reshape(-1)
+    dev = 0 if device is None else int(device)
+    st = _tone(lambda *a: capi.load().nl_tone(capi.fptr(out), int(out.size), *a, dev), kind, p, stats)
+    return (out, st) if stats else out
+
+
+def _export_gray(call, n, min, max, gamma, bits):
+    """call(min, max, gamma, bits, out) into n counts: uint8, or big-endian uint16 as the bytes lie in image.Gray16.Pix"""
+    raw = np.empty(int(n) * (2 if int(bits) == 16 else 1), np.uint8)
+    capi.check(call(float(min), float(max), float(gamma), int(bits), raw.ctypes.data_as(C.c_void_p)))
+    return raw.view(">u2") if int(bits) == 16 else raw
+
+
+def export_gray(frame, min, max, gamma=1.0, bits=16, device=None):
+    """OpSave's pixel loop (WriteMonoTIFF16 / WriteMonoJPG) over a host frame: (d - min) / (max - min) clipped to
+    [0, 1] (NaN: 0), gamma, then counts of 16 bits (returned as big-endian uint16, the byte layout of Go's
+    image.Gray16.Pix) or 8 bits (uint8) by truncation."""
+    src = np.ascontiguousarray(frame, dtype=np.float32).reshape(-1)
+    dev = 0 if device is None else int(device)
+    return _export_gray(lambda *a: capi.load().nl_export_gray(capi.fptr(src), int(src.size), *a, dev), src.size, min,
+                        max, gamma, bits)
 
 
 def _cstr(s):
