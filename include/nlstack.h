@@ -784,6 +784,101 @@ int nl_stack_result_export_gray(nl_stack_t *h, float min, float max, float gamma
 int nl_export_gray(const float *data_host, int64_t n, float min, float max, float gamma, int bits, void *out_host,
                    int device);
 
+/* ---- the rgb / lrgb command around its tone curves: combine, balance, chroma and hue steps, colour export ----
+ * (internal/fits/rgb.go:43-281, internal/fits/pixelops.go:441-550 and :679-692, internal/fits/tiff16.go:45-91,
+ * internal/fits/writejpg.go:43-89)
+ * An RGB (or HCL / HSLuv) image is three slots of one whole-image handle, named by planes[3] in the reference's channel
+ * order {0, 1, 2}: three distinct valid slot indices.  The entries take the planes as they are: the conversions between
+ * colour spaces (RGBToHSLuv, HSLuvToRGB, MonoToHSLuvLum), SCNR and the target of OpHSLScaleBlack are go-colorful's
+ * arithmetic, not the reference's own, and stay with the caller; so do Stats.Location() / Scale() as everywhere else.
+ * Everything here is bit-exact against the reference: fp32 without FMA, sums in its order, Go's Min / Max semantics (a
+ * NaN stays NaN, -0 and every negative become +0); the two powers (NL_CHROMA_GAMMA, the export's gamma) carry the
+ * reservation of the tone curves above (one fp32 ulp / one count at a rounding boundary).
+ * Errors, NL_ERR_INVALID_ARG with a message naming the site: null pointers, bad or repeated plane indices, an unknown
+ * kind, a whole-image step (darkest block, star intensity, balance) on a row-tile handle, and where the reference
+ * would index out of range or convert a non-finite value: block < 1, border NaN or < 0 or so large that the first block
+ * lies below 0, skip_bright / skip_dim that put the star range outside the list, a selected star whose HFR is NaN,
+ * negative or gives a disc radius above 1024, an export gamma that is NaN or <= 0, bits other than 8 / 16.  Without a
+ * device every entry but nl_rgb_normalization and nl_rgb_balance_coeffs fails with NL_ERR_NO_DEVICE. */
+typedef struct nl_rgb { float r, g, b; } nl_rgb_t;               /* fits.RGB (rgb.go:28-32) */
+/* getCommonNormalizationFactors (rgb.go:65-78): min and max over the channels' Stats.Min() / Max() by strict compares
+ * from channel 0 on, mult = 1 / (max - min) in fp32.  Host only, needs no device. */
+int nl_rgb_normalization(const float mins[3], const float maxs[3], float *min, float *mult);
+/* The pixel loop of NewRGBFromChannels (rgb.go:55-60): dst slot dst_idx = (src slot src_idx - min) * mult, two fp32
+ * roundings.  src_idx == -1 reads the last pass's result of src; dst == src with the same slot runs in place.  Same
+ * device and same geometry (width, height, row tile); per-pixel, so row-tile handles are served. */
+int nl_stack_frame_combine_from(nl_stack_t *dst, int dst_idx, nl_stack_t *src, int src_idx, float min, float mult);
+/* ScaleOffsetClampRGB (pixelops.go:679-692): plane c = float32(math.Max(math.Min(1, float64(alpha[c] * d + beta[c])),
+ * 0)), product and sum in fp32, the three planes in one launch.  stats_out is optional: {min, mean, max} of plane 0,
+ * 1, 2 from the same pass, bit for bit what nl_stack_frame_stats returns on each slot afterwards.  Per-pixel. */
+int nl_stack_rgb_scale_offset_clamp(nl_stack_t *h, const int planes[3], const float alpha[3], const float beta[3],
+                                    float stats_out[9]);
+/* findDarkestBlock (rgb.go:153-219): the mean colour of the block x block square with the lowest (r + g + b) / 3
+ * inside the border; the first minimum in row-major order wins, a NaN never does, and with no block in range the
+ * result is {MaxFloat32, MaxFloat32, MaxFloat32}.  The device computes every block's channel means (12 bytes per block
+ * cross PCIe), the host scans them.  Developer switch of nl_stack_set_dev_flags: bit 17 (131072) = no strip is staged
+ * in LDS (the results are the same). */
+int nl_stack_rgb_darkest_block(nl_stack_t *h, const int planes[3], int block, float border, nl_rgb_t *out);
+/* meanStarIntensity (rgb.go:223-281) over stars[sStart:sEnd] with sStart = int(float32(n) * skip_bright), sEnd = n -
+ * int(float32(n) * skip_dim): per star the pixels within (0.75 HFR + 0.01) of its centre whose three channels lie
+ * below clip, summed in the reference's order; the host folds the stars in order.  No star or an empty range gives
+ * {0, 0, 0}; no pixel at all the reference's 0 * +Inf = NaN. */
+int nl_stack_rgb_mean_star_intensity(nl_stack_t *h, const int planes[3], const nl_star_t *stars, int n_stars,
+                                     float skip_bright, float skip_dim, nl_rgb_t clip, nl_rgb_t *out);
+/* The scalar part of setBlackWhitePoints (rgb.go:125-145) in fp32, operation for operation.  Host only. */
+int nl_rgb_balance_coeffs(nl_rgb_t cur_shadows, nl_rgb_t cur_highlights, nl_rgb_t target_shadows,
+                          nl_rgb_t target_highlights, float alpha[3], float beta[3]);
+/* what SetBlackWhitePoints logs: the coefficients of both passes, the darkest block and the mean star colour */
+typedef struct nl_rgb_balance {
+    float alpha1[3], beta1[3];     /* first pass: location -> shadows, location + 3 scale -> highlights */
+    float alpha2[3], beta2[3];     /* second pass: darkest block -> shadows, mean star colour -> highlights */
+    nl_rgb_t darkest, stars;
+} nl_rgb_balance_t;
+/* SetBlackWhitePoints (rgb.go:94-120), the whole of OpRGBBalance.Apply behind its zero-stars guard, which stays with
+ * the caller: loc / scale are the channels' Stats.Location() / Scale(); the first clamp pass also reduces the
+ * statistics whose maxima times 0.9 clip the star pixels.  report may be NULL.  With the planes resident only the star
+ * list, the block means and these scalars cross PCIe. */
+int nl_stack_rgb_balance(nl_stack_t *h, const int planes[3], const nl_star_t *stars, int n_stars, int block,
+                         float border, float skip_bright, float skip_dim, nl_rgb_t shadows, nl_rgb_t highlights,
+                         const float loc[3], const float scale[3], nl_rgb_balance_t *report);
+/* ... on 3 * width * height floats of host memory (plane after plane, fits.Image.Data), in place, on a handle of the
+ * call's own */
+int nl_rgb_balance(float *planar_host, int width, int height, const nl_star_t *stars, int n_stars, int block,
+                   float border, float skip_bright, float skip_dim, nl_rgb_t shadows, nl_rgb_t highlights,
+                   const float loc[3], const float scale[3], nl_rgb_balance_t *report, int device);
+/* The chroma and hue steps of the OpHSL... operators (pixelops.go:441-550) on planes {h, c, l} (or {h, s, l}), one
+ * elementwise in-place kernel each; only the plane the reference writes is written, a pixel it skips keeps its bits,
+ * and a NaN in the deciding plane falls through the comparisons as in Go.  Per-pixel.
+ *   kind                   p[0] ... p[3]               per pixel
+ *   NL_CHROMA_GAMMA        gamma, threshold            l < threshold keeps c; else c = float32(pow(float64(c), gg)),
+ *                                                      gg = float64(1.0 / gamma)                          (:448-455)
+ *   NL_CHROMA_NEUTRALIZE   low, high                   as the reference computes it: it reads both bounds from .Low
+ *                                                      (:473), so l < low zeroes c and every other pixel keeps its
+ *                                                      bits; high is accepted and ignored                (:472-484)
+ *   NL_CHROMA_FOR_HUES     from, to, factor            where (from <= to && h > from && h < to) || (from > to &&
+ *                                                      (h > from || h < to)): c = float32(math.Max(0, math.Min(1,
+ *                                                      float64(c * factor))))                            (:501-511)
+ *   NL_ROTATE_HUES         from, to, offset, lthres    l < lthres keeps h; where the same hue test holds, h += offset
+ *                                                                                                        (:530-543)
+ * The operators' guards (Gamma == 1, Factor == 1, Offset == 0) act on their fields and stay with the caller. */
+#define NL_CHROMA_GAMMA       0
+#define NL_CHROMA_NEUTRALIZE  1
+#define NL_CHROMA_FOR_HUES    2
+#define NL_ROTATE_HUES        3
+typedef struct nl_chroma {
+    int32_t kind;   /* NL_CHROMA_* / NL_ROTATE_HUES */
+    float p[4];     /* the pixel function's arguments in the table's order; unused ones are ignored */
+} nl_chroma_t;
+int nl_stack_rgb_chroma(nl_stack_t *h, const int planes[3], const nl_chroma_t *op);
+/* The pixel loop of WriteTIFF16 (tiff16.go:50-87) / WriteJPG (writejpg.go:48-85), channel by channel as the gray export
+ * above.  out_host receives per pixel R G B A: bits 16 four big-endian uint16 with A = 0xFFFF, 8 bytes -- the layout of
+ * image.RGBA64.Pix -- bits 8 the bytes R G B 255 -- image.RGBA.Pix.  The planes stay as they are; 8 or 4 bytes per
+ * pixel cross PCIe instead of 12.  Per-pixel. */
+int nl_stack_rgb_export(nl_stack_t *h, const int planes[3], float min, float max, float gamma, int bits, void *out_host);
+/* ... of 3 * n floats of host memory, plane after plane (n < 2^31), on a handle of the call's own */
+int nl_export_rgb(const float *planar_host, int64_t n, float min, float max, float gamma, int bits, void *out_host,
+                  int device);
+
 /* ---- host-side operator mirror (nightlight_amd/host/, C++) ----
  * The reference's stack operator decoded from its JSON form and run through
  * MakePromises/Apply exactly as OpSequence would drive it

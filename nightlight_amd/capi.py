@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("NLSTACK_LIB") or os.path.join(_PKG, "libnlstack.so")
 ST_MEDIAN, ST_MEAN, ST_SIGMA, ST_WINSOR_SIGMA, ST_MAD_SIGMA, ST_LINEAR_FIT, ST_AUTO = range(7)
 WEIGHT_NONE, WEIGHT_EXPOSURE, WEIGHT_INVERSE_NOISE, WEIGHT_INVERSE_HFR = range(4)
 TONE_SCALE_OFFSET, TONE_NORMALIZE, TONE_GAMMA, TONE_PARTIAL_GAMMA, TONE_MIDTONES, TONE_SHIFT_BLACK = range(6)
+CHROMA_GAMMA, CHROMA_NEUTRALIZE, CHROMA_FOR_HUES, ROTATE_HUES = range(4)
 
 OK = 0
 ERR_INVALID_MODE = -1
@@ -66,6 +67,9 @@ EXPORTS = [
     "nl_stack_frame_tone", "nl_stack_result_tone", "nl_tone",
     "nl_stack_frame_export_gray", "nl_stack_result_export_gray", "nl_export_gray",
     "nl_stack_frame_project_from", "nl_group_frame_project_from", "nl_stack_project_tile_paths",
+    "nl_rgb_normalization", "nl_stack_frame_combine_from", "nl_stack_rgb_scale_offset_clamp",
+    "nl_stack_rgb_darkest_block", "nl_stack_rgb_mean_star_intensity", "nl_rgb_balance_coeffs", "nl_stack_rgb_balance",
+    "nl_rgb_balance", "nl_stack_rgb_chroma", "nl_stack_rgb_export", "nl_export_rgb",
 ]
 
 # nl_star_t = star.Star (findstars.go:30-37), 24 bytes
@@ -90,6 +94,22 @@ class Deband(C.Structure):
 class Tone(C.Structure):
     """nl_tone_t: one curve of the stretch command, the kind and the pixel function's arguments."""
     _fields_ = [("kind", C.c_int32), ("p", C.c_float * 3)]
+
+
+class Rgb(C.Structure):
+    """nl_rgb_t: fits.RGB (rgb.go:28-32)."""
+    _fields_ = [("r", C.c_float), ("g", C.c_float), ("b", C.c_float)]
+
+
+class RgbBalance(C.Structure):
+    """nl_rgb_balance_t: what SetBlackWhitePoints logs."""
+    _fields_ = [("alpha1", C.c_float * 3), ("beta1", C.c_float * 3), ("alpha2", C.c_float * 3),
+                ("beta2", C.c_float * 3), ("darkest", Rgb), ("stars", Rgb)]
+
+
+class Chroma(C.Structure):
+    """nl_chroma_t: one chroma or hue step of the OpHSL... operators, the kind and the pixel function's arguments."""
+    _fields_ = [("kind", C.c_int32), ("p", C.c_float * 4)]
 
 
 class NlError(RuntimeError):
@@ -299,6 +319,20 @@ def open_library(path):
     L.nl_stack_frame_project_from.argtypes = [vp, C.c_int, vp, C.c_int, _f32p, C.c_float]
     L.nl_group_frame_project_from.argtypes = [vp, C.c_int, vp, C.c_int, _f32p, C.c_float]
     L.nl_stack_project_tile_paths.argtypes = [vp, vp, C.c_int, _f32p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    _planes = C.POINTER(C.c_int)
+    # stars, n_stars, block, border, skip_bright, skip_dim, shadows, highlights, loc, scale, report
+    _balance_args = [vp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, Rgb, Rgb, _f32p, _f32p, C.POINTER(RgbBalance)]
+    L.nl_rgb_normalization.argtypes = [_f32p, _f32p, _f32p, _f32p]
+    L.nl_stack_frame_combine_from.argtypes = [vp, C.c_int, vp, C.c_int, C.c_float, C.c_float]
+    L.nl_stack_rgb_scale_offset_clamp.argtypes = [vp, _planes, _f32p, _f32p, _f32p]
+    L.nl_stack_rgb_darkest_block.argtypes = [vp, _planes, C.c_int, C.c_float, C.POINTER(Rgb)]
+    L.nl_stack_rgb_mean_star_intensity.argtypes = [vp, _planes, vp, C.c_int, C.c_float, C.c_float, Rgb, C.POINTER(Rgb)]
+    L.nl_rgb_balance_coeffs.argtypes = [Rgb, Rgb, Rgb, Rgb, _f32p, _f32p]
+    L.nl_stack_rgb_balance.argtypes = [vp, _planes] + _balance_args
+    L.nl_rgb_balance.argtypes = [_f32p, C.c_int, C.c_int] + _balance_args + [C.c_int]
+    L.nl_stack_rgb_chroma.argtypes = [vp, _planes, C.POINTER(Chroma)]
+    L.nl_stack_rgb_export.argtypes = [vp, _planes] + _gray_args
+    L.nl_export_rgb.argtypes = [_f32p, C.c_int64] + _gray_args + [C.c_int]
     return L
 
 

@@ -10,6 +10,7 @@
 
 #include "background.hpp"
 #include "blur.hpp"
+#include "colour.hpp"
 #include "deband.hpp"
 #include "dev_memory.hpp"
 #include "project.hpp"
@@ -30,15 +31,20 @@ int select_device(int device);
 // own per call carries stream and scratch, so concurrent calls share nothing.  run(h) runs on it; its error message
 // outlives the handle.  A handle that cannot be created gives NL_ERR_HIP with nl_stack_create's message.
 template <class Run>
-int with_scratch_handle(int width, int height, int device, Run run)
+int with_scratch_frames(int n_frames, int width, int height, int device, Run run)
 {
-    nl_stack_t *h = nl_stack_create(1, width, height, 0, height, device);
+    nl_stack_t *h = nl_stack_create(n_frames, width, height, 0, height, device);
     if (!h) return NL_ERR_HIP;
     const int rc = run(h);
     const std::string keep = g_err;
     nl_stack_destroy(h);
     g_err = keep;
     return rc;
+}
+template <class Run>
+int with_scratch_handle(int width, int height, int device, Run run)
+{
+    return with_scratch_frames(1, width, height, device, run);
 }
 
 // the inverse of the forward Transform2D t (internal/star/coord.go:159-199, fp32 as written there); a singular one is
@@ -47,7 +53,7 @@ int invert_transform(const float t[6], float inv[6]);
 
 }  // namespace nl
 
-using nl::cached_free, nl::cached_malloc, nl::dev_malloc, nl::fail, nl::g_err, nl::invert_transform, nl::select_device, nl::with_scratch_handle;
+using nl::cached_free, nl::cached_malloc, nl::dev_malloc, nl::fail, nl::g_err, nl::invert_transform, nl::select_device, nl::with_scratch_frames, nl::with_scratch_handle;
 
 #define NL_HIP(call)                                                                        \
     do {                                                                                    \
@@ -162,10 +168,12 @@ struct nl_stack {
         nl::BlurWork blur_work;
         // the tone curves with statistics (nl_stack_frame_tone, ...): the transformed element 0, one float
         nl::DevBuffer tone_seed;
+        // the colour steps (nl_stack_rgb_*): partials and seeds of three planes, block means, stars and their sums
+        nl::ColourWork colour_work;
         size_t bytes() const
         {
             return bp_diff.bytes + bp_seg.bytes + bp_list.bytes + bp_small.bytes + cfa.bytes + star_work.bytes() +
-                   back_work.bytes() + deband_work.bytes() + blur_work.bytes() + tone_seed.bytes;
+                   back_work.bytes() + deband_work.bytes() + blur_work.bytes() + tone_seed.bytes + colour_work.bytes();
         }
         void release(int device)
         {
@@ -179,6 +187,7 @@ struct nl_stack {
             deband_work.release();
             blur_work.release();
             tone_seed.release();
+            colour_work.release();
         }
     } frame_scratch;
     int max_grid = 0;
@@ -190,6 +199,7 @@ struct nl_stack {
 // developer switches of the projection (nl_stack_set_dev_flags; the others: nlstack_pass.hip) as launch_project takes them
 constexpr unsigned kDevProjectDirect = 32768u;       // no tile stages its source box in LDS
 constexpr unsigned kDevProjectPlainStores = 65536u;  // plain instead of nontemporal result stores
+constexpr unsigned kDevColourDirect = 131072u;       // the darkest-block means stage no strip in LDS
 inline unsigned project_switches(const nl_stack *h)
 {
     return ((h->dev_flags & kDevProjectDirect) ? nl::kProjDirectOnly : 0u) |

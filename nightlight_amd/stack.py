@@ -417,6 +417,55 @@ class StackHandle:
         return _export_gray(lambda *a: self._lib.nl_stack_result_export_gray(self._h, *a), self.tile_pixels, min, max,
                             gamma, bits)
 
+    # -- the rgb / lrgb command: three slots `planes` of this handle are the channels ------------------------------
+    def frame_combine_from(self, idx, src, src_idx, min, mult):
+        """The pixel loop of NewRGBFromChannels: slot idx = (slot src_idx of `src` - min) * mult; src_idx -1 reads the
+        last pass's result of `src`; src may be this handle and the same slot (in place)."""
+        capi.check(self._lib.nl_stack_frame_combine_from(self._h, int(idx), src._h, int(src_idx), float(min),
+                                                         float(mult)))
+
+    def rgb_scale_offset_clamp(self, planes, alpha, beta, stats=False):
+        """ScaleOffsetClampRGB on the three planes, in place.  stats=True: returns a (3, 3) array, {min, mean, max} per
+        plane from the same pass, the bits frame_stats would return afterwards."""
+        a, b = _f32x3(alpha), _f32x3(beta)
+        out = np.zeros(9, np.float32) if stats else None
+        capi.check(self._lib.nl_stack_rgb_scale_offset_clamp(self._h, _planes(planes), capi.fptr(a), capi.fptr(b),
+                                                             None if out is None else capi.fptr(out)))
+        return None if out is None else out.reshape(3, 3)
+
+    def rgb_darkest_block(self, planes, block, border):
+        """findDarkestBlock: the (r, g, b) means of the darkest block x block square inside the border."""
+        out = capi.Rgb()
+        capi.check(self._lib.nl_stack_rgb_darkest_block(self._h, _planes(planes), int(block), float(border),
+                                                        C.byref(out)))
+        return _rgb_out(out)
+
+    def rgb_mean_star_intensity(self, planes, stars, skip_bright, skip_dim, clip):
+        """meanStarIntensity over the star list (capi.STAR_DTYPE) with the channel clip levels `clip`."""
+        stars = np.ascontiguousarray(np.zeros(0, capi.STAR_DTYPE) if stars is None else stars, dtype=capi.STAR_DTYPE)
+        out = capi.Rgb()
+        capi.check(self._lib.nl_stack_rgb_mean_star_intensity(
+            self._h, _planes(planes), stars.ctypes.data_as(C.c_void_p), int(stars.size), float(skip_bright),
+            float(skip_dim), _rgb_in(clip), C.byref(out)))
+        return _rgb_out(out)
+
+    def rgb_balance(self, planes, stars, block, border, skip_bright, skip_dim, shadows, highlights, loc, scale):
+        """SetBlackWhitePoints on the three planes, in place (see rgb_balance).  Returns the report dict."""
+        return _rgb_balance(lambda *a: self._lib.nl_stack_rgb_balance(self._h, _planes(planes), *a), stars, block,
+                            border, skip_bright, skip_dim, shadows, highlights, loc, scale)
+
+    def rgb_chroma(self, planes, kind, *p):
+        """One chroma or hue step (capi.CHROMA_GAMMA (gamma, threshold), CHROMA_NEUTRALIZE (low, high), CHROMA_FOR_HUES
+        (from, to, factor), ROTATE_HUES (from, to, offset, lthres)) on planes {h, c, l}, in place."""
+        assert len(p) <= 4
+        op = capi.Chroma(int(kind), (C.c_float * 4)(*[float(v) for v in p]))
+        capi.check(self._lib.nl_stack_rgb_chroma(self._h, _planes(planes), C.byref(op)))
+
+    def rgb_export(self, planes, min, max, gamma=1.0, bits=16):
+        """WriteTIFF16 / WriteJPG's pixel loop on the three planes (see export_rgb); the planes stay as they are."""
+        return _export_rgb(lambda *a: self._lib.nl_stack_rgb_export(self._h, _planes(planes), *a), self.tile_pixels,
+                           min, max, gamma, bits)
+
     def frame_bin_from(self, idx, src, src_idx, n):
         """NewImageBinNxN of resident slot src_idx of the whole-image handle `src` into slot idx of this one, whose
         shape is bin_shape of the source's (n <= 1: a device copy)."""
@@ -893,6 +942,85 @@ def export_gray(frame, min, max, gamma=1.0, bits=16, device=None):
     dev = 0 if device is None else int(device)
     return _export_gray(lambda *a: capi.load().nl_export_gray(capi.fptr(src), int(src.size), *a, dev), src.size, min,
                         max, gamma, bits)
+
+
+def _planes(planes):
+    assert len(planes) == 3
+    return (C.c_int * 3)(*[int(v) for v in planes])
+
+
+def _f32x3(v):
+    a = np.ascontiguousarray(v, dtype=np.float32).reshape(-1)
+    assert a.size == 3
+    return a
+
+
+def _rgb_in(v):
+    return capi.Rgb(*[float(x) for x in v])
+
+
+def _rgb_out(c):
+    return np.array([c.r, c.g, c.b], np.float32)
+
+
+def rgb_normalization(mins, maxs):
+    """getCommonNormalizationFactors (rgb.go:65-78) of the channels' Stats.Min() / Max(): (min, mult).  Host only."""
+    mn, mult = C.c_float(), C.c_float()
+    capi.check(capi.load().nl_rgb_normalization(capi.fptr(_f32x3(mins)), capi.fptr(_f32x3(maxs)), C.byref(mn),
+                                                C.byref(mult)))
+    return np.float32(mn.value), np.float32(mult.value)
+
+
+def rgb_balance_coeffs(cur_shadows, cur_highlights, target_shadows, target_highlights):
+    """The scalar part of setBlackWhitePoints (rgb.go:125-145): (alpha[3], beta[3]).  Host only."""
+    alpha, beta = np.zeros(3, np.float32), np.zeros(3, np.float32)
+    capi.check(capi.load().nl_rgb_balance_coeffs(_rgb_in(cur_shadows), _rgb_in(cur_highlights), _rgb_in(target_shadows),
+                                                 _rgb_in(target_highlights), capi.fptr(alpha), capi.fptr(beta)))
+    return alpha, beta
+
+
+def _rgb_balance(call, stars, block, border, skip_bright, skip_dim, shadows, highlights, loc, scale):
+    """One nl_*rgb_balance call through `call(<parameters from stars on>)`: the dict of nl_rgb_balance_t."""
+    stars = np.ascontiguousarray(np.zeros(0, capi.STAR_DTYPE) if stars is None else stars, dtype=capi.STAR_DTYPE)
+    rep = capi.RgbBalance()
+    capi.check(call(stars.ctypes.data_as(C.c_void_p), int(stars.size), int(block), float(border), float(skip_bright),
+                    float(skip_dim), _rgb_in(shadows), _rgb_in(highlights), capi.fptr(_f32x3(loc)),
+                    capi.fptr(_f32x3(scale)), C.byref(rep)))
+    out = {k: np.array(getattr(rep, k), np.float32) for k in ("alpha1", "beta1", "alpha2", "beta2")}
+    out["darkest"], out["stars"] = _rgb_out(rep.darkest), _rgb_out(rep.stars)
+    return out
+
+
+def rgb_balance(planar, width, height, stars, block, border, skip_bright, skip_dim, shadows, highlights, loc, scale,
+                device=None):
+    """SetBlackWhitePoints (rgb.go:94-120) of a planar RGB image (3 * width * height floats, fits.Image.Data) on
+    `device` (default 0): loc / scale are the channels' Stats.Location() / Scale(), shadows / highlights the target
+    colours.  Bit-exact.  Returns (balanced image, report dict)."""
+    out = np.array(planar, dtype=np.float32, copy=True).reshape(-1)
+    assert out.size == 3 * int(width) * int(height)
+    lib = capi.load()
+    rep = _rgb_balance(lambda *a: lib.nl_rgb_balance(capi.fptr(out), int(width), int(height), *a,
+                                                     0 if device is None else int(device)),
+                       stars, block, border, skip_bright, skip_dim, shadows, highlights, loc, scale)
+    return out, rep
+
+
+def _export_rgb(call, n, min, max, gamma, bits):
+    """call(min, max, gamma, bits, out) into n pixels of R G B A: an (n, 4) array of uint8, or of big-endian uint16 as
+    the bytes lie in image.RGBA64.Pix"""
+    raw = np.empty(int(n) * (8 if int(bits) == 16 else 4), np.uint8)
+    capi.check(call(float(min), float(max), float(gamma), int(bits), raw.ctypes.data_as(C.c_void_p)))
+    return (raw.view(">u2") if int(bits) == 16 else raw).reshape(-1, 4)
+
+
+def export_rgb(planar, min, max, gamma=1.0, bits=16, device=None):
+    """The pixel loop of WriteTIFF16 (bits 16) / WriteJPG (bits 8) over a planar RGB image (3 * n floats): per pixel
+    R G B A with A all ones, as image.RGBA64.Pix / image.RGBA.Pix hold them."""
+    src = np.ascontiguousarray(planar, dtype=np.float32).reshape(-1)
+    assert src.size % 3 == 0
+    dev = 0 if device is None else int(device)
+    return _export_rgb(lambda *a: capi.load().nl_export_rgb(capi.fptr(src), src.size // 3, *a, dev), src.size // 3, min,
+                       max, gamma, bits)
 
 
 def _cstr(s):
