@@ -1,5 +1,5 @@
 // background.hpp -- background extraction (OpBackExtract: pre.NewBackground + Background.Subtract / Render,
-// internal/ops/pre/background.go:68-462) for the C ABI in nlstack_frame.hip.
+// internal/ops/pre/background.go:68-462) for the C ABI in nlstack_frame_pre.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

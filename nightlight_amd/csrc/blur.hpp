@@ -1,5 +1,5 @@
 // blur.hpp -- OpGaussianBlur / OpUnsharpMask (internal/ops/stretch/stretch.go:339-424, internal/ops/stretch/usm.go) for
-// the C ABI in nlstack_frame.hip.
+// the C ABI in nlstack_frame_stretch.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,5 +1,5 @@
 // colour.hpp -- the steps of the reference's rgb / lrgb command whose arithmetic is written out in its own source, on
-// three planes resident in a handle, for the C ABI in nlstack_frame.hip:
+// three planes resident in a handle, for the C ABI in nlstack_frame_rgb.hip:
 //   internal/fits/rgb.go:43-78        NewRGBFromChannels, getCommonNormalizationFactors
 //                       :94-149       SetBlackWhitePoints, setBlackWhitePoints
 //                       :153-219      findDarkestBlock

@@ -1,5 +1,5 @@
 // deband.hpp -- OpDebandHoriz / OpDebandVert (internal/ops/pre/banding.go:61-270) and OpBin's NewImageBinNxN
-// (internal/fits/fits.go:163-195) for the C ABI in nlstack_frame.hip.
+// (internal/fits/fits.go:163-195) for the C ABI in nlstack_frame_pre.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,8 +1,9 @@
 // nlstack_api.hip -- the C ABI of libnlstack.so (include/nlstack.h): error state, the device-memory cache, the pinned
 // staging pool and the stream pool; handle create / destroy / attach / weights / accessors; every upload and download,
-// FITS and projected ingest included.  Stack passes: nlstack_pass.hip; steps on one resident frame: nlstack_frame.hip;
-// what the three share: nlstack_internal.hpp.  There is no CPU fallback: without a HIP device every compute entry
-// point fails with NL_ERR_NO_DEVICE / NL_ERR_HIP.
+// FITS and projected ingest included.  Stack passes: nlstack_pass.hip; steps on one resident frame: nlstack_frame.hip
+// (statistics, median filters, projection) and, by the reference command they serve, nlstack_frame_pre.hip,
+// nlstack_frame_stretch.hip and nlstack_frame_rgb.hip; what all share: nlstack_internal.hpp.  There is no CPU fallback:
+// without a HIP device every compute entry point fails with NL_ERR_NO_DEVICE / NL_ERR_HIP.
 #include <math.h>
 #include <stdarg.h>
 #include <stdio.h>

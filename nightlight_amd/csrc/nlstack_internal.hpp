@@ -1,4 +1,5 @@
-// nlstack_internal.hpp -- what the three units of the C ABI (nlstack_api.hip, nlstack_pass.hip, nlstack_frame.hip)
+// nlstack_internal.hpp -- what the units of the C ABI (nlstack_api.hip, nlstack_pass.hip and, through
+// nlstack_frame_common.hpp, nlstack_frame.hip, nlstack_frame_pre.hip, nlstack_frame_stretch.hip, nlstack_frame_rgb.hip)
 // share: the handle and the error state (the allocator and the scratch types: dev_memory.hpp).  Private: no kernel
 // source includes it, not installed.
 #pragma once
@@ -149,7 +150,7 @@ struct nl_stack {
     bool stage_used[kStageSlots] = {false, false, false, false};
     int stage_next = 0;
     bool uploads_pending = false;
-    // scratch of the steps on one resident frame (nlstack_frame.hip), lazily allocated
+    // scratch of the steps on one resident frame (nlstack_frame*.hip), lazily allocated
     struct FrameScratch {
         // bad-pixel step (nl_stack_frame_badpixel): diff, per-workgroup lists, ordered list (parked between handles);
         // nl::BpParams + per-workgroup list lengths, offsets, bad-pixel counts

@@ -113,7 +113,7 @@ struct FastArgs {
 
 // sets what nl_last_error() returns on this thread (nlstack_api.hip)
 void set_last_error(const char *msg);
-// nl_stack_frame_project_from / nl_group_frame_project_from (nlstack_frame.hip); who = the call's name in messages
+// nl_stack_frame_project_from / nl_group_frame_project_from (nlstack_frame.hip, with nl::stack_settle); who = the call's name in messages
 int stack_project_from(nl_stack_t *dst, int dst_idx, nl_stack_t *src, int src_idx, const float trans[6],
                        float out_of_bounds, const char *who, bool from_group);
 int stack_settle(nl_stack_t *h);

@@ -1,7 +1,7 @@
 // tone.hpp -- the per-pixel curves of the stretch command (OpNormalizeRange, OpStretchIterative's two pixel passes,
 // OpMidtones, OpGamma, OpGammaPP, OpScaleBlack: internal/ops/stretch/stretch.go:40-335 over internal/fits/pixelops.go)
 // and OpSave's quantisation to 16- or 8-bit gray (internal/fits/tiff16.go:108-135, writejpg.go:106-131) for the C ABI in
-// nlstack_frame.hip.
+// nlstack_frame_stretch.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -718,11 +718,28 @@ class Calibration:
             pass
 
 
+def _device(device):
+    """The device of a host form: `device`, default 0."""
+    return 0 if device is None else int(device)
+
+
+def _host_frame(frame, width=None, height=None, copy=True, planes=1):
+    """A host frame (or `planes` of them) as flat contiguous float32: a copy of the caller's that the library may write
+    in place, or with copy=False the caller's own where it already is one.  Without width and height any size that
+    holds `planes` whole planes."""
+    out = np.array(frame, dtype=np.float32, copy=True) if copy else np.ascontiguousarray(frame, dtype=np.float32)
+    out = out.reshape(-1)
+    if width is None:
+        assert out.size % int(planes) == 0
+    else:
+        assert out.size == int(planes) * int(width) * int(height)
+    return out
+
+
 def preprocess_frame(frame, width, height, calib=None, sigma_low=3.0, sigma_high=5.0, frame_id=0, device=None):
     """OpCalibrate then OpBadPixel (mono) on one host frame, on calib's device (else `device`, default 0).
     Returns (out, removed, (diff_mean, diff_std))."""
-    frame = np.ascontiguousarray(frame, dtype=np.float32).reshape(-1)
-    assert frame.size == int(width) * int(height)
+    frame = _host_frame(frame, width, height, copy=False)
     if device is None:
         device = calib.device if calib is not None else 0
     out = np.empty_like(frame)
@@ -755,11 +772,10 @@ def find_stars(frame, width, height, location, scale, star_sig=15.0, bp_sigma=5.
     """star.FindStars (internal/star/findstars.go:59-103) on one host frame on `device` (default 0).
     location / scale: the frame's Stats.Location() / Scale(); diff_std: MedianDiffStats.StdDev() or None (nil).
     Returns (stars, sum_of_shifts, avg_hfr): stars a structured array with the fields index value x y mass hfr."""
-    frame = np.ascontiguousarray(frame, dtype=np.float32).reshape(-1)
-    assert frame.size == int(width) * int(height)
+    frame = _host_frame(frame, width, height, copy=False)
     lib = capi.load()
     return _find_stars(lambda *a: lib.nl_find_stars(capi.fptr(frame), int(width), int(height), *a,
-                                                    0 if device is None else int(device)),
+                                                    _device(device)),
                        location, scale, star_sig, bp_sigma, star_in_out, radius, diff_std)
 
 
@@ -785,11 +801,10 @@ def back_extract(frame, width, height, stars, grid_size, hfr_factor=4.0, sigma=1
     find_stars returned, then Subtract (render=False) or Render + subtract (render=True), on `device` (default 0).
     Returns (out, background or None, cells, info): out the subtracted frame (None when grid_size <= 0, the
     reference's no-op), cells the smoothed grid, info the dict of nl_background_t."""
-    out = np.array(frame, dtype=np.float32, copy=True).reshape(-1)
-    assert out.size == int(width) * int(height)
+    out = _host_frame(frame, width, height)
     lib = capi.load()
     _, bg, cells, info = _back_extract(
-        lambda *a: lib.nl_back_extract(capi.fptr(out), int(width), int(height), *a, 0 if device is None else int(device)),
+        lambda *a: lib.nl_back_extract(capi.fptr(out), int(width), int(height), *a, _device(device)),
         width, height, stars, grid_size, hfr_factor, sigma, clip, render)
     return (out if int(grid_size) > 0 else None), bg, cells, info
 
@@ -802,9 +817,8 @@ def _deband(call, percentile, window, sigma, location, scale):
 
 
 def _deband_host(entry, frame, width, height, percentile, window, sigma, location, scale, device):
-    out = np.array(frame, dtype=np.float32, copy=True).reshape(-1)
-    assert out.size == int(width) * int(height)
-    info = _deband(lambda *a: entry(capi.fptr(out), int(width), int(height), *a, 0 if device is None else int(device)),
+    out = _host_frame(frame, width, height)
+    info = _deband(lambda *a: entry(capi.fptr(out), int(width), int(height), *a, _device(device)),
                    percentile, window, sigma, location, scale)
     return out, info
 
@@ -835,12 +849,11 @@ def bin_shape(width, height, n):
 def bin_nxn(frame, width, height, n, device=None):
     """fits.NewImageBinNxN (internal/fits/fits.go:163-195) of one host frame on `device` (default 0); n <= 1 copies.
     Returns (out, out_width, out_height)."""
-    frame = np.ascontiguousarray(frame, dtype=np.float32).reshape(-1)
-    assert frame.size == int(width) * int(height)
+    frame = _host_frame(frame, width, height, copy=False)
     ow, oh = bin_shape(width, height, n)
     out = np.empty(ow * oh, np.float32)
     capi.check(capi.load().nl_bin_nxn(capi.fptr(frame), int(width), int(height), int(n), capi.fptr(out),
-                                      0 if device is None else int(device)))
+                                      _device(device)))
     return out, ow, oh
 
 
@@ -867,19 +880,13 @@ def blur_tap_paths(n_taps):
     return bool(row.value), bool(col.value)
 
 
-def _host_frame(frame, width, height):
-    out = np.array(frame, dtype=np.float32, copy=True).reshape(-1)
-    assert out.size == int(width) * int(height)
-    return out
-
-
 def convolve_separable(frame, width, height, taps, device=None):
     """Convolve1DX then Convolve1DY (usm.go:85-114) of one host frame with the caller's taps on `device` (default 0);
     bit-exact.  Returns the filtered frame."""
     out = _host_frame(frame, width, height)
     t = np.ascontiguousarray(taps, dtype=np.float32).reshape(-1)
     capi.check(capi.load().nl_convolve_separable(capi.fptr(out), int(width), int(height), capi.fptr(t) if t.size else None,
-                                                 int(t.size), 0 if device is None else int(device)))
+                                                 int(t.size), _device(device)))
     return out
 
 
@@ -887,19 +894,18 @@ def gaussian_blur(frame, width, height, sigma, device=None):
     """OpGaussianBlur (internal/ops/stretch/stretch.go:368-376) of one host frame; sigma 0 returns it unchanged."""
     out = _host_frame(frame, width, height)
     capi.check(capi.load().nl_gaussian_blur(capi.fptr(out), int(width), int(height), float(sigma),
-                                            0 if device is None else int(device)))
+                                            _device(device)))
     return out
 
 
 def unsharp_mask(frame, width, height, sigma, gain, min, max, abs_threshold, device=None):
     """UnsharpMask (usm.go:153-159) of one host frame: pixels below abs_threshold stay, the others become
     d + (d - blurred) * gain clipped to min, then max; sigma 0 or gain 0 returns the frame unchanged."""
-    src = np.ascontiguousarray(frame, dtype=np.float32).reshape(-1)
-    assert src.size == int(width) * int(height)
+    src = _host_frame(frame, width, height, copy=False)
     out = np.empty_like(src)
     capi.check(capi.load().nl_unsharp_mask(capi.fptr(src), capi.fptr(out), int(width), int(height), float(sigma),
                                            float(gain), float(min), float(max), float(abs_threshold),
-                                           0 if device is None else int(device)))
+                                           _device(device)))
     return out
 
 
@@ -921,8 +927,8 @@ def tone(frame, kind, *p, stats=False, device=None):
     TONE_NORMALIZE (min, max), TONE_GAMMA (g), TONE_PARTIAL_GAMMA (from, to, g), TONE_MIDTONES (mid, black),
     TONE_SHIFT_BLACK (before, after).  Bit-exact but for pixels whose power falls on a rounding boundary (one fp32 ulp).
     Returns the transformed frame; with stats=True (frame, (min, mean, max)) from the same pass."""
-    out = np.array(frame, dtype=np.float32, copy=True).reshape(-1)
-    dev = 0 if device is None else int(device)
+    out = _host_frame(frame)
+    dev = _device(device)
     st = _tone(lambda *a: capi.load().nl_tone(capi.fptr(out), int(out.size), *a, dev), kind, p, stats)
     return (out, st) if stats else out
 
@@ -938,8 +944,8 @@ def export_gray(frame, min, max, gamma=1.0, bits=16, device=None):
     """OpSave's pixel loop (WriteMonoTIFF16 / WriteMonoJPG) over a host frame: (d - min) / (max - min) clipped to
     [0, 1] (NaN: 0), gamma, then counts of 16 bits (returned as big-endian uint16, the byte layout of Go's
     image.Gray16.Pix) or 8 bits (uint8) by truncation."""
-    src = np.ascontiguousarray(frame, dtype=np.float32).reshape(-1)
-    dev = 0 if device is None else int(device)
+    src = _host_frame(frame, copy=False)
+    dev = _device(device)
     return _export_gray(lambda *a: capi.load().nl_export_gray(capi.fptr(src), int(src.size), *a, dev), src.size, min,
                         max, gamma, bits)
 
@@ -996,11 +1002,10 @@ def rgb_balance(planar, width, height, stars, block, border, skip_bright, skip_d
     """SetBlackWhitePoints (rgb.go:94-120) of a planar RGB image (3 * width * height floats, fits.Image.Data) on
     `device` (default 0): loc / scale are the channels' Stats.Location() / Scale(), shadows / highlights the target
     colours.  Bit-exact.  Returns (balanced image, report dict)."""
-    out = np.array(planar, dtype=np.float32, copy=True).reshape(-1)
-    assert out.size == 3 * int(width) * int(height)
+    out = _host_frame(planar, width, height, planes=3)
     lib = capi.load()
     rep = _rgb_balance(lambda *a: lib.nl_rgb_balance(capi.fptr(out), int(width), int(height), *a,
-                                                     0 if device is None else int(device)),
+                                                     _device(device)),
                        stars, block, border, skip_bright, skip_dim, shadows, highlights, loc, scale)
     return out, rep
 
@@ -1016,9 +1021,8 @@ def _export_rgb(call, n, min, max, gamma, bits):
 def export_rgb(planar, min, max, gamma=1.0, bits=16, device=None):
     """The pixel loop of WriteTIFF16 (bits 16) / WriteJPG (bits 8) over a planar RGB image (3 * n floats): per pixel
     R G B A with A all ones, as image.RGBA64.Pix / image.RGBA.Pix hold them."""
-    src = np.ascontiguousarray(planar, dtype=np.float32).reshape(-1)
-    assert src.size % 3 == 0
-    dev = 0 if device is None else int(device)
+    src = _host_frame(planar, copy=False, planes=3)
+    dev = _device(device)
     return _export_rgb(lambda *a: capi.load().nl_export_rgb(capi.fptr(src), src.size // 3, *a, dev), src.size // 3, min,
                        max, gamma, bits)
 
@@ -1040,8 +1044,7 @@ def preprocess_frame_cfa(frame, width, height, channel, cfa="RGGB", calib=None, 
     """OpCalibrate, OpBadPixel and OpDebayer on one host frame, on calib's device (else `device`, default 0).
     Returns (out, out_width, out_height, removed, (mean, std)): the Bayer branch's delta statistics, or the mono
     MedianDiffStats when channel is ""."""
-    frame = np.ascontiguousarray(frame, dtype=np.float32).reshape(-1)
-    assert frame.size == int(width) * int(height)
+    frame = _host_frame(frame, width, height, copy=False)
     if device is None:
         device = calib.device if calib is not None else 0
     lib = capi.load()
