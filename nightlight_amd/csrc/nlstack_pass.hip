@@ -37,7 +37,8 @@ constexpr unsigned kDevNoCertificate = 16384u;     // winsorization loops withou
 // reported.  A handle that lives for one Apply never has one: its pass ran with 16 384-workgroup replay grids and the
 // plain protocol (headline stack: 2.04 instead of 1.73 ms).  The lengths are therefore also remembered per geometry --
 // frames, tile pixels, mode, weighted -- in a small process-wide table: the next handle of that geometry starts from
-// what the last one saw (stacks of one session resemble each other; a wrong hint costs time, never correctness).
+// what the last one saw (stacks of one session resemble each other; a wrong hint costs time, never correctness:
+// tests/test_gpu_pass_history.py runs hints that are wrong by orders of magnitude, both ways, against the oracle).
 struct HintKey { int frames; int64_t npix; int mode; bool weighted; };
 struct HintEntry { HintKey key; unsigned fb, gen; };
 std::mutex g_hint_mu;

@@ -565,6 +565,11 @@ class StackGroup:
     def fill_synthetic(self, seed=0x4E4C5354):
         capi.check(self._lib.nl_group_fill_synthetic(self._g, C.c_uint64(seed)))
 
+    def set_active_frames(self, n):
+        """StackHandle.set_active_frames on every tile."""
+        capi.check(self._lib.nl_group_set_active_frames(self._g, int(n)))
+        self.n_frames = int(n)
+
     def set_weights(self, weights):
         w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float32)
         capi.check(self._lib.nl_group_set_weights(self._g, capi.fptr(w) if w is not None else None))

@@ -5,26 +5,11 @@ OpStack.Apply, internal/ops/stack/stack.go:156-190."""
 import numpy as np
 import pytest
 
-from util import bits_equal, describe_mismatch, make_frames, same_values
+from util import RTOL, bits_equal, close_values, describe_mismatch, make_frames, same_values
 
 pytestmark = pytest.mark.gpu
 
 MODES = {0: "median", 1: "mean", 2: "sigma", 3: "winsor", 4: "mad", 5: "linearfit"}
-
-
-# fp32 tolerance of the north star ("within 1e-5 relative"); only the
-# register-resident sigma kernel needs it (its sums run in sorted order, the
-# reference's in quickselect order) -- everything else is bit-exact.
-RTOL = 1e-5
-
-
-def close_values(a, b, rtol=RTOL):
-    a = np.asarray(a, np.float32)
-    b = np.asarray(b, np.float32)
-    if a.shape != b.shape or not np.array_equal(np.isnan(a), np.isnan(b)):
-        return False
-    ok = ~np.isnan(a) & (a != b)          # equal values (incl. +-Inf) are fine as they are
-    return bool(np.all(np.abs(a[ok].astype(np.float64) - b[ok]) <= rtol * np.abs(b[ok].astype(np.float64))))
 
 
 def run_both(nl, oracle, mode, frames, width, height, weights, sl, sh, ref_loc=0.0, exact=True):

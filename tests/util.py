@@ -48,6 +48,21 @@ def same_values(a, b):
     return a.shape == b.shape and np.array_equal(a, b, equal_nan=True)
 
 
+# fp32 tolerance of the north star ("within 1e-5 relative"); only the
+# register-resident sigma kernel needs it (its sums run in sorted order, the
+# reference's in quickselect order) -- everything else is bit-exact.
+RTOL = 1e-5
+
+
+def close_values(a, b, rtol=RTOL):
+    a = np.asarray(a, np.float32)
+    b = np.asarray(b, np.float32)
+    if a.shape != b.shape or not np.array_equal(np.isnan(a), np.isnan(b)):
+        return False
+    ok = ~np.isnan(a) & (a != b)          # equal values (incl. +-Inf) are fine as they are
+    return bool(np.all(np.abs(a[ok].astype(np.float64) - b[ok]) <= rtol * np.abs(b[ok].astype(np.float64))))
+
+
 def describe_mismatch(got, want, limit=5):
     bad = np.flatnonzero(~((got == want) | (np.isnan(got) & np.isnan(want))))
     rows = ["%d: got %r want %r" % (i, got[i], want[i]) for i in bad[:limit]]
