@@ -67,6 +67,29 @@ func GroupProjectFrom(g unsafe.Pointer, idx int, src unsafe.Pointer, srcIdx int,
 	return nil
 }
 
+// LocationScale is Stats.Location() / Scale() (internal/stats/stats.go:225-244) of a frame that is resident on the
+// device: slot idx of the whole-image handle h (idx < 0: the last pass's result), with the estimator the reference
+// runs (stats.LSEstimator as an int, 3 = LSESCMedianQn by default; 2 = LSEIKSS is not implemented on the device).
+// The reference seeds every sampling call from the clock; here the seeds of one estimate derive from key, and the
+// result is the reference's for those seeds, bit for bit.  minMax: nil, or the cached Stats.Min() / Max() where
+// UpdateCachedWith has moved them away from the frame's own.
+func LocationScale(h unsafe.Pointer, idx int, estimator int, key uint64, minMax *[2]float32) (location, scale float32, err error) {
+	runtime.LockOSThread() // nl_last_error() is per OS thread
+	defer runtime.UnlockOSThread()
+	var seeds [C.NL_LOCSCALE_MAX_SEEDS]C.uint32_t
+	C.nl_locscale_seeds(C.uint64_t(key), &seeds[0], C.NL_LOCSCALE_MAX_SEEDS)
+	var mm *C.float
+	if minMax != nil {
+		mm = (*C.float)(unsafe.Pointer(&minMax[0]))
+	}
+	var l, s C.float
+	if rc := C.nl_stack_frame_location_scale((*C.nl_stack_t)(h), C.int(idx), C.int(estimator), C.NL_LOCSCALE_SAMPLES,
+		&seeds[0], C.NL_LOCSCALE_MAX_SEEDS, mm, &l, &s, nil); rc != C.NL_OK {
+		return 0, 0, lastError()
+	}
+	return float32(l), float32(s), nil
+}
+
 // Apply stacks a set of light frames on the GPUs.  Same contract as
 // internal/ops/stack/stack.go:115-227: mode validation and auto selection,
 // weights from getWeights (kept in Go, stack.go:231-270), one result image with

@@ -355,6 +355,11 @@ int nl_stack_frame_noise(nl_stack_t *h, int idx, float *noise);
  * (stack.go:241-253).  noise_out: n_frames floats or NULL. */
 int nl_stack_weights_from_noise(nl_stack_t *h, float *noise_out);
 
+/* ---- Stats.Location() / Scale() of a resident frame (internal/stats/stats.go:225-244) ----
+ * nl_stack_frame_location_scale, nl_location_scale, nl_locscale_seeds, nl_locscale_t and the NL_LSE_* estimators:
+ * declared in nlstack_locscale.h, which is part of this interface. */
+#include "nlstack_locscale.h"
+
 /* ---- formats and steps either side of the stack (F3, F4) ----
  * A frame goes from its on-disk bytes to its slot of the stack buffer without
  * a CPU pass.  All of these are bit-exact restatements (elementwise fp32, the
@@ -500,7 +505,7 @@ int nl_stack_upload_frame_cfa(nl_stack_t *h, int idx, const float *raw_host, int
  * copy it straight into a []star.Star.
  *
  * location, scale: the caller's f.Stats.Location() / Scale(), as OpStarDetect.Apply passes them
- * (pre/preprocess.go:448); this library does not estimate them.  diff_std: f.MedianDiffStats.StdDev()
+ * (pre/preprocess.go:448); nl_stack_frame_location_scale estimates them on the resident frame.  diff_std: f.MedianDiffStats.StdDev()
  * (nl_stack_frame_badpixel's diff_stats_out[1]); NaN means MedianDiffStats == nil.  At most capacity
  * stars are written to stars_out; *n_stars always receives the full count.  sum_of_shifts, avg_hfr:
  * FindStars' other two results (avg_hfr is NaN when no star is left, 0/0 as there).  n_stars,
@@ -587,7 +592,7 @@ int nl_stack_frame_back_extract(nl_stack_t *h, int idx, int grid_size, float hfr
  * percentiles, fixWindowEdge (:134-162), the window medians and the factors median / percentile run on
  * the host literally; then every pixel is multiplied by its row's / column's factor on the device.
  * threshold is MaxFloat32 when sigma == 0, else location + sigma * scale with the caller's
- * f.Stats.Location() / Scale() (as for nl_find_stars; this library does not estimate them).
+ * f.Stats.Location() / Scale() (as for nl_find_stars; from nl_stack_frame_location_scale when the frame is resident).
  * info (may be NULL): what the reference's log line prints, "... threshold %.2f, factors in [%.3f, %.3f]".
  * The operators' own guards -- percentile <= 0 or >= 100, and for horiz window <= 0 (:62, :198) -- are
  * no-ops: NL_OK, every bit of the frame unchanged, info = {threshold, 1, 0}.  Without a device every
@@ -673,7 +678,7 @@ int nl_stack_project_tile_paths(nl_stack_t *dst, nl_stack_t *src, int src_idx, c
  * the Go binary's; everything after the taps is bit-exact, and nl_convolve_separable has no reservation.
  * min, max and abs_threshold are the caller's scalars (OpUnsharpMask: f.Stats.Min(), f.Stats.Max(),
  * Location() + Scale() * Threshold; OpHSLUnsharpMask: the luminance plane's), as location / scale are for
- * nl_find_stars.  The operators' own guards -- sigma == 0 in the blur and unsharp-mask entries, gain == 0 in
+ * nl_find_stars (nl_stack_frame_location_scale).  The operators' own guards -- sigma == 0 in the blur and unsharp-mask entries, gain == 0 in
  * the unsharp-mask entries (stretch.go:369, :414) -- are no-ops: NL_OK, every bit unchanged (the host
  * unsharp mask copies in to out).
  * Deviations, all NL_ERR_INVALID_ARG with a message naming the site:
@@ -746,7 +751,7 @@ int nl_blur_tap_paths(int n_taps, int *row_staged, int *col_staged);
  * Guards: g == 1 of NL_TONE_GAMMA (OpGamma.Apply, stretch.go:240) is a no-op that leaves every bit.  The g == 1 guard
  * of OpGammaPP (:279) and the guards of OpStretchIterative, OpMidtones and OpScaleBlack (:104, :196, :323) act on the
  * operator's fields, not on the pixel function's arguments: they stay with the caller.  Location() / Scale() are the
- * caller's scalars as everywhere else.
+ * caller's scalars as everywhere else (nl_stack_frame_location_scale gives them without a download).
  * Statistics: every one of these curves ends in Stats.Clear(), and the next operator asks for Min() / Mean() / Max()
  * again.  mn, mean, mx are optional; when any is non-NULL the kernel also reduces what it writes, and the three
  * values are bit for bit what nl_stack_frame_stats would return on the slot immediately afterwards (a no-op fills
@@ -790,7 +795,8 @@ int nl_export_gray(const float *data_host, int64_t n, float min, float max, floa
  * An RGB (or HCL / HSLuv) image is three slots of one whole-image handle, named by planes[3] in the reference's channel
  * order {0, 1, 2}: three distinct valid slot indices.  The entries take the planes as they are: the conversions between
  * colour spaces (RGBToHSLuv, HSLuvToRGB, MonoToHSLuvLum), SCNR and the target of OpHSLScaleBlack are go-colorful's
- * arithmetic, not the reference's own, and stay with the caller; so do Stats.Location() / Scale() as everywhere else.
+ * arithmetic, not the reference's own, and stay with the caller; Stats.Location() / Scale() are arguments as everywhere else
+ * (one nl_stack_frame_location_scale per plane).
  * Everything here is bit-exact against the reference: fp32 without FMA, sums in its order, Go's Min / Max semantics (a
  * NaN stays NaN, -0 and every negative become +0); the two powers (NL_CHROMA_GAMMA, the export's gamma) carry the
  * reservation of the tone curves above (one fp32 ulp / one count at a rounding boundary).
@@ -835,7 +841,7 @@ typedef struct nl_rgb_balance {
     nl_rgb_t darkest, stars;
 } nl_rgb_balance_t;
 /* SetBlackWhitePoints (rgb.go:94-120), the whole of OpRGBBalance.Apply behind its zero-stars guard, which stays with
- * the caller: loc / scale are the channels' Stats.Location() / Scale(); the first clamp pass also reduces the
+ * the caller: loc / scale are the channels' Stats.Location() / Scale() (nl_stack_frame_location_scale per plane); the first clamp pass also reduces the
  * statistics whose maxima times 0.9 clip the star pixels.  report may be NULL.  With the planes resident only the star
  * list, the block means and these scalars cross PCIe. */
 int nl_stack_rgb_balance(nl_stack_t *h, const int planes[3], const nl_star_t *stars, int n_stars, int block,

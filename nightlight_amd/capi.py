@@ -17,6 +17,9 @@ ST_MEDIAN, ST_MEAN, ST_SIGMA, ST_WINSOR_SIGMA, ST_MAD_SIGMA, ST_LINEAR_FIT, ST_A
 WEIGHT_NONE, WEIGHT_EXPOSURE, WEIGHT_INVERSE_NOISE, WEIGHT_INVERSE_HFR = range(4)
 TONE_SCALE_OFFSET, TONE_NORMALIZE, TONE_GAMMA, TONE_PARTIAL_GAMMA, TONE_MIDTONES, TONE_SHIFT_BLACK = range(6)
 CHROMA_GAMMA, CHROMA_NEUTRALIZE, CHROMA_FOR_HUES, ROTATE_HUES = range(4)
+LSE_MEAN_STDDEV, LSE_MEDIAN_MAD, LSE_IKSS, LSE_SC_MEDIAN_QN, LSE_HISTOGRAM = range(5)     # stats.go:31-37
+LOCSCALE_SAMPLES = 131072
+LOCSCALE_MAX_SEEDS = 25
 
 OK = 0
 ERR_INVALID_MODE = -1
@@ -72,6 +75,9 @@ EXPORTS = [
     "nl_rgb_balance", "nl_stack_rgb_chroma", "nl_stack_rgb_export", "nl_export_rgb",
 ]
 
+# every symbol include/nlstack_locscale.h declares (the part of the interface nlstack.h includes)
+LOCSCALE_EXPORTS = ["nl_stack_frame_location_scale", "nl_location_scale", "nl_locscale_seeds"]
+
 # nl_star_t = star.Star (findstars.go:30-37), 24 bytes
 STAR_DTYPE = np.dtype([("index", "<i4"), ("value", "<f4"), ("x", "<f4"), ("y", "<f4"), ("mass", "<f4"),
                        ("hfr", "<f4")])
@@ -89,6 +95,14 @@ class Background(C.Structure):
 class Deband(C.Structure):
     """nl_deband_t: what the debanding operators' log lines print (banding.go:129, :267)."""
     _fields_ = [("threshold", C.c_float), ("lowest", C.c_float), ("highest", C.c_float)]
+
+
+class LocScale(C.Structure):
+    """nl_locscale_t: how an estimate of location and scale came about."""
+    _fields_ = [("iterations", C.c_int32), ("converged", C.c_int32), ("seeds_used", C.c_int32),
+                ("draws", C.c_uint32 * LOCSCALE_MAX_SEEDS), ("min", C.c_float), ("max", C.c_float),
+                ("epsilon", C.c_float), ("peak_bin", C.c_uint32), ("peak_count", C.c_uint32),
+                ("half_width", C.c_uint32)]
 
 
 class Tone(C.Structure):
@@ -239,6 +253,11 @@ def open_library(path):
     L.nl_stack_accumulate_finalize.argtypes = [vp, C.c_float, _f32p]
     L.nl_stack_frame_stats.argtypes = [vp, C.c_int, _f32p, _f32p, _f32p, C.POINTER(C.c_double)]
     L.nl_stack_frame_noise.argtypes = [vp, C.c_int, _f32p]
+    _u32p = C.POINTER(C.c_uint32)
+    _locscale_args = [C.c_int, C.c_int, _u32p, C.c_int, _f32p, _f32p, _f32p, C.POINTER(LocScale)]
+    L.nl_stack_frame_location_scale.argtypes = [vp, C.c_int] + _locscale_args
+    L.nl_location_scale.argtypes = [_f32p, C.c_int, C.c_int] + _locscale_args + [C.c_int]
+    L.nl_locscale_seeds.argtypes = [C.c_uint64, _u32p, C.c_int]
     L.nl_stack_weights_from_noise.argtypes = [vp, _f32p]
     L.nl_median_filter_3x3.argtypes = [_f32p, _f32p, C.c_int, C.c_int, C.c_int]
     L.nl_median_filter_mask.argtypes = [_f32p, _f32p, C.c_int64, C.POINTER(C.c_int32), C.c_int, C.c_int]

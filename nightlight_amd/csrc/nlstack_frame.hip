@@ -1,5 +1,5 @@
-// nlstack_frame.hip -- steps on one resident frame that belong to no single command: statistics and noise (stats.go,
-// noise.go), the affine step, the median filters (ops/pre/badpixels.go:54-77, internal/median/gather.go:26-38), OpAlign's
+// nlstack_frame.hip -- steps on one resident frame that belong to no single command: statistics, location and scale,
+// and noise (stats.go, noise.go; the estimators' kernels in locscale.hip), the affine step, the median filters (ops/pre/badpixels.go:54-77, internal/median/gather.go:26-38), OpAlign's
 // projection from a resident frame, and what the four units of the frame steps share (nlstack_frame_common.hpp; the
 // others: nlstack_frame_pre.hip, _stretch.hip, _rgb.hip).  Kernels in frame_stats.hip and project.hip.
 #include <assert.h>
@@ -253,6 +253,94 @@ int nl_stack_frame_stats(nl_stack_t *h, int idx, float *mn, float *mean, float *
     float *d;
     const int rc = resident_entry(h, idx, "frame_stats", false, &d);
     return rc == NL_OK ? frame_stats_impl(h, d, h->npix, mn, mean, mx, variance) : rc;
+}
+
+// ---- Stats.Location() / Scale() (stats.go:225-244; kernels and the sampling calls in locscale.hip) ----------------
+
+// what needs no device: the estimator, the sample count, the seeds it reads
+static int locscale_check(const char *who, int estimator, int num_samples, const uint32_t *seeds, int n_seeds,
+                          float *location, float *scale)
+{
+    if (!location || !scale) return fail(NL_ERR_INVALID_ARG, "%s: null output", who);
+    if (estimator == NL_LSE_IKSS)
+        return fail(NL_ERR_INVALID_ARG, "%s: estimator %d, LSEIKSS (stats.go:535-566), sorts the whole frame: not implemented on the device",
+                    who, estimator);
+    if (estimator < NL_LSE_MEAN_STDDEV || estimator > NL_LSE_HISTOGRAM)
+        return fail(NL_ERR_INVALID_ARG, "%s: unknown estimator %d (stats.go:31-37)", who, estimator);
+    const int need = estimator == NL_LSE_MEDIAN_MAD ? 2 : estimator == NL_LSE_SC_MEDIAN_QN ? NL_LOCSCALE_MAX_SEEDS : 0;
+    if (need == 0) return NL_OK;
+    if (num_samples < 4 || num_samples > nl::kLocScaleMaxSamples)
+        return fail(NL_ERR_INVALID_ARG, "%s: %d samples (4 .. %d)", who, num_samples, nl::kLocScaleMaxSamples);
+    if (n_seeds < need || !seeds)
+        return fail(NL_ERR_INVALID_ARG, "%s: %d seeds, estimator %d reads %d", who, seeds ? n_seeds : 0, estimator, need);
+    for (int i = 0; i < need; i++)
+        if (seeds[i] == 0)
+            return fail(NL_ERR_INVALID_ARG, "%s: seed %d is zero (fastrand would replace it by one from the clock)", who, i);
+    return NL_OK;
+}
+
+static int locscale_impl(nl_stack_t *h, const float *d, const char *who, int estimator, int num_samples,
+                         const uint32_t *seeds, const float *min_max, float *location, float *scale,
+                         nl_locscale_t *info)
+{
+    int rc = need_whole_frame(h, who, "the samples come from the whole frame");
+    if (rc != NL_OK) return rc;
+    if (h->npix < 2) return fail(NL_ERR_INVALID_ARG, "%s: a frame of %lld pixels (Uint32n(len(data) - 1), stats.go:440)", who, (long long)h->npix);
+    nl_locscale_t out{};
+    if (estimator == NL_LSE_MEAN_STDDEV) {                      // :229-230, StdDev() :134-144
+        double variance;
+        if ((rc = frame_stats_impl(h, d, h->npix, &out.min, location, &out.max, &variance)) != NL_OK) return rc;
+        *scale = (float)sqrt(variance);
+    } else {
+        if (estimator == NL_LSE_MEDIAN_MAD) ;                  // (reads neither Min() nor Max(): info keeps 0, 0)
+        else if (min_max) { out.min = min_max[0]; out.max = min_max[1]; }
+        else if ((rc = frame_stats_impl(h, d, h->npix, &out.min, nullptr, &out.max, nullptr)) != NL_OK) return rc;
+        if (estimator == NL_LSE_SC_MEDIAN_QN) out.epsilon = (out.max - out.min) / 65535.0f;       // :239
+        std::string msg;
+        rc = nl::locscale_run(d, h->npix, estimator, num_samples, seeds, out.min, out.max, h->frame_scratch.locscale_work,
+                              h->stream, location, scale, &out, &msg);
+        if (rc != NL_OK) fail(rc, "%s: %s", who, msg.c_str());
+    }
+    if (info) *info = out;
+    return rc;
+}
+
+int nl_stack_frame_location_scale(nl_stack_t *h, int idx, int estimator, int num_samples, const uint32_t *seeds,
+                                  int n_seeds, const float *min_max, float *location, float *scale, nl_locscale_t *info)
+{
+    const char *who = idx < 0 ? "result_location_scale" : "frame_location_scale";
+    int rc = locscale_check(who, estimator, num_samples, seeds, n_seeds, location, scale);
+    if (rc != NL_OK) return rc;
+    float *d;
+    if ((rc = resident_entry(h, idx, who, true, &d)) != NL_OK) return rc;
+    return locscale_impl(h, d, who, estimator, num_samples, seeds, min_max, location, scale, info);
+}
+
+int nl_location_scale(const float *data_host, int width, int height, int estimator, int num_samples,
+                      const uint32_t *seeds, int n_seeds, const float *min_max, float *location, float *scale,
+                      nl_locscale_t *info, int device)
+{
+    if (!data_host || width < 1 || height < 1) return fail(NL_ERR_INVALID_ARG, "location_scale: bad argument");
+    int rc = locscale_check("location_scale", estimator, num_samples, seeds, n_seeds, location, scale);
+    if (rc != NL_OK) return rc;
+    if ((rc = select_device(device)) != NL_OK) return rc;
+    return host_frames_run(1, data_host, nullptr, width, height, device, [&](nl_stack_t *h) {
+        return locscale_impl(h, h->d_frames, "location_scale", estimator, num_samples, seeds, min_max, location, scale, info);
+    });
+}
+
+int nl_locscale_seeds(uint64_t key, uint32_t *seeds, int n)
+{
+    if (n < 0 || (n > 0 && !seeds)) return fail(NL_ERR_INVALID_ARG, "locscale_seeds: %d seeds with no output", n);
+    uint64_t x = key;
+    for (int i = 0; i < n;) {                                   // splitmix64; the high half, zeros skipped
+        uint64_t z = (x += 0x9e3779b97f4a7c15ull);
+        z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+        z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+        z ^= z >> 31;
+        if ((uint32_t)(z >> 32) != 0) seeds[i++] = (uint32_t)(z >> 32);
+    }
+    return NL_OK;
 }
 
 int nl_stack_frame_noise(nl_stack_t *h, int idx, float *noise)

@@ -14,6 +14,7 @@
 #include "colour.hpp"
 #include "deband.hpp"
 #include "dev_memory.hpp"
+#include "locscale.hpp"
 #include "project.hpp"
 #include "stars.hpp"
 #include "tone.hpp"
@@ -171,10 +172,13 @@ struct nl_stack {
         nl::DevBuffer tone_seed;
         // the colour steps (nl_stack_rgb_*): partials and seeds of three planes, block means, stars and their sums
         nl::ColourWork colour_work;
+        // location and scale (nl_stack_frame_location_scale)
+        nl::LocScaleWork locscale_work;
         size_t bytes() const
         {
             return bp_diff.bytes + bp_seg.bytes + bp_list.bytes + bp_small.bytes + cfa.bytes + star_work.bytes() +
-                   back_work.bytes() + deband_work.bytes() + blur_work.bytes() + tone_seed.bytes + colour_work.bytes();
+                   back_work.bytes() + deband_work.bytes() + blur_work.bytes() + tone_seed.bytes + colour_work.bytes() +
+                   locscale_work.bytes();
         }
         void release(int device)
         {
@@ -189,6 +193,7 @@ struct nl_stack {
             blur_work.release();
             tone_seed.release();
             colour_work.release();
+            locscale_work.release();
         }
     } frame_scratch;
     int max_grid = 0;

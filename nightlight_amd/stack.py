@@ -275,6 +275,13 @@ class StackHandle:
         return (np.float32(mn.value), np.float32(mean.value), np.float32(mx.value),
                 float(var.value) if variance else None)
 
+    def frame_location_scale(self, idx, estimator=capi.LSE_SC_MEDIAN_QN, seeds=None, num_samples=capi.LOCSCALE_SAMPLES,
+                             min_max=None):
+        """Stats.Location() / Scale() of resident slot idx of a whole-image handle (idx < 0: of the last pass's
+        result), see location_scale.  Returns (location, scale, info)."""
+        return _location_scale(lambda *a: self._lib.nl_stack_frame_location_scale(self._h, int(idx), *a), estimator,
+                               seeds, num_samples, min_max)
+
     def frame_noise(self, idx):
         v = C.c_float()
         capi.check(self._lib.nl_stack_frame_noise(self._h, int(idx), C.byref(v)))
@@ -812,6 +819,44 @@ def back_extract(frame, width, height, stars, grid_size, hfr_factor=4.0, sigma=1
         lambda *a: lib.nl_back_extract(capi.fptr(out), int(width), int(height), *a, _device(device)),
         width, height, stars, grid_size, hfr_factor, sigma, clip, render)
     return (out if int(grid_size) > 0 else None), bg, cells, info
+
+
+def locscale_seeds(key, n=capi.LOCSCALE_MAX_SEEDS):
+    """n nonzero xorshift32 seeds from one 64-bit key (splitmix64), for callers that want the reference's "any seed"
+    behaviour.  Host only."""
+    seeds = np.zeros(int(n), np.uint32)
+    capi.check(capi.load().nl_locscale_seeds(int(key) & (2 ** 64 - 1), seeds.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                             seeds.size))
+    return seeds
+
+
+def _location_scale(call, estimator, seeds, num_samples, min_max):
+    """One nl_*location_scale call through `call(<parameters from estimator on>)`: (location, scale, info)."""
+    seeds = np.ascontiguousarray(np.zeros(0, np.uint32) if seeds is None else seeds, dtype=np.uint32)
+    mm = None if min_max is None else np.ascontiguousarray(min_max, dtype=np.float32)
+    assert mm is None or mm.size == 2
+    loc, scale, info = C.c_float(), C.c_float(), capi.LocScale()
+    capi.check(call(int(estimator), int(num_samples), seeds.ctypes.data_as(C.POINTER(C.c_uint32)), seeds.size,
+                    None if mm is None else capi.fptr(mm), C.byref(loc), C.byref(scale), C.byref(info)))
+    out = {name: getattr(info, name) for name, _ in capi.LocScale._fields_}
+    out["draws"] = [int(v) for v in info.draws]
+    for name in ("min", "max", "epsilon"):
+        out[name] = np.float32(out[name])
+    return np.float32(loc.value), np.float32(scale.value), out
+
+
+def location_scale(frame, width, height, estimator=capi.LSE_SC_MEDIAN_QN, seeds=None,
+                   num_samples=capi.LOCSCALE_SAMPLES, min_max=None, device=None):
+    """Stats.Location() / Scale() (internal/stats/stats.go:225-244) of one host frame on `device` (default 0), bit-exact
+    given the seeds: estimator capi.LSE_MEAN_STDDEV, LSE_MEDIAN_MAD (2 seeds), LSE_SC_MEDIAN_QN (25 seeds, the
+    reference's default) or LSE_HISTOGRAM; seeds nonzero uint32, one per sampling call (locscale_seeds); min_max the
+    cached Stats.Min() / Max() where they differ from the frame's.  Returns (location, scale, info): info the dict of
+    nl_locscale_t."""
+    frame = _host_frame(frame, width, height, copy=False)
+    lib = capi.load()
+    return _location_scale(lambda *a: lib.nl_location_scale(capi.fptr(frame), int(width), int(height), *a,
+                                                            _device(device)),
+                           estimator, seeds, num_samples, min_max)
 
 
 def _deband(call, percentile, window, sigma, location, scale):
