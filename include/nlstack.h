@@ -549,6 +549,11 @@ int nl_stack_result_find_stars(nl_stack_t *h, float location, float scale, float
                                nl_star_t *stars_out, int capacity, int *n_stars, float *sum_of_shifts,
                                float *avg_hfr);
 
+/* ---- OpAlign's estimate: star.Aligner up to the minimiser (internal/star/align.go:58-206) ----
+ * nl_aligner_create, nl_aligner_destroy, nl_aligner_info, nl_aligner_match, nl_aligner_match_stars and their types:
+ * declared in nlstack_align.h, which is part of this interface. */
+#include "nlstack_align.h"
+
 /* ---- OpBackExtract: pre.NewBackground + Background.Subtract / Render ----
  * (internal/ops/pre/preprocess.go:372-398, internal/ops/pre/background.go:68-462)
  * Bit-exact wherever the reference returns: the smoothed grid (cells_out), the info fields, the

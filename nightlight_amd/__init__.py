@@ -10,7 +10,7 @@ from .capi import (CHROMA_FOR_HUES, CHROMA_GAMMA, CHROMA_NEUTRALIZE, LOCSCALE_MA
                    ST_SIGMA, ST_WINSOR_SIGMA, TONE_GAMMA, TONE_MIDTONES, TONE_NORMALIZE, TONE_PARTIAL_GAMMA,
                    TONE_SCALE_OFFSET, TONE_SHIFT_BLACK, WEIGHT_EXPOSURE, WEIGHT_INVERSE_HFR,
                    WEIGHT_INVERSE_NOISE, WEIGHT_NONE, device_count)
-from .stack import (Calibration, StackGroup, StackHandle, back_extract, bin_nxn, bin_shape, blur_tap_paths,  # noqa: F401
+from .stack import (Aligner, Calibration, StackGroup, StackHandle, back_extract, bin_nxn, bin_shape, blur_tap_paths,  # noqa: F401
                     convolve_separable, debayer_shape, deband_horiz, deband_vert, export_gray, export_rgb, find_stars, fits_padded_bytes,
                     fits_parse_header, fits_write_header, gaussian_blur, gaussian_kernel_1d, location_scale, locscale_seeds,
                     median_filter_3x3,

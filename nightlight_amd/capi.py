@@ -20,6 +20,7 @@ CHROMA_GAMMA, CHROMA_NEUTRALIZE, CHROMA_FOR_HUES, ROTATE_HUES = range(4)
 LSE_MEAN_STDDEV, LSE_MEDIAN_MAD, LSE_IKSS, LSE_SC_MEDIAN_QN, LSE_HISTOGRAM = range(5)     # stats.go:31-37
 LOCSCALE_SAMPLES = 131072
 LOCSCALE_MAX_SEEDS = 25
+ALIGN_MAX_K = 128
 
 OK = 0
 ERR_INVALID_MODE = -1
@@ -78,10 +79,20 @@ EXPORTS = [
 # every symbol include/nlstack_locscale.h declares (the part of the interface nlstack.h includes)
 LOCSCALE_EXPORTS = ["nl_stack_frame_location_scale", "nl_location_scale", "nl_locscale_seeds"]
 
+# every symbol include/nlstack_align.h declares (likewise)
+ALIGN_EXPORTS = ["nl_aligner_create", "nl_aligner_destroy", "nl_aligner_info", "nl_aligner_match",
+                 "nl_aligner_match_stars"]
+
 # nl_star_t = star.Star (findstars.go:30-37), 24 bytes
 STAR_DTYPE = np.dtype([("index", "<i4"), ("value", "<f4"), ("x", "<f4"), ("y", "<f4"), ("mass", "<f4"),
                        ("hfr", "<f4")])
 assert STAR_DTYPE.itemsize == 24
+# nl_align_triangle_t = star.Triangle (align.go:39-46), 24 bytes; nl_align_candidate_t, 72 bytes
+TRIANGLE_DTYPE = np.dtype([("d_ab", "<f4"), ("d_ac", "<f4"), ("d_bc", "<f4"), ("a", "<i4"), ("b", "<i4"), ("c", "<i4")])
+CANDIDATE_DTYPE = np.dtype([("dist", "<f4"), ("tri_index", "<i4"), ("ref_tri_index", "<i4"), ("a", "<i4"), ("b", "<i4"),
+                            ("c", "<i4"), ("ref_a", "<i4"), ("ref_b", "<i4"), ("ref_c", "<i4"), ("trans", "<f4", (6,)),
+                            ("trans_ok", "<i4"), ("num_matches", "<i4"), ("enough", "<i4")])
+assert TRIANGLE_DTYPE.itemsize == 24 and CANDIDATE_DTYPE.itemsize == 72
 
 
 
@@ -103,6 +114,13 @@ class LocScale(C.Structure):
                 ("draws", C.c_uint32 * LOCSCALE_MAX_SEEDS), ("min", C.c_float), ("max", C.c_float),
                 ("epsilon", C.c_float), ("peak_bin", C.c_uint32), ("peak_count", C.c_uint32),
                 ("half_width", C.c_uint32)]
+
+
+class AlignInfo(C.Structure):
+    """nl_align_info_t: how a match came about; the three pointers are the caller's optional buffers."""
+    _fields_ = [("triangles", C.c_void_p), ("tri_dist", C.POINTER(C.c_float)), ("tri_ref", C.POINTER(C.c_int32)),
+                ("tri_capacity", C.c_int32), ("n_picked", C.c_int32), ("n_triangles", C.c_int32),
+                ("scale_factor", C.c_float), ("picked", C.c_int32 * ALIGN_MAX_K)]
 
 
 class Tone(C.Structure):
@@ -258,6 +276,14 @@ def open_library(path):
     L.nl_stack_frame_location_scale.argtypes = [vp, C.c_int] + _locscale_args
     L.nl_location_scale.argtypes = [_f32p, C.c_int, C.c_int] + _locscale_args + [C.c_int]
     L.nl_locscale_seeds.argtypes = [C.c_uint64, _u32p, C.c_int]
+    _i32p = C.POINTER(C.c_int32)
+    L.nl_aligner_create.argtypes = [C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int]
+    L.nl_aligner_create.restype = vp
+    L.nl_aligner_destroy.argtypes = [vp]
+    L.nl_aligner_destroy.restype = None
+    L.nl_aligner_info.argtypes = [vp, _i32p, C.c_int, _intp, _intp, vp, C.c_int]
+    L.nl_aligner_match.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int, _intp, _i32p, C.POINTER(AlignInfo)]
+    L.nl_aligner_match_stars.argtypes = [vp, _f32p, C.c_int, vp, C.c_int, _i32p, _i32p]
     L.nl_stack_weights_from_noise.argtypes = [vp, _f32p]
     L.nl_median_filter_3x3.argtypes = [_f32p, _f32p, C.c_int, C.c_int, C.c_int]
     L.nl_median_filter_mask.argtypes = [_f32p, _f32p, C.c_int64, C.POINTER(C.c_int32), C.c_int, C.c_int]

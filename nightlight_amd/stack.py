@@ -859,6 +859,88 @@ def location_scale(frame, width, height, estimator=capi.LSE_SC_MEDIAN_QN, seeds=
                            estimator, seeds, num_samples, min_max)
 
 
+class Aligner:
+    """star.Aligner up to the minimiser (internal/star/align.go:58-206) on `device` (default 0): NewAligner over the
+    reference frame's stars (find_stars' array, brightest first) and the priming constant k.  Immutable once created;
+    match and match_stars may be called from several threads at once."""
+
+    def __init__(self, ref_width, ref_height, ref_stars, k=50, device=None):
+        self._lib = capi.load()
+        self.k = int(k)
+        ref_stars = np.ascontiguousarray(ref_stars, dtype=capi.STAR_DTYPE)
+        self.n_ref_stars = int(ref_stars.size)
+        self._h = self._lib.nl_aligner_create(_device(device), int(ref_width), int(ref_height),
+                                              ref_stars.ctypes.data_as(C.c_void_p), self.n_ref_stars, self.k)
+        if not self._h:
+            raise capi.NlError(capi.ERR_INVALID_ARG, capi.last_error())
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.nl_aligner_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def info(self):
+        """(picked, triangles): pickBrightestDistant's indices into the reference stars and the reference triangles
+        (capi.TRIANGLE_DTYPE) in generateTriangles' order."""
+        n_picked, n_tris = C.c_int(0), C.c_int(0)
+        picked = np.zeros(capi.ALIGN_MAX_K, np.int32)
+        p32 = C.POINTER(C.c_int32)
+        capi.check(self._lib.nl_aligner_info(self._h, picked.ctypes.data_as(p32), picked.size, C.byref(n_picked),
+                                             C.byref(n_tris), None, 0))
+        tris = np.zeros(max(n_tris.value, 1), capi.TRIANGLE_DTYPE)
+        capi.check(self._lib.nl_aligner_info(self._h, None, 0, None, None, tris.ctypes.data_as(C.c_void_p), tris.size))
+        return picked[:n_picked.value].copy(), tris[:n_tris.value].copy()
+
+    def match(self, frame_width, stars, triangles=False):
+        """Align (:74-83) up to the minimiser for one frame's stars.  Returns (candidates, ref_index, info): the
+        shortlist (capi.CANDIDATE_DTYPE), per candidate and star the index of its reference star or -1, and the dict
+        of nl_align_info_t -- with triangles=True also the frame's triangles and every triangle's nearest reference
+        triangle (tri_dist, tri_ref)."""
+        stars = np.ascontiguousarray(stars, dtype=capi.STAR_DTYPE)
+        cands = np.zeros(self.k, capi.CANDIDATE_DTYPE)
+        ref_index = np.zeros((self.k, max(stars.size, 1)), np.int32)
+        n_cands, info = C.c_int(0), capi.AlignInfo()
+        if triangles:
+            cap = min(self.k, max(stars.size, 1))
+            cap = max(cap * (cap - 1) * (cap - 2) // 6, 1)
+            tris, dist, ref = np.zeros(cap, capi.TRIANGLE_DTYPE), np.zeros(cap, np.float32), np.zeros(cap, np.int32)
+            info.triangles = tris.ctypes.data_as(C.c_void_p)
+            info.tri_dist, info.tri_ref = capi.fptr(dist), ref.ctypes.data_as(C.POINTER(C.c_int32))
+            info.tri_capacity = cap
+        capi.check(self._lib.nl_aligner_match(self._h, int(frame_width), stars.ctypes.data_as(C.c_void_p),
+                                              int(stars.size), cands.ctypes.data_as(C.c_void_p), self.k,
+                                              C.byref(n_cands), ref_index.ctypes.data_as(C.POINTER(C.c_int32)),
+                                              C.byref(info)))
+        nc, nt = n_cands.value, info.n_triangles
+        out = {"n_picked": info.n_picked, "n_triangles": nt, "scale_factor": np.float32(info.scale_factor),
+               "picked": np.array(info.picked[:info.n_picked], np.int32)}
+        if triangles:
+            out.update(triangles=tris[:nt].copy(), tri_dist=dist[:nt].copy(), tri_ref=ref[:nt].copy())
+        # (the library writes nc rows of n_stars, one behind the other)
+        rows = ref_index.reshape(-1)[:nc * stars.size].reshape(nc, stars.size).copy()
+        return cands[:nc].copy(), rows, out
+
+    def match_stars(self, transforms, stars):
+        """findBestMatch's matching alone (:194-206) for the caller's transforms (n x 6): (ref_index, num_matches)."""
+        stars = np.ascontiguousarray(stars, dtype=capi.STAR_DTYPE)
+        t = np.ascontiguousarray(transforms, dtype=np.float32).reshape(-1, 6)
+        ref_index = np.zeros((t.shape[0], max(stars.size, 1)), np.int32)
+        counts = np.zeros(max(t.shape[0], 1), np.int32)
+        p32 = C.POINTER(C.c_int32)
+        capi.check(self._lib.nl_aligner_match_stars(self._h, capi.fptr(t), t.shape[0], stars.ctypes.data_as(C.c_void_p),
+                                                    int(stars.size), ref_index.ctypes.data_as(p32),
+                                                    counts.ctypes.data_as(p32)))
+        return ref_index[:, :stars.size].copy(), counts[:t.shape[0]].copy()
+
+
 def _deband(call, percentile, window, sigma, location, scale):
     """One nl_*deband_* call through `call(<parameters from percentile on>)`: the dict of nl_deband_t."""
     info = capi.Deband()
