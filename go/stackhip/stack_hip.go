@@ -90,6 +90,45 @@ func LocationScale(h unsafe.Pointer, idx int, estimator int, key uint64, minMax 
 	return float32(l), float32(s), nil
 }
 
+// GroupRunMaps is one stack pass over the tiles of a group (*C.nl_group_t) that also says where it clipped
+// (include/nlstack_maps.h): rejectLow[p] / rejectHigh[p] count the increments of numClippedLow / numClippedHigh at
+// pixel p (stack.go:411-424 and its siblings), their sums are the two totals; out is the bit-exact result.  All three
+// are whole-image slices of width*height elements; nil leaves that output out.  The reference has no counterpart: it
+// keeps the totals only.
+func GroupRunMaps(g unsafe.Pointer, mode StackMode, sigmaLow, sigmaHigh, refFrameLoc float32, out []float32,
+	rejectLow, rejectHigh []uint16) (clipLow, clipHigh int64, err error) {
+	runtime.LockOSThread() // nl_last_error() is per OS thread
+	defer runtime.UnlockOSThread()
+	var o *C.float
+	var lo, hi *C.uint16_t
+	if out != nil {
+		o = (*C.float)(unsafe.Pointer(&out[0]))
+	}
+	if rejectLow != nil {
+		lo = (*C.uint16_t)(unsafe.Pointer(&rejectLow[0]))
+	}
+	if rejectHigh != nil {
+		hi = (*C.uint16_t)(unsafe.Pointer(&rejectHigh[0]))
+	}
+	var cl, ch C.int64_t
+	if rc := C.nl_group_run_maps((*C.nl_group_t)(g), C.int(mode), C.float(sigmaLow), C.float(sigmaHigh),
+		C.float(refFrameLoc), o, &cl, &ch, lo, hi); rc != C.NL_OK {
+		return 0, 0, lastError()
+	}
+	return int64(cl), int64(ch), nil
+}
+
+// GroupCoverage fills coverage (width*height elements) with the number of frames that have a sample at each pixel:
+// the n the gather of every Stack* function leaves (stack.go:380-387).
+func GroupCoverage(g unsafe.Pointer, coverage []uint16) error {
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	if rc := C.nl_group_coverage((*C.nl_group_t)(g), (*C.uint16_t)(unsafe.Pointer(&coverage[0]))); rc != C.NL_OK {
+		return lastError()
+	}
+	return nil
+}
+
 // Apply stacks a set of light frames on the GPUs.  Same contract as
 // internal/ops/stack/stack.go:115-227: mode validation and auto selection,
 // weights from getWeights (kept in Go, stack.go:231-270), one result image with

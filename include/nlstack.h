@@ -336,6 +336,11 @@ int nl_group_find_sigmas(nl_group_t *g, int mode, float ref_loc, float clip_perc
 int nl_group_accumulate(nl_group_t *g, float weight, int first);
 int nl_group_accumulate_finalize(nl_group_t *g, float weight_sum, float *out_host);
 
+/* ---- per-pixel rejection maps of a pass, coverage map of a stack ----
+ * nl_stack_run_maps, nl_stack_coverage, nl_stack_last_coverage_ms, nl_group_run_maps, nl_group_coverage: declared in
+ * nlstack_maps.h, which is part of this interface. */
+#include "nlstack_maps.h"
+
 /* ---- stack of stacks (StackIncremental / Finalize, stack.go:924-944) ----
  * acc += result_of_last_pass * weight (first != 0: acc = result*weight),
  * on the device; finalize multiplies by 1/weight_sum and downloads. */

@@ -79,6 +79,10 @@ EXPORTS = [
 # every symbol include/nlstack_locscale.h declares (the part of the interface nlstack.h includes)
 LOCSCALE_EXPORTS = ["nl_stack_frame_location_scale", "nl_location_scale", "nl_locscale_seeds"]
 
+# every symbol include/nlstack_maps.h declares (likewise)
+MAPS_EXPORTS = ["nl_stack_run_maps", "nl_stack_coverage", "nl_stack_last_coverage_ms", "nl_group_run_maps",
+                "nl_group_coverage"]
+
 # every symbol include/nlstack_align.h declares (likewise)
 ALIGN_EXPORTS = ["nl_aligner_create", "nl_aligner_destroy", "nl_aligner_info", "nl_aligner_match",
                  "nl_aligner_match_stars"]
@@ -254,6 +258,14 @@ def open_library(path):
     L.nl_group_set_exact.argtypes = [vp, C.c_int]
     L.nl_group_run.argtypes = [vp, C.c_int, C.c_float, C.c_float, C.c_float, _f32p, _i64p, _i64p]
     L.nl_group_last_mode.argtypes = [vp]
+    _u16p = C.POINTER(C.c_uint16)
+    _maps_args = [vp, C.c_int, C.c_float, C.c_float, C.c_float, _f32p, _i64p, _i64p, _u16p, _u16p]
+    L.nl_stack_run_maps.argtypes = _maps_args
+    L.nl_group_run_maps.argtypes = _maps_args
+    L.nl_stack_coverage.argtypes = [vp, _u16p]
+    L.nl_group_coverage.argtypes = [vp, _u16p]
+    L.nl_stack_last_coverage_ms.argtypes = [vp]
+    L.nl_stack_last_coverage_ms.restype = C.c_float
     L.nl_group_find_sigmas.argtypes = [vp, C.c_int, C.c_float, C.c_float, C.c_float, _f32p, _i64p, _i64p,
                                        _f32p, _f32p, _intp]
     L.nl_group_accumulate.argtypes = [vp, C.c_float, C.c_int]

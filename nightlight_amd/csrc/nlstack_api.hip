@@ -436,6 +436,10 @@ static int destroy_impl(nl_stack_t *h)
     cached_free(h->d_frames_owned, (size_t)h->fstride_owned * sizeof(float) * (size_t)h->n_capacity, h->device);
     cached_free(h->d_out, (size_t)h->npix * sizeof(float), h->device);
     if (h->d_acc) (void)hipFree(h->d_acc);
+    if (h->d_reject_map) (void)hipFree(h->d_reject_map);
+    if (h->d_coverage) (void)hipFree(h->d_coverage);
+    if (h->ev_cov0) (void)hipEventDestroy(h->ev_cov0);
+    if (h->ev_cov1) (void)hipEventDestroy(h->ev_cov1);
     if (h->d_weights) (void)hipFree(h->d_weights);
     if (h->d_xstat) (void)hipFree(h->d_xstat);
     if (h->d_sets) (void)hipFree(h->d_sets);
@@ -673,6 +677,8 @@ int64_t nl_stack_device_bytes(nl_stack_t *h)
     if (h->d_frames_owned) b += h->fstride_owned * 4 * h->n_capacity;
     if (h->d_out) b += np * 4;
     if (h->d_acc) b += np * 4;
+    if (h->d_reject_map) b += np * 4;
+    if (h->d_coverage) b += np * 2;
     if (h->d_weights) b += 4 * (int64_t)h->n_capacity;
     if (h->d_xstat) b += 8 * (int64_t)(h->n_capacity + 1);
     if (h->d_sets) b += 2 * (int64_t)kScratchBytes;

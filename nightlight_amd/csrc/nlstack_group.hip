@@ -249,6 +249,57 @@ int nl_group_run(nl_group_t *g, int mode, float sigma_low, float sigma_high, flo
     return NL_OK;
 }
 
+// nl_group_run with the maps (include/nlstack_maps.h): the same protocol -- every pass that was started is finished,
+// the first error with its message is the caller's -- and every tile writes its own rows of the three host buffers
+int nl_group_run_maps(nl_group_t *g, int mode, float sigma_low, float sigma_high, float ref_loc,
+                      float *out_host, int64_t *clip_low, int64_t *clip_high,
+                      uint16_t *reject_low_host, uint16_t *reject_high_host)
+{
+    if (!g) { nl::set_last_error("null group"); return NL_ERR_INVALID_ARG; }
+    int first_rc = NL_OK;
+    std::string first_msg;
+    auto note = [&](int rc) {
+        if (rc != NL_OK && first_rc == NL_OK) { first_rc = rc; first_msg = nl_last_error(); }
+    };
+    size_t started = 0;
+    for (; started < g->tiles.size() && first_rc == NL_OK; started++)
+        note(nl::stack_run_maps_async(g->tiles[started], mode, sigma_low, sigma_high, ref_loc));
+    if (first_rc != NL_OK) started--;                     // (a failing start settles its handle: nothing of it is in flight)
+    const bool ok = first_rc == NL_OK;
+    int64_t lo = 0, hi = 0;
+    if (ok && finish_in_parallel(g)) {
+        std::vector<int64_t> l(g->tiles.size(), 0), h(g->tiles.size(), 0);
+        const int rc = for_each_tile(g, [&](size_t t) {
+            return nl::stack_finish_maps(g->tiles[t], out_host, &l[t], &h[t], reject_low_host, reject_high_host);
+        });
+        if (rc != NL_OK) return rc;
+        for (size_t t = 0; t < g->tiles.size(); t++) { lo += l[t]; hi += h[t]; }
+    } else {
+        for (size_t t = 0; t < started; t++) {
+            int64_t l = 0, h = 0;
+            note(nl::stack_finish_maps(g->tiles[t], ok ? out_host : nullptr, &l, &h, ok ? reject_low_host : nullptr,
+                                       ok ? reject_high_host : nullptr));
+            lo += l;                                      // stack.go:193-198
+            hi += h;
+        }
+        if (first_rc != NL_OK) {
+            nl::set_last_error(first_msg.c_str());
+            return first_rc;
+        }
+    }
+    if (clip_low) *clip_low = lo;
+    if (clip_high) *clip_high = hi;
+    return NL_OK;
+}
+
+// every tile counts on its own device and writes its own rows
+int nl_group_coverage(nl_group_t *g, uint16_t *coverage_host)
+{
+    if (!g) { nl::set_last_error("null group"); return NL_ERR_INVALID_ARG; }
+    if (!coverage_host) { nl::set_last_error("coverage: null output"); return NL_ERR_INVALID_ARG; }
+    return for_each_tile(g, [&](size_t t) { return nl_stack_coverage(g->tiles[t], coverage_host); });
+}
+
 int nl_group_last_mode(nl_group_t *g) { return (g && !g->tiles.empty()) ? nl_stack_last_mode(g->tiles[0]) : -1; }
 
 // stackfindsigma.go:48-98 with the counters summed over the tiles after every pass

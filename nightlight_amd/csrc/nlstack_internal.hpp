@@ -121,6 +121,11 @@ struct nl_stack {
     float2 *d_bounds = nullptr;                // decision pass of weighted stacks: [kBoundRounds][npix] thresholds, lazily allocated
     unsigned char *d_nrounds = nullptr;        // [npix]
     bool bounds_tried = false;
+    // maps (nl_stack_run_maps / nl_stack_coverage), allocated by the first call that needs them, held until destroy
+    unsigned *d_reject_map = nullptr;          // [npix] clipLow count | clipHigh count << 16 of the last maps pass
+    bool last_maps = false;                    // the last pass was a maps pass: d_reject_map belongs to it
+    uint16_t *d_coverage = nullptr;            // [npix]
+    hipEvent_t ev_cov0 = nullptr, ev_cov1 = nullptr;       // around the kernels of the last nl_stack_coverage
     unsigned fb_hint = 0;                      // exact-list length of the last finished fast pass + 1 (0 = unknown)
     unsigned gen_hint = 0;                     // same for the generic list
     bool last_weighted = false;                // the last pass ran with weights (key of the hints it leaves)

@@ -190,6 +190,7 @@ struct PassSetup {
     bool timed;               // the pass records its timing events (not with kDevUntimed)
     bool fused;               // fused protocol (fused_protocol_on; only the SigmaFast engine runs it)
     nl::StackArgs a;
+    bool maps = false;        // a maps pass (nl_stack_run_maps): a.reject_map is set
 };
 
 // Pure: allocates nothing, enqueues nothing.  The first engine whose condition holds runs the pass.
@@ -198,6 +199,7 @@ static Engine select_engine(const nl_stack *h, int mode, bool weighted, const nl
     const bool fast = !h->force_exact;
     const int n = a.n_frames;
     if (mode == NL_ST_MEAN) return Engine::Mean;
+    if (a.reject_map) return Engine::ExactColumns;      // a maps pass: the one engine that carries the per-pixel counts out
     if (fast && mode == NL_ST_MEDIAN && nl::fast_supported(mode, weighted, n, a.npix)) return Engine::MedianRegisters;
     if (fast && mode == NL_ST_MEDIAN && nl::fast_ml_supported(mode, weighted, n, a.npix)) return Engine::MedianMultiLane;
     if (fast && h->d_fb_list &&
@@ -291,6 +293,8 @@ static int decision_pass(nl_stack *h, const PassSetup &p, nl::StackArgs &a)
 
 static int run_mean(nl_stack *h, const PassSetup &p, PassFacts *)
 {
+    // (a maps pass: the mean rejects nothing)
+    if (p.maps) NL_HIP(hipMemsetAsync(p.a.reject_map, 0, (size_t)p.a.npix * sizeof(unsigned), h->stream));
     NL_HIP(nl::launch_stack_mean(p.weighted, p.a, h->stream, &h->last_kernel));
     NL_HIP(hipEventRecord(h->ev_dom1, h->stream));
     return NL_OK;
@@ -549,21 +553,19 @@ static int run_exact_columns(nl_stack *h, const PassSetup &p, PassFacts *facts)
         return fail(NL_ERR_TOO_MANY_FRAMES, "%d frames do not fit the per-pixel LDS column (mode %d)", a.n_frames, p.mode);
     a.tiles = (a.npix + lanes - 1) / lanes;
     const int grid = (int)(a.tiles < (int64_t)h->max_grid ? a.tiles : (int64_t)h->max_grid);
-    NL_HIP(nl::launch_stack_exact(p.mode, p.weighted, a, lanes, grid, lds, h->stream, &h->last_kernel));
+    if (p.maps) NL_HIP(nl::launch_stack_exact_maps(p.mode, p.weighted, a, lanes, grid, lds, h->stream, &h->last_kernel));
+    else        NL_HIP(nl::launch_stack_exact(p.mode, p.weighted, a, lanes, grid, lds, h->stream, &h->last_kernel));
     NL_HIP(hipEventRecord(h->ev_dom1, h->stream));
     NL_HIP(nl::launch_reduce_counters(h->d_partial, nl::kClipSlots, h->d_counters, h->stream));
     facts->has_counters = p.mode != NL_ST_MEDIAN;
     return NL_OK;
 }
 
-static int run_async_impl(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc);
+static int run_async_impl(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc, bool maps);
 
-// A pass that fails half-way (a launch or an event call after the first kernel) must not hand control back with work in
-// flight on the handle's streams and its bookkeeping half-updated: whatever was enqueued is waited for, the scratch
-// sets count as dirty, no list lengths or hints are taken from the broken pass.  The error of the failing call is kept.
-int nl_stack_run_async(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc)
+// what a pass that failed half-way leaves behind (nl_stack_run_async, nl::stack_run_maps_async)
+static int settle_failed_pass(nl_stack_t *h, int rc)
 {
-    const int rc = run_async_impl(h, mode, sigma_low, sigma_high, ref_loc);
     if (rc != NL_OK && h && h->stream) {
         const std::string keep = g_err;
         (void)hipSetDevice(h->device);
@@ -579,7 +581,19 @@ int nl_stack_run_async(nl_stack_t *h, int mode, float sigma_low, float sigma_hig
     return rc;
 }
 
-static int run_async_impl(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc)
+// A pass that fails half-way (a launch or an event call after the first kernel) must not hand control back with work in
+// flight on the handle's streams and its bookkeeping half-updated: whatever was enqueued is waited for, the scratch
+// sets count as dirty, no list lengths or hints are taken from the broken pass.  The error of the failing call is kept.
+int nl_stack_run_async(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc)
+{
+    return settle_failed_pass(h, run_async_impl(h, mode, sigma_low, sigma_high, ref_loc, false));
+}
+
+// maps: the pass of nl_stack_run_maps -- every mode but the mean on the one-pixel-per-lane column kernel, whose MAPS
+// instantiation also stores each pixel's two clip counts in h->d_reject_map.  Such a pass takes part in none of what
+// default passes remember from one another: it takes and leaves no list-length hints (it has no lists), never runs the
+// fused protocol, and leaves the scratch sets as any other plain-protocol pass does.
+static int run_async_impl(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc, bool maps)
 {
     NL_CHECK_HANDLE(h);
     if (mode < NL_ST_MEDIAN || mode > NL_ST_AUTO) return fail(NL_ERR_INVALID_MODE, "invalid stacking mode");
@@ -588,6 +602,12 @@ static int run_async_impl(nl_stack_t *h, int mode, float sigma_low, float sigma_
     if (mode == NL_ST_MAD_SIGMA && weighted)
         return fail(NL_ERR_WEIGHTED_MAD, "MADSigma stacking with weights is still unimplemented");
     if (mode == NL_ST_LINEAR_FIT || mode == NL_ST_MEDIAN) weighted = false;  // stack.go:158,188-189
+    if (maps) {
+        // (a pixel's count is bounded by its samples: 16 bits hold it up to 65 535 frames)
+        if (h->n_frames > 65535)
+            return fail(NL_ERR_TOO_MANY_FRAMES, "run_maps: %d active frames, a uint16 map holds counts up to 65535", h->n_frames);
+        if (!h->d_reject_map) NL_HIP(dev_malloc(&h->d_reject_map, (size_t)h->npix * sizeof(unsigned)));
+    }
 
     if (h->uploads_pending) {
         // asynchronous uploads: the pass waits for the last DMA on the device
@@ -607,6 +627,7 @@ static int run_async_impl(nl_stack_t *h, int mode, float sigma_low, float sigma_
     a.sig_lo = sigma_low; a.sig_hi = sigma_high; a.ref_loc = ref_loc;
     a.out = h->d_out;
     a.partial = h->d_partial;
+    a.reject_map = maps ? h->d_reject_map : nullptr;
 
     {
         const int slot = (int)(h->pass_seq % kTimingRing);
@@ -656,7 +677,7 @@ static int run_async_impl(nl_stack_t *h, int mode, float sigma_low, float sigma_
     h->partial_clean = false;
     if (timed && !one_start) NL_HIP(hipEventRecord(h->ev_dom0, h->stream));
 
-    const PassSetup p{mode, weighted, timed, fused, a};
+    const PassSetup p{mode, weighted, timed, fused, a, maps};
     PassFacts facts;
     int rc = NL_OK;
     switch (engine) {
@@ -676,6 +697,7 @@ static int run_async_impl(nl_stack_t *h, int mode, float sigma_low, float sigma_
     h->partial_clean = facts.zeroed_behind || keep_clean;
     h->pass_seq++;
     h->last_mode = mode;
+    h->last_maps = maps;
     h->pending = true;
     return NL_OK;
 }
@@ -710,6 +732,80 @@ int nl_stack_run(nl_stack_t *h, int mode, float sigma_low, float sigma_high, flo
     return nl_stack_finish(h, out_host, clip_low, clip_high);
 }
 
+}  // extern "C"
+
+// ---- the maps pass (include/nlstack_maps.h) ----------------------------------------------------------------------------
+int nl::stack_run_maps_async(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc)
+{
+    return settle_failed_pass(h, run_async_impl(h, mode, sigma_low, sigma_high, ref_loc, true));
+}
+
+// nl_stack_finish, and the two planes of the map.  The packed words come down in ONE copy and are split here: the same
+// bytes cross the link as two uint16 planes would, and no second device buffer or kernel exists for what is a 16-bit
+// shuffle beside a PCIe transfer.
+int nl::stack_finish_maps(nl_stack_t *h, float *out_host, int64_t *clip_low, int64_t *clip_high, uint16_t *reject_low_host,
+                          uint16_t *reject_high_host)
+{
+    NL_CHECK_HANDLE(h);
+    if (!h->last_maps || !h->d_reject_map) return fail(NL_ERR_INVALID_ARG, "finish_maps: the last pass was no maps pass");
+    std::vector<unsigned> packed;
+    if (reject_low_host || reject_high_host) {
+        packed.resize((size_t)h->npix);
+        // (enqueued in front of nl_stack_finish's own copies; its synchronize covers this one)
+        NL_HIP(hipMemcpyAsync(packed.data(), h->d_reject_map, (size_t)h->npix * sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
+    }
+    const int rc = nl_stack_finish(h, out_host, clip_low, clip_high);
+    if (rc != NL_OK) {
+        (void)hipStreamSynchronize(h->stream);          // (the copy into `packed` may still be in flight)
+        return rc;
+    }
+    const int64_t at = (int64_t)h->row0 * h->width;
+    if (reject_low_host)
+        for (int64_t i = 0; i < h->npix; i++) reject_low_host[at + i] = (uint16_t)(packed[(size_t)i] & 0xffffu);
+    if (reject_high_host)
+        for (int64_t i = 0; i < h->npix; i++) reject_high_host[at + i] = (uint16_t)(packed[(size_t)i] >> 16);
+    return NL_OK;
+}
+
+extern "C" {
+
+int nl_stack_run_maps(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc,
+                      float *out_host, int64_t *clip_low, int64_t *clip_high,
+                      uint16_t *reject_low_host, uint16_t *reject_high_host)
+{
+    const int rc = nl::stack_run_maps_async(h, mode, sigma_low, sigma_high, ref_loc);
+    if (rc != NL_OK) return rc;
+    return nl::stack_finish_maps(h, out_host, clip_low, clip_high, reject_low_host, reject_high_host);
+}
+
+// no pass: it reads the active frames behind whatever is enqueued on the handle's stream and leaves the last pass's
+// result, mode, kernel name and bookkeeping alone
+int nl_stack_coverage(nl_stack_t *h, uint16_t *coverage_host)
+{
+    NL_CHECK_HANDLE(h);
+    if (!coverage_host) return fail(NL_ERR_INVALID_ARG, "coverage: null output");
+    if (h->n_frames > 65535)
+        return fail(NL_ERR_TOO_MANY_FRAMES, "coverage: %d active frames, a uint16 map holds counts up to 65535", h->n_frames);
+    if (h->uploads_pending) {
+        // asynchronous uploads: wait for the last DMA on the device, as a pass does
+        const int last = (h->stage_next + kStageSlots - 1) % kStageSlots;
+        NL_HIP(hipStreamWaitEvent(h->stream, h->stage_done[last], 0));
+        h->uploads_pending = false;
+    }
+    if (!h->d_coverage) NL_HIP(dev_malloc(&h->d_coverage, (size_t)h->npix * sizeof(uint16_t)));
+    if (!h->ev_cov0) {
+        NL_HIP(hipEventCreateWithFlags(&h->ev_cov0, hipEventDefault | h->ev_rel));
+        NL_HIP(hipEventCreateWithFlags(&h->ev_cov1, hipEventDefault | h->ev_rel));
+    }
+    NL_HIP(hipEventRecord(h->ev_cov0, h->stream));
+    NL_HIP(nl::launch_stack_coverage(h->d_frames, h->fstride, h->npix, h->n_frames, h->d_coverage, h->stream));
+    NL_HIP(hipEventRecord(h->ev_cov1, h->stream));
+    NL_HIP(hipMemcpyAsync(coverage_host + (int64_t)h->row0 * h->width, h->d_coverage, (size_t)h->npix * sizeof(uint16_t),
+                          hipMemcpyDeviceToHost, h->stream));
+    NL_HIP(hipStreamSynchronize(h->stream));
+    return NL_OK;
+}
+
 // GPU time from event `from` to event `to` of the last pass, once `to` has completed; -1 where unavailable
 static float elapsed_ms(nl_stack_t *h, hipEvent_t from, hipEvent_t to)
 {
@@ -720,6 +816,7 @@ static float elapsed_ms(nl_stack_t *h, hipEvent_t from, hipEvent_t to)
     return ms;
 }
 
+float nl_stack_last_coverage_ms(nl_stack_t *h) { return h && h->ev_cov0 ? elapsed_ms(h, h->ev_cov0, h->ev_cov1) : -1.0f; }
 float nl_stack_last_dominant_kernel_ms(nl_stack_t *h) { return h && h->ev_dom0 ? elapsed_ms(h, h->ev_dom0, h->ev_dom1) : -1.0f; }
 
 int nl_stack_set_exact(nl_stack_t *h, int on)

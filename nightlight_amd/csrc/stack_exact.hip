@@ -220,8 +220,10 @@ __device__ __forceinline__ int wave_sum(int v)
 // ---- the kernel -----------------------------------------------------------
 // MODE: NL_ST_* (0 median, 2 sigma, 3 winsor, 4 MAD, 5 linear fit);
 // W: weighted (sigma / winsor only); LANES: pixels per wavefront (64/32/16,
-// smaller when a 64-wide tile would not fit the 160 KiB LDS).
-template <int MODE, bool W, int LANES>
+// smaller when a 64-wide tile would not fit the 160 KiB LDS); MAPS: the maps
+// pass (nl_stack_run_maps) -- the lane also stores its pixel's own two clip
+// counts, p.reject_map (whole tile only; no other instantiation reads it).
+template <int MODE, bool W, int LANES, bool MAPS = false>
 __global__ __launch_bounds__(64) void stack_exact_kernel(StackArgs p)
 {
     extern __shared__ float lds[];
@@ -242,6 +244,7 @@ __global__ __launch_bounds__(64) void stack_exact_kernel(StackArgs p)
     }
 
     for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const int c_lo0 = c_lo, c_hi0 = c_hi;      // (MAPS: the lane's running counts before this pixel)
         const int64_t idx = tile * LANES + lane;
         const bool on = lane_on && idx < limit;
         const int64_t pix = p.list ? (int64_t)p.list[on ? idx : 0] : idx;
@@ -371,6 +374,9 @@ __global__ __launch_bounds__(64) void stack_exact_kernel(StackArgs p)
         }
 
         if (on) p.out[pix] = res;
+        // a pixel's counts are bounded by its samples (every increment removes one): 16 bits each, nlstack_pass.hip
+        // refuses a maps pass over more than 65 535 frames
+        if (MAPS && on) p.reject_map[pix] = (unsigned)(c_lo - c_lo0) | ((unsigned)(c_hi - c_hi0) << 16);
     }
 
     // clip totals (stack.go:193-198): wave sum -> one integer atomic per
@@ -423,12 +429,12 @@ __global__ __launch_bounds__(256) void reduce_counters_kernel(unsigned long long
 }
 
 // ---- host-side launcher ----------------------------------------------------
-template <int MODE, bool W>
+template <int MODE, bool W, bool MAPS = false>
 static hipError_t launch_exact(const StackArgs &args, int lanes, int grid, size_t lds_bytes, hipStream_t stream)
 {
     Launcher L(stream);
-    L(lanes == 64 ? stack_exact_kernel<MODE, W, 64> : lanes == 32 ? stack_exact_kernel<MODE, W, 32>
-      : lanes == 16 ? stack_exact_kernel<MODE, W, 16> : stack_exact_kernel<MODE, W, 4>, grid, 64, lds_bytes, args);
+    L(lanes == 64 ? stack_exact_kernel<MODE, W, 64, MAPS> : lanes == 32 ? stack_exact_kernel<MODE, W, 32, MAPS>
+      : lanes == 16 ? stack_exact_kernel<MODE, W, 16, MAPS> : stack_exact_kernel<MODE, W, 4, MAPS>, grid, 64, lds_bytes, args);
     return L.err;
 }
 
@@ -477,6 +483,39 @@ hipError_t launch_stack_exact(int mode, bool weighted, const StackArgs &args, in
     case NL_ST_LINEAR_FIT:
         *name = "stack_exact_kernel<linearfit>";
         return launch_exact<NL_ST_LINEAR_FIT, false>(args, lanes, grid, lds_bytes, stream);
+    default:
+        return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_stack_exact_maps(int mode, bool weighted, const StackArgs &args, int lanes, int grid,
+                                   size_t lds_bytes, hipStream_t stream, const char **name)
+{
+    if (!args.reject_map || args.list) return hipErrorInvalidValue;
+    switch (mode) {
+    case NL_ST_MEDIAN:
+        *name = "stack_exact_kernel<median,maps>";
+        return launch_exact<NL_ST_MEDIAN, false, true>(args, lanes, grid, lds_bytes, stream);
+    case NL_ST_SIGMA:
+        if (weighted) {
+            *name = "stack_exact_kernel<sigma,weighted,maps>";
+            return launch_exact<NL_ST_SIGMA, true, true>(args, lanes, grid, lds_bytes, stream);
+        }
+        *name = "stack_exact_kernel<sigma,maps>";
+        return launch_exact<NL_ST_SIGMA, false, true>(args, lanes, grid, lds_bytes, stream);
+    case NL_ST_WINSOR_SIGMA:
+        if (weighted) {
+            *name = "stack_exact_kernel<winsor,weighted,maps>";
+            return launch_exact<NL_ST_WINSOR_SIGMA, true, true>(args, lanes, grid, lds_bytes, stream);
+        }
+        *name = "stack_exact_kernel<winsor,maps>";
+        return launch_exact<NL_ST_WINSOR_SIGMA, false, true>(args, lanes, grid, lds_bytes, stream);
+    case NL_ST_MAD_SIGMA:
+        *name = "stack_exact_kernel<mad,maps>";
+        return launch_exact<NL_ST_MAD_SIGMA, false, true>(args, lanes, grid, lds_bytes, stream);
+    case NL_ST_LINEAR_FIT:
+        *name = "stack_exact_kernel<linearfit,maps>";
+        return launch_exact<NL_ST_LINEAR_FIT, false, true>(args, lanes, grid, lds_bytes, stream);
     default:
         return hipErrorInvalidValue;
     }

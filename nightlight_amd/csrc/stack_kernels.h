@@ -62,6 +62,9 @@ struct StackArgs {
     // decided: the replay computes its own bounds, as without these).  nullptr: off.
     float2 *bounds;
     unsigned char *nrounds;
+    // Maps pass (nl_stack_run_maps): [npix] words, the pixel's clipLow count | clipHigh count << 16.  Read by the MAPS
+    // instantiations of stack_exact_kernel only; nullptr everywhere else.
+    unsigned *reject_map;
 };
 
 // words (64 bit) of one per-pass scratch set: clip accumulators + {exact-list length, generic-list length,
@@ -117,6 +120,11 @@ void set_last_error(const char *msg);
 int stack_project_from(nl_stack_t *dst, int dst_idx, nl_stack_t *src, int src_idx, const float trans[6],
                        float out_of_bounds, const char *who, bool from_group);
 int stack_settle(nl_stack_t *h);
+// the two halves of nl_stack_run_maps (nlstack_pass.hip), so that nl_group_run_maps starts every tile before it awaits any;
+// a failing first half settles the handle as nl_stack_run_async does
+int stack_run_maps_async(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc);
+int stack_finish_maps(nl_stack_t *h, float *out_host, int64_t *clip_low, int64_t *clip_high, uint16_t *reject_low_host,
+                      uint16_t *reject_high_host);
 
 // Bisection of the goal-seek (spec: internal/ops/stack/stackfindsigma.go:48-98): sigma_low and
 // sigma_high in [1,11], percentages in the reference's fp32 arithmetic, 21 passes at most.
@@ -205,6 +213,9 @@ int exact_plan(int mode, bool weighted, int n_frames, int n_pad, int max_lanes, 
                size_t *lds_bytes);
 hipError_t launch_stack_exact(int mode, bool weighted, const StackArgs &args, int lanes, int grid,
                               size_t lds_bytes, hipStream_t stream, const char **name);
+// the MAPS instantiations: as above, and every pixel's two clip counts go to args.reject_map (whole tile, no list)
+hipError_t launch_stack_exact_maps(int mode, bool weighted, const StackArgs &args, int lanes, int grid,
+                                   size_t lds_bytes, hipStream_t stream, const char **name);
 // list_counts (optional): {exact-list length, generic-list length} of the pass, left in counters[2] (low | high << 32)
 // zero_after: the kernel leaves the scratch set (kScratchWords words at `partial`) zeroed for the next pass
 hipError_t launch_reduce_counters(unsigned long long *partial, int n_blocks,
@@ -309,6 +320,10 @@ hipError_t launch_stack_mean(bool weighted, const StackArgs &args, hipStream_t s
 hipError_t launch_axpy(float *acc, const float *x, float weight, int first, int64_t n,
                        hipStream_t stream);
 hipError_t launch_scale(float *acc, float factor, int64_t n, hipStream_t stream);
+
+// ---- stack_coverage.hip: out[p] = frames whose sample at p is not NaN (the n of the gather, stack.go:380-387) ----
+hipError_t launch_stack_coverage(const float *frames, int64_t stride, int64_t npix, int n_frames, uint16_t *out,
+                                 hipStream_t stream);
 
 // ---- ingest.hip (FITS payload decode / encode, MatchHistogram, Project from a frame that was just uploaded) ----
 int fits_bytes_per_value(int bitpix);

@@ -11,6 +11,10 @@ import numpy as np
 from . import capi
 
 
+def _u16ptr(a):
+    return a.ctypes.data_as(C.POINTER(C.c_uint16))
+
+
 class StackHandle:
     """Frames of one row tile [row0, row0+rows) resident in HBM as planar
     [n_frames][rows*width] fp32, plus the result tile and clip counters."""
@@ -143,6 +147,38 @@ class StackHandle:
                                           C.c_float(sigma_high), C.c_float(ref_loc), optr,
                                           C.byref(cl), C.byref(ch)))
         return (out if fetch else None), cl.value, ch.value
+
+    def run_maps(self, mode, sigma_low=2.75, sigma_high=2.75, ref_loc=0.0, out=None, reject_low=None,
+                 reject_high=None):
+        """One pass on the bit-exact column kernel that also says WHERE it clipped (include/nlstack_maps.h).
+        Returns (result, clip_low, clip_high, reject_low, reject_high): the maps are whole-image uint16 arrays,
+        reject_low[p] / reject_high[p] = how often the reference increments clipLow / clipHigh at pixel p; their
+        sums are the two totals.  `out`, `reject_low`, `reject_high`: whole-image arrays (float32, uint16, uint16)
+        whose tile rows get written; those not given are made here, zero outside the tile."""
+        n = self.width * self.height
+        out = np.zeros(n, np.float32) if out is None else out
+        reject_low = np.zeros(n, np.uint16) if reject_low is None else reject_low
+        reject_high = np.zeros(n, np.uint16) if reject_high is None else reject_high
+        for a, t in ((out, np.float32), (reject_low, np.uint16), (reject_high, np.uint16)):
+            assert a.dtype == t and a.size == n and a.flags.c_contiguous
+        cl, ch = C.c_int64(0), C.c_int64(0)
+        capi.check(self._lib.nl_stack_run_maps(self._h, int(mode), C.c_float(sigma_low), C.c_float(sigma_high),
+                                               C.c_float(ref_loc), capi.fptr(out), C.byref(cl), C.byref(ch),
+                                               _u16ptr(reject_low), _u16ptr(reject_high)))
+        return out, cl.value, ch.value, reject_low, reject_high
+
+    def coverage(self, out=None):
+        """Whole-image uint16 map of how many active frames have a sample (not NaN) at each pixel: the tile's rows
+        of `out` (made here, zero outside the tile, if not given).  No pass: the last result stays."""
+        out = np.zeros(self.width * self.height, np.uint16) if out is None else out
+        assert out.dtype == np.uint16 and out.size == self.width * self.height and out.flags.c_contiguous
+        capi.check(self._lib.nl_stack_coverage(self._h, _u16ptr(out)))
+        return out
+
+    @property
+    def last_coverage_ms(self):
+        """GPU time of the kernels of the last coverage() call; -1 before the first."""
+        return float(self._lib.nl_stack_last_coverage_ms(self._h))
 
     def run_async(self, mode, sigma_low=2.75, sigma_high=2.75, ref_loc=0.0):
         capi.check(self._lib.nl_stack_run_async(self._h, int(mode), C.c_float(sigma_low),
@@ -592,6 +628,23 @@ class StackGroup:
                                           C.c_float(ref_loc), capi.fptr(out) if download else None,
                                           C.byref(cl), C.byref(ch)))
         return out, cl.value, ch.value
+
+    def run_maps(self, mode, sigma_low=2.75, sigma_high=2.75, ref_loc=0.0):
+        """StackHandle.run_maps over the tiles: (result, clip_low, clip_high, reject_low, reject_high), every tile
+        writing its own rows."""
+        n = self.width * self.height
+        out, lo, hi = np.zeros(n, np.float32), np.zeros(n, np.uint16), np.zeros(n, np.uint16)
+        cl, ch = C.c_int64(0), C.c_int64(0)
+        capi.check(self._lib.nl_group_run_maps(self._g, int(mode), C.c_float(sigma_low), C.c_float(sigma_high),
+                                               C.c_float(ref_loc), capi.fptr(out), C.byref(cl), C.byref(ch),
+                                               _u16ptr(lo), _u16ptr(hi)))
+        return out, cl.value, ch.value, lo, hi
+
+    def coverage(self):
+        """StackHandle.coverage over the tiles."""
+        out = np.zeros(self.width * self.height, np.uint16)
+        capi.check(self._lib.nl_group_coverage(self._g, _u16ptr(out)))
+        return out
 
     def upload_frame(self, idx, frame):
         """Overlapped upload of one whole frame (nl_group_upload_frame)."""

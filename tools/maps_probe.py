@@ -1,0 +1,91 @@
+#!/usr/bin/env python3
+"""GPU times of a maps pass and of the coverage map beside the passes they sit next to (include/nlstack_maps.h).
+
+  python tools/maps_probe.py [--frames 128 --width 4096 --height 4096 --mode 2 --sigma 3 --reps 20 --out DIR]
+      On ONE handle in one process, synthetic frames (nl_stack_fill_synthetic), median and minimum over --reps runs
+      after 3 warm-up runs, each from the HIP events the library records on the handle's stream
+      (nl_stack_pass_times; nl_stack_last_coverage_ms):
+        the default pass          nl_stack_run, result left on the device
+        the maps pass             nl_stack_run_maps, every host pointer NULL (the download of the maps is not timed)
+        the mean pass             nl_stack_run(NL_ST_MEAN): reads the same bytes as the coverage kernel
+        nl_stack_coverage         its kernels only (the call also downloads the map)
+      DIR receives the lines as maps_probe.txt.
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def stats(ms):
+    return "median %.3f ms, min %.3f ms" % (float(np.median(ms)), float(np.min(ms)))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", type=int, default=128)
+    ap.add_argument("--width", type=int, default=4096)
+    ap.add_argument("--height", type=int, default=4096)
+    ap.add_argument("--mode", type=int, default=2)
+    ap.add_argument("--sigma", type=float, default=3.0)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    import nightlight_amd as nl
+    from nightlight_amd import capi
+    L = capi.load()
+    warm = 3
+    lines = []
+    try:
+        import torch
+        lines.append("device: %s" % torch.cuda.get_device_name(0))
+    except Exception:
+        pass
+    lines.append("%d frames of %d x %d, mode %d, sigma %.2f / %.2f; %d runs after %d warm-up runs"
+                 % (a.frames, a.width, a.height, a.mode, a.sigma, a.sigma, a.reps, warm))
+    with nl.StackHandle(a.frames, a.width, a.height) as st:
+        st.fill_synthetic(seed=7)
+        cov = np.zeros(a.width * a.height, np.uint16)
+
+        def default_pass():
+            st.run(a.mode, a.sigma, a.sigma, 0.0, fetch=False)
+            return st.pass_times(0)[0]
+
+        def maps_pass():
+            capi.check(L.nl_stack_run_maps(st._h, a.mode, a.sigma, a.sigma, 0.0, None, None, None, None, None))
+            return st.pass_times(0)[0]
+
+        def mean_pass():
+            st.run(capi.ST_MEAN, a.sigma, a.sigma, 0.0, fetch=False)
+            return st.pass_times(0)[0]
+
+        def coverage():
+            st.coverage(out=cov)
+            return st.last_coverage_ms
+
+        times = {}
+        for label, fn in (("default pass", default_pass), ("maps pass", maps_pass), ("mean pass", mean_pass),
+                          ("coverage", coverage)):
+            ms = [fn() for _ in range(warm + a.reps)][warm:]
+            times[label] = float(np.median(ms))
+            kernel = "stack_coverage_kernel" if label == "coverage" else st.last_kernel_name
+            lines.append("%-13s %-42s %s" % (label, kernel, stats(ms)))
+        read = 4.0 * a.frames * a.width * a.height
+        lines.append("coverage / mean pass = %.3f; coverage reads %.2f GB: %.2f TB/s; maps pass / default pass = %.1f"
+                     % (times["coverage"] / times["mean pass"], read / 1e9, read / times["coverage"] / 1e9,
+                        times["maps pass"] / times["default pass"]))
+        lines.append("coverage: %d ... %d frames per pixel" % (int(cov.min()), int(cov.max())))
+    text = "\n".join(lines)
+    print(text)
+    if a.out:
+        os.makedirs(a.out, exist_ok=True)
+        with open(os.path.join(a.out, "maps_probe.txt"), "w") as f:
+            f.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()
