@@ -201,8 +201,20 @@ func (op *OpStack) Apply(f []*fits.Image, c *ops.Context) (result *fits.Image, e
 
 	data := make([]float32, len(f[0].Data))
 	var clipLow, clipHigh C.int64_t
-	if rc := C.nl_group_run(g, C.int(mode), C.float(op.SigmaLow), C.float(op.SigmaHigh), C.float(op.RefFrameLoc),
-		(*C.float)(unsafe.Pointer(&data[0])), &clipLow, &clipHigh); rc != C.NL_OK {
+	// An EXTENSION, not in the reference (include/nlstack_wlinfit.h): OpStack gains the field
+	//	WeightedLinearFit bool `json:"weightedLinearFit,omitempty"`
+	// in stack.go's struct (default false, so existing JSON round-trips unchanged).  When it is set, the mode
+	// resolves to the linear fit and there are weights, the fit rejects as always and the survivors are averaged
+	// with the weights; otherwise the linear fit drops the weights as the reference does (stack.go:188-189).
+	var rc C.int
+	if op.WeightedLinearFit && mode == StLinearFit && weights != nil {
+		rc = C.nl_group_run_linfit_weighted(g, C.float(op.SigmaLow), C.float(op.SigmaHigh), C.float(op.RefFrameLoc),
+			(*C.float)(unsafe.Pointer(&data[0])), &clipLow, &clipHigh)
+	} else {
+		rc = C.nl_group_run(g, C.int(mode), C.float(op.SigmaLow), C.float(op.SigmaHigh), C.float(op.RefFrameLoc),
+			(*C.float)(unsafe.Pointer(&data[0])), &clipLow, &clipHigh)
+	}
+	if rc != C.NL_OK {
 		return nil, lastError()
 	}
 	if mode >= StSigma {

@@ -341,6 +341,11 @@ int nl_group_accumulate_finalize(nl_group_t *g, float weight_sum, float *out_hos
  * nlstack_maps.h, which is part of this interface. */
 #include "nlstack_maps.h"
 
+/* ---- linear-fit rejection with a weighted mean of the survivors (an extension: the reference's fit takes no weights) ----
+ * nl_stack_run_linfit_weighted, nl_stack_run_linfit_weighted_async, nl_group_run_linfit_weighted: declared in
+ * nlstack_wlinfit.h, which is part of this interface. */
+#include "nlstack_wlinfit.h"
+
 /* ---- stack of stacks (StackIncremental / Finalize, stack.go:924-944) ----
  * acc += result_of_last_pass * weight (first != 0: acc = result*weight),
  * on the device; finalize multiplies by 1/weight_sum and downloads. */

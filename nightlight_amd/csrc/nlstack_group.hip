@@ -206,11 +206,12 @@ int nl_group_set_exact(nl_group_t *g, int on)
     return NL_OK;
 }
 
-// stack.go:142-210 over the devices: enqueue every tile's pass, then collect
-int nl_group_run(nl_group_t *g, int mode, float sigma_low, float sigma_high, float ref_loc,
-                 float *out_host, int64_t *clip_low, int64_t *clip_high)
+}  // extern "C"
+
+// stack.go:142-210 over the devices: start(tile) enqueues every tile's pass, then nl_stack_finish collects
+template <class Start>
+static int run_tiles(nl_group_t *g, Start &&start, float *out_host, int64_t *clip_low, int64_t *clip_high)
 {
-    if (!g) return NL_ERR_INVALID_ARG;
     // A failing tile must not leave the other tiles' passes enqueued and pending: every pass that was
     // started is also finished, and the FIRST error (with its message) is what the caller gets.
     int first_rc = NL_OK;
@@ -220,8 +221,8 @@ int nl_group_run(nl_group_t *g, int mode, float sigma_low, float sigma_high, flo
     };
     size_t started = 0;
     for (; started < g->tiles.size() && first_rc == NL_OK; started++)
-        note(nl_stack_run_async(g->tiles[started], mode, sigma_low, sigma_high, ref_loc));
-    if (first_rc != NL_OK) started--;                     // (nl_stack_run_async settles a handle whose pass failed: nothing of it is in flight)
+        note(start(g->tiles[started]));
+    if (first_rc != NL_OK) started--;                     // (a failing start settles its handle: nothing of it is in flight)
     int64_t lo = 0, hi = 0;
     if (first_rc == NL_OK && finish_in_parallel(g)) {
         // one host thread per tile: a tile's finish is a wait and the copy of its rows into the caller's (pageable) buffer --
@@ -247,6 +248,25 @@ int nl_group_run(nl_group_t *g, int mode, float sigma_low, float sigma_high, flo
     if (clip_low) *clip_low = lo;
     if (clip_high) *clip_high = hi;
     return NL_OK;
+}
+
+extern "C" {
+
+int nl_group_run(nl_group_t *g, int mode, float sigma_low, float sigma_high, float ref_loc,
+                 float *out_host, int64_t *clip_low, int64_t *clip_high)
+{
+    if (!g) return NL_ERR_INVALID_ARG;
+    return run_tiles(g, [&](nl_stack_t *h) { return nl_stack_run_async(h, mode, sigma_low, sigma_high, ref_loc); },
+                     out_host, clip_low, clip_high);
+}
+
+// the weighted linear-fit pass (include/nlstack_wlinfit.h) over the tiles: nl_group_run's protocol
+int nl_group_run_linfit_weighted(nl_group_t *g, float sigma_low, float sigma_high, float ref_loc,
+                                 float *out_host, int64_t *clip_low, int64_t *clip_high)
+{
+    if (!g) { nl::set_last_error("null group"); return NL_ERR_INVALID_ARG; }
+    return run_tiles(g, [&](nl_stack_t *h) { return nl_stack_run_linfit_weighted_async(h, sigma_low, sigma_high, ref_loc); },
+                     out_host, clip_low, clip_high);
 }
 
 // nl_group_run with the maps (include/nlstack_maps.h): the same protocol -- every pass that was started is finished,

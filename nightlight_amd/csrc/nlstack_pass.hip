@@ -193,6 +193,13 @@ struct PassSetup {
     bool maps = false;        // a maps pass (nl_stack_run_maps): a.reject_map is set
 };
 
+// what kind of pass run_async_impl sets up
+enum class PassKind {
+    Default,              // nl_stack_run_async
+    Maps,                 // nl_stack_run_maps (include/nlstack_maps.h)
+    WeightedLinfit,       // nl_stack_run_linfit_weighted (include/nlstack_wlinfit.h): an engine of its own, run_linfit_weighted
+};
+
 // Pure: allocates nothing, enqueues nothing.  The first engine whose condition holds runs the pass.
 static Engine select_engine(const nl_stack *h, int mode, bool weighted, const nl::StackArgs &a)
 {
@@ -561,9 +568,37 @@ static int run_exact_columns(nl_stack *h, const PassSetup &p, PassFacts *facts)
     return NL_OK;
 }
 
-static int run_async_impl(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc, bool maps);
+// The weighted linear-fit pass (include/nlstack_wlinfit.h, an extension): up to 128 frames the register-resident kernel
+// of stack_linfit_weighted.hip, which hands the pixels it cannot decide to the exact list, and the column kernel's
+// <linfit,weighted> instantiation over that list; deeper stacks, handles without a list and nl_stack_set_exact: the
+// column kernel over the whole tile.  Plain protocol throughout, as run_listed and run_exact_columns.
+static int run_linfit_weighted(nl_stack *h, const PassSetup &p, PassFacts *facts)
+{
+    nl::StackArgs a = p.a;
+    if (!h->force_exact && h->d_fb_list && nl::linfit_weighted_supported(a.n_frames, a.npix)) {
+        NL_HIP(nl::launch_stack_linfit_weighted(a, list_args(h, true, false), h->stream, &h->last_kernel));
+        NL_HIP(hipEventRecord(h->ev_dom1, h->stream));
+        const int rc = replay_list(h, p.mode, true, a);
+        if (rc != NL_OK) return rc;
+        facts->used_fast = true;
+    } else {
+        int lanes = 0;
+        size_t lds = 0;
+        if (nl::exact_plan(p.mode, true, a.n_frames, a.n_pad, 64, &lanes, &lds) != 0)
+            return fail(NL_ERR_TOO_MANY_FRAMES, "%d frames do not fit the per-pixel LDS columns of the weighted linear fit", a.n_frames);
+        a.tiles = (a.npix + lanes - 1) / lanes;
+        const int grid = (int)(a.tiles < (int64_t)h->max_grid ? a.tiles : (int64_t)h->max_grid);
+        NL_HIP(nl::launch_stack_exact(p.mode, true, a, lanes, grid, lds, h->stream, &h->last_kernel));
+        NL_HIP(hipEventRecord(h->ev_dom1, h->stream));
+    }
+    NL_HIP(nl::launch_reduce_counters(h->d_partial, nl::kClipSlots, h->d_counters, h->stream));
+    facts->has_counters = true;
+    return NL_OK;
+}
 
-// what a pass that failed half-way leaves behind (nl_stack_run_async, nl::stack_run_maps_async)
+static int run_async_impl(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc, PassKind kind);
+
+// what a pass that failed half-way leaves behind (nl_stack_run_async, nl::stack_run_maps_async, nl_stack_run_linfit_weighted_async)
 static int settle_failed_pass(nl_stack_t *h, int rc)
 {
     if (rc != NL_OK && h && h->stream) {
@@ -586,22 +621,28 @@ static int settle_failed_pass(nl_stack_t *h, int rc)
 // sets count as dirty, no list lengths or hints are taken from the broken pass.  The error of the failing call is kept.
 int nl_stack_run_async(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc)
 {
-    return settle_failed_pass(h, run_async_impl(h, mode, sigma_low, sigma_high, ref_loc, false));
+    return settle_failed_pass(h, run_async_impl(h, mode, sigma_low, sigma_high, ref_loc, PassKind::Default));
 }
 
 // maps: the pass of nl_stack_run_maps -- every mode but the mean on the one-pixel-per-lane column kernel, whose MAPS
 // instantiation also stores each pixel's two clip counts in h->d_reject_map.  Such a pass takes part in none of what
 // default passes remember from one another: it takes and leaves no list-length hints (it has no lists), never runs the
 // fused protocol, and leaves the scratch sets as any other plain-protocol pass does.
-static int run_async_impl(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc, bool maps)
+// The same holds for the weighted linear-fit pass (PassKind::WeightedLinfit; `mode` is NL_ST_LINEAR_FIT), which keeps the
+// weights the default linear fit drops and runs on run_linfit_weighted.
+static int run_async_impl(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc, PassKind kind)
 {
     NL_CHECK_HANDLE(h);
+    const bool maps = kind == PassKind::Maps, wlinfit = kind == PassKind::WeightedLinfit;
+    if (wlinfit && !h->has_weights)
+        return fail(NL_ERR_INVALID_ARG, "run_linfit_weighted: the handle has no weights (nl_stack_set_weights); "
+                                        "the unweighted fit is nl_stack_run with NL_ST_LINEAR_FIT");
     if (mode < NL_ST_MEDIAN || mode > NL_ST_AUTO) return fail(NL_ERR_INVALID_MODE, "invalid stacking mode");
     if (mode == NL_ST_AUTO) mode = auto_select_mode(h->n_frames);
     bool weighted = h->has_weights;
     if (mode == NL_ST_MAD_SIGMA && weighted)
         return fail(NL_ERR_WEIGHTED_MAD, "MADSigma stacking with weights is still unimplemented");
-    if (mode == NL_ST_LINEAR_FIT || mode == NL_ST_MEDIAN) weighted = false;  // stack.go:158,188-189
+    if ((mode == NL_ST_LINEAR_FIT && !wlinfit) || mode == NL_ST_MEDIAN) weighted = false;  // stack.go:158,188-189
     if (maps) {
         // (a pixel's count is bounded by its samples: 16 bits hold it up to 65 535 frames)
         if (h->n_frames > 65535)
@@ -680,7 +721,8 @@ static int run_async_impl(nl_stack_t *h, int mode, float sigma_low, float sigma_
     const PassSetup p{mode, weighted, timed, fused, a, maps};
     PassFacts facts;
     int rc = NL_OK;
-    switch (engine) {
+    if (wlinfit) rc = run_linfit_weighted(h, p, &facts);
+    else switch (engine) {
     case Engine::Mean:            rc = run_mean(h, p, &facts); break;
     case Engine::MedianRegisters: rc = run_median(h, p, false); break;
     case Engine::MedianMultiLane: rc = run_median(h, p, true); break;
@@ -737,7 +779,7 @@ int nl_stack_run(nl_stack_t *h, int mode, float sigma_low, float sigma_high, flo
 // ---- the maps pass (include/nlstack_maps.h) ----------------------------------------------------------------------------
 int nl::stack_run_maps_async(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc)
 {
-    return settle_failed_pass(h, run_async_impl(h, mode, sigma_low, sigma_high, ref_loc, true));
+    return settle_failed_pass(h, run_async_impl(h, mode, sigma_low, sigma_high, ref_loc, PassKind::Maps));
 }
 
 // nl_stack_finish, and the two planes of the map.  The packed words come down in ONE copy and are split here: the same
@@ -768,6 +810,20 @@ int nl::stack_finish_maps(nl_stack_t *h, float *out_host, int64_t *clip_low, int
 }
 
 extern "C" {
+
+// ---- the weighted linear-fit pass (include/nlstack_wlinfit.h) ------------------------------------------------------------
+int nl_stack_run_linfit_weighted_async(nl_stack_t *h, float sigma_low, float sigma_high, float ref_loc)
+{
+    return settle_failed_pass(h, run_async_impl(h, NL_ST_LINEAR_FIT, sigma_low, sigma_high, ref_loc, PassKind::WeightedLinfit));
+}
+
+int nl_stack_run_linfit_weighted(nl_stack_t *h, float sigma_low, float sigma_high, float ref_loc,
+                                 float *out_host, int64_t *clip_low, int64_t *clip_high)
+{
+    const int rc = nl_stack_run_linfit_weighted_async(h, sigma_low, sigma_high, ref_loc);
+    if (rc != NL_OK) return rc;
+    return nl_stack_finish(h, out_host, clip_low, clip_high);
+}
 
 int nl_stack_run_maps(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc,
                       float *out_host, int64_t *clip_low, int64_t *clip_high,

@@ -210,6 +210,30 @@ __device__ void bitonic_sort(Col<S> a, int n_pad)
     }
 }
 
+// The same network on (value, index) pairs: ascending by value, equal values (+0 == -0) by index.  The
+// weighted linear-fit pass only: it has to know WHICH frame sits at a sorted position.
+template <int S>
+__device__ void bitonic_sort_keyed(Col<S> a, Col<S> b, int n_pad)
+{
+    for (int k = 2; k <= n_pad; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            const int half = n_pad >> 1;
+            for (int t = 0; t < half; t++) {
+                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+                const int l = i | j;
+                const float x = a.get(i), y = a.get(l);
+                const float xi = b.get(i), yi = b.get(l);
+                const bool y_first = y < x || (y == x && __float_as_int(yi) < __float_as_int(xi));
+                const bool asc = (i & k) == 0;
+                if (y_first == asc) {
+                    a.set(i, y); a.set(l, x);
+                    b.set(i, yi); b.set(l, xi);
+                }
+            }
+        }
+    }
+}
+
 __device__ __forceinline__ int wave_sum(int v)
 {
 #pragma unroll
@@ -219,7 +243,8 @@ __device__ __forceinline__ int wave_sum(int v)
 
 // ---- the kernel -----------------------------------------------------------
 // MODE: NL_ST_* (0 median, 2 sigma, 3 winsor, 4 MAD, 5 linear fit);
-// W: weighted (sigma / winsor only); LANES: pixels per wavefront (64/32/16,
+// W: weighted (sigma / winsor; with the linear fit: the weighted linear-fit
+// pass of include/nlstack_wlinfit.h, an extension); LANES: pixels per wavefront (64/32/16,
 // smaller when a 64-wide tile would not fit the 160 KiB LDS); MAPS: the maps
 // pass (nl_stack_run_maps) -- the lane also stores its pixel's own two clip
 // counts, p.reject_map (whole tile only; no other instantiation reads it).
@@ -263,7 +288,7 @@ __global__ __launch_bounds__(64) void stack_exact_kernel(StackArgs p)
                 for (int u = 0; u < 8; u++) {
                     if (v[u] == v[u]) {
                         a.set(n, v[u]);
-                        if (W) b.set(n, p.weights[k + u]);
+                        if (W) b.set(n, (MODE == NL_ST_LINEAR_FIT) ? __int_as_float(k + u) : p.weights[k + u]);
                         n++;
                     }
                 }
@@ -273,7 +298,7 @@ __global__ __launch_bounds__(64) void stack_exact_kernel(StackArgs p)
             const float v = fr[(int64_t)k * p.stride];
             if (on && v == v) {
                 a.set(n, v);
-                if (W) b.set(n, p.weights[k]);
+                if (W) b.set(n, (MODE == NL_ST_LINEAR_FIT) ? __int_as_float(k) : p.weights[k]);
                 n++;
             }
         }
@@ -315,6 +340,78 @@ __global__ __launch_bounds__(64) void stack_exact_kernel(StackArgs p)
                 float s = 0.0f;
                 for (int i = 0; i < n; i++) s += a.get(i);
                 res = s / (float)n;
+            }
+        } else if (MODE == NL_ST_LINEAR_FIT && W) {
+            // The weighted linear-fit pass (include/nlstack_wlinfit.h; no counterpart in the reference).  The
+            // fit below is the unweighted branch's, operation for operation; what differs is what it keeps:
+            // the second column carries every sample's FRAME INDEX through the sort -- keys (value, index),
+            // pads (+Inf, N + slot) behind every real sample -- and through the stable compaction, and the
+            // sweep that ends the loop does not compact, so that slots 0 .. n-1 of the index column name the
+            // frames the LAST regression ran over.  Their samples are then averaged with the frames' weights
+            // in frame order: StackMeanWeighted's arithmetic (stack.go:343-364) over those frames.
+            for (int i = n; i < p.n_pad; i++) { a.set(i, __builtin_inff()); b.set(i, __int_as_float(N + i)); }
+            bitonic_sort_keyed(a, b, p.n_pad);
+            if (n > 0) {
+                for (;;) {
+                    const float fn = (float)n;
+                    const float xm = p.xstat[2 * n], xsd = p.xstat[2 * n + 1];
+                    float ym, ysd;
+                    mean_stddev(a, n, ym, ysd);
+                    float corr = 0.0f;
+                    for (int i = 0; i < n; i++) {
+                        const float dx = (float)i - xm;
+                        const float dy = a.get(i) - ym;
+                        const float d = dx * dy;
+                        corr += d;
+                    }
+                    float den = xsd * ysd;
+                    den = den * (fn + 1.0f);
+                    corr = corr / den;
+                    float slope = corr * ysd;
+                    slope = slope / xsd;
+                    const float sx = slope * xm;
+                    const float icpt = ym - sx;
+                    float sg = 0.0f;
+                    for (int i = 0; i < n; i++) {
+                        float lin = (float)i * slope;
+                        lin = lin + icpt;
+                        const float diff = a.get(i) - lin;
+                        sg += fabsf(diff);
+                    }
+                    sg = sg / fn;
+                    const float lb = p.sig_lo * sg, hb = p.sig_hi * sg;
+                    const bool last = n < 3;            // this sweep ends the loop whatever it rejects: count only
+                    int kept = 0;
+                    for (int i = 0; i < n; i++) {
+                        const float g = a.get(i);
+                        float lin = (float)i * slope;
+                        lin = lin + icpt;
+                        const bool low = (lin - g) > lb;
+                        const bool high = !low && ((g - lin) > hb);
+                        if (low) c_lo++;
+                        else if (high) c_hi++;
+                        else {
+                            if (!last) { a.set(kept, g); b.set(kept, b.get(i)); }
+                            kept++;
+                        }
+                    }
+                    if (kept == n || last) break;       // (nothing rejected: the compaction wrote every slot onto itself)
+                    n = kept;
+                }
+                // the value column is free now: slot k = "frame k is one of the n frames of the last regression"
+                for (int k2 = 0; k2 < N; k2++) a.set(k2, 0.0f);
+                for (int i = 0; i < n; i++) a.set(__float_as_int(b.get(i)), 1.0f);
+                float num = 0.0f, wsum = 0.0f;
+                for (int k2 = 0; k2 < N; k2++) {
+                    const float v = fr[(int64_t)k2 * p.stride];
+                    if (a.get(k2) != 0.0f) {
+                        const float wk = p.weights[k2];
+                        const float pr = v * wk;
+                        num += pr;
+                        wsum += wk;
+                    }
+                }
+                res = num / wsum;
             }
         } else if (MODE == NL_ST_LINEAR_FIT) {
             // pad the column with +Inf up to n_pad and sort once; rejects are
@@ -442,7 +539,7 @@ int exact_plan(int mode, bool weighted, int n_frames, int n_pad, int max_lanes, 
                size_t *lds_bytes)
 {
     const int columns = ((mode == NL_ST_MAD_SIGMA) ||
-                         (weighted && (mode == NL_ST_SIGMA || mode == NL_ST_WINSOR_SIGMA))) ? 2 : 1;
+                         (weighted && (mode == NL_ST_SIGMA || mode == NL_ST_WINSOR_SIGMA || mode == NL_ST_LINEAR_FIT))) ? 2 : 1;
     const size_t n_alloc = (mode == NL_ST_LINEAR_FIT) ? (size_t)n_pad : (size_t)n_frames;
     for (int l = 64; l >= 4; l >>= 1) {
         if (l > max_lanes || l == 8) continue;
@@ -481,6 +578,11 @@ hipError_t launch_stack_exact(int mode, bool weighted, const StackArgs &args, in
         *name = "stack_exact_kernel<mad>";
         return launch_exact<NL_ST_MAD_SIGMA, false>(args, lanes, grid, lds_bytes, stream);
     case NL_ST_LINEAR_FIT:
+        if (weighted) {                  // the weighted linear-fit pass (include/nlstack_wlinfit.h), never a default pass
+            if (!args.weights) return hipErrorInvalidValue;
+            *name = "stack_exact_kernel<linfit,weighted>";
+            return launch_exact<NL_ST_LINEAR_FIT, true>(args, lanes, grid, lds_bytes, stream);
+        }
         *name = "stack_exact_kernel<linearfit>";
         return launch_exact<NL_ST_LINEAR_FIT, false>(args, lanes, grid, lds_bytes, stream);
     default:

@@ -314,6 +314,12 @@ hipError_t launch_stack_linfit_fast(const StackArgs &args, const FastArgs &fargs
 hipError_t launch_stack_linfit_ml(const StackArgs &args, const FastArgs &fargs, const LinfitCascade *cascade,
                                   hipStream_t stream, const char **name, hipEvent_t dominant_done);
 
+// ---- stack_linfit_weighted.hip (the weighted linear-fit pass, include/nlstack_wlinfit.h: register-resident fit, one
+// pixel per lane, up to 128 frames; args.weights must be set; pixels it cannot decide go to fargs.fb_list, for
+// launch_stack_exact(NL_ST_LINEAR_FIT, weighted = true, ...)) ----
+int linfit_weighted_supported(int n_frames, int64_t npix);
+hipError_t launch_stack_linfit_weighted(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name);
+
 // ---- stack_mean.hip ----
 hipError_t launch_stack_mean(bool weighted, const StackArgs &args, hipStream_t stream,
                              const char **name);

@@ -132,7 +132,9 @@ std::string OpStack::MarshalJSON() const
 {
     std::ostringstream o;
     o << "{\"type\":\"" << Type << "\",\"mode\":" << Mode << ",\"weighting\":" << Weighting
-      << ",\"sigmaLow\":" << fmt_g(SigmaLow) << ",\"sigmaHigh\":" << fmt_g(SigmaHigh) << "}";
+      << ",\"sigmaLow\":" << fmt_g(SigmaLow) << ",\"sigmaHigh\":" << fmt_g(SigmaHigh);
+    if (WeightedLinearFit) o << ",\"weightedLinearFit\":true";       // (an extension: absent unless set)
+    o << "}";
     return o.str();
 }
 
@@ -173,7 +175,8 @@ bool OpStack::UnmarshalJSON(const std::string &data, std::string *err)
     if (find_value(data, "weighting", &v)) def.Weighting = (int)strtol(v.c_str(), &end, 10);
     if (find_value(data, "sigmaLow", &v)) def.SigmaLow = strtof(v.c_str(), &end);
     if (find_value(data, "sigmaHigh", &v)) def.SigmaHigh = strtof(v.c_str(), &end);
-    Type = def.Type; Mode = def.Mode; Weighting = def.Weighting;
+    if (find_value(data, "weightedLinearFit", &v)) def.WeightedLinearFit = v == "true";
+    Type = def.Type; Mode = def.Mode; Weighting = def.Weighting; WeightedLinearFit = def.WeightedLinearFit;
     SigmaLow = def.SigmaLow; SigmaHigh = def.SigmaHigh; RefFrameLoc = 0;
     return true;
 }
@@ -301,7 +304,12 @@ Result OpStack::Apply(const std::vector<ImagePtr> &f, Context *c)
         // with a resident group the result stays on the devices (Data left empty)
         std::vector<float> data(Resident ? 0 : f[0]->Data.size());
         int64_t clipLow = 0, clipHigh = 0;
-        if (rc == NL_OK) rc = nl_group_run(h, mode, SigmaLow, SigmaHigh, RefFrameLoc, Resident ? nullptr : data.data(), &clipLow, &clipHigh);
+        // (the extension: the fit rejects, the weights average; the reference's fit drops them)
+        const bool weightedFit = WeightedLinearFit && mode == StLinearFit && !weights.empty();
+        if (rc == NL_OK && weightedFit)
+            rc = nl_group_run_linfit_weighted(h, SigmaLow, SigmaHigh, RefFrameLoc, Resident ? nullptr : data.data(), &clipLow, &clipHigh);
+        else if (rc == NL_OK)
+            rc = nl_group_run(h, mode, SigmaLow, SigmaHigh, RefFrameLoc, Resident ? nullptr : data.data(), &clipLow, &clipHigh);
         if (rc != NL_OK) { out.err = nl_last_error(); break; }
         if (mode >= StSigma && c && c->Log) {          // stack.go:214-218
             const float total = (float)((int64_t)f[0]->Data.size() * (int64_t)f.size());

@@ -18,6 +18,10 @@ struct OpStack : Operator, OpBase {
     float SigmaLow = 2.75f;       // json:"sigmaLow"
     float SigmaHigh = 2.75f;      // json:"sigmaHigh"
     float RefFrameLoc = 0;        // json:"-"  (never assigned in the reference)
+    // not in the reference (an EXTENSION, include/nlstack_wlinfit.h): when the mode resolves to the linear fit and the
+    // weighting is not none, reject by the fit and average the survivors with the weights, instead of dropping the
+    // weights as the reference does (stack.go:188-189).  Parsed when present, emitted only when true.
+    bool WeightedLinearFit = false;   // json:"weightedLinearFit"
     // not in the reference: a group of device handles the caller keeps across several Apply calls
     // (OpStackBatches).  When set, Apply stacks on it and leaves the result tile on the devices
     // (the returned image carries metadata only) for nl_group_accumulate.

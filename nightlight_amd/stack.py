@@ -167,6 +167,24 @@ class StackHandle:
                                                _u16ptr(reject_low), _u16ptr(reject_high)))
         return out, cl.value, ch.value, reject_low, reject_high
 
+    def run_linfit_weighted(self, sigma_low=2.75, sigma_high=2.75, ref_loc=0.0, out=None, fetch=True):
+        """One pass of the weighted linear fit (include/nlstack_wlinfit.h; an EXTENSION, the reference's fit takes
+        no weights): the reference's linear-fit rejection, then the mean of the survivors with the weights of
+        set_weights.  Returns (result or None, clip_low, clip_high) as run does; the counters are those of
+        run(ST_LINEAR_FIT).  Without weights it raises NlError (ERR_INVALID_ARG)."""
+        cl, ch = C.c_int64(0), C.c_int64(0)
+        if fetch and out is None:
+            out = np.zeros(self.width * self.height, np.float32)
+        optr = capi.fptr(out) if (fetch and out is not None) else None
+        capi.check(self._lib.nl_stack_run_linfit_weighted(self._h, C.c_float(sigma_low), C.c_float(sigma_high),
+                                                          C.c_float(ref_loc), optr, C.byref(cl), C.byref(ch)))
+        return (out if fetch else None), cl.value, ch.value
+
+    def run_linfit_weighted_async(self, sigma_low=2.75, sigma_high=2.75, ref_loc=0.0):
+        """run_linfit_weighted without the wait: finish() completes it."""
+        capi.check(self._lib.nl_stack_run_linfit_weighted_async(self._h, C.c_float(sigma_low), C.c_float(sigma_high),
+                                                                C.c_float(ref_loc)))
+
     def coverage(self, out=None):
         """Whole-image uint16 map of how many active frames have a sample (not NaN) at each pixel: the tile's rows
         of `out` (made here, zero outside the tile, if not given).  No pass: the last result stays."""
@@ -639,6 +657,15 @@ class StackGroup:
                                                C.c_float(ref_loc), capi.fptr(out), C.byref(cl), C.byref(ch),
                                                _u16ptr(lo), _u16ptr(hi)))
         return out, cl.value, ch.value, lo, hi
+
+    def run_linfit_weighted(self, sigma_low=2.75, sigma_high=2.75, ref_loc=0.0, download=True):
+        """StackHandle.run_linfit_weighted over the tiles: (result or None, clip_low, clip_high)."""
+        out = np.zeros(self.width * self.height, np.float32) if download else None
+        cl, ch = C.c_int64(0), C.c_int64(0)
+        capi.check(self._lib.nl_group_run_linfit_weighted(self._g, C.c_float(sigma_low), C.c_float(sigma_high),
+                                                          C.c_float(ref_loc), capi.fptr(out) if download else None,
+                                                          C.byref(cl), C.byref(ch)))
+        return out, cl.value, ch.value
 
     def coverage(self):
         """StackHandle.coverage over the tiles."""
