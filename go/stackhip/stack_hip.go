@@ -67,6 +67,40 @@ func GroupProjectFrom(g unsafe.Pointer, idx int, src unsafe.Pointer, srcIdx int,
 	return nil
 }
 
+// ResampleFrom is ProjectFrom with a resampling kernel of the caller's choice (include/nlstack_resample.h): kernel 0 is
+// the reference's bilinear interpolation, 1 bicubic (Catmull-Rom), 2 Lanczos-3; clamp holds every pixel to the range of
+// its four nearest source pixels.  An EXTENSION, not in the reference: Image.Project resamples bilinearly.
+func ResampleFrom(dst unsafe.Pointer, dstIdx int, src unsafe.Pointer, srcIdx int, trans [6]float32, outOfBounds float32,
+	kernel int, clamp bool) error {
+	runtime.LockOSThread() // nl_last_error() is per OS thread
+	defer runtime.UnlockOSThread()
+	c := C.int(0)
+	if clamp {
+		c = 1
+	}
+	if rc := C.nl_stack_frame_resample_from((*C.nl_stack_t)(dst), C.int(dstIdx), (*C.nl_stack_t)(src), C.int(srcIdx),
+		(*C.float)(unsafe.Pointer(&trans[0])), C.float(outOfBounds), C.int(kernel), c); rc != C.NL_OK {
+		return lastError()
+	}
+	return nil
+}
+
+// GroupResampleFrom is ResampleFrom into slot idx of every tile of a group (*C.nl_group_t): each tile resamples its own rows.
+func GroupResampleFrom(g unsafe.Pointer, idx int, src unsafe.Pointer, srcIdx int, trans [6]float32, outOfBounds float32,
+	kernel int, clamp bool) error {
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	c := C.int(0)
+	if clamp {
+		c = 1
+	}
+	if rc := C.nl_group_frame_resample_from((*C.nl_group_t)(g), C.int(idx), (*C.nl_stack_t)(src), C.int(srcIdx),
+		(*C.float)(unsafe.Pointer(&trans[0])), C.float(outOfBounds), C.int(kernel), c); rc != C.NL_OK {
+		return lastError()
+	}
+	return nil
+}
+
 // LocationScale is Stats.Location() / Scale() (internal/stats/stats.go:225-244) of a frame that is resident on the
 // device: slot idx of the whole-image handle h (idx < 0: the last pass's result), with the estimator the reference
 // runs (stats.LSEstimator as an int, 3 = LSESCMedianQn by default; 2 = LSEIKSS is not implemented on the device).

@@ -681,6 +681,11 @@ int nl_group_frame_project_from(nl_group_t *g, int idx, nl_stack_t *src, int src
 int nl_stack_project_tile_paths(nl_stack_t *dst, nl_stack_t *src, int src_idx, const float trans[6],
                                 int64_t *staged, int64_t *direct);
 
+/* The same projection with a bicubic or Lanczos-3 resampling kernel (AN EXTENSION: the reference resamples
+ * bilinearly): nl_stack_frame_resample_from, nl_group_frame_resample_from, nl_stack_resample_tile_paths and
+ * nl_resample_lanczos3_table are declared in nlstack_resample.h, which is part of this interface. */
+#include "nlstack_resample.h"
+
 /* ---- OpGaussianBlur / OpUnsharpMask / OpHSLUnsharpMask's UnsharpMask ----
  * (internal/ops/stretch/stretch.go:339-424, internal/ops/stretch/usm.go, internal/ops/hsl/hsl.go:538-551)
  * The two passes of GaussFilter2D (usm.go:118-122): Convolve1DX (usm.go:85-98) into a scratch frame of the

@@ -90,6 +90,13 @@ WLINFIT_EXPORTS = ["nl_stack_run_linfit_weighted", "nl_stack_run_linfit_weighted
 ALIGN_EXPORTS = ["nl_aligner_create", "nl_aligner_destroy", "nl_aligner_info", "nl_aligner_match",
                  "nl_aligner_match_stars"]
 
+# every symbol include/nlstack_resample.h declares (likewise): bicubic / Lanczos-3 resampling of the resident projection,
+# an extension
+RESAMPLE_EXPORTS = ["nl_resample_lanczos3_table", "nl_stack_frame_resample_from", "nl_group_frame_resample_from",
+                    "nl_stack_resample_tile_paths"]
+RS_BILINEAR, RS_BICUBIC, RS_LANCZOS3 = range(3)
+RS_PHASES = 1024
+
 # nl_star_t = star.Star (findstars.go:30-37), 24 bytes
 STAR_DTYPE = np.dtype([("index", "<i4"), ("value", "<f4"), ("x", "<f4"), ("y", "<f4"), ("mass", "<f4"),
                        ("hfr", "<f4")])
@@ -383,6 +390,10 @@ def open_library(path):
     L.nl_stack_frame_project_from.argtypes = [vp, C.c_int, vp, C.c_int, _f32p, C.c_float]
     L.nl_group_frame_project_from.argtypes = [vp, C.c_int, vp, C.c_int, _f32p, C.c_float]
     L.nl_stack_project_tile_paths.argtypes = [vp, vp, C.c_int, _f32p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.nl_resample_lanczos3_table.argtypes = [_f32p]
+    L.nl_stack_frame_resample_from.argtypes = [vp, C.c_int, vp, C.c_int, _f32p, C.c_float, C.c_int, C.c_int]
+    L.nl_group_frame_resample_from.argtypes = [vp, C.c_int, vp, C.c_int, _f32p, C.c_float, C.c_int, C.c_int]
+    L.nl_stack_resample_tile_paths.argtypes = [vp, vp, C.c_int, _f32p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     _planes = C.POINTER(C.c_int)
     # stars, n_stars, block, border, skip_bright, skip_dim, shadows, highlights, loc, scale, report
     _balance_args = [vp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, Rgb, Rgb, _f32p, _f32p, C.POINTER(RgbBalance)]

@@ -55,8 +55,8 @@ int project_from_check(const char *who, nl_stack_t *dst, int dst_idx, nl_stack_t
 }
 
 // the source rows [*y0, *y1] that the destination rows of dst can tap (project.hpp: the corners of a rectangle bound
-// every pixel's coordinates); false: none
-bool project_source_rows(const nl_stack_t *dst, const nl_stack_t *src, const float inv[6], int *y0, int *y1)
+// every pixel's coordinates) with a kernel of radius grow + 1; false: none
+bool project_source_rows(const nl_stack_t *dst, const nl_stack_t *src, const float inv[6], int grow, int *y0, int *y1)
 {
     const nl::ProjInv t = {inv[0], inv[1], inv[2], inv[3], inv[4], inv[5]};
     const float px[2] = {0.0f, (float)(dst->width - 1)}, py[2] = {(float)dst->row0, (float)(dst->row0 + dst->rows - 1)};
@@ -67,8 +67,8 @@ bool project_source_rows(const nl_stack_t *dst, const nl_stack_t *src, const flo
         lo = fminf(lo, y);
         hi = fmaxf(hi, y);
     }
-    *y0 = std::max(nl::proj_floor_clamped(lo), 0);
-    *y1 = std::min(nl::proj_floor_clamped(hi) + 1, src->height - 1);
+    *y0 = std::max(nl::proj_floor_clamped(lo) - grow, 0);
+    *y1 = std::min(nl::proj_floor_clamped(hi) + 1 + grow, src->height - 1);
     return *y0 <= *y1;
 }
 
@@ -215,7 +215,7 @@ int nl::stack_settle(nl_stack_t *h)
 // threads of their own; a destination on another device than the source first receives the source rows it can tap,
 // peer to peer, at their place in its ingest buffer.
 int nl::stack_project_from(nl_stack_t *dst, int dst_idx, nl_stack_t *src, int src_idx, const float trans[6],
-                           float out_of_bounds, const char *who, bool from_group)
+                           float out_of_bounds, const char *who, bool from_group, int kernel, int clamp)
 {
     NL_CHECK_HANDLE(src);
     NL_CHECK_HANDLE(dst);
@@ -231,17 +231,33 @@ int nl::stack_project_from(nl_stack_t *dst, int dst_idx, nl_stack_t *src, int sr
     if (src->device != dst->device) {
         NL_HIP(dst->ingest.reserve((size_t)src->npix * sizeof(float), dst->stream));
         int y0 = 0, y1 = 0;
-        if (project_source_rows(dst, src, inv, &y0, &y1)) {
+        if (project_source_rows(dst, src, inv, kernel, &y0, &y1)) {               // (NL_RS_*: the radius - 1)
             const size_t at = (size_t)y0 * (size_t)src->width;
             NL_HIP(hipMemcpyPeerAsync(static_cast<float *>(dst->ingest.ptr) + at, dst->device, s + at, src->device,
                                       sizeof(float) * (size_t)(y1 - y0 + 1) * (size_t)src->width, dst->stream));
         }
         s = static_cast<float *>(dst->ingest.ptr);
     }
-    NL_HIP(nl::launch_project_tiled(s, src->width, src->height, d, dst->width, dst->row0, dst->rows, inv, out_of_bounds,
-                                    project_switches(dst), dst->stream));
+    if (kernel == NL_RS_BILINEAR) {
+        NL_HIP(nl::launch_project_tiled(s, src->width, src->height, d, dst->width, dst->row0, dst->rows, inv, out_of_bounds,
+                                        project_switches(dst), dst->stream));
+    } else {                                                   // include/nlstack_resample.h (an extension)
+        const float *table = nullptr;
+        if (kernel == NL_RS_LANCZOS3) NL_HIP(nl::lanczos3_table_device(dst->device, &table));
+        NL_HIP(nl::launch_resample_tiled(s, src->width, src->height, d, dst->width, dst->row0, dst->rows, inv, out_of_bounds,
+                                         kernel + 1, clamp != 0, table, project_switches(dst), dst->stream));
+    }
     NL_HIP(hipStreamSynchronize(dst->stream));                 // the caller may overwrite the source slot at once
     return NL_OK;
+}
+
+int nl::resample_args_check(const char *who, int kernel, const float *trans)
+{
+    if (kernel != NL_RS_BILINEAR && kernel != NL_RS_BICUBIC && kernel != NL_RS_LANCZOS3)
+        return fail(NL_ERR_INVALID_ARG, "%s: unknown kernel %d (NL_RS_BILINEAR 0, NL_RS_BICUBIC 1, NL_RS_LANCZOS3 2)", who, kernel);
+    if (!trans) return fail(NL_ERR_INVALID_ARG, "%s: null transform", who);
+    float inv[6];
+    return invert_transform(trans, inv);
 }
 
 extern "C" {
@@ -428,6 +444,41 @@ int nl_stack_project_tile_paths(nl_stack_t *dst, nl_stack_t *src, int src_idx, c
     if (rc != NL_OK) return rc;
     nl::project_tile_paths(s, src->width, src->height, dst->width, dst->row0, dst->rows, inv, project_switches(dst),
                            staged, direct);
+    return NL_OK;
+}
+
+// ---- the same projection with a bicubic or Lanczos-3 kernel (include/nlstack_resample.h, an extension; kernels in resample.hip) ----
+
+int nl_resample_lanczos3_table(float *table)
+{
+    if (!table) return fail(NL_ERR_INVALID_ARG, "resample_lanczos3_table: null table");
+    memcpy(table, nl::lanczos3_table_host(), sizeof(float) * NL_RS_PHASES * 6);
+    return NL_OK;
+}
+
+int nl_stack_frame_resample_from(nl_stack_t *dst, int dst_idx, nl_stack_t *src, int src_idx, const float trans[6],
+                                 float out_of_bounds, int kernel, int clamp)
+{
+    const int rc = nl::resample_args_check("frame_resample_from", kernel, trans);      // in front of any device work
+    if (rc != NL_OK) return rc;
+    if (!dst || !src) return fail(NL_ERR_INVALID_ARG, "frame_resample_from: null handle");
+    return nl::stack_project_from(dst, dst_idx, src, src_idx, trans, out_of_bounds, "frame_resample_from", false, kernel, clamp);
+}
+
+int nl_stack_resample_tile_paths(nl_stack_t *dst, nl_stack_t *src, int src_idx, const float trans[6], int kernel,
+                                 int64_t *staged, int64_t *direct)
+{
+    if (!dst || !src || !trans || !staged || !direct) return fail(NL_ERR_INVALID_ARG, "resample_tile_paths: null argument");
+    const int rc = nl::resample_args_check("resample_tile_paths", kernel, trans);
+    if (rc != NL_OK) return rc;
+    if (kernel == NL_RS_BILINEAR) return nl_stack_project_tile_paths(dst, src, src_idx, trans, staged, direct);
+    if (src_idx < 0 || src_idx >= src->n_frames)               // (a host query: no device, no stream is touched)
+        return fail(NL_ERR_INVALID_ARG, "resample_tile_paths: bad index %d", src_idx);
+    const float *s = src->d_frames + (int64_t)src_idx * src->fstride;
+    float inv[6];
+    (void)invert_transform(trans, inv);
+    nl::resample_tile_paths(s, src->width, src->height, dst->width, dst->row0, dst->rows, inv, kernel + 1,
+                            project_switches(dst), staged, direct);
     return NL_OK;
 }
 

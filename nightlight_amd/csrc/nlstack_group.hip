@@ -165,6 +165,23 @@ int nl_group_frame_project_from(nl_group_t *g, int idx, nl_stack_t *src, int src
     });
 }
 
+// nl_group_frame_project_from with a bicubic or Lanczos-3 kernel (include/nlstack_resample.h, an extension)
+int nl_group_frame_resample_from(nl_group_t *g, int idx, nl_stack_t *src, int src_idx, const float trans[6],
+                                 float out_of_bounds, int kernel, int clamp)
+{
+    int rc = nl::resample_args_check("group_frame_resample_from", kernel, trans);     // in front of any device work
+    if (rc != NL_OK) return rc;
+    if (!g || !src) {
+        nl::set_last_error(g ? "group_frame_resample_from: null handle" : "group_frame_resample_from: null group");
+        return NL_ERR_INVALID_ARG;
+    }
+    if ((rc = nl::stack_settle(src)) != NL_OK) return rc;  // once, here: the tiles' threads only read the source
+    return for_each_tile(g, [&](size_t t) {
+        return nl::stack_project_from(g->tiles[t], idx, src, src_idx, trans, out_of_bounds, "group_frame_resample_from", true,
+                                      kernel, clamp);
+    });
+}
+
 int nl_group_fill_synthetic(nl_group_t *g, uint64_t seed)
 {
     if (!g) return NL_ERR_INVALID_ARG;

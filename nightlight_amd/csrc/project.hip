@@ -22,44 +22,6 @@ namespace nl {
 
 namespace {
 
-// the box of the tile into LDS: unit = 4 floats (16-byte loads) or 1; at most kProjLdsFloats / 256 units per lane in
-// flight per round
-template <bool VEC>
-__device__ __forceinline__ void stage_box(const float *__restrict__ src, int src_w, const ProjBox &b, float *lds)
-{
-    constexpr int U = VEC ? 6 : 8;
-    const int per_row = VEC ? b.w >> 2 : b.w;
-    const int total = per_row * b.h;
-    const float *base = src + (int64_t)b.y0 * src_w + b.x0;
-    for (int first = threadIdx.x; first < total; first += 256 * U) {
-        float4 v[U];
-        int at[U];
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            const int i = first + 256 * u;
-            at[u] = -1;
-            if (i < total) {
-                const int y = i / per_row, x = i - y * per_row;
-                if constexpr (VEC) {
-                    v[u] = *reinterpret_cast<const float4 *>(base + (int64_t)y * src_w + 4 * x);
-                    at[u] = y * b.pitch + 4 * x;
-                } else {
-                    v[u].x = base[(int64_t)y * src_w + x];
-                    at[u] = y * b.pitch + x;
-                }
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            if (at[u] < 0) continue;
-            lds[at[u]] = v[u].x;
-            if constexpr (VEC) {
-                lds[at[u] + 1] = v[u].y; lds[at[u] + 2] = v[u].z; lds[at[u] + 3] = v[u].w;
-            }
-        }
-    }
-}
-
 // rows of the tile for this wave, four pixels per lane and row.  STAGED: taps from the box in LDS, else from src.
 // A pixel out of bounds taps element 0 (always there) and drops the result: no branch around the loads.
 template <bool NT, bool STAGED>

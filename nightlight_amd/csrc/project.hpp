@@ -1,6 +1,7 @@
-// project.hpp -- the tile geometry of project.hip and the one piece of arithmetic its kernel and the host share: the
-// source box of a destination tile.  Host and device run the same fp32 operations (no contraction on either side), so
-// project_tile_paths() counts exactly the tiles the kernel stages.
+// project.hpp -- the tile geometry of project.hip and resample.hip (the same projection with a wider resampling kernel),
+// the one piece of arithmetic their kernels and the host share: the source box of a destination tile, and how a
+// workgroup stages that box in LDS.  Host and device run the same fp32 operations (no contraction on either side), so
+// project_tile_paths() and resample_tile_paths() count exactly the tiles the kernels stage.
 #pragma once
 #include <stdint.h>
 
@@ -43,8 +44,12 @@ __host__ __device__ inline int proj_floor_clamped(float v)
 // included -- are therefore taken at corners, and floor(X), floor(X) + 1 of every pixel lie in
 // [floor(min corner), floor(max corner) + 1].  Same for Y.  With finite coefficients a NaN (inf - inf) inside the
 // rectangle implies one at a corner by the same argument; the launcher stages nothing when a coefficient is not finite.
+//
+// grow (resample.hip: R - 1 of a kernel of radius R) widens the box by that many pixels on every side, as far as the
+// source reaches: the wide footprints of the same pixels.  Whether a tile has a pixel in bounds does not depend on it.
+// lds_floats is the budget of the kernel that asks.
 __host__ __device__ inline bool proj_tile_box(const ProjInv &t, int src_w, int src_h, int c0, int c1, int r0, int r1,
-                                              bool vec, ProjBox &b)
+                                              bool vec, ProjBox &b, int grow = 0, int lds_floats = kProjLdsFloats)
 {
     const float px0 = (float)c0, px1 = (float)c1, py0 = (float)r0, py1 = (float)r1;
     const float x00 = proj_x(t, px0, py0), x10 = proj_x(t, px1, py0), x01 = proj_x(t, px0, py1), x11 = proj_x(t, px1, py1);
@@ -61,6 +66,10 @@ __host__ __device__ inline bool proj_tile_box(const ProjInv &t, int src_w, int s
     if (x1 > src_w - 1) x1 = src_w - 1;
     if (y1 > src_h - 1) y1 = src_h - 1;
     if (x1 - x0 < 1 || y1 - y0 < 1) return false;          // no room for one 2x2 footprint
+    x0 = x0 - grow < 0 ? 0 : x0 - grow;
+    y0 = y0 - grow < 0 ? 0 : y0 - grow;
+    x1 = x1 + grow > src_w - 1 ? src_w - 1 : x1 + grow;
+    y1 = y1 + grow > src_h - 1 ? src_h - 1 : y1 + grow;
     if (vec) {                                             // whole 16-byte groups of a row (src_w is a multiple of 4)
         x0 &= ~3;
         x1 |= 3;
@@ -70,7 +79,45 @@ __host__ __device__ inline bool proj_tile_box(const ProjInv &t, int src_w, int s
     b.w = x1 - x0 + 1;
     b.h = y1 - y0 + 1;
     b.pitch = b.w | 1;                                     // odd: taps down a column (a 90 degree turn) spread over the banks
-    return (int64_t)b.pitch * b.h <= kProjLdsFloats;
+    return (int64_t)b.pitch * b.h <= lds_floats;
+}
+
+// the box of the tile into LDS: unit = 4 floats (16-byte loads) or 1; at most kProjLdsFloats / 256 units per lane in
+// flight per round
+template <bool VEC>
+__device__ __forceinline__ void stage_box(const float *__restrict__ src, int src_w, const ProjBox &b, float *lds)
+{
+    constexpr int U = VEC ? 6 : 8;
+    const int per_row = VEC ? b.w >> 2 : b.w;
+    const int total = per_row * b.h;
+    const float *base = src + (int64_t)b.y0 * src_w + b.x0;
+    for (int first = threadIdx.x; first < total; first += 256 * U) {
+        float4 v[U];
+        int at[U];
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const int i = first + 256 * u;
+            at[u] = -1;
+            if (i < total) {
+                const int y = i / per_row, x = i - y * per_row;
+                if constexpr (VEC) {
+                    v[u] = *reinterpret_cast<const float4 *>(base + (int64_t)y * src_w + 4 * x);
+                    at[u] = y * b.pitch + 4 * x;
+                } else {
+                    v[u].x = base[(int64_t)y * src_w + x];
+                    at[u] = y * b.pitch + x;
+                }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            if (at[u] < 0) continue;
+            lds[at[u]] = v[u].x;
+            if constexpr (VEC) {
+                lds[at[u] + 1] = v[u].y; lds[at[u] + 2] = v[u].z; lds[at[u] + 3] = v[u].w;
+            }
+        }
+    }
 }
 
 }  // namespace nl

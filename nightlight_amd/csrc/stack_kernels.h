@@ -116,9 +116,12 @@ struct FastArgs {
 
 // sets what nl_last_error() returns on this thread (nlstack_api.hip)
 void set_last_error(const char *msg);
-// nl_stack_frame_project_from / nl_group_frame_project_from (nlstack_frame.hip, with nl::stack_settle); who = the call's name in messages
+// nl_stack_frame_project_from / nl_group_frame_project_from and, with a kernel (NL_RS_*, checked by the caller) and the
+// clamp, their _resample_from forms (nlstack_frame.hip, with nl::stack_settle); who = the call's name in messages
 int stack_project_from(nl_stack_t *dst, int dst_idx, nl_stack_t *src, int src_idx, const float trans[6],
-                       float out_of_bounds, const char *who, bool from_group);
+                       float out_of_bounds, const char *who, bool from_group, int kernel = NL_RS_BILINEAR, int clamp = 0);
+// what the _resample_from entries check in front of their handles: the kernel's id, a null or singular transform
+int resample_args_check(const char *who, int kernel, const float *trans);
 int stack_settle(nl_stack_t *h);
 // the two halves of nl_stack_run_maps (nlstack_pass.hip), so that nl_group_run_maps starts every tile before it awaits any;
 // a failing first half settles the handle as nl_stack_run_async does
@@ -348,6 +351,18 @@ hipError_t launch_project_tiled(const float *src, int src_w, int src_h, float *d
 // how many tiles of that launch stage their source box in LDS, how many tap global memory (host arithmetic, the kernel's own)
 void project_tile_paths(const float *src, int src_w, int src_h, int dst_w, int row0, int rows, const float inv[6],
                         unsigned switches, int64_t *staged, int64_t *direct);
+
+// ---- resample.hip (the same projection with a bicubic or Lanczos-3 kernel, include/nlstack_resample.h: an extension) ----
+// radius = 2 (bicubic) or 3 (Lanczos-3, with table = lanczos3_table_device of the stream's device); switches as above
+hipError_t launch_resample_tiled(const float *src, int src_w, int src_h, float *dst, int dst_w, int row0, int rows,
+                                 const float inv[6], float oob, int radius, bool clamp, const float *table,
+                                 unsigned switches, hipStream_t stream);
+void resample_tile_paths(const float *src, int src_w, int src_h, int dst_w, int row0, int rows, const float inv[6],
+                         int radius, unsigned switches, int64_t *staged, int64_t *direct);
+// the NL_RS_PHASES x 6 Lanczos-3 table: built once on the host; one copy per device, made by the first call that asks
+// for it (the caller has selected `device`), kept for the life of the library
+const float *lanczos3_table_host();
+hipError_t lanczos3_table_device(int device, const float **table);
 
 // ---- synth.hip ----
 hipError_t launch_fill_synthetic(float *frames, int64_t stride, int n_frames, int width,

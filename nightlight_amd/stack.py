@@ -549,6 +549,24 @@ class StackHandle:
                                                          C.byref(staged), C.byref(direct)))
         return int(staged.value), int(direct.value)
 
+    def frame_resample_from(self, idx, src, src_idx, trans, out_of_bounds=float("nan"), kernel=capi.RS_LANCZOS3,
+                            clamp=False):
+        """frame_project_from with the resampling kernel `kernel` (capi.RS_BILINEAR, RS_BICUBIC, RS_LANCZOS3) and, with
+        clamp, the result held to the range of its four central taps (include/nlstack_resample.h; an EXTENSION, the
+        reference resamples bilinearly).  Where a pixel's wide footprint does not fit the source it gets the bilinear
+        value, so the valid area does not depend on the kernel."""
+        t = np.ascontiguousarray(trans, dtype=np.float32).reshape(6)
+        capi.check(self._lib.nl_stack_frame_resample_from(self._h, int(idx), src._h, int(src_idx), capi.fptr(t),
+                                                          float(out_of_bounds), int(kernel), int(bool(clamp))))
+
+    def resample_tile_paths(self, src, src_idx, trans, kernel=capi.RS_LANCZOS3):
+        """project_tile_paths for frame_resample_from(., src, src_idx, trans, ., kernel) (developer query)."""
+        t = np.ascontiguousarray(trans, dtype=np.float32).reshape(6)
+        staged, direct = C.c_int64(0), C.c_int64(0)
+        capi.check(self._lib.nl_stack_resample_tile_paths(self._h, src._h, int(src_idx), capi.fptr(t), int(kernel),
+                                                          C.byref(staged), C.byref(direct)))
+        return int(staged.value), int(direct.value)
+
     def download_result_fits(self):
         raw = np.empty(self.tile_pixels * 4, np.uint8)
         capi.check(self._lib.nl_stack_download_result_fits(self._h, raw.ctypes.data_as(C.c_void_p)))
@@ -622,6 +640,13 @@ class StackGroup:
         t = np.ascontiguousarray(trans, dtype=np.float32).reshape(6)
         capi.check(self._lib.nl_group_frame_project_from(self._g, int(idx), src._h, int(src_idx), capi.fptr(t),
                                                          float(out_of_bounds)))
+
+    def frame_resample_from(self, idx, src, src_idx, trans, out_of_bounds=float("nan"), kernel=capi.RS_LANCZOS3,
+                            clamp=False):
+        """StackHandle.frame_resample_from on the group: every tile resamples its own rows from the resident slot."""
+        t = np.ascontiguousarray(trans, dtype=np.float32).reshape(6)
+        capi.check(self._lib.nl_group_frame_resample_from(self._g, int(idx), src._h, int(src_idx), capi.fptr(t),
+                                                          float(out_of_bounds), int(kernel), int(bool(clamp))))
 
     def fill_synthetic(self, seed=0x4E4C5354):
         capi.check(self._lib.nl_group_fill_synthetic(self._g, C.c_uint64(seed)))
@@ -1082,6 +1107,13 @@ def gaussian_kernel_1d(sigma, capacity=None):
     taps = np.empty(max(int(capacity), 1), np.float32)
     capi.check(lib.nl_gaussian_kernel_1d(float(sigma), capi.fptr(taps), int(capacity), C.byref(n)))
     return taps[:n.value].copy()
+
+
+def lanczos3_table():
+    """The library's Lanczos-3 table, [RS_PHASES, 6] float32 (include/nlstack_resample.h; host only, no device)."""
+    table = np.empty((capi.RS_PHASES, 6), np.float32)
+    capi.check(capi.load().nl_resample_lanczos3_table(capi.fptr(table)))
+    return table
 
 
 def blur_tap_paths(n_taps):
