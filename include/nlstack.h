@@ -341,6 +341,10 @@ int nl_group_accumulate_finalize(nl_group_t *g, float weight_sum, float *out_hos
  * nlstack_maps.h, which is part of this interface. */
 #include "nlstack_maps.h"
 
+/* ---- the same maps from the default pass's engines (sigma / winsorized clipping, unweighted, up to 128 frames) ----
+ * nl_stack_run_maps_fast, nl_group_run_maps_fast: declared in nlstack_fastmaps.h, which is part of this interface. */
+#include "nlstack_fastmaps.h"
+
 /* ---- linear-fit rejection with a weighted mean of the survivors (an extension: the reference's fit takes no weights) ----
  * nl_stack_run_linfit_weighted, nl_stack_run_linfit_weighted_async, nl_group_run_linfit_weighted: declared in
  * nlstack_wlinfit.h, which is part of this interface. */

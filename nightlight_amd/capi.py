@@ -83,6 +83,9 @@ LOCSCALE_EXPORTS = ["nl_stack_frame_location_scale", "nl_location_scale", "nl_lo
 MAPS_EXPORTS = ["nl_stack_run_maps", "nl_stack_coverage", "nl_stack_last_coverage_ms", "nl_group_run_maps",
                 "nl_group_coverage"]
 
+# every symbol include/nlstack_fastmaps.h declares (likewise): the maps pass on the default pass's engines
+FASTMAPS_EXPORTS = ["nl_stack_run_maps_fast", "nl_group_run_maps_fast"]
+
 # every symbol include/nlstack_wlinfit.h declares (likewise): the weighted linear-fit pass, an extension
 WLINFIT_EXPORTS = ["nl_stack_run_linfit_weighted", "nl_stack_run_linfit_weighted_async", "nl_group_run_linfit_weighted"]
 
@@ -272,6 +275,8 @@ def open_library(path):
     _maps_args = [vp, C.c_int, C.c_float, C.c_float, C.c_float, _f32p, _i64p, _i64p, _u16p, _u16p]
     L.nl_stack_run_maps.argtypes = _maps_args
     L.nl_group_run_maps.argtypes = _maps_args
+    L.nl_stack_run_maps_fast.argtypes = _maps_args
+    L.nl_group_run_maps_fast.argtypes = _maps_args
     _wlinfit_args = [vp, C.c_float, C.c_float, C.c_float, _f32p, _i64p, _i64p]
     L.nl_stack_run_linfit_weighted.argtypes = _wlinfit_args
     L.nl_group_run_linfit_weighted.argtypes = _wlinfit_args

@@ -286,11 +286,12 @@ int nl_group_run_linfit_weighted(nl_group_t *g, float sigma_low, float sigma_hig
                      out_host, clip_low, clip_high);
 }
 
-// nl_group_run with the maps (include/nlstack_maps.h): the same protocol -- every pass that was started is finished,
-// the first error with its message is the caller's -- and every tile writes its own rows of the three host buffers
-int nl_group_run_maps(nl_group_t *g, int mode, float sigma_low, float sigma_high, float ref_loc,
-                      float *out_host, int64_t *clip_low, int64_t *clip_high,
-                      uint16_t *reject_low_host, uint16_t *reject_high_host)
+// nl_group_run with the maps (include/nlstack_maps.h; fast: include/nlstack_fastmaps.h): the same protocol -- every pass
+// that was started is finished, the first error with its message is the caller's -- and every tile writes its own rows
+// of the three host buffers
+static int group_run_maps(nl_group_t *g, bool fast, int mode, float sigma_low, float sigma_high, float ref_loc,
+                          float *out_host, int64_t *clip_low, int64_t *clip_high,
+                          uint16_t *reject_low_host, uint16_t *reject_high_host)
 {
     if (!g) { nl::set_last_error("null group"); return NL_ERR_INVALID_ARG; }
     int first_rc = NL_OK;
@@ -300,7 +301,8 @@ int nl_group_run_maps(nl_group_t *g, int mode, float sigma_low, float sigma_high
     };
     size_t started = 0;
     for (; started < g->tiles.size() && first_rc == NL_OK; started++)
-        note(nl::stack_run_maps_async(g->tiles[started], mode, sigma_low, sigma_high, ref_loc));
+        note(fast ? nl::stack_run_maps_fast_async(g->tiles[started], mode, sigma_low, sigma_high, ref_loc)
+                  : nl::stack_run_maps_async(g->tiles[started], mode, sigma_low, sigma_high, ref_loc));
     if (first_rc != NL_OK) started--;                     // (a failing start settles its handle: nothing of it is in flight)
     const bool ok = first_rc == NL_OK;
     int64_t lo = 0, hi = 0;
@@ -327,6 +329,22 @@ int nl_group_run_maps(nl_group_t *g, int mode, float sigma_low, float sigma_high
     if (clip_low) *clip_low = lo;
     if (clip_high) *clip_high = hi;
     return NL_OK;
+}
+
+int nl_group_run_maps(nl_group_t *g, int mode, float sigma_low, float sigma_high, float ref_loc,
+                      float *out_host, int64_t *clip_low, int64_t *clip_high,
+                      uint16_t *reject_low_host, uint16_t *reject_high_host)
+{
+    return group_run_maps(g, false, mode, sigma_low, sigma_high, ref_loc, out_host, clip_low, clip_high, reject_low_host,
+                          reject_high_host);
+}
+
+int nl_group_run_maps_fast(nl_group_t *g, int mode, float sigma_low, float sigma_high, float ref_loc,
+                           float *out_host, int64_t *clip_low, int64_t *clip_high,
+                           uint16_t *reject_low_host, uint16_t *reject_high_host)
+{
+    return group_run_maps(g, true, mode, sigma_low, sigma_high, ref_loc, out_host, clip_low, clip_high, reject_low_host,
+                          reject_high_host);
 }
 
 // every tile counts on its own device and writes its own rows

@@ -178,6 +178,7 @@ enum class Engine {
     MedianMultiLane,      // 129 ... 512 frames, 2 or 4 lanes per pixel
     Listed,               // MAD sigma / linear fit, one- or multi-lane: dominant kernel + bit-exact replay of its list
     SigmaFast,            // sigma / winsorized: dominant kernel + generic pass, replays of the pixels both hand over
+    SigmaFastMaps,        // the same kernels with the per-pixel counts, plain protocol (a fast maps pass only)
     WeightedTile,         // bit-exact replay, 64 consecutive pixels per wave with their columns in LDS
     DenseReplay,          // bit-exact wave-per-pixel replay over the whole tile (behind a decision pass where there is one)
     ExactColumns,         // bit-exact, one pixel per lane with its column in LDS: every mode, any depth
@@ -190,23 +191,28 @@ struct PassSetup {
     bool timed;               // the pass records its timing events (not with kDevUntimed)
     bool fused;               // fused protocol (fused_protocol_on; only the SigmaFast engine runs it)
     nl::StackArgs a;
-    bool maps = false;        // a maps pass (nl_stack_run_maps): a.reject_map is set
+    bool maps = false;        // a maps pass (nl_stack_run_maps, nl_stack_run_maps_fast): a.reject_map is set
 };
 
 // what kind of pass run_async_impl sets up
 enum class PassKind {
     Default,              // nl_stack_run_async
     Maps,                 // nl_stack_run_maps (include/nlstack_maps.h)
+    FastMaps,             // nl_stack_run_maps_fast (include/nlstack_fastmaps.h): a maps pass on the default pass's engines where they exist
     WeightedLinfit,       // nl_stack_run_linfit_weighted (include/nlstack_wlinfit.h): an engine of its own, run_linfit_weighted
 };
 
 // Pure: allocates nothing, enqueues nothing.  The first engine whose condition holds runs the pass.
-static Engine select_engine(const nl_stack *h, int mode, bool weighted, const nl::StackArgs &a)
+// fast_maps: a maps pass may run on the register-resident sigma kernels (PassKind::FastMaps).
+static Engine select_engine(const nl_stack *h, int mode, bool weighted, const nl::StackArgs &a, bool fast_maps)
 {
     const bool fast = !h->force_exact;
     const int n = a.n_frames;
     if (mode == NL_ST_MEAN) return Engine::Mean;
-    if (a.reject_map) return Engine::ExactColumns;      // a maps pass: the one engine that carries the per-pixel counts out
+    if (a.reject_map && fast_maps && fast && h->d_fb_list && h->d_gen_list && (mode == NL_ST_SIGMA || mode == NL_ST_WINSOR_SIGMA) &&
+        nl::fast_supported(mode, weighted, n, a.npix))
+        return Engine::SigmaFastMaps;
+    if (a.reject_map) return Engine::ExactColumns;      // a maps pass: the one engine that carries the per-pixel counts out of every mode
     if (fast && mode == NL_ST_MEDIAN && nl::fast_supported(mode, weighted, n, a.npix)) return Engine::MedianRegisters;
     if (fast && mode == NL_ST_MEDIAN && nl::fast_ml_supported(mode, weighted, n, a.npix)) return Engine::MedianMultiLane;
     if (fast && h->d_fb_list &&
@@ -244,8 +250,9 @@ static nl::FastArgs list_args(const nl_stack *h, bool exact_list, bool generic_l
     return f;
 }
 
-// the exact list (d_fb_list) replayed by the LDS-column kernel, kListLanes pixels per wave
-static int replay_list(nl_stack *h, int mode, bool weighted, const nl::StackArgs &a)
+// the exact list (d_fb_list) replayed by the LDS-column kernel, kListLanes pixels per wave; maps: by its MAPS
+// instantiation, which also stores the listed pixels' words of a.reject_map
+static int replay_list(nl_stack *h, int mode, bool weighted, const nl::StackArgs &a, bool maps = false)
 {
     int lanes = 0;
     size_t lds = 0;
@@ -256,7 +263,8 @@ static int replay_list(nl_stack *h, int mode, bool weighted, const nl::StackArgs
     e.list_count = h->d_fb_count;
     e.list_capacity = (unsigned)h->npix;
     const char *exact_name = "";
-    NL_HIP(nl::launch_stack_exact(mode, weighted, e, lanes, kListGrid, lds, h->stream, &exact_name));
+    if (maps) NL_HIP(nl::launch_stack_exact_maps(mode, weighted, e, lanes, kListGrid, lds, h->stream, &exact_name));
+    else      NL_HIP(nl::launch_stack_exact(mode, weighted, e, lanes, kListGrid, lds, h->stream, &exact_name));
     return NL_OK;
 }
 
@@ -379,8 +387,9 @@ static CascadePlan parse_cascade_plan(const char *p)
     return pl;
 }
 
-// Winsorized fast passes: how the generic pass and the winsorization loops are budgeted.  true: the winsorization cascade runs.
-static bool winsor_setup(nl_stack *h, int n_frames, nl::FastArgs &f)
+// Winsorized fast passes: how the generic pass and the winsorization loops are budgeted.  true: the winsorization cascade runs
+// (never without may_cascade: the fast maps pass, whose kernels have no continuation form).
+static bool winsor_setup(nl_stack *h, int n_frames, nl::FastArgs &f, bool may_cascade = true)
 {
     // winsorized generic passes and the stages of the cascade behind the dominant kernel: a wave runs for its slowest pixel,
     // and the few pixels whose winsorization loops take dozens of rounds are cheaper in the replay (NL_GEN_ROUND_CAP: rounds per clipping pass; 100 = the limit of every kernel)
@@ -399,7 +408,7 @@ static bool winsor_setup(nl_stack *h, int n_frames, nl::FastArgs &f)
     // stage finishes them.  Lists and states live in the buffers of the linear-fit cascade (same sizes, never in
     // use at the same time); their lengths in the scratch set.  NL_WCAS="b1,b2" sets the budgets, "0" turns it off;
     // developer switch kDevNoWinsorCascade: off (A/B inside one process)
-    if (n_frames > 128 || n_frames < 12 || (h->dev_flags & kDevNoWinsorCascade)) return false;
+    if (!may_cascade || n_frames > 128 || n_frames < 12 || (h->dev_flags & kDevNoWinsorCascade)) return false;
     static const CascadePlan env_plan = [] { const char *e = getenv("NL_WCAS"); return e ? parse_cascade_plan(e) : CascadePlan{}; }();
     static const bool env_off = [] { const char *e = getenv("NL_WCAS"); return e && e[0] == '0' && e[1] == 0; }();
     CascadePlan pl{};
@@ -512,6 +521,39 @@ static int run_sigma_fast(nl_stack *h, const PassSetup &p, PassFacts *facts)
     return NL_OK;
 }
 
+// The fast maps pass (include/nlstack_fastmaps.h) where the register-resident sigma kernels exist: unweighted sigma /
+// winsorized clipping of 2 ... 128 frames.  The kernels of run_sigma_fast in their MAPS instantiations
+// (stack_fast_maps_impl.hpp), each lane storing its pixel's two clip counts beside its result, in the PLAIN protocol on the
+// handle's one stream -- no fused protocol or tail, no side stream, no cascade, no hints read or left:
+//   1. the dominant kernel over the tile (below 16 frames: the generic kernel over the whole tile, and 2. has nothing to do),
+//   2. the generic kernel over the generic list,
+//   3. the column kernel's MAPS instantiation over the exact list, once, behind both of them,
+//   4. the reduction of the sharded clip counters.
+// Every pixel's word of the map is written by exactly one of 1 - 3: by the lane that stores its result.  The two list
+// lengths stay in the scratch set (as run_listed leaves them), where nl_stack_last_*_pixels read them: nothing sits
+// behind the totals, so nl_stack_finish takes no hints from this pass.
+static int run_sigma_fast_maps(nl_stack *h, const PassSetup &p, PassFacts *facts)
+{
+    const bool winsor = p.mode == NL_ST_WINSOR_SIGMA;
+    const nl::StackArgs &a = p.a;
+    nl::FastArgs f = list_args(h, true, true);          // (no snapshot cell, no hint: fixed grids)
+    if (winsor) (void)winsor_setup(h, a.n_frames, f, false);
+    const hipEvent_t dominant_done = p.timed ? h->ev_dom1 : nullptr;
+    if (winsor) {
+        NL_HIP(nl::launch_stack_winsor_maps_dominant(a, f, h->stream, &h->last_kernel, dominant_done));
+        NL_HIP(nl::launch_stack_winsor_maps_generic(a, f, h->stream));
+    } else {
+        NL_HIP(nl::launch_stack_sigma_maps_dominant(a, f, h->stream, &h->last_kernel, dominant_done));
+        NL_HIP(nl::launch_stack_sigma_maps_generic(a, f, h->stream));
+    }
+    const int rc = replay_list(h, p.mode, false, a, true);
+    if (rc != NL_OK) return rc;
+    NL_HIP(nl::launch_reduce_counters(h->d_partial, nl::kClipSlots, h->d_counters, h->stream));
+    facts->has_counters = true;
+    facts->used_fast = true;
+    return NL_OK;
+}
+
 // Bit-exact replay over the whole tile, 64 consecutive pixels per wave with their columns in LDS, one pixel per lane:
 // the default for weighted sigma / winsorized clipping (their result depends on the reference's permutation, so there
 // is no register-resident shortcut) up to kTileMaxFrames* frames -- the LDS column limits it to one wave per SIMD at
@@ -598,7 +640,8 @@ static int run_linfit_weighted(nl_stack *h, const PassSetup &p, PassFacts *facts
 
 static int run_async_impl(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc, PassKind kind);
 
-// what a pass that failed half-way leaves behind (nl_stack_run_async, nl::stack_run_maps_async, nl_stack_run_linfit_weighted_async)
+// what a pass that failed half-way leaves behind (nl_stack_run_async, nl::stack_run_maps_async, nl::stack_run_maps_fast_async,
+// nl_stack_run_linfit_weighted_async)
 static int settle_failed_pass(nl_stack_t *h, int rc)
 {
     if (rc != NL_OK && h && h->stream) {
@@ -628,12 +671,14 @@ int nl_stack_run_async(nl_stack_t *h, int mode, float sigma_low, float sigma_hig
 // instantiation also stores each pixel's two clip counts in h->d_reject_map.  Such a pass takes part in none of what
 // default passes remember from one another: it takes and leaves no list-length hints (it has no lists), never runs the
 // fused protocol, and leaves the scratch sets as any other plain-protocol pass does.
+// PassKind::FastMaps (nl_stack_run_maps_fast) is a maps pass that select_engine may give to run_sigma_fast_maps: it has
+// lists, but keeps all of the above (plain protocol, no hints either way).
 // The same holds for the weighted linear-fit pass (PassKind::WeightedLinfit; `mode` is NL_ST_LINEAR_FIT), which keeps the
 // weights the default linear fit drops and runs on run_linfit_weighted.
 static int run_async_impl(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc, PassKind kind)
 {
     NL_CHECK_HANDLE(h);
-    const bool maps = kind == PassKind::Maps, wlinfit = kind == PassKind::WeightedLinfit;
+    const bool maps = kind == PassKind::Maps || kind == PassKind::FastMaps, wlinfit = kind == PassKind::WeightedLinfit;
     if (wlinfit && !h->has_weights)
         return fail(NL_ERR_INVALID_ARG, "run_linfit_weighted: the handle has no weights (nl_stack_set_weights); "
                                         "the unweighted fit is nl_stack_run with NL_ST_LINEAR_FIT");
@@ -685,7 +730,7 @@ static int run_async_impl(nl_stack_t *h, int mode, float sigma_low, float sigma_
     h->ring_timed[h->pass_seq % kTimingRing] = timed;
     if (timed) NL_HIP(hipEventRecord(h->ev_start, h->stream));
     const bool fused_on = fused_protocol_on();
-    const Engine engine = select_engine(h, mode, weighted, a);
+    const Engine engine = select_engine(h, mode, weighted, a, kind == PassKind::FastMaps);
     const bool sigma_fast = engine == Engine::SigmaFast;
     // (only while the exact list is short -- the length the last finished pass reported: its replays add their
     // counts to ONE word, and thousands of workgroups doing that take longer than a reduction kernel)
@@ -728,6 +773,7 @@ static int run_async_impl(nl_stack_t *h, int mode, float sigma_low, float sigma_
     case Engine::MedianMultiLane: rc = run_median(h, p, true); break;
     case Engine::Listed:          rc = run_listed(h, p, &facts); break;
     case Engine::SigmaFast:       rc = run_sigma_fast(h, p, &facts); break;
+    case Engine::SigmaFastMaps:   rc = run_sigma_fast_maps(h, p, &facts); break;
     case Engine::WeightedTile:    rc = run_weighted_tile(h, p, &facts); break;
     case Engine::DenseReplay:     rc = run_dense_replay(h, p, &facts); break;
     case Engine::ExactColumns:    rc = run_exact_columns(h, p, &facts); break;
@@ -782,7 +828,13 @@ int nl::stack_run_maps_async(nl_stack_t *h, int mode, float sigma_low, float sig
     return settle_failed_pass(h, run_async_impl(h, mode, sigma_low, sigma_high, ref_loc, PassKind::Maps));
 }
 
-// nl_stack_finish, and the two planes of the map.  The packed words come down in ONE copy and are split here: the same
+// the fast maps pass (include/nlstack_fastmaps.h)
+int nl::stack_run_maps_fast_async(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc)
+{
+    return settle_failed_pass(h, run_async_impl(h, mode, sigma_low, sigma_high, ref_loc, PassKind::FastMaps));
+}
+
+// nl_stack_finish, and the two planes of the map (of either kind of maps pass).  The packed words come down in ONE copy and are split here: the same
 // bytes cross the link as two uint16 planes would, and no second device buffer or kernel exists for what is a 16-bit
 // shuffle beside a PCIe transfer.
 int nl::stack_finish_maps(nl_stack_t *h, float *out_host, int64_t *clip_low, int64_t *clip_high, uint16_t *reject_low_host,
@@ -830,6 +882,15 @@ int nl_stack_run_maps(nl_stack_t *h, int mode, float sigma_low, float sigma_high
                       uint16_t *reject_low_host, uint16_t *reject_high_host)
 {
     const int rc = nl::stack_run_maps_async(h, mode, sigma_low, sigma_high, ref_loc);
+    if (rc != NL_OK) return rc;
+    return nl::stack_finish_maps(h, out_host, clip_low, clip_high, reject_low_host, reject_high_host);
+}
+
+int nl_stack_run_maps_fast(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc,
+                           float *out_host, int64_t *clip_low, int64_t *clip_high,
+                           uint16_t *reject_low_host, uint16_t *reject_high_host)
+{
+    const int rc = nl::stack_run_maps_fast_async(h, mode, sigma_low, sigma_high, ref_loc);
     if (rc != NL_OK) return rc;
     return nl::stack_finish_maps(h, out_host, clip_low, clip_high, reject_low_host, reject_high_host);
 }

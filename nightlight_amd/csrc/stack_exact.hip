@@ -247,7 +247,8 @@ __device__ __forceinline__ int wave_sum(int v)
 // pass of include/nlstack_wlinfit.h, an extension); LANES: pixels per wavefront (64/32/16,
 // smaller when a 64-wide tile would not fit the 160 KiB LDS); MAPS: the maps
 // pass (nl_stack_run_maps) -- the lane also stores its pixel's own two clip
-// counts, p.reject_map (whole tile only; no other instantiation reads it).
+// counts, p.reject_map[pix] (whole tile, or the listed pixels: the replay of
+// the fast maps pass; no other instantiation reads it).
 template <int MODE, bool W, int LANES, bool MAPS = false>
 __global__ __launch_bounds__(64) void stack_exact_kernel(StackArgs p)
 {
@@ -593,7 +594,7 @@ hipError_t launch_stack_exact(int mode, bool weighted, const StackArgs &args, in
 hipError_t launch_stack_exact_maps(int mode, bool weighted, const StackArgs &args, int lanes, int grid,
                                    size_t lds_bytes, hipStream_t stream, const char **name)
 {
-    if (!args.reject_map || args.list) return hipErrorInvalidValue;
+    if (!args.reject_map) return hipErrorInvalidValue;
     switch (mode) {
     case NL_ST_MEDIAN:
         *name = "stack_exact_kernel<median,maps>";

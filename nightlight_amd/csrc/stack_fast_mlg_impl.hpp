@@ -111,7 +111,9 @@ __device__ __forceinline__ void range_moments(const float *col, float c, int i, 
 
 // The kernel's body, workgroup `block` of `nblocks` (stack_sigma_mlg_kernel, stack_fast_mlg.hip: the whole grid; stack_tail_fused.hip: the
 // upper workgroups of a grid whose lower part replays the dominant kernel's exact list).
-template <int LPP, bool WINSOR>
+// MAPS: the fast maps pass (include/nlstack_fastmaps.h) -- the lane that stores a pixel's result also stores its two clip
+// counts, low | high << 16, in p.reject_map[pix]; no other instantiation reads p.reject_map.
+template <int LPP, bool WINSOR, bool MAPS = false>
 __device__ __forceinline__ void mlg_body(const StackArgs &p, const FastArgs &q, const unsigned block, const unsigned nblocks)
 {
     using LY = MlgLayout<LPP>;
@@ -339,6 +341,7 @@ __device__ __forceinline__ void mlg_body(const StackArgs &p, const FastArgs &q, 
         const bool rep = on && role == 0;
         if (rep && !to_exact) {
             p.out[pix] = res;
+            if constexpr (MAPS) p.reject_map[pix] = (unsigned)c_lo | ((unsigned)c_hi << 16);
             c_lo_total += c_lo;
             c_hi_total += c_hi;
         }

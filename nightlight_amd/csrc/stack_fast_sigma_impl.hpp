@@ -34,6 +34,12 @@ namespace nl {
 // Only the stage that finishes a pixel books its counters, so a pixel that turns undecidable in a later stage is
 // replayed from scratch as before.
 // CONT (zonal only): the kernel runs over q.in_list / q.in_state instead of the tile.
+// MAPS: the fast maps pass (include/nlstack_fastmaps.h).  Where a lane stores its pixel's result it also stores the
+//                pixel's own two clip counts, low | high << 16, in p.reject_map[pix] -- the counts it adds to the wave
+//                totals, which are the reference's for that pixel (a pixel it cannot decide is handed over before it
+//                counts anything).  A pixel that goes to a hand-over list gets its word from whoever finishes it.  No
+//                other instantiation reads p.reject_map: the store is not in their code.  No RECORD or CONT form (the
+//                maps pass runs no decision pass and no cascade).
 
 #ifndef NL_CERT_ON
 #define NL_CERT_ON(ns) true
@@ -59,7 +65,7 @@ namespace nl {
 // The same one step down: 48 ... 96 positions take 118 ... 134 registers for exactly NS frames (133 with padding at 48) -- a
 // fourth wave costs a handful of spills: 64 / 80 / 96 frames dominant kernel -11 / -8 / -6 %, 44 frames -15 %; the padded
 // instantiations of 64 ... 96 positions (155 registers) lose 5 % when forced and stay.
-template <int NS, bool ZONAL, bool WINSOR, bool TIGHT, bool RECORD = false, bool CONT = false>
+template <int NS, bool ZONAL, bool WINSOR, bool TIGHT, bool RECORD = false, bool CONT = false, bool MAPS = false>
 __global__ __launch_bounds__(256)
 __attribute__((amdgpu_waves_per_eu((ZONAL && WINSOR && !CONT) ? (NS >= 112 ? (TIGHT ? 1 : 3) : (RECORD ? 1 : (NS >= 64 ? (TIGHT ? 4 : 1) : (NS >= 48 ? 4 : 1)))) : 1, 8)))
 void stack_sigma_fast_kernel(StackArgs p, FastArgs q)
@@ -67,6 +73,7 @@ void stack_sigma_fast_kernel(StackArgs p, FastArgs q)
     static_assert(!TIGHT || ZONAL, "TIGHT is a variant of the zonal kernels");
     static_assert(!RECORD || ZONAL, "RECORD is a variant of the zonal kernels");
     static_assert(!CONT || (ZONAL && WINSOR && !RECORD), "CONT continues a winsorized zonal pass");
+    static_assert(!MAPS || (!RECORD && !CONT), "the maps pass has no decision pass and no cascade");
     constexpr bool CASCADE = ZONAL && WINSOR && !RECORD;      // this instantiation knows about budgets and continuation lists
     if constexpr (ZONAL && !RECORD && !CONT) fused_prologue_dominant(p);
     if constexpr (!ZONAL) { if (q.in_list) { fused_collect_slots(p, blockIdx.x); snapshot_fb_list(q); } }
@@ -757,6 +764,7 @@ void stack_sigma_fast_kernel(StackArgs p, FastArgs q)
         auto flush = [&]() NL_INL {
         if (on && !active && !to_generic && !to_exact && !defer) {
             NL_STORE_RESULT(&p.out[pix], res);
+            if constexpr (MAPS) p.reject_map[pix] = (unsigned)c_lo | ((unsigned)c_hi << 16);
             c_lo_total += c_lo;
             c_hi_total += c_hi;
         }

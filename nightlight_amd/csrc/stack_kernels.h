@@ -62,8 +62,8 @@ struct StackArgs {
     // decided: the replay computes its own bounds, as without these).  nullptr: off.
     float2 *bounds;
     unsigned char *nrounds;
-    // Maps pass (nl_stack_run_maps): [npix] words, the pixel's clipLow count | clipHigh count << 16.  Read by the MAPS
-    // instantiations of stack_exact_kernel only; nullptr everywhere else.
+    // Maps pass (nl_stack_run_maps, nl_stack_run_maps_fast): [npix] words, the pixel's clipLow count | clipHigh count << 16.
+    // Read by the MAPS instantiations only (stack_exact_kernel; stack_fast_maps_impl.hpp); nullptr everywhere else.
     unsigned *reject_map;
 };
 
@@ -128,6 +128,8 @@ int stack_settle(nl_stack_t *h);
 int stack_run_maps_async(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc);
 int stack_finish_maps(nl_stack_t *h, float *out_host, int64_t *clip_low, int64_t *clip_high, uint16_t *reject_low_host,
                       uint16_t *reject_high_host);
+// the first half of nl_stack_run_maps_fast (include/nlstack_fastmaps.h); stack_finish_maps finishes either kind
+int stack_run_maps_fast_async(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc);
 
 // Bisection of the goal-seek (spec: internal/ops/stack/stackfindsigma.go:48-98): sigma_low and
 // sigma_high in [1,11], percentages in the reference's fp32 arithmetic, 21 passes at most.
@@ -216,7 +218,8 @@ int exact_plan(int mode, bool weighted, int n_frames, int n_pad, int max_lanes, 
                size_t *lds_bytes);
 hipError_t launch_stack_exact(int mode, bool weighted, const StackArgs &args, int lanes, int grid,
                               size_t lds_bytes, hipStream_t stream, const char **name);
-// the MAPS instantiations: as above, and every pixel's two clip counts go to args.reject_map (whole tile, no list)
+// the MAPS instantiations: as above, and every pixel's two clip counts go to args.reject_map (the whole tile, or -- the
+// replay of the fast maps pass -- the pixels of args.list)
 hipError_t launch_stack_exact_maps(int mode, bool weighted, const StackArgs &args, int lanes, int grid,
                                    size_t lds_bytes, hipStream_t stream, const char **name);
 // list_counts (optional): {exact-list length, generic-list length} of the pass, left in counters[2] (low | high << 32)
@@ -252,6 +255,15 @@ hipError_t launch_stack_sigma_fast_dominant(const StackArgs &args, const FastArg
                                             const char **name, hipEvent_t dominant_done, bool winsor);
 hipError_t launch_stack_sigma_fast_generic(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, bool winsor,
                                            const StackArgs *first_replay = nullptr, unsigned replay_blocks = 0);
+// ---- stack_fast_maps_sigma.hip / stack_fast_maps_winsor.hip: the two parts of the fast maps pass (include/nlstack_fastmaps.h),
+// 2 ... 128 frames, args.reject_map set.  As the parts above with one more store per pixel, its two clip counts; no
+// cascade, no fused tail, no hints: the generic part runs a fixed grid ----
+hipError_t launch_stack_sigma_maps_dominant(const StackArgs &args, const FastArgs &fargs, hipStream_t stream,
+                                            const char **name, hipEvent_t dominant_done);
+hipError_t launch_stack_sigma_maps_generic(const StackArgs &args, const FastArgs &fargs, hipStream_t stream);
+hipError_t launch_stack_winsor_maps_dominant(const StackArgs &args, const FastArgs &fargs, hipStream_t stream,
+                                             const char **name, hipEvent_t dominant_done);
+hipError_t launch_stack_winsor_maps_generic(const StackArgs &args, const FastArgs &fargs, hipStream_t stream);
 // ---- stack_tail_fused.hip: generic pass (one lane per pixel, LDS columns) + first replay in one grid; plain sigma, 65 ... 128 frames
 int tail_fused_supported(int mode, bool weighted, int n_frames);
 hipError_t launch_stack_sigma_tail(const StackArgs &generic, const FastArgs &fargs, unsigned gen_blocks,

@@ -149,8 +149,11 @@ class StackHandle:
         return (out if fetch else None), cl.value, ch.value
 
     def run_maps(self, mode, sigma_low=2.75, sigma_high=2.75, ref_loc=0.0, out=None, reject_low=None,
-                 reject_high=None):
+                 reject_high=None, fast=False):
         """One pass on the bit-exact column kernel that also says WHERE it clipped (include/nlstack_maps.h).
+        fast=True: nl_stack_run_maps_fast (include/nlstack_fastmaps.h) -- the same maps from the default pass's
+        engines where they exist (unweighted sigma / winsorized clipping up to 128 frames; the result is then the
+        default pass's, not the bit-exact one), the column kernel everywhere else.
         Returns (result, clip_low, clip_high, reject_low, reject_high): the maps are whole-image uint16 arrays,
         reject_low[p] / reject_high[p] = how often the reference increments clipLow / clipHigh at pixel p; their
         sums are the two totals.  `out`, `reject_low`, `reject_high`: whole-image arrays (float32, uint16, uint16)
@@ -162,9 +165,9 @@ class StackHandle:
         for a, t in ((out, np.float32), (reject_low, np.uint16), (reject_high, np.uint16)):
             assert a.dtype == t and a.size == n and a.flags.c_contiguous
         cl, ch = C.c_int64(0), C.c_int64(0)
-        capi.check(self._lib.nl_stack_run_maps(self._h, int(mode), C.c_float(sigma_low), C.c_float(sigma_high),
-                                               C.c_float(ref_loc), capi.fptr(out), C.byref(cl), C.byref(ch),
-                                               _u16ptr(reject_low), _u16ptr(reject_high)))
+        entry = self._lib.nl_stack_run_maps_fast if fast else self._lib.nl_stack_run_maps
+        capi.check(entry(self._h, int(mode), C.c_float(sigma_low), C.c_float(sigma_high), C.c_float(ref_loc),
+                         capi.fptr(out), C.byref(cl), C.byref(ch), _u16ptr(reject_low), _u16ptr(reject_high)))
         return out, cl.value, ch.value, reject_low, reject_high
 
     def run_linfit_weighted(self, sigma_low=2.75, sigma_high=2.75, ref_loc=0.0, out=None, fetch=True):
@@ -672,15 +675,15 @@ class StackGroup:
                                           C.byref(cl), C.byref(ch)))
         return out, cl.value, ch.value
 
-    def run_maps(self, mode, sigma_low=2.75, sigma_high=2.75, ref_loc=0.0):
+    def run_maps(self, mode, sigma_low=2.75, sigma_high=2.75, ref_loc=0.0, fast=False):
         """StackHandle.run_maps over the tiles: (result, clip_low, clip_high, reject_low, reject_high), every tile
-        writing its own rows."""
+        writing its own rows.  fast=True: nl_group_run_maps_fast."""
         n = self.width * self.height
         out, lo, hi = np.zeros(n, np.float32), np.zeros(n, np.uint16), np.zeros(n, np.uint16)
         cl, ch = C.c_int64(0), C.c_int64(0)
-        capi.check(self._lib.nl_group_run_maps(self._g, int(mode), C.c_float(sigma_low), C.c_float(sigma_high),
-                                               C.c_float(ref_loc), capi.fptr(out), C.byref(cl), C.byref(ch),
-                                               _u16ptr(lo), _u16ptr(hi)))
+        entry = self._lib.nl_group_run_maps_fast if fast else self._lib.nl_group_run_maps
+        capi.check(entry(self._g, int(mode), C.c_float(sigma_low), C.c_float(sigma_high), C.c_float(ref_loc),
+                         capi.fptr(out), C.byref(cl), C.byref(ch), _u16ptr(lo), _u16ptr(hi)))
         return out, cl.value, ch.value, lo, hi
 
     def run_linfit_weighted(self, sigma_low=2.75, sigma_high=2.75, ref_loc=0.0, download=True):

@@ -10,6 +10,16 @@
         the mean pass             nl_stack_run(NL_ST_MEAN): reads the same bytes as the coverage kernel
         nl_stack_coverage         its kernels only (the call also downloads the map)
       DIR receives the lines as maps_probe.txt.
+
+  python tools/maps_probe.py --fastmaps [--width 4096 --height 4096 --sigma 3 --reps 20 --out DIR]
+      The fast maps pass (include/nlstack_fastmaps.h) beside the passes it sits next to.  On ONE handle of 128 frames,
+      with 128 and then 24 of them active, sigma and winsorized clipping, the same statistics of:
+        the default pass          nl_stack_run
+        the plain default pass    nl_stack_run under developer switch 1 (memset before, reduction kernel after: the
+                                  protocol class of the fast maps pass, and its yardstick)
+        the fast maps pass        nl_stack_run_maps_fast, every host pointer NULL
+        the column maps pass      nl_stack_run_maps, every host pointer NULL
+      and the two hand-over list lengths of the fast maps pass.  DIR receives the lines as fastmaps_probe.txt.
 """
 import argparse
 import os
@@ -25,8 +35,68 @@ def stats(ms):
     return "median %.3f ms, min %.3f ms" % (float(np.median(ms)), float(np.min(ms)))
 
 
+def fastmaps(a):
+    import nightlight_amd as nl
+    from nightlight_amd import capi
+    L = capi.load()
+    warm, n = 3, 128
+    lines = []
+    try:
+        import torch
+        lines.append("device: %s" % torch.cuda.get_device_name(0))
+    except Exception:
+        pass
+    lines.append("%d frames of %d x %d resident, sigma %.2f / %.2f; %d runs after %d warm-up runs; GPU time of the whole pass"
+                 % (n, a.width, a.height, a.sigma, a.sigma, a.reps, warm))
+    with nl.StackHandle(n, a.width, a.height) as st:
+        st.fill_synthetic(seed=7)
+        for active in (128, 24):
+            st.set_active_frames(active)
+            for mode in (capi.ST_SIGMA, capi.ST_WINSOR_SIGMA):
+                def default_pass():
+                    st.run(mode, a.sigma, a.sigma, 0.0, fetch=False)
+                    return st.pass_times(0)
+
+                def fast_maps_pass():
+                    capi.check(L.nl_stack_run_maps_fast(st._h, mode, a.sigma, a.sigma, 0.0, None, None, None, None, None))
+                    return st.pass_times(0)
+
+                def column_maps_pass():
+                    capi.check(L.nl_stack_run_maps(st._h, mode, a.sigma, a.sigma, 0.0, None, None, None, None, None))
+                    return st.pass_times(0)
+
+                lines.append("-- %d active frames, mode %d" % (active, mode))
+                med, med_dom = {}, {}
+                for label, fn, flags in (("default pass", default_pass, 0), ("plain default pass", default_pass, 1),
+                                         ("fast maps pass", fast_maps_pass, 0), ("column maps pass", column_maps_pass, 0)):
+                    st.set_dev_flags(flags)
+                    both = [fn() for _ in range(warm + a.reps)][warm:]
+                    st.set_dev_flags(0)
+                    ms, dom = [t[0] for t in both], [t[1] for t in both]
+                    med[label], med_dom[label] = float(np.median(ms)), float(np.median(dom))
+                    tail = "; dominant kernel median %.3f ms" % med_dom[label]
+                    if label == "fast maps pass":
+                        tail += "; exact list %d, generic list %d" % (st.last_fallback_pixels, st.last_generic_pixels)
+                    lines.append("%-19s %-68s %s; protocol %d%s" % (label, st.last_kernel_name, stats(ms), st.last_pass_protocol, tail))
+                lines.append("fast maps / plain default = %.3f (one more 4-byte store per %d bytes read: %.4f); "
+                             "fast maps / default = %.3f; column maps / fast maps = %.1f"
+                             % (med["fast maps pass"] / med["plain default pass"], 4 * active, 1.0 + 1.0 / active,
+                                med["fast maps pass"] / med["default pass"], med["column maps pass"] / med["fast maps pass"]))
+                lines.append("dominant kernels, fast maps / plain default = %.3f; behind the dominant kernel: %.3f ms against %.3f ms"
+                             % (med_dom["fast maps pass"] / med_dom["plain default pass"],
+                                med["fast maps pass"] - med_dom["fast maps pass"],
+                                med["plain default pass"] - med_dom["plain default pass"]))
+    text = "\n".join(lines)
+    print(text)
+    if a.out:
+        os.makedirs(a.out, exist_ok=True)
+        with open(os.path.join(a.out, "fastmaps_probe.txt"), "w") as f:
+            f.write(text + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--fastmaps", action="store_true")
     ap.add_argument("--frames", type=int, default=128)
     ap.add_argument("--width", type=int, default=4096)
     ap.add_argument("--height", type=int, default=4096)
@@ -35,6 +105,8 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.fastmaps:
+        return fastmaps(a)
     import nightlight_amd as nl
     from nightlight_amd import capi
     L = capi.load()
