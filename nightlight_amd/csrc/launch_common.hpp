@@ -39,10 +39,10 @@ decltype(auto) with_ml_lanes(int n_frames, F &&f)
     return f(std::integral_constant<int, 4>{});
 }
 
-// workgroups of 256 threads over npix pixels at lpp lanes per pixel
-inline unsigned pixel_grid(int64_t npix, int lpp = 1)
+// workgroups of `block` threads over npix pixels at lpp lanes per pixel
+inline unsigned pixel_grid(int64_t npix, int lpp = 1, int block = 256)
 {
-    const int64_t per_wg = 256 / lpp;
+    const int64_t per_wg = block / lpp;
     return (unsigned)((npix + per_wg - 1) / per_wg);
 }
 

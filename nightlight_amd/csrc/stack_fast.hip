@@ -500,6 +500,11 @@ static void launch_cascade_stages(Launcher &L, const StackArgs &args, const Fast
     }
 }
 
+// threads per workgroup of the wave-owned dominant kernels (a build-time switch for A/B libraries: 64, 128, 256)
+#ifndef NL_WAVE_OWNED_BLOCK
+#define NL_WAVE_OWNED_BLOCK 256
+#endif
+
 template <int NS, bool WINSOR>
 static hipError_t launch_dominant(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name, hipEvent_t dominant_done)
 {
@@ -507,12 +512,19 @@ static hipError_t launch_dominant(const StackArgs &args, const FastArgs &fargs, 
     const unsigned tile_blocks = pixel_grid(args.npix);
     if constexpr (NS >= kZonalMinSize) {
         const FastArgs f = zonal_args(fargs, WINSOR);
-        // (workgroups of 64 or 128 threads instead of 256 -- no wave waits for its workgroup's slowest at the barriers of the
-        // hand-over lists -- measured the same within the noise at 32 and 128 frames, round 4)
+        // The wave-owned instantiations (stack_fast_sigma_impl.hpp: no barrier, no LDS) are correct at any whole number of
+        // waves per workgroup and were measured at one, two and four (same box, headline step,
+        // parent 1.523 - 1.547 ms): four waves 1.500 - 1.508 ms, one wave 1.536 - 1.547 ms -- what the barriers cost comes
+        // back with 256 threads, and one wave per workgroup gives it away again (262 144 workgroups to dispatch, and
+        // the four waves over a row of 256 pixels no longer share a compute unit).  Hence 256.
+        // Every other instantiation keeps its barriers and its 256 threads: round 4 launched them as they were, barriers
+        // included, with 64 and 128 threads and measured no difference at 32 and 128 frames.
         with_bool(args.n_frames == NS, [&](auto T) {
             constexpr bool TIGHT = decltype(T)::value;
+            constexpr unsigned block = sigma_wave_owned(NS, true, WINSOR, TIGHT, false, false) ? NL_WAVE_OWNED_BLOCK : 256;
+            static_assert(block % 64 == 0 && block <= 256, "whole waves, within the kernel's launch bounds");
             *name = kernel_name<kSigmaFastName, NS, true, WINSOR, TIGHT, false, false>();
-            L(stack_sigma_fast_kernel<NS, true, WINSOR, TIGHT>, tile_blocks, 256, 0, args, f);
+            L(stack_sigma_fast_kernel<NS, true, WINSOR, TIGHT>, pixel_grid(args.npix, 1, block), block, 0, args, f);
         });
         L.record(dominant_done);
         if constexpr (WINSOR) {

@@ -54,6 +54,33 @@ namespace nl {
 #ifndef NL_PEEL_FIRST
 #define NL_PEEL_FIRST(ns) ((ns) >= 128)
 #endif
+// WAVE-OWNED kernels: the zonal plain-sigma kernel of a stack of exactly NS frames, where a wave
+// shares nothing with the other waves of its workgroup -- no LDS, no barrier.  It reserves its own run of the generic
+// hand-over list (one device atomic per wave that hands anything over: affordable only because a TIGHT stack hands over
+// few pixels -- about 4 k of 262 144 waves at 128 frames; the padded and the small-zone instantiations send pixels from
+// half of their waves and keep the per-workgroup reservation, see flush()) and adds its own clip totals to a slot.  The
+// body is correct for any block size that is a multiple of 64 (stack_fast.hip:launch_dominant has the measured choice).
+// Measured at 128 frames only.
+#ifndef NL_WAVE_OWNED
+#define NL_WAVE_OWNED(ns) ((ns) >= 128)
+#endif
+constexpr bool sigma_wave_owned(int ns, bool zonal, bool winsor, bool tight, bool record, bool cont)
+{
+    return zonal && !winsor && tight && !record && !cont && NL_WAVE_OWNED(ns);
+}
+
+// sum over the wave of an int every lane holds (all 64 lanes active): four DPP steps inside each row of 16 lanes, then
+// the four rows through scalar registers -- no LDS crossbar (the __shfl_xor form is 6 ds_bpermute_b32 per value)
+__device__ __forceinline__ int wave_sum_dpp(int x)
+{
+    x += __builtin_amdgcn_update_dpp(0, x, 0xb1, 0xf, 0xf, true);       // quad_perm [1, 0, 3, 2]
+    x += __builtin_amdgcn_update_dpp(0, x, 0x4e, 0xf, 0xf, true);       // quad_perm [2, 3, 0, 1]
+    x += __builtin_amdgcn_update_dpp(0, x, 0x141, 0xf, 0xf, true);      // row_half_mirror
+    x += __builtin_amdgcn_update_dpp(0, x, 0x140, 0xf, 0xf, true);      // row_mirror
+    return (__builtin_amdgcn_readlane(x, 0) + __builtin_amdgcn_readlane(x, 16)) +
+           (__builtin_amdgcn_readlane(x, 32) + __builtin_amdgcn_readlane(x, 48));
+}
+
 #ifndef NL_WINSOR_WL
 #define NL_WINSOR_WL(ns) ((ns) >= 112 ? 20 : ((ns) >= 80 ? 16 : ((ns) / 4 + 3) / 4 * 4))
 #endif
@@ -75,6 +102,7 @@ void stack_sigma_fast_kernel(StackArgs p, FastArgs q)
     static_assert(!CONT || (ZONAL && WINSOR && !RECORD), "CONT continues a winsorized zonal pass");
     static_assert(!MAPS || (!RECORD && !CONT), "the maps pass has no decision pass and no cascade");
     constexpr bool CASCADE = ZONAL && WINSOR && !RECORD;      // this instantiation knows about budgets and continuation lists
+    constexpr bool WAVE_OWNED = sigma_wave_owned(NS, ZONAL, WINSOR, TIGHT, RECORD, CONT);     // no LDS, no barrier (MAPS follows its twin)
     if constexpr (ZONAL && !RECORD && !CONT) fused_prologue_dominant(p);
     if constexpr (!ZONAL) { if (q.in_list) { fused_collect_slots(p, blockIdx.x); snapshot_fb_list(q); } }
     // zone widths: 8 clipped + 8 missing samples per lane for the larger
@@ -99,7 +127,7 @@ void stack_sigma_fast_kernel(StackArgs p, FastArgs q)
     if constexpr (CASCADE) {
         if (threadIdx.x == 0) s_cont = 0u;
     }
-    if constexpr (ZONAL && !RECORD) {
+    if constexpr (ZONAL && !RECORD && !WAVE_OWNED) {
         if (threadIdx.x == 0) s_gen = 0u;
         __syncthreads();
     }
@@ -787,7 +815,17 @@ void stack_sigma_fast_kernel(StackArgs p, FastArgs q)
         // frame count just above a network size sends 1 - 3 % of the pixels here from half of the 262 144 waves: 1.4 ms
         // of serialised atomics inside a 0.4 ms kernel at 25 frames), lanes fill it in order, so the consumer's loads
         // stay coalesced
-        if constexpr (ZONAL && !RECORD) {
+        // (WAVE_OWNED: a run per wave, reserved by the wave itself like the exact list's below -- few waves have one)
+        if constexpr (WAVE_OWNED) {
+            const unsigned long long gm = __ballot(on && to_generic);
+            if (gm) {
+                unsigned base = 0;
+                if (lane == 0) base = atomicAdd(q.gen_count, (unsigned)__popcll(gm));
+                base = (unsigned)__builtin_amdgcn_readfirstlane((int)base);
+                const unsigned slot = base + (unsigned)__popcll(gm & ((1ull << lane) - 1ull));
+                if (on && to_generic && slot < q.gen_capacity) q.gen_list[slot] = (unsigned)pix;
+            }
+        } else if constexpr (ZONAL && !RECORD) {
             const unsigned long long gm = __ballot(on && to_generic);
             unsigned woff = 0;
             if (lane == 0 && gm) woff = atomicAdd(&s_gen, (unsigned)__popcll(gm));          // LDS
@@ -806,7 +844,8 @@ void stack_sigma_fast_kernel(StackArgs p, FastArgs q)
         if (em) {
             unsigned base = 0;
             if (lane == 0) base = atomicAdd(q.fb_count, (unsigned)__popcll(em));
-            base = __shfl(base, 0, 64);
+            if constexpr (WAVE_OWNED) base = (unsigned)__builtin_amdgcn_readfirstlane((int)base);
+            else base = __shfl(base, 0, 64);
             const unsigned slot = base + (unsigned)__popcll(em & ((1ull << lane) - 1ull));
             if (on && to_exact && slot < q.fb_capacity) q.fb_list[slot] = (unsigned)pix;
         }
@@ -847,6 +886,17 @@ void stack_sigma_fast_kernel(StackArgs p, FastArgs q)
         }
     }
 
+    if constexpr (WAVE_OWNED) {
+        // clip totals: wave sum -> one slot per wave (non-returning atomics; most waves of a clean stack add nothing)
+        const int t_lo = wave_sum_dpp(c_lo_total), t_hi = wave_sum_dpp(c_hi_total);
+        if (lane == 0) {
+            const unsigned wave_index = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+            unsigned long long *slot = p.partial + 2 * (size_t)(wave_index % kClipSlots);
+            if (t_lo) atomicAdd(slot + 0, (unsigned long long)t_lo);
+            if (t_hi) atomicAdd(slot + 1, (unsigned long long)t_hi);
+        }
+        return;
+    }
     // clip totals: wave sum -> block sum -> one slot per workgroup
     __shared__ int s_lo[4], s_hi[4];
 #pragma unroll
