@@ -240,9 +240,17 @@ func (op *OpStack) Apply(f []*fits.Image, c *ops.Context) (result *fits.Image, e
 	// in stack.go's struct (default false, so existing JSON round-trips unchanged).  When it is set, the mode
 	// resolves to the linear fit and there are weights, the fit rejects as always and the survivors are averaged
 	// with the weights; otherwise the linear fit drops the weights as the reference does (stack.go:188-189).
+	// Another EXTENSION (include/nlstack_wclip.h): the field
+	//	WeightsFollowFrames bool `json:"weightsFollowFrames,omitempty"`
+	// When it is set, the mode resolves to sigma or winsorized sigma clipping and there are weights, the rejection runs
+	// as always and each survivor is averaged with ITS frame's weight; otherwise a survivor takes the weight that
+	// QSelectMedianFloat32 left in its slot, as in the reference (stack.go:487).
 	var rc C.int
 	if op.WeightedLinearFit && mode == StLinearFit && weights != nil {
 		rc = C.nl_group_run_linfit_weighted(g, C.float(op.SigmaLow), C.float(op.SigmaHigh), C.float(op.RefFrameLoc),
+			(*C.float)(unsafe.Pointer(&data[0])), &clipLow, &clipHigh)
+	} else if op.WeightsFollowFrames && (mode == StSigma || mode == StWinsorSigma) && weights != nil {
+		rc = C.nl_group_run_clip_weighted(g, C.int(mode), C.float(op.SigmaLow), C.float(op.SigmaHigh), C.float(op.RefFrameLoc),
 			(*C.float)(unsafe.Pointer(&data[0])), &clipLow, &clipHigh)
 	} else {
 		rc = C.nl_group_run(g, C.int(mode), C.float(op.SigmaLow), C.float(op.SigmaHigh), C.float(op.RefFrameLoc),

@@ -350,6 +350,12 @@ int nl_group_accumulate_finalize(nl_group_t *g, float weight_sum, float *out_hos
  * nlstack_wlinfit.h, which is part of this interface. */
 #include "nlstack_wlinfit.h"
 
+/* ---- sigma / winsorized rejection with a weighted mean whose weights follow their frames (an extension: the reference's
+ * weights follow Hoare's permutation) ----
+ * nl_stack_run_clip_weighted, nl_stack_run_clip_weighted_async, nl_group_run_clip_weighted: declared in
+ * nlstack_wclip.h, which is part of this interface. */
+#include "nlstack_wclip.h"
+
 /* ---- stack of stacks (StackIncremental / Finalize, stack.go:924-944) ----
  * acc += result_of_last_pass * weight (first != 0: acc = result*weight),
  * on the device; finalize multiplies by 1/weight_sum and downloads. */

@@ -89,6 +89,10 @@ FASTMAPS_EXPORTS = ["nl_stack_run_maps_fast", "nl_group_run_maps_fast"]
 # every symbol include/nlstack_wlinfit.h declares (likewise): the weighted linear-fit pass, an extension
 WLINFIT_EXPORTS = ["nl_stack_run_linfit_weighted", "nl_stack_run_linfit_weighted_async", "nl_group_run_linfit_weighted"]
 
+# every symbol include/nlstack_wclip.h declares (likewise): weighted sigma / winsorized clipping whose weights follow
+# their frames, an extension
+WCLIP_EXPORTS = ["nl_stack_run_clip_weighted", "nl_stack_run_clip_weighted_async", "nl_group_run_clip_weighted"]
+
 # every symbol include/nlstack_align.h declares (likewise)
 ALIGN_EXPORTS = ["nl_aligner_create", "nl_aligner_destroy", "nl_aligner_info", "nl_aligner_match",
                  "nl_aligner_match_stars"]
@@ -281,6 +285,10 @@ def open_library(path):
     L.nl_stack_run_linfit_weighted.argtypes = _wlinfit_args
     L.nl_group_run_linfit_weighted.argtypes = _wlinfit_args
     L.nl_stack_run_linfit_weighted_async.argtypes = [vp, C.c_float, C.c_float, C.c_float]
+    _wclip_args = [vp, C.c_int, C.c_float, C.c_float, C.c_float, _f32p, _i64p, _i64p]
+    L.nl_stack_run_clip_weighted.argtypes = _wclip_args
+    L.nl_group_run_clip_weighted.argtypes = _wclip_args
+    L.nl_stack_run_clip_weighted_async.argtypes = [vp, C.c_int, C.c_float, C.c_float, C.c_float]
     L.nl_stack_coverage.argtypes = [vp, _u16p]
     L.nl_group_coverage.argtypes = [vp, _u16p]
     L.nl_stack_last_coverage_ms.argtypes = [vp]

@@ -286,6 +286,21 @@ int nl_group_run_linfit_weighted(nl_group_t *g, float sigma_low, float sigma_hig
                      out_host, clip_low, clip_high);
 }
 
+// the weighted clip pass whose weights follow their frames (include/nlstack_wclip.h) over the tiles: nl_group_run's protocol
+// (what can be told from the mode alone is told first, as nl_stack_run_clip_weighted_async does)
+int nl_group_run_clip_weighted(nl_group_t *g, int mode, float sigma_low, float sigma_high, float ref_loc,
+                               float *out_host, int64_t *clip_low, int64_t *clip_high)
+{
+    if (mode < NL_ST_MEDIAN || mode > NL_ST_AUTO) { nl::set_last_error("invalid stacking mode"); return NL_ERR_INVALID_MODE; }
+    if (mode != NL_ST_AUTO && mode != NL_ST_SIGMA && mode != NL_ST_WINSOR_SIGMA) {
+        nl::set_last_error("run_clip_weighted: the mode is neither NL_ST_SIGMA nor NL_ST_WINSOR_SIGMA");
+        return NL_ERR_INVALID_MODE;
+    }
+    if (!g) { nl::set_last_error("null group"); return NL_ERR_INVALID_ARG; }
+    return run_tiles(g, [&](nl_stack_t *h) { return nl_stack_run_clip_weighted_async(h, mode, sigma_low, sigma_high, ref_loc); },
+                     out_host, clip_low, clip_high);
+}
+
 // nl_group_run with the maps (include/nlstack_maps.h; fast: include/nlstack_fastmaps.h): the same protocol -- every pass
 // that was started is finished, the first error with its message is the caller's -- and every tile writes its own rows
 // of the three host buffers

@@ -200,6 +200,7 @@ enum class PassKind {
     Maps,                 // nl_stack_run_maps (include/nlstack_maps.h)
     FastMaps,             // nl_stack_run_maps_fast (include/nlstack_fastmaps.h): a maps pass on the default pass's engines where they exist
     WeightedLinfit,       // nl_stack_run_linfit_weighted (include/nlstack_wlinfit.h): an engine of its own, run_linfit_weighted
+    WeightedClip,         // nl_stack_run_clip_weighted (include/nlstack_wclip.h): an engine of its own, run_clip_weighted
 };
 
 // Pure: allocates nothing, enqueues nothing.  The first engine whose condition holds runs the pass.
@@ -638,10 +639,73 @@ static int run_linfit_weighted(nl_stack *h, const PassSetup &p, PassFacts *facts
     return NL_OK;
 }
 
+// The weighted clip pass whose weights follow their frames (include/nlstack_wclip.h, an extension): sigma / winsorized
+// rejection, then the mean of the survivors, each with its own frame's weight.
+//   1. the decision pass of the weighted stacks, unchanged (decision_pass: 33 ... 512 frames), or its shallow
+//      instantiations (9 ... 32 frames, stack_fast_decide_shallow.hip): thresholds per pixel and round in h->d_bounds;
+//   2. one streaming read of the frames under those thresholds (stack_clip_weighted.hip), which hands the pixels without
+//      a complete record to the exact list;
+//   3. the column kernel's <follow> instantiation over that list;
+//   4. the reduction of the sharded clip counters.
+// Up to 8 frames and beyond 512, after nl_stack_set_exact, on handles without a list and where the thresholds cannot be
+// had (ensure_bounds): the column kernel over the whole tile.  Plain protocol throughout, as run_linfit_weighted.
+static bool clip_weighted_decided(nl_stack *h, int mode, const nl::StackArgs &a)
+{
+    return !h->force_exact && h->d_fb_list && a.npix < nl::kFastMaxPixels &&
+           (nl::decide_supported(mode, a.n_frames, a.npix) || nl::decide_ml_supported(mode, a.n_frames, a.npix) ||
+            nl::decide_shallow_supported(mode, a.n_frames, a.npix));
+}
+
+static int run_clip_weighted(nl_stack *h, const PassSetup &p, PassFacts *facts)
+{
+    nl::StackArgs a = p.a;
+    int lanes = 0;
+    size_t lds = 0;
+    bool streamed = false;
+    if (clip_weighted_decided(h, p.mode, a)) {
+        const int rc = decision_pass(h, p, a);
+        if (rc != NL_OK) return rc;
+        if (!a.bounds && nl::decide_shallow_supported(p.mode, a.n_frames, a.npix) && ensure_bounds(h)) {
+            const char *ignored = "";
+            a.bounds = h->d_bounds;
+            a.nrounds = h->d_nrounds;
+            NL_HIP(nl::launch_stack_sigma_decide_shallow(a, h->stream, p.mode == NL_ST_WINSOR_SIGMA, &ignored));
+        }
+        streamed = a.bounds != nullptr;
+    }
+    if (streamed) {
+        NL_HIP(nl::launch_stack_clip_weighted(a, list_args(h, true, false), h->stream, &h->last_kernel));
+        NL_HIP(hipEventRecord(h->ev_dom1, h->stream));
+        if (nl::exact_plan(p.mode, false, a.n_frames, a.n_pad, kListLanes, &lanes, &lds) != 0)
+            return fail(NL_ERR_TOO_MANY_FRAMES, "%d frames do not fit the per-pixel LDS column (mode %d)", a.n_frames, p.mode);
+        nl::StackArgs e = a;
+        e.bounds = nullptr;
+        e.nrounds = nullptr;
+        e.list = h->d_fb_list;
+        e.list_count = h->d_fb_count;
+        e.list_capacity = (unsigned)h->npix;
+        const char *exact_name = "";
+        NL_HIP(nl::launch_stack_exact_follow(p.mode, e, lanes, kListGrid, lds, h->stream, &exact_name));
+        facts->used_fast = true;
+    } else {
+        a.bounds = nullptr;
+        a.nrounds = nullptr;
+        if (nl::exact_plan(p.mode, false, a.n_frames, a.n_pad, 64, &lanes, &lds) != 0)
+            return fail(NL_ERR_TOO_MANY_FRAMES, "%d frames do not fit the per-pixel LDS column (mode %d)", a.n_frames, p.mode);
+        a.tiles = (a.npix + lanes - 1) / lanes;
+        const int grid = (int)(a.tiles < (int64_t)h->max_grid ? a.tiles : (int64_t)h->max_grid);
+        NL_HIP(nl::launch_stack_exact_follow(p.mode, a, lanes, grid, lds, h->stream, &h->last_kernel));
+        NL_HIP(hipEventRecord(h->ev_dom1, h->stream));
+    }
+    NL_HIP(nl::launch_reduce_counters(h->d_partial, nl::kClipSlots, h->d_counters, h->stream));
+    facts->has_counters = true;
+    return NL_OK;
+}
+
 static int run_async_impl(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc, PassKind kind);
 
 // what a pass that failed half-way leaves behind (nl_stack_run_async, nl::stack_run_maps_async, nl::stack_run_maps_fast_async,
-// nl_stack_run_linfit_weighted_async)
+// nl_stack_run_linfit_weighted_async, nl_stack_run_clip_weighted_async)
 static int settle_failed_pass(nl_stack_t *h, int rc)
 {
     if (rc != NL_OK && h && h->stream) {
@@ -674,16 +738,23 @@ int nl_stack_run_async(nl_stack_t *h, int mode, float sigma_low, float sigma_hig
 // PassKind::FastMaps (nl_stack_run_maps_fast) is a maps pass that select_engine may give to run_sigma_fast_maps: it has
 // lists, but keeps all of the above (plain protocol, no hints either way).
 // The same holds for the weighted linear-fit pass (PassKind::WeightedLinfit; `mode` is NL_ST_LINEAR_FIT), which keeps the
-// weights the default linear fit drops and runs on run_linfit_weighted.
+// weights the default linear fit drops and runs on run_linfit_weighted, and for the weighted clip pass whose weights follow
+// their frames (PassKind::WeightedClip; `mode` resolves to sigma or winsorized sigma), which runs on run_clip_weighted.
 static int run_async_impl(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc, PassKind kind)
 {
     NL_CHECK_HANDLE(h);
     const bool maps = kind == PassKind::Maps || kind == PassKind::FastMaps, wlinfit = kind == PassKind::WeightedLinfit;
+    const bool wclip = kind == PassKind::WeightedClip;
+    if (wclip && !h->has_weights)
+        return fail(NL_ERR_INVALID_ARG, "run_clip_weighted: the handle has no weights (nl_stack_set_weights); "
+                                        "the unweighted pass is nl_stack_run");
     if (wlinfit && !h->has_weights)
         return fail(NL_ERR_INVALID_ARG, "run_linfit_weighted: the handle has no weights (nl_stack_set_weights); "
                                         "the unweighted fit is nl_stack_run with NL_ST_LINEAR_FIT");
     if (mode < NL_ST_MEDIAN || mode > NL_ST_AUTO) return fail(NL_ERR_INVALID_MODE, "invalid stacking mode");
     if (mode == NL_ST_AUTO) mode = auto_select_mode(h->n_frames);
+    if (wclip && mode != NL_ST_SIGMA && mode != NL_ST_WINSOR_SIGMA)
+        return fail(NL_ERR_INVALID_MODE, "run_clip_weighted: mode %d is neither NL_ST_SIGMA nor NL_ST_WINSOR_SIGMA", mode);
     bool weighted = h->has_weights;
     if (mode == NL_ST_MAD_SIGMA && weighted)
         return fail(NL_ERR_WEIGHTED_MAD, "MADSigma stacking with weights is still unimplemented");
@@ -767,6 +838,7 @@ static int run_async_impl(nl_stack_t *h, int mode, float sigma_low, float sigma_
     PassFacts facts;
     int rc = NL_OK;
     if (wlinfit) rc = run_linfit_weighted(h, p, &facts);
+    else if (wclip) rc = run_clip_weighted(h, p, &facts);
     else switch (engine) {
     case Engine::Mean:            rc = run_mean(h, p, &facts); break;
     case Engine::MedianRegisters: rc = run_median(h, p, false); break;
@@ -873,6 +945,24 @@ int nl_stack_run_linfit_weighted(nl_stack_t *h, float sigma_low, float sigma_hig
                                  float *out_host, int64_t *clip_low, int64_t *clip_high)
 {
     const int rc = nl_stack_run_linfit_weighted_async(h, sigma_low, sigma_high, ref_loc);
+    if (rc != NL_OK) return rc;
+    return nl_stack_finish(h, out_host, clip_low, clip_high);
+}
+
+// ---- the weighted clip pass whose weights follow their frames (include/nlstack_wclip.h) -------------------------------------
+// (what can be told from the mode alone is told in front of the handle; NL_ST_AUTO is resolved behind it)
+int nl_stack_run_clip_weighted_async(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc)
+{
+    if (mode < NL_ST_MEDIAN || mode > NL_ST_AUTO) return fail(NL_ERR_INVALID_MODE, "invalid stacking mode");
+    if (mode != NL_ST_AUTO && mode != NL_ST_SIGMA && mode != NL_ST_WINSOR_SIGMA)
+        return fail(NL_ERR_INVALID_MODE, "run_clip_weighted: mode %d is neither NL_ST_SIGMA nor NL_ST_WINSOR_SIGMA", mode);
+    return settle_failed_pass(h, run_async_impl(h, mode, sigma_low, sigma_high, ref_loc, PassKind::WeightedClip));
+}
+
+int nl_stack_run_clip_weighted(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc,
+                               float *out_host, int64_t *clip_low, int64_t *clip_high)
+{
+    const int rc = nl_stack_run_clip_weighted_async(h, mode, sigma_low, sigma_high, ref_loc);
     if (rc != NL_OK) return rc;
     return nl_stack_finish(h, out_host, clip_low, clip_high);
 }

@@ -21,6 +21,7 @@
 // exact form the kernel is limited by per-lane LDS latency and VALU issue,
 // see DESIGN.md section 4.
 #include "launch_common.hpp"
+#include "wclip_common.hpp"
 
 namespace nl {
 
@@ -241,6 +242,29 @@ __device__ __forceinline__ int wave_sum(int v)
     return v;
 }
 
+// The weighted clip pass whose weights follow their frames (include/nlstack_wclip.h; no counterpart in the
+// reference), behind the UNWEIGHTED rejection loop: slots 0 .. n-1 of the column hold the survivors K.  A
+// sample's fate is a predicate on its value and the survivors of a chain of intervals are the samples inside
+// one interval, so K = the samples in [min K, max K] (an empty K has no interval: nothing is in).  The frames
+// are read again in frame order and go through the accumulation the streaming kernel uses (wclip_take).
+template <int S>
+__device__ float follow_mean(Col<S> a, int n, const float *fr, const StackArgs &p)
+{
+    float2 bd = make_float2(__builtin_inff(), -__builtin_inff());      // (no sample is inside)
+    if (n > 0) {
+        float mn = a.get(0), mx = mn;
+        for (int i = 1; i < n; i++) {
+            const float g = a.get(i);
+            mn = g < mn ? g : mn;
+            mx = g > mx ? g : mx;
+        }
+        bd = make_float2(mn, mx);
+    }
+    WclipAcc acc;
+    for (int k = 0; k < p.n_frames; k++) wclip_take<0>(fr[(int64_t)k * p.stride], p.weights[k], nullptr, bd, acc);
+    return acc.num / acc.den;
+}
+
 // ---- the kernel -----------------------------------------------------------
 // MODE: NL_ST_* (0 median, 2 sigma, 3 winsor, 4 MAD, 5 linear fit);
 // W: weighted (sigma / winsor; with the linear fit: the weighted linear-fit
@@ -248,8 +272,11 @@ __device__ __forceinline__ int wave_sum(int v)
 // smaller when a 64-wide tile would not fit the 160 KiB LDS); MAPS: the maps
 // pass (nl_stack_run_maps) -- the lane also stores its pixel's own two clip
 // counts, p.reject_map[pix] (whole tile, or the listed pixels: the replay of
-// the fast maps pass; no other instantiation reads it).
-template <int MODE, bool W, int LANES, bool MAPS = false>
+// the fast maps pass; no other instantiation reads it).  FOLLOW (sigma / winsor,
+// W = false): the weighted clip pass whose weights follow their frames
+// (include/nlstack_wclip.h, an extension) -- the unweighted rejection, then
+// follow_mean over the frames; p.weights is set.
+template <int MODE, bool W, int LANES, bool MAPS = false, bool FOLLOW = false>
 __global__ __launch_bounds__(64) void stack_exact_kernel(StackArgs p)
 {
     extern __shared__ float lds[];
@@ -320,7 +347,8 @@ __global__ __launch_bounds__(64) void stack_exact_kernel(StackArgs p)
                     const int before = n;
                     n = clip_pass<LANES, W>(a, b, n, lo, hi, c_lo, c_hi);
                     if (n == before || n <= 1) {
-                        res = W ? weighted_mean(a, b, n) : mean;
+                        if constexpr (FOLLOW) res = follow_mean(a, n, fr, p);
+                        else res = W ? weighted_mean(a, b, n) : mean;
                         break;
                     }
                 }
@@ -527,12 +555,12 @@ __global__ __launch_bounds__(256) void reduce_counters_kernel(unsigned long long
 }
 
 // ---- host-side launcher ----------------------------------------------------
-template <int MODE, bool W, bool MAPS = false>
+template <int MODE, bool W, bool MAPS = false, bool FOLLOW = false>
 static hipError_t launch_exact(const StackArgs &args, int lanes, int grid, size_t lds_bytes, hipStream_t stream)
 {
     Launcher L(stream);
-    L(lanes == 64 ? stack_exact_kernel<MODE, W, 64, MAPS> : lanes == 32 ? stack_exact_kernel<MODE, W, 32, MAPS>
-      : lanes == 16 ? stack_exact_kernel<MODE, W, 16, MAPS> : stack_exact_kernel<MODE, W, 4, MAPS>, grid, 64, lds_bytes, args);
+    L(lanes == 64 ? stack_exact_kernel<MODE, W, 64, MAPS, FOLLOW> : lanes == 32 ? stack_exact_kernel<MODE, W, 32, MAPS, FOLLOW>
+      : lanes == 16 ? stack_exact_kernel<MODE, W, 16, MAPS, FOLLOW> : stack_exact_kernel<MODE, W, 4, MAPS, FOLLOW>, grid, 64, lds_bytes, args);
     return L.err;
 }
 
@@ -586,6 +614,23 @@ hipError_t launch_stack_exact(int mode, bool weighted, const StackArgs &args, in
         }
         *name = "stack_exact_kernel<linearfit>";
         return launch_exact<NL_ST_LINEAR_FIT, false>(args, lanes, grid, lds_bytes, stream);
+    default:
+        return hipErrorInvalidValue;
+    }
+}
+
+// the <follow> instantiations (include/nlstack_wclip.h): one column (plan with weighted = false), args.weights set
+hipError_t launch_stack_exact_follow(int mode, const StackArgs &args, int lanes, int grid, size_t lds_bytes,
+                                     hipStream_t stream, const char **name)
+{
+    if (!args.weights) return hipErrorInvalidValue;
+    switch (mode) {
+    case NL_ST_SIGMA:
+        *name = "stack_exact_kernel<sigma,follow>";
+        return launch_exact<NL_ST_SIGMA, false, false, true>(args, lanes, grid, lds_bytes, stream);
+    case NL_ST_WINSOR_SIGMA:
+        *name = "stack_exact_kernel<winsor,follow>";
+        return launch_exact<NL_ST_WINSOR_SIGMA, false, false, true>(args, lanes, grid, lds_bytes, stream);
     default:
         return hipErrorInvalidValue;
     }

@@ -335,6 +335,19 @@ hipError_t launch_stack_linfit_ml(const StackArgs &args, const FastArgs &fargs, 
 int linfit_weighted_supported(int n_frames, int64_t npix);
 hipError_t launch_stack_linfit_weighted(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name);
 
+// ---- the weighted clip pass whose weights follow their frames (include/nlstack_wclip.h, an extension) ----
+// stack_fast_decide_shallow.hip: the decision pass at 9 ... 32 frames (RECORD instantiations at network sizes 16 / 24 / 32);
+// this pass only -- decide_supported and the weighted default pass stay at 33 frames
+int decide_shallow_supported(int mode, int n_frames, int64_t npix);
+hipError_t launch_stack_sigma_decide_shallow(const StackArgs &args, hipStream_t stream, bool winsor, const char **name);
+// stack_clip_weighted.hip: one streaming read of the frames under the thresholds in args.bounds / args.nrounds, the
+// weights from args.weights; pixels without a complete record go to fargs.fb_list, for launch_stack_exact_follow
+hipError_t launch_stack_clip_weighted(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name);
+// stack_exact.hip: the column kernel's <follow> instantiations (NL_ST_SIGMA / NL_ST_WINSOR_SIGMA; one column: plan
+// with weighted = false; args.weights must be set), over the tile or over args.list
+hipError_t launch_stack_exact_follow(int mode, const StackArgs &args, int lanes, int grid, size_t lds_bytes,
+                                     hipStream_t stream, const char **name);
+
 // ---- stack_mean.hip ----
 hipError_t launch_stack_mean(bool weighted, const StackArgs &args, hipStream_t stream,
                              const char **name);

@@ -134,6 +134,7 @@ std::string OpStack::MarshalJSON() const
     o << "{\"type\":\"" << Type << "\",\"mode\":" << Mode << ",\"weighting\":" << Weighting
       << ",\"sigmaLow\":" << fmt_g(SigmaLow) << ",\"sigmaHigh\":" << fmt_g(SigmaHigh);
     if (WeightedLinearFit) o << ",\"weightedLinearFit\":true";       // (an extension: absent unless set)
+    if (WeightsFollowFrames) o << ",\"weightsFollowFrames\":true";   // (likewise)
     o << "}";
     return o.str();
 }
@@ -176,7 +177,9 @@ bool OpStack::UnmarshalJSON(const std::string &data, std::string *err)
     if (find_value(data, "sigmaLow", &v)) def.SigmaLow = strtof(v.c_str(), &end);
     if (find_value(data, "sigmaHigh", &v)) def.SigmaHigh = strtof(v.c_str(), &end);
     if (find_value(data, "weightedLinearFit", &v)) def.WeightedLinearFit = v == "true";
+    if (find_value(data, "weightsFollowFrames", &v)) def.WeightsFollowFrames = v == "true";
     Type = def.Type; Mode = def.Mode; Weighting = def.Weighting; WeightedLinearFit = def.WeightedLinearFit;
+    WeightsFollowFrames = def.WeightsFollowFrames;
     SigmaLow = def.SigmaLow; SigmaHigh = def.SigmaHigh; RefFrameLoc = 0;
     return true;
 }
@@ -306,8 +309,13 @@ Result OpStack::Apply(const std::vector<ImagePtr> &f, Context *c)
         int64_t clipLow = 0, clipHigh = 0;
         // (the extension: the fit rejects, the weights average; the reference's fit drops them)
         const bool weightedFit = WeightedLinearFit && mode == StLinearFit && !weights.empty();
+        // (the other extension: sigma / winsorized clipping averages each survivor with ITS frame's weight, not with
+        // the one the reference's quickselect left in its slot)
+        const bool followFrames = WeightsFollowFrames && (mode == StSigma || mode == StWinsorSigma) && !weights.empty();
         if (rc == NL_OK && weightedFit)
             rc = nl_group_run_linfit_weighted(h, SigmaLow, SigmaHigh, RefFrameLoc, Resident ? nullptr : data.data(), &clipLow, &clipHigh);
+        else if (rc == NL_OK && followFrames)
+            rc = nl_group_run_clip_weighted(h, mode, SigmaLow, SigmaHigh, RefFrameLoc, Resident ? nullptr : data.data(), &clipLow, &clipHigh);
         else if (rc == NL_OK)
             rc = nl_group_run(h, mode, SigmaLow, SigmaHigh, RefFrameLoc, Resident ? nullptr : data.data(), &clipLow, &clipHigh);
         if (rc != NL_OK) { out.err = nl_last_error(); break; }

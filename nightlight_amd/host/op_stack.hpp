@@ -22,6 +22,11 @@ struct OpStack : Operator, OpBase {
     // weighting is not none, reject by the fit and average the survivors with the weights, instead of dropping the
     // weights as the reference does (stack.go:188-189).  Parsed when present, emitted only when true.
     bool WeightedLinearFit = false;   // json:"weightedLinearFit"
+    // not in the reference either (an EXTENSION, include/nlstack_wclip.h): when the mode resolves to sigma or winsorized
+    // sigma clipping and the weighting is not none, average each survivor with its own frame's weight, instead of the
+    // weight the reference's quickselect left in the survivor's slot (stack.go:487).  Parsed when present, emitted only
+    // when true.
+    bool WeightsFollowFrames = false; // json:"weightsFollowFrames"
     // not in the reference: a group of device handles the caller keeps across several Apply calls
     // (OpStackBatches).  When set, Apply stacks on it and leaves the result tile on the devices
     // (the returned image carries metadata only) for nl_group_accumulate.

@@ -188,6 +188,26 @@ class StackHandle:
         capi.check(self._lib.nl_stack_run_linfit_weighted_async(self._h, C.c_float(sigma_low), C.c_float(sigma_high),
                                                                 C.c_float(ref_loc)))
 
+    def run_clip_weighted(self, mode=capi.ST_AUTO, sigma_low=2.75, sigma_high=2.75, ref_loc=0.0, out=None, fetch=True):
+        """One pass of weighted sigma / winsorized clipping whose weights follow their frames
+        (include/nlstack_wclip.h; an EXTENSION: the reference multiplies a survivor by whichever weight its
+        quickselect left in the survivor's slot): the reference's rejection, then the mean of the survivors, each
+        with its own frame's weight of set_weights.  `mode` is ST_SIGMA, ST_WINSOR_SIGMA, or ST_AUTO where that
+        resolves to one of them.  Returns (result or None, clip_low, clip_high) as run does; the counters are those of
+        run(mode).  Without weights it raises NlError (ERR_INVALID_ARG)."""
+        cl, ch = C.c_int64(0), C.c_int64(0)
+        if fetch and out is None:
+            out = np.zeros(self.width * self.height, np.float32)
+        optr = capi.fptr(out) if (fetch and out is not None) else None
+        capi.check(self._lib.nl_stack_run_clip_weighted(self._h, int(mode), C.c_float(sigma_low), C.c_float(sigma_high),
+                                                        C.c_float(ref_loc), optr, C.byref(cl), C.byref(ch)))
+        return (out if fetch else None), cl.value, ch.value
+
+    def run_clip_weighted_async(self, mode=capi.ST_AUTO, sigma_low=2.75, sigma_high=2.75, ref_loc=0.0):
+        """run_clip_weighted without the wait: finish() completes it."""
+        capi.check(self._lib.nl_stack_run_clip_weighted_async(self._h, int(mode), C.c_float(sigma_low),
+                                                              C.c_float(sigma_high), C.c_float(ref_loc)))
+
     def coverage(self, out=None):
         """Whole-image uint16 map of how many active frames have a sample (not NaN) at each pixel: the tile's rows
         of `out` (made here, zero outside the tile, if not given).  No pass: the last result stays."""
@@ -693,6 +713,15 @@ class StackGroup:
         capi.check(self._lib.nl_group_run_linfit_weighted(self._g, C.c_float(sigma_low), C.c_float(sigma_high),
                                                           C.c_float(ref_loc), capi.fptr(out) if download else None,
                                                           C.byref(cl), C.byref(ch)))
+        return out, cl.value, ch.value
+
+    def run_clip_weighted(self, mode=capi.ST_AUTO, sigma_low=2.75, sigma_high=2.75, ref_loc=0.0, download=True):
+        """StackHandle.run_clip_weighted over the tiles: (result or None, clip_low, clip_high)."""
+        out = np.zeros(self.width * self.height, np.float32) if download else None
+        cl, ch = C.c_int64(0), C.c_int64(0)
+        capi.check(self._lib.nl_group_run_clip_weighted(self._g, int(mode), C.c_float(sigma_low), C.c_float(sigma_high),
+                                                        C.c_float(ref_loc), capi.fptr(out) if download else None,
+                                                        C.byref(cl), C.byref(ch)))
         return out, cl.value, ch.value
 
     def coverage(self):
