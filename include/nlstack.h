@@ -345,6 +345,12 @@ int nl_group_accumulate_finalize(nl_group_t *g, float weight_sum, float *out_hos
  * nl_stack_run_maps_fast, nl_group_run_maps_fast: declared in nlstack_fastmaps.h, which is part of this interface. */
 #include "nlstack_fastmaps.h"
 
+/* ---- the same maps from the engines that keep a pixel's column in registers: those of nlstack_fastmaps.h, and the linear
+ * fit's kernels with their cascade (1 ... 512 frames, bit-exact) ----
+ * nl_stack_run_maps_resident, nl_group_run_maps_resident: declared in nlstack_residentmaps.h, which is part of this
+ * interface. */
+#include "nlstack_residentmaps.h"
+
 /* ---- linear-fit rejection with a weighted mean of the survivors (an extension: the reference's fit takes no weights) ----
  * nl_stack_run_linfit_weighted, nl_stack_run_linfit_weighted_async, nl_group_run_linfit_weighted: declared in
  * nlstack_wlinfit.h, which is part of this interface. */

@@ -86,6 +86,10 @@ MAPS_EXPORTS = ["nl_stack_run_maps", "nl_stack_coverage", "nl_stack_last_coverag
 # every symbol include/nlstack_fastmaps.h declares (likewise): the maps pass on the default pass's engines
 FASTMAPS_EXPORTS = ["nl_stack_run_maps_fast", "nl_group_run_maps_fast"]
 
+# every symbol include/nlstack_residentmaps.h declares (likewise): the maps pass on the register-resident engines, the
+# linear fit's kernels and cascade included
+RESIDENTMAPS_EXPORTS = ["nl_stack_run_maps_resident", "nl_group_run_maps_resident"]
+
 # every symbol include/nlstack_wlinfit.h declares (likewise): the weighted linear-fit pass, an extension
 WLINFIT_EXPORTS = ["nl_stack_run_linfit_weighted", "nl_stack_run_linfit_weighted_async", "nl_group_run_linfit_weighted"]
 
@@ -281,6 +285,8 @@ def open_library(path):
     L.nl_group_run_maps.argtypes = _maps_args
     L.nl_stack_run_maps_fast.argtypes = _maps_args
     L.nl_group_run_maps_fast.argtypes = _maps_args
+    L.nl_stack_run_maps_resident.argtypes = _maps_args
+    L.nl_group_run_maps_resident.argtypes = _maps_args
     _wlinfit_args = [vp, C.c_float, C.c_float, C.c_float, _f32p, _i64p, _i64p]
     L.nl_stack_run_linfit_weighted.argtypes = _wlinfit_args
     L.nl_group_run_linfit_weighted.argtypes = _wlinfit_args

@@ -301,10 +301,12 @@ int nl_group_run_clip_weighted(nl_group_t *g, int mode, float sigma_low, float s
                      out_host, clip_low, clip_high);
 }
 
-// nl_group_run with the maps (include/nlstack_maps.h; fast: include/nlstack_fastmaps.h): the same protocol -- every pass
+// nl_group_run with the maps (include/nlstack_maps.h; MapsEntry::Fast: include/nlstack_fastmaps.h; MapsEntry::Resident:
+// include/nlstack_residentmaps.h): the same protocol -- every pass
 // that was started is finished, the first error with its message is the caller's -- and every tile writes its own rows
 // of the three host buffers
-static int group_run_maps(nl_group_t *g, bool fast, int mode, float sigma_low, float sigma_high, float ref_loc,
+enum class MapsEntry { Column, Fast, Resident };
+static int group_run_maps(nl_group_t *g, MapsEntry entry, int mode, float sigma_low, float sigma_high, float ref_loc,
                           float *out_host, int64_t *clip_low, int64_t *clip_high,
                           uint16_t *reject_low_host, uint16_t *reject_high_host)
 {
@@ -316,8 +318,9 @@ static int group_run_maps(nl_group_t *g, bool fast, int mode, float sigma_low, f
     };
     size_t started = 0;
     for (; started < g->tiles.size() && first_rc == NL_OK; started++)
-        note(fast ? nl::stack_run_maps_fast_async(g->tiles[started], mode, sigma_low, sigma_high, ref_loc)
-                  : nl::stack_run_maps_async(g->tiles[started], mode, sigma_low, sigma_high, ref_loc));
+        note(entry == MapsEntry::Resident ? nl::stack_run_maps_resident_async(g->tiles[started], mode, sigma_low, sigma_high, ref_loc)
+             : entry == MapsEntry::Fast   ? nl::stack_run_maps_fast_async(g->tiles[started], mode, sigma_low, sigma_high, ref_loc)
+                                          : nl::stack_run_maps_async(g->tiles[started], mode, sigma_low, sigma_high, ref_loc));
     if (first_rc != NL_OK) started--;                     // (a failing start settles its handle: nothing of it is in flight)
     const bool ok = first_rc == NL_OK;
     int64_t lo = 0, hi = 0;
@@ -350,7 +353,7 @@ int nl_group_run_maps(nl_group_t *g, int mode, float sigma_low, float sigma_high
                       float *out_host, int64_t *clip_low, int64_t *clip_high,
                       uint16_t *reject_low_host, uint16_t *reject_high_host)
 {
-    return group_run_maps(g, false, mode, sigma_low, sigma_high, ref_loc, out_host, clip_low, clip_high, reject_low_host,
+    return group_run_maps(g, MapsEntry::Column, mode, sigma_low, sigma_high, ref_loc, out_host, clip_low, clip_high, reject_low_host,
                           reject_high_host);
 }
 
@@ -358,8 +361,16 @@ int nl_group_run_maps_fast(nl_group_t *g, int mode, float sigma_low, float sigma
                            float *out_host, int64_t *clip_low, int64_t *clip_high,
                            uint16_t *reject_low_host, uint16_t *reject_high_host)
 {
-    return group_run_maps(g, true, mode, sigma_low, sigma_high, ref_loc, out_host, clip_low, clip_high, reject_low_host,
+    return group_run_maps(g, MapsEntry::Fast, mode, sigma_low, sigma_high, ref_loc, out_host, clip_low, clip_high, reject_low_host,
                           reject_high_host);
+}
+
+int nl_group_run_maps_resident(nl_group_t *g, int mode, float sigma_low, float sigma_high, float ref_loc,
+                               float *out_host, int64_t *clip_low, int64_t *clip_high,
+                               uint16_t *reject_low_host, uint16_t *reject_high_host)
+{
+    return group_run_maps(g, MapsEntry::Resident, mode, sigma_low, sigma_high, ref_loc, out_host, clip_low, clip_high,
+                          reject_low_host, reject_high_host);
 }
 
 // every tile counts on its own device and writes its own rows

@@ -178,7 +178,8 @@ enum class Engine {
     MedianMultiLane,      // 129 ... 512 frames, 2 or 4 lanes per pixel
     Listed,               // MAD sigma / linear fit, one- or multi-lane: dominant kernel + bit-exact replay of its list
     SigmaFast,            // sigma / winsorized: dominant kernel + generic pass, replays of the pixels both hand over
-    SigmaFastMaps,        // the same kernels with the per-pixel counts, plain protocol (a fast maps pass only)
+    SigmaFastMaps,        // the same kernels with the per-pixel counts, plain protocol (a fast or resident maps pass only)
+    LinfitMaps,           // the linear fit's kernels and cascade with the per-pixel counts (a resident maps pass only)
     WeightedTile,         // bit-exact replay, 64 consecutive pixels per wave with their columns in LDS
     DenseReplay,          // bit-exact wave-per-pixel replay over the whole tile (behind a decision pass where there is one)
     ExactColumns,         // bit-exact, one pixel per lane with its column in LDS: every mode, any depth
@@ -191,7 +192,7 @@ struct PassSetup {
     bool timed;               // the pass records its timing events (not with kDevUntimed)
     bool fused;               // fused protocol (fused_protocol_on; only the SigmaFast engine runs it)
     nl::StackArgs a;
-    bool maps = false;        // a maps pass (nl_stack_run_maps, nl_stack_run_maps_fast): a.reject_map is set
+    bool maps = false;        // a maps pass (nl_stack_run_maps, nl_stack_run_maps_fast, nl_stack_run_maps_resident): a.reject_map is set
 };
 
 // what kind of pass run_async_impl sets up
@@ -199,20 +200,26 @@ enum class PassKind {
     Default,              // nl_stack_run_async
     Maps,                 // nl_stack_run_maps (include/nlstack_maps.h)
     FastMaps,             // nl_stack_run_maps_fast (include/nlstack_fastmaps.h): a maps pass on the default pass's engines where they exist
+    ResidentMaps,         // nl_stack_run_maps_resident (include/nlstack_residentmaps.h): FastMaps, and the linear fit on its own kernels and cascade
     WeightedLinfit,       // nl_stack_run_linfit_weighted (include/nlstack_wlinfit.h): an engine of its own, run_linfit_weighted
     WeightedClip,         // nl_stack_run_clip_weighted (include/nlstack_wclip.h): an engine of its own, run_clip_weighted
 };
 
 // Pure: allocates nothing, enqueues nothing.  The first engine whose condition holds runs the pass.
-// fast_maps: a maps pass may run on the register-resident sigma kernels (PassKind::FastMaps).
-static Engine select_engine(const nl_stack *h, int mode, bool weighted, const nl::StackArgs &a, bool fast_maps)
+// kind: a maps pass may run on the register-resident sigma kernels (PassKind::FastMaps, PassKind::ResidentMaps) and on
+// the linear fit's (PassKind::ResidentMaps).
+static Engine select_engine(const nl_stack *h, int mode, bool weighted, const nl::StackArgs &a, PassKind kind)
 {
+    const bool fast_maps = kind == PassKind::FastMaps || kind == PassKind::ResidentMaps;
     const bool fast = !h->force_exact;
     const int n = a.n_frames;
     if (mode == NL_ST_MEAN) return Engine::Mean;
     if (a.reject_map && fast_maps && fast && h->d_fb_list && h->d_gen_list && (mode == NL_ST_SIGMA || mode == NL_ST_WINSOR_SIGMA) &&
         nl::fast_supported(mode, weighted, n, a.npix))
         return Engine::SigmaFastMaps;
+    if (a.reject_map && kind == PassKind::ResidentMaps && fast && h->d_fb_list && mode == NL_ST_LINEAR_FIT &&
+        (nl::linfit_fast_supported(mode, n, a.npix) || nl::linfit_ml_supported(mode, n, a.npix)))
+        return Engine::LinfitMaps;
     if (a.reject_map) return Engine::ExactColumns;      // a maps pass: the one engine that carries the per-pixel counts out of every mode
     if (fast && mode == NL_ST_MEDIAN && nl::fast_supported(mode, weighted, n, a.npix)) return Engine::MedianRegisters;
     if (fast && mode == NL_ST_MEDIAN && nl::fast_ml_supported(mode, weighted, n, a.npix)) return Engine::MedianMultiLane;
@@ -555,6 +562,38 @@ static int run_sigma_fast_maps(nl_stack *h, const PassSetup &p, PassFacts *facts
     return NL_OK;
 }
 
+// The resident maps pass of the linear fit (include/nlstack_residentmaps.h): run_listed's linear-fit branch with the MAPS
+// instantiations of its kernels (stack_linfit_maps.hip) and the column kernel's MAPS replay -- the same plain protocol on
+// the handle's one stream, the same cascade, quotas and grids:
+//   1. the dominant kernel over the tile: every lane that does not hand its pixel to the exact list STORES the pixel's
+//      word of the map, p_lo | p_hi << 16, whether the pixel is finished or goes on;
+//   2. the continuation stages of the cascade: the lane that owns a listed pixel ADDS its stage's counts to that word
+//      (load, add, store: a pixel is on a stage's list at most once, the stages are ordered on the stream);
+//   3. the column kernel's MAPS instantiation over the exact list (the pixels with an infinite sample), which stores
+//      theirs: no stage touched them;
+//   4. the reduction of the sharded clip counters.
+// Every word is first written by exactly one plain store of 1. or 3.; 2. only adds to words this pass wrote: no memset,
+// no stale word of an earlier pass.  Both kernels are bit-exact, so the result is the bit-exact one as well.  The stage
+// lengths stay in d_lf_count and the exact list's in the scratch set, as run_listed leaves them.
+static int run_linfit_maps(nl_stack *h, const PassSetup &p, PassFacts *facts)
+{
+    const nl::StackArgs &a = p.a;
+    const nl::FastArgs f = list_args(h, true, false);
+    nl::LinfitCascade cascade;
+    const nl::LinfitCascade *cas = linfit_cascade(h, &cascade);
+    if (cas) NL_HIP(hipMemsetAsync(h->d_lf_count, 0, sizeof(unsigned) * nl::kLinfitCounters, h->stream));
+    if (nl::linfit_ml_supported(p.mode, a.n_frames, a.npix))
+        NL_HIP(nl::launch_stack_linfit_ml_maps(a, f, cas, h->stream, &h->last_kernel, h->ev_dom1));
+    else
+        NL_HIP(nl::launch_stack_linfit_fast_maps(a, f, cas, h->stream, &h->last_kernel, h->ev_dom1));
+    const int rc = replay_list(h, p.mode, p.weighted, a, true);
+    if (rc != NL_OK) return rc;
+    NL_HIP(nl::launch_reduce_counters(h->d_partial, nl::kClipSlots, h->d_counters, h->stream));
+    facts->has_counters = true;
+    facts->used_fast = true;
+    return NL_OK;
+}
+
 // Bit-exact replay over the whole tile, 64 consecutive pixels per wave with their columns in LDS, one pixel per lane:
 // the default for weighted sigma / winsorized clipping (their result depends on the reference's permutation, so there
 // is no register-resident shortcut) up to kTileMaxFrames* frames -- the LDS column limits it to one wave per SIMD at
@@ -705,6 +744,7 @@ static int run_clip_weighted(nl_stack *h, const PassSetup &p, PassFacts *facts)
 static int run_async_impl(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc, PassKind kind);
 
 // what a pass that failed half-way leaves behind (nl_stack_run_async, nl::stack_run_maps_async, nl::stack_run_maps_fast_async,
+// nl::stack_run_maps_resident_async,
 // nl_stack_run_linfit_weighted_async, nl_stack_run_clip_weighted_async)
 static int settle_failed_pass(nl_stack_t *h, int rc)
 {
@@ -736,14 +776,16 @@ int nl_stack_run_async(nl_stack_t *h, int mode, float sigma_low, float sigma_hig
 // default passes remember from one another: it takes and leaves no list-length hints (it has no lists), never runs the
 // fused protocol, and leaves the scratch sets as any other plain-protocol pass does.
 // PassKind::FastMaps (nl_stack_run_maps_fast) is a maps pass that select_engine may give to run_sigma_fast_maps: it has
-// lists, but keeps all of the above (plain protocol, no hints either way).
+// lists, but keeps all of the above (plain protocol, no hints either way).  PassKind::ResidentMaps
+// (nl_stack_run_maps_resident) is that pass with one more engine, run_linfit_maps for the linear fit, under the same rules;
+// the linear fit drops the handle's weights here as in every other unweighted entry (stack.go:158).
 // The same holds for the weighted linear-fit pass (PassKind::WeightedLinfit; `mode` is NL_ST_LINEAR_FIT), which keeps the
 // weights the default linear fit drops and runs on run_linfit_weighted, and for the weighted clip pass whose weights follow
 // their frames (PassKind::WeightedClip; `mode` resolves to sigma or winsorized sigma), which runs on run_clip_weighted.
 static int run_async_impl(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc, PassKind kind)
 {
     NL_CHECK_HANDLE(h);
-    const bool maps = kind == PassKind::Maps || kind == PassKind::FastMaps, wlinfit = kind == PassKind::WeightedLinfit;
+    const bool maps = kind == PassKind::Maps || kind == PassKind::FastMaps || kind == PassKind::ResidentMaps, wlinfit = kind == PassKind::WeightedLinfit;
     const bool wclip = kind == PassKind::WeightedClip;
     if (wclip && !h->has_weights)
         return fail(NL_ERR_INVALID_ARG, "run_clip_weighted: the handle has no weights (nl_stack_set_weights); "
@@ -801,7 +843,7 @@ static int run_async_impl(nl_stack_t *h, int mode, float sigma_low, float sigma_
     h->ring_timed[h->pass_seq % kTimingRing] = timed;
     if (timed) NL_HIP(hipEventRecord(h->ev_start, h->stream));
     const bool fused_on = fused_protocol_on();
-    const Engine engine = select_engine(h, mode, weighted, a, kind == PassKind::FastMaps);
+    const Engine engine = select_engine(h, mode, weighted, a, kind);
     const bool sigma_fast = engine == Engine::SigmaFast;
     // (only while the exact list is short -- the length the last finished pass reported: its replays add their
     // counts to ONE word, and thousands of workgroups doing that take longer than a reduction kernel)
@@ -846,6 +888,7 @@ static int run_async_impl(nl_stack_t *h, int mode, float sigma_low, float sigma_
     case Engine::Listed:          rc = run_listed(h, p, &facts); break;
     case Engine::SigmaFast:       rc = run_sigma_fast(h, p, &facts); break;
     case Engine::SigmaFastMaps:   rc = run_sigma_fast_maps(h, p, &facts); break;
+    case Engine::LinfitMaps:      rc = run_linfit_maps(h, p, &facts); break;
     case Engine::WeightedTile:    rc = run_weighted_tile(h, p, &facts); break;
     case Engine::DenseReplay:     rc = run_dense_replay(h, p, &facts); break;
     case Engine::ExactColumns:    rc = run_exact_columns(h, p, &facts); break;
@@ -904,6 +947,12 @@ int nl::stack_run_maps_async(nl_stack_t *h, int mode, float sigma_low, float sig
 int nl::stack_run_maps_fast_async(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc)
 {
     return settle_failed_pass(h, run_async_impl(h, mode, sigma_low, sigma_high, ref_loc, PassKind::FastMaps));
+}
+
+// the resident maps pass (include/nlstack_residentmaps.h)
+int nl::stack_run_maps_resident_async(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc)
+{
+    return settle_failed_pass(h, run_async_impl(h, mode, sigma_low, sigma_high, ref_loc, PassKind::ResidentMaps));
 }
 
 // nl_stack_finish, and the two planes of the map (of either kind of maps pass).  The packed words come down in ONE copy and are split here: the same
@@ -981,6 +1030,15 @@ int nl_stack_run_maps_fast(nl_stack_t *h, int mode, float sigma_low, float sigma
                            uint16_t *reject_low_host, uint16_t *reject_high_host)
 {
     const int rc = nl::stack_run_maps_fast_async(h, mode, sigma_low, sigma_high, ref_loc);
+    if (rc != NL_OK) return rc;
+    return nl::stack_finish_maps(h, out_host, clip_low, clip_high, reject_low_host, reject_high_host);
+}
+
+int nl_stack_run_maps_resident(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc,
+                               float *out_host, int64_t *clip_low, int64_t *clip_high,
+                               uint16_t *reject_low_host, uint16_t *reject_high_host)
+{
+    const int rc = nl::stack_run_maps_resident_async(h, mode, sigma_low, sigma_high, ref_loc);
     if (rc != NL_OK) return rc;
     return nl::stack_finish_maps(h, out_host, clip_low, clip_high, reject_low_host, reject_high_host);
 }

@@ -62,8 +62,9 @@ struct StackArgs {
     // decided: the replay computes its own bounds, as without these).  nullptr: off.
     float2 *bounds;
     unsigned char *nrounds;
-    // Maps pass (nl_stack_run_maps, nl_stack_run_maps_fast): [npix] words, the pixel's clipLow count | clipHigh count << 16.
-    // Read by the MAPS instantiations only (stack_exact_kernel; stack_fast_maps_impl.hpp); nullptr everywhere else.
+    // Maps pass (nl_stack_run_maps, nl_stack_run_maps_fast, nl_stack_run_maps_resident): [npix] words, the pixel's clipLow
+    // count | clipHigh count << 16.  Read by the MAPS instantiations only (stack_exact_kernel; stack_fast_maps_impl.hpp;
+    // stack_linfit_impl.hpp); nullptr everywhere else.
     unsigned *reject_map;
 };
 
@@ -130,6 +131,8 @@ int stack_finish_maps(nl_stack_t *h, float *out_host, int64_t *clip_low, int64_t
                       uint16_t *reject_high_host);
 // the first half of nl_stack_run_maps_fast (include/nlstack_fastmaps.h); stack_finish_maps finishes either kind
 int stack_run_maps_fast_async(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc);
+// the first half of nl_stack_run_maps_resident (include/nlstack_residentmaps.h); stack_finish_maps finishes it as well
+int stack_run_maps_resident_async(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc);
 
 // Bisection of the goal-seek (spec: internal/ops/stack/stackfindsigma.go:48-98): sigma_low and
 // sigma_high in [1,11], percentages in the reference's fp32 arithmetic, 21 passes at most.
@@ -328,6 +331,13 @@ hipError_t launch_stack_linfit_fast(const StackArgs &args, const FastArgs &fargs
                                     hipStream_t stream, const char **name, hipEvent_t dominant_done);
 hipError_t launch_stack_linfit_ml(const StackArgs &args, const FastArgs &fargs, const LinfitCascade *cascade,
                                   hipStream_t stream, const char **name, hipEvent_t dominant_done);
+// ---- stack_linfit_maps.hip: the MAPS instantiations of the same kernels (the resident maps pass,
+// include/nlstack_residentmaps.h), args.reject_map set.  Same classes, cascade, quotas and grids; every lane that holds a
+// pixel's two clip counts leaves them in args.reject_map (stage 0 stores, continuation stages add: stack_linfit_impl.hpp) ----
+hipError_t launch_stack_linfit_fast_maps(const StackArgs &args, const FastArgs &fargs, const LinfitCascade *cascade,
+                                         hipStream_t stream, const char **name, hipEvent_t dominant_done);
+hipError_t launch_stack_linfit_ml_maps(const StackArgs &args, const FastArgs &fargs, const LinfitCascade *cascade,
+                                       hipStream_t stream, const char **name, hipEvent_t dominant_done);
 
 // ---- stack_linfit_weighted.hip (the weighted linear-fit pass, include/nlstack_wlinfit.h: register-resident fit, one
 // pixel per lane, up to 128 frames; args.weights must be set; pixels it cannot decide go to fargs.fb_list, for

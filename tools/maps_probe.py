@@ -20,6 +20,16 @@
         the fast maps pass        nl_stack_run_maps_fast, every host pointer NULL
         the column maps pass      nl_stack_run_maps, every host pointer NULL
       and the two hand-over list lengths of the fast maps pass.  DIR receives the lines as fastmaps_probe.txt.
+
+  python tools/maps_probe.py --linfit [--linfit-frames 128,32,256 --width 4096 --height 4096 --sigma 3 --reps 20 --out DIR]
+      The resident maps pass of the linear fit (include/nlstack_residentmaps.h) beside the passes it sits next to.  Per
+      frame count ONE handle, and on it the same statistics -- whole pass and dominant kernel -- of:
+        the default pass          nl_stack_run(NL_ST_LINEAR_FIT): plain protocol already, the yardstick
+        the resident maps pass    nl_stack_run_maps_resident, every host pointer NULL
+        the default pass again    the spread between two blocks of the same pass, to read the ratio against
+        the column maps pass      nl_stack_run_maps, every host pointer NULL
+      with the cascade's list lengths and the exact list's.  A frame count whose handle cannot be made (memory) is
+      reported and skipped.  DIR receives the lines as linfitmaps_probe.txt.
 """
 import argparse
 import os
@@ -94,9 +104,72 @@ def fastmaps(a):
             f.write(text + "\n")
 
 
+def linfit(a):
+    import nightlight_amd as nl
+    from nightlight_amd import capi
+    L = capi.load()
+    warm, mode = 3, capi.ST_LINEAR_FIT
+    lines = []
+    try:
+        import torch
+        lines.append("device: %s" % torch.cuda.get_device_name(0))
+    except Exception:
+        pass
+    lines.append("linear fit, frames of %d x %d resident, sigma %.2f / %.2f; %d runs after %d warm-up runs; GPU time of the whole pass"
+                 % (a.width, a.height, a.sigma, a.sigma, a.reps, warm))
+    for n in [int(x) for x in a.linfit_frames.split(",")]:
+        lines.append("-- %d frames" % n)
+        try:
+            st = nl.StackHandle(n, a.width, a.height)
+        except capi.NlError as e:
+            lines.append("no handle of %d frames: %s" % (n, e))
+            continue
+        with st:
+            st.fill_synthetic(seed=7)
+
+            def default_pass():
+                st.run(mode, a.sigma, a.sigma, 0.0, fetch=False)
+                return st.pass_times(0)
+
+            def resident_maps_pass():
+                capi.check(L.nl_stack_run_maps_resident(st._h, mode, a.sigma, a.sigma, 0.0, None, None, None, None, None))
+                return st.pass_times(0)
+
+            def column_maps_pass():
+                capi.check(L.nl_stack_run_maps(st._h, mode, a.sigma, a.sigma, 0.0, None, None, None, None, None))
+                return st.pass_times(0)
+
+            med, med_dom = {}, {}
+            for label, fn in (("default pass", default_pass), ("resident maps pass", resident_maps_pass),
+                              ("default pass again", default_pass), ("column maps pass", column_maps_pass)):
+                both = [fn() for _ in range(warm + a.reps)][warm:]
+                ms, dom = [t[0] for t in both], [t[1] for t in both]
+                med[label], med_dom[label] = float(np.median(ms)), float(np.median(dom))
+                tail = "; dominant kernel median %.3f ms, min %.3f ms" % (med_dom[label], float(np.min(dom)))
+                if label != "column maps pass":
+                    tail += "; exact list %d, stages %r" % (st.last_fallback_pixels, st.linfit_stage_counts[:3])
+                lines.append("%-19s %-44s %s; protocol %d%s" % (label, st.last_kernel_name, stats(ms), st.last_pass_protocol, tail))
+            base = 0.5 * (med["default pass"] + med["default pass again"])
+            lines.append("resident maps / default = %.4f (one more 4-byte store per %d bytes read: %.4f; default again / default = %.4f); "
+                         "column maps / resident maps = %.1f"
+                         % (med["resident maps pass"] / base, 4 * n, 1.0 + 1.0 / n, med["default pass again"] / med["default pass"],
+                            med["column maps pass"] / med["resident maps pass"]))
+            lines.append("dominant kernels, resident maps / default = %.4f; behind the dominant kernel: %.3f ms against %.3f ms"
+                         % (med_dom["resident maps pass"] / (0.5 * (med_dom["default pass"] + med_dom["default pass again"])),
+                            med["resident maps pass"] - med_dom["resident maps pass"], med["default pass"] - med_dom["default pass"]))
+    text = "\n".join(lines)
+    print(text)
+    if a.out:
+        os.makedirs(a.out, exist_ok=True)
+        with open(os.path.join(a.out, "linfitmaps_probe.txt"), "w") as f:
+            f.write(text + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--fastmaps", action="store_true")
+    ap.add_argument("--linfit", action="store_true")
+    ap.add_argument("--linfit-frames", default="128,32,256")
     ap.add_argument("--frames", type=int, default=128)
     ap.add_argument("--width", type=int, default=4096)
     ap.add_argument("--height", type=int, default=4096)
@@ -107,6 +180,8 @@ def main():
     a = ap.parse_args()
     if a.fastmaps:
         return fastmaps(a)
+    if a.linfit:
+        return linfit(a)
     import nightlight_amd as nl
     from nightlight_amd import capi
     L = capi.load()
