@@ -326,6 +326,21 @@ __device__ __forceinline__ void index_bits(int idx, bool (&bit)[M])
     });
 }
 
+// ---- per-lane lookups through LDS rows (the wave-owned sigma kernel, NL_LDS_LOOKUP) ----
+// Tables of floats, one row of kLutThreads floats per index: entry (row, thread) at row * kLutThreads + thread.
+// A thread only ever touches its own column, so the waves of a workgroup share nothing (no barrier), and the 32 lanes
+// of a half wave fall on 32 different banks whatever row each of them asks for (bank = thread mod 32).  Two rows at a
+// constant distance are one ds_read2st64_b32 / ds_write2st64_b32, whose two data registers need not be neighbours.
+// lut_row<BASE, ENTRIES>(idx): the entry of index idx of the table that starts at row BASE; ENTRIES is a power of two and
+// idx is taken modulo it, so a lane whose index is out of range (one that is not active any more) stays inside its table.
+constexpr int kLutThreads = 256;
+template <int BASE, int ENTRIES>
+__device__ __forceinline__ unsigned lut_row(int idx)
+{
+    static_assert(ENTRIES > 0 && (ENTRIES & (ENTRIES - 1)) == 0, "lookup tables hold a power of two of entries");
+    return ((unsigned)BASE + ((unsigned)idx & (unsigned)(ENTRIES - 1))) * (unsigned)kLutThreads + threadIdx.x;
+}
+
 // Rank of a threshold in a sorted zone of Z = 2^M values, as a branch-free binary search.  z(j) (j in [0, Z)) is
 // the zone in the order in which pred holds for a prefix (pred(x): x < t on an ascending zone, x > t on a
 // descending one).  Returns r = #{j < Z-1 : pred(z(j))} in [0, Z-1] -- M compares, each on a candidate selected by

@@ -55,7 +55,8 @@ namespace nl {
 #define NL_PEEL_FIRST(ns) ((ns) >= 128)
 #endif
 // WAVE-OWNED kernels: the zonal plain-sigma kernel of a stack of exactly NS frames, where a wave
-// shares nothing with the other waves of its workgroup -- no LDS, no barrier.  It reserves its own run of the generic
+// shares nothing with the other waves of its workgroup -- no barrier, no LDS but the lookup rows below, of which a
+// thread reads and writes its own column only.  It reserves its own run of the generic
 // hand-over list (one device atomic per wave that hands anything over: affordable only because a TIGHT stack hands over
 // few pixels -- about 4 k of 262 144 waves at 128 frames; the padded and the small-zone instantiations send pixels from
 // half of their waves and keep the per-workgroup reservation, see flush()) and adds its own clip totals to a slot.  The
@@ -67,6 +68,19 @@ namespace nl {
 constexpr bool sigma_wave_owned(int ns, bool zonal, bool winsor, bool tight, bool record, bool cont)
 {
     return zonal && !winsor && tight && !record && !cont && NL_WAVE_OWNED(ns);
+}
+// LDS LOOKUP, wave-owned kernels only: what a clipping pass of the loop looks up by a per-lane
+// index -- the zone tables at a and NS - b, the median pair at kk -- sits in LDS rows a lane fills once and reads with
+// one ds_read_b64 per lookup, instead of a tree of selects over registers per value.  Row (entry, thread) is
+// s_lut[entry * 256 + thread] (LdsLookup, fast_common.hpp): a thread reads and writes its own column only, so a wave
+// shares nothing with its neighbours and orders its accesses by its own s_waitcnt -- no barrier.  The peeled first
+// pass keeps its folded constants and reads no LDS.
+#ifndef NL_LDS_LOOKUP
+#define NL_LDS_LOOKUP(ns) ((ns) >= 128)
+#endif
+constexpr bool sigma_lds_lookup(int ns, bool zonal, bool winsor, bool tight, bool record, bool cont)
+{
+    return sigma_wave_owned(ns, zonal, winsor, tight, record, cont) && NL_LDS_LOOKUP(ns);
 }
 
 // sum over the wave of an int every lane holds (all 64 lanes active): four DPP steps inside each row of 16 lanes, then
@@ -102,7 +116,7 @@ void stack_sigma_fast_kernel(StackArgs p, FastArgs q)
     static_assert(!CONT || (ZONAL && WINSOR && !RECORD), "CONT continues a winsorized zonal pass");
     static_assert(!MAPS || (!RECORD && !CONT), "the maps pass has no decision pass and no cascade");
     constexpr bool CASCADE = ZONAL && WINSOR && !RECORD;      // this instantiation knows about budgets and continuation lists
-    constexpr bool WAVE_OWNED = sigma_wave_owned(NS, ZONAL, WINSOR, TIGHT, RECORD, CONT);     // no LDS, no barrier (MAPS follows its twin)
+    constexpr bool WAVE_OWNED = sigma_wave_owned(NS, ZONAL, WINSOR, TIGHT, RECORD, CONT);     // no barrier, no shared LDS (MAPS follows its twin)
     if constexpr (ZONAL && !RECORD && !CONT) fused_prologue_dominant(p);
     if constexpr (!ZONAL) { if (q.in_list) { fused_collect_slots(p, blockIdx.x); snapshot_fb_list(q); } }
     // zone widths: 8 clipped + 8 missing samples per lane for the larger
@@ -113,6 +127,15 @@ void stack_sigma_fast_kernel(StackArgs p, FastArgs q)
     static_assert(!ZONAL || NS >= 16, "zonal passes need room between the zones");
     constexpr int ZL = KZ;                                    // low zone  = positions [0, ZL)
     constexpr int ZH = ZONAL ? NS - KZ - KP : NS;             // high zone = positions [ZH, NS)
+    // LDS lookup rows (see NL_LDS_LOOKUP): the four zone tables (ZL rows tdl, ZL rows tql, NS - ZH rows tdh and as many
+    // tqh) and the median window v[LK0 - 1 ... LK0 + LKN - 1], a median at kk in [LK0, LK0 + LKN) reading rows kk - LK0 and
+    // the next -- 41 rows of 256 floats at 128 positions, 41 984 bytes: three workgroups per compute unit (160 KiB), as the
+    // registers allow.  No other instantiation references the array.
+    constexpr bool LDSL = sigma_lds_lookup(NS, ZONAL, WINSOR, TIGHT, RECORD, CONT);
+    constexpr int LK0 = (ZH + 1) / 2, LKN = (ZL - 1 + NS) / 2 - LK0 + 1;
+    constexpr int LUT_QL = ZL, LUT_DH = 2 * ZL, LUT_QH = LUT_DH + (NS - ZH), LUT_MED = LUT_QH + (NS - ZH), LUT_ROWS = LUT_MED + LKN + 1;
+    static_assert(!LDSL || LUT_ROWS * kLutThreads * 4 <= 53248, "three workgroups of lookup rows per compute unit");
+    __shared__ float s_lut[LDSL ? LUT_ROWS * kLutThreads : 1];
 
     int c_lo_total = 0, c_hi_total = 0;
     // ZONAL, or GENERIC without a list: the grid covers the tile, one pixel per
@@ -246,6 +269,10 @@ void stack_sigma_fast_kernel(StackArgs p, FastArgs q)
                 sq = __builtin_fmaf(e, e, sq);
                 tdl[k] = sd;                                             // sum over [k, ZL)
                 tql[k] = sq;
+                if constexpr (LDSL) {                                    // (the loop reads these; the peeled pass entry 0 of the registers)
+                    s_lut[lut_row<0, ZL>(k)] = sd;
+                    s_lut[lut_row<LUT_QL, ZL>(k)] = sq;
+                }
             });
             sd = 0.0f; sq = 0.0f;
             static_range<ZH, NS>([&](auto K) NL_INL {
@@ -255,7 +282,18 @@ void stack_sigma_fast_kernel(StackArgs p, FastArgs q)
                 sq = __builtin_fmaf(e, e, sq);
                 tdh[NS - 1 - k] = sd;                                    // sum over [ZH, b), b = k + 1: index NS - b
                 tqh[NS - 1 - k] = sq;
+                if constexpr (LDSL) {
+                    s_lut[lut_row<LUT_DH, ZHW>(NS - 1 - k)] = sd;
+                    s_lut[lut_row<LUT_QH, ZHW>(NS - 1 - k)] = sq;
+                }
             });
+            if constexpr (LDSL) {
+                // the median window: a median at position kk reads rows kk - LK0 (v[kk - 1]) and kk - LK0 + 1 (v[kk])
+                static_range<0, LKN + 1>([&](auto J) NL_INL {
+                    constexpr int j = decltype(J)::value;
+                    s_lut[lut_row<LUT_MED + j, 1>(0)] = v[LK0 - 1 + j];
+                });
+            }
         }
 
         // winsorization (stack.go:646-672) clamps at median -/+ 1.5 sigma: in the zonal
@@ -316,7 +354,9 @@ void stack_sigma_fast_kernel(StackArgs p, FastArgs q)
         int rnd = 0;                           // RECORD: clipping rounds decided so far
         if (ZONAL && lane == 0) NL_STAT(4, 1);
         // one clipping pass of every active lane (stack.go:401-431; the winsorized variants with their loop inside)
-        auto one_pass = [&]() NL_INL {
+        // (PEELED: the call under `peel` below -- its lookups fold to constants and stay on the registers)
+        auto one_pass = [&](auto PEELED) NL_INL {
+            constexpr bool LUT = LDSL && !decltype(PEELED)::value;
             if constexpr (CASCADE) {
                 if (passes_left <= 0) {                    // whoever needs another pass takes it in the next stage
                     defer = defer || active;
@@ -334,7 +374,22 @@ void stack_sigma_fast_kernel(StackArgs p, FastArgs q)
             const int cnt = b - a;
             const float fcnt = (float)cnt;
             float dz0 = 0.0f, dz1 = 0.0f, qz0 = 0.0f, qz1 = 0.0f;
-            if constexpr (ZT) {
+            float med_lower = 0.0f, med_upper = 0.0f;        // LUT: the two ranks of the median, read with the tables
+            if constexpr (LUT) {
+                // the zones' sums: one two-dword LDS read per side, from the rows this lane wrote behind the sort
+                // (NS - b through a register of its own: left to the compiler it becomes a product, v_mul_lo_u32 by -256)
+                const unsigned ra = lut_row<0, ZL>(a), rb = lut_row<LUT_DH, ZHW>(opaque(NS - b));
+                dz0 = s_lut[ra]; qz0 = s_lut[ra + (LUT_QL - 0) * kLutThreads];
+                dz1 = s_lut[rb]; qz1 = s_lut[rb + (LUT_QH - LUT_DH) * kLutThreads];
+                // the median (see below): position a + cnt / 2 in [LK0, LK0 + LKN), rows kk - LK0 and the next of the
+                // median window -- issued here, so that a pass waits for its LDS reads once
+                const unsigned rk = lut_row<LUT_MED, LKN>(a + (cnt >> 1) - LK0);
+                med_lower = s_lut[rk];
+                med_upper = s_lut[rk + kLutThreads];
+                // (both are wanted here, by every lane: otherwise the read of the lower one moves into a divergent branch
+                // over the lanes with an even count, with a wait of its own)
+                asm volatile("" : "+v"(med_lower), "+v"(med_upper));
+            } else if constexpr (ZT) {
                 // the zones' sums: two table lookups per side (a in [0, ZL), NS - b in [0, NS - ZH))
                 bool ba[ML], bb[MH];
                 index_bits(a, ba);
@@ -426,9 +481,12 @@ void stack_sigma_fast_kernel(StackArgs p, FastArgs q)
             // zonal: a in [0,ZL), b in (ZH,NS]  =>  kk in [ZH/2, ZL-1+NS/2]
             const int kk = a + (cnt >> 1);
             float upper, lower;
-            if constexpr (ZT) {
+            if constexpr (LUT) {
+                lower = med_lower;                       // (read with the zone tables, above)
+                upper = med_upper;
+            } else if constexpr (ZT) {
                 // kk = floor((a + b) / 2) in [K0, K1] (a < ZL, b > ZH): a select tree on the bits of kk - K0
-                constexpr int K0 = (ZH + 1) / 2, K1 = (ZL - 1 + NS) / 2, MK = ilog2_ceil(K1 - K0 + 1);
+                constexpr int K0= (ZH + 1) / 2, K1 = (ZL - 1 + NS) / 2, MK = ilog2_ceil(K1 - K0 + 1);
                 static_assert(K0 - 1 >= W0 && K1 < W1, "the median window holds exact ranks");
                 bool bk[MK];
                 index_bits(kk - K0, bk);
@@ -863,9 +921,9 @@ void stack_sigma_fast_kernel(StackArgs p, FastArgs q)
         if (peel) {
             b = NS;                                            // (what it is: n == NS on every lane)
             amax = fmaxf(fabsf(v[0]), fabsf(v[NS - 1]));
-            one_pass();
+            one_pass(std::true_type{});
         }
-        while (__any(active)) one_pass();
+        while (__any(active)) one_pass(std::false_type{});
         if constexpr (RECORD) {
             // (a pixel without data is left to the full replay, which writes RefFrameLoc)
             const bool decided = on && !to_generic && !to_exact && n > 0 && rnd <= kBoundRounds;

@@ -9,7 +9,9 @@ cd "$(dirname "$0")/.." && export TMPDIR=/tmp
 O=${1:-gpurun_out/final}; mkdir -p $O
 # The headline kernel holds three waves per SIMD up to 168 VGPRs, and its count hangs on where the compiler places one
 # branch (stack_fast_sigma_impl.hpp, the peeled first pass): 164 today, 191 - 199 when it goes wrong.  No spills either.
-# It is wave-owned: no LDS and no workgroup barrier -- one of either ties its waves together again.
+# It is wave-owned: no workgroup barrier, which would tie its waves together again.  Its LDS is the
+# lookup rows of section 16, which a thread shares with nobody: at most 53 248 bytes, so that three workgroups fit a compute
+# unit's 160 KiB as the registers allow.
 make -s -C nightlight_amd/csrc kernel-info SRC=stack_fast.hip > $O/kernel_info.txt || exit 1
 make -s -C nightlight_amd/csrc kernel-disasm > $O/kernel_disasm.txt || exit 1
 python3 - $O/kernel_info.txt $O/kernel_disasm.txt <<'PY' || exit 1
@@ -28,7 +30,7 @@ barriers = sum(1 for l in body if re.search(r"\bs_barrier\b", l))
 print("headline kernel: %s VGPRs, %s spilled, %s bytes of LDS, %d s_barrier in %d instructions"
       % (f["vgpr_count"], f["vgpr_spill_count"], f["group_segment_fixed_size"], barriers, len(body)))
 sys.exit(0 if int(f["vgpr_count"]) <= 168 and int(f["vgpr_spill_count"]) == 0 and int(f["private_segment_fixed_size"]) == 0
-         and int(f["group_segment_fixed_size"]) == 0 and barriers == 0 else 1)
+         and int(f["group_segment_fixed_size"]) <= 53248 and barriers == 0 else 1)
 PY
 timeout -k 10 3000 python -m pytest tests -m gpu -x -q > $O/tests_gpu.log 2>&1; rc=$?; echo "rc=$rc" >> $O/tests_gpu.log; tail -3 $O/tests_gpu.log
 [ $rc -eq 0 ] || exit $rc
