@@ -351,6 +351,11 @@ int nl_group_accumulate_finalize(nl_group_t *g, float weight_sum, float *out_hos
  * interface. */
 #include "nlstack_residentmaps.h"
 
+/* ---- the same maps from the LDS-column engines of deep sigma / winsorized stacks (129 ... 512 frames, unweighted), and
+ * from the engines of nlstack_residentmaps.h for everything else ----
+ * nl_stack_run_maps_deep, nl_group_run_maps_deep: declared in nlstack_deepmaps.h, which is part of this interface. */
+#include "nlstack_deepmaps.h"
+
 /* ---- linear-fit rejection with a weighted mean of the survivors (an extension: the reference's fit takes no weights) ----
  * nl_stack_run_linfit_weighted, nl_stack_run_linfit_weighted_async, nl_group_run_linfit_weighted: declared in
  * nlstack_wlinfit.h, which is part of this interface. */

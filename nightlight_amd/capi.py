@@ -90,6 +90,10 @@ FASTMAPS_EXPORTS = ["nl_stack_run_maps_fast", "nl_group_run_maps_fast"]
 # linear fit's kernels and cascade included
 RESIDENTMAPS_EXPORTS = ["nl_stack_run_maps_resident", "nl_group_run_maps_resident"]
 
+# every symbol include/nlstack_deepmaps.h declares (likewise): the maps pass with the LDS-column engines of deep
+# (129 ... 512 frames) sigma / winsorized stacks as well
+DEEPMAPS_EXPORTS = ["nl_stack_run_maps_deep", "nl_group_run_maps_deep"]
+
 # every symbol include/nlstack_wlinfit.h declares (likewise): the weighted linear-fit pass, an extension
 WLINFIT_EXPORTS = ["nl_stack_run_linfit_weighted", "nl_stack_run_linfit_weighted_async", "nl_group_run_linfit_weighted"]
 
@@ -287,6 +291,8 @@ def open_library(path):
     L.nl_group_run_maps_fast.argtypes = _maps_args
     L.nl_stack_run_maps_resident.argtypes = _maps_args
     L.nl_group_run_maps_resident.argtypes = _maps_args
+    L.nl_stack_run_maps_deep.argtypes = _maps_args
+    L.nl_group_run_maps_deep.argtypes = _maps_args
     _wlinfit_args = [vp, C.c_float, C.c_float, C.c_float, _f32p, _i64p, _i64p]
     L.nl_stack_run_linfit_weighted.argtypes = _wlinfit_args
     L.nl_group_run_linfit_weighted.argtypes = _wlinfit_args

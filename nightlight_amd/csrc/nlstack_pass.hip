@@ -179,7 +179,8 @@ enum class Engine {
     Listed,               // MAD sigma / linear fit, one- or multi-lane: dominant kernel + bit-exact replay of its list
     SigmaFast,            // sigma / winsorized: dominant kernel + generic pass, replays of the pixels both hand over
     SigmaFastMaps,        // the same kernels with the per-pixel counts, plain protocol (a fast or resident maps pass only)
-    LinfitMaps,           // the linear fit's kernels and cascade with the per-pixel counts (a resident maps pass only)
+    LinfitMaps,           // the linear fit's kernels and cascade with the per-pixel counts (a resident or deep maps pass only)
+    SigmaDeepMaps,        // the LDS-column sigma kernels of 129 ... 512 frames with the per-pixel counts, plain protocol (a deep maps pass only)
     WeightedTile,         // bit-exact replay, 64 consecutive pixels per wave with their columns in LDS
     DenseReplay,          // bit-exact wave-per-pixel replay over the whole tile (behind a decision pass where there is one)
     ExactColumns,         // bit-exact, one pixel per lane with its column in LDS: every mode, any depth
@@ -192,7 +193,7 @@ struct PassSetup {
     bool timed;               // the pass records its timing events (not with kDevUntimed)
     bool fused;               // fused protocol (fused_protocol_on; only the SigmaFast engine runs it)
     nl::StackArgs a;
-    bool maps = false;        // a maps pass (nl_stack_run_maps, nl_stack_run_maps_fast, nl_stack_run_maps_resident): a.reject_map is set
+    bool maps = false;        // a maps pass (nl_stack_run_maps, nl_stack_run_maps_fast, nl_stack_run_maps_resident, nl_stack_run_maps_deep): a.reject_map is set
 };
 
 // what kind of pass run_async_impl sets up
@@ -201,25 +202,31 @@ enum class PassKind {
     Maps,                 // nl_stack_run_maps (include/nlstack_maps.h)
     FastMaps,             // nl_stack_run_maps_fast (include/nlstack_fastmaps.h): a maps pass on the default pass's engines where they exist
     ResidentMaps,         // nl_stack_run_maps_resident (include/nlstack_residentmaps.h): FastMaps, and the linear fit on its own kernels and cascade
+    DeepMaps,             // nl_stack_run_maps_deep (include/nlstack_deepmaps.h): ResidentMaps, and sigma / winsorized clipping of 129 ... 512 frames on the LDS-column kernels
     WeightedLinfit,       // nl_stack_run_linfit_weighted (include/nlstack_wlinfit.h): an engine of its own, run_linfit_weighted
     WeightedClip,         // nl_stack_run_clip_weighted (include/nlstack_wclip.h): an engine of its own, run_clip_weighted
 };
 
 // Pure: allocates nothing, enqueues nothing.  The first engine whose condition holds runs the pass.
-// kind: a maps pass may run on the register-resident sigma kernels (PassKind::FastMaps, PassKind::ResidentMaps) and on
-// the linear fit's (PassKind::ResidentMaps).
+// kind: a maps pass may run on the register-resident sigma kernels (PassKind::FastMaps, PassKind::ResidentMaps,
+// PassKind::DeepMaps), on the linear fit's (PassKind::ResidentMaps, PassKind::DeepMaps) and on the LDS-column sigma kernels
+// of 129 ... 512 frames (PassKind::DeepMaps).
 static Engine select_engine(const nl_stack *h, int mode, bool weighted, const nl::StackArgs &a, PassKind kind)
 {
-    const bool fast_maps = kind == PassKind::FastMaps || kind == PassKind::ResidentMaps;
+    const bool resident_maps = kind == PassKind::ResidentMaps || kind == PassKind::DeepMaps;
+    const bool fast_maps = kind == PassKind::FastMaps || resident_maps;
     const bool fast = !h->force_exact;
     const int n = a.n_frames;
     if (mode == NL_ST_MEAN) return Engine::Mean;
     if (a.reject_map && fast_maps && fast && h->d_fb_list && h->d_gen_list && (mode == NL_ST_SIGMA || mode == NL_ST_WINSOR_SIGMA) &&
         nl::fast_supported(mode, weighted, n, a.npix))
         return Engine::SigmaFastMaps;
-    if (a.reject_map && kind == PassKind::ResidentMaps && fast && h->d_fb_list && mode == NL_ST_LINEAR_FIT &&
+    if (a.reject_map && resident_maps && fast && h->d_fb_list && mode == NL_ST_LINEAR_FIT &&
         (nl::linfit_fast_supported(mode, n, a.npix) || nl::linfit_ml_supported(mode, n, a.npix)))
         return Engine::LinfitMaps;
+    if (a.reject_map && kind == PassKind::DeepMaps && fast && h->d_fb_list && h->d_gen_list &&
+        (mode == NL_ST_SIGMA || mode == NL_ST_WINSOR_SIGMA) && !weighted && nl::fast_ml_supported(mode, false, n, a.npix))
+        return Engine::SigmaDeepMaps;
     if (a.reject_map) return Engine::ExactColumns;      // a maps pass: the one engine that carries the per-pixel counts out of every mode
     if (fast && mode == NL_ST_MEDIAN && nl::fast_supported(mode, weighted, n, a.npix)) return Engine::MedianRegisters;
     if (fast && mode == NL_ST_MEDIAN && nl::fast_ml_supported(mode, weighted, n, a.npix)) return Engine::MedianMultiLane;
@@ -562,6 +569,34 @@ static int run_sigma_fast_maps(nl_stack *h, const PassSetup &p, PassFacts *facts
     return NL_OK;
 }
 
+// The deep maps pass (include/nlstack_deepmaps.h) where the LDS-column sigma kernels exist: unweighted sigma / winsorized
+// clipping of 129 ... 512 frames.  The kernels of run_sigma_fast's multi-lane branch in their MAPS instantiations
+// (stack_fast_mlz_maps_*.hip, stack_fast_mlg.hip), each storing a pixel's two clip counts beside its result, in the PLAIN
+// protocol on the handle's one stream -- no fused protocol or tail, no side stream, no threshold record (a.bounds stays
+// null), no hints read or left:
+//   1. the dominant kernel of the frame-count class over the tile,
+//   2. the generic kernel over the generic list, on the grid ml_generic_grid(n, 0),
+//   3. the column kernel's MAPS instantiation over the exact list, once, behind both of them,
+//   4. the reduction of the sharded clip counters.
+// Every pixel's word of the map is written by exactly one of 1 - 3: by the lane that stores its result.  The two list
+// lengths stay in the scratch set, as run_sigma_fast_maps leaves them: nl_stack_finish takes no hints from this pass.
+static int run_sigma_deep_maps(nl_stack *h, const PassSetup &p, PassFacts *facts)
+{
+    const bool winsor = p.mode == NL_ST_WINSOR_SIGMA;
+    const nl::StackArgs &a = p.a;
+    nl::FastArgs f = list_args(h, true, true);          // (no snapshot cell, no hint: fixed grids)
+    if (winsor) (void)winsor_setup(h, a.n_frames, f, false);      // (the round cap of the generic pass, as run_sigma_fast sets it)
+    NL_HIP(nl::launch_stack_sigma_mlz_maps(a, nl::whole_tile(f), h->stream, &h->last_kernel, winsor));
+    if (p.timed) NL_HIP(hipEventRecord(h->ev_dom1, h->stream));
+    NL_HIP(nl::launch_stack_sigma_mlg_maps(a, nl::over_generic_list(nl::whole_tile(f)), h->stream, winsor));
+    const int rc = replay_list(h, p.mode, false, a, true);
+    if (rc != NL_OK) return rc;
+    NL_HIP(nl::launch_reduce_counters(h->d_partial, nl::kClipSlots, h->d_counters, h->stream));
+    facts->has_counters = true;
+    facts->used_fast = true;
+    return NL_OK;
+}
+
 // The resident maps pass of the linear fit (include/nlstack_residentmaps.h): run_listed's linear-fit branch with the MAPS
 // instantiations of its kernels (stack_linfit_maps.hip) and the column kernel's MAPS replay -- the same plain protocol on
 // the handle's one stream, the same cascade, quotas and grids:
@@ -744,7 +779,7 @@ static int run_clip_weighted(nl_stack *h, const PassSetup &p, PassFacts *facts)
 static int run_async_impl(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc, PassKind kind);
 
 // what a pass that failed half-way leaves behind (nl_stack_run_async, nl::stack_run_maps_async, nl::stack_run_maps_fast_async,
-// nl::stack_run_maps_resident_async,
+// nl::stack_run_maps_resident_async, nl::stack_run_maps_deep_async,
 // nl_stack_run_linfit_weighted_async, nl_stack_run_clip_weighted_async)
 static int settle_failed_pass(nl_stack_t *h, int rc)
 {
@@ -778,14 +813,16 @@ int nl_stack_run_async(nl_stack_t *h, int mode, float sigma_low, float sigma_hig
 // PassKind::FastMaps (nl_stack_run_maps_fast) is a maps pass that select_engine may give to run_sigma_fast_maps: it has
 // lists, but keeps all of the above (plain protocol, no hints either way).  PassKind::ResidentMaps
 // (nl_stack_run_maps_resident) is that pass with one more engine, run_linfit_maps for the linear fit, under the same rules;
-// the linear fit drops the handle's weights here as in every other unweighted entry (stack.go:158).
+// the linear fit drops the handle's weights here as in every other unweighted entry (stack.go:158).  PassKind::DeepMaps
+// (nl_stack_run_maps_deep) is that pass again with one more engine, run_sigma_deep_maps for unweighted sigma / winsorized
+// clipping of 129 ... 512 frames, under the same rules.
 // The same holds for the weighted linear-fit pass (PassKind::WeightedLinfit; `mode` is NL_ST_LINEAR_FIT), which keeps the
 // weights the default linear fit drops and runs on run_linfit_weighted, and for the weighted clip pass whose weights follow
 // their frames (PassKind::WeightedClip; `mode` resolves to sigma or winsorized sigma), which runs on run_clip_weighted.
 static int run_async_impl(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc, PassKind kind)
 {
     NL_CHECK_HANDLE(h);
-    const bool maps = kind == PassKind::Maps || kind == PassKind::FastMaps || kind == PassKind::ResidentMaps, wlinfit = kind == PassKind::WeightedLinfit;
+    const bool maps = kind == PassKind::Maps || kind == PassKind::FastMaps || kind == PassKind::ResidentMaps || kind == PassKind::DeepMaps, wlinfit = kind == PassKind::WeightedLinfit;
     const bool wclip = kind == PassKind::WeightedClip;
     if (wclip && !h->has_weights)
         return fail(NL_ERR_INVALID_ARG, "run_clip_weighted: the handle has no weights (nl_stack_set_weights); "
@@ -889,6 +926,7 @@ static int run_async_impl(nl_stack_t *h, int mode, float sigma_low, float sigma_
     case Engine::SigmaFast:       rc = run_sigma_fast(h, p, &facts); break;
     case Engine::SigmaFastMaps:   rc = run_sigma_fast_maps(h, p, &facts); break;
     case Engine::LinfitMaps:      rc = run_linfit_maps(h, p, &facts); break;
+    case Engine::SigmaDeepMaps:   rc = run_sigma_deep_maps(h, p, &facts); break;
     case Engine::WeightedTile:    rc = run_weighted_tile(h, p, &facts); break;
     case Engine::DenseReplay:     rc = run_dense_replay(h, p, &facts); break;
     case Engine::ExactColumns:    rc = run_exact_columns(h, p, &facts); break;
@@ -953,6 +991,12 @@ int nl::stack_run_maps_fast_async(nl_stack_t *h, int mode, float sigma_low, floa
 int nl::stack_run_maps_resident_async(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc)
 {
     return settle_failed_pass(h, run_async_impl(h, mode, sigma_low, sigma_high, ref_loc, PassKind::ResidentMaps));
+}
+
+// the deep maps pass (include/nlstack_deepmaps.h)
+int nl::stack_run_maps_deep_async(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc)
+{
+    return settle_failed_pass(h, run_async_impl(h, mode, sigma_low, sigma_high, ref_loc, PassKind::DeepMaps));
 }
 
 // nl_stack_finish, and the two planes of the map (of either kind of maps pass).  The packed words come down in ONE copy and are split here: the same
@@ -1039,6 +1083,15 @@ int nl_stack_run_maps_resident(nl_stack_t *h, int mode, float sigma_low, float s
                                uint16_t *reject_low_host, uint16_t *reject_high_host)
 {
     const int rc = nl::stack_run_maps_resident_async(h, mode, sigma_low, sigma_high, ref_loc);
+    if (rc != NL_OK) return rc;
+    return nl::stack_finish_maps(h, out_host, clip_low, clip_high, reject_low_host, reject_high_host);
+}
+
+int nl_stack_run_maps_deep(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc,
+                           float *out_host, int64_t *clip_low, int64_t *clip_high,
+                           uint16_t *reject_low_host, uint16_t *reject_high_host)
+{
+    const int rc = nl::stack_run_maps_deep_async(h, mode, sigma_low, sigma_high, ref_loc);
     if (rc != NL_OK) return rc;
     return nl::stack_finish_maps(h, out_host, clip_low, clip_high, reject_low_host, reject_high_host);
 }

@@ -71,4 +71,30 @@ hipError_t launch_stack_sigma_mlg(const StackArgs &args, const FastArgs &fargs, 
     return L.err;
 }
 
+// the MAPS instantiations for 129 ... 512 frames (2 or 4 lanes per pixel): the generic pass of the deep maps pass
+// (include/nlstack_deepmaps.h).  mlg_body's one store of a pixel's word sits beside the store of its result, under
+// `on && role == 0`: one lane of the 2 or 4 that hold the pixel, which all carry the same counts.
+template <int LPP, bool WINSOR>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2)))
+void stack_sigma_mlg_lanes_maps_kernel(StackArgs p, FastArgs q)
+{
+    static_assert(LPP == 2 || LPP == 4, "one lane per pixel: stack_fast_maps_impl.hpp");
+    mlg_body<LPP, WINSOR, true>(p, q, blockIdx.x, gridDim.x);
+}
+
+// over fargs.in_list, args.reject_map set; the list's length is only known on the device and a maps pass reads no hint:
+// the grid of launch_stack_sigma_mlg without one, ml_generic_grid(n, 0)
+hipError_t launch_stack_sigma_mlg_maps(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, bool winsor)
+{
+    if (!args.reject_map || args.n_frames <= kMlNS || args.n_frames > 4 * kMlNS) return hipErrorInvalidValue;
+    Launcher L(stream);
+    const unsigned grid = ml_generic_grid(args.n_frames, 0);
+    with_bool(winsor, [&](auto W) {
+        with_ml_lanes(args.n_frames, [&](auto LPP) {
+            L(stack_sigma_mlg_lanes_maps_kernel<decltype(LPP)::value, decltype(W)::value>, grid, 64, 0, args, fargs);
+        });
+    });
+    return L.err;
+}
+
 }  // namespace nl

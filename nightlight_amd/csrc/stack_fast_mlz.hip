@@ -8,6 +8,11 @@ bool launch_mlz_part_a(int ntop, bool winsor, const StackArgs &args, const FastA
 bool launch_mlz_part_b(int ntop, bool winsor, const StackArgs &args, const FastArgs &f, Launcher &L, const char **name);
 bool launch_mlz_part_c(int ntop, bool winsor, const StackArgs &args, const FastArgs &f, Launcher &L, const char **name);
 bool launch_mlz_part_d(int ntop, bool winsor, const StackArgs &args, const FastArgs &f, Launcher &L, const char **name);
+// (stack_fast_mlz_maps_{a,b,c,d}.hip: the MAPS instantiations of the same classes)
+bool launch_mlz_maps_part_a(int ntop, bool winsor, const StackArgs &args, const FastArgs &f, Launcher &L, const char **name);
+bool launch_mlz_maps_part_b(int ntop, bool winsor, const StackArgs &args, const FastArgs &f, Launcher &L, const char **name);
+bool launch_mlz_maps_part_c(int ntop, bool winsor, const StackArgs &args, const FastArgs &f, Launcher &L, const char **name);
+bool launch_mlz_maps_part_d(int ntop, bool winsor, const StackArgs &args, const FastArgs &f, Launcher &L, const char **name);
 
 int fast_mlz_supported(int mode, bool weighted, int n_frames)
 {
@@ -30,6 +35,21 @@ hipError_t launch_stack_sigma_mlz(const StackArgs &args, const FastArgs &fargs, 
     const int ntop = (args.n_frames + 15) / 16 * 16;
     const bool ok = launch_mlz_part_a(ntop, winsor, args, f, L, name) || launch_mlz_part_b(ntop, winsor, args, f, L, name) ||
                     launch_mlz_part_c(ntop, winsor, args, f, L, name) || launch_mlz_part_d(ntop, winsor, args, f, L, name);
+    return ok ? L.err : hipErrorInvalidValue;
+}
+
+// the same launch with the MAPS instantiation of the class (the deep maps pass, include/nlstack_deepmaps.h): every pixel
+// the kernel decides gets its word of args.reject_map beside its result; never a record-only pass
+hipError_t launch_stack_sigma_mlz_maps(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name,
+                                       bool winsor)
+{
+    if (!args.reject_map || fargs.record_only || !fast_mlz_supported(winsor ? NL_ST_WINSOR_SIGMA : NL_ST_SIGMA, false, args.n_frames))
+        return hipErrorInvalidValue;
+    Launcher L(stream);
+    const FastArgs f = whole_tile(fargs);
+    const int ntop = (args.n_frames + 15) / 16 * 16;
+    const bool ok = launch_mlz_maps_part_a(ntop, winsor, args, f, L, name) || launch_mlz_maps_part_b(ntop, winsor, args, f, L, name) ||
+                    launch_mlz_maps_part_c(ntop, winsor, args, f, L, name) || launch_mlz_maps_part_d(ntop, winsor, args, f, L, name);
     return ok ? L.err : hipErrorInvalidValue;
 }
 

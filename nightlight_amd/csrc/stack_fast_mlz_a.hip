@@ -6,7 +6,7 @@ namespace nl {
 
 bool launch_mlz_part_a(int ntop, bool winsor, const StackArgs &args, const FastArgs &f, Launcher &L, const char **name)
 {
-    return launch_mlz_classes<2, 144, 160, 176, 192, 208, 224, 240, 256>(ntop, winsor, args, f, L, name);
+    return launch_mlz_classes<2, false, 144, 160, 176, 192, 208, 224, 240, 256>(ntop, winsor, args, f, L, name);
 }
 
 }  // namespace nl

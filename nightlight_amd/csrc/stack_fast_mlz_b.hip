@@ -6,7 +6,7 @@ namespace nl {
 
 bool launch_mlz_part_b(int ntop, bool winsor, const StackArgs &args, const FastArgs &f, Launcher &L, const char **name)
 {
-    return launch_mlz_classes<4, 272, 288, 304, 320, 336, 352>(ntop, winsor, args, f, L, name);
+    return launch_mlz_classes<4, false, 272, 288, 304, 320, 336, 352>(ntop, winsor, args, f, L, name);
 }
 
 }  // namespace nl

@@ -6,7 +6,7 @@ namespace nl {
 
 bool launch_mlz_part_c(int ntop, bool winsor, const StackArgs &args, const FastArgs &f, Launcher &L, const char **name)
 {
-    return launch_mlz_classes<4, 368, 384, 400, 416, 432>(ntop, winsor, args, f, L, name);
+    return launch_mlz_classes<4, false, 368, 384, 400, 416, 432>(ntop, winsor, args, f, L, name);
 }
 
 }  // namespace nl

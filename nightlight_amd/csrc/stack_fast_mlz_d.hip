@@ -6,7 +6,7 @@ namespace nl {
 
 bool launch_mlz_part_d(int ntop, bool winsor, const StackArgs &args, const FastArgs &f, Launcher &L, const char **name)
 {
-    return launch_mlz_classes<4, 448, 464, 480, 496, 512>(ntop, winsor, args, f, L, name);
+    return launch_mlz_classes<4, false, 448, 464, 480, 496, 512>(ntop, winsor, args, f, L, name);
 }
 
 }  // namespace nl

@@ -53,10 +53,14 @@ template <int LPP>
 constexpr int mlz_block = LPP == 2 ? 128 : 256;     // threads per workgroup
 
 // NTOP: ranks in use (the frame count rounded up to a multiple of 16; NT for a stack that fills its lanes)
-template <int LPP, bool WINSOR, int NTOP>
+// ROOMY (the deep maps pass only, NTOP == NT): the layout of the classes that do NOT fill their lanes -- columns for 23
+// missing samples instead of 15, a full merge instead of the selection front end -- for stacks of NT - 15 ... NT - 1
+// frames, which are up to 15 samples short before the first NaN (see launch_mlz_classes)
+template <int LPP, bool WINSOR, int NTOP, bool ROOMY = false>
 struct MlzLayout {
     static constexpr int NS = kMlNS, NT = NS * LPP;
-    static constexpr bool FULL = NTOP == NT;                    // the columns sit at the ends of lanes
+    static_assert(!ROOMY || NTOP == NT, "only the class that fills its lanes has a second layout");
+    static constexpr bool FULL = NTOP == NT && !ROOMY;          // the columns sit at the ends of lanes
     // a lane is dealt at most NTOP / LPP frames: its positions from there on hold +Inf, the in-lane sort is the
     // network of the next tabulated size (sort_tables.inc: 80, 96, 112, 128)
     static constexpr int NSL = NTOP / LPP <= 80 ? 80 : (NTOP / LPP <= 96 ? 96 : (NTOP / LPP <= 112 ? 112 : 128));
@@ -352,13 +356,18 @@ __device__ __forceinline__ void lds_settle() { asm volatile("s_waitcnt lgkmcnt(0
 #define NL_MLZ_WINSOR_WAVES 2
 #endif
 // (PHASE is always 0: the rocprofv3 name stack_sigma_mlz_kernel<L, W, N, 0> keys the measured traffic of profiles/r0*_traffic.json in bench.py)
-template <int LPP, bool WINSOR, int NTOP, int PHASE = 0>
+// MAPS: the deep maps pass (include/nlstack_deepmaps.h, stack_fast_mlz_maps_*.hip) -- the lane that stores a pixel's result
+// also stores its two clip counts, low | high << 16, in p.reject_map[pix]; a pixel handed to the generic or the exact list
+// stores nothing (whoever decides it writes its word).  No other instantiation reads p.reject_map.
+// ROOMY (MAPS only): MlzLayout's second layout of the class that fills its lanes; the kernel itself is the same.
+template <int LPP, bool WINSOR, int NTOP, int PHASE = 0, bool MAPS = false, bool ROOMY = false>
 __global__ __launch_bounds__(mlz_block<LPP>)
 __attribute__((amdgpu_waves_per_eu(WINSOR ? NL_MLZ_WINSOR_WAVES : 3, 8)))
 void stack_sigma_mlz_kernel(StackArgs p, FastArgs q)
 {
     static_assert(PHASE == 0, "one kernel per pass");
-    using L = MlzLayout<LPP, WINSOR, NTOP>;
+    static_assert(!ROOMY || MAPS, "the default pass runs one layout per class");
+    using L = MlzLayout<LPP, WINSOR, NTOP, ROOMY>;
     using V = MlzRows<L>;
     constexpr int NS = L::NS, PW = L::PW, KL = L::KL, KH = L::KH, CR = L::CR, H0 = L::H0, W0 = L::W0;
     __shared__ float lds[L::ROWS * PW];
@@ -842,6 +851,7 @@ void stack_sigma_mlz_kernel(StackArgs p, FastArgs q)
     const bool rep = on && role == 0 && !rec;
     if (rep && !to_generic && !to_exact) {
         NL_STORE_RESULT(&p.out[pix], res);
+        if constexpr (MAPS) p.reject_map[pix] = (unsigned)c_lo | ((unsigned)c_hi << 16);
         c_lo_total += c_lo;
         c_hi_total += c_hi;
     }
@@ -917,8 +927,25 @@ void stack_sigma_mlz_kernel(StackArgs p, FastArgs q)
 
 constexpr char kMlzName[] = "stack_sigma_mlz_kernel";
 
-// launches the kernel of frame-count class `ntop` if it is one of this translation unit's (consecutive multiples of 16)
-template <int LPP, int FIRST, int... MORE>
+// the default pass's display name of the same instantiation with "maps" as its last argument (maps_kernel_name,
+// stack_fast_maps_impl.hpp)
+template <int LPP, bool WINSOR, int NTOP>
+const char *mlz_maps_kernel_name()
+{
+    static const std::string name = [] {
+        std::string s = kernel_name<kMlzName, LPP, WINSOR, NTOP, 0>();
+        s.pop_back();
+        return s + ", maps>";
+    }();
+    return name.c_str();
+}
+
+// launches the kernel of frame-count class `ntop` if it is one of this translation unit's (consecutive multiples of 16);
+// MAPS: its MAPS instantiation (stack_fast_mlz_maps_*.hip).  A stack of 241 ... 255 or 497 ... 511 frames runs the class that
+// fills its lanes, whose columns take 15 missing samples -- and is up to 15 short already: at 497 frames every pixel with
+// one NaN goes to the generic pass (measured: 904 of 943 pixels of tests/test_gpu_deepmaps.py, 84 at 496 and at 512).
+// The default pass lives with that; a MAPS pass of such a stack runs the class's ROOMY layout instead (23 missing samples).
+template <int LPP, bool MAPS, int FIRST, int... MORE>
 static bool launch_mlz_classes(int ntop, bool winsor, const StackArgs &args, const FastArgs &f, Launcher &L, const char **name)
 {
     if (ntop < FIRST || ntop > std::max({FIRST, MORE...})) return false;
@@ -927,8 +954,16 @@ static bool launch_mlz_classes(int ntop, bool winsor, const StackArgs &args, con
             constexpr bool WINSOR = decltype(W)::value;
             constexpr int NTOP = decltype(C)::value;
             using LY = MlzLayout<LPP, WINSOR, NTOP>;
-            *name = kernel_name<kMlzName, LPP, WINSOR, NTOP, 0>();
-            L(stack_sigma_mlz_kernel<LPP, WINSOR, NTOP>, (unsigned)((args.npix + LY::PW - 1) / LY::PW), LY::BLOCK, 0, args, f);
+            if constexpr (MAPS) *name = mlz_maps_kernel_name<LPP, WINSOR, NTOP>();
+            else                *name = kernel_name<kMlzName, LPP, WINSOR, NTOP, 0>();
+            if constexpr (MAPS && NTOP == kMlNS * LPP) {
+                if (args.n_frames < NTOP) {
+                    using LR = MlzLayout<LPP, WINSOR, NTOP, true>;
+                    L(stack_sigma_mlz_kernel<LPP, WINSOR, NTOP, 0, true, true>, (unsigned)((args.npix + LR::PW - 1) / LR::PW), LR::BLOCK, 0, args, f);
+                    return;
+                }
+            }
+            L(stack_sigma_mlz_kernel<LPP, WINSOR, NTOP, 0, MAPS>, (unsigned)((args.npix + LY::PW - 1) / LY::PW), LY::BLOCK, 0, args, f);
         });
     });
     return true;

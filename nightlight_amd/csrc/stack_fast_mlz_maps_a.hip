@@ -1,0 +1,13 @@
+// stack_fast_mlz_maps_a.hip -- the MAPS instantiations of the LDS-column sigma / winsor kernels (stack_fast_mlz_impl.hpp) of
+// the frame-count classes 144 .. 256 (2 lanes per pixel): the dominant kernels of the deep maps pass
+// (include/nlstack_deepmaps.h); units of their own beside stack_fast_mlz_a.hip, which instantiates exactly what it did
+#include "stack_fast_mlz_impl.hpp"
+
+namespace nl {
+
+bool launch_mlz_maps_part_a(int ntop, bool winsor, const StackArgs &args, const FastArgs &f, Launcher &L, const char **name)
+{
+    return launch_mlz_classes<2, true, 144, 160, 176, 192, 208, 224, 240, 256>(ntop, winsor, args, f, L, name);
+}
+
+}  // namespace nl

@@ -133,6 +133,8 @@ int stack_finish_maps(nl_stack_t *h, float *out_host, int64_t *clip_low, int64_t
 int stack_run_maps_fast_async(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc);
 // the first half of nl_stack_run_maps_resident (include/nlstack_residentmaps.h); stack_finish_maps finishes it as well
 int stack_run_maps_resident_async(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc);
+// the first half of nl_stack_run_maps_deep (include/nlstack_deepmaps.h); stack_finish_maps finishes it as well
+int stack_run_maps_deep_async(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc);
 
 // Bisection of the goal-seek (spec: internal/ops/stack/stackfindsigma.go:48-98): sigma_low and
 // sigma_high in [1,11], percentages in the reference's fp32 arithmetic, 21 passes at most.
@@ -249,6 +251,12 @@ hipError_t launch_stack_sigma_mlg(const StackArgs &args, const FastArgs &fargs, 
 int fast_mlz_supported(int mode, bool weighted, int n_frames);
 hipError_t launch_stack_sigma_mlz(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name,
                                   bool winsor);
+// ---- stack_fast_mlz_maps_{a,b,c,d}.hip / stack_fast_mlg.hip: the two parts of the deep maps pass (include/nlstack_deepmaps.h),
+// unweighted sigma / winsorized clipping of 129 ... 512 frames, args.reject_map set.  As the two launches above with one
+// more store per pixel, its two clip counts; no hints: the generic part runs the grid ml_generic_grid(n, 0) ----
+hipError_t launch_stack_sigma_mlz_maps(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name,
+                                       bool winsor);
+hipError_t launch_stack_sigma_mlg_maps(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, bool winsor);
 // sigma / winsorized clipping of 2 ... 128 frames, in the two parts a pass enqueues them.  Dominant part: the zonal kernel
 // (network size 8: the generic kernel over the whole tile), dominant_done (optional) recorded behind it, and for winsorized
 // stacks the continuation stages of the cascade.  Generic part: the pass over the generic list (network size 8: nothing);

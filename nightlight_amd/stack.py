@@ -188,6 +188,24 @@ class StackHandle:
                                                         _u16ptr(reject_low), _u16ptr(reject_high)))
         return out, cl.value, ch.value, reject_low, reject_high
 
+    def run_maps_deep(self, mode, sigma_low=2.75, sigma_high=2.75, ref_loc=0.0, out=None, reject_low=None,
+                      reject_high=None):
+        """run_maps_resident with the deep sigma / winsorized stacks on their own engines as well
+        (nl_stack_run_maps_deep, include/nlstack_deepmaps.h): unweighted sigma / winsorized clipping of 129 ... 512
+        frames on the LDS-column kernels of the default pass -- the result is then the default pass's -- and the pass
+        of run_maps_resident everywhere else.  Arguments and return value are those of run_maps."""
+        n = self.width * self.height
+        out = np.zeros(n, np.float32) if out is None else out
+        reject_low = np.zeros(n, np.uint16) if reject_low is None else reject_low
+        reject_high = np.zeros(n, np.uint16) if reject_high is None else reject_high
+        for a, t in ((out, np.float32), (reject_low, np.uint16), (reject_high, np.uint16)):
+            assert a.dtype == t and a.size == n and a.flags.c_contiguous
+        cl, ch = C.c_int64(0), C.c_int64(0)
+        capi.check(self._lib.nl_stack_run_maps_deep(self._h, int(mode), C.c_float(sigma_low), C.c_float(sigma_high),
+                                                    C.c_float(ref_loc), capi.fptr(out), C.byref(cl), C.byref(ch),
+                                                    _u16ptr(reject_low), _u16ptr(reject_high)))
+        return out, cl.value, ch.value, reject_low, reject_high
+
     def run_linfit_weighted(self, sigma_low=2.75, sigma_high=2.75, ref_loc=0.0, out=None, fetch=True):
         """One pass of the weighted linear fit (include/nlstack_wlinfit.h; an EXTENSION, the reference's fit takes
         no weights): the reference's linear-fit rejection, then the mean of the survivors with the weights of
@@ -732,6 +750,16 @@ class StackGroup:
         capi.check(self._lib.nl_group_run_maps_resident(self._g, int(mode), C.c_float(sigma_low), C.c_float(sigma_high),
                                                         C.c_float(ref_loc), capi.fptr(out), C.byref(cl), C.byref(ch),
                                                         _u16ptr(lo), _u16ptr(hi)))
+        return out, cl.value, ch.value, lo, hi
+
+    def run_maps_deep(self, mode, sigma_low=2.75, sigma_high=2.75, ref_loc=0.0):
+        """StackHandle.run_maps_deep over the tiles (nl_group_run_maps_deep): the return value of run_maps."""
+        n = self.width * self.height
+        out, lo, hi = np.zeros(n, np.float32), np.zeros(n, np.uint16), np.zeros(n, np.uint16)
+        cl, ch = C.c_int64(0), C.c_int64(0)
+        capi.check(self._lib.nl_group_run_maps_deep(self._g, int(mode), C.c_float(sigma_low), C.c_float(sigma_high),
+                                                    C.c_float(ref_loc), capi.fptr(out), C.byref(cl), C.byref(ch),
+                                                    _u16ptr(lo), _u16ptr(hi)))
         return out, cl.value, ch.value, lo, hi
 
     def run_linfit_weighted(self, sigma_low=2.75, sigma_high=2.75, ref_loc=0.0, download=True):

@@ -30,6 +30,21 @@
         the column maps pass      nl_stack_run_maps, every host pointer NULL
       with the cascade's list lengths and the exact list's.  A frame count whose handle cannot be made (memory) is
       reported and skipped.  DIR receives the lines as linfitmaps_probe.txt.
+
+  python tools/maps_probe.py --deep [--deep-workloads 512x4096x4096:2,256x4096x4096:2,512x4096x512:3 --sigma 3 --reps 20
+                                     --column-reps 3 --out DIR]
+      The deep maps pass (include/nlstack_deepmaps.h) beside the passes it sits next to.  Per workload
+      FRAMESxWIDTHxHEIGHT:MODE (sigma or winsorized clipping of 129 ... 512 frames) ONE handle, and on it, INTERLEAVED --
+      one run of each per repetition, so that a drift of the box meets all of them alike -- the same statistics, whole
+      pass and dominant kernel, of:
+        the default pass          nl_stack_run, twice, the second run timed (behind a plain-protocol pass a fused
+                                  pass first clears both scratch sets: the second run is the pass in its steady state)
+        the plain default pass    nl_stack_run under developer switch 1 (memset before, reduction kernel after: the
+                                  protocol class of the deep maps pass; its dominant kernel is the plain twin)
+        the deep maps pass        nl_stack_run_maps_deep, every host pointer NULL
+        the column maps pass      nl_stack_run_maps, every host pointer NULL; in the first --column-reps repetitions only
+      with the two hand-over list lengths of the deep maps pass.  A workload whose handle cannot be made (memory) is
+      reported and skipped.  DIR receives the lines as deepmaps_probe.txt, workload by workload as they finish.
 """
 import argparse
 import os
@@ -165,11 +180,105 @@ def linfit(a):
             f.write(text + "\n")
 
 
+def deep(a):
+    import nightlight_amd as nl
+    from nightlight_amd import capi
+    L = capi.load()
+    warm = 3
+    lines = []
+
+    def emit(line):
+        print(line, flush=True)
+        lines.append(line)
+        if a.out:
+            os.makedirs(a.out, exist_ok=True)
+            with open(os.path.join(a.out, "deepmaps_probe.txt"), "w") as f:
+                f.write("\n".join(lines) + "\n")
+
+    try:
+        import torch
+        emit("device: %s" % torch.cuda.get_device_name(0))
+    except Exception:
+        pass
+    emit("sigma %.2f / %.2f, frames resident; per workload %d interleaved repetitions after %d warm-up runs (column maps pass: "
+         "%d after 1); GPU time of the whole pass" % (a.sigma, a.sigma, a.reps, warm, a.column_reps))
+    for spec in a.deep_workloads.split(","):
+        shape, mode = spec.split(":")
+        n, width, height = (int(x) for x in shape.split("x"))
+        mode = int(mode)
+        emit("-- %d frames of %d x %d, mode %d" % (n, width, height, mode))
+        try:
+            st = nl.StackHandle(n, width, height)
+        except capi.NlError as e:
+            emit("no handle of %d frames: %s" % (n, e))
+            continue
+        with st:
+            st.fill_synthetic(seed=7)
+
+            def default_pass():
+                st.run(mode, a.sigma, a.sigma, 0.0, fetch=False)
+                return st.pass_times(0)
+
+            def steady_default_pass():
+                # (twice, the second one timed: behind a plain-protocol pass a fused pass first clears both scratch sets)
+                default_pass()
+                return default_pass()
+
+            def plain_default_pass():
+                st.set_dev_flags(1)
+                try:
+                    return default_pass()
+                finally:
+                    st.set_dev_flags(0)
+
+            def deep_maps_pass():
+                capi.check(L.nl_stack_run_maps_deep(st._h, mode, a.sigma, a.sigma, 0.0, None, None, None, None, None))
+                return st.pass_times(0)
+
+            def column_maps_pass():
+                capi.check(L.nl_stack_run_maps(st._h, mode, a.sigma, a.sigma, 0.0, None, None, None, None, None))
+                return st.pass_times(0)
+
+            passes = (("default pass", steady_default_pass),("plain default pass", plain_default_pass),
+                      ("deep maps pass", deep_maps_pass), ("column maps pass", column_maps_pass))
+            times = {label: [] for label, _ in passes}
+            facts = {}
+            for r in range(-warm, a.reps):
+                for label, fn in passes:
+                    if label == "column maps pass" and not -1 <= r < a.column_reps:
+                        continue
+                    t = fn()
+                    if r >= 0:
+                        times[label].append(t)
+                    tail = "; protocol %d" % st.last_pass_protocol
+                    if label == "deep maps pass":
+                        tail += "; exact list %d, generic list %d" % (st.last_fallback_pixels, st.last_generic_pixels)
+                    facts[label] = (st.last_kernel_name, tail)
+            med, med_dom = {}, {}
+            for label, _ in passes:
+                ms, dom = [t[0] for t in times[label]], [t[1] for t in times[label]]
+                med[label], med_dom[label] = float(np.median(ms)), float(np.median(dom))
+                emit("%-19s %-50s %s (%d runs)%s; dominant kernel median %.3f ms, min %.3f ms"
+                     % (label, facts[label][0], stats(ms), len(ms), facts[label][1], med_dom[label], float(np.min(dom))))
+            emit("deep maps / default = %.3f; deep maps / plain default = %.3f (one more 4-byte store per %d bytes read: %.4f); "
+                 "column maps / deep maps = %.1f"
+                 % (med["deep maps pass"] / med["default pass"], med["deep maps pass"] / med["plain default pass"], 4 * n,
+                    1.0 + 1.0 / n, med["column maps pass"] / med["deep maps pass"]))
+            emit("dominant kernels, deep maps / plain default = %.4f, deep maps / default = %.4f; behind the dominant kernel: "
+                 "%.3f ms (deep maps), %.3f ms (plain default), %.3f ms (default)"
+                 % (med_dom["deep maps pass"] / med_dom["plain default pass"], med_dom["deep maps pass"] / med_dom["default pass"],
+                    med["deep maps pass"] - med_dom["deep maps pass"], med["plain default pass"] - med_dom["plain default pass"],
+                    med["default pass"] - med_dom["default pass"]))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--fastmaps", action="store_true")
     ap.add_argument("--linfit", action="store_true")
     ap.add_argument("--linfit-frames", default="128,32,256")
+    ap.add_argument("--deep", action="store_true")
+    ap.add_argument("--deep-workloads", default="512x4096x4096:2,256x4096x4096:2,512x4096x512:3")
+    ap.add_argument("--column-reps", type=int, default=3)
     ap.add_argument("--frames", type=int, default=128)
     ap.add_argument("--width", type=int, default=4096)
     ap.add_argument("--height", type=int, default=4096)
@@ -182,6 +291,8 @@ def main():
         return fastmaps(a)
     if a.linfit:
         return linfit(a)
+    if a.deep:
+        return deep(a)
     import nightlight_amd as nl
     from nightlight_amd import capi
     L = capi.load()
