@@ -285,14 +285,9 @@ def open_library(path):
     L.nl_group_last_mode.argtypes = [vp]
     _u16p = C.POINTER(C.c_uint16)
     _maps_args = [vp, C.c_int, C.c_float, C.c_float, C.c_float, _f32p, _i64p, _i64p, _u16p, _u16p]
-    L.nl_stack_run_maps.argtypes = _maps_args
-    L.nl_group_run_maps.argtypes = _maps_args
-    L.nl_stack_run_maps_fast.argtypes = _maps_args
-    L.nl_group_run_maps_fast.argtypes = _maps_args
-    L.nl_stack_run_maps_resident.argtypes = _maps_args
-    L.nl_group_run_maps_resident.argtypes = _maps_args
-    L.nl_stack_run_maps_deep.argtypes = _maps_args
-    L.nl_group_run_maps_deep.argtypes = _maps_args
+    for suffix in ("", "_fast", "_resident", "_deep"):
+        getattr(L, "nl_stack_run_maps" + suffix).argtypes = _maps_args
+        getattr(L, "nl_group_run_maps" + suffix).argtypes = _maps_args
     _wlinfit_args = [vp, C.c_float, C.c_float, C.c_float, _f32p, _i64p, _i64p]
     L.nl_stack_run_linfit_weighted.argtypes = _wlinfit_args
     L.nl_group_run_linfit_weighted.argtypes = _wlinfit_args

@@ -18,7 +18,7 @@
 #include <thread>
 #include <vector>
 
-#include "stack_kernels.h"
+#include "nlstack_internal.hpp"
 
 struct nl_group {
     int n_frames = 0, width = 0, height = 0;
@@ -301,12 +301,9 @@ int nl_group_run_clip_weighted(nl_group_t *g, int mode, float sigma_low, float s
                      out_host, clip_low, clip_high);
 }
 
-// nl_group_run with the maps (include/nlstack_maps.h; MapsEntry::Fast: include/nlstack_fastmaps.h; MapsEntry::Resident:
-// include/nlstack_residentmaps.h; MapsEntry::Deep: include/nlstack_deepmaps.h): the same protocol -- every pass
-// that was started is finished, the first error with its message is the caller's -- and every tile writes its own rows
-// of the three host buffers
-enum class MapsEntry { Column, Fast, Resident, Deep };
-static int group_run_maps(nl_group_t *g, MapsEntry entry, int mode, float sigma_low, float sigma_high, float ref_loc,
+// nl_group_run with the maps, on the tier of the entry (nl::MapsTier): the same protocol -- every pass that was started is
+// finished, the first error with its message is the caller's -- and every tile writes its own rows of the three host buffers
+static int group_run_maps(nl_group_t *g, nl::MapsTier tier, int mode, float sigma_low, float sigma_high, float ref_loc,
                           float *out_host, int64_t *clip_low, int64_t *clip_high,
                           uint16_t *reject_low_host, uint16_t *reject_high_host)
 {
@@ -318,10 +315,7 @@ static int group_run_maps(nl_group_t *g, MapsEntry entry, int mode, float sigma_
     };
     size_t started = 0;
     for (; started < g->tiles.size() && first_rc == NL_OK; started++)
-        note(entry == MapsEntry::Deep     ? nl::stack_run_maps_deep_async(g->tiles[started], mode, sigma_low, sigma_high, ref_loc)
-             : entry == MapsEntry::Resident ? nl::stack_run_maps_resident_async(g->tiles[started], mode, sigma_low, sigma_high, ref_loc)
-             : entry == MapsEntry::Fast   ? nl::stack_run_maps_fast_async(g->tiles[started], mode, sigma_low, sigma_high, ref_loc)
-                                          : nl::stack_run_maps_async(g->tiles[started], mode, sigma_low, sigma_high, ref_loc));
+        note(nl::stack_run_maps_async(g->tiles[started], tier, mode, sigma_low, sigma_high, ref_loc));
     if (first_rc != NL_OK) started--;                     // (a failing start settles its handle: nothing of it is in flight)
     const bool ok = first_rc == NL_OK;
     int64_t lo = 0, hi = 0;
@@ -354,7 +348,7 @@ int nl_group_run_maps(nl_group_t *g, int mode, float sigma_low, float sigma_high
                       float *out_host, int64_t *clip_low, int64_t *clip_high,
                       uint16_t *reject_low_host, uint16_t *reject_high_host)
 {
-    return group_run_maps(g, MapsEntry::Column, mode, sigma_low, sigma_high, ref_loc, out_host, clip_low, clip_high, reject_low_host,
+    return group_run_maps(g, nl::MapsTier::Column, mode, sigma_low, sigma_high, ref_loc, out_host, clip_low, clip_high, reject_low_host,
                           reject_high_host);
 }
 
@@ -362,7 +356,7 @@ int nl_group_run_maps_fast(nl_group_t *g, int mode, float sigma_low, float sigma
                            float *out_host, int64_t *clip_low, int64_t *clip_high,
                            uint16_t *reject_low_host, uint16_t *reject_high_host)
 {
-    return group_run_maps(g, MapsEntry::Fast, mode, sigma_low, sigma_high, ref_loc, out_host, clip_low, clip_high, reject_low_host,
+    return group_run_maps(g, nl::MapsTier::Fast, mode, sigma_low, sigma_high, ref_loc, out_host, clip_low, clip_high, reject_low_host,
                           reject_high_host);
 }
 
@@ -370,7 +364,7 @@ int nl_group_run_maps_resident(nl_group_t *g, int mode, float sigma_low, float s
                                float *out_host, int64_t *clip_low, int64_t *clip_high,
                                uint16_t *reject_low_host, uint16_t *reject_high_host)
 {
-    return group_run_maps(g, MapsEntry::Resident, mode, sigma_low, sigma_high, ref_loc, out_host, clip_low, clip_high,
+    return group_run_maps(g, nl::MapsTier::Resident, mode, sigma_low, sigma_high, ref_loc, out_host, clip_low, clip_high,
                           reject_low_host, reject_high_host);
 }
 
@@ -378,7 +372,7 @@ int nl_group_run_maps_deep(nl_group_t *g, int mode, float sigma_low, float sigma
                            float *out_host, int64_t *clip_low, int64_t *clip_high,
                            uint16_t *reject_low_host, uint16_t *reject_high_host)
 {
-    return group_run_maps(g, MapsEntry::Deep, mode, sigma_low, sigma_high, ref_loc, out_host, clip_low, clip_high,
+    return group_run_maps(g, nl::MapsTier::Deep, mode, sigma_low, sigma_high, ref_loc, out_host, clip_low, clip_high,
                           reject_low_host, reject_high_host);
 }
 

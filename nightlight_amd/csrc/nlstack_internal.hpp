@@ -1,4 +1,4 @@
-// nlstack_internal.hpp -- what the units of the C ABI (nlstack_api.hip, nlstack_pass.hip and, through
+// nlstack_internal.hpp -- what the units of the C ABI (nlstack_api.hip, nlstack_pass.hip, nlstack_group.hip and, through
 // nlstack_frame_common.hpp, nlstack_frame.hip, nlstack_frame_pre.hip, nlstack_frame_stretch.hip, nlstack_frame_rgb.hip)
 // share: the handle and the error state (the allocator and the scratch types: dev_memory.hpp).  Private: no kernel
 // source includes it, not installed.
@@ -52,6 +52,20 @@ int with_scratch_handle(int width, int height, int device, Run run)
 // the inverse of the forward Transform2D t (internal/star/coord.go:159-199, fp32 as written there); a singular one is
 // NL_ERR_INVALID_ARG "Matrix has no inverse" (nlstack_api.hip)
 int invert_transform(const float t[6], float inv[6]);
+
+// Which engines a maps pass may run on.  Ordered: every tier includes the ones below it.
+enum class MapsTier {
+    None,                 // no maps pass
+    Column,               // nl_stack_run_maps (include/nlstack_maps.h): the column kernel, every mode
+    Fast,                 // nl_stack_run_maps_fast (include/nlstack_fastmaps.h): and the register-resident sigma / winsorized kernels, 2 ... 128 frames
+    Resident,             // nl_stack_run_maps_resident (include/nlstack_residentmaps.h): and the linear fit's kernels and cascade
+    Deep,                 // nl_stack_run_maps_deep (include/nlstack_deepmaps.h): and the LDS-column sigma / winsorized kernels, 129 ... 512 frames
+};
+// the two halves of the four nl_stack_run_maps* entries (nlstack_pass.hip), so that the nl_group_run_maps* (nlstack_group.hip)
+// start every tile before they await any; a failing first half settles the handle as nl_stack_run_async does
+int stack_run_maps_async(nl_stack_t *h, MapsTier tier, int mode, float sigma_low, float sigma_high, float ref_loc);
+int stack_finish_maps(nl_stack_t *h, float *out_host, int64_t *clip_low, int64_t *clip_high, uint16_t *reject_low_host,
+                      uint16_t *reject_high_host);
 
 }  // namespace nl
 

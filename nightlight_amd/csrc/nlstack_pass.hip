@@ -170,6 +170,19 @@ static int auto_select_mode(int l)   // stack.go:45-55
 }
 
 // ---- one stack pass: run_async_impl sets it up, select_engine picks the engine that runs it ----------------------------
+//
+// The ladder of the maps passes (nl::MapsTier).  A maps pass is a plain-protocol pass whose kernels
+// also store each pixel's two clip counts in h->d_reject_map.  Its tier says on which engines it may run, and every tier
+// includes the ones below it:
+//   Column    (nl_stack_run_maps)           the one-pixel-per-lane column kernel, every mode but the mean;
+//   Fast      (nl_stack_run_maps_fast)      and run_sigma_maps on the register-resident sigma / winsorized kernels, 2 ... 128 frames;
+//   Resident  (nl_stack_run_maps_resident)  and run_listed's linear fit, on its own kernels and cascade;
+//   Deep      (nl_stack_run_maps_deep)      and run_sigma_maps on the LDS-column sigma / winsorized kernels, 129 ... 512 frames.
+// What no engine of its tier takes runs on the column kernel.  On every tier the pass takes part in none of what default
+// passes remember from one another: it takes and leaves no list-length hints, never runs the fused protocol, and leaves the
+// scratch sets as any other plain-protocol pass does; the linear fit drops the handle's weights as in every other
+// unweighted entry (stack.go:158).  One more engine with per-pixel counts is one predicate in select_engine and one
+// `maps` at its launch sites.
 
 // the engines, in the order select_engine tries them
 enum class Engine {
@@ -178,9 +191,7 @@ enum class Engine {
     MedianMultiLane,      // 129 ... 512 frames, 2 or 4 lanes per pixel
     Listed,               // MAD sigma / linear fit, one- or multi-lane: dominant kernel + bit-exact replay of its list
     SigmaFast,            // sigma / winsorized: dominant kernel + generic pass, replays of the pixels both hand over
-    SigmaFastMaps,        // the same kernels with the per-pixel counts, plain protocol (a fast or resident maps pass only)
-    LinfitMaps,           // the linear fit's kernels and cascade with the per-pixel counts (a resident or deep maps pass only)
-    SigmaDeepMaps,        // the LDS-column sigma kernels of 129 ... 512 frames with the per-pixel counts, plain protocol (a deep maps pass only)
+    SigmaMaps,            // the same kernels with the per-pixel counts, plain protocol (a maps pass from MapsTier::Fast on)
     WeightedTile,         // bit-exact replay, 64 consecutive pixels per wave with their columns in LDS
     DenseReplay,          // bit-exact wave-per-pixel replay over the whole tile (behind a decision pass where there is one)
     ExactColumns,         // bit-exact, one pixel per lane with its column in LDS: every mode, any depth
@@ -193,40 +204,33 @@ struct PassSetup {
     bool timed;               // the pass records its timing events (not with kDevUntimed)
     bool fused;               // fused protocol (fused_protocol_on; only the SigmaFast engine runs it)
     nl::StackArgs a;
-    bool maps = false;        // a maps pass (nl_stack_run_maps, nl_stack_run_maps_fast, nl_stack_run_maps_resident, nl_stack_run_maps_deep): a.reject_map is set
+    nl::MapsTier tier = nl::MapsTier::None;
+    bool maps() const { return tier != nl::MapsTier::None; }      // a maps pass: a.reject_map is set
 };
 
-// what kind of pass run_async_impl sets up
+// the passes that run on an engine of their own instead of select_engine's
 enum class PassKind {
-    Default,              // nl_stack_run_async
-    Maps,                 // nl_stack_run_maps (include/nlstack_maps.h)
-    FastMaps,             // nl_stack_run_maps_fast (include/nlstack_fastmaps.h): a maps pass on the default pass's engines where they exist
-    ResidentMaps,         // nl_stack_run_maps_resident (include/nlstack_residentmaps.h): FastMaps, and the linear fit on its own kernels and cascade
-    DeepMaps,             // nl_stack_run_maps_deep (include/nlstack_deepmaps.h): ResidentMaps, and sigma / winsorized clipping of 129 ... 512 frames on the LDS-column kernels
-    WeightedLinfit,       // nl_stack_run_linfit_weighted (include/nlstack_wlinfit.h): an engine of its own, run_linfit_weighted
-    WeightedClip,         // nl_stack_run_clip_weighted (include/nlstack_wclip.h): an engine of its own, run_clip_weighted
+    Default,              // nl_stack_run_async and, with a tier, the nl_stack_run_maps* entries
+    WeightedLinfit,       // nl_stack_run_linfit_weighted (include/nlstack_wlinfit.h): run_linfit_weighted
+    WeightedClip,         // nl_stack_run_clip_weighted (include/nlstack_wclip.h): run_clip_weighted
 };
 
-// Pure: allocates nothing, enqueues nothing.  The first engine whose condition holds runs the pass.
-// kind: a maps pass may run on the register-resident sigma kernels (PassKind::FastMaps, PassKind::ResidentMaps,
-// PassKind::DeepMaps), on the linear fit's (PassKind::ResidentMaps, PassKind::DeepMaps) and on the LDS-column sigma kernels
-// of 129 ... 512 frames (PassKind::DeepMaps).
-static Engine select_engine(const nl_stack *h, int mode, bool weighted, const nl::StackArgs &a, PassKind kind)
+// Pure: allocates nothing, enqueues nothing.  The first engine whose condition holds runs the pass.  tier: the ladder above.
+static Engine select_engine(const nl_stack *h, int mode, bool weighted, const nl::StackArgs &a, nl::MapsTier tier)
 {
-    const bool resident_maps = kind == PassKind::ResidentMaps || kind == PassKind::DeepMaps;
-    const bool fast_maps = kind == PassKind::FastMaps || resident_maps;
     const bool fast = !h->force_exact;
+    const bool clip = mode == NL_ST_SIGMA || mode == NL_ST_WINSOR_SIGMA;
     const int n = a.n_frames;
     if (mode == NL_ST_MEAN) return Engine::Mean;
-    if (a.reject_map && fast_maps && fast && h->d_fb_list && h->d_gen_list && (mode == NL_ST_SIGMA || mode == NL_ST_WINSOR_SIGMA) &&
+    if (a.reject_map && tier >= nl::MapsTier::Fast && fast && h->d_fb_list && h->d_gen_list && clip &&
         nl::fast_supported(mode, weighted, n, a.npix))
-        return Engine::SigmaFastMaps;
-    if (a.reject_map && resident_maps && fast && h->d_fb_list && mode == NL_ST_LINEAR_FIT &&
+        return Engine::SigmaMaps;
+    if (a.reject_map && tier >= nl::MapsTier::Resident && fast && h->d_fb_list && mode == NL_ST_LINEAR_FIT &&
         (nl::linfit_fast_supported(mode, n, a.npix) || nl::linfit_ml_supported(mode, n, a.npix)))
-        return Engine::LinfitMaps;
-    if (a.reject_map && kind == PassKind::DeepMaps && fast && h->d_fb_list && h->d_gen_list &&
-        (mode == NL_ST_SIGMA || mode == NL_ST_WINSOR_SIGMA) && !weighted && nl::fast_ml_supported(mode, false, n, a.npix))
-        return Engine::SigmaDeepMaps;
+        return Engine::Listed;
+    if (a.reject_map && tier >= nl::MapsTier::Deep && fast && h->d_fb_list && h->d_gen_list && clip && !weighted &&
+        nl::fast_ml_supported(mode, false, n, a.npix))
+        return Engine::SigmaMaps;
     if (a.reject_map) return Engine::ExactColumns;      // a maps pass: the one engine that carries the per-pixel counts out of every mode
     if (fast && mode == NL_ST_MEDIAN && nl::fast_supported(mode, weighted, n, a.npix)) return Engine::MedianRegisters;
     if (fast && mode == NL_ST_MEDIAN && nl::fast_ml_supported(mode, weighted, n, a.npix)) return Engine::MedianMultiLane;
@@ -265,9 +269,19 @@ static nl::FastArgs list_args(const nl_stack *h, bool exact_list, bool generic_l
     return f;
 }
 
-// the exact list (d_fb_list) replayed by the LDS-column kernel, kListLanes pixels per wave; maps: by its MAPS
-// instantiation, which also stores the listed pixels' words of a.reject_map
-static int replay_list(nl_stack *h, int mode, bool weighted, const nl::StackArgs &a, bool maps = false)
+// The column kernel (stack_exact.hip): its plain instantiations, the MAPS ones, which also store each pixel's word of
+// a.reject_map, or the <follow> ones of the weighted clip pass (one column: planned with weighted = false)
+enum class Columns { Plain, Maps, Follow };
+
+static hipError_t launch_columns(Columns variant, int mode, bool weighted, const nl::StackArgs &a, int lanes, int grid, size_t lds,
+                                 hipStream_t stream, const char **name)
+{
+    if (variant == Columns::Follow) return nl::launch_stack_exact_follow(mode, a, lanes, grid, lds, stream, name);
+    return nl::launch_stack_exact(mode, weighted, a, lanes, grid, lds, stream, name, variant == Columns::Maps);
+}
+
+// ... over the exact list (d_fb_list), kListLanes pixels per wave
+static int replay_list(nl_stack *h, int mode, bool weighted, const nl::StackArgs &a, Columns variant = Columns::Plain)
 {
     int lanes = 0;
     size_t lds = 0;
@@ -278,8 +292,23 @@ static int replay_list(nl_stack *h, int mode, bool weighted, const nl::StackArgs
     e.list_count = h->d_fb_count;
     e.list_capacity = (unsigned)h->npix;
     const char *exact_name = "";
-    if (maps) NL_HIP(nl::launch_stack_exact_maps(mode, weighted, e, lanes, kListGrid, lds, h->stream, &exact_name));
-    else      NL_HIP(nl::launch_stack_exact(mode, weighted, e, lanes, kListGrid, lds, h->stream, &exact_name));
+    NL_HIP(launch_columns(variant, mode, weighted, e, lanes, kListGrid, lds, h->stream, &exact_name));
+    return NL_OK;
+}
+
+// ... over the whole tile, as the dominant kernel of the pass: ev_dom1 is recorded behind it
+static int columns_over_tile(nl_stack *h, int mode, bool weighted, nl::StackArgs a, Columns variant = Columns::Plain)
+{
+    int lanes = 0;
+    size_t lds = 0;
+    if (nl::exact_plan(mode, weighted, a.n_frames, a.n_pad, 64, &lanes, &lds) != 0)
+        return weighted && mode == NL_ST_LINEAR_FIT
+                   ? fail(NL_ERR_TOO_MANY_FRAMES, "%d frames do not fit the per-pixel LDS columns of the weighted linear fit", a.n_frames)
+                   : fail(NL_ERR_TOO_MANY_FRAMES, "%d frames do not fit the per-pixel LDS column (mode %d)", a.n_frames, mode);
+    a.tiles = (a.npix + lanes - 1) / lanes;
+    const int grid = (int)(a.tiles < (int64_t)h->max_grid ? a.tiles : (int64_t)h->max_grid);
+    NL_HIP(launch_columns(variant, mode, weighted, a, lanes, grid, lds, h->stream, &h->last_kernel));
+    NL_HIP(hipEventRecord(h->ev_dom1, h->stream));
     return NL_OK;
 }
 
@@ -324,7 +353,7 @@ static int decision_pass(nl_stack *h, const PassSetup &p, nl::StackArgs &a)
 static int run_mean(nl_stack *h, const PassSetup &p, PassFacts *)
 {
     // (a maps pass: the mean rejects nothing)
-    if (p.maps) NL_HIP(hipMemsetAsync(p.a.reject_map, 0, (size_t)p.a.npix * sizeof(unsigned), h->stream));
+    if (p.maps()) NL_HIP(hipMemsetAsync(p.a.reject_map, 0, (size_t)p.a.npix * sizeof(unsigned), h->stream));
     NL_HIP(nl::launch_stack_mean(p.weighted, p.a, h->stream, &h->last_kernel));
     NL_HIP(hipEventRecord(h->ev_dom1, h->stream));
     return NL_OK;
@@ -343,7 +372,19 @@ static int run_median(nl_stack *h, const PassSetup &p, bool multi_lane)
     return NL_OK;
 }
 
-// MAD sigma / linear fit: register-resident, the exact kernel replays the pixels the dominant kernel lists
+// MAD sigma / linear fit: register-resident, the exact kernel replays the pixels the dominant kernel lists.
+// The linear fit of a maps pass (MapsTier::Resident and up) runs the same plain protocol on the handle's one stream, the same
+// cascade, quotas and grids, with the MAPS instantiations of its kernels (stack_linfit_maps.hip) and of the column kernel:
+//   1. the dominant kernel over the tile: every lane that does not hand its pixel to the exact list STORES the pixel's
+//      word of the map, p_lo | p_hi << 16, whether the pixel is finished or goes on;
+//   2. the continuation stages of the cascade: the lane that owns a listed pixel ADDS its stage's counts to that word
+//      (load, add, store: a pixel is on a stage's list at most once, the stages are ordered on the stream);
+//   3. the column kernel's MAPS instantiation over the exact list (the pixels with an infinite sample), which stores
+//      theirs: no stage touched them;
+//   4. the reduction of the sharded clip counters.
+// Every word is first written by exactly one plain store of 1. or 3.; 2. only adds to words this pass wrote: no memset,
+// no stale word of an earlier pass.  Both kernels are bit-exact, so the result is the bit-exact one as well.  The stage
+// lengths stay in d_lf_count and the exact list's in the scratch set, with or without the map.
 static int run_listed(nl_stack *h, const PassSetup &p, PassFacts *facts)
 {
     const nl::StackArgs &a = p.a;
@@ -362,11 +403,11 @@ static int run_listed(nl_stack *h, const PassSetup &p, PassFacts *facts)
         const nl::LinfitCascade *cas = linfit_cascade(h, &cascade);
         if (cas) NL_HIP(hipMemsetAsync(h->d_lf_count, 0, sizeof(unsigned) * nl::kLinfitCounters, h->stream));
         if (nl::linfit_ml_supported(p.mode, a.n_frames, a.npix))
-            NL_HIP(nl::launch_stack_linfit_ml(a, f, cas, h->stream, &h->last_kernel, h->ev_dom1));
+            NL_HIP(nl::launch_stack_linfit_ml(a, f, cas, h->stream, &h->last_kernel, h->ev_dom1, p.maps()));
         else
-            NL_HIP(nl::launch_stack_linfit_fast(a, f, cas, h->stream, &h->last_kernel, h->ev_dom1));
+            NL_HIP(nl::launch_stack_linfit_fast(a, f, cas, h->stream, &h->last_kernel, h->ev_dom1, p.maps()));
     }
-    const int rc = replay_list(h, p.mode, p.weighted, a);
+    const int rc = replay_list(h, p.mode, p.weighted, a, p.maps() ? Columns::Maps : Columns::Plain);
     if (rc != NL_OK) return rc;
     NL_HIP(nl::launch_reduce_counters(h->d_partial, nl::kClipSlots, h->d_counters, h->stream));
     facts->has_counters = true;
@@ -536,92 +577,33 @@ static int run_sigma_fast(nl_stack *h, const PassSetup &p, PassFacts *facts)
     return NL_OK;
 }
 
-// The fast maps pass (include/nlstack_fastmaps.h) where the register-resident sigma kernels exist: unweighted sigma /
-// winsorized clipping of 2 ... 128 frames.  The kernels of run_sigma_fast in their MAPS instantiations
-// (stack_fast_maps_impl.hpp), each lane storing its pixel's two clip counts beside its result, in the PLAIN protocol on the
-// handle's one stream -- no fused protocol or tail, no side stream, no cascade, no hints read or left:
-//   1. the dominant kernel over the tile (below 16 frames: the generic kernel over the whole tile, and 2. has nothing to do),
-//   2. the generic kernel over the generic list,
-//   3. the column kernel's MAPS instantiation over the exact list, once, behind both of them,
+// Sigma / winsorized clipping of a maps pass (MapsTier::Fast: 2 ... 128 frames, include/nlstack_fastmaps.h; MapsTier::Deep:
+// 129 ... 512 frames, include/nlstack_deepmaps.h), unweighted.  The kernels of run_sigma_fast in their MAPS instantiations
+// (stack_fast_maps_impl.hpp; stack_fast_mlz_maps_*.hip, stack_fast_mlg.hip), each lane storing its pixel's two clip counts
+// beside its result, in the PLAIN protocol on the handle's one stream -- no fused protocol or tail, no side stream, no
+// cascade, no threshold record (a.bounds stays null), no hints read or left:
+//   1. the dominant kernel over the tile -- up to 128 frames the register-resident one (below 16 frames: the generic kernel
+//      over the whole tile, and 2. has nothing to do), beyond that the LDS-column kernel of the frame-count class;
+//   2. the generic kernel over the generic list, on a fixed grid (beyond 128 frames: ml_generic_grid(n, 0));
+//   3. the column kernel's MAPS instantiation over the exact list, once, behind both of them;
 //   4. the reduction of the sharded clip counters.
 // Every pixel's word of the map is written by exactly one of 1 - 3: by the lane that stores its result.  The two list
 // lengths stay in the scratch set (as run_listed leaves them), where nl_stack_last_*_pixels read them: nothing sits
 // behind the totals, so nl_stack_finish takes no hints from this pass.
-static int run_sigma_fast_maps(nl_stack *h, const PassSetup &p, PassFacts *facts)
-{
-    const bool winsor = p.mode == NL_ST_WINSOR_SIGMA;
-    const nl::StackArgs &a = p.a;
-    nl::FastArgs f = list_args(h, true, true);          // (no snapshot cell, no hint: fixed grids)
-    if (winsor) (void)winsor_setup(h, a.n_frames, f, false);
-    const hipEvent_t dominant_done = p.timed ? h->ev_dom1 : nullptr;
-    if (winsor) {
-        NL_HIP(nl::launch_stack_winsor_maps_dominant(a, f, h->stream, &h->last_kernel, dominant_done));
-        NL_HIP(nl::launch_stack_winsor_maps_generic(a, f, h->stream));
-    } else {
-        NL_HIP(nl::launch_stack_sigma_maps_dominant(a, f, h->stream, &h->last_kernel, dominant_done));
-        NL_HIP(nl::launch_stack_sigma_maps_generic(a, f, h->stream));
-    }
-    const int rc = replay_list(h, p.mode, false, a, true);
-    if (rc != NL_OK) return rc;
-    NL_HIP(nl::launch_reduce_counters(h->d_partial, nl::kClipSlots, h->d_counters, h->stream));
-    facts->has_counters = true;
-    facts->used_fast = true;
-    return NL_OK;
-}
-
-// The deep maps pass (include/nlstack_deepmaps.h) where the LDS-column sigma kernels exist: unweighted sigma / winsorized
-// clipping of 129 ... 512 frames.  The kernels of run_sigma_fast's multi-lane branch in their MAPS instantiations
-// (stack_fast_mlz_maps_*.hip, stack_fast_mlg.hip), each storing a pixel's two clip counts beside its result, in the PLAIN
-// protocol on the handle's one stream -- no fused protocol or tail, no side stream, no threshold record (a.bounds stays
-// null), no hints read or left:
-//   1. the dominant kernel of the frame-count class over the tile,
-//   2. the generic kernel over the generic list, on the grid ml_generic_grid(n, 0),
-//   3. the column kernel's MAPS instantiation over the exact list, once, behind both of them,
-//   4. the reduction of the sharded clip counters.
-// Every pixel's word of the map is written by exactly one of 1 - 3: by the lane that stores its result.  The two list
-// lengths stay in the scratch set, as run_sigma_fast_maps leaves them: nl_stack_finish takes no hints from this pass.
-static int run_sigma_deep_maps(nl_stack *h, const PassSetup &p, PassFacts *facts)
+static int run_sigma_maps(nl_stack *h, const PassSetup &p, PassFacts *facts)
 {
     const bool winsor = p.mode == NL_ST_WINSOR_SIGMA;
     const nl::StackArgs &a = p.a;
     nl::FastArgs f = list_args(h, true, true);          // (no snapshot cell, no hint: fixed grids)
     if (winsor) (void)winsor_setup(h, a.n_frames, f, false);      // (the round cap of the generic pass, as run_sigma_fast sets it)
-    NL_HIP(nl::launch_stack_sigma_mlz_maps(a, nl::whole_tile(f), h->stream, &h->last_kernel, winsor));
-    if (p.timed) NL_HIP(hipEventRecord(h->ev_dom1, h->stream));
-    NL_HIP(nl::launch_stack_sigma_mlg_maps(a, nl::over_generic_list(nl::whole_tile(f)), h->stream, winsor));
-    const int rc = replay_list(h, p.mode, false, a, true);
-    if (rc != NL_OK) return rc;
-    NL_HIP(nl::launch_reduce_counters(h->d_partial, nl::kClipSlots, h->d_counters, h->stream));
-    facts->has_counters = true;
-    facts->used_fast = true;
-    return NL_OK;
-}
-
-// The resident maps pass of the linear fit (include/nlstack_residentmaps.h): run_listed's linear-fit branch with the MAPS
-// instantiations of its kernels (stack_linfit_maps.hip) and the column kernel's MAPS replay -- the same plain protocol on
-// the handle's one stream, the same cascade, quotas and grids:
-//   1. the dominant kernel over the tile: every lane that does not hand its pixel to the exact list STORES the pixel's
-//      word of the map, p_lo | p_hi << 16, whether the pixel is finished or goes on;
-//   2. the continuation stages of the cascade: the lane that owns a listed pixel ADDS its stage's counts to that word
-//      (load, add, store: a pixel is on a stage's list at most once, the stages are ordered on the stream);
-//   3. the column kernel's MAPS instantiation over the exact list (the pixels with an infinite sample), which stores
-//      theirs: no stage touched them;
-//   4. the reduction of the sharded clip counters.
-// Every word is first written by exactly one plain store of 1. or 3.; 2. only adds to words this pass wrote: no memset,
-// no stale word of an earlier pass.  Both kernels are bit-exact, so the result is the bit-exact one as well.  The stage
-// lengths stay in d_lf_count and the exact list's in the scratch set, as run_listed leaves them.
-static int run_linfit_maps(nl_stack *h, const PassSetup &p, PassFacts *facts)
-{
-    const nl::StackArgs &a = p.a;
-    const nl::FastArgs f = list_args(h, true, false);
-    nl::LinfitCascade cascade;
-    const nl::LinfitCascade *cas = linfit_cascade(h, &cascade);
-    if (cas) NL_HIP(hipMemsetAsync(h->d_lf_count, 0, sizeof(unsigned) * nl::kLinfitCounters, h->stream));
-    if (nl::linfit_ml_supported(p.mode, a.n_frames, a.npix))
-        NL_HIP(nl::launch_stack_linfit_ml_maps(a, f, cas, h->stream, &h->last_kernel, h->ev_dom1));
-    else
-        NL_HIP(nl::launch_stack_linfit_fast_maps(a, f, cas, h->stream, &h->last_kernel, h->ev_dom1));
-    const int rc = replay_list(h, p.mode, p.weighted, a, true);
+    const hipEvent_t dominant_done = p.timed ? h->ev_dom1 : nullptr;
+    const bool one_lane = a.n_frames <= 128;          // 129 ... 512 frames: 2 or 4 lanes per pixel, the LDS-column kernels
+    if (one_lane) NL_HIP(nl::launch_stack_sigma_maps_dominant(a, f, h->stream, &h->last_kernel, dominant_done, winsor));
+    else          NL_HIP(nl::launch_stack_sigma_mlz(a, nl::whole_tile(f), h->stream, &h->last_kernel, winsor, true));
+    if (!one_lane && dominant_done) NL_HIP(hipEventRecord(dominant_done, h->stream));
+    if (one_lane) NL_HIP(nl::launch_stack_sigma_maps_generic(a, f, h->stream, winsor));
+    else          NL_HIP(nl::launch_stack_sigma_mlg(a, nl::over_generic_list(nl::whole_tile(f)), nl::ml_generic_grid(a.n_frames, 0), h->stream, winsor, true));
+    const int rc = replay_list(h, p.mode, false, a, Columns::Maps);
     if (rc != NL_OK) return rc;
     NL_HIP(nl::launch_reduce_counters(h->d_partial, nl::kClipSlots, h->d_counters, h->stream));
     facts->has_counters = true;
@@ -670,16 +652,8 @@ static int run_dense_replay(nl_stack *h, const PassSetup &p, PassFacts *facts)
 // one pixel per lane with its column in LDS: every mode at any depth (nl_stack_set_exact(h, 1), and what no other engine takes)
 static int run_exact_columns(nl_stack *h, const PassSetup &p, PassFacts *facts)
 {
-    nl::StackArgs a = p.a;
-    int lanes = 0;
-    size_t lds = 0;
-    if (nl::exact_plan(p.mode, p.weighted, a.n_frames, a.n_pad, 64, &lanes, &lds) != 0)
-        return fail(NL_ERR_TOO_MANY_FRAMES, "%d frames do not fit the per-pixel LDS column (mode %d)", a.n_frames, p.mode);
-    a.tiles = (a.npix + lanes - 1) / lanes;
-    const int grid = (int)(a.tiles < (int64_t)h->max_grid ? a.tiles : (int64_t)h->max_grid);
-    if (p.maps) NL_HIP(nl::launch_stack_exact_maps(p.mode, p.weighted, a, lanes, grid, lds, h->stream, &h->last_kernel));
-    else        NL_HIP(nl::launch_stack_exact(p.mode, p.weighted, a, lanes, grid, lds, h->stream, &h->last_kernel));
-    NL_HIP(hipEventRecord(h->ev_dom1, h->stream));
+    const int rc = columns_over_tile(h, p.mode, p.weighted, p.a, p.maps() ? Columns::Maps : Columns::Plain);
+    if (rc != NL_OK) return rc;
     NL_HIP(nl::launch_reduce_counters(h->d_partial, nl::kClipSlots, h->d_counters, h->stream));
     facts->has_counters = p.mode != NL_ST_MEDIAN;
     return NL_OK;
@@ -691,7 +665,7 @@ static int run_exact_columns(nl_stack *h, const PassSetup &p, PassFacts *facts)
 // column kernel over the whole tile.  Plain protocol throughout, as run_listed and run_exact_columns.
 static int run_linfit_weighted(nl_stack *h, const PassSetup &p, PassFacts *facts)
 {
-    nl::StackArgs a = p.a;
+    const nl::StackArgs &a = p.a;
     if (!h->force_exact && h->d_fb_list && nl::linfit_weighted_supported(a.n_frames, a.npix)) {
         NL_HIP(nl::launch_stack_linfit_weighted(a, list_args(h, true, false), h->stream, &h->last_kernel));
         NL_HIP(hipEventRecord(h->ev_dom1, h->stream));
@@ -699,14 +673,8 @@ static int run_linfit_weighted(nl_stack *h, const PassSetup &p, PassFacts *facts
         if (rc != NL_OK) return rc;
         facts->used_fast = true;
     } else {
-        int lanes = 0;
-        size_t lds = 0;
-        if (nl::exact_plan(p.mode, true, a.n_frames, a.n_pad, 64, &lanes, &lds) != 0)
-            return fail(NL_ERR_TOO_MANY_FRAMES, "%d frames do not fit the per-pixel LDS columns of the weighted linear fit", a.n_frames);
-        a.tiles = (a.npix + lanes - 1) / lanes;
-        const int grid = (int)(a.tiles < (int64_t)h->max_grid ? a.tiles : (int64_t)h->max_grid);
-        NL_HIP(nl::launch_stack_exact(p.mode, true, a, lanes, grid, lds, h->stream, &h->last_kernel));
-        NL_HIP(hipEventRecord(h->ev_dom1, h->stream));
+        const int rc = columns_over_tile(h, p.mode, true, a);
+        if (rc != NL_OK) return rc;
     }
     NL_HIP(nl::launch_reduce_counters(h->d_partial, nl::kClipSlots, h->d_counters, h->stream));
     facts->has_counters = true;
@@ -733,8 +701,6 @@ static bool clip_weighted_decided(nl_stack *h, int mode, const nl::StackArgs &a)
 static int run_clip_weighted(nl_stack *h, const PassSetup &p, PassFacts *facts)
 {
     nl::StackArgs a = p.a;
-    int lanes = 0;
-    size_t lds = 0;
     bool streamed = false;
     if (clip_weighted_decided(h, p.mode, a)) {
         const int rc = decision_pass(h, p, a);
@@ -750,36 +716,22 @@ static int run_clip_weighted(nl_stack *h, const PassSetup &p, PassFacts *facts)
     if (streamed) {
         NL_HIP(nl::launch_stack_clip_weighted(a, list_args(h, true, false), h->stream, &h->last_kernel));
         NL_HIP(hipEventRecord(h->ev_dom1, h->stream));
-        if (nl::exact_plan(p.mode, false, a.n_frames, a.n_pad, kListLanes, &lanes, &lds) != 0)
-            return fail(NL_ERR_TOO_MANY_FRAMES, "%d frames do not fit the per-pixel LDS column (mode %d)", a.n_frames, p.mode);
-        nl::StackArgs e = a;
-        e.bounds = nullptr;
-        e.nrounds = nullptr;
-        e.list = h->d_fb_list;
-        e.list_count = h->d_fb_count;
-        e.list_capacity = (unsigned)h->npix;
-        const char *exact_name = "";
-        NL_HIP(nl::launch_stack_exact_follow(p.mode, e, lanes, kListGrid, lds, h->stream, &exact_name));
         facts->used_fast = true;
-    } else {
-        a.bounds = nullptr;
-        a.nrounds = nullptr;
-        if (nl::exact_plan(p.mode, false, a.n_frames, a.n_pad, 64, &lanes, &lds) != 0)
-            return fail(NL_ERR_TOO_MANY_FRAMES, "%d frames do not fit the per-pixel LDS column (mode %d)", a.n_frames, p.mode);
-        a.tiles = (a.npix + lanes - 1) / lanes;
-        const int grid = (int)(a.tiles < (int64_t)h->max_grid ? a.tiles : (int64_t)h->max_grid);
-        NL_HIP(nl::launch_stack_exact_follow(p.mode, a, lanes, grid, lds, h->stream, &h->last_kernel));
-        NL_HIP(hipEventRecord(h->ev_dom1, h->stream));
     }
+    // (the <follow> column kernel computes its own bounds: one column, planned with weighted = false)
+    a.bounds = nullptr;
+    a.nrounds = nullptr;
+    const int rc = streamed ? replay_list(h, p.mode, false, a, Columns::Follow) : columns_over_tile(h, p.mode, false, a, Columns::Follow);
+    if (rc != NL_OK) return rc;
     NL_HIP(nl::launch_reduce_counters(h->d_partial, nl::kClipSlots, h->d_counters, h->stream));
     facts->has_counters = true;
     return NL_OK;
 }
 
-static int run_async_impl(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc, PassKind kind);
+static int run_async_impl(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc, PassKind kind,
+                          nl::MapsTier tier = nl::MapsTier::None);
 
-// what a pass that failed half-way leaves behind (nl_stack_run_async, nl::stack_run_maps_async, nl::stack_run_maps_fast_async,
-// nl::stack_run_maps_resident_async, nl::stack_run_maps_deep_async,
+// what a pass that failed half-way leaves behind (nl_stack_run_async, nl::stack_run_maps_async,
 // nl_stack_run_linfit_weighted_async, nl_stack_run_clip_weighted_async)
 static int settle_failed_pass(nl_stack_t *h, int rc)
 {
@@ -806,24 +758,15 @@ int nl_stack_run_async(nl_stack_t *h, int mode, float sigma_low, float sigma_hig
     return settle_failed_pass(h, run_async_impl(h, mode, sigma_low, sigma_high, ref_loc, PassKind::Default));
 }
 
-// maps: the pass of nl_stack_run_maps -- every mode but the mean on the one-pixel-per-lane column kernel, whose MAPS
-// instantiation also stores each pixel's two clip counts in h->d_reject_map.  Such a pass takes part in none of what
-// default passes remember from one another: it takes and leaves no list-length hints (it has no lists), never runs the
-// fused protocol, and leaves the scratch sets as any other plain-protocol pass does.
-// PassKind::FastMaps (nl_stack_run_maps_fast) is a maps pass that select_engine may give to run_sigma_fast_maps: it has
-// lists, but keeps all of the above (plain protocol, no hints either way).  PassKind::ResidentMaps
-// (nl_stack_run_maps_resident) is that pass with one more engine, run_linfit_maps for the linear fit, under the same rules;
-// the linear fit drops the handle's weights here as in every other unweighted entry (stack.go:158).  PassKind::DeepMaps
-// (nl_stack_run_maps_deep) is that pass again with one more engine, run_sigma_deep_maps for unweighted sigma / winsorized
-// clipping of 129 ... 512 frames, under the same rules.
-// The same holds for the weighted linear-fit pass (PassKind::WeightedLinfit; `mode` is NL_ST_LINEAR_FIT), which keeps the
-// weights the default linear fit drops and runs on run_linfit_weighted, and for the weighted clip pass whose weights follow
-// their frames (PassKind::WeightedClip; `mode` resolves to sigma or winsorized sigma), which runs on run_clip_weighted.
-static int run_async_impl(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc, PassKind kind)
+// tier: a maps pass, on the ladder described above the engines.  Like a maps pass, two more passes take part in nothing
+// default passes remember from one another: the weighted linear-fit pass (PassKind::WeightedLinfit; `mode` is
+// NL_ST_LINEAR_FIT), which keeps the weights the default linear fit drops and runs on run_linfit_weighted, and the weighted
+// clip pass whose weights follow their frames (PassKind::WeightedClip; `mode` resolves to sigma or winsorized sigma), which
+// runs on run_clip_weighted.
+static int run_async_impl(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc, PassKind kind, nl::MapsTier tier)
 {
     NL_CHECK_HANDLE(h);
-    const bool maps = kind == PassKind::Maps || kind == PassKind::FastMaps || kind == PassKind::ResidentMaps || kind == PassKind::DeepMaps, wlinfit = kind == PassKind::WeightedLinfit;
-    const bool wclip = kind == PassKind::WeightedClip;
+    const bool maps = tier != nl::MapsTier::None, wlinfit = kind == PassKind::WeightedLinfit, wclip = kind == PassKind::WeightedClip;
     if (wclip && !h->has_weights)
         return fail(NL_ERR_INVALID_ARG, "run_clip_weighted: the handle has no weights (nl_stack_set_weights); "
                                         "the unweighted pass is nl_stack_run");
@@ -880,7 +823,7 @@ static int run_async_impl(nl_stack_t *h, int mode, float sigma_low, float sigma_
     h->ring_timed[h->pass_seq % kTimingRing] = timed;
     if (timed) NL_HIP(hipEventRecord(h->ev_start, h->stream));
     const bool fused_on = fused_protocol_on();
-    const Engine engine = select_engine(h, mode, weighted, a, kind);
+    const Engine engine = select_engine(h, mode, weighted, a, tier);
     const bool sigma_fast = engine == Engine::SigmaFast;
     // (only while the exact list is short -- the length the last finished pass reported: its replays add their
     // counts to ONE word, and thousands of workgroups doing that take longer than a reduction kernel)
@@ -913,7 +856,7 @@ static int run_async_impl(nl_stack_t *h, int mode, float sigma_low, float sigma_
     h->partial_clean = false;
     if (timed && !one_start) NL_HIP(hipEventRecord(h->ev_dom0, h->stream));
 
-    const PassSetup p{mode, weighted, timed, fused, a, maps};
+    const PassSetup p{mode, weighted, timed, fused, a, tier};
     PassFacts facts;
     int rc = NL_OK;
     if (wlinfit) rc = run_linfit_weighted(h, p, &facts);
@@ -924,9 +867,7 @@ static int run_async_impl(nl_stack_t *h, int mode, float sigma_low, float sigma_
     case Engine::MedianMultiLane: rc = run_median(h, p, true); break;
     case Engine::Listed:          rc = run_listed(h, p, &facts); break;
     case Engine::SigmaFast:       rc = run_sigma_fast(h, p, &facts); break;
-    case Engine::SigmaFastMaps:   rc = run_sigma_fast_maps(h, p, &facts); break;
-    case Engine::LinfitMaps:      rc = run_linfit_maps(h, p, &facts); break;
-    case Engine::SigmaDeepMaps:   rc = run_sigma_deep_maps(h, p, &facts); break;
+    case Engine::SigmaMaps:       rc = run_sigma_maps(h, p, &facts); break;
     case Engine::WeightedTile:    rc = run_weighted_tile(h, p, &facts); break;
     case Engine::DenseReplay:     rc = run_dense_replay(h, p, &facts); break;
     case Engine::ExactColumns:    rc = run_exact_columns(h, p, &facts); break;
@@ -975,28 +916,10 @@ int nl_stack_run(nl_stack_t *h, int mode, float sigma_low, float sigma_high, flo
 
 }  // extern "C"
 
-// ---- the maps pass (include/nlstack_maps.h) ----------------------------------------------------------------------------
-int nl::stack_run_maps_async(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc)
+// ---- the maps passes (include/nlstack_maps.h, nlstack_fastmaps.h, nlstack_residentmaps.h, nlstack_deepmaps.h) ----------
+int nl::stack_run_maps_async(nl_stack_t *h, nl::MapsTier tier, int mode, float sigma_low, float sigma_high, float ref_loc)
 {
-    return settle_failed_pass(h, run_async_impl(h, mode, sigma_low, sigma_high, ref_loc, PassKind::Maps));
-}
-
-// the fast maps pass (include/nlstack_fastmaps.h)
-int nl::stack_run_maps_fast_async(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc)
-{
-    return settle_failed_pass(h, run_async_impl(h, mode, sigma_low, sigma_high, ref_loc, PassKind::FastMaps));
-}
-
-// the resident maps pass (include/nlstack_residentmaps.h)
-int nl::stack_run_maps_resident_async(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc)
-{
-    return settle_failed_pass(h, run_async_impl(h, mode, sigma_low, sigma_high, ref_loc, PassKind::ResidentMaps));
-}
-
-// the deep maps pass (include/nlstack_deepmaps.h)
-int nl::stack_run_maps_deep_async(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc)
-{
-    return settle_failed_pass(h, run_async_impl(h, mode, sigma_low, sigma_high, ref_loc, PassKind::DeepMaps));
+    return settle_failed_pass(h, run_async_impl(h, mode, sigma_low, sigma_high, ref_loc, PassKind::Default, tier));
 }
 
 // nl_stack_finish, and the two planes of the map (of either kind of maps pass).  The packed words come down in ONE copy and are split here: the same
@@ -1060,40 +983,40 @@ int nl_stack_run_clip_weighted(nl_stack_t *h, int mode, float sigma_low, float s
     return nl_stack_finish(h, out_host, clip_low, clip_high);
 }
 
+static int run_maps(nl_stack_t *h, nl::MapsTier tier, int mode, float sigma_low, float sigma_high, float ref_loc,
+                    float *out_host, int64_t *clip_low, int64_t *clip_high, uint16_t *reject_low_host, uint16_t *reject_high_host)
+{
+    const int rc = nl::stack_run_maps_async(h, tier, mode, sigma_low, sigma_high, ref_loc);
+    if (rc != NL_OK) return rc;
+    return nl::stack_finish_maps(h, out_host, clip_low, clip_high, reject_low_host, reject_high_host);
+}
+
 int nl_stack_run_maps(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc,
                       float *out_host, int64_t *clip_low, int64_t *clip_high,
                       uint16_t *reject_low_host, uint16_t *reject_high_host)
 {
-    const int rc = nl::stack_run_maps_async(h, mode, sigma_low, sigma_high, ref_loc);
-    if (rc != NL_OK) return rc;
-    return nl::stack_finish_maps(h, out_host, clip_low, clip_high, reject_low_host, reject_high_host);
+    return run_maps(h, nl::MapsTier::Column, mode, sigma_low, sigma_high, ref_loc, out_host, clip_low, clip_high, reject_low_host, reject_high_host);
 }
 
 int nl_stack_run_maps_fast(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc,
                            float *out_host, int64_t *clip_low, int64_t *clip_high,
                            uint16_t *reject_low_host, uint16_t *reject_high_host)
 {
-    const int rc = nl::stack_run_maps_fast_async(h, mode, sigma_low, sigma_high, ref_loc);
-    if (rc != NL_OK) return rc;
-    return nl::stack_finish_maps(h, out_host, clip_low, clip_high, reject_low_host, reject_high_host);
+    return run_maps(h, nl::MapsTier::Fast, mode, sigma_low, sigma_high, ref_loc, out_host, clip_low, clip_high, reject_low_host, reject_high_host);
 }
 
 int nl_stack_run_maps_resident(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc,
                                float *out_host, int64_t *clip_low, int64_t *clip_high,
                                uint16_t *reject_low_host, uint16_t *reject_high_host)
 {
-    const int rc = nl::stack_run_maps_resident_async(h, mode, sigma_low, sigma_high, ref_loc);
-    if (rc != NL_OK) return rc;
-    return nl::stack_finish_maps(h, out_host, clip_low, clip_high, reject_low_host, reject_high_host);
+    return run_maps(h, nl::MapsTier::Resident, mode, sigma_low, sigma_high, ref_loc, out_host, clip_low, clip_high, reject_low_host, reject_high_host);
 }
 
 int nl_stack_run_maps_deep(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc,
                            float *out_host, int64_t *clip_low, int64_t *clip_high,
                            uint16_t *reject_low_host, uint16_t *reject_high_host)
 {
-    const int rc = nl::stack_run_maps_deep_async(h, mode, sigma_low, sigma_high, ref_loc);
-    if (rc != NL_OK) return rc;
-    return nl::stack_finish_maps(h, out_host, clip_low, clip_high, reject_low_host, reject_high_host);
+    return run_maps(h, nl::MapsTier::Deep, mode, sigma_low, sigma_high, ref_loc, out_host, clip_low, clip_high, reject_low_host, reject_high_host);
 }
 
 // no pass: it reads the active frames behind whatever is enqueued on the handle's stream and leaves the last pass's

@@ -1,6 +1,6 @@
 // stack_fast_maps_impl.hpp -- the MAPS instantiations of the register-resident sigma / winsorized sigma kernels and of
 // their LDS-column generic pass, with their launchers: the engines of the fast maps pass (include/nlstack_fastmaps.h,
-// run_sigma_fast_maps in nlstack_pass.hip).  Included by stack_fast_maps_sigma.hip and stack_fast_maps_winsor.hip, one
+// run_sigma_maps in nlstack_pass.hip).  Included by stack_fast_maps_sigma.hip and stack_fast_maps_winsor.hip, one
 // translation unit per mode (compile time); stack_fast.hip and stack_fast_mlg.hip instantiate exactly what they did.
 //
 // The kernels are those of the default pass (stack_fast.hip has the exactness contract) with one more store: the lane

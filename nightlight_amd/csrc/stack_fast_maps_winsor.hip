@@ -4,13 +4,13 @@
 
 namespace nl {
 
-hipError_t launch_stack_winsor_maps_dominant(const StackArgs &args, const FastArgs &fargs, hipStream_t stream,
-                                             const char **name, hipEvent_t dominant_done)
+hipError_t maps_winsor_dominant(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name,
+                                hipEvent_t dominant_done)
 {
     return maps_dominant<true>(args, fargs, stream, name, dominant_done);
 }
 
-hipError_t launch_stack_winsor_maps_generic(const StackArgs &args, const FastArgs &fargs, hipStream_t stream)
+hipError_t maps_winsor_generic(const StackArgs &args, const FastArgs &fargs, hipStream_t stream)
 {
     return maps_generic<true>(args, fargs, stream);
 }

@@ -55,9 +55,12 @@ void stack_sigma_mlg_kernel(StackArgs p, FastArgs q)
 // one-lane kernels of stack_fast.hip, whose register version of this pass runs 28 lock-step
 // winsorization rounds over all 128 masked positions -- 1.0 ms for the 57 k border pixels of a
 // 128 x 4096^2 stack, less than one wave per SIMD, pure latency
+static hipError_t launch_mlg_lanes_maps(const StackArgs &args, const FastArgs &fargs, unsigned grid, hipStream_t stream, bool winsor);
+
 hipError_t launch_stack_sigma_mlg(const StackArgs &args, const FastArgs &fargs, unsigned grid, hipStream_t stream,
-                                  bool winsor)
+                                  bool winsor, bool maps)
 {
+    if (maps) return launch_mlg_lanes_maps(args, fargs, grid, stream, winsor);
     Launcher L(stream);
     with_bool(winsor, [&](auto W) {
         constexpr bool WINSOR = decltype(W)::value;
@@ -83,12 +86,11 @@ void stack_sigma_mlg_lanes_maps_kernel(StackArgs p, FastArgs q)
 }
 
 // over fargs.in_list, args.reject_map set; the list's length is only known on the device and a maps pass reads no hint:
-// the grid of launch_stack_sigma_mlg without one, ml_generic_grid(n, 0)
-hipError_t launch_stack_sigma_mlg_maps(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, bool winsor)
+// its caller passes the grid without one, ml_generic_grid(n, 0)
+static hipError_t launch_mlg_lanes_maps(const StackArgs &args, const FastArgs &fargs, unsigned grid, hipStream_t stream, bool winsor)
 {
     if (!args.reject_map || args.n_frames <= kMlNS || args.n_frames > 4 * kMlNS) return hipErrorInvalidValue;
     Launcher L(stream);
-    const unsigned grid = ml_generic_grid(args.n_frames, 0);
     with_bool(winsor, [&](auto W) {
         with_ml_lanes(args.n_frames, [&](auto LPP) {
             L(stack_sigma_mlg_lanes_maps_kernel<decltype(LPP)::value, decltype(W)::value>, grid, 64, 0, args, fargs);

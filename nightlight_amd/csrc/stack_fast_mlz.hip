@@ -13,6 +13,9 @@ bool launch_mlz_maps_part_a(int ntop, bool winsor, const StackArgs &args, const 
 bool launch_mlz_maps_part_b(int ntop, bool winsor, const StackArgs &args, const FastArgs &f, Launcher &L, const char **name);
 bool launch_mlz_maps_part_c(int ntop, bool winsor, const StackArgs &args, const FastArgs &f, Launcher &L, const char **name);
 bool launch_mlz_maps_part_d(int ntop, bool winsor, const StackArgs &args, const FastArgs &f, Launcher &L, const char **name);
+static constexpr decltype(&launch_mlz_part_a) kParts[4] = {launch_mlz_part_a, launch_mlz_part_b, launch_mlz_part_c, launch_mlz_part_d};
+static constexpr decltype(&launch_mlz_part_a) kMapsParts[4] = {launch_mlz_maps_part_a, launch_mlz_maps_part_b, launch_mlz_maps_part_c,
+                                                               launch_mlz_maps_part_d};
 
 int fast_mlz_supported(int mode, bool weighted, int n_frames)
 {
@@ -26,30 +29,19 @@ int decide_ml_supported(int mode, int n_frames, int64_t npix)
 }
 
 // the zonal launch over the whole tile (the generic pass over its hand-over list is stack_fast_mlg.hip); the part that
-// instantiates the class sets *name
+// instantiates the class sets *name.  maps: the MAPS instantiation of the class -- every pixel the kernel decides gets its
+// word of args.reject_map beside its result; never a record-only pass
 hipError_t launch_stack_sigma_mlz(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name,
-                                  bool winsor)
+                                  bool winsor, bool maps)
 {
-    Launcher L(stream);
-    const FastArgs f = whole_tile(fargs);
-    const int ntop = (args.n_frames + 15) / 16 * 16;
-    const bool ok = launch_mlz_part_a(ntop, winsor, args, f, L, name) || launch_mlz_part_b(ntop, winsor, args, f, L, name) ||
-                    launch_mlz_part_c(ntop, winsor, args, f, L, name) || launch_mlz_part_d(ntop, winsor, args, f, L, name);
-    return ok ? L.err : hipErrorInvalidValue;
-}
-
-// the same launch with the MAPS instantiation of the class (the deep maps pass, include/nlstack_deepmaps.h): every pixel
-// the kernel decides gets its word of args.reject_map beside its result; never a record-only pass
-hipError_t launch_stack_sigma_mlz_maps(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name,
-                                       bool winsor)
-{
-    if (!args.reject_map || fargs.record_only || !fast_mlz_supported(winsor ? NL_ST_WINSOR_SIGMA : NL_ST_SIGMA, false, args.n_frames))
+    if (maps && (!args.reject_map || fargs.record_only || !fast_mlz_supported(winsor ? NL_ST_WINSOR_SIGMA : NL_ST_SIGMA, false, args.n_frames)))
         return hipErrorInvalidValue;
     Launcher L(stream);
     const FastArgs f = whole_tile(fargs);
     const int ntop = (args.n_frames + 15) / 16 * 16;
-    const bool ok = launch_mlz_maps_part_a(ntop, winsor, args, f, L, name) || launch_mlz_maps_part_b(ntop, winsor, args, f, L, name) ||
-                    launch_mlz_maps_part_c(ntop, winsor, args, f, L, name) || launch_mlz_maps_part_d(ntop, winsor, args, f, L, name);
+    const auto *const parts = maps ? kMapsParts : kParts;
+    bool ok = false;
+    for (int i = 0; i < 4 && !ok; i++) ok = parts[i](ntop, winsor, args, f, L, name);
     return ok ? L.err : hipErrorInvalidValue;
 }
 

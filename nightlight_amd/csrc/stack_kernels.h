@@ -124,17 +124,6 @@ int stack_project_from(nl_stack_t *dst, int dst_idx, nl_stack_t *src, int src_id
 // what the _resample_from entries check in front of their handles: the kernel's id, a null or singular transform
 int resample_args_check(const char *who, int kernel, const float *trans);
 int stack_settle(nl_stack_t *h);
-// the two halves of nl_stack_run_maps (nlstack_pass.hip), so that nl_group_run_maps starts every tile before it awaits any;
-// a failing first half settles the handle as nl_stack_run_async does
-int stack_run_maps_async(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc);
-int stack_finish_maps(nl_stack_t *h, float *out_host, int64_t *clip_low, int64_t *clip_high, uint16_t *reject_low_host,
-                      uint16_t *reject_high_host);
-// the first half of nl_stack_run_maps_fast (include/nlstack_fastmaps.h); stack_finish_maps finishes either kind
-int stack_run_maps_fast_async(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc);
-// the first half of nl_stack_run_maps_resident (include/nlstack_residentmaps.h); stack_finish_maps finishes it as well
-int stack_run_maps_resident_async(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc);
-// the first half of nl_stack_run_maps_deep (include/nlstack_deepmaps.h); stack_finish_maps finishes it as well
-int stack_run_maps_deep_async(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc);
 
 // Bisection of the goal-seek (spec: internal/ops/stack/stackfindsigma.go:48-98): sigma_low and
 // sigma_high in [1,11], percentages in the reference's fp32 arithmetic, 21 passes at most.
@@ -221,12 +210,10 @@ struct SigmaNewton {
 // Picks lanes-per-wave and LDS bytes for the exact kernel; -1 if it cannot fit.
 int exact_plan(int mode, bool weighted, int n_frames, int n_pad, int max_lanes, int *lanes,
                size_t *lds_bytes);
+// maps: the MAPS instantiations -- every pixel's two clip counts also go to args.reject_map (the whole tile, or -- the
+// replay behind the other kernels of a maps pass -- the pixels of args.list)
 hipError_t launch_stack_exact(int mode, bool weighted, const StackArgs &args, int lanes, int grid,
-                              size_t lds_bytes, hipStream_t stream, const char **name);
-// the MAPS instantiations: as above, and every pixel's two clip counts go to args.reject_map (the whole tile, or -- the
-// replay of the fast maps pass -- the pixels of args.list)
-hipError_t launch_stack_exact_maps(int mode, bool weighted, const StackArgs &args, int lanes, int grid,
-                                   size_t lds_bytes, hipStream_t stream, const char **name);
+                              size_t lds_bytes, hipStream_t stream, const char **name, bool maps = false);
 // list_counts (optional): {exact-list length, generic-list length} of the pass, left in counters[2] (low | high << 32)
 // zero_after: the kernel leaves the scratch set (kScratchWords words at `partial`) zeroed for the next pass
 hipError_t launch_reduce_counters(unsigned long long *partial, int n_blocks,
@@ -246,17 +233,13 @@ hipError_t launch_stack_mad_fast(const StackArgs &args, const FastArgs &fargs, h
 // 249..256 / 505..512 frames: zonal sigma / winsorized sigma pass with the clipping rounds on LDS
 // columns (stack_fast_mlz.hip); hand-over lists as the other fast kernels
 // generic pass of the multi-lane sigma / winsor kernels over fargs.in_list, whole columns in LDS (stack_fast_mlg.hip)
+// maps (both launches, 129 ... 512 frames, args.reject_map set: the two parts of a maps pass at that depth): the MAPS
+// instantiations (stack_fast_mlz_maps_{a,b,c,d}.hip, stack_fast_mlg.hip), one more store per pixel, its two clip counts
 hipError_t launch_stack_sigma_mlg(const StackArgs &args, const FastArgs &fargs, unsigned grid, hipStream_t stream,
-                                  bool winsor);
+                                  bool winsor, bool maps = false);
 int fast_mlz_supported(int mode, bool weighted, int n_frames);
 hipError_t launch_stack_sigma_mlz(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name,
-                                  bool winsor);
-// ---- stack_fast_mlz_maps_{a,b,c,d}.hip / stack_fast_mlg.hip: the two parts of the deep maps pass (include/nlstack_deepmaps.h),
-// unweighted sigma / winsorized clipping of 129 ... 512 frames, args.reject_map set.  As the two launches above with one
-// more store per pixel, its two clip counts; no hints: the generic part runs the grid ml_generic_grid(n, 0) ----
-hipError_t launch_stack_sigma_mlz_maps(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name,
-                                       bool winsor);
-hipError_t launch_stack_sigma_mlg_maps(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, bool winsor);
+                                  bool winsor, bool maps = false);
 // sigma / winsorized clipping of 2 ... 128 frames, in the two parts a pass enqueues them.  Dominant part: the zonal kernel
 // (network size 8: the generic kernel over the whole tile), dominant_done (optional) recorded behind it, and for winsorized
 // stacks the continuation stages of the cascade.  Generic part: the pass over the generic list (network size 8: nothing);
@@ -266,15 +249,12 @@ hipError_t launch_stack_sigma_fast_dominant(const StackArgs &args, const FastArg
                                             const char **name, hipEvent_t dominant_done, bool winsor);
 hipError_t launch_stack_sigma_fast_generic(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, bool winsor,
                                            const StackArgs *first_replay = nullptr, unsigned replay_blocks = 0);
-// ---- stack_fast_maps_sigma.hip / stack_fast_maps_winsor.hip: the two parts of the fast maps pass (include/nlstack_fastmaps.h),
-// 2 ... 128 frames, args.reject_map set.  As the parts above with one more store per pixel, its two clip counts; no
-// cascade, no fused tail, no hints: the generic part runs a fixed grid ----
+// ---- stack_fast_maps_sigma.hip / stack_fast_maps_winsor.hip: the two parts of a maps pass of 2 ... 128 frames,
+// args.reject_map set.  As the parts above with one more store per pixel, its two clip counts; no cascade, no fused
+// tail, no hints: the generic part runs a fixed grid ----
 hipError_t launch_stack_sigma_maps_dominant(const StackArgs &args, const FastArgs &fargs, hipStream_t stream,
-                                            const char **name, hipEvent_t dominant_done);
-hipError_t launch_stack_sigma_maps_generic(const StackArgs &args, const FastArgs &fargs, hipStream_t stream);
-hipError_t launch_stack_winsor_maps_dominant(const StackArgs &args, const FastArgs &fargs, hipStream_t stream,
-                                             const char **name, hipEvent_t dominant_done);
-hipError_t launch_stack_winsor_maps_generic(const StackArgs &args, const FastArgs &fargs, hipStream_t stream);
+                                            const char **name, hipEvent_t dominant_done, bool winsor);
+hipError_t launch_stack_sigma_maps_generic(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, bool winsor);
 // ---- stack_tail_fused.hip: generic pass (one lane per pixel, LDS columns) + first replay in one grid; plain sigma, 65 ... 128 frames
 int tail_fused_supported(int mode, bool weighted, int n_frames);
 hipError_t launch_stack_sigma_tail(const StackArgs &generic, const FastArgs &fargs, unsigned gen_blocks,
@@ -335,17 +315,13 @@ constexpr int kLinfitCounters = 8;  // device list lengths of one pass (the bit-
 int linfit_fast_supported(int mode, int n_frames, int64_t npix);
 int linfit_ml_supported(int mode, int n_frames, int64_t npix);
 
+// maps (args.reject_map set): the MAPS instantiations of the same kernels (stack_linfit_maps.hip).  Same classes, cascade,
+// quotas and grids; every lane that holds a pixel's two clip counts leaves them in args.reject_map (stage 0 stores,
+// continuation stages add: stack_linfit_impl.hpp)
 hipError_t launch_stack_linfit_fast(const StackArgs &args, const FastArgs &fargs, const LinfitCascade *cascade,
-                                    hipStream_t stream, const char **name, hipEvent_t dominant_done);
+                                    hipStream_t stream, const char **name, hipEvent_t dominant_done, bool maps = false);
 hipError_t launch_stack_linfit_ml(const StackArgs &args, const FastArgs &fargs, const LinfitCascade *cascade,
-                                  hipStream_t stream, const char **name, hipEvent_t dominant_done);
-// ---- stack_linfit_maps.hip: the MAPS instantiations of the same kernels (the resident maps pass,
-// include/nlstack_residentmaps.h), args.reject_map set.  Same classes, cascade, quotas and grids; every lane that holds a
-// pixel's two clip counts leaves them in args.reject_map (stage 0 stores, continuation stages add: stack_linfit_impl.hpp) ----
-hipError_t launch_stack_linfit_fast_maps(const StackArgs &args, const FastArgs &fargs, const LinfitCascade *cascade,
-                                         hipStream_t stream, const char **name, hipEvent_t dominant_done);
-hipError_t launch_stack_linfit_ml_maps(const StackArgs &args, const FastArgs &fargs, const LinfitCascade *cascade,
-                                       hipStream_t stream, const char **name, hipEvent_t dominant_done);
+                                  hipStream_t stream, const char **name, hipEvent_t dominant_done, bool maps = false);
 
 // ---- stack_linfit_weighted.hip (the weighted linear-fit pass, include/nlstack_wlinfit.h: register-resident fit, one
 // pixel per lane, up to 128 frames; args.weights must be set; pixels it cannot decide go to fargs.fb_list, for

@@ -158,6 +158,11 @@ class StackHandle:
         reject_low[p] / reject_high[p] = how often the reference increments clipLow / clipHigh at pixel p; their
         sums are the two totals.  `out`, `reject_low`, `reject_high`: whole-image arrays (float32, uint16, uint16)
         whose tile rows get written; those not given are made here, zero outside the tile."""
+        entry = self._lib.nl_stack_run_maps_fast if fast else self._lib.nl_stack_run_maps
+        return self._run_maps(entry, mode, sigma_low, sigma_high, ref_loc, out, reject_low, reject_high)
+
+    def _run_maps(self, entry, mode, sigma_low, sigma_high, ref_loc, out, reject_low, reject_high):
+        """What the run_maps* methods share: `entry` is the nl_stack_run_maps* function of the library."""
         n = self.width * self.height
         out = np.zeros(n, np.float32) if out is None else out
         reject_low = np.zeros(n, np.uint16) if reject_low is None else reject_low
@@ -165,7 +170,6 @@ class StackHandle:
         for a, t in ((out, np.float32), (reject_low, np.uint16), (reject_high, np.uint16)):
             assert a.dtype == t and a.size == n and a.flags.c_contiguous
         cl, ch = C.c_int64(0), C.c_int64(0)
-        entry = self._lib.nl_stack_run_maps_fast if fast else self._lib.nl_stack_run_maps
         capi.check(entry(self._h, int(mode), C.c_float(sigma_low), C.c_float(sigma_high), C.c_float(ref_loc),
                          capi.fptr(out), C.byref(cl), C.byref(ch), _u16ptr(reject_low), _u16ptr(reject_high)))
         return out, cl.value, ch.value, reject_low, reject_high
@@ -176,17 +180,7 @@ class StackHandle:
         the linear fit of up to 512 frames on its own kernels and cascade -- the result is then bit-exact, the pass
         about as fast as run(ST_LINEAR_FIT) -- sigma / winsorized clipping as run_maps(fast=True), the column kernel
         everywhere else.  Arguments and return value are those of run_maps."""
-        n = self.width * self.height
-        out = np.zeros(n, np.float32) if out is None else out
-        reject_low = np.zeros(n, np.uint16) if reject_low is None else reject_low
-        reject_high = np.zeros(n, np.uint16) if reject_high is None else reject_high
-        for a, t in ((out, np.float32), (reject_low, np.uint16), (reject_high, np.uint16)):
-            assert a.dtype == t and a.size == n and a.flags.c_contiguous
-        cl, ch = C.c_int64(0), C.c_int64(0)
-        capi.check(self._lib.nl_stack_run_maps_resident(self._h, int(mode), C.c_float(sigma_low), C.c_float(sigma_high),
-                                                        C.c_float(ref_loc), capi.fptr(out), C.byref(cl), C.byref(ch),
-                                                        _u16ptr(reject_low), _u16ptr(reject_high)))
-        return out, cl.value, ch.value, reject_low, reject_high
+        return self._run_maps(self._lib.nl_stack_run_maps_resident, mode, sigma_low, sigma_high, ref_loc, out, reject_low, reject_high)
 
     def run_maps_deep(self, mode, sigma_low=2.75, sigma_high=2.75, ref_loc=0.0, out=None, reject_low=None,
                       reject_high=None):
@@ -194,17 +188,7 @@ class StackHandle:
         (nl_stack_run_maps_deep, include/nlstack_deepmaps.h): unweighted sigma / winsorized clipping of 129 ... 512
         frames on the LDS-column kernels of the default pass -- the result is then the default pass's -- and the pass
         of run_maps_resident everywhere else.  Arguments and return value are those of run_maps."""
-        n = self.width * self.height
-        out = np.zeros(n, np.float32) if out is None else out
-        reject_low = np.zeros(n, np.uint16) if reject_low is None else reject_low
-        reject_high = np.zeros(n, np.uint16) if reject_high is None else reject_high
-        for a, t in ((out, np.float32), (reject_low, np.uint16), (reject_high, np.uint16)):
-            assert a.dtype == t and a.size == n and a.flags.c_contiguous
-        cl, ch = C.c_int64(0), C.c_int64(0)
-        capi.check(self._lib.nl_stack_run_maps_deep(self._h, int(mode), C.c_float(sigma_low), C.c_float(sigma_high),
-                                                    C.c_float(ref_loc), capi.fptr(out), C.byref(cl), C.byref(ch),
-                                                    _u16ptr(reject_low), _u16ptr(reject_high)))
-        return out, cl.value, ch.value, reject_low, reject_high
+        return self._run_maps(self._lib.nl_stack_run_maps_deep, mode, sigma_low, sigma_high, ref_loc, out, reject_low, reject_high)
 
     def run_linfit_weighted(self, sigma_low=2.75, sigma_high=2.75, ref_loc=0.0, out=None, fetch=True):
         """One pass of the weighted linear fit (include/nlstack_wlinfit.h; an EXTENSION, the reference's fit takes
@@ -734,33 +718,24 @@ class StackGroup:
     def run_maps(self, mode, sigma_low=2.75, sigma_high=2.75, ref_loc=0.0, fast=False):
         """StackHandle.run_maps over the tiles: (result, clip_low, clip_high, reject_low, reject_high), every tile
         writing its own rows.  fast=True: nl_group_run_maps_fast."""
+        return self._run_maps(self._lib.nl_group_run_maps_fast if fast else self._lib.nl_group_run_maps, mode, sigma_low, sigma_high, ref_loc)
+
+    def _run_maps(self, entry, mode, sigma_low, sigma_high, ref_loc):
+        """What the run_maps* methods share: `entry` is the nl_group_run_maps* function of the library."""
         n = self.width * self.height
         out, lo, hi = np.zeros(n, np.float32), np.zeros(n, np.uint16), np.zeros(n, np.uint16)
         cl, ch = C.c_int64(0), C.c_int64(0)
-        entry = self._lib.nl_group_run_maps_fast if fast else self._lib.nl_group_run_maps
         capi.check(entry(self._g, int(mode), C.c_float(sigma_low), C.c_float(sigma_high), C.c_float(ref_loc),
                          capi.fptr(out), C.byref(cl), C.byref(ch), _u16ptr(lo), _u16ptr(hi)))
         return out, cl.value, ch.value, lo, hi
 
     def run_maps_resident(self, mode, sigma_low=2.75, sigma_high=2.75, ref_loc=0.0):
         """StackHandle.run_maps_resident over the tiles (nl_group_run_maps_resident): the return value of run_maps."""
-        n = self.width * self.height
-        out, lo, hi = np.zeros(n, np.float32), np.zeros(n, np.uint16), np.zeros(n, np.uint16)
-        cl, ch = C.c_int64(0), C.c_int64(0)
-        capi.check(self._lib.nl_group_run_maps_resident(self._g, int(mode), C.c_float(sigma_low), C.c_float(sigma_high),
-                                                        C.c_float(ref_loc), capi.fptr(out), C.byref(cl), C.byref(ch),
-                                                        _u16ptr(lo), _u16ptr(hi)))
-        return out, cl.value, ch.value, lo, hi
+        return self._run_maps(self._lib.nl_group_run_maps_resident, mode, sigma_low, sigma_high, ref_loc)
 
     def run_maps_deep(self, mode, sigma_low=2.75, sigma_high=2.75, ref_loc=0.0):
         """StackHandle.run_maps_deep over the tiles (nl_group_run_maps_deep): the return value of run_maps."""
-        n = self.width * self.height
-        out, lo, hi = np.zeros(n, np.float32), np.zeros(n, np.uint16), np.zeros(n, np.uint16)
-        cl, ch = C.c_int64(0), C.c_int64(0)
-        capi.check(self._lib.nl_group_run_maps_deep(self._g, int(mode), C.c_float(sigma_low), C.c_float(sigma_high),
-                                                    C.c_float(ref_loc), capi.fptr(out), C.byref(cl), C.byref(ch),
-                                                    _u16ptr(lo), _u16ptr(hi)))
-        return out, cl.value, ch.value, lo, hi
+        return self._run_maps(self._lib.nl_group_run_maps_deep, mode, sigma_low, sigma_high, ref_loc)
 
     def run_linfit_weighted(self, sigma_low=2.75, sigma_high=2.75, ref_loc=0.0, download=True):
         """StackHandle.run_linfit_weighted over the tiles: (result or None, clip_low, clip_high)."""

@@ -8,7 +8,7 @@ columns read 8 ranks per side and pass.  So the rates here scale as 1 / n: per p
 workgroup.  Every array is computed once per process and returned read-only."""
 import numpy as np
 
-import rejmap_ref as ref
+import maps_cases
 
 SIGMAS = (3.0, 3.0)
 TIGHT = (1.2, 1.2)                           # nearly every pixel clips more than the columns hold: the generic pass
@@ -55,13 +55,5 @@ def truth(oracle, n, mode, n_active=None, sigmas=SIGMAS):
     key = (n, mode, n_active, sigmas)
     if key not in _truths:
         fr = np.ascontiguousarray(frames_of(n)[:n if n_active is None else n_active])
-        result, low, high = ref.per_pixel(oracle, mode, fr, None, sigmas[0], sigmas[1], REF_LOC)
-        rc, _, cl, ch, _ = oracle.stack_apply(mode, fr, None, sigmas[0], sigmas[1], REF_LOC)
-        assert rc == 0 and (cl, ch) == (int(low.sum()), int(high.sum()))
-        assert low.max(initial=0) <= 65535 and high.max(initial=0) <= 65535
-        t = ref.Truth(result, int(cl), int(ch), low.astype(np.uint16), high.astype(np.uint16),
-                      (~np.isnan(fr)).sum(0).astype(np.uint16))
-        for a in (t.result, t.reject_low, t.reject_high, t.coverage):
-            a.setflags(write=False)
-        _truths[key] = t
+        _truths[key] = maps_cases.truth_of(oracle, mode, fr, sigmas, REF_LOC)
     return _truths[key]

@@ -21,7 +21,9 @@ import numpy as np
 import pytest
 
 import deepmaps_frames as deep
+import maps_cases as cases
 import rejmap_ref as ref
+from maps_cases import assert_deep_maps as assert_maps, is_deep_maps_name, ref_mismatch
 from nightlight_amd import capi
 from util import RTOL, bits_equal, close_values
 
@@ -40,35 +42,11 @@ DEPTHS = [129, 144, 145, 200, 255, 256, 257, 272, 300, 400, 496, 497, 511, 512]
 
 
 def open_handle(nl, n, row0=0, rows=None):
-    st = nl.StackHandle(n, W, H, row0=row0, rows=rows)
-    st.upload_frames(deep.frames_of(n))
-    return st
-
-
-def is_deep_maps_name(name):
-    return "stack_sigma_mlz_kernel" in name and "maps" in name
+    return cases.open_handle(nl, n, row0, rows, frames=deep.frames_of)
 
 
 def deep_pass(st, mode, sigmas=SIGMAS, **kw):
     return st.run_maps_deep(mode, sigmas[0], sigmas[1], REF_LOC, **kw)
-
-
-def assert_maps(got, t, rows=slice(None)):
-    """got: what a maps pass returned; t: the truth; rows: the pixels to compare.  Maps and totals count for count, the
-    result within RTOL; bit for bit at the pixels the column kernel replays and at the pixel without data."""
-    out, cl, ch, low, high = got
-    assert low.dtype == np.uint16 and high.dtype == np.uint16
-    assert np.array_equal(low[rows], t.reject_low[rows]) and np.array_equal(high[rows], t.reject_high[rows])
-    assert (cl, ch) == (int(low[rows].astype(np.int64).sum()), int(high[rows].astype(np.int64).sum()))
-    assert (cl, ch) == (int(t.reject_low[rows].astype(np.int64).sum()), int(t.reject_high[rows].astype(np.int64).sum()))
-    assert np.all(low[rows].astype(np.int64) + high[rows] <= t.coverage[rows])
-    assert close_values(out[rows], t.result[rows], RTOL), ref_mismatch(out[rows], t.result[rows])
-
-
-def ref_mismatch(got, want):
-    ok = ~np.isnan(want) & (want != got)
-    rel = np.abs(got[ok].astype(np.float64) - want[ok]) / np.abs(want[ok].astype(np.float64))
-    return "%d pixels differ, largest relative difference %g" % (int(ok.sum()), rel.max(initial=0.0))
 
 
 @pytest.mark.parametrize("mode", sorted(MODES))

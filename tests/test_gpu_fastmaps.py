@@ -2,98 +2,24 @@
 the CPU oracle called pixel by pixel (tests/rejmap_ref.py).  The maps and totals are exact equalities; the result is the
 default pass's (util.RTOL), bit-exact on the pixels the exact kernel replays and on the pixel without data.  The frames
 are those of tests/rejmap_ref.py with what sends pixels down the two hand-over paths: a block with half of its frames
-missing and a block that clips more than a zone holds (generic pass), infinite samples (exact replay).  The image is
-41 x 23 = 943 pixels: three full workgroups and a partial one, no multiple of 64.  Every truth is computed once."""
+missing and a block that clips more than a zone holds (generic pass), infinite samples (exact replay): tests/maps_cases.py
+has them, their truths and the comparisons.  The image is 41 x 23 = 943 pixels: three full workgroups and a partial one,
+no multiple of 64.  Every truth is computed once."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
 import rejmap_ref as ref
+from maps_cases import (H, HALF_NAN, INF_PIXELS, NO_DATA, P, REF_LOC, SIGMA_HIGH, SIGMA_LOW, W, assert_exact_maps,
+                        assert_fast_maps, frames_of, is_fast_maps_name, open_handle, truth)
 from nightlight_amd import capi
 from util import RTOL, bits_equal, close_values
 
 pytestmark = pytest.mark.gpu
 
-SIGMA_LOW, SIGMA_HIGH = 2.0, 2.5
-REF_LOC = 123.0
-W, H = 41, 23
-P = W * H
-NO_DATA = 3                                  # rejmap_ref.make_frames: the pixel without data
-HALF_NAN = slice(220, 280)                   # the upper half of the frames is NaN: an aligned frame's border
-HEAVY = slice(300, 320)                      # 10 samples of +400: more clipped than a zone of 8 holds
-INF_PIXELS = (400, 401, 402)                 # +Inf, +Inf, -Inf in one sample each: the exact list
 FRAME_COUNTS = [5, 16, 17, 24, 33, 48, 64, 65, 100, 112, 127, 128]
 MODES = [capi.ST_SIGMA, capi.ST_WINSOR_SIGMA]
-
-_frames, _truths = {}, {}
-
-
-def frames_of(n):
-    """[n, P] float32, read-only: rejmap_ref's frames of n with the hand-over pixels added"""
-    if n not in _frames:
-        f = ref.make_frames(n, W, H).copy()
-        rng = np.random.default_rng(77 + n)
-        f[n // 2:, HALF_NAN] = np.nan
-        k = min(10, n)
-        f[:k, HEAVY] = (1400.0 + 20.0 * rng.standard_normal((k, HEAVY.stop - HEAVY.start))).astype(np.float32)
-        f[1, INF_PIXELS[0]] = np.inf
-        f[2, INF_PIXELS[1]] = np.inf
-        f[0, INF_PIXELS[2]] = -np.inf
-        f.setflags(write=False)
-        _frames[n] = f
-    return _frames[n]
-
-
-Truth = ref.Truth
-
-
-def truth(oracle, n, mode, n_active=None, sigmas=(SIGMA_LOW, SIGMA_HIGH)):
-    """the maps of frames_of(n)[:n_active] from the oracle pixel by pixel, held to its whole-image totals; computed once"""
-    key = (n, mode, n_active, sigmas)
-    if key not in _truths:
-        fr = np.ascontiguousarray(frames_of(n)[:n if n_active is None else n_active])
-        result, low, high = ref.per_pixel(oracle, mode, fr, None, sigmas[0], sigmas[1], REF_LOC)
-        rc, _, cl, ch, _ = oracle.stack_apply(mode, fr, None, sigmas[0], sigmas[1], REF_LOC)
-        assert rc == 0 and (cl, ch) == (int(low.sum()), int(high.sum()))
-        t = Truth(result, int(cl), int(ch), low.astype(np.uint16), high.astype(np.uint16),
-                  (~np.isnan(fr)).sum(0).astype(np.uint16))
-        for a in (t.result, t.reject_low, t.reject_high, t.coverage):
-            a.setflags(write=False)
-        _truths[key] = t
-    return _truths[key]
-
-
-def open_handle(nl, n, row0=0, rows=None):
-    st = nl.StackHandle(n, W, H, row0=row0, rows=rows)
-    st.upload_frames(frames_of(n))
-    return st
-
-
-def assert_fast_maps(got, t, rows=slice(None)):
-    """got: what run_maps(fast=True) returned on the fast engines; t: the truth; rows: the pixels to compare"""
-    out, cl, ch, low, high = got
-    assert low.dtype == np.uint16 and high.dtype == np.uint16
-    assert np.array_equal(low[rows], t.reject_low[rows]) and np.array_equal(high[rows], t.reject_high[rows])
-    sums = (int(t.reject_low[rows].astype(np.int64).sum()), int(t.reject_high[rows].astype(np.int64).sum()))
-    assert (cl, ch) == sums
-    assert close_values(out[rows], t.result[rows], RTOL)
-    exact = np.zeros(P, bool)
-    exact[list(INF_PIXELS) + [NO_DATA]] = True
-    assert bits_equal(out[rows][exact[rows]], t.result[rows][exact[rows]])
-    assert np.all(low[rows].astype(np.int64) + high[rows] <= t.coverage[rows])
-
-
-def assert_exact_maps(got, t, rows=slice(None)):
-    """... on the column kernel: bit for bit"""
-    out, cl, ch, low, high = got
-    assert bits_equal(out[rows], t.result[rows])
-    assert np.array_equal(low[rows], t.reject_low[rows]) and np.array_equal(high[rows], t.reject_high[rows])
-    assert (cl, ch) == (int(t.reject_low[rows].astype(np.int64).sum()), int(t.reject_high[rows].astype(np.int64).sum()))
-
-
-def is_fast_maps_name(name):
-    return "stack_sigma_fast_kernel" in name and "maps" in name
 
 
 @pytest.mark.parametrize("mode", MODES)

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import rejmap_ref as ref
+from maps_cases import assert_exact_maps as assert_maps
 from nightlight_amd import capi
 from util import bits_equal
 
@@ -26,15 +27,6 @@ def open_handle(nl, case, row0=0, rows=None):
     if case.weighted:
         st.set_weights(ref.weights_of(case.frames))
     return st
-
-
-def assert_maps(got, t, rows=slice(None)):
-    """got: what run_maps returned; t: the truth; rows: the pixels to compare"""
-    out, cl, ch, low, high = got
-    assert bits_equal(out[rows], t.result[rows])
-    assert np.array_equal(low[rows], t.reject_low[rows]) and np.array_equal(high[rows], t.reject_high[rows])
-    assert low.dtype == np.uint16 and high.dtype == np.uint16
-    assert (cl, ch) == (int(t.reject_low[rows].astype(np.int64).sum()), int(t.reject_high[rows].astype(np.int64).sum()))
 
 
 @pytest.mark.parametrize("case", ref.CASES, ids=[c.name for c in ref.CASES])

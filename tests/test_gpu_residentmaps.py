@@ -1,7 +1,7 @@
 """GPU: the resident maps pass (include/nlstack_residentmaps.h) -- nl_stack_run_maps_resident /
 nl_group_run_maps_resident -- against the CPU oracle called pixel by pixel (tests/rejmap_ref.py).  For the linear fit
 everything is an exact equality: both kernels are bit-exact, so the result is compared bit for bit, the maps count for
-count.  The frames are those of tests/test_gpu_fastmaps.py (the construction is copied, not imported): rejmap_ref's with a
+count.  The frames are those of tests/test_gpu_fastmaps.py (tests/maps_cases.py): rejmap_ref's with a
 block whose upper half of the frames is missing, a block with ten samples of +400, and three infinite samples, which go
 to the exact list.  The image is 41 x 23 = 943 pixels: three full workgroups and a partial one, no multiple of 64.
 Every truth is computed once per key.
@@ -15,88 +15,24 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import maps_cases as cases
 import rejmap_ref as ref
+from maps_cases import (H, HALF_NAN, INF_PIXELS, NO_DATA, P, REF_LOC, SIGMA_HIGH, SIGMA_LOW, TIGHT, W, assert_exact_maps,
+                        frames_of, is_fast_maps_name, is_linfit_maps_name, open_handle)
 from nightlight_amd import capi
 from util import RTOL, bits_equal, close_values
 
 pytestmark = pytest.mark.gpu
 
-SIGMA_LOW, SIGMA_HIGH = 2.0, 2.5
-TIGHT = (1.2, 1.2)
-REF_LOC = 123.0
-W, H = 41, 23
-P = W * H
-NO_DATA = 3                                  # rejmap_ref.make_frames: the pixel without data
-HALF_NAN = slice(220, 280)                   # the upper half of the frames is NaN: an aligned frame's border
-HEAVY = slice(300, 320)                      # 10 samples of +400
-INF_PIXELS = (400, 401, 402)                 # +Inf, +Inf, -Inf in one sample each: the exact list
 LINFIT = capi.ST_LINEAR_FIT
 # every with_class size of the one-lane kernel and both sides of each boundary (8 | 16 | 32 | 48 | 64 | 96 | 128; the
 # parked 128 class from 97), both lane counts of the multi-lane kernel (2 up to 256 frames, then 4)
 ONE_LANE = [5, 8, 9, 16, 17, 24, 32, 33, 48, 49, 64, 65, 96, 97, 112, 128]
 MULTI_LANE = [129, 200, 257, 300]
 
-_frames, _truths = {}, {}
-
-
-def frames_of(n):
-    """[n, P] float32, read-only: rejmap_ref's frames of n with the hand-over pixels added"""
-    if n not in _frames:
-        f = ref.make_frames(n, W, H).copy()
-        rng = np.random.default_rng(77 + n)
-        f[n // 2:, HALF_NAN] = np.nan
-        k = min(10, n)
-        f[:k, HEAVY] = (1400.0 + 20.0 * rng.standard_normal((k, HEAVY.stop - HEAVY.start))).astype(np.float32)
-        f[1, INF_PIXELS[0]] = np.inf
-        f[2, INF_PIXELS[1]] = np.inf
-        f[0, INF_PIXELS[2]] = -np.inf
-        f.setflags(write=False)
-        _frames[n] = f
-    return _frames[n]
-
-
-Truth = ref.Truth
-
 
 def truth(oracle, n, mode=LINFIT, n_active=None, sigmas=(SIGMA_LOW, SIGMA_HIGH)):
-    """the maps of frames_of(n)[:n_active] from the oracle pixel by pixel, held to its whole-image totals; computed once"""
-    key = (n, mode, n_active, sigmas)
-    if key not in _truths:
-        fr = np.ascontiguousarray(frames_of(n)[:n if n_active is None else n_active])
-        result, low, high = ref.per_pixel(oracle, mode, fr, None, sigmas[0], sigmas[1], REF_LOC)
-        rc, _, cl, ch, _ = oracle.stack_apply(mode, fr, None, sigmas[0], sigmas[1], REF_LOC)
-        assert rc == 0 and (cl, ch) == (int(low.sum()), int(high.sum()))
-        t = Truth(result, int(cl), int(ch), low.astype(np.uint16), high.astype(np.uint16),
-                  (~np.isnan(fr)).sum(0).astype(np.uint16))
-        for a in (t.result, t.reject_low, t.reject_high, t.coverage):
-            a.setflags(write=False)
-        _truths[key] = t
-    return _truths[key]
-
-
-def open_handle(nl, n, row0=0, rows=None):
-    st = nl.StackHandle(n, W, H, row0=row0, rows=rows)
-    st.upload_frames(frames_of(n))
-    return st
-
-
-def assert_exact_maps(got, t, rows=slice(None)):
-    """got: what a maps pass returned; t: the truth; rows: the pixels to compare.  Bit for bit, count for count."""
-    out, cl, ch, low, high = got
-    assert low.dtype == np.uint16 and high.dtype == np.uint16
-    assert bits_equal(out[rows], t.result[rows])
-    assert np.array_equal(low[rows], t.reject_low[rows]) and np.array_equal(high[rows], t.reject_high[rows])
-    assert (cl, ch) == (int(low[rows].astype(np.int64).sum()), int(high[rows].astype(np.int64).sum()))
-    assert (cl, ch) == (int(t.reject_low[rows].astype(np.int64).sum()), int(t.reject_high[rows].astype(np.int64).sum()))
-    assert np.all(low[rows].astype(np.int64) + high[rows] <= t.coverage[rows])
-
-
-def is_linfit_maps_name(name, n):
-    return ("stack_linfit_fast_kernel" if n <= 128 else "stack_linfit_ml_kernel") in name and "maps" in name
-
-
-def is_fast_maps_name(name):
-    return "stack_sigma_fast_kernel" in name and "maps" in name
+    return cases.truth(oracle, n, mode, n_active, sigmas)
 
 
 def resident(st, sigmas=(SIGMA_LOW, SIGMA_HIGH), mode=LINFIT, **kw):

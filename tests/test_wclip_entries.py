@@ -1,7 +1,7 @@
 """The entries of the weighted clip pass whose weights follow their frames: include/nlstack_wclip.h (part of the
 interface nlstack.h includes) declares exactly capi.WCLIP_EXPORTS, the library exports them, every argument check that
 ends in front of the device gives its code and message (a characterisation table in the form of
-tests/test_rejmap_entries.py), no entry gives a result where no handle can be made, and the host operator's JSON
+tests/test_maps_entries.py), no entry gives a result where no handle can be made, and the host operator's JSON
 carries the switch only when it is set.
 
 What can be told from the mode alone -- an id out of range, the median, the mean, MAD sigma, the linear fit -- is told in

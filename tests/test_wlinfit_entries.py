@@ -1,6 +1,6 @@
 """The entries of the weighted linear-fit pass: include/nlstack_wlinfit.h (part of the interface nlstack.h includes)
 declares exactly capi.WLINFIT_EXPORTS, the library exports them, every argument check that ends in front of the device
-gives its code and message (a characterisation table in the form of tests/test_rejmap_entries.py), and the host
+gives its code and message (a characterisation table in the form of tests/test_maps_entries.py), and the host
 operator's JSON carries the switch only when it is set."""
 import ctypes as C
 import json

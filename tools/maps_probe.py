@@ -60,63 +60,122 @@ def stats(ms):
     return "median %.3f ms, min %.3f ms" % (float(np.median(ms)), float(np.min(ms)))
 
 
+class Report:
+    """the lines of one mode: printed as they come, and DIR/name rewritten with all of them so far"""
+
+    def __init__(self, out, name):
+        self.lines, self.out, self.name = [], out, name
+        try:
+            import torch
+            self("device: %s" % torch.cuda.get_device_name(0))
+        except Exception:
+            pass
+
+    def __call__(self, line):
+        print(line, flush=True)
+        self.lines.append(line)
+        if self.out:
+            os.makedirs(self.out, exist_ok=True)
+            with open(os.path.join(self.out, self.name), "w") as f:
+                f.write("\n".join(self.lines) + "\n")
+
+
+class Timing:
+    """the runs of one pass: whole-pass and dominant-kernel times, and what the handle said after the last of them"""
+
+    def __init__(self):
+        self.ms, self.dom = [], []
+        self.kernel, self.protocol, self.exact_list, self.generic_list = "", 0, 0, 0
+
+    med = property(lambda self: float(np.median(self.ms)))
+    med_dom = property(lambda self: float(np.median(self.dom)))
+    min_dom = property(lambda self: float(np.min(self.dom)))
+
+
+def measure(st, passes, warm, reps, interleaved=False, fewer=None):
+    """passes: (label, fn) or (label, fn, developer flags); fn() runs one pass and returns (whole pass ms, dominant kernel
+    ms).  Block by block -- warm + reps runs of one pass, then the next -- or interleaved: one run of each per repetition.
+    fewer: {label: (warm-up runs, runs)} of the passes that run less often.  Returns {label: Timing}."""
+    passes = [(p + (0,))[:3] for p in passes]
+    result = {label: Timing() for label, _, _ in passes}
+
+    def run(label, fn, flags, keep):
+        st.set_dev_flags(flags)
+        try:
+            t = fn()
+        finally:
+            st.set_dev_flags(0)
+        r = result[label]
+        if keep:
+            r.ms.append(t[0])
+            r.dom.append(t[1])
+        r.kernel, r.protocol = st.last_kernel_name, st.last_pass_protocol
+        r.exact_list, r.generic_list = st.last_fallback_pixels, st.last_generic_pixels
+
+    def wanted(label, i):
+        w, n = (fewer or {}).get(label, (warm, reps))
+        return -w <= i < n
+
+    if interleaved:
+        for i in range(-warm, reps):
+            for label, fn, flags in passes:
+                if wanted(label, i):
+                    run(label, fn, flags, i >= 0)
+    else:
+        for label, fn, flags in passes:
+            for i in range(-warm, reps):
+                if wanted(label, i):
+                    run(label, fn, flags, i >= 0)
+    return result
+
+
+def pass_fns(st, L, mode, sigma):
+    """(default pass, maps pass of an entry) on the handle: the result stays on the device, every host pointer NULL"""
+    from nightlight_amd import capi
+
+    def default_pass():
+        st.run(mode, sigma, sigma, 0.0, fetch=False)
+        return st.pass_times(0)
+
+    def maps_pass(entry):
+        def fn():
+            capi.check(getattr(L, entry)(st._h, mode, sigma, sigma, 0.0, None, None, None, None, None))
+            return st.pass_times(0)
+        return fn
+
+    return default_pass, maps_pass
+
+
 def fastmaps(a):
     import nightlight_amd as nl
     from nightlight_amd import capi
     L = capi.load()
     warm, n = 3, 128
-    lines = []
-    try:
-        import torch
-        lines.append("device: %s" % torch.cuda.get_device_name(0))
-    except Exception:
-        pass
-    lines.append("%d frames of %d x %d resident, sigma %.2f / %.2f; %d runs after %d warm-up runs; GPU time of the whole pass"
-                 % (n, a.width, a.height, a.sigma, a.sigma, a.reps, warm))
+    emit = Report(a.out, "fastmaps_probe.txt")
+    emit("%d frames of %d x %d resident, sigma %.2f / %.2f; %d runs after %d warm-up runs; GPU time of the whole pass"
+         % (n, a.width, a.height, a.sigma, a.sigma, a.reps, warm))
     with nl.StackHandle(n, a.width, a.height) as st:
         st.fill_synthetic(seed=7)
         for active in (128, 24):
             st.set_active_frames(active)
             for mode in (capi.ST_SIGMA, capi.ST_WINSOR_SIGMA):
-                def default_pass():
-                    st.run(mode, a.sigma, a.sigma, 0.0, fetch=False)
-                    return st.pass_times(0)
-
-                def fast_maps_pass():
-                    capi.check(L.nl_stack_run_maps_fast(st._h, mode, a.sigma, a.sigma, 0.0, None, None, None, None, None))
-                    return st.pass_times(0)
-
-                def column_maps_pass():
-                    capi.check(L.nl_stack_run_maps(st._h, mode, a.sigma, a.sigma, 0.0, None, None, None, None, None))
-                    return st.pass_times(0)
-
-                lines.append("-- %d active frames, mode %d" % (active, mode))
-                med, med_dom = {}, {}
-                for label, fn, flags in (("default pass", default_pass, 0), ("plain default pass", default_pass, 1),
-                                         ("fast maps pass", fast_maps_pass, 0), ("column maps pass", column_maps_pass, 0)):
-                    st.set_dev_flags(flags)
-                    both = [fn() for _ in range(warm + a.reps)][warm:]
-                    st.set_dev_flags(0)
-                    ms, dom = [t[0] for t in both], [t[1] for t in both]
-                    med[label], med_dom[label] = float(np.median(ms)), float(np.median(dom))
-                    tail = "; dominant kernel median %.3f ms" % med_dom[label]
+                default_pass, maps_pass = pass_fns(st, L, mode, a.sigma)
+                emit("-- %d active frames, mode %d" % (active, mode))
+                t = measure(st, (("default pass", default_pass), ("plain default pass", default_pass, 1),
+                                 ("fast maps pass", maps_pass("nl_stack_run_maps_fast")),
+                                 ("column maps pass", maps_pass("nl_stack_run_maps"))), warm, a.reps)
+                for label, r in t.items():
+                    tail = "; dominant kernel median %.3f ms" % r.med_dom
                     if label == "fast maps pass":
-                        tail += "; exact list %d, generic list %d" % (st.last_fallback_pixels, st.last_generic_pixels)
-                    lines.append("%-19s %-68s %s; protocol %d%s" % (label, st.last_kernel_name, stats(ms), st.last_pass_protocol, tail))
-                lines.append("fast maps / plain default = %.3f (one more 4-byte store per %d bytes read: %.4f); "
-                             "fast maps / default = %.3f; column maps / fast maps = %.1f"
-                             % (med["fast maps pass"] / med["plain default pass"], 4 * active, 1.0 + 1.0 / active,
-                                med["fast maps pass"] / med["default pass"], med["column maps pass"] / med["fast maps pass"]))
-                lines.append("dominant kernels, fast maps / plain default = %.3f; behind the dominant kernel: %.3f ms against %.3f ms"
-                             % (med_dom["fast maps pass"] / med_dom["plain default pass"],
-                                med["fast maps pass"] - med_dom["fast maps pass"],
-                                med["plain default pass"] - med_dom["plain default pass"]))
-    text = "\n".join(lines)
-    print(text)
-    if a.out:
-        os.makedirs(a.out, exist_ok=True)
-        with open(os.path.join(a.out, "fastmaps_probe.txt"), "w") as f:
-            f.write(text + "\n")
+                        tail += "; exact list %d, generic list %d" % (r.exact_list, r.generic_list)
+                    emit("%-19s %-68s %s; protocol %d%s" % (label, r.kernel, stats(r.ms), r.protocol, tail))
+                fast, plain = t["fast maps pass"], t["plain default pass"]
+                emit("fast maps / plain default = %.3f (one more 4-byte store per %d bytes read: %.4f); "
+                     "fast maps / default = %.3f; column maps / fast maps = %.1f"
+                     % (fast.med / plain.med, 4 * active, 1.0 + 1.0 / active, fast.med / t["default pass"].med,
+                        t["column maps pass"].med / fast.med))
+                emit("dominant kernels, fast maps / plain default = %.3f; behind the dominant kernel: %.3f ms against %.3f ms"
+                     % (fast.med_dom / plain.med_dom, fast.med - fast.med_dom, plain.med - plain.med_dom))
 
 
 def linfit(a):
@@ -124,60 +183,35 @@ def linfit(a):
     from nightlight_amd import capi
     L = capi.load()
     warm, mode = 3, capi.ST_LINEAR_FIT
-    lines = []
-    try:
-        import torch
-        lines.append("device: %s" % torch.cuda.get_device_name(0))
-    except Exception:
-        pass
-    lines.append("linear fit, frames of %d x %d resident, sigma %.2f / %.2f; %d runs after %d warm-up runs; GPU time of the whole pass"
-                 % (a.width, a.height, a.sigma, a.sigma, a.reps, warm))
+    emit = Report(a.out, "linfitmaps_probe.txt")
+    emit("linear fit, frames of %d x %d resident, sigma %.2f / %.2f; %d runs after %d warm-up runs; GPU time of the whole pass"
+         % (a.width, a.height, a.sigma, a.sigma, a.reps, warm))
     for n in [int(x) for x in a.linfit_frames.split(",")]:
-        lines.append("-- %d frames" % n)
+        emit("-- %d frames" % n)
         try:
             st = nl.StackHandle(n, a.width, a.height)
         except capi.NlError as e:
-            lines.append("no handle of %d frames: %s" % (n, e))
+            emit("no handle of %d frames: %s" % (n, e))
             continue
         with st:
             st.fill_synthetic(seed=7)
-
-            def default_pass():
-                st.run(mode, a.sigma, a.sigma, 0.0, fetch=False)
-                return st.pass_times(0)
-
-            def resident_maps_pass():
-                capi.check(L.nl_stack_run_maps_resident(st._h, mode, a.sigma, a.sigma, 0.0, None, None, None, None, None))
-                return st.pass_times(0)
-
-            def column_maps_pass():
-                capi.check(L.nl_stack_run_maps(st._h, mode, a.sigma, a.sigma, 0.0, None, None, None, None, None))
-                return st.pass_times(0)
-
-            med, med_dom = {}, {}
-            for label, fn in (("default pass", default_pass), ("resident maps pass", resident_maps_pass),
-                              ("default pass again", default_pass), ("column maps pass", column_maps_pass)):
-                both = [fn() for _ in range(warm + a.reps)][warm:]
-                ms, dom = [t[0] for t in both], [t[1] for t in both]
-                med[label], med_dom[label] = float(np.median(ms)), float(np.median(dom))
-                tail = "; dominant kernel median %.3f ms, min %.3f ms" % (med_dom[label], float(np.min(dom)))
+            default_pass, maps_pass = pass_fns(st, L, mode, a.sigma)
+            # (block by block, one at a time: the stage lengths are read behind each block)
+            t = {}
+            for label, fn in (("default pass", default_pass), ("resident maps pass", maps_pass("nl_stack_run_maps_resident")),
+                              ("default pass again", default_pass), ("column maps pass", maps_pass("nl_stack_run_maps"))):
+                r = t[label] = measure(st, ((label, fn),), warm, a.reps)[label]
+                tail = "; dominant kernel median %.3f ms, min %.3f ms" % (r.med_dom, r.min_dom)
                 if label != "column maps pass":
-                    tail += "; exact list %d, stages %r" % (st.last_fallback_pixels, st.linfit_stage_counts[:3])
-                lines.append("%-19s %-44s %s; protocol %d%s" % (label, st.last_kernel_name, stats(ms), st.last_pass_protocol, tail))
-            base = 0.5 * (med["default pass"] + med["default pass again"])
-            lines.append("resident maps / default = %.4f (one more 4-byte store per %d bytes read: %.4f; default again / default = %.4f); "
-                         "column maps / resident maps = %.1f"
-                         % (med["resident maps pass"] / base, 4 * n, 1.0 + 1.0 / n, med["default pass again"] / med["default pass"],
-                            med["column maps pass"] / med["resident maps pass"]))
-            lines.append("dominant kernels, resident maps / default = %.4f; behind the dominant kernel: %.3f ms against %.3f ms"
-                         % (med_dom["resident maps pass"] / (0.5 * (med_dom["default pass"] + med_dom["default pass again"])),
-                            med["resident maps pass"] - med_dom["resident maps pass"], med["default pass"] - med_dom["default pass"]))
-    text = "\n".join(lines)
-    print(text)
-    if a.out:
-        os.makedirs(a.out, exist_ok=True)
-        with open(os.path.join(a.out, "linfitmaps_probe.txt"), "w") as f:
-            f.write(text + "\n")
+                    tail += "; exact list %d, stages %r" % (r.exact_list, st.linfit_stage_counts[:3])
+                emit("%-19s %-44s %s; protocol %d%s" % (label, r.kernel, stats(r.ms), r.protocol, tail))
+            first, again, res = t["default pass"], t["default pass again"], t["resident maps pass"]
+            emit("resident maps / default = %.4f (one more 4-byte store per %d bytes read: %.4f; default again / default = %.4f); "
+                 "column maps / resident maps = %.1f"
+                 % (res.med / (0.5 * (first.med + again.med)), 4 * n, 1.0 + 1.0 / n, again.med / first.med,
+                    t["column maps pass"].med / res.med))
+            emit("dominant kernels, resident maps / default = %.4f; behind the dominant kernel: %.3f ms against %.3f ms"
+                 % (res.med_dom / (0.5 * (first.med_dom + again.med_dom)), res.med - res.med_dom, first.med - first.med_dom))
 
 
 def deep(a):
@@ -185,21 +219,7 @@ def deep(a):
     from nightlight_amd import capi
     L = capi.load()
     warm = 3
-    lines = []
-
-    def emit(line):
-        print(line, flush=True)
-        lines.append(line)
-        if a.out:
-            os.makedirs(a.out, exist_ok=True)
-            with open(os.path.join(a.out, "deepmaps_probe.txt"), "w") as f:
-                f.write("\n".join(lines) + "\n")
-
-    try:
-        import torch
-        emit("device: %s" % torch.cuda.get_device_name(0))
-    except Exception:
-        pass
+    emit = Report(a.out, "deepmaps_probe.txt")
     emit("sigma %.2f / %.2f, frames resident; per workload %d interleaved repetitions after %d warm-up runs (column maps pass: "
          "%d after 1); GPU time of the whole pass" % (a.sigma, a.sigma, a.reps, warm, a.column_reps))
     for spec in a.deep_workloads.split(","):
@@ -214,61 +234,63 @@ def deep(a):
             continue
         with st:
             st.fill_synthetic(seed=7)
-
-            def default_pass():
-                st.run(mode, a.sigma, a.sigma, 0.0, fetch=False)
-                return st.pass_times(0)
+            default_pass, maps_pass = pass_fns(st, L, mode, a.sigma)
 
             def steady_default_pass():
                 # (twice, the second one timed: behind a plain-protocol pass a fused pass first clears both scratch sets)
                 default_pass()
                 return default_pass()
 
-            def plain_default_pass():
-                st.set_dev_flags(1)
-                try:
-                    return default_pass()
-                finally:
-                    st.set_dev_flags(0)
-
-            def deep_maps_pass():
-                capi.check(L.nl_stack_run_maps_deep(st._h, mode, a.sigma, a.sigma, 0.0, None, None, None, None, None))
-                return st.pass_times(0)
-
-            def column_maps_pass():
-                capi.check(L.nl_stack_run_maps(st._h, mode, a.sigma, a.sigma, 0.0, None, None, None, None, None))
-                return st.pass_times(0)
-
-            passes = (("default pass", steady_default_pass),("plain default pass", plain_default_pass),
-                      ("deep maps pass", deep_maps_pass), ("column maps pass", column_maps_pass))
-            times = {label: [] for label, _ in passes}
-            facts = {}
-            for r in range(-warm, a.reps):
-                for label, fn in passes:
-                    if label == "column maps pass" and not -1 <= r < a.column_reps:
-                        continue
-                    t = fn()
-                    if r >= 0:
-                        times[label].append(t)
-                    tail = "; protocol %d" % st.last_pass_protocol
-                    if label == "deep maps pass":
-                        tail += "; exact list %d, generic list %d" % (st.last_fallback_pixels, st.last_generic_pixels)
-                    facts[label] = (st.last_kernel_name, tail)
-            med, med_dom = {}, {}
-            for label, _ in passes:
-                ms, dom = [t[0] for t in times[label]], [t[1] for t in times[label]]
-                med[label], med_dom[label] = float(np.median(ms)), float(np.median(dom))
+            t = measure(st, (("default pass", steady_default_pass), ("plain default pass", default_pass, 1),
+                             ("deep maps pass", maps_pass("nl_stack_run_maps_deep")),
+                             ("column maps pass", maps_pass("nl_stack_run_maps"))), warm, a.reps, interleaved=True,
+                        fewer={"column maps pass": (1, a.column_reps)})
+            for label, r in t.items():
+                tail = "; protocol %d" % r.protocol
+                if label == "deep maps pass":
+                    tail += "; exact list %d, generic list %d" % (r.exact_list, r.generic_list)
                 emit("%-19s %-50s %s (%d runs)%s; dominant kernel median %.3f ms, min %.3f ms"
-                     % (label, facts[label][0], stats(ms), len(ms), facts[label][1], med_dom[label], float(np.min(dom))))
+                     % (label, r.kernel, stats(r.ms), len(r.ms), tail, r.med_dom, r.min_dom))
+            dm, plain, default = t["deep maps pass"], t["plain default pass"], t["default pass"]
             emit("deep maps / default = %.3f; deep maps / plain default = %.3f (one more 4-byte store per %d bytes read: %.4f); "
                  "column maps / deep maps = %.1f"
-                 % (med["deep maps pass"] / med["default pass"], med["deep maps pass"] / med["plain default pass"], 4 * n,
-                    1.0 + 1.0 / n, med["column maps pass"] / med["deep maps pass"]))
+                 % (dm.med / default.med, dm.med / plain.med, 4 * n, 1.0 + 1.0 / n, t["column maps pass"].med / dm.med))
             emit("dominant kernels, deep maps / plain default = %.4f, deep maps / default = %.4f; behind the dominant kernel: "
                  "%.3f ms (deep maps), %.3f ms (plain default), %.3f ms (default)"
-                 % (med_dom["deep maps pass"] / med_dom["plain default pass"], med_dom["deep maps pass"] / med_dom["default pass"],
-                    med["deep maps pass"] - med_dom["deep maps pass"], med["plain default pass"] - med_dom["plain default pass"],
-                    med["default pass"] - med_dom["default pass"]))
+                 % (dm.med_dom / plain.med_dom, dm.med_dom / default.med_dom, dm.med - dm.med_dom, plain.med - plain.med_dom,
+                    default.med - default.med_dom))
+
+
+def column(a):
+    import nightlight_amd as nl
+    from nightlight_amd import capi
+    L = capi.load()
+    warm = 3
+    emit = Report(a.out, "maps_probe.txt")
+    emit("%d frames of %d x %d, mode %d, sigma %.2f / %.2f; %d runs after %d warm-up runs"
+         % (a.frames, a.width, a.height, a.mode, a.sigma, a.sigma, a.reps, warm))
+    with nl.StackHandle(a.frames, a.width, a.height) as st:
+        st.fill_synthetic(seed=7)
+        cov = np.zeros(a.width * a.height, np.uint16)
+        default_pass, maps_pass = pass_fns(st, L, a.mode, a.sigma)
+
+        def mean_pass():
+            st.run(capi.ST_MEAN, a.sigma, a.sigma, 0.0, fetch=False)
+            return st.pass_times(0)
+
+        def coverage():
+            st.coverage(out=cov)
+            return st.last_coverage_ms, st.last_coverage_ms
+
+        t = measure(st, (("default pass", default_pass), ("maps pass", maps_pass("nl_stack_run_maps")), ("mean pass", mean_pass),
+                         ("coverage", coverage)), warm, a.reps)
+        for label, r in t.items():
+            emit("%-13s %-42s %s" % (label, "stack_coverage_kernel" if label == "coverage" else r.kernel, stats(r.ms)))
+        read = 4.0 * a.frames * a.width * a.height
+        emit("coverage / mean pass = %.3f; coverage reads %.2f GB: %.2f TB/s; maps pass / default pass = %.1f"
+             % (t["coverage"].med / t["mean pass"].med, read / 1e9, read / t["coverage"].med / 1e9,
+                t["maps pass"].med / t["default pass"].med))
+        emit("coverage: %d ... %d frames per pixel" % (int(cov.min()), int(cov.max())))
 
 
 def main():
@@ -287,62 +309,7 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    if a.fastmaps:
-        return fastmaps(a)
-    if a.linfit:
-        return linfit(a)
-    if a.deep:
-        return deep(a)
-    import nightlight_amd as nl
-    from nightlight_amd import capi
-    L = capi.load()
-    warm = 3
-    lines = []
-    try:
-        import torch
-        lines.append("device: %s" % torch.cuda.get_device_name(0))
-    except Exception:
-        pass
-    lines.append("%d frames of %d x %d, mode %d, sigma %.2f / %.2f; %d runs after %d warm-up runs"
-                 % (a.frames, a.width, a.height, a.mode, a.sigma, a.sigma, a.reps, warm))
-    with nl.StackHandle(a.frames, a.width, a.height) as st:
-        st.fill_synthetic(seed=7)
-        cov = np.zeros(a.width * a.height, np.uint16)
-
-        def default_pass():
-            st.run(a.mode, a.sigma, a.sigma, 0.0, fetch=False)
-            return st.pass_times(0)[0]
-
-        def maps_pass():
-            capi.check(L.nl_stack_run_maps(st._h, a.mode, a.sigma, a.sigma, 0.0, None, None, None, None, None))
-            return st.pass_times(0)[0]
-
-        def mean_pass():
-            st.run(capi.ST_MEAN, a.sigma, a.sigma, 0.0, fetch=False)
-            return st.pass_times(0)[0]
-
-        def coverage():
-            st.coverage(out=cov)
-            return st.last_coverage_ms
-
-        times = {}
-        for label, fn in (("default pass", default_pass), ("maps pass", maps_pass), ("mean pass", mean_pass),
-                          ("coverage", coverage)):
-            ms = [fn() for _ in range(warm + a.reps)][warm:]
-            times[label] = float(np.median(ms))
-            kernel = "stack_coverage_kernel" if label == "coverage" else st.last_kernel_name
-            lines.append("%-13s %-42s %s" % (label, kernel, stats(ms)))
-        read = 4.0 * a.frames * a.width * a.height
-        lines.append("coverage / mean pass = %.3f; coverage reads %.2f GB: %.2f TB/s; maps pass / default pass = %.1f"
-                     % (times["coverage"] / times["mean pass"], read / 1e9, read / times["coverage"] / 1e9,
-                        times["maps pass"] / times["default pass"]))
-        lines.append("coverage: %d ... %d frames per pixel" % (int(cov.min()), int(cov.max())))
-    text = "\n".join(lines)
-    print(text)
-    if a.out:
-        os.makedirs(a.out, exist_ok=True)
-        with open(os.path.join(a.out, "maps_probe.txt"), "w") as f:
-            f.write(text + "\n")
+    return (fastmaps if a.fastmaps else linfit if a.linfit else deep if a.deep else column)(a)
 
 
 if __name__ == "__main__":
