@@ -6,6 +6,7 @@
 #include <utility>
 
 #include "stack_kernels.h"
+#include "wave_lists.hpp"
 
 namespace nl {
 
@@ -76,11 +77,6 @@ __device__ __forceinline__ void fused_collect_slots(const StackArgs &p, unsigned
             if (hi) atomicAdd(p.final + 1, hi);
         }
     }
-}
-// where a kernel that runs AFTER the dominant one adds its clip counts: the totals, or (plain protocol) a shard
-__device__ __forceinline__ unsigned long long *clip_slot(const StackArgs &p, unsigned block)
-{
-    return p.final ? p.final : p.partial + 2 * (size_t)(block % kClipSlots);
 }
 
 // compile-time loops: every index is a constant, so register columns never

@@ -16,6 +16,11 @@ __device__ __forceinline__ T wave_sum(T v)
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
     return v;
 }
+// number of lanes of a ballot below `lane`: a flagged lane's place among the wave's flagged lanes
+__device__ __forceinline__ unsigned lane_rank(unsigned long long mask, int lane)
+{
+    return (unsigned)__popcll(mask & ((1ull << lane) - 1ull));
+}
 // (fminf / fmaxf: a NaN loses against a number)
 __device__ __forceinline__ float wave_min(float v)
 {

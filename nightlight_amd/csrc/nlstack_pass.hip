@@ -280,6 +280,12 @@ static hipError_t launch_columns(Columns variant, int mode, bool weighted, const
     return nl::launch_stack_exact(mode, weighted, a, lanes, grid, lds, stream, name, variant == Columns::Maps);
 }
 
+// how a pass of the plain protocol ends: the sharded clip counts (d_partial) -> the pass's totals (d_counters)
+static hipError_t reduce_clip_slots(nl_stack *h)
+{
+    return nl::launch_reduce_counters(h->d_partial, nl::kClipSlots, h->d_counters, h->stream);
+}
+
 // ... over the exact list (d_fb_list), kListLanes pixels per wave
 static int replay_list(nl_stack *h, int mode, bool weighted, const nl::StackArgs &a, Columns variant = Columns::Plain)
 {
@@ -409,7 +415,7 @@ static int run_listed(nl_stack *h, const PassSetup &p, PassFacts *facts)
     }
     const int rc = replay_list(h, p.mode, p.weighted, a, p.maps() ? Columns::Maps : Columns::Plain);
     if (rc != NL_OK) return rc;
-    NL_HIP(nl::launch_reduce_counters(h->d_partial, nl::kClipSlots, h->d_counters, h->stream));
+    NL_HIP(reduce_clip_slots(h));
     facts->has_counters = true;
     facts->used_fast = true;
     return NL_OK;
@@ -605,7 +611,7 @@ static int run_sigma_maps(nl_stack *h, const PassSetup &p, PassFacts *facts)
     else          NL_HIP(nl::launch_stack_sigma_mlg(a, nl::over_generic_list(nl::whole_tile(f)), nl::ml_generic_grid(a.n_frames, 0), h->stream, winsor, true));
     const int rc = replay_list(h, p.mode, false, a, Columns::Maps);
     if (rc != NL_OK) return rc;
-    NL_HIP(nl::launch_reduce_counters(h->d_partial, nl::kClipSlots, h->d_counters, h->stream));
+    NL_HIP(reduce_clip_slots(h));
     facts->has_counters = true;
     facts->used_fast = true;
     return NL_OK;
@@ -622,7 +628,7 @@ static int run_weighted_tile(nl_stack *h, const PassSetup &p, PassFacts *facts)
     const int64_t g = tiles < (1 << 20) ? tiles : (1 << 20);
     NL_HIP(nl::launch_stack_sigma_tile(p.mode, p.a, (int)g, h->stream, &h->last_kernel));
     NL_HIP(hipEventRecord(h->ev_dom1, h->stream));
-    NL_HIP(nl::launch_reduce_counters(h->d_partial, nl::kClipSlots, h->d_counters, h->stream));
+    NL_HIP(reduce_clip_slots(h));
     facts->has_counters = true;
     return NL_OK;
 }
@@ -644,7 +650,7 @@ static int run_dense_replay(nl_stack *h, const PassSetup &p, PassFacts *facts)
     if (p.mode == NL_ST_MEDIAN) NL_HIP(nl::launch_stack_median_coop(a, (int)g, h->stream, &h->last_kernel));
     else                        NL_HIP(nl::launch_stack_sigma_coop(p.mode, a, (int)g, h->stream, &h->last_kernel));
     NL_HIP(hipEventRecord(h->ev_dom1, h->stream));
-    NL_HIP(nl::launch_reduce_counters(h->d_partial, nl::kClipSlots, h->d_counters, h->stream));
+    NL_HIP(reduce_clip_slots(h));
     facts->has_counters = p.mode != NL_ST_MEDIAN;
     return NL_OK;
 }
@@ -654,7 +660,7 @@ static int run_exact_columns(nl_stack *h, const PassSetup &p, PassFacts *facts)
 {
     const int rc = columns_over_tile(h, p.mode, p.weighted, p.a, p.maps() ? Columns::Maps : Columns::Plain);
     if (rc != NL_OK) return rc;
-    NL_HIP(nl::launch_reduce_counters(h->d_partial, nl::kClipSlots, h->d_counters, h->stream));
+    NL_HIP(reduce_clip_slots(h));
     facts->has_counters = p.mode != NL_ST_MEDIAN;
     return NL_OK;
 }
@@ -676,7 +682,7 @@ static int run_linfit_weighted(nl_stack *h, const PassSetup &p, PassFacts *facts
         const int rc = columns_over_tile(h, p.mode, true, a);
         if (rc != NL_OK) return rc;
     }
-    NL_HIP(nl::launch_reduce_counters(h->d_partial, nl::kClipSlots, h->d_counters, h->stream));
+    NL_HIP(reduce_clip_slots(h));
     facts->has_counters = true;
     return NL_OK;
 }
@@ -723,7 +729,7 @@ static int run_clip_weighted(nl_stack *h, const PassSetup &p, PassFacts *facts)
     a.nrounds = nullptr;
     const int rc = streamed ? replay_list(h, p.mode, false, a, Columns::Follow) : columns_over_tile(h, p.mode, false, a, Columns::Follow);
     if (rc != NL_OK) return rc;
-    NL_HIP(nl::launch_reduce_counters(h->d_partial, nl::kClipSlots, h->d_counters, h->stream));
+    NL_HIP(reduce_clip_slots(h));
     facts->has_counters = true;
     return NL_OK;
 }

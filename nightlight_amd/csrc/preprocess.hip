@@ -205,10 +205,7 @@ __global__ __launch_bounds__(kBpThreads) void bp_classify_kernel(float *data, co
             total += s_wave[w];
             removed += s_bad[w];
         }
-        if (chained) {
-            const unsigned rank = (unsigned)__popcll(ch_mask & ((1ull << lane) - 1ull));
-            seg[base + before + rank] = (unsigned)i;
-        }
+        if (chained) seg[base + before + lane_rank(ch_mask, lane)] = (unsigned)i;
         listed += total;
         __syncthreads();                                   // s_wave / s_bad are rewritten by the next step
     }

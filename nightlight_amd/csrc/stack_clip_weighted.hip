@@ -25,6 +25,7 @@
 // here, on the data.  A pixel with no round on record, without samples, or with an incomplete record is appended to the
 // exact list; nothing is stored or counted for it.
 #include "launch_common.hpp"
+#include "wave_lists.hpp"
 #include "wclip_common.hpp"
 
 namespace nl {
@@ -146,7 +147,7 @@ __global__ __launch_bounds__(256) void stack_clip_weighted_kernel(StackArgs p, F
                 unsigned at = 0;
                 if (lane == 0) at = atomicAdd(q.fb_count, (unsigned)__popcll(em));
                 at = __shfl(at, 0, 64);
-                const unsigned slot = at + (unsigned)__popcll(em & ((1ull << lane) - 1ull));
+                const unsigned slot = at + lane_rank(em, lane);
                 if (to_exact && slot < q.fb_capacity) q.fb_list[slot] = (unsigned)(pix0 + j);
             }
         }
@@ -161,11 +162,9 @@ __global__ __launch_bounds__(256) void stack_clip_weighted_kernel(StackArgs p, F
     if (lane == 0) { s_lo[threadIdx.x >> 6] = c_lo; s_hi[threadIdx.x >> 6] = c_hi; }
     __syncthreads();
     if (threadIdx.x == 0) {
-        const int t_lo = s_lo[0] + s_lo[1] + s_lo[2] + s_lo[3];
+        const int t_lo = s_lo[0] + s_lo[1] + s_lo[2] + s_lo[3];      // (four waves: the launcher starts 256 threads)
         const int t_hi = s_hi[0] + s_hi[1] + s_hi[2] + s_hi[3];
-        unsigned long long *slot = p.partial + 2 * (size_t)(blockIdx.x % kClipSlots);
-        if (t_lo) atomicAdd(slot + 0, (unsigned long long)t_lo);
-        if (t_hi) atomicAdd(slot + 1, (unsigned long long)t_hi);
+        add_clip_totals(partial_slot(p, blockIdx.x), t_lo, t_hi);
     }
 }
 

@@ -21,6 +21,7 @@
 // exact form the kernel is limited by per-lane LDS latency and VALU issue,
 // see DESIGN.md section 4.
 #include "launch_common.hpp"
+#include "wave_lists.hpp"
 #include "wclip_common.hpp"
 
 namespace nl {
@@ -233,13 +234,6 @@ __device__ void bitonic_sort_keyed(Col<S> a, Col<S> b, int n_pad)
             }
         }
     }
-}
-
-__device__ __forceinline__ int wave_sum(int v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
 }
 
 // The weighted clip pass whose weights follow their frames (include/nlstack_wclip.h; no counterpart in the
@@ -505,15 +499,8 @@ __global__ __launch_bounds__(64) void stack_exact_kernel(StackArgs p)
         if (MAPS && on) p.reject_map[pix] = (unsigned)(c_lo - c_lo0) | ((unsigned)(c_hi - c_hi0) << 16);
     }
 
-    // clip totals (stack.go:193-198): wave sum -> one integer atomic per
-    // workgroup into kClipSlots sharded accumulators (integer adds commute:
-    // the totals are deterministic), summed by reduce_counters_kernel
     const int t_lo = wave_sum(c_lo), t_hi = wave_sum(c_hi);
-    if (lane == 0) {
-        unsigned long long *slot = p.partial + 2 * (size_t)(blockIdx.x % kClipSlots);
-        if (t_lo) atomicAdd(slot + 0, (unsigned long long)t_lo);
-        if (t_hi) atomicAdd(slot + 1, (unsigned long long)t_hi);
-    }
+    if (lane == 0) add_clip_totals(partial_slot(p, blockIdx.x), t_lo, t_hi);
 }
 
 // zero_after: the scratch set goes back to all zeros behind the sums -- the clip slots and the two words of list

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "stack_kernels.h"
+#include "wave_lists.hpp"
 
 #ifndef NL_T0
 #define NL_T0() do {} while (0)
@@ -602,9 +603,7 @@ __device__ __forceinline__ void coop_body(const StackArgs &p, float *a, const un
         // fused pass protocol (StackArgs::final): straight to the totals; the replay of the generic pass's
         // additions is the last kernel of a pass and leaves the list lengths behind them ({exact | generic << 32}:
         // the scratch layout of nlstack_api.hip) -- read back by nl_stack_finish with the totals
-        unsigned long long *slot = p.final ? p.final : p.partial + 2 * (size_t)(block % kClipSlots);
-        if (c_lo) atomicAdd(slot + 0, (unsigned long long)c_lo);
-        if (c_hi) atomicAdd(slot + 1, (unsigned long long)c_hi);
+        add_clip_totals(clip_slot(p, block), c_lo, c_hi);                   // (counted by ballots: wave totals already)
         if (p.final && p.list && p.list_part == 1 && block == 0)
             p.final[2] = (unsigned long long)p.list_count[0] | ((unsigned long long)p.list_count[1] << 32);
     }

@@ -28,6 +28,7 @@
 // Same fp32 operations in the same order as the reference (no FMA contraction): every output
 // bit and both counters equal the oracle's.
 #include "launch_common.hpp"
+#include "wave_lists.hpp"
 
 namespace nl {
 
@@ -44,13 +45,6 @@ __device__ __forceinline__ int wave_max_i(int v)
 {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
-__device__ __forceinline__ int wave_sum_i(int v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
 
@@ -329,12 +323,8 @@ __global__ __launch_bounds__(64) void stack_sigma_tile_kernel(StackArgs p)
         if (on) p.out[pix] = res;
     }
 
-    const int t_lo = wave_sum_i(c_lo), t_hi = wave_sum_i(c_hi);
-    if (lane == 0) {
-        unsigned long long *slot = p.partial + 2 * (size_t)(blockIdx.x % kClipSlots);
-        if (t_lo) atomicAdd(slot + 0, (unsigned long long)t_lo);
-        if (t_hi) atomicAdd(slot + 1, (unsigned long long)t_hi);
-    }
+    const int t_lo = wave_sum(c_lo), t_hi = wave_sum(c_hi);
+    if (lane == 0) add_clip_totals(partial_slot(p, blockIdx.x), t_lo, t_hi);
 }
 
 // LDS bytes of one tile, 0 if it does not fit the CU

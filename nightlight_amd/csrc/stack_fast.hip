@@ -99,14 +99,7 @@ __global__ __launch_bounds__(256) void stack_median_fast_kernel(StackArgs p, Fas
             if (on) NL_STORE_RESULT(&p.out[pix], res);
         }
         if constexpr (WINDOW) {
-            const unsigned long long gm = __ballot(hand_over);
-            if (gm) {
-                unsigned base = 0;
-                if (lane == 0) base = atomicAdd(q.gen_count, (unsigned)__popcll(gm));
-                base = __shfl(base, 0, 64);
-                const unsigned slot = base + (unsigned)__popcll(gm & ((1ull << lane) - 1ull));
-                if (hand_over && slot < q.gen_capacity) q.gen_list[slot] = (unsigned)pix;
-            }
+            wave_append(q.gen_list, q.gen_count, q.gen_capacity, hand_over, (unsigned)pix, lane);
             break;
         }
     }
@@ -228,7 +221,7 @@ void stack_mad_fast_kernel(StackArgs p, FastArgs q)
         unsigned base = 0;
         if (lane == 0) base = atomicAdd(q.fb_count, (unsigned)__popcll(em));
         base = __shfl(base, 0, 64);
-        const unsigned slot = base + (unsigned)__popcll(em & ((1ull << lane) - 1ull));
+        const unsigned slot = base + lane_rank(em, lane);
         if (to_exact && slot < q.fb_capacity) q.fb_list[slot] = (unsigned)pix;
     }
   }
@@ -242,11 +235,9 @@ void stack_mad_fast_kernel(StackArgs p, FastArgs q)
     if (lane == 0) { s_lo[threadIdx.x >> 6] = c_lo; s_hi[threadIdx.x >> 6] = c_hi; }
     __syncthreads();
     if (threadIdx.x == 0) {
-        const int t_l = s_lo[0] + s_lo[1] + s_lo[2] + s_lo[3];
+        const int t_l = s_lo[0] + s_lo[1] + s_lo[2] + s_lo[3];      // (four waves: the launcher starts 256 threads)
         const int t_h = s_hi[0] + s_hi[1] + s_hi[2] + s_hi[3];
-        unsigned long long *slot = p.partial + 2 * (size_t)(blockIdx.x % kClipSlots);
-        if (t_l) atomicAdd(slot + 0, (unsigned long long)t_l);
-        if (t_h) atomicAdd(slot + 1, (unsigned long long)t_h);
+        add_clip_totals(partial_slot(p, blockIdx.x), t_l, t_h);
     }
 }
 
@@ -337,14 +328,14 @@ void stack_mad_bitonic_kernel(StackArgs p, FastArgs q)
         unsigned base = 0;
         if (lane == 0) base = atomicAdd(q.fb_count, (unsigned)__popcll(em));
         base = __shfl(base, 0, 64);
-        const unsigned slot = base + (unsigned)__popcll(em & ((1ull << lane) - 1ull));
+        const unsigned slot = base + lane_rank(em, lane);
         if (to_exact && slot < q.fb_capacity) q.fb_list[slot] = (unsigned)pix;
     }
     if (gm) {
         unsigned base = 0;
         if (lane == 0) base = atomicAdd(q.gen_count, (unsigned)__popcll(gm));
         base = __shfl(base, 0, 64);
-        const unsigned slot = base + (unsigned)__popcll(gm & ((1ull << lane) - 1ull));
+        const unsigned slot = base + lane_rank(gm, lane);
         if (narrow && slot < q.gen_capacity) q.gen_list[slot] = (unsigned)pix;
     }
     __shared__ int s_lo[4], s_hi[4];
@@ -356,11 +347,9 @@ void stack_mad_bitonic_kernel(StackArgs p, FastArgs q)
     if (lane == 0) { s_lo[threadIdx.x >> 6] = c_lo; s_hi[threadIdx.x >> 6] = c_hi; }
     __syncthreads();
     if (threadIdx.x == 0) {
-        const int t_l = s_lo[0] + s_lo[1] + s_lo[2] + s_lo[3];
+        const int t_l = s_lo[0] + s_lo[1] + s_lo[2] + s_lo[3];      // (four waves: the launcher starts 256 threads)
         const int t_h = s_hi[0] + s_hi[1] + s_hi[2] + s_hi[3];
-        unsigned long long *slot = p.partial + 2 * (size_t)(blockIdx.x % kClipSlots);
-        if (t_l) atomicAdd(slot + 0, (unsigned long long)t_l);
-        if (t_h) atomicAdd(slot + 1, (unsigned long long)t_h);
+        add_clip_totals(partial_slot(p, blockIdx.x), t_l, t_h);
     }
 }
 

@@ -152,14 +152,7 @@ void stack_mad_ml_kernel(StackArgs p, FastArgs q)
     const bool to_exact = rep && degenerate;
     if (rep && !to_exact) NL_STORE_RESULT(&p.out[pix], res);
     if (!rep || to_exact || n == 0) { c_lo = 0; c_hi = 0; }
-    const unsigned long long em = __ballot(to_exact);
-    if (em) {
-        unsigned base = 0;
-        if (lane == 0) base = atomicAdd(q.fb_count, (unsigned)__popcll(em));
-        base = __shfl(base, 0, 64);
-        const unsigned slot = base + (unsigned)__popcll(em & ((1ull << lane) - 1ull));
-        if (to_exact && slot < q.fb_capacity) q.fb_list[slot] = (unsigned)pix;
-    }
+    wave_append(q.fb_list, q.fb_count, q.fb_capacity, to_exact, (unsigned)pix, lane);
     __shared__ int s_lo[4], s_hi[4];
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
@@ -169,11 +162,9 @@ void stack_mad_ml_kernel(StackArgs p, FastArgs q)
     if (lane == 0) { s_lo[threadIdx.x >> 6] = c_lo; s_hi[threadIdx.x >> 6] = c_hi; }
     __syncthreads();
     if (threadIdx.x == 0) {
-        const int t_l = s_lo[0] + s_lo[1] + s_lo[2] + s_lo[3];
+        const int t_l = s_lo[0] + s_lo[1] + s_lo[2] + s_lo[3];      // (four waves: the launcher starts 256 threads)
         const int t_h = s_hi[0] + s_hi[1] + s_hi[2] + s_hi[3];
-        unsigned long long *slot = p.partial + 2 * (size_t)(blockIdx.x % kClipSlots);
-        if (t_l) atomicAdd(slot + 0, (unsigned long long)t_l);
-        if (t_h) atomicAdd(slot + 1, (unsigned long long)t_h);
+        add_clip_totals(partial_slot(p, blockIdx.x), t_l, t_h);
     }
 }
 

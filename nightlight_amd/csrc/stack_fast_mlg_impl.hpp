@@ -346,26 +346,14 @@ __device__ __forceinline__ void mlg_body(const StackArgs &p, const FastArgs &q, 
             c_hi_total += c_hi;
         }
         if (rep && to_exact && p.nrounds) p.nrounds[pix] = 0;       // (no decided rounds on record for the replay)
-        const unsigned long long em = __ballot(rep && to_exact);
-        if (em) {
-            unsigned base = 0;
-            if (lane == 0) base = atomicAdd(q.fb_count, (unsigned)__popcll(em));
-            base = __shfl(base, 0, 64);
-            const unsigned slot = base + (unsigned)__popcll(em & ((1ull << lane) - 1ull));
-            if (rep && to_exact && slot < q.fb_capacity) q.fb_list[slot] = (unsigned)pix;
-        }
+        wave_append(q.fb_list, q.fb_count, q.fb_capacity, rep && to_exact, (unsigned)pix, lane);
     }
-
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         c_lo_total += __shfl_xor(c_lo_total, o, 64);
         c_hi_total += __shfl_xor(c_hi_total, o, 64);
     }
-    if (lane == 0) {
-        unsigned long long *slot = clip_slot(p, block);
-        if (c_lo_total) atomicAdd(slot + 0, (unsigned long long)c_lo_total);
-        if (c_hi_total) atomicAdd(slot + 1, (unsigned long long)c_hi_total);
-    }
+    if (lane == 0) add_clip_totals(clip_slot(p, block), c_lo_total, c_hi_total);
 }
 
 }  // namespace nl

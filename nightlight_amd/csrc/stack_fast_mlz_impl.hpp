@@ -861,7 +861,7 @@ void stack_sigma_mlz_kernel(StackArgs p, FastArgs q)
             unsigned base = 0;
             if (lane == 0) base = atomicAdd(q.gen_count, (unsigned)__popcll(gm));
             base = __shfl(base, 0, 64);
-            const unsigned slot = base + (unsigned)__popcll(gm & ((1ull << lane) - 1ull));
+            const unsigned slot = base + lane_rank(gm, lane);
             if (rep && to_generic && slot < q.gen_capacity) q.gen_list[slot] = (unsigned)pix;
         }
         const unsigned long long em = __ballot(rep && to_exact);
@@ -869,7 +869,7 @@ void stack_sigma_mlz_kernel(StackArgs p, FastArgs q)
             unsigned base = 0;
             if (lane == 0) base = atomicAdd(q.fb_count, (unsigned)__popcll(em));
             base = __shfl(base, 0, 64);
-            const unsigned slot = base + (unsigned)__popcll(em & ((1ull << lane) - 1ull));
+            const unsigned slot = base + lane_rank(em, lane);
             if (rep && to_exact && slot < q.fb_capacity) q.fb_list[slot] = (unsigned)pix;
         }
     }
@@ -883,20 +883,14 @@ void stack_sigma_mlz_kernel(StackArgs p, FastArgs q)
     if (lane == 0) { NL_STAT(6, __builtin_readcyclecounter() - exp_t0); NL_STAT(7, 1); }
 #endif
     if constexpr (L::PACK) {
-        if (lane == 0) {                                   // (the one wave of the rounds phase)
-            unsigned long long *slot = p.partial + 2 * (size_t)(blk % kClipSlots);
-            if (c_lo_total) atomicAdd(slot + 0, (unsigned long long)c_lo_total);
-            if (c_hi_total) atomicAdd(slot + 1, (unsigned long long)c_hi_total);
-        }
+        if (lane == 0) add_clip_totals(partial_slot(p, blk), c_lo_total, c_hi_total);      // (the one wave of the rounds phase)
     } else {
         if (lane == 0) { s_lo[threadIdx.x >> 6] = c_lo_total; s_hi[threadIdx.x >> 6] = c_hi_total; }
         __syncthreads();
         if (threadIdx.x == 0) {
             int t_lo = 0, t_hi = 0;
             for (int w = 0; w < L::BLOCK / 64; w++) { t_lo += s_lo[w]; t_hi += s_hi[w]; }
-            unsigned long long *slot = p.partial + 2 * (size_t)(blk % kClipSlots);
-            if (t_lo) atomicAdd(slot + 0, (unsigned long long)t_lo);
-            if (t_hi) atomicAdd(slot + 1, (unsigned long long)t_hi);
+            add_clip_totals(partial_slot(p, blk), t_lo, t_hi);
         }
     }
     };   // ---- end of the rounds phase ----

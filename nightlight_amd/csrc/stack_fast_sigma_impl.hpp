@@ -83,18 +83,6 @@ constexpr bool sigma_lds_lookup(int ns, bool zonal, bool winsor, bool tight, boo
     return sigma_wave_owned(ns, zonal, winsor, tight, record, cont) && NL_LDS_LOOKUP(ns);
 }
 
-// sum over the wave of an int every lane holds (all 64 lanes active): four DPP steps inside each row of 16 lanes, then
-// the four rows through scalar registers -- no LDS crossbar (the __shfl_xor form is 6 ds_bpermute_b32 per value)
-__device__ __forceinline__ int wave_sum_dpp(int x)
-{
-    x += __builtin_amdgcn_update_dpp(0, x, 0xb1, 0xf, 0xf, true);       // quad_perm [1, 0, 3, 2]
-    x += __builtin_amdgcn_update_dpp(0, x, 0x4e, 0xf, 0xf, true);       // quad_perm [2, 3, 0, 1]
-    x += __builtin_amdgcn_update_dpp(0, x, 0x141, 0xf, 0xf, true);      // row_half_mirror
-    x += __builtin_amdgcn_update_dpp(0, x, 0x140, 0xf, 0xf, true);      // row_mirror
-    return (__builtin_amdgcn_readlane(x, 0) + __builtin_amdgcn_readlane(x, 16)) +
-           (__builtin_amdgcn_readlane(x, 32) + __builtin_amdgcn_readlane(x, 48));
-}
-
 #ifndef NL_WINSOR_WL
 #define NL_WINSOR_WL(ns) ((ns) >= 112 ? 20 : ((ns) >= 80 ? 16 : ((ns) / 4 + 3) / 4 * 4))
 #endif
@@ -860,7 +848,7 @@ void stack_sigma_fast_kernel(StackArgs p, FastArgs q)
                 unsigned base = 0;
                 if (lane == 0) base = atomicAdd(&s_cont, (unsigned)__popcll(dm));       // LDS
                 base = __shfl(base, 0, 64);
-                const unsigned slot = base + (unsigned)__popcll(dm & ((1ull << lane) - 1ull));
+                const unsigned slot = base + lane_rank(dm, lane);
                 if (on && defer && slot < q.cont_region) {
                     const size_t at = (size_t)blockIdx.x * q.cont_region + slot;
                     q.cont_list[at] = (unsigned)pix;
@@ -880,7 +868,7 @@ void stack_sigma_fast_kernel(StackArgs p, FastArgs q)
                 unsigned base = 0;
                 if (lane == 0) base = atomicAdd(q.gen_count, (unsigned)__popcll(gm));
                 base = (unsigned)__builtin_amdgcn_readfirstlane((int)base);
-                const unsigned slot = base + (unsigned)__popcll(gm & ((1ull << lane) - 1ull));
+                const unsigned slot = base + lane_rank(gm, lane);
                 if (on && to_generic && slot < q.gen_capacity) q.gen_list[slot] = (unsigned)pix;
             }
         } else if constexpr (ZONAL && !RECORD) {
@@ -892,7 +880,7 @@ void stack_sigma_fast_kernel(StackArgs p, FastArgs q)
             __syncthreads();
             if (gm) {
                 const unsigned base = s_gen_base + (unsigned)__shfl((int)woff, 0, 64);
-                const unsigned slot = base + (unsigned)__popcll(gm & ((1ull << lane) - 1ull));
+                const unsigned slot = base + lane_rank(gm, lane);
                 if (on && to_generic && slot < q.gen_capacity) q.gen_list[slot] = (unsigned)pix;
             }
             __syncthreads();
@@ -904,7 +892,7 @@ void stack_sigma_fast_kernel(StackArgs p, FastArgs q)
             if (lane == 0) base = atomicAdd(q.fb_count, (unsigned)__popcll(em));
             if constexpr (WAVE_OWNED) base = (unsigned)__builtin_amdgcn_readfirstlane((int)base);
             else base = __shfl(base, 0, 64);
-            const unsigned slot = base + (unsigned)__popcll(em & ((1ull << lane) - 1ull));
+            const unsigned slot = base + lane_rank(em, lane);
             if (on && to_exact && slot < q.fb_capacity) q.fb_list[slot] = (unsigned)pix;
         }
             on = on && active;                         // (whoever is not active any more is done with)
@@ -949,7 +937,7 @@ void stack_sigma_fast_kernel(StackArgs p, FastArgs q)
         const int t_lo = wave_sum_dpp(c_lo_total), t_hi = wave_sum_dpp(c_hi_total);
         if (lane == 0) {
             const unsigned wave_index = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-            unsigned long long *slot = p.partial + 2 * (size_t)(wave_index % kClipSlots);
+            unsigned long long *slot = partial_slot(p, wave_index);
             if (t_lo) atomicAdd(slot + 0, (unsigned long long)t_lo);
             if (t_hi) atomicAdd(slot + 1, (unsigned long long)t_hi);
         }
@@ -967,7 +955,7 @@ void stack_sigma_fast_kernel(StackArgs p, FastArgs q)
     if (threadIdx.x == 0) {
         int t_lo = 0, t_hi = 0;
         for (unsigned w = 0; w < (blockDim.x >> 6); w++) { t_lo += s_lo[w]; t_hi += s_hi[w]; }
-        unsigned long long *slot = p.partial + 2 * (size_t)(blockIdx.x % kClipSlots);
+        unsigned long long *slot = partial_slot(p, blockIdx.x);
         if constexpr (!ZONAL) slot = clip_slot(p, blockIdx.x);
         if (t_lo) atomicAdd(slot + 0, (unsigned long long)t_lo);
         if (t_hi) atomicAdd(slot + 1, (unsigned long long)t_hi);

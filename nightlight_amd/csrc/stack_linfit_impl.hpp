@@ -381,7 +381,7 @@ void stack_linfit_fast_kernel(StackArgs p, FastArgs q, LinfitStage g)
         unsigned base = 0;
         if (lane == 0) base = atomicAdd(g.out_count, (unsigned)__popcll(mm));
         base = __shfl(base, 0, 64);
-        const unsigned slot = base + (unsigned)__popcll(mm & ((1ull << lane) - 1ull));
+        const unsigned slot = base + lane_rank(mm, lane);
         if (more && slot < g.out_capacity) {
             g.out_list[slot] = (unsigned)pix;
             unsigned w4[4] = {0u, 0u, 0u, 0u};
@@ -389,14 +389,7 @@ void stack_linfit_fast_kernel(StackArgs p, FastArgs q, LinfitStage g)
             g.out_state[slot] = make_uint4(w4[0], w4[1], w4[2], w4[3]);
         }
     }
-    const unsigned long long em = __ballot(on && to_exact);
-    if (em) {
-        unsigned base = 0;
-        if (lane == 0) base = atomicAdd(q.fb_count, (unsigned)__popcll(em));
-        base = __shfl(base, 0, 64);
-        const unsigned slot = base + (unsigned)__popcll(em & ((1ull << lane) - 1ull));
-        if (on && to_exact && slot < q.fb_capacity) q.fb_list[slot] = (unsigned)pix;
-    }
+    wave_append(q.fb_list, q.fb_count, q.fb_capacity, on && to_exact, (unsigned)pix, lane);
   }
 
     __shared__ int s_lo[4], s_hi[4];
@@ -408,11 +401,9 @@ void stack_linfit_fast_kernel(StackArgs p, FastArgs q, LinfitStage g)
     if ((threadIdx.x & 63) == 0) { s_lo[threadIdx.x >> 6] = c_lo; s_hi[threadIdx.x >> 6] = c_hi; }
     __syncthreads();
     if (threadIdx.x == 0) {
-        const int t_lo = s_lo[0] + s_lo[1] + s_lo[2] + s_lo[3];
+        const int t_lo = s_lo[0] + s_lo[1] + s_lo[2] + s_lo[3];      // (four waves: the launcher starts 256 threads)
         const int t_hi = s_hi[0] + s_hi[1] + s_hi[2] + s_hi[3];
-        unsigned long long *slot = p.partial + 2 * (size_t)(blockIdx.x % kClipSlots);
-        if (t_lo) atomicAdd(slot + 0, (unsigned long long)t_lo);
-        if (t_hi) atomicAdd(slot + 1, (unsigned long long)t_hi);
+        add_clip_totals(partial_slot(p, blockIdx.x), t_lo, t_hi);
     }
 }
 
@@ -706,21 +697,14 @@ void stack_linfit_ml_kernel(StackArgs p, FastArgs q, LinfitStage g)
         unsigned base = 0;
         if (lane == 0 && mm) base = atomicAdd(g.out_count, (unsigned)__popcll(mm));
         base = __shfl(base, 0, 64);
-        int slot = (int)(base + (unsigned)__popcll(mm & ((1ull << lane) - 1ull)));     // valid in the pixel's lane 0
+        int slot = (int)(base + lane_rank(mm, lane));     // valid in the pixel's lane 0
         slot = __float_as_int(quad_from<LPP, 0>(__int_as_float(slot)));
         if (more && (unsigned)slot < g.out_capacity) {
             if (role == 0) g.out_list[slot] = (unsigned)pix;
             g.out_state[(int64_t)slot * LPP + role] = make_uint4(live[0], live[1], live[2], live[3]);
         }
     }
-    const unsigned long long em = __ballot(rep && to_exact);
-    if (em) {
-        unsigned base = 0;
-        if (lane == 0) base = atomicAdd(q.fb_count, (unsigned)__popcll(em));
-        base = __shfl(base, 0, 64);
-        const unsigned slot = base + (unsigned)__popcll(em & ((1ull << lane) - 1ull));
-        if (rep && to_exact && slot < q.fb_capacity) q.fb_list[slot] = (unsigned)pix;
-    }
+    wave_append(q.fb_list, q.fb_count, q.fb_capacity, rep && to_exact, (unsigned)pix, lane);
   }
 
     __shared__ int s_lo[4], s_hi[4];
@@ -732,11 +716,9 @@ void stack_linfit_ml_kernel(StackArgs p, FastArgs q, LinfitStage g)
     if (lane == 0) { s_lo[threadIdx.x >> 6] = c_lo; s_hi[threadIdx.x >> 6] = c_hi; }
     __syncthreads();
     if (threadIdx.x == 0) {
-        const int t_lo = s_lo[0] + s_lo[1] + s_lo[2] + s_lo[3];
+        const int t_lo = s_lo[0] + s_lo[1] + s_lo[2] + s_lo[3];      // (four waves: the launcher starts 256 threads)
         const int t_hi = s_hi[0] + s_hi[1] + s_hi[2] + s_hi[3];
-        unsigned long long *slot = p.partial + 2 * (size_t)(blockIdx.x % kClipSlots);
-        if (t_lo) atomicAdd(slot + 0, (unsigned long long)t_lo);
-        if (t_hi) atomicAdd(slot + 1, (unsigned long long)t_hi);
+        add_clip_totals(partial_slot(p, blockIdx.x), t_lo, t_hi);
     }
 }
 

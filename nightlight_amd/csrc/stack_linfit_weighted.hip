@@ -210,14 +210,7 @@ __global__ __launch_bounds__(256) void stack_linfit_weighted_kernel(StackArgs p,
         c_lo = p_lo;
         c_hi = p_hi;
     }
-    const unsigned long long em = __ballot(on && to_exact);
-    if (em) {
-        unsigned base = 0;
-        if (lane == 0) base = atomicAdd(q.fb_count, (unsigned)__popcll(em));
-        base = __shfl(base, 0, 64);
-        const unsigned slot = base + (unsigned)__popcll(em & ((1ull << lane) - 1ull));
-        if (on && to_exact && slot < q.fb_capacity) q.fb_list[slot] = (unsigned)pix;
-    }
+    wave_append(q.fb_list, q.fb_count, q.fb_capacity, on && to_exact, (unsigned)pix, lane);
 
     __shared__ int s_lo[4], s_hi[4];
 #pragma unroll
@@ -228,11 +221,9 @@ __global__ __launch_bounds__(256) void stack_linfit_weighted_kernel(StackArgs p,
     if (lane == 0) { s_lo[threadIdx.x >> 6] = c_lo; s_hi[threadIdx.x >> 6] = c_hi; }
     __syncthreads();
     if (threadIdx.x == 0) {
-        const int t_lo = s_lo[0] + s_lo[1] + s_lo[2] + s_lo[3];
+        const int t_lo = s_lo[0] + s_lo[1] + s_lo[2] + s_lo[3];      // (four waves: the launcher starts 256 threads)
         const int t_hi = s_hi[0] + s_hi[1] + s_hi[2] + s_hi[3];
-        unsigned long long *slot = p.partial + 2 * (size_t)(blockIdx.x % kClipSlots);
-        if (t_lo) atomicAdd(slot + 0, (unsigned long long)t_lo);
-        if (t_hi) atomicAdd(slot + 1, (unsigned long long)t_hi);
+        add_clip_totals(partial_slot(p, blockIdx.x), t_lo, t_hi);
     }
 }
 
