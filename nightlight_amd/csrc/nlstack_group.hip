@@ -18,6 +18,7 @@
 #include <thread>
 #include <vector>
 
+#include "goal_seek.hpp"
 #include "nlstack_internal.hpp"
 
 struct nl_group {
@@ -110,6 +111,18 @@ static int for_each_tile(nl_group_t *g, F &&f)
     return NL_OK;
 }
 
+// Runs f(handle) tile after tile on the calling thread and stops at the first error, whose message stays the thread's: the
+// setters, the stack of stacks, the finish of a goal-seek -- calls that wait on their device or are too short for a thread.
+template <class F>
+static int each_tile_in_turn(nl_group_t *g, F &&f)
+{
+    for (nl_stack_t *h : g->tiles) {
+        const int rc = f(h);
+        if (rc != NL_OK) return rc;
+    }
+    return NL_OK;
+}
+
 // The finish of a group pass on worker threads: when the tiles sit on more than one device (the copies of the result rows then
 // run over separate links); NL_GROUP_PARALLEL_FINISH=1 / 0 forces it on / off (the tests force it on one device).
 static bool finish_in_parallel(const nl_group_t *g)
@@ -185,49 +198,34 @@ int nl_group_frame_resample_from(nl_group_t *g, int idx, nl_stack_t *src, int sr
 int nl_group_fill_synthetic(nl_group_t *g, uint64_t seed)
 {
     if (!g) return NL_ERR_INVALID_ARG;
-    for (size_t t = 0; t < g->tiles.size(); t++) {
-        int rc = nl_stack_fill_synthetic(g->tiles[t], seed);
-        if (rc != NL_OK) return rc;
-    }
-    return NL_OK;
+    return each_tile_in_turn(g, [&](nl_stack_t *h) { return nl_stack_fill_synthetic(h, seed); });
 }
 
 int nl_group_set_active_frames(nl_group_t *g, int n)
 {
     if (!g) return NL_ERR_INVALID_ARG;
-    for (size_t t = 0; t < g->tiles.size(); t++) {
-        int rc = nl_stack_set_active_frames(g->tiles[t], n);
-        if (rc != NL_OK) return rc;
-    }
-    g->n_frames = n;
-    return NL_OK;
+    const int rc = each_tile_in_turn(g, [&](nl_stack_t *h) { return nl_stack_set_active_frames(h, n); });
+    if (rc == NL_OK) g->n_frames = n;
+    return rc;
 }
 
 int nl_group_set_weights(nl_group_t *g, const float *weights)
 {
     if (!g) return NL_ERR_INVALID_ARG;
-    for (size_t t = 0; t < g->tiles.size(); t++) {
-        int rc = nl_stack_set_weights(g->tiles[t], weights);
-        if (rc != NL_OK) return rc;
-    }
-    return NL_OK;
+    return each_tile_in_turn(g, [&](nl_stack_t *h) { return nl_stack_set_weights(h, weights); });
 }
 
 int nl_group_set_exact(nl_group_t *g, int on)
 {
     if (!g) return NL_ERR_INVALID_ARG;
-    for (size_t t = 0; t < g->tiles.size(); t++) {
-        int rc = nl_stack_set_exact(g->tiles[t], on);
-        if (rc != NL_OK) return rc;
-    }
-    return NL_OK;
+    return each_tile_in_turn(g, [&](nl_stack_t *h) { return nl_stack_set_exact(h, on); });
 }
 
 }  // extern "C"
 
-// stack.go:142-210 over the devices: start(tile) enqueues every tile's pass, then nl_stack_finish collects
-template <class Start>
-static int run_tiles(nl_group_t *g, Start &&start, float *out_host, int64_t *clip_low, int64_t *clip_high)
+// One pass over the tiles, stack.go:142-210 over the devices: every tile's pass is started before any
+// is awaited, every tile writes its own rows of the caller's buffers, the two counters are summed on the host.
+static int run_tiles(nl_group_t *g, const nl::PassRequest &req, const nl::PassOutputs &to)
 {
     // A failing tile must not leave the other tiles' passes enqueued and pending: every pass that was
     // started is also finished, and the FIRST error (with its message) is what the caller gets.
@@ -236,58 +234,66 @@ static int run_tiles(nl_group_t *g, Start &&start, float *out_host, int64_t *cli
     auto note = [&](int rc) {
         if (rc != NL_OK && first_rc == NL_OK) { first_rc = rc; first_msg = nl_last_error(); }
     };
+    const size_t n = g->tiles.size();
     size_t started = 0;
-    for (; started < g->tiles.size() && first_rc == NL_OK; started++)
-        note(start(g->tiles[started]));
+    for (; started < n && first_rc == NL_OK; started++)
+        note(nl::stack_start(g->tiles[started], req));
     if (first_rc != NL_OK) started--;                     // (a failing start settles its handle: nothing of it is in flight)
-    int64_t lo = 0, hi = 0;
+    std::vector<int64_t> lo(n, 0), hi(n, 0);
+    // tile t's finish: a wait and the copy of its rows; into the caller's buffers while all is well, nowhere after a failure
+    auto finish = [&](size_t t) {
+        const bool ok = first_rc == NL_OK;
+        return nl::stack_finish(g->tiles[t], req, {ok ? to.out : nullptr, &lo[t], &hi[t], ok ? to.reject_low : nullptr,
+                                                   ok ? to.reject_high : nullptr});
+    };
     if (first_rc == NL_OK && finish_in_parallel(g)) {
-        // one host thread per tile: a tile's finish is a wait and the copy of its rows into the caller's (pageable) buffer --
-        // 8 MiB of a 4096 x 4096 result per tile of eight, each over its own device's link
-        std::vector<int64_t> l(g->tiles.size(), 0), h(g->tiles.size(), 0);
-        const int rc = for_each_tile(g, [&](size_t t) { return nl_stack_finish(g->tiles[t], out_host, &l[t], &h[t]); });
+        // one host thread per tile: the copies into the caller's (pageable) buffer -- 8 MiB of a 4096 x 4096 result per
+        // tile of eight -- each run over their own device's link
+        const int rc = for_each_tile(g, finish);
         if (rc != NL_OK) return rc;                       // (for_each_tile finished every tile and kept the first message)
-        for (size_t t = 0; t < g->tiles.size(); t++) { lo += l[t]; hi += h[t]; }
-        if (clip_low) *clip_low = lo;
-        if (clip_high) *clip_high = hi;
-        return NL_OK;
+    } else {
+        for (size_t t = 0; t < started; t++) note(finish(t));
+        if (first_rc != NL_OK) {
+            nl::set_last_error(first_msg.c_str());
+            return first_rc;
+        }
     }
-    for (size_t t = 0; t < started; t++) {
-        int64_t l = 0, h = 0;
-        note(nl_stack_finish(g->tiles[t], first_rc == NL_OK ? out_host : nullptr, &l, &h));
-        lo += l;                                          // stack.go:193-198
-        hi += h;
-    }
-    if (first_rc != NL_OK) {
-        nl::set_last_error(first_msg.c_str());
-        return first_rc;
-    }
-    if (clip_low) *clip_low = lo;
-    if (clip_high) *clip_high = hi;
+    int64_t sum_lo = 0, sum_hi = 0;                       // stack.go:193-198
+    for (size_t t = 0; t < n; t++) { sum_lo += lo[t]; sum_hi += hi[t]; }
+    if (to.clip_low) *to.clip_low = sum_lo;
+    if (to.clip_high) *to.clip_high = sum_hi;
     return NL_OK;
 }
 
+static int null_group()
+{
+    nl::set_last_error("null group");
+    return NL_ERR_INVALID_ARG;
+}
+
+using nl::MapsTier, nl::PassKind;
+
 extern "C" {
 
+// The pass entries: forwards to run_tiles.  (nl_group_run, like the setters, gives a null group its code without a message.)
 int nl_group_run(nl_group_t *g, int mode, float sigma_low, float sigma_high, float ref_loc,
                  float *out_host, int64_t *clip_low, int64_t *clip_high)
 {
     if (!g) return NL_ERR_INVALID_ARG;
-    return run_tiles(g, [&](nl_stack_t *h) { return nl_stack_run_async(h, mode, sigma_low, sigma_high, ref_loc); },
-                     out_host, clip_low, clip_high);
+    return run_tiles(g, {PassKind::Default, MapsTier::None, mode, sigma_low, sigma_high, ref_loc}, {out_host, clip_low, clip_high, nullptr, nullptr});
 }
 
-// the weighted linear-fit pass (include/nlstack_wlinfit.h) over the tiles: nl_group_run's protocol
+// the weighted linear-fit pass (include/nlstack_wlinfit.h)
 int nl_group_run_linfit_weighted(nl_group_t *g, float sigma_low, float sigma_high, float ref_loc,
                                  float *out_host, int64_t *clip_low, int64_t *clip_high)
 {
-    if (!g) { nl::set_last_error("null group"); return NL_ERR_INVALID_ARG; }
-    return run_tiles(g, [&](nl_stack_t *h) { return nl_stack_run_linfit_weighted_async(h, sigma_low, sigma_high, ref_loc); },
-                     out_host, clip_low, clip_high);
+    if (!g) return null_group();
+    return run_tiles(g, {PassKind::WeightedLinfit, MapsTier::None, NL_ST_LINEAR_FIT, sigma_low, sigma_high, ref_loc},
+                     {out_host, clip_low, clip_high, nullptr, nullptr});
 }
 
-// the weighted clip pass whose weights follow their frames (include/nlstack_wclip.h) over the tiles: nl_group_run's protocol
-// (what can be told from the mode alone is told first, as nl_stack_run_clip_weighted_async does)
+// the weighted clip pass whose weights follow their frames (include/nlstack_wclip.h); what can be told from the mode alone
+// is told first, as nl_stack_run_clip_weighted_async does -- in the group's own words, and every tile checks again
 int nl_group_run_clip_weighted(nl_group_t *g, int mode, float sigma_low, float sigma_high, float ref_loc,
                                float *out_host, int64_t *clip_low, int64_t *clip_high)
 {
@@ -296,84 +302,42 @@ int nl_group_run_clip_weighted(nl_group_t *g, int mode, float sigma_low, float s
         nl::set_last_error("run_clip_weighted: the mode is neither NL_ST_SIGMA nor NL_ST_WINSOR_SIGMA");
         return NL_ERR_INVALID_MODE;
     }
-    if (!g) { nl::set_last_error("null group"); return NL_ERR_INVALID_ARG; }
-    return run_tiles(g, [&](nl_stack_t *h) { return nl_stack_run_clip_weighted_async(h, mode, sigma_low, sigma_high, ref_loc); },
-                     out_host, clip_low, clip_high);
+    if (!g) return null_group();
+    return run_tiles(g, {PassKind::WeightedClip, MapsTier::None, mode, sigma_low, sigma_high, ref_loc},
+                     {out_host, clip_low, clip_high, nullptr, nullptr});
 }
 
-// nl_group_run with the maps, on the tier of the entry (nl::MapsTier): the same protocol -- every pass that was started is
-// finished, the first error with its message is the caller's -- and every tile writes its own rows of the three host buffers
-static int group_run_maps(nl_group_t *g, nl::MapsTier tier, int mode, float sigma_low, float sigma_high, float ref_loc,
-                          float *out_host, int64_t *clip_low, int64_t *clip_high,
-                          uint16_t *reject_low_host, uint16_t *reject_high_host)
-{
-    if (!g) { nl::set_last_error("null group"); return NL_ERR_INVALID_ARG; }
-    int first_rc = NL_OK;
-    std::string first_msg;
-    auto note = [&](int rc) {
-        if (rc != NL_OK && first_rc == NL_OK) { first_rc = rc; first_msg = nl_last_error(); }
-    };
-    size_t started = 0;
-    for (; started < g->tiles.size() && first_rc == NL_OK; started++)
-        note(nl::stack_run_maps_async(g->tiles[started], tier, mode, sigma_low, sigma_high, ref_loc));
-    if (first_rc != NL_OK) started--;                     // (a failing start settles its handle: nothing of it is in flight)
-    const bool ok = first_rc == NL_OK;
-    int64_t lo = 0, hi = 0;
-    if (ok && finish_in_parallel(g)) {
-        std::vector<int64_t> l(g->tiles.size(), 0), h(g->tiles.size(), 0);
-        const int rc = for_each_tile(g, [&](size_t t) {
-            return nl::stack_finish_maps(g->tiles[t], out_host, &l[t], &h[t], reject_low_host, reject_high_host);
-        });
-        if (rc != NL_OK) return rc;
-        for (size_t t = 0; t < g->tiles.size(); t++) { lo += l[t]; hi += h[t]; }
-    } else {
-        for (size_t t = 0; t < started; t++) {
-            int64_t l = 0, h = 0;
-            note(nl::stack_finish_maps(g->tiles[t], ok ? out_host : nullptr, &l, &h, ok ? reject_low_host : nullptr,
-                                       ok ? reject_high_host : nullptr));
-            lo += l;                                      // stack.go:193-198
-            hi += h;
-        }
-        if (first_rc != NL_OK) {
-            nl::set_last_error(first_msg.c_str());
-            return first_rc;
-        }
-    }
-    if (clip_low) *clip_low = lo;
-    if (clip_high) *clip_high = hi;
-    return NL_OK;
-}
-
+// the maps passes, one tier (nl::MapsTier) each
 int nl_group_run_maps(nl_group_t *g, int mode, float sigma_low, float sigma_high, float ref_loc,
-                      float *out_host, int64_t *clip_low, int64_t *clip_high,
-                      uint16_t *reject_low_host, uint16_t *reject_high_host)
+                      float *out_host, int64_t *clip_low, int64_t *clip_high, uint16_t *reject_low_host, uint16_t *reject_high_host)
 {
-    return group_run_maps(g, nl::MapsTier::Column, mode, sigma_low, sigma_high, ref_loc, out_host, clip_low, clip_high, reject_low_host,
-                          reject_high_host);
+    if (!g) return null_group();
+    return run_tiles(g, {PassKind::Default, MapsTier::Column, mode, sigma_low, sigma_high, ref_loc},
+                     {out_host, clip_low, clip_high, reject_low_host, reject_high_host});
 }
 
 int nl_group_run_maps_fast(nl_group_t *g, int mode, float sigma_low, float sigma_high, float ref_loc,
-                           float *out_host, int64_t *clip_low, int64_t *clip_high,
-                           uint16_t *reject_low_host, uint16_t *reject_high_host)
+                           float *out_host, int64_t *clip_low, int64_t *clip_high, uint16_t *reject_low_host, uint16_t *reject_high_host)
 {
-    return group_run_maps(g, nl::MapsTier::Fast, mode, sigma_low, sigma_high, ref_loc, out_host, clip_low, clip_high, reject_low_host,
-                          reject_high_host);
+    if (!g) return null_group();
+    return run_tiles(g, {PassKind::Default, MapsTier::Fast, mode, sigma_low, sigma_high, ref_loc},
+                     {out_host, clip_low, clip_high, reject_low_host, reject_high_host});
 }
 
 int nl_group_run_maps_resident(nl_group_t *g, int mode, float sigma_low, float sigma_high, float ref_loc,
-                               float *out_host, int64_t *clip_low, int64_t *clip_high,
-                               uint16_t *reject_low_host, uint16_t *reject_high_host)
+                               float *out_host, int64_t *clip_low, int64_t *clip_high, uint16_t *reject_low_host, uint16_t *reject_high_host)
 {
-    return group_run_maps(g, nl::MapsTier::Resident, mode, sigma_low, sigma_high, ref_loc, out_host, clip_low, clip_high,
-                          reject_low_host, reject_high_host);
+    if (!g) return null_group();
+    return run_tiles(g, {PassKind::Default, MapsTier::Resident, mode, sigma_low, sigma_high, ref_loc},
+                     {out_host, clip_low, clip_high, reject_low_host, reject_high_host});
 }
 
 int nl_group_run_maps_deep(nl_group_t *g, int mode, float sigma_low, float sigma_high, float ref_loc,
-                           float *out_host, int64_t *clip_low, int64_t *clip_high,
-                           uint16_t *reject_low_host, uint16_t *reject_high_host)
+                           float *out_host, int64_t *clip_low, int64_t *clip_high, uint16_t *reject_low_host, uint16_t *reject_high_host)
 {
-    return group_run_maps(g, nl::MapsTier::Deep, mode, sigma_low, sigma_high, ref_loc, out_host, clip_low, clip_high,
-                          reject_low_host, reject_high_host);
+    if (!g) return null_group();
+    return run_tiles(g, {PassKind::Default, MapsTier::Deep, mode, sigma_low, sigma_high, ref_loc},
+                     {out_host, clip_low, clip_high, reject_low_host, reject_high_host});
 }
 
 // every tile counts on its own device and writes its own rows
@@ -386,86 +350,37 @@ int nl_group_coverage(nl_group_t *g, uint16_t *coverage_host)
 
 int nl_group_last_mode(nl_group_t *g) { return (g && !g->tiles.empty()) ? nl_stack_last_mode(g->tiles[0]) : -1; }
 
-// stackfindsigma.go:48-98 with the counters summed over the tiles after every pass
+// the goal-seek (goal_seek.hpp) with the counters summed over the tiles after every pass.  The mode is not checked here:
+// an invalid one fails in the first pass, with the handle's code and message.
 int nl_group_find_sigmas(nl_group_t *g, int mode, float ref_loc, float clip_perc_low, float clip_perc_high,
                          float *out_host, int64_t *clip_low, int64_t *clip_high,
                          float *sigma_low, float *sigma_high, int *passes)
 {
     if (!g || g->tiles.empty()) return NL_ERR_INVALID_ARG;
     const int64_t total = (int64_t)g->width * g->height * (int64_t)g->n_frames;
-    auto finish_all = [&](float *out) -> int {
-        if (out)
-            for (size_t t = 0; t < g->tiles.size(); t++) {
-                int rc = nl_stack_finish(g->tiles[t], out, nullptr, nullptr);
-                if (rc != NL_OK) return rc;
-            }
-        return NL_OK;
-    };
-    int m = mode;
-    if (m == NL_ST_AUTO) {                                        // stack.go:45-55
-        const int l = g->n_frames;
-        m = l >= 25 ? NL_ST_LINEAR_FIT : (l >= 15 ? NL_ST_WINSOR_SIGMA : (l >= 6 ? NL_ST_SIGMA : NL_ST_MEAN));
-    }
-    int64_t lo = 0, hi = 0;
-    int rc = NL_OK, n_pass = 0;
-    if (m == NL_ST_SIGMA || m == NL_ST_WINSOR_SIGMA) {
-        nl::SigmaBisection bis(clip_perc_low, clip_perc_high, total);
-        for (;;) {                                            // stackfindsigma.go:48-98
-            rc = nl_group_run(g, m, bis.low_mid, bis.high_mid, ref_loc, nullptr, &lo, &hi);
-            if (rc != NL_OK) return rc;
-            n_pass++;
-            if (bis.step(lo, hi)) {
-                if (clip_low) *clip_low = lo;
-                if (clip_high) *clip_high = hi;
-                if (sigma_low) *sigma_low = bis.low_mid;
-                if (sigma_high) *sigma_high = bis.high_mid;
-                if (passes) *passes = n_pass;
-                return finish_all(out_host);
-            }
-        }
-    }
-    // stackfindsigma.go:40-46, 101-170: Newton's method for the linear fit; the other modes "do not
-    // support sigmas" and are stacked once with 0, 0
-    const bool newton = m == NL_ST_LINEAR_FIT;
-    nl::SigmaNewton nw(clip_perc_low, total);
-    for (;;) {
-        rc = nl_group_run(g, m, newton ? nw.next_low() : 0.0f, newton ? nw.next_high() : 0.0f, ref_loc, nullptr, &lo, &hi);
-        if (rc != NL_OK) return rc;
-        n_pass++;
-        const int st = newton ? nw.step(lo, hi) : 1;
-        if (st == 0) continue;
-        if (st == 2) {
-            rc = nl_group_run(g, m, nw.sig_low, nw.sig_high, ref_loc, nullptr, nullptr, nullptr);
-            if (rc != NL_OK) return rc;
-        }
-        if (clip_low) *clip_low = newton ? nw.base_lo : lo;
-        if (clip_high) *clip_high = newton ? nw.base_hi : hi;
-        if (sigma_low) *sigma_low = newton ? nw.sig_low : 0.0f;
-        if (sigma_high) *sigma_high = newton ? nw.sig_high : 0.0f;
-        if (passes) *passes = n_pass;
-        return finish_all(out_host);
-    }
+    const int m = mode == NL_ST_AUTO ? nl::auto_select_mode(g->n_frames) : mode;
+    return nl::goal_seek(
+        m, clip_perc_low, clip_perc_high, total,
+        [&](float lo, float hi, int64_t c[2]) { return nl_group_run(g, m, lo, hi, ref_loc, nullptr, &c[0], &c[1]); },
+        [&](float lo, float hi) { return nl_group_run(g, m, lo, hi, ref_loc, nullptr, nullptr, nullptr); },
+        [&] {
+            if (!out_host) return NL_OK;
+            return each_tile_in_turn(g, [&](nl_stack_t *h) { return nl_stack_finish(h, out_host, nullptr, nullptr); });
+        },
+        {clip_low, clip_high, sigma_low, sigma_high, passes});
 }
 
 // StackIncremental / StackIncrementalFinalize (stack.go:924-944) on every tile's device
 int nl_group_accumulate(nl_group_t *g, float weight, int first)
 {
     if (!g) return NL_ERR_INVALID_ARG;
-    for (size_t t = 0; t < g->tiles.size(); t++) {
-        int rc = nl_stack_accumulate(g->tiles[t], weight, first);
-        if (rc != NL_OK) return rc;
-    }
-    return NL_OK;
+    return each_tile_in_turn(g, [&](nl_stack_t *h) { return nl_stack_accumulate(h, weight, first); });
 }
 
 int nl_group_accumulate_finalize(nl_group_t *g, float weight_sum, float *out_host)
 {
     if (!g) return NL_ERR_INVALID_ARG;
-    for (size_t t = 0; t < g->tiles.size(); t++) {
-        int rc = nl_stack_accumulate_finalize(g->tiles[t], weight_sum, out_host);
-        if (rc != NL_OK) return rc;
-    }
-    return NL_OK;
+    return each_tile_in_turn(g, [&](nl_stack_t *h) { return nl_stack_accumulate_finalize(h, weight_sum, out_host); });
 }
 
 }  // extern "C"

@@ -61,11 +61,31 @@ enum class MapsTier {
     Resident,             // nl_stack_run_maps_resident (include/nlstack_residentmaps.h): and the linear fit's kernels and cascade
     Deep,                 // nl_stack_run_maps_deep (include/nlstack_deepmaps.h): and the LDS-column sigma / winsorized kernels, 129 ... 512 frames
 };
-// the two halves of the four nl_stack_run_maps* entries (nlstack_pass.hip), so that the nl_group_run_maps* (nlstack_group.hip)
-// start every tile before they await any; a failing first half settles the handle as nl_stack_run_async does
-int stack_run_maps_async(nl_stack_t *h, MapsTier tier, int mode, float sigma_low, float sigma_high, float ref_loc);
-int stack_finish_maps(nl_stack_t *h, float *out_host, int64_t *clip_low, int64_t *clip_high, uint16_t *reject_low_host,
-                      uint16_t *reject_high_host);
+// the passes that run on an engine of their own instead of select_engine's (nlstack_pass.hip)
+enum class PassKind {
+    Default,              // nl_stack_run_async and, with a tier, the nl_stack_run_maps* entries
+    WeightedLinfit,       // nl_stack_run_linfit_weighted (include/nlstack_wlinfit.h): run_linfit_weighted; mode is NL_ST_LINEAR_FIT
+    WeightedClip,         // nl_stack_run_clip_weighted (include/nlstack_wclip.h): run_clip_weighted
+};
+// One stack pass as every pass entry of the handle and of the group asks for it, and where its results go; any output
+// may be null, the two maps are read by a maps pass only.
+struct PassRequest {
+    PassKind kind;
+    MapsTier tier;
+    int mode;
+    float sigma_low, sigma_high, ref_loc;
+};
+struct PassOutputs {
+    float *out;
+    int64_t *clip_low, *clip_high;
+    uint16_t *reject_low, *reject_high;
+};
+// The two halves of a pass (nlstack_pass.hip), so that the group (nlstack_group.hip) starts every tile before it awaits
+// any.  stack_start enqueues; a failing one leaves nothing in flight on the handle.  stack_finish waits and copies out:
+// nl_stack_finish, with the two planes of the map behind a maps request.
+int stack_start(nl_stack_t *h, const PassRequest &req);
+int stack_finish(nl_stack_t *h, const PassRequest &req, const PassOutputs &to);
+int auto_select_mode(int n_frames);         // stack.go:45-55: what NL_ST_AUTO stands for
 
 }  // namespace nl
 

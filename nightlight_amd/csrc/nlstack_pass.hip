@@ -2,8 +2,11 @@
 // run_async_impl sets a pass up, select_engine picks the engine that runs it; all pixel arithmetic runs in the kernels.
 #include <mutex>
 
+#include "goal_seek.hpp"
 #include "launch_common.hpp"
 #include "nlstack_internal.hpp"
+
+using nl::MapsTier, nl::PassKind;
 
 namespace {
 
@@ -94,6 +97,14 @@ static int dense_grid(int64_t items, int64_t max_grid, int width, int pixels_per
     return (int)g;
 }
 
+int nl::auto_select_mode(int l)   // stack.go:45-55
+{
+    if (l >= 25) return NL_ST_LINEAR_FIT;
+    if (l >= 15) return NL_ST_WINSOR_SIGMA;
+    if (l >= 6) return NL_ST_SIGMA;
+    return NL_ST_MEAN;
+}
+
 extern "C" {
 
 // Linear-fit cascade buffers (stack_linfit.hip): two pixel lists and state arrays with lanes_per_pixel liveness masks
@@ -161,14 +172,6 @@ static bool fused_protocol_on()
     return on;
 }
 
-static int auto_select_mode(int l)   // stack.go:45-55
-{
-    if (l >= 25) return NL_ST_LINEAR_FIT;
-    if (l >= 15) return NL_ST_WINSOR_SIGMA;
-    if (l >= 6) return NL_ST_SIGMA;
-    return NL_ST_MEAN;
-}
-
 // ---- one stack pass: run_async_impl sets it up, select_engine picks the engine that runs it ----------------------------
 //
 // The ladder of the maps passes (nl::MapsTier).  A maps pass is a plain-protocol pass whose kernels
@@ -206,13 +209,6 @@ struct PassSetup {
     nl::StackArgs a;
     nl::MapsTier tier = nl::MapsTier::None;
     bool maps() const { return tier != nl::MapsTier::None; }      // a maps pass: a.reject_map is set
-};
-
-// the passes that run on an engine of their own instead of select_engine's
-enum class PassKind {
-    Default,              // nl_stack_run_async and, with a tier, the nl_stack_run_maps* entries
-    WeightedLinfit,       // nl_stack_run_linfit_weighted (include/nlstack_wlinfit.h): run_linfit_weighted
-    WeightedClip,         // nl_stack_run_clip_weighted (include/nlstack_wclip.h): run_clip_weighted
 };
 
 // Pure: allocates nothing, enqueues nothing.  The first engine whose condition holds runs the pass.  tier: the ladder above.
@@ -734,11 +730,9 @@ static int run_clip_weighted(nl_stack *h, const PassSetup &p, PassFacts *facts)
     return NL_OK;
 }
 
-static int run_async_impl(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc, PassKind kind,
-                          nl::MapsTier tier = nl::MapsTier::None);
-
-// what a pass that failed half-way leaves behind (nl_stack_run_async, nl::stack_run_maps_async,
-// nl_stack_run_linfit_weighted_async, nl_stack_run_clip_weighted_async)
+// A pass that fails half-way (a launch or an event call after the first kernel) must not hand control back with work in
+// flight on the handle's streams and its bookkeeping half-updated: whatever was enqueued is waited for, the scratch
+// sets count as dirty, no list lengths or hints are taken from the broken pass.  The error of the failing call is kept.
 static int settle_failed_pass(nl_stack_t *h, int rc)
 {
     if (rc != NL_OK && h && h->stream) {
@@ -756,23 +750,18 @@ static int settle_failed_pass(nl_stack_t *h, int rc)
     return rc;
 }
 
-// A pass that fails half-way (a launch or an event call after the first kernel) must not hand control back with work in
-// flight on the handle's streams and its bookkeeping half-updated: whatever was enqueued is waited for, the scratch
-// sets count as dirty, no list lengths or hints are taken from the broken pass.  The error of the failing call is kept.
-int nl_stack_run_async(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc)
-{
-    return settle_failed_pass(h, run_async_impl(h, mode, sigma_low, sigma_high, ref_loc, PassKind::Default));
-}
-
-// tier: a maps pass, on the ladder described above the engines.  Like a maps pass, two more passes take part in nothing
+// req.tier: a maps pass, on the ladder described above the engines.  Like a maps pass, two more passes take part in nothing
 // default passes remember from one another: the weighted linear-fit pass (PassKind::WeightedLinfit; `mode` is
 // NL_ST_LINEAR_FIT), which keeps the weights the default linear fit drops and runs on run_linfit_weighted, and the weighted
 // clip pass whose weights follow their frames (PassKind::WeightedClip; `mode` resolves to sigma or winsorized sigma), which
 // runs on run_clip_weighted.
-static int run_async_impl(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc, PassKind kind, nl::MapsTier tier)
+static int run_async_impl(nl_stack_t *h, const nl::PassRequest &req)
 {
     NL_CHECK_HANDLE(h);
-    const bool maps = tier != nl::MapsTier::None, wlinfit = kind == PassKind::WeightedLinfit, wclip = kind == PassKind::WeightedClip;
+    const nl::MapsTier tier = req.tier;
+    const float sigma_low = req.sigma_low, sigma_high = req.sigma_high, ref_loc = req.ref_loc;
+    int mode = req.mode;
+    const bool maps = tier != nl::MapsTier::None, wlinfit = req.kind == PassKind::WeightedLinfit, wclip = req.kind == PassKind::WeightedClip;
     if (wclip && !h->has_weights)
         return fail(NL_ERR_INVALID_ARG, "run_clip_weighted: the handle has no weights (nl_stack_set_weights); "
                                         "the unweighted pass is nl_stack_run");
@@ -780,7 +769,7 @@ static int run_async_impl(nl_stack_t *h, int mode, float sigma_low, float sigma_
         return fail(NL_ERR_INVALID_ARG, "run_linfit_weighted: the handle has no weights (nl_stack_set_weights); "
                                         "the unweighted fit is nl_stack_run with NL_ST_LINEAR_FIT");
     if (mode < NL_ST_MEDIAN || mode > NL_ST_AUTO) return fail(NL_ERR_INVALID_MODE, "invalid stacking mode");
-    if (mode == NL_ST_AUTO) mode = auto_select_mode(h->n_frames);
+    if (mode == NL_ST_AUTO) mode = nl::auto_select_mode(h->n_frames);
     if (wclip && mode != NL_ST_SIGMA && mode != NL_ST_WINSOR_SIGMA)
         return fail(NL_ERR_INVALID_MODE, "run_clip_weighted: mode %d is neither NL_ST_SIGMA nor NL_ST_WINSOR_SIGMA", mode);
     bool weighted = h->has_weights;
@@ -912,27 +901,13 @@ int nl_stack_finish(nl_stack_t *h, float *out_host, int64_t *clip_low, int64_t *
     return NL_OK;
 }
 
-int nl_stack_run(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc,
-                 float *out_host, int64_t *clip_low, int64_t *clip_high)
-{
-    int rc = nl_stack_run_async(h, mode, sigma_low, sigma_high, ref_loc);
-    if (rc != NL_OK) return rc;
-    return nl_stack_finish(h, out_host, clip_low, clip_high);
-}
-
 }  // extern "C"
-
-// ---- the maps passes (include/nlstack_maps.h, nlstack_fastmaps.h, nlstack_residentmaps.h, nlstack_deepmaps.h) ----------
-int nl::stack_run_maps_async(nl_stack_t *h, nl::MapsTier tier, int mode, float sigma_low, float sigma_high, float ref_loc)
-{
-    return settle_failed_pass(h, run_async_impl(h, mode, sigma_low, sigma_high, ref_loc, PassKind::Default, tier));
-}
 
 // nl_stack_finish, and the two planes of the map (of either kind of maps pass).  The packed words come down in ONE copy and are split here: the same
 // bytes cross the link as two uint16 planes would, and no second device buffer or kernel exists for what is a 16-bit
 // shuffle beside a PCIe transfer.
-int nl::stack_finish_maps(nl_stack_t *h, float *out_host, int64_t *clip_low, int64_t *clip_high, uint16_t *reject_low_host,
-                          uint16_t *reject_high_host)
+static int stack_finish_maps(nl_stack_t *h, float *out_host, int64_t *clip_low, int64_t *clip_high, uint16_t *reject_low_host,
+                             uint16_t *reject_high_host)
 {
     NL_CHECK_HANDLE(h);
     if (!h->last_maps || !h->d_reject_map) return fail(NL_ERR_INVALID_ARG, "finish_maps: the last pass was no maps pass");
@@ -955,74 +930,99 @@ int nl::stack_finish_maps(nl_stack_t *h, float *out_host, int64_t *clip_low, int
     return NL_OK;
 }
 
+// ---- the two halves of a pass, and the pass entries of the handle as forwards to them ----------
+int nl::stack_start(nl_stack_t *h, const nl::PassRequest &req) { return settle_failed_pass(h, run_async_impl(h, req)); }
+
+int nl::stack_finish(nl_stack_t *h, const nl::PassRequest &req, const nl::PassOutputs &to)
+{
+    if (req.tier == nl::MapsTier::None) return nl_stack_finish(h, to.out, to.clip_low, to.clip_high);
+    return stack_finish_maps(h, to.out, to.clip_low, to.clip_high, to.reject_low, to.reject_high);
+}
+
+static int run_pass(nl_stack_t *h, const nl::PassRequest &req, const nl::PassOutputs &to)
+{
+    const int rc = nl::stack_start(h, req);
+    return rc != NL_OK ? rc : nl::stack_finish(h, req, to);
+}
+
+// what nl_stack_run_clip_weighted* can tell from the mode alone, in front of the handle (NL_ST_AUTO is resolved behind it)
+static int clip_weighted_mode_check(int mode)
+{
+    if (mode < NL_ST_MEDIAN || mode > NL_ST_AUTO) return fail(NL_ERR_INVALID_MODE, "invalid stacking mode");
+    if (mode != NL_ST_AUTO && mode != NL_ST_SIGMA && mode != NL_ST_WINSOR_SIGMA)
+        return fail(NL_ERR_INVALID_MODE, "run_clip_weighted: mode %d is neither NL_ST_SIGMA nor NL_ST_WINSOR_SIGMA", mode);
+    return NL_OK;
+}
+
 extern "C" {
 
-// ---- the weighted linear-fit pass (include/nlstack_wlinfit.h) ------------------------------------------------------------
+int nl_stack_run_async(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc)
+{
+    return nl::stack_start(h, {PassKind::Default, MapsTier::None, mode, sigma_low, sigma_high, ref_loc});
+}
+
+int nl_stack_run(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc,
+                 float *out_host, int64_t *clip_low, int64_t *clip_high)
+{
+    return run_pass(h, {PassKind::Default, MapsTier::None, mode, sigma_low, sigma_high, ref_loc}, {out_host, clip_low, clip_high, nullptr, nullptr});
+}
+
+// the weighted linear-fit pass (include/nlstack_wlinfit.h)
 int nl_stack_run_linfit_weighted_async(nl_stack_t *h, float sigma_low, float sigma_high, float ref_loc)
 {
-    return settle_failed_pass(h, run_async_impl(h, NL_ST_LINEAR_FIT, sigma_low, sigma_high, ref_loc, PassKind::WeightedLinfit));
+    return nl::stack_start(h, {PassKind::WeightedLinfit, MapsTier::None, NL_ST_LINEAR_FIT, sigma_low, sigma_high, ref_loc});
 }
 
 int nl_stack_run_linfit_weighted(nl_stack_t *h, float sigma_low, float sigma_high, float ref_loc,
                                  float *out_host, int64_t *clip_low, int64_t *clip_high)
 {
-    const int rc = nl_stack_run_linfit_weighted_async(h, sigma_low, sigma_high, ref_loc);
-    if (rc != NL_OK) return rc;
-    return nl_stack_finish(h, out_host, clip_low, clip_high);
+    return run_pass(h, {PassKind::WeightedLinfit, MapsTier::None, NL_ST_LINEAR_FIT, sigma_low, sigma_high, ref_loc},
+                    {out_host, clip_low, clip_high, nullptr, nullptr});
 }
 
-// ---- the weighted clip pass whose weights follow their frames (include/nlstack_wclip.h) -------------------------------------
-// (what can be told from the mode alone is told in front of the handle; NL_ST_AUTO is resolved behind it)
+// the weighted clip pass whose weights follow their frames (include/nlstack_wclip.h)
 int nl_stack_run_clip_weighted_async(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc)
 {
-    if (mode < NL_ST_MEDIAN || mode > NL_ST_AUTO) return fail(NL_ERR_INVALID_MODE, "invalid stacking mode");
-    if (mode != NL_ST_AUTO && mode != NL_ST_SIGMA && mode != NL_ST_WINSOR_SIGMA)
-        return fail(NL_ERR_INVALID_MODE, "run_clip_weighted: mode %d is neither NL_ST_SIGMA nor NL_ST_WINSOR_SIGMA", mode);
-    return settle_failed_pass(h, run_async_impl(h, mode, sigma_low, sigma_high, ref_loc, PassKind::WeightedClip));
+    const int rc = clip_weighted_mode_check(mode);
+    return rc != NL_OK ? rc : nl::stack_start(h, {PassKind::WeightedClip, MapsTier::None, mode, sigma_low, sigma_high, ref_loc});
 }
 
 int nl_stack_run_clip_weighted(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc,
                                float *out_host, int64_t *clip_low, int64_t *clip_high)
 {
-    const int rc = nl_stack_run_clip_weighted_async(h, mode, sigma_low, sigma_high, ref_loc);
-    if (rc != NL_OK) return rc;
-    return nl_stack_finish(h, out_host, clip_low, clip_high);
+    const int rc = clip_weighted_mode_check(mode);
+    return rc != NL_OK ? rc
+                       : run_pass(h, {PassKind::WeightedClip, MapsTier::None, mode, sigma_low, sigma_high, ref_loc},
+                                  {out_host, clip_low, clip_high, nullptr, nullptr});
 }
 
-static int run_maps(nl_stack_t *h, nl::MapsTier tier, int mode, float sigma_low, float sigma_high, float ref_loc,
-                    float *out_host, int64_t *clip_low, int64_t *clip_high, uint16_t *reject_low_host, uint16_t *reject_high_host)
-{
-    const int rc = nl::stack_run_maps_async(h, tier, mode, sigma_low, sigma_high, ref_loc);
-    if (rc != NL_OK) return rc;
-    return nl::stack_finish_maps(h, out_host, clip_low, clip_high, reject_low_host, reject_high_host);
-}
-
+// the maps passes (include/nlstack_maps.h, nlstack_fastmaps.h, nlstack_residentmaps.h, nlstack_deepmaps.h): one tier each
 int nl_stack_run_maps(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc,
-                      float *out_host, int64_t *clip_low, int64_t *clip_high,
-                      uint16_t *reject_low_host, uint16_t *reject_high_host)
+                      float *out_host, int64_t *clip_low, int64_t *clip_high, uint16_t *reject_low_host, uint16_t *reject_high_host)
 {
-    return run_maps(h, nl::MapsTier::Column, mode, sigma_low, sigma_high, ref_loc, out_host, clip_low, clip_high, reject_low_host, reject_high_host);
+    return run_pass(h, {PassKind::Default, MapsTier::Column, mode, sigma_low, sigma_high, ref_loc},
+                    {out_host, clip_low, clip_high, reject_low_host, reject_high_host});
 }
 
 int nl_stack_run_maps_fast(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc,
-                           float *out_host, int64_t *clip_low, int64_t *clip_high,
-                           uint16_t *reject_low_host, uint16_t *reject_high_host)
+                           float *out_host, int64_t *clip_low, int64_t *clip_high, uint16_t *reject_low_host, uint16_t *reject_high_host)
 {
-    return run_maps(h, nl::MapsTier::Fast, mode, sigma_low, sigma_high, ref_loc, out_host, clip_low, clip_high, reject_low_host, reject_high_host);
+    return run_pass(h, {PassKind::Default, MapsTier::Fast, mode, sigma_low, sigma_high, ref_loc},
+                    {out_host, clip_low, clip_high, reject_low_host, reject_high_host});
 }
 
 int nl_stack_run_maps_resident(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc,
-                               float *out_host, int64_t *clip_low, int64_t *clip_high,
-                               uint16_t *reject_low_host, uint16_t *reject_high_host)
+                               float *out_host, int64_t *clip_low, int64_t *clip_high, uint16_t *reject_low_host, uint16_t *reject_high_host)
 {
-    return run_maps(h, nl::MapsTier::Resident, mode, sigma_low, sigma_high, ref_loc, out_host, clip_low, clip_high, reject_low_host, reject_high_host);
+    return run_pass(h, {PassKind::Default, MapsTier::Resident, mode, sigma_low, sigma_high, ref_loc},
+                    {out_host, clip_low, clip_high, reject_low_host, reject_high_host});
 }
 
 int nl_stack_run_maps_deep(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc,
-                           float *out_host, int64_t *clip_low, int64_t *clip_high,
-                           uint16_t *reject_low_host, uint16_t *reject_high_host)
+                           float *out_host, int64_t *clip_low, int64_t *clip_high, uint16_t *reject_low_host, uint16_t *reject_high_host)
 {
-    return run_maps(h, nl::MapsTier::Deep, mode, sigma_low, sigma_high, ref_loc, out_host, clip_low, clip_high, reject_low_host, reject_high_host);
+    return run_pass(h, {PassKind::Default, MapsTier::Deep, mode, sigma_low, sigma_high, ref_loc},
+                    {out_host, clip_low, clip_high, reject_low_host, reject_high_host});
 }
 
 // no pass: it reads the active frames behind whatever is enqueued on the handle's stream and leaves the last pass's
@@ -1204,57 +1204,24 @@ int nl_stack_find_sigmas(nl_stack_t *h, int mode, float ref_loc,
                          float *sigma_low, float *sigma_high, int *passes)
 {
     NL_CHECK_HANDLE(h);
-    if (mode == NL_ST_AUTO) mode = auto_select_mode(h->n_frames);
+    if (mode == NL_ST_AUTO) mode = nl::auto_select_mode(h->n_frames);
     if (mode < NL_ST_MEDIAN || mode > NL_ST_LINEAR_FIT) return fail(NL_ERR_INVALID_MODE, "invalid stacking mode");
     // the counters cover the samples the percentages are taken of: with a reducer the whole
     // image (every tile contributes), without one only this handle's tile
     const int64_t total = reduce ? (int64_t)h->width * h->height * (int64_t)h->n_frames
                                  : h->npix * (int64_t)h->n_frames;
-    int n_pass = 0;
-    // one pass with the given sigmas; c = its clip counters (with a reducer: over every tile)
-    auto counted_pass = [&](float lo, float hi, int64_t c[2]) {
-        int rc = nl_stack_run(h, mode, lo, hi, ref_loc, nullptr, &c[0], &c[1]);
-        if (rc != NL_OK) return rc;
-        n_pass++;
-        if (reduce && (rc = reduce(c, user)) != 0)
-            return fail(NL_ERR_INVALID_ARG, "counter reduction callback failed (%d)", rc);
-        return NL_OK;
-    };
-    // the outcome: the counters and sigmas of the pass whose result the handle holds
-    auto report = [&](int64_t lo, int64_t hi, float sig_lo, float sig_hi) {
-        if (clip_low) *clip_low = lo;
-        if (clip_high) *clip_high = hi;
-        if (sigma_low) *sigma_low = sig_lo;
-        if (sigma_high) *sigma_high = sig_hi;
-        if (passes) *passes = n_pass;
-        return out_host ? nl_stack_finish(h, out_host, nullptr, nullptr) : NL_OK;
-    };
-    if (mode != NL_ST_SIGMA && mode != NL_ST_WINSOR_SIGMA) {
-        // stackfindsigma.go:40-46: Newton's method for the linear fit; the other modes "do not support
-        // sigmas" and are stacked once with 0, 0
-        nl::SigmaNewton nw(clip_perc_low, total);
-        const bool newton = mode == NL_ST_LINEAR_FIT;
-        for (;;) {
-            int64_t c[2] = {0, 0};
-            int rc = counted_pass(newton ? nw.next_low() : 0.0f, newton ? nw.next_high() : 0.0f, c);
+    return nl::goal_seek(
+        mode, clip_perc_low, clip_perc_high, total,
+        [&](float lo, float hi, int64_t c[2]) {          // (with a reducer: c over every tile)
+            int rc = nl_stack_run(h, mode, lo, hi, ref_loc, nullptr, &c[0], &c[1]);
             if (rc != NL_OK) return rc;
-            const int st = newton ? nw.step(c[0], c[1]) : 1;
-            if (st == 0) continue;
-            if (st == 2) {                       // a probe pass overwrote the result: re-make the base pass
-                rc = nl_stack_run(h, mode, nw.sig_low, nw.sig_high, ref_loc, nullptr, nullptr, nullptr);
-                if (rc != NL_OK) return rc;
-            }
-            if (!newton) return report(c[0], c[1], 0.0f, 0.0f);
-            return report(nw.base_lo, nw.base_hi, nw.sig_low, nw.sig_high);
-        }
-    }
-    nl::SigmaBisection bis(clip_perc_low, clip_perc_high, total);
-    for (;;) {
-        int64_t c[2] = {0, 0};
-        const int rc = counted_pass(bis.low_mid, bis.high_mid, c);
-        if (rc != NL_OK) return rc;
-        if (bis.step(c[0], c[1])) return report(c[0], c[1], bis.low_mid, bis.high_mid);
-    }
+            if (reduce && (rc = reduce(c, user)) != 0)
+                return fail(NL_ERR_INVALID_ARG, "counter reduction callback failed (%d)", rc);
+            return NL_OK;
+        },
+        [&](float lo, float hi) { return nl_stack_run(h, mode, lo, hi, ref_loc, nullptr, nullptr, nullptr); },
+        [&] { return out_host ? nl_stack_finish(h, out_host, nullptr, nullptr) : NL_OK; },
+        {clip_low, clip_high, sigma_low, sigma_high, passes});
 }
 
 // StackIncremental / StackIncrementalFinalize, stack.go:924-944

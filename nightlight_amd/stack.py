@@ -15,6 +15,33 @@ def _u16ptr(a):
     return a.ctypes.data_as(C.POINTER(C.c_uint16))
 
 
+def _sigmas(sigma_low, sigma_high, ref_loc):
+    return C.c_float(sigma_low), C.c_float(sigma_high), C.c_float(ref_loc)
+
+
+def _run_counted(entry, ptr, lead, out):
+    """One counted pass through `entry`, a pass entry of the library without maps, on the handle or group `ptr`:
+    entry(ptr, *lead, out, &clip_low, &clip_high).  `out`: the whole-image float32 array the rows are written to, or
+    None (the result stays on the device).  Returns (out, clip_low, clip_high)."""
+    cl, ch = C.c_int64(0), C.c_int64(0)
+    capi.check(entry(ptr, *lead, capi.fptr(out) if out is not None else None, C.byref(cl), C.byref(ch)))
+    return out, cl.value, ch.value
+
+
+def _run_maps(entry, ptr, n, lead, out=None, reject_low=None, reject_high=None):
+    """One maps pass through `entry`, an nl_stack_run_maps* / nl_group_run_maps* function of the library, over an image
+    of n pixels; the whole-image arrays not given are made here.  Returns (out, clip_low, clip_high, reject_low,
+    reject_high)."""
+    out = np.zeros(n, np.float32) if out is None else out
+    reject_low = np.zeros(n, np.uint16) if reject_low is None else reject_low
+    reject_high = np.zeros(n, np.uint16) if reject_high is None else reject_high
+    for a, t in ((out, np.float32), (reject_low, np.uint16), (reject_high, np.uint16)):
+        assert a.dtype == t and a.size == n and a.flags.c_contiguous
+    cl, ch = C.c_int64(0), C.c_int64(0)
+    capi.check(entry(ptr, *lead, capi.fptr(out), C.byref(cl), C.byref(ch), _u16ptr(reject_low), _u16ptr(reject_high)))
+    return out, cl.value, ch.value, reject_low, reject_high
+
+
 class StackHandle:
     """Frames of one row tile [row0, row0+rows) resident in HBM as planar
     [n_frames][rows*width] fp32, plus the result tile and clip counters."""
@@ -139,14 +166,14 @@ class StackHandle:
         """One pass. Returns (result or None, clip_low, clip_high).  `out` is a
         full-image float32 array whose tile rows get written; with fetch=False
         the result stays on the device."""
-        cl, ch = C.c_int64(0), C.c_int64(0)
-        if fetch and out is None:
-            out = np.zeros(self.width * self.height, np.float32)
-        optr = capi.fptr(out) if (fetch and out is not None) else None
-        capi.check(self._lib.nl_stack_run(self._h, int(mode), C.c_float(sigma_low),
-                                          C.c_float(sigma_high), C.c_float(ref_loc), optr,
-                                          C.byref(cl), C.byref(ch)))
-        return (out if fetch else None), cl.value, ch.value
+        return _run_counted(self._lib.nl_stack_run, self._h, (int(mode),) + _sigmas(sigma_low, sigma_high, ref_loc),
+                            self._result_array(out, fetch))
+
+    def _result_array(self, out, fetch):
+        """Where a pass's rows go: `out`, a fresh whole-image array if none is given, None with fetch=False."""
+        if not fetch:
+            return None
+        return np.zeros(self.width * self.height, np.float32) if out is None else out
 
     def run_maps(self, mode, sigma_low=2.75, sigma_high=2.75, ref_loc=0.0, out=None, reject_low=None,
                  reject_high=None, fast=False):
@@ -161,18 +188,9 @@ class StackHandle:
         entry = self._lib.nl_stack_run_maps_fast if fast else self._lib.nl_stack_run_maps
         return self._run_maps(entry, mode, sigma_low, sigma_high, ref_loc, out, reject_low, reject_high)
 
-    def _run_maps(self, entry, mode, sigma_low, sigma_high, ref_loc, out, reject_low, reject_high):
-        """What the run_maps* methods share: `entry` is the nl_stack_run_maps* function of the library."""
-        n = self.width * self.height
-        out = np.zeros(n, np.float32) if out is None else out
-        reject_low = np.zeros(n, np.uint16) if reject_low is None else reject_low
-        reject_high = np.zeros(n, np.uint16) if reject_high is None else reject_high
-        for a, t in ((out, np.float32), (reject_low, np.uint16), (reject_high, np.uint16)):
-            assert a.dtype == t and a.size == n and a.flags.c_contiguous
-        cl, ch = C.c_int64(0), C.c_int64(0)
-        capi.check(entry(self._h, int(mode), C.c_float(sigma_low), C.c_float(sigma_high), C.c_float(ref_loc),
-                         capi.fptr(out), C.byref(cl), C.byref(ch), _u16ptr(reject_low), _u16ptr(reject_high)))
-        return out, cl.value, ch.value, reject_low, reject_high
+    def _run_maps(self, entry, mode, sigma_low, sigma_high, ref_loc, out=None, reject_low=None, reject_high=None):
+        return _run_maps(entry, self._h, self.width * self.height, (int(mode),) + _sigmas(sigma_low, sigma_high, ref_loc),
+                         out, reject_low, reject_high)
 
     def run_maps_resident(self, mode, sigma_low=2.75, sigma_high=2.75, ref_loc=0.0, out=None, reject_low=None,
                           reject_high=None):
@@ -195,13 +213,8 @@ class StackHandle:
         no weights): the reference's linear-fit rejection, then the mean of the survivors with the weights of
         set_weights.  Returns (result or None, clip_low, clip_high) as run does; the counters are those of
         run(ST_LINEAR_FIT).  Without weights it raises NlError (ERR_INVALID_ARG)."""
-        cl, ch = C.c_int64(0), C.c_int64(0)
-        if fetch and out is None:
-            out = np.zeros(self.width * self.height, np.float32)
-        optr = capi.fptr(out) if (fetch and out is not None) else None
-        capi.check(self._lib.nl_stack_run_linfit_weighted(self._h, C.c_float(sigma_low), C.c_float(sigma_high),
-                                                          C.c_float(ref_loc), optr, C.byref(cl), C.byref(ch)))
-        return (out if fetch else None), cl.value, ch.value
+        return _run_counted(self._lib.nl_stack_run_linfit_weighted, self._h, _sigmas(sigma_low, sigma_high, ref_loc),
+                            self._result_array(out, fetch))
 
     def run_linfit_weighted_async(self, sigma_low=2.75, sigma_high=2.75, ref_loc=0.0):
         """run_linfit_weighted without the wait: finish() completes it."""
@@ -215,13 +228,8 @@ class StackHandle:
         with its own frame's weight of set_weights.  `mode` is ST_SIGMA, ST_WINSOR_SIGMA, or ST_AUTO where that
         resolves to one of them.  Returns (result or None, clip_low, clip_high) as run does; the counters are those of
         run(mode).  Without weights it raises NlError (ERR_INVALID_ARG)."""
-        cl, ch = C.c_int64(0), C.c_int64(0)
-        if fetch and out is None:
-            out = np.zeros(self.width * self.height, np.float32)
-        optr = capi.fptr(out) if (fetch and out is not None) else None
-        capi.check(self._lib.nl_stack_run_clip_weighted(self._h, int(mode), C.c_float(sigma_low), C.c_float(sigma_high),
-                                                        C.c_float(ref_loc), optr, C.byref(cl), C.byref(ch)))
-        return (out if fetch else None), cl.value, ch.value
+        return _run_counted(self._lib.nl_stack_run_clip_weighted, self._h,
+                            (int(mode),) + _sigmas(sigma_low, sigma_high, ref_loc), self._result_array(out, fetch))
 
     def run_clip_weighted_async(self, mode=capi.ST_AUTO, sigma_low=2.75, sigma_high=2.75, ref_loc=0.0):
         """run_clip_weighted without the wait: finish() completes it."""
@@ -708,12 +716,11 @@ class StackGroup:
 
     def run(self, mode, sigma_low=2.75, sigma_high=2.75, ref_loc=0.0, download=True):
         """download=False: the result stays on the devices (e.g. for accumulate); returns (None, low, high)."""
-        out = np.zeros(self.width * self.height, np.float32) if download else None
-        cl, ch = C.c_int64(0), C.c_int64(0)
-        capi.check(self._lib.nl_group_run(self._g, int(mode), C.c_float(sigma_low), C.c_float(sigma_high),
-                                          C.c_float(ref_loc), capi.fptr(out) if download else None,
-                                          C.byref(cl), C.byref(ch)))
-        return out, cl.value, ch.value
+        return _run_counted(self._lib.nl_group_run, self._g, (int(mode),) + _sigmas(sigma_low, sigma_high, ref_loc),
+                            self._result_array(download))
+
+    def _result_array(self, download):
+        return np.zeros(self.width * self.height, np.float32) if download else None
 
     def run_maps(self, mode, sigma_low=2.75, sigma_high=2.75, ref_loc=0.0, fast=False):
         """StackHandle.run_maps over the tiles: (result, clip_low, clip_high, reject_low, reject_high), every tile
@@ -721,13 +728,7 @@ class StackGroup:
         return self._run_maps(self._lib.nl_group_run_maps_fast if fast else self._lib.nl_group_run_maps, mode, sigma_low, sigma_high, ref_loc)
 
     def _run_maps(self, entry, mode, sigma_low, sigma_high, ref_loc):
-        """What the run_maps* methods share: `entry` is the nl_group_run_maps* function of the library."""
-        n = self.width * self.height
-        out, lo, hi = np.zeros(n, np.float32), np.zeros(n, np.uint16), np.zeros(n, np.uint16)
-        cl, ch = C.c_int64(0), C.c_int64(0)
-        capi.check(entry(self._g, int(mode), C.c_float(sigma_low), C.c_float(sigma_high), C.c_float(ref_loc),
-                         capi.fptr(out), C.byref(cl), C.byref(ch), _u16ptr(lo), _u16ptr(hi)))
-        return out, cl.value, ch.value, lo, hi
+        return _run_maps(entry, self._g, self.width * self.height, (int(mode),) + _sigmas(sigma_low, sigma_high, ref_loc))
 
     def run_maps_resident(self, mode, sigma_low=2.75, sigma_high=2.75, ref_loc=0.0):
         """StackHandle.run_maps_resident over the tiles (nl_group_run_maps_resident): the return value of run_maps."""
@@ -739,21 +740,13 @@ class StackGroup:
 
     def run_linfit_weighted(self, sigma_low=2.75, sigma_high=2.75, ref_loc=0.0, download=True):
         """StackHandle.run_linfit_weighted over the tiles: (result or None, clip_low, clip_high)."""
-        out = np.zeros(self.width * self.height, np.float32) if download else None
-        cl, ch = C.c_int64(0), C.c_int64(0)
-        capi.check(self._lib.nl_group_run_linfit_weighted(self._g, C.c_float(sigma_low), C.c_float(sigma_high),
-                                                          C.c_float(ref_loc), capi.fptr(out) if download else None,
-                                                          C.byref(cl), C.byref(ch)))
-        return out, cl.value, ch.value
+        return _run_counted(self._lib.nl_group_run_linfit_weighted, self._g, _sigmas(sigma_low, sigma_high, ref_loc),
+                            self._result_array(download))
 
     def run_clip_weighted(self, mode=capi.ST_AUTO, sigma_low=2.75, sigma_high=2.75, ref_loc=0.0, download=True):
         """StackHandle.run_clip_weighted over the tiles: (result or None, clip_low, clip_high)."""
-        out = np.zeros(self.width * self.height, np.float32) if download else None
-        cl, ch = C.c_int64(0), C.c_int64(0)
-        capi.check(self._lib.nl_group_run_clip_weighted(self._g, int(mode), C.c_float(sigma_low), C.c_float(sigma_high),
-                                                        C.c_float(ref_loc), capi.fptr(out) if download else None,
-                                                        C.byref(cl), C.byref(ch)))
-        return out, cl.value, ch.value
+        return _run_counted(self._lib.nl_group_run_clip_weighted, self._g,
+                            (int(mode),) + _sigmas(sigma_low, sigma_high, ref_loc), self._result_array(download))
 
     def coverage(self):
         """StackHandle.coverage over the tiles."""

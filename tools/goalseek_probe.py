@@ -15,7 +15,7 @@ from nightlight_amd.stack import StackHandle
 
 
 def bisection(perc_low, perc_high, total):
-    """nl::SigmaBisection (stack_kernels.h) -- a generator fed with counters."""
+    """nl::SigmaBisection (goal_seek.hpp) -- a generator fed with counters."""
     f = np.float32
     ll, lr, hl, hr = f(1.0), f(11.0), f(1.0), f(11.0)
     lm, hm = f(0.5) * (ll + lr), f(0.5) * (hl + hr)

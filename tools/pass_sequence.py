@@ -1,7 +1,8 @@
 """The kernels a stack pass enqueues, in enqueue order (run on the GPU box):
     rocprofv3 --kernel-trace --stats -d DIR -o seq --output-format csv -- python tools/pass_sequence.py run
     python tools/pass_sequence.py list DIR > profiles/<name>.txt
-`run`: two passes each, on one handle each, of sigma 128 frames, winsorized 24 and winsorized 300 on a 512-row tile.
+`run`: two passes each, on one handle each, of sigma 128 frames, winsorized 24 and winsorized 300 on a 512-row tile; then
+a group of three 256-row tiles on device 0, sigma 300 frames: one default pass and one maps pass on the deep tier.
 `list`: kernel name, grid and workgroup size and queue (numbered by first appearance) of every dispatch of the trace,
 in dispatch order -- two libraries that enqueue the same work in the same order give the same listing."""
 import csv
@@ -12,12 +13,16 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 if sys.argv[1] == "run":
-    from nightlight_amd import StackHandle
+    from nightlight_amd import StackGroup, StackHandle
     for mode, n in ((2, 128), (3, 24), (3, 300)):
         with StackHandle(n, 4096, 4096, device=0, row0=1536, rows=512) as st:
             st.fill_synthetic(seed=1)
             for _ in range(2):
                 st.run(mode, 3.0, 3.0, fetch=False)
+    with StackGroup(300, 4096, 768, devices=[0, 0, 0]) as g:
+        g.fill_synthetic(seed=1)
+        g.run(2, 3.0, 3.0, download=False)
+        g.run_maps_deep(2, 3.0, 3.0)
 else:
     path, = glob.glob(os.path.join(sys.argv[2], "**", "*kernel_trace.csv"), recursive=True)
     rows = sorted(csv.DictReader(open(path)), key=lambda r: int(r["Dispatch_Id"]))
