@@ -322,7 +322,7 @@ __device__ __forceinline__ void index_bits(int idx, bool (&bit)[M])
     });
 }
 
-// ---- per-lane lookups through LDS rows (the wave-owned sigma kernel, NL_LDS_LOOKUP) ----
+// ---- per-lane lookups through LDS rows (the wave-owned sigma kernel, sigma_lds_lookup) ----
 // Tables of floats, one row of kLutThreads floats per index: entry (row, thread) at row * kLutThreads + thread.
 // A thread only ever touches its own column, so the waves of a workgroup share nothing (no barrier), and the 32 lanes
 // of a half wave fall on 32 different banks whatever row each of them asks for (bank = thread mod 32).  Two rows at a

@@ -1,5 +1,6 @@
 // frame_common.hpp -- what the kernels of the per-frame operators (preprocess.hip, bayer.hip, stars.hip,
-// background.hip, frame_stats.hip, ingest.hip, tone.hip) share: the wave reductions, the block sum, Go's float -> int32.
+// background.hip, frame_stats.hip, ingest.hip, tone.hip) share: the wave reductions, the block sum, Go's float -> int32; and,
+// with the stack kernels (through wave_lists.hpp), Go's fp32 square root.
 // Summation order is part of the results (fp64 partials feed bit-exact fp32 statistics): the butterfly runs over the
 // xor distances 32, 16, ... 1, the wave values are added left to right.
 #pragma once
@@ -91,6 +92,14 @@ __device__ __forceinline__ void block_min_sum_max(float mn, double sum, float mx
         partial[3 * (size_t)blockIdx.x + 1] = sum;
         partial[3 * (size_t)blockIdx.x + 2] = (double)mx;
     }
+}
+
+// Go's float32(math.Sqrt(float64(x))) (stats.go:259): the square root in fp64, rounded once to fp32 = the correctly
+// rounded fp32 root.  NOT __fsqrt_rn: without OCML_BASIC_ROUNDED_OPERATIONS HIP maps that to the 1-ulp native
+// v_sqrt_f32, which flipped one clip decision in 2.1e9 samples against the oracle.
+__device__ __forceinline__ float sqrt_go(float x)
+{
+    return (float)__builtin_sqrt((double)x);
 }
 
 // Go's float -> int32 conversion is CVTTSS2SL / CVTTSD2SL on amd64: truncation, and 0x80000000 for NaN or out of range

@@ -4,11 +4,6 @@
 
 namespace nl {
 
-__device__ __forceinline__ float sqrt_go(float x)      // float32(math.Sqrt(float64(x))), stats.go:259
-{
-    return (float)__builtin_sqrt((double)x);
-}
-
 // These make the compiler forget what it knows about a value (no instruction is
 // emitted).  Used between the passes of an iteration: otherwise it keeps the
 // 128 per-sample liveness factors and the 128 differences x-ymean of one pass

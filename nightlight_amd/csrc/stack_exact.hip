@@ -84,15 +84,6 @@ __device__ float select_median(Col<S> a, int n)
     return res;
 }
 
-// float32(math.Sqrt(float64(x))) (stats.go:259): square root in fp64, rounded
-// once to fp32 = the correctly rounded fp32 root.  NOT __fsqrt_rn: without
-// OCML_BASIC_ROUNDED_OPERATIONS HIP maps that to the 1-ulp native v_sqrt_f32,
-// which flipped one clip decision in 2.1e9 samples against the oracle.
-__device__ __forceinline__ float sqrt_like_go(float x)
-{
-    return (float)__builtin_sqrt((double)x);
-}
-
 // stats.go:246-261
 template <int S>
 __device__ void mean_stddev(Col<S> a, int n, float &mean, float &sd)
@@ -108,7 +99,7 @@ __device__ void mean_stddev(Col<S> a, int n, float &mean, float &sd)
     }
     v = v / fn;
     mean = m;
-    sd = sqrt_like_go(v);
+    sd = sqrt_go(v);
 }
 
 // stack.go:411-424 (+ :494-511 with the mirrored weight column)
@@ -183,7 +174,7 @@ __device__ float winsorized_stddev(Col<S> a, int n, float median, float sd)
         }
         v = v / fn;
         const float old = sd;
-        sd = 1.134f * sqrt_like_go(v);
+        sd = 1.134f * sqrt_go(v);
         const float factor = fabsf(sd - old) / old;
         if (changed == 0 || factor <= 0.0005f) break;
     }

@@ -19,11 +19,6 @@ namespace nl {
 
 namespace {
 
-__device__ __forceinline__ float sqrt_like_go(float x)      // stats.go:259
-{
-    return (float)__builtin_sqrt((double)x);
-}
-
 __device__ __forceinline__ unsigned long long ballot64(bool p)      // the compare's own wave mask (HIP's __ballot goes
 {                                                                    // through an integer: v_cndmask + v_cmp_ne on top)
     return __builtin_amdgcn_ballot_w64(p);
@@ -492,7 +487,7 @@ __device__ __forceinline__ void coop_body(const StackArgs &p, float *a, const un
                     return i < n ? d * d : 0.0f;
                 });
                 const float var = vs / fn;
-                float sd = sqrt_like_go(var);
+                float sd = sqrt_go(var);
                 if constexpr (WINSOR) {
                     // stack.go:646-672: clamp a copy to median -/+ 1.5 sd, sd = 1.134 * stddev(copy),
                     // until no sample moved or sd changed by <= 0.05 %
@@ -519,7 +514,7 @@ __device__ __forceinline__ void coop_body(const StackArgs &p, float *a, const un
                             return i < n ? d * d : 0.0f;
                         });
                         const float old = sd;
-                        sd = 1.134f * sqrt_like_go(wvs / fn);
+                        sd = 1.134f * sqrt_go(wvs / fn);
                         const float diff = sd - old;
                         const float factor = fabsf(diff) / old;
                         if (changed == 0 || factor <= 0.0005f) break;

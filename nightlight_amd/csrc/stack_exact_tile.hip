@@ -36,11 +36,6 @@ namespace {
 
 constexpr int TS = 64;     // lanes = pixels per tile = LDS row length in floats
 
-__device__ __forceinline__ float sqrt_go32(float x)      // float32(math.Sqrt(float64(x))), stats.go:259
-{
-    return (float)__builtin_sqrt((double)x);
-}
-
 __device__ __forceinline__ int wave_max_i(int v)
 {
 #pragma unroll
@@ -197,7 +192,7 @@ __global__ __launch_bounds__(64) void stack_sigma_tile_kernel(StackArgs p)
             const float s = seq_rows(a, n, nmax, top, [](float x, int) { return x; });
             const float mean = s / fn;
             const float vs = seq_rows(a, n, nmax, top, [mean](float x, int) { const float d = x - mean; return d * d; });
-            float sd = sqrt_go32(vs / fn);
+            float sd = sqrt_go(vs / fn);
             if constexpr (WINSOR) {
                 // stack.go:646-672 with the running clamp of stack_exact.hip:winsorized_stddev
                 float Leff = -__builtin_inff(), Heff = __builtin_inff();
@@ -223,7 +218,7 @@ __global__ __launch_bounds__(64) void stack_sigma_tile_kernel(StackArgs p)
                         const float d = wz - wm;
                         return d * d;
                     });
-                    const float sdn = 1.134f * sqrt_go32(wv / fn);
+                    const float sdn = 1.134f * sqrt_go(wv / fn);
                     const float factor = fabsf(sdn - sd) / sd;
                     if (wact) {
                         Leff = Lc; Heff = Hc;

@@ -489,10 +489,8 @@ static void launch_cascade_stages(Launcher &L, const StackArgs &args, const Fast
     }
 }
 
-// threads per workgroup of the wave-owned dominant kernels (a build-time switch for A/B libraries: 64, 128, 256)
-#ifndef NL_WAVE_OWNED_BLOCK
-#define NL_WAVE_OWNED_BLOCK 256
-#endif
+// threads per workgroup of the wave-owned dominant kernels (64, 128 and 256 were measured: launch_dominant below)
+constexpr unsigned kWaveOwnedBlock = 256;
 
 template <int NS, bool WINSOR>
 static hipError_t launch_dominant(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name, hipEvent_t dominant_done)
@@ -510,7 +508,7 @@ static hipError_t launch_dominant(const StackArgs &args, const FastArgs &fargs, 
         // included, with 64 and 128 threads and measured no difference at 32 and 128 frames.
         with_bool(args.n_frames == NS, [&](auto T) {
             constexpr bool TIGHT = decltype(T)::value;
-            constexpr unsigned block = sigma_wave_owned(NS, true, WINSOR, TIGHT, false, false) ? NL_WAVE_OWNED_BLOCK : 256;
+            constexpr unsigned block = sigma_wave_owned(NS, true, WINSOR, TIGHT, false, false) ? kWaveOwnedBlock : 256;
             static_assert(block % 64 == 0 && block <= 256, "whole waves, within the kernel's launch bounds");
             *name = kernel_name<kSigmaFastName, NS, true, WINSOR, TIGHT, false, false>();
             L(stack_sigma_fast_kernel<NS, true, WINSOR, TIGHT>, pixel_grid(args.npix, 1, block), block, 0, args, f);

@@ -69,11 +69,7 @@ struct MlzLayout {
     // some of its workgroups are down to their rounds wave.  (With 64 pixels per workgroup -- 60 KiB, two workgroups per
     // CU -- the packed rounds measured 1 - 4 % SLOWER than unpacked ones; with 32: C3 tile kernel 3.98 -> 3.15 ms,
     // winsorized 300 / 400 frames 6.62 / 6.96 -> 5.12 / 5.50 ms.)
-#ifdef NL_MLZ_SPACK
-    static constexpr int BLOCK = (LPP == 4) ? 128 : mlz_block<LPP>;      // (A/B builds: the sigma kernels, too)
-#else
     static constexpr int BLOCK = (WINSOR && LPP == 4) ? 128 : mlz_block<LPP>;
-#endif
     static constexpr int PW = BLOCK / LPP;                      // pixels per workgroup = LDS row length (64 or 32)
     // alive window: a < ZLC, b > NTOP - ZHC; up to PADS missing samples (frames short of NTOP + NaNs)
     static constexpr int ZLC = 16, ZHC = FULL ? 24 : 32, PADS = FULL ? 15 : 23;
@@ -86,21 +82,13 @@ struct MlzLayout {
     static constexpr int KH = (WINSOR ? (LPP == 4 ? 72 : 40) : 32) + (FULL ? 0 : 8);   // high column: ranks [NTOP-KH, NTOP)
     // SELECT: the columns and the median window are SELECTED from the lanes' sorted runs (select_ends / select_window below)
     // instead of read off a full cross-lane merge -- stacks that fill their lanes, plain sigma clipping
-#ifdef NL_NO_SELECT
-    static constexpr bool SELECT = false;                       // (A/B builds: tools/ab_lib.sh)
-#else
     // (four lanes per pixel only: with two the full merge is one cross-lane stage and measures 4 % faster)
     static constexpr bool SELECT = FULL && !WINSOR && LPP == 4;
-#endif
     // PACK: the clipping rounds run in ONE lane per pixel -- one wave for the workgroup's pixels, the others retire
     // (see the kernel).  A workgroup in its rounds still holds its LDS: the freed wave slots only fill if the CU has LDS
     // for more workgroups -- hence the smaller workgroups of the winsorized kernels (BLOCK above); the winsorized kernels
     // with two lanes per pixel (35 - 39 KiB for 64 pixels in two waves) stay unpacked.
-#ifdef NL_MLZ_W2PACK
-    static constexpr bool PACK = true;                           // (A/B builds: winsorized kernels with two lanes per pixel, too)
-#else
     static constexpr bool PACK = !WINSOR || LPP == 4;
-#endif
     static constexpr int KE = 32;                               // SELECT: ranks selected per end (>= KL, KH)
     static constexpr int KLS = SELECT ? KE : KL;                // LDS rows of the low column
     static constexpr int GL = KL / 4 + 1, GH = KH / 4 + 1;      // table entries
@@ -115,14 +103,9 @@ struct MlzLayout {
     // the squares taken off again, window flag, innermost ranks outside the columns; they share the rows of the tables,
     // which the rounds phase builds after it has read them.  32 KiB or less for the sigma kernels: five workgroups
     // per CU -- a workgroup in its rounds phase is one wave, but holds its LDS.)
-#ifdef NL_MLZ_BIGLDS            // (A/B builds: tables and scalars in rows of their own, 35 KiB)
-    static constexpr int XL = 0, XH = XL + KLS, SL1 = XH + KH, SL2 = SL1 + GL, SH1 = SL2 + GL, SH2 = SH1 + GH,
-                         XW = SH2 + GH + (SELECT ? 2 : 0), PS = XW + MW + (SELECT ? 8 : 0), ROWS = PS + 8;
-#else
     static constexpr int XL = 0, XH = XL + KLS, SL1 = SELECT ? XL + KL : XH + KH, SL2 = SELECT ? XH + KH : SL1 + GL,
                          SH1 = SL2 + GL, SH2 = SH1 + GH, XW = SH2 + GH + (SELECT ? 2 : 0), ROWS = XW + MW + (SELECT ? 8 : 0),
                          PS = SL2;
-#endif
     static_assert(!SELECT || GL <= KLS - KL, "the low table fits behind the low column");
     static_assert(GL + GH >= 8, "rows for the per-pixel scalars");
     // roundings a term of the moment sums can see: fixed part (4 accumulators + quad adds), tables, assembly
@@ -349,12 +332,7 @@ __device__ __forceinline__ void lds_settle() { asm volatile("s_waitcnt lgkmcnt(0
 
 }  // namespace
 
-#ifndef NL_MLZ_STAGGER
-#define NL_MLZ_STAGGER 3        // x 8 128 cycles per third of the grid
-#endif
-#ifndef NL_MLZ_WINSOR_WAVES
-#define NL_MLZ_WINSOR_WAVES 2
-#endif
+constexpr int kMlzWinsorWaves = 2;       // waves per SIMD the winsorized kernels are compiled for (the sigma kernels: 3)
 // (PHASE is always 0: the rocprofv3 name stack_sigma_mlz_kernel<L, W, N, 0> keys the measured traffic of profiles/r0*_traffic.json in bench.py)
 // MAPS: the deep maps pass (include/nlstack_deepmaps.h, stack_fast_mlz_maps_*.hip) -- the lane that stores a pixel's result
 // also stores its two clip counts, low | high << 16, in p.reject_map[pix]; a pixel handed to the generic or the exact list
@@ -362,7 +340,7 @@ __device__ __forceinline__ void lds_settle() { asm volatile("s_waitcnt lgkmcnt(0
 // ROOMY (MAPS only): MlzLayout's second layout of the class that fills its lanes; the kernel itself is the same.
 template <int LPP, bool WINSOR, int NTOP, int PHASE = 0, bool MAPS = false, bool ROOMY = false>
 __global__ __launch_bounds__(mlz_block<LPP>)
-__attribute__((amdgpu_waves_per_eu(WINSOR ? NL_MLZ_WINSOR_WAVES : 3, 8)))
+__attribute__((amdgpu_waves_per_eu(WINSOR ? kMlzWinsorWaves : 3, 8)))
 void stack_sigma_mlz_kernel(StackArgs p, FastArgs q)
 {
     static_assert(PHASE == 0, "one kernel per pass");
@@ -394,24 +372,11 @@ void stack_sigma_mlz_kernel(StackArgs p, FastArgs q)
     // (columns of the plain sigma kernel, median window); the winsorized columns are longer, and the
     // columns of a shorter stack sit inside the lanes: full merge
     int n;
-#if defined(NL_ROUND_STATS) && defined(NL_MLZ_EXP_TIMING)
-    const unsigned long long sp0 = __builtin_readcyclecounter();
-    unsigned long long sp1 = sp0, sp2 = sp0, sp3 = sp0;
-#endif
     if constexpr (L::SELECT) {
-        // (the lanes' runs are not merged: select_ends / select_window)
-#ifdef NL_MLZ_HALVES             // (A/B builds: sort the first 64 positions while the other 64 loads are in flight -- 8 % slower)
-        n = ml_gather_sort_halves<LPP, NS, (NTOP - 16) / LPP, NTOP / LPP>(p.frames, p.stride, N, on, pix, role, v);
-#else
+        // (the lanes' runs are not merged: select_ends / select_window.  The first 64 positions sorted while the other
+        // 64 loads are in flight measured 8 % slower)
         n = ml_gather_raw<LPP, NS, (NTOP - 16) / LPP, NTOP / LPP, LPP == 2>(p.frames, p.stride, N, on, pix, role, v);      // (nt at two lanes per pixel: fast_ml_common.hpp)
-#if defined(NL_ROUND_STATS) && defined(NL_MLZ_EXP_TIMING)
-        __builtin_amdgcn_sched_barrier(0); sp1 = __builtin_readcyclecounter(); __builtin_amdgcn_sched_barrier(0);
-#endif
         sort_network<NS>(v);
-#if defined(NL_ROUND_STATS) && defined(NL_MLZ_EXP_TIMING)
-        __builtin_amdgcn_sched_barrier(0); sp2 = __builtin_readcyclecounter(); __builtin_amdgcn_sched_barrier(0);
-#endif
-#endif
     } else {
         n = ml_gather_sorted<LPP, NS, L::FULL && !WINSOR, 32, 32, L::NSL, (NTOP - 16) / LPP, NTOP / LPP, LPP == 2 && !WINSOR>(p.frames, p.stride, N, on, pix,
                                                                                                               role, v);
@@ -433,9 +398,6 @@ void stack_sigma_mlz_kernel(StackArgs p, FastArgs q)
         c_sel = bcast_f(std::integral_constant<int, 0>{}, v[NS / 2]);
         float t_lo, t_hi;                                  // innermost values of the low / high column
         select_ends<L, LPP, NS, V>(v, role, col, t_lo, t_hi);
-#if defined(NL_ROUND_STATS) && defined(NL_MLZ_EXP_TIMING)
-        __builtin_amdgcn_sched_barrier(0); sp3 = __builtin_readcyclecounter(); __builtin_amdgcn_sched_barrier(0);
-#endif
         // moments of every sample of the pixel, the ends of the runs clamped to [t_lo, t_hi]: the KL + KH samples
         // of the columns count as t_lo / t_hi (a missing sample, +Inf, as t_hi) and are taken off again
         {
@@ -522,12 +484,6 @@ void stack_sigma_mlz_kernel(StackArgs p, FastArgs q)
         col[(V::PS + 6) * PW] = x_in_lo;
         col[(V::PS + 7) * PW] = x_in_hi;
     }
-#if defined(NL_ROUND_STATS) && defined(NL_MLZ_EXP_TIMING)
-    if (threadIdx.x == 0) {
-        const unsigned long long sp4 = __builtin_readcyclecounter();
-        NL_STAT(8, sp1 - sp0); NL_STAT(9, sp2 - sp1); NL_STAT(10, sp3 - sp2); NL_STAT(11, sp4 - sp3); NL_STAT(12, 1);
-    }
-#endif
     };   // ---- end of the sorting phase ----
 
     // ---- rounds phase of block `blk`: columns at `colbase`, tables at `tabbase` ----
@@ -535,9 +491,6 @@ void stack_sigma_mlz_kernel(StackArgs p, FastArgs q)
     int c_lo_total = 0, c_hi_total = 0;
     int tid = (int)threadIdx.x;
     const int lane = tid & 63;
-#if defined(NL_ROUND_STATS) && defined(NL_MLZ_EXP_TIMING)
-    const unsigned long long exp_t0 = __builtin_readcyclecounter();      // (timing experiment: cycles of the rounds phase)
-#endif
     // ---- rounds phase: PACK: lane = pixel of the workgroup; else every lane of a pixel runs its rounds ----
     const int role = L::PACK ? 0 : (int)(threadIdx.x % LPP);         // (role 0 reports)
     const int slot_px = L::PACK ? min(lane, PW - 1) : (int)(threadIdx.x / LPP);      // (PW < 64: the upper lanes idle)
@@ -610,11 +563,7 @@ void stack_sigma_mlz_kernel(StackArgs p, FastArgs q)
     // (+8: the means are taken with a hardware reciprocal of the sample count, <= 1 ulp, instead of IEEE divisions --
     // a round is a chain of dependent operations in ONE wave that holds the workgroup's LDS and wave slots, and the two
     // divisions and two correctly rounded square roots were a fifth of its instructions)
-#ifdef NL_MLZ_IEEE_ROUNDS
-    constexpr float kErrF = (float)(2 * L::ROUNDINGS + 8);
-#else
     constexpr float kErrF = (float)(2 * L::ROUNDINGS + 16);
-#endif
 
     while (__any(active)) {
         const int cnt = b - a;
@@ -660,19 +609,10 @@ void stack_sigma_mlz_kernel(StackArgs p, FastArgs q)
         }
         const float dsum = (d_fix + dz) + (sl1 + sh1);
         const float qsum = (q_fix + qz) + (sl2 + sh2);
-#ifdef NL_MLZ_IEEE_ROUNDS
-        const float inv_cnt = 1.0f / fcnt;
-        const float delta = dsum / fcnt;                   // mean~ - c
-#else
         const float inv_cnt = __builtin_amdgcn_rcpf(fcnt);
         const float delta = dsum * inv_cnt;                // mean~ - c
-#endif
         const float m = c + delta;
-#ifdef NL_MLZ_IEEE_ROUNDS
-        const float aa = qsum / fcnt;                      // E[(x-c)^2]~
-#else
         const float aa = qsum * inv_cnt;                   // E[(x-c)^2]~
-#endif
         const float bb = delta * delta;
         const float var = fmaxf(aa - bb, 0.0f);
 
@@ -690,14 +630,9 @@ void stack_sigma_mlz_kernel(StackArgs p, FastArgs q)
         const float v_dn = fmaxf(var - err_o, 0.0f);
         const float v_hi = v_up + v_up * eps_r + e_m * e_m;
         const float v_lo = fmaxf(v_dn - v_dn * eps_r, 0.0f);
-#ifdef NL_MLZ_IEEE_ROUNDS
-        float s_max = __fsqrt_rn(v_hi) * (1.0f + 4.0f * kU);
-        float s_min = __fsqrt_rn(v_lo) * (1.0f - 4.0f * kU);
-#else
         // hardware square root: <= 1 ulp = 2u, flushes denormals (the absolute term; a flushed lower end is 0, still a lower end)
         float s_max = __builtin_amdgcn_sqrtf(v_hi) * (1.0f + 6.0f * kU) + 4.0e-19f;
         float s_min = __builtin_amdgcn_sqrtf(v_lo) * (1.0f - 6.0f * kU);
-#endif
         bool bail = !(v_hi < 3.0e38f);
 
         if constexpr (WINSOR) {
@@ -879,9 +814,6 @@ void stack_sigma_mlz_kernel(StackArgs p, FastArgs q)
         c_lo_total += __shfl_xor(c_lo_total, o, 64);
         c_hi_total += __shfl_xor(c_hi_total, o, 64);
     }
-#if defined(NL_ROUND_STATS) && defined(NL_MLZ_EXP_TIMING)
-    if (lane == 0) { NL_STAT(6, __builtin_readcyclecounter() - exp_t0); NL_STAT(7, 1); }
-#endif
     if constexpr (L::PACK) {
         if (lane == 0) add_clip_totals(partial_slot(p, blk), c_lo_total, c_hi_total);      // (the one wave of the rounds phase)
     } else {
@@ -898,19 +830,7 @@ void stack_sigma_mlz_kernel(StackArgs p, FastArgs q)
     sorting_phase((int64_t)blockIdx.x, lds);
     if constexpr (L::PACK) {
         __syncthreads();
-#ifdef NL_MLZ_EXP_SORTONLY
-        if (p.npix > 0) return;                            // (timing experiment: the sorting phase alone)
-#endif
         if ((int)(threadIdx.x >> 6) != (int)(blockIdx.x % (L::BLOCK / 64))) return;
-#ifdef NL_MLZ_EXP_PRIO
-        __builtin_amdgcn_s_setprio(NL_MLZ_EXP_PRIO);
-#endif
-#ifdef NL_MLZ_EXP_SLEEP
-        if (p.npix > 0) {                                  // (timing experiment: the rounds wave only holds its slot)
-            for (int i = 0; i < NL_MLZ_EXP_SLEEP; i++) __builtin_amdgcn_s_sleep(127);
-            return;
-        }
-#endif
         // (s_setprio 3 for this wave -- it holds the workgroup's LDS -- measured 0.5 % slower, two interleaved runs)
     } else {
         lds_settle();

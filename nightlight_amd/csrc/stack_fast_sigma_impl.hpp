@@ -41,19 +41,14 @@ namespace nl {
 //                other instantiation reads p.reject_map: the store is not in their code.  No RECORD or CONT form (the
 //                maps pass runs no decision pass and no cascade).
 
-#ifndef NL_CERT_ON
-#define NL_CERT_ON(ns) true
-#endif
+// which network sizes run the invariant-interval certificate of the winsorization loop (CERT in the kernel): all of them
+constexpr bool sigma_cert_on(int ns) { return true; }
 // Round 8, both for the 128-position kernels only, where they were measured to pay.  The same
 // source costs the smaller exact-size kernels registers -- 64 positions 86 -> 100 and a wave per SIMD, 96: 114 -> 132,
 // 112: 141 -> 148 -- and at 112 frames, the one of them that was timed with both, it gained nothing.
-// NL_GATHER_RUN: the gather's running descriptor base.  NL_PEEL_FIRST: the peeled first pass.
-#ifndef NL_GATHER_RUN
-#define NL_GATHER_RUN(ns) ((ns) >= 128)
-#endif
-#ifndef NL_PEEL_FIRST
-#define NL_PEEL_FIRST(ns) ((ns) >= 128)
-#endif
+// sigma_gather_run: the gather's running descriptor base.  sigma_peel_first: the peeled first pass.
+constexpr bool sigma_gather_run(int ns) { return ns >= 128; }
+constexpr bool sigma_peel_first(int ns) { return ns >= 128; }
 // WAVE-OWNED kernels: the zonal plain-sigma kernel of a stack of exactly NS frames, where a wave
 // shares nothing with the other waves of its workgroup -- no barrier, no LDS but the lookup rows below, of which a
 // thread reads and writes its own column only.  It reserves its own run of the generic
@@ -62,12 +57,10 @@ namespace nl {
 // half of their waves and keep the per-workgroup reservation, see flush()) and adds its own clip totals to a slot.  The
 // body is correct for any block size that is a multiple of 64 (stack_fast.hip:launch_dominant has the measured choice).
 // Measured at 128 frames only.
-#ifndef NL_WAVE_OWNED
-#define NL_WAVE_OWNED(ns) ((ns) >= 128)
-#endif
+constexpr bool sigma_wave_owned_size(int ns) { return ns >= 128; }
 constexpr bool sigma_wave_owned(int ns, bool zonal, bool winsor, bool tight, bool record, bool cont)
 {
-    return zonal && !winsor && tight && !record && !cont && NL_WAVE_OWNED(ns);
+    return zonal && !winsor && tight && !record && !cont && sigma_wave_owned_size(ns);
 }
 // LDS LOOKUP, wave-owned kernels only: what a clipping pass of the loop looks up by a per-lane
 // index -- the zone tables at a and NS - b, the median pair at kk -- sits in LDS rows a lane fills once and reads with
@@ -75,17 +68,14 @@ constexpr bool sigma_wave_owned(int ns, bool zonal, bool winsor, bool tight, boo
 // s_lut[entry * 256 + thread] (LdsLookup, fast_common.hpp): a thread reads and writes its own column only, so a wave
 // shares nothing with its neighbours and orders its accesses by its own s_waitcnt -- no barrier.  The peeled first
 // pass keeps its folded constants and reads no LDS.
-#ifndef NL_LDS_LOOKUP
-#define NL_LDS_LOOKUP(ns) ((ns) >= 128)
-#endif
+constexpr bool sigma_lds_lookup_size(int ns) { return ns >= 128; }
 constexpr bool sigma_lds_lookup(int ns, bool zonal, bool winsor, bool tight, bool record, bool cont)
 {
-    return sigma_wave_owned(ns, zonal, winsor, tight, record, cont) && NL_LDS_LOOKUP(ns);
+    return sigma_wave_owned(ns, zonal, winsor, tight, record, cont) && sigma_lds_lookup_size(ns);
 }
 
-#ifndef NL_WINSOR_WL
-#define NL_WINSOR_WL(ns) ((ns) >= 112 ? 20 : ((ns) >= 80 ? 16 : ((ns) / 4 + 3) / 4 * 4))
-#endif
+// WL of the winsorized zonal kernels: the sorted positions below it (and as many at the top) may reach a clamp
+constexpr int sigma_winsor_wl(int ns) { return ns >= 112 ? 20 : (ns >= 80 ? 16 : (ns / 4 + 3) / 4 * 4); }
 
 // Occupancy.  The winsorized zonal kernels are chains of dependent operations (interval arithmetic, square roots,
 // divisions): a third wave per SIMD is worth a few spilled registers.  The instantiations for stacks of exactly NS frames
@@ -115,7 +105,7 @@ void stack_sigma_fast_kernel(StackArgs p, FastArgs q)
     static_assert(!ZONAL || NS >= 16, "zonal passes need room between the zones");
     constexpr int ZL = KZ;                                    // low zone  = positions [0, ZL)
     constexpr int ZH = ZONAL ? NS - KZ - KP : NS;             // high zone = positions [ZH, NS)
-    // LDS lookup rows (see NL_LDS_LOOKUP): the four zone tables (ZL rows tdl, ZL rows tql, NS - ZH rows tdh and as many
+    // LDS lookup rows (see sigma_lds_lookup): the four zone tables (ZL rows tdl, ZL rows tql, NS - ZH rows tdh and as many
     // tqh) and the median window v[LK0 - 1 ... LK0 + LKN - 1], a median at kk in [LK0, LK0 + LKN) reading rows kk - LK0 and
     // the next -- 41 rows of 256 floats at 128 positions, 41 984 bytes: three workgroups per compute unit (160 KiB), as the
     // registers allow.  No other instantiation references the array.
@@ -204,7 +194,7 @@ void stack_sigma_fast_kernel(StackArgs p, FastArgs q)
             lo_pads = min(max(KZ / 2 + 1 - (N - ZH), 0), KZ == 4 ? KZ / 2 : KZ / 2 - 1);     // (N is wave-uniform)
         }
         bool clean = false;                                   // wave-uniform: no lane holds a NaN or an infinite sample
-        const int n = gather_sorted<NS, 16, Sorter, true, !TIGHT, NL_GATHER_RUN(NS) && !RECORD>(p.frames, p.stride, N, boff, v, lo_pads, &clean);
+        const int n = gather_sorted<NS, 16, Sorter, true, !TIGHT, sigma_gather_run(NS) && !RECORD>(p.frames, p.stride, N, boff, v, lo_pads, &clean);
         bool to_exact = false;
 
         float res = p.ref_loc;
@@ -289,7 +279,7 @@ void stack_sigma_fast_kernel(StackArgs p, FastArgs q)
         // the inner half contributes these fixed sums
         // (the clamps sit at +-1.5 sigma: 6.7 % of a Gaussian column per side, 8.6 +- 2.8 samples of 128;
         // a pixel with more goes to the replay through shape_ok)
-        constexpr int WL = ZONAL ? NL_WINSOR_WL(NS) : 0, WH = ZONAL ? NS - WL - KP : NS;
+        constexpr int WL = ZONAL ? sigma_winsor_wl(NS) : 0, WH = ZONAL ? NS - WL - KP : NS;
         float d_in = 0.0f, q_in = 0.0f;
         if constexpr (ZONAL && WINSOR) {
             static_assert(WL >= ZL && WH <= ZH && (WL - ZL) % 4 == 0 && (WH - WL) % 4 == 0, "winsor zones");
@@ -329,7 +319,7 @@ void stack_sigma_fast_kernel(StackArgs p, FastArgs q)
         // that waits for the zone tables: a branch it can place divides the block behind the sorting network, and the
         // kernel then takes 191 - 199 registers instead of 164 -- two waves per SIMD; tools/final_check.sh checks the headline's count.  For the same reason c above stays
         // a pick: a branch of its own for v[NS / 2] cost 27 registers more than the 26 instructions were worth.)
-        constexpr bool PEEL = NL_PEEL_FIRST(NS) && ZT && TIGHT && !RECORD;
+        constexpr bool PEEL = sigma_peel_first(NS) && ZT && TIGHT && !RECORD;
         int peel_s = 0;
         if constexpr (PEEL) {
             peel_s = __builtin_amdgcn_readfirstlane(clean ? 1 : 0);
@@ -421,19 +411,10 @@ void stack_sigma_fast_kernel(StackArgs p, FastArgs q)
             // (the means through a hardware reciprocal of the sample count, <= 1 ulp, and the square roots in hardware, <= 1 ulp:
             // these are OUR moments and the ends of an interval, not the reference's arithmetic -- the margins below pay for it:
             // two IEEE divisions and two correctly rounded square roots were 45 of a clipping pass's 540 instructions)
-#ifdef NL_IEEE_PASS
-            const float inv_cnt = 1.0f / fcnt;
-            const float delta = dsum / fcnt;             // mean~ - c
-#else
             const float inv_cnt = __builtin_amdgcn_rcpf(fcnt);
             const float delta = dsum * inv_cnt;          // mean~ - c
-#endif
             const float m = c + delta;
-#ifdef NL_IEEE_PASS
-            const float aa = qsum / fcnt;                // E[(x-c)^2]~
-#else
             const float aa = qsum * inv_cnt;             // E[(x-c)^2]~
-#endif
             const float bb = delta * delta;
             const float var = fmaxf(aa - bb, 0.0f);
 
@@ -442,11 +423,7 @@ void stack_sigma_fast_kernel(StackArgs p, FastArgs q)
             // <= (NS/4+7) u mean|e|, and 2|delta| mean|e| <= aa + bb: together <= (NS/2+17) u (aa+bb)
             // (ZT: the zone tables are running sums over the same positions -- a zone term passes through at most ZL resp.
             // NS-ZH additions there as under the rank masks, which only added exact zeros -- so the constant is unchanged)
-#ifdef NL_IEEE_PASS
-            const float err_o = ((float)(NS / 2 + 24)) * kU * (aa + bb);
-#else
             const float err_o = ((float)(NS / 2 + 32)) * kU * (aa + bb);     // (+8: the reciprocal's ulp in delta, delta^2 and aa)
-#endif
             // reference: relative gamma_(n+3) on its variance, its mean off by <= e_m
             // (the scaling by kU = 2^-24 is exact, so these are 1.02f * (fcnt + 8) * kU etc. bit for bit, one multiply fewer)
             const float eps_r = (fcnt + 8.0f) * (1.02f * kU);
@@ -455,14 +432,9 @@ void stack_sigma_fast_kernel(StackArgs p, FastArgs q)
             const float v_dn = fmaxf(var - err_o, 0.0f);
             const float v_hi = v_up + v_up * eps_r + e_m * e_m;
             const float v_lo = fmaxf(v_dn - v_dn * eps_r, 0.0f);
-#ifdef NL_IEEE_PASS
-            float s_max = __fsqrt_rn(v_hi) * (1.0f + 4.0f * kU);
-            float s_min = __fsqrt_rn(v_lo) * (1.0f - 4.0f * kU);
-#else
             // (hardware square root: <= 1 ulp = 2u, flushes denormals -- the absolute term; a flushed lower end is 0)
             float s_max = __builtin_amdgcn_sqrtf(v_hi) * (1.0f + 6.0f * kU) + 4.0e-19f;
             float s_min = __builtin_amdgcn_sqrtf(v_lo) * (1.0f - 6.0f * kU);
-#endif
             bool bail = !(v_hi < 3.0e38f);          // overflow / NaN (e.g. an Inf sample): exact kernel
 
             // ---- exact median (qsort.go:68-82): sorted column, position lookup ----
@@ -489,6 +461,9 @@ void stack_sigma_fast_kernel(StackArgs p, FastArgs q)
             // fp32 multiply then add, never fused), and the certain (c1, d1) / possible (c2, d2) clips they imply.  The
             // column is sorted, so the samples below a threshold are a prefix and those above it a suffix (pads are
             // +Inf): counted over the whole zone without rank masks, minus what is already excluded ----
+            // (written out here, in stack_fast_mlz_impl.hpp and in stack_fast_mlg_impl.hpp: as calls of one shared function
+            // these lines and the bracket above move instructions in the winsorized kernels of this file and in the generic
+            // LDS pass -- profiles/switch_retirement_codeobj.txt)
             float lo_min, lo_max, hi_min, hi_max;
             auto thresholds = [&](const float smin, const float smax) NL_INL {
                 const float tl0 = __fmul_rn(p.sig_lo, smin), tl1 = __fmul_rn(p.sig_lo, smax);
@@ -555,7 +530,7 @@ void stack_sigma_fast_kernel(StackArgs p, FastArgs q)
                 // A trial is an iteration of the SAME loop -- the one evaluation of the clamped variance, at the trial's clamp
                 // instead of the round's: a second inlined copy of that evaluation took the 128-position kernel from 165 to 237
                 // registers (two waves per SIMD instead of three: 4.5 -> 5.7 ms).
-                constexpr bool CERT = NL_CERT_ON(NS) && (ZONAL || NS <= 32) && !RECORD;
+                constexpr bool CERT = sigma_cert_on(NS) && (ZONAL || NS <= 32) && !RECORD;
                 float wl_h0 = s_min, wl_h1 = s_min;        // lower ends of the std one and two rounds ago
                 int wr = 0;
                 bool trial_next = false;                   // wave-uniform
@@ -645,11 +620,7 @@ void stack_sigma_fast_kernel(StackArgs p, FastArgs q)
                     const float wa = ((q0 + q1) + (q2 + q3)) * inv_cnt;      // covered by werr
                     const float wb = wd * wd;
                     wvar = fmaxf(wa - wb, 0.0f);
-#ifdef NL_IEEE_PASS
-                    werr = ((float)(NS / 2 + 34)) * kU * (wa + wb);
-#else
                     werr = ((float)(NS / 2 + 40)) * kU * (wa + wb);
-#endif
                     wmean_c = wd;                                  // mean of the copy, minus c
                     wrms = wa;                                     // E[(copy - c)^2]
                     };

@@ -42,27 +42,23 @@
 
 namespace nl {
 
-#ifndef NL_LF_CHUNK
-#define NL_LF_CHUNK 8
-#endif
+constexpr int kLfChunk = 8;       // samples per chunk of the sorted column (liveness classes, parking)
 // Parked chunks (round 6, NS = 128 only).  At three waves per SIMD the kernel has 168 registers, 128 of them the column: the
 // allocator spilled 9 - 31 of the rest to scratch and re-loaded ~20 of them per fit iteration -- SQ_WAIT_ANY (waves parked at
 // s_waitcnt) was 25 % of the wave cycles of the first stage (profiles/r06_linfit_pmc.txt), and three waves do not hide it.  The
-// NL_LF_PARK lowest and NL_LF_PARK highest chunks of the sorted column therefore live in LDS instead ([slot][thread]:
+// kLfPark lowest and kLfPark highest chunks of the sorted column therefore live in LDS instead ([slot][thread]:
 // ds_read2st64_b32 with constant offsets, conflict-free) and are read back chunk by chunk inside the sweeps.  The ends are the
 // chunks that die first (the reference rejects from the ends inwards; pads sit on top), so their reads fade out with the
-// iterations.  Measured on 128 / 112 / 100 frames x 4096^2 (profiles/r06_linfit_park.txt): nothing parked 16.8 / 14.8 / 13.5 ms,
+// iterations.  Measured on 128 / 112 / 100 frames x 4096^2 (profiles/r06_linfit_park.txt): nothing parked (rounds 2 - 5) 16.8 / 14.8 / 13.5 ms,
 // one chunk per end 16.0 / 13.9 / 12.7, two 16.2 / 14.0 / 12.8, three 16.8 / 14.3 / 12.9; every fourth chunk with its reads issued
 // one chunk ahead 16.1 - 16.4 / 14.1 (the reads ahead cost the registers the parking freed).  A fourth wave is out of reach: 128
 // registers would leave ~70 for the column, i.e. 58 parked samples = 14.5 KiB per wave, and 16 waves x 14.5 KiB exceed the
-// CU's 160 KiB.  NL_LF_PARK=0: everything in registers (the kernel of rounds 2 - 5).
-#ifndef NL_LF_PARK
-#define NL_LF_PARK 1
-#endif
+// CU's 160 KiB.
+constexpr int kLfPark = 1;
 template <int NS, int CH>
 struct LfPark {
     static constexpr int NC = NS / CH;
-    static constexpr int ends = (NS == 128) ? NL_LF_PARK : 0;
+    static constexpr int ends = (NS == 128) ? kLfPark : 0;
     static constexpr int slots = 2 * ends * CH;                       // parked samples per pixel
     static constexpr __host__ __device__ bool parked(int c) { return c < ends || c >= NC - ends; }
     static constexpr __host__ __device__ int slot(int c) { return c < ends ? c : c - (NC - 2 * ends); }
@@ -124,25 +120,25 @@ void stack_linfit_fast_kernel(StackArgs p, FastArgs q, LinfitStage g)
     }
     const bool to_exact = inf_any != 0;
 
-    using Park = LfPark<NS, NL_LF_CHUNK>;
+    using Park = LfPark<NS, kLfChunk>;
     __shared__ float park[Park::slots > 0 ? Park::slots : 1][256];
     if constexpr (Park::slots > 0) {
-        static_range<0, NS / NL_LF_CHUNK>([&](auto C) NL_INL {
+        static_range<0, NS / kLfChunk>([&](auto C) NL_INL {
             constexpr int c = decltype(C)::value;
             if constexpr (Park::parked(c))
-                static_range<0, NL_LF_CHUNK>([&](auto J) NL_INL {
+                static_range<0, kLfChunk>([&](auto J) NL_INL {
                     constexpr int j = decltype(J)::value;
-                    park[Park::slot(c) * NL_LF_CHUNK + j][threadIdx.x] = v[c * NL_LF_CHUNK + j];
+                    park[Park::slot(c) * kLfChunk + j][threadIdx.x] = v[c * kLfChunk + j];
                 });
         });
     }
     // x[0..CH) = the samples of chunk c: registers, or (parked chunks) this thread's column slots in LDS
 #define NL_CHUNK_VALS(c, x)                                                                                  \
-    float x[NL_LF_CHUNK];                                                                                    \
-    static_range<0, NL_LF_CHUNK>([&](auto J_) NL_INL {                                                        \
+    float x[kLfChunk];                                                                                       \
+    static_range<0, kLfChunk>([&](auto J_) NL_INL {                                                           \
         constexpr int j_ = decltype(J_)::value;                                                              \
-        if constexpr (Park::slots > 0 && Park::parked(c)) x[j_] = park[Park::slot(c) * NL_LF_CHUNK + j_][threadIdx.x]; \
-        else x[j_] = v[(c) * NL_LF_CHUNK + j_];                                                              \
+        if constexpr (Park::slots > 0 && Park::parked(c)) x[j_] = park[Park::slot(c) * kLfChunk + j_][threadIdx.x];    \
+        else x[j_] = v[(c) * kLfChunk + j_];                                                                 \
     })
 
     float res = p.ref_loc;
@@ -160,7 +156,7 @@ void stack_linfit_fast_kernel(StackArgs p, FastArgs q, LinfitStage g)
     // run the masked code.  The reference rejects from the ends of the sorted column inwards
     // (12 + 12 of 128 samples on the bench stack) and, in late iterations, singles in the
     // middle; 10-11 of 16 chunks are fully alive on average.
-    constexpr int CH = NL_LF_CHUNK, NC = NS / CH, CPW = 32 / CH;     // chunks per liveness word
+    constexpr int CH = kLfChunk, NC = NS / CH, CPW = 32 / CH;     // chunks per liveness word
     static_assert(NS % CH == 0, "chunks");
     while (__any(active) && (g.max_iters == 0 || iters < g.max_iters)) {
         iters++;
@@ -479,7 +475,7 @@ void stack_linfit_ml_kernel(StackArgs p, FastArgs q, LinfitStage g)
     // chunk classes as in the one-lane kernel: a chunk index is classified over ALL lanes of the wave
     // (lane r of a pixel holds ranks [128 r, 128 r + 128), so the clipped ends of a column sit in the
     // low chunks of its first and the high chunks of its last lane)
-    constexpr int CH = NL_LF_CHUNK, NC = NS / CH, CPW = 32 / CH;
+    constexpr int CH = kLfChunk, NC = NS / CH, CPW = 32 / CH;
     while (__any(active) && (g.max_iters == 0 || iters < g.max_iters)) {
         iters++;
         const float fm = (float)m;

@@ -1,5 +1,6 @@
 #!/bin/bash
-# A/B timing of library builds: tools/ab_lib.sh [nightlight_amd/libnlstack_<variant>.so ...]  (run on the GPU box)
+# A/B timing of library builds: tools/ab_lib.sh [build/<name>/libnlstack.so ...]  (the libraries of tools/build_variant.sh;
+# run on the GPU box)
 for lib in "" "$@"; do
   echo "== lib: ${lib:-default}"
   if [ -z "$lib" ]; then unset NLSTACK_LIB; else export NLSTACK_LIB=$PWD/$lib; fi

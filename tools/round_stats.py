@@ -31,10 +31,6 @@ with StackHandle(n, 4096, h, device=0) as st:
     if n > 128 and hasattr(lib, "nl_debug_round_stats_mlz"):
         lib.nl_debug_round_stats_mlz(out, 1)
         print("  LDS-column kernel hand-overs: missing %d, c2>=8 %d, d2>=8 %d, low zone %d, high zone %d; shape -> exact %d; winsor bail %d, guard>100 %d" % tuple(list(out)[:8]))
-        o = list(out)
-        if o[12]:
-            print("  sorting phase, cycles per block (wave 0): gather %.0f, network %.0f, ends %.0f, moments + window %.0f; rounds %.0f per block (%d)"
-                  % (o[8] / o[12], o[9] / o[12], o[10] / o[12], o[11] / o[12], o[6] / max(o[7], 1), o[7]))
     if n > 128 and hasattr(lib, "nl_debug_round_stats_mlg"):
         lib.nl_debug_round_stats_mlg(out, 1)
         g = list(out)
