@@ -182,7 +182,7 @@ func (op *OpStack) Apply(f []*fits.Image, c *ops.Context) (result *fits.Image, e
 	if err != nil {
 		return nil, err
 	}
-	if mode == StMADSigma && weights != nil {
+	if mode == StMADSigma && weights != nil && !op.WeightsFollowFrames { // (with the switch: nl_group_run_mad_weighted, below)
 		return nil, errors.New("MADSigma stacking with weights is still unimplemented") // reference panics, stack.go:185
 	}
 
@@ -244,13 +244,19 @@ func (op *OpStack) Apply(f []*fits.Image, c *ops.Context) (result *fits.Image, e
 	//	WeightsFollowFrames bool `json:"weightsFollowFrames,omitempty"`
 	// When it is set, the mode resolves to sigma or winsorized sigma clipping and there are weights, the rejection runs
 	// as always and each survivor is averaged with ITS frame's weight; otherwise a survivor takes the weight that
-	// QSelectMedianFloat32 left in its slot, as in the reference (stack.go:487).
+	// QSelectMedianFloat32 left in its slot, as in the reference (stack.go:487).  With MAD sigma and weights
+	// (include/nlstack_wmad.h) the same switch runs the MAD rejection and averages each survivor with its frame's weight;
+	// without it that combination fails as above.
 	var rc C.int
 	if op.WeightedLinearFit && mode == StLinearFit && weights != nil {
 		rc = C.nl_group_run_linfit_weighted(g, C.float(op.SigmaLow), C.float(op.SigmaHigh), C.float(op.RefFrameLoc),
 			(*C.float)(unsafe.Pointer(&data[0])), &clipLow, &clipHigh)
 	} else if op.WeightsFollowFrames && (mode == StSigma || mode == StWinsorSigma) && weights != nil {
 		rc = C.nl_group_run_clip_weighted(g, C.int(mode), C.float(op.SigmaLow), C.float(op.SigmaHigh), C.float(op.RefFrameLoc),
+			(*C.float)(unsafe.Pointer(&data[0])), &clipLow, &clipHigh)
+	} else if op.WeightsFollowFrames && mode == StMADSigma && weights != nil {
+		// (include/nlstack_wmad.h: without the switch weighted MAD sigma fails as in the reference)
+		rc = C.nl_group_run_mad_weighted(g, C.float(op.SigmaLow), C.float(op.SigmaHigh), C.float(op.RefFrameLoc),
 			(*C.float)(unsafe.Pointer(&data[0])), &clipLow, &clipHigh)
 	} else {
 		rc = C.nl_group_run(g, C.int(mode), C.float(op.SigmaLow), C.float(op.SigmaHigh), C.float(op.RefFrameLoc),

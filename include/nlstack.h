@@ -367,6 +367,12 @@ int nl_group_accumulate_finalize(nl_group_t *g, float weight_sum, float *out_hos
  * nlstack_wclip.h, which is part of this interface. */
 #include "nlstack_wclip.h"
 
+/* ---- MAD-sigma rejection with a weighted mean whose weights follow their frames (an extension: the reference panics
+ * on MAD sigma with weights, and nl_stack_run keeps failing with NL_ERR_WEIGHTED_MAD) ----
+ * nl_stack_run_mad_weighted, nl_stack_run_mad_weighted_async, nl_group_run_mad_weighted: declared in nlstack_wmad.h,
+ * which is part of this interface. */
+#include "nlstack_wmad.h"
+
 /* ---- stack of stacks (StackIncremental / Finalize, stack.go:924-944) ----
  * acc += result_of_last_pass * weight (first != 0: acc = result*weight),
  * on the device; finalize multiplies by 1/weight_sum and downloads. */

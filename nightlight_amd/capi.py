@@ -101,6 +101,10 @@ WLINFIT_EXPORTS = ["nl_stack_run_linfit_weighted", "nl_stack_run_linfit_weighted
 # their frames, an extension
 WCLIP_EXPORTS = ["nl_stack_run_clip_weighted", "nl_stack_run_clip_weighted_async", "nl_group_run_clip_weighted"]
 
+# every symbol include/nlstack_wmad.h declares (likewise): weighted MAD-sigma stacking whose weights follow their frames,
+# an extension
+WMAD_EXPORTS = ["nl_stack_run_mad_weighted", "nl_stack_run_mad_weighted_async", "nl_group_run_mad_weighted"]
+
 # every symbol include/nlstack_align.h declares (likewise)
 ALIGN_EXPORTS = ["nl_aligner_create", "nl_aligner_destroy", "nl_aligner_info", "nl_aligner_match",
                  "nl_aligner_match_stars"]
@@ -296,6 +300,9 @@ def open_library(path):
     L.nl_stack_run_clip_weighted.argtypes = _wclip_args
     L.nl_group_run_clip_weighted.argtypes = _wclip_args
     L.nl_stack_run_clip_weighted_async.argtypes = [vp, C.c_int, C.c_float, C.c_float, C.c_float]
+    L.nl_stack_run_mad_weighted.argtypes = _wlinfit_args
+    L.nl_group_run_mad_weighted.argtypes = _wlinfit_args
+    L.nl_stack_run_mad_weighted_async.argtypes = [vp, C.c_float, C.c_float, C.c_float]
     L.nl_stack_coverage.argtypes = [vp, _u16p]
     L.nl_group_coverage.argtypes = [vp, _u16p]
     L.nl_stack_last_coverage_ms.argtypes = [vp]

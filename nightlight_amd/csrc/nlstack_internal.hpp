@@ -66,6 +66,7 @@ enum class PassKind {
     Default,              // nl_stack_run_async and, with a tier, the nl_stack_run_maps* entries
     WeightedLinfit,       // nl_stack_run_linfit_weighted (include/nlstack_wlinfit.h): run_linfit_weighted; mode is NL_ST_LINEAR_FIT
     WeightedClip,         // nl_stack_run_clip_weighted (include/nlstack_wclip.h): run_clip_weighted
+    WeightedMad,          // nl_stack_run_mad_weighted (include/nlstack_wmad.h): run_mad_weighted; mode is NL_ST_MAD_SIGMA
 };
 // One stack pass as every pass entry of the handle and of the group asks for it, and where its results go; any output
 // may be null, the two maps are read by a maps pass only.

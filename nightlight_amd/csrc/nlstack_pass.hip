@@ -730,6 +730,48 @@ static int run_clip_weighted(nl_stack *h, const PassSetup &p, PassFacts *facts)
     return NL_OK;
 }
 
+// The weighted MAD-sigma pass (include/nlstack_wmad.h, an extension): StackMADSigma's rejection on the values alone, then
+// the mean of the survivors in frame order, each with its own frame's weight.  Every engine takes the bounds from two
+// medians and accumulates through wclip_take under that one round, so all of them give the same bits.
+//   1 ... 128 frames: the FOLLOW instantiations of the register-resident MAD kernels (launch_stack_mad_fast), whose second
+//      read is in frame order; pixels without a finite median go to the exact list;
+//   129 ... 512 frames: the record-only instantiation of the multi-lane MAD kernel leaves (lo, hi) per pixel in h->d_bounds,
+//      and the streaming kernel of the weighted clip pass reads the frames once under them (one recorded round is a
+//      complete record); it hands pixels without a finite median or without a sample to the exact list;
+//   then the column kernel's <mad,follow> instantiation over that list, and the reduction of the sharded clip counters.
+// Beyond 512 frames, after nl_stack_set_exact, on handles without a list and where the thresholds cannot be had
+// (ensure_bounds): the column kernel over the whole tile.  Plain protocol throughout, as run_clip_weighted.
+static int run_mad_weighted(nl_stack *h, const PassSetup &p, PassFacts *facts)
+{
+    nl::StackArgs a = p.a;
+    const bool lists = !h->force_exact && h->d_fb_list != nullptr;
+    bool listed = false;
+    if (lists && nl::mad_fast_supported(p.mode, false, a.n_frames, a.npix)) {
+        NL_HIP(nl::launch_stack_mad_fast(a, list_args(h, true, true), h->stream, &h->last_kernel, true));
+        listed = true;
+    } else if (lists && nl::fast_ml_supported(p.mode, false, a.n_frames, a.npix) && ensure_bounds(h)) {
+        const char *ignored = "";
+        a.bounds = h->d_bounds;
+        a.nrounds = h->d_nrounds;
+        nl::FastArgs none;
+        memset(&none, 0, sizeof none);
+        NL_HIP(nl::launch_stack_mad_ml(a, none, h->stream, &ignored, true));
+        NL_HIP(nl::launch_stack_clip_weighted(a, list_args(h, true, false), h->stream, &h->last_kernel, true));
+        a.bounds = nullptr;
+        a.nrounds = nullptr;
+        listed = true;
+    }
+    if (listed) {
+        NL_HIP(hipEventRecord(h->ev_dom1, h->stream));
+        facts->used_fast = true;
+    }
+    const int rc = listed ? replay_list(h, p.mode, false, a, Columns::Follow) : columns_over_tile(h, p.mode, false, a, Columns::Follow);
+    if (rc != NL_OK) return rc;
+    NL_HIP(reduce_clip_slots(h));
+    facts->has_counters = true;
+    return NL_OK;
+}
+
 // A pass that fails half-way (a launch or an event call after the first kernel) must not hand control back with work in
 // flight on the handle's streams and its bookkeeping half-updated: whatever was enqueued is waited for, the scratch
 // sets count as dirty, no list lengths or hints are taken from the broken pass.  The error of the failing call is kept.
@@ -754,7 +796,8 @@ static int settle_failed_pass(nl_stack_t *h, int rc)
 // default passes remember from one another: the weighted linear-fit pass (PassKind::WeightedLinfit; `mode` is
 // NL_ST_LINEAR_FIT), which keeps the weights the default linear fit drops and runs on run_linfit_weighted, and the weighted
 // clip pass whose weights follow their frames (PassKind::WeightedClip; `mode` resolves to sigma or winsorized sigma), which
-// runs on run_clip_weighted.
+// runs on run_clip_weighted.  A third: the weighted MAD-sigma pass (PassKind::WeightedMad; `mode` is NL_ST_MAD_SIGMA), the one
+// entry that takes MAD sigma with weights, on run_mad_weighted.
 static int run_async_impl(nl_stack_t *h, const nl::PassRequest &req)
 {
     NL_CHECK_HANDLE(h);
@@ -762,6 +805,10 @@ static int run_async_impl(nl_stack_t *h, const nl::PassRequest &req)
     const float sigma_low = req.sigma_low, sigma_high = req.sigma_high, ref_loc = req.ref_loc;
     int mode = req.mode;
     const bool maps = tier != nl::MapsTier::None, wlinfit = req.kind == PassKind::WeightedLinfit, wclip = req.kind == PassKind::WeightedClip;
+    const bool wmad = req.kind == PassKind::WeightedMad;
+    if (wmad && !h->has_weights)
+        return fail(NL_ERR_INVALID_ARG, "run_mad_weighted: the handle has no weights (nl_stack_set_weights); "
+                                        "the unweighted pass is nl_stack_run with NL_ST_MAD_SIGMA");
     if (wclip && !h->has_weights)
         return fail(NL_ERR_INVALID_ARG, "run_clip_weighted: the handle has no weights (nl_stack_set_weights); "
                                         "the unweighted pass is nl_stack_run");
@@ -773,7 +820,7 @@ static int run_async_impl(nl_stack_t *h, const nl::PassRequest &req)
     if (wclip && mode != NL_ST_SIGMA && mode != NL_ST_WINSOR_SIGMA)
         return fail(NL_ERR_INVALID_MODE, "run_clip_weighted: mode %d is neither NL_ST_SIGMA nor NL_ST_WINSOR_SIGMA", mode);
     bool weighted = h->has_weights;
-    if (mode == NL_ST_MAD_SIGMA && weighted)
+    if (mode == NL_ST_MAD_SIGMA && weighted && !wmad)
         return fail(NL_ERR_WEIGHTED_MAD, "MADSigma stacking with weights is still unimplemented");
     if ((mode == NL_ST_LINEAR_FIT && !wlinfit) || mode == NL_ST_MEDIAN) weighted = false;  // stack.go:158,188-189
     if (maps) {
@@ -856,6 +903,7 @@ static int run_async_impl(nl_stack_t *h, const nl::PassRequest &req)
     int rc = NL_OK;
     if (wlinfit) rc = run_linfit_weighted(h, p, &facts);
     else if (wclip) rc = run_clip_weighted(h, p, &facts);
+    else if (wmad) rc = run_mad_weighted(h, p, &facts);
     else switch (engine) {
     case Engine::Mean:            rc = run_mean(h, p, &facts); break;
     case Engine::MedianRegisters: rc = run_median(h, p, false); break;
@@ -994,6 +1042,19 @@ int nl_stack_run_clip_weighted(nl_stack_t *h, int mode, float sigma_low, float s
     return rc != NL_OK ? rc
                        : run_pass(h, {PassKind::WeightedClip, MapsTier::None, mode, sigma_low, sigma_high, ref_loc},
                                   {out_host, clip_low, clip_high, nullptr, nullptr});
+}
+
+// the weighted MAD-sigma pass (include/nlstack_wmad.h)
+int nl_stack_run_mad_weighted_async(nl_stack_t *h, float sigma_low, float sigma_high, float ref_loc)
+{
+    return nl::stack_start(h, {PassKind::WeightedMad, MapsTier::None, NL_ST_MAD_SIGMA, sigma_low, sigma_high, ref_loc});
+}
+
+int nl_stack_run_mad_weighted(nl_stack_t *h, float sigma_low, float sigma_high, float ref_loc,
+                              float *out_host, int64_t *clip_low, int64_t *clip_high)
+{
+    return run_pass(h, {PassKind::WeightedMad, MapsTier::None, NL_ST_MAD_SIGMA, sigma_low, sigma_high, ref_loc},
+                    {out_host, clip_low, clip_high, nullptr, nullptr});
 }
 
 // the maps passes (include/nlstack_maps.h, nlstack_fastmaps.h, nlstack_residentmaps.h, nlstack_deepmaps.h): one tier each

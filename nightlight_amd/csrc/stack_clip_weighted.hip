@@ -30,8 +30,9 @@
 
 namespace nl {
 
+// (R = 0: no front rounds, `front` is not read)
 template <int PX, int R>
-__device__ __forceinline__ void wclip_frames(const StackArgs &p, int64_t pix0, const float2 (&front)[PX][R],
+__device__ __forceinline__ void wclip_frames(const StackArgs &p, int64_t pix0, const float2 (&front)[PX][R > 0 ? R : 1],
                                              const float2 (&last)[PX], WclipAcc (&acc)[PX])
 {
     typedef float f4 __attribute__((ext_vector_type(4)));
@@ -67,7 +68,10 @@ __device__ __forceinline__ void wclip_frames(const StackArgs &p, int64_t pix0, c
 }
 
 // PX pixels per lane: 4 (aligned tiles, first = 0) or 1 (the pixels from `first` on: tails, unaligned tiles)
-template <int PX>
+// ONE: the weighted MAD-sigma pass (include/nlstack_wmad.h) -- its rejection has no loop, the record-only
+// stack_mad_ml_kernel leaves the pixel's one round (lo, hi) with nrounds = 1, or 0 for a pixel without a finite median or
+// without a sample, and one recorded round IS a complete record: no front rounds, no completeness test.
+template <int PX, bool ONE = false>
 __global__ __launch_bounds__(256) void stack_clip_weighted_kernel(StackArgs p, FastArgs q, int64_t first)
 {
     static_assert(PX == 1 || PX == 4, "one pixel or one 16-byte load per lane");
@@ -93,27 +97,33 @@ __global__ __launch_bounds__(256) void stack_clip_weighted_kernel(StackArgs p, F
         // fold: all of them as one; last: the round behind which the record ends
         float2 front[PX][kBoundRounds - 1], fold[PX][1], last[PX];
         bool may_fold = true;
+        if constexpr (ONE) {
 #pragma unroll
-        for (int j = 0; j < PX; j++) {
-            float lo = -__builtin_inff(), hi = __builtin_inff();
-            last[j] = wclip_no_round();
+            for (int j = 0; j < PX; j++) last[j] = nr[j] > 0 ? p.bounds[(size_t)(pix0 + j)] : wclip_no_round();
+        } else {
 #pragma unroll
-            for (int r = 0; r < kBoundRounds; r++) {
-                const float2 b = r < nr[j] ? p.bounds[(size_t)r * (size_t)p.npix + (size_t)(pix0 + j)] : wclip_no_round();
-                const bool in_front = r < nr[j] - 1;
-                if (r < kBoundRounds - 1) front[j][r] = in_front ? b : wclip_no_round();
-                lo = (in_front && b.x > lo) ? b.x : lo;
-                hi = (in_front && b.y < hi) ? b.y : hi;
-                last[j] = (r == nr[j] - 1) ? b : last[j];
+            for (int j = 0; j < PX; j++) {
+                float lo = -__builtin_inff(), hi = __builtin_inff();
+                last[j] = wclip_no_round();
+#pragma unroll
+                for (int r = 0; r < kBoundRounds; r++) {
+                    const float2 b = r < nr[j] ? p.bounds[(size_t)r * (size_t)p.npix + (size_t)(pix0 + j)] : wclip_no_round();
+                    const bool in_front = r < nr[j] - 1;
+                    if (r < kBoundRounds - 1) front[j][r] = in_front ? b : wclip_no_round();
+                    lo = (in_front && b.x > lo) ? b.x : lo;
+                    hi = (in_front && b.y < hi) ? b.y : hi;
+                    last[j] = (r == nr[j] - 1) ? b : last[j];
+                }
+                fold[j][0] = make_float2(lo, hi);
+                may_fold = may_fold && lo <= hi;
             }
-            fold[j][0] = make_float2(lo, hi);
-            may_fold = may_fold && lo <= hi;
         }
 
         // ---- one read of the frames in frame order ----
         WclipAcc acc[PX];
-        if (__all(may_fold)) wclip_frames<PX, 1>(p, pix0, fold, last, acc);
-        else                 wclip_frames<PX, kBoundRounds - 1>(p, pix0, front, last, acc);
+        if constexpr (ONE)        wclip_frames<PX, 0>(p, pix0, fold, last, acc);
+        else if (__all(may_fold)) wclip_frames<PX, 1>(p, pix0, fold, last, acc);
+        else                      wclip_frames<PX, kBoundRounds - 1>(p, pix0, front, last, acc);
 
         // ---- results, counts, hand-over ----
         float res[PX];
@@ -123,7 +133,7 @@ __global__ __launch_bounds__(256) void stack_clip_weighted_kernel(StackArgs p, F
         for (int j = 0; j < PX; j++) {
             const int n = acc[j].kept + acc[j].lo + acc[j].hi;
             // the reference's loop ends behind the last round on record (stack.go:427)
-            done[j] = nr[j] > 0 && n > 0 && (acc[j].last == 0 || acc[j].kept <= 1);
+            done[j] = nr[j] > 0 && n > 0 && (ONE || acc[j].last == 0 || acc[j].kept <= 1);
             res[j] = acc[j].num / acc[j].den;
             all_done = all_done && done[j];
             if (on && done[j]) {
@@ -176,7 +186,8 @@ static int wclip_grid(int64_t items)
 
 constexpr char kClipWeightedName[] = "stack_clip_weighted_kernel";
 
-hipError_t launch_stack_clip_weighted(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name)
+// one_round: the ONE instantiations (the weighted MAD-sigma pass)
+hipError_t launch_stack_clip_weighted(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name, bool one_round)
 {
     // (the exact list holds 32-bit pixel indices)
     if (!args.weights || !args.bounds || !args.nrounds || !fargs.fb_list || !fargs.fb_count || args.npix < 1 ||
@@ -185,16 +196,22 @@ hipError_t launch_stack_clip_weighted(const StackArgs &args, const FastArgs &far
     const bool vec_ok = (args.stride % 4 == 0) && ((reinterpret_cast<uintptr_t>(args.frames) & 15) == 0) &&
                         ((reinterpret_cast<uintptr_t>(args.out) & 15) == 0) && ((reinterpret_cast<uintptr_t>(args.nrounds) & 3) == 0);
     Launcher L(stream);
-    int64_t done = 0;
-    *name = kernel_name<kClipWeightedName, 1>();
-    if (vec_ok && args.npix >= 4) {
-        *name = kernel_name<kClipWeightedName, 4>();
-        const int64_t quads = args.npix >> 2;
-        L(stack_clip_weighted_kernel<4>, wclip_grid(quads), 256, 0, args, fargs, (int64_t)0);
-        if (L.err != hipSuccess) return L.err;
-        done = quads << 2;
-    }
-    if (done < args.npix) L(stack_clip_weighted_kernel<1>, wclip_grid(args.npix - done), 256, 0, args, fargs, done);
+    with_bool(one_round, [&](auto O) {
+        constexpr bool ONE = decltype(O)::value;
+        // (the default instantiations keep the names they had before the second parameter)
+        auto named = [](auto PX) { if constexpr (ONE) return kernel_name<kClipWeightedName, decltype(PX)::value, true>();
+                                   else               return kernel_name<kClipWeightedName, decltype(PX)::value>(); };
+        int64_t done = 0;
+        *name = named(std::integral_constant<int, 1>{});
+        if (vec_ok && args.npix >= 4) {
+            *name = named(std::integral_constant<int, 4>{});
+            const int64_t quads = args.npix >> 2;
+            L(stack_clip_weighted_kernel<4, ONE>, wclip_grid(quads), 256, 0, args, fargs, (int64_t)0);
+            if (L.err != hipSuccess) return;
+            done = quads << 2;
+        }
+        if (done < args.npix) L(stack_clip_weighted_kernel<1, ONE>, wclip_grid(args.npix - done), 256, 0, args, fargs, done);
+    });
     return L.err;
 }
 

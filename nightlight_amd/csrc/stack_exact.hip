@@ -260,7 +260,9 @@ __device__ float follow_mean(Col<S> a, int n, const float *fr, const StackArgs &
 // the fast maps pass; no other instantiation reads it).  FOLLOW (sigma / winsor,
 // W = false): the weighted clip pass whose weights follow their frames
 // (include/nlstack_wclip.h, an extension) -- the unweighted rejection, then
-// follow_mean over the frames; p.weights is set.
+// follow_mean over the frames; p.weights is set.  FOLLOW with MAD sigma: the
+// weighted MAD-sigma pass (include/nlstack_wmad.h, an extension) -- the
+// unweighted bounds, then the frames in frame order under them.
 template <int MODE, bool W, int LANES, bool MAPS = false, bool FOLLOW = false>
 __global__ __launch_bounds__(64) void stack_exact_kernel(StackArgs p)
 {
@@ -350,10 +352,20 @@ __global__ __launch_bounds__(64) void stack_exact_kernel(StackArgs p)
                 const float sd = mad * 1.4826f;
                 const float t_lo = p.sig_lo * sd, t_hi = p.sig_hi * sd;
                 const float lo = median - t_lo, hi = median + t_hi;
-                n = clip_pass<LANES, false>(a, b, n, lo, hi, c_lo, c_hi);
-                float s = 0.0f;
-                for (int i = 0; i < n; i++) s += a.get(i);
-                res = s / (float)n;
+                if constexpr (FOLLOW) {
+                    // (the one round (lo, hi) decides every sample as clip_pass does: the counts come from the same calls)
+                    WclipAcc acc;
+                    for (int k2 = 0; k2 < N; k2++)
+                        wclip_take<0>(fr[(int64_t)k2 * p.stride], p.weights[k2], nullptr, make_float2(lo, hi), acc);
+                    c_lo += acc.lo;
+                    c_hi += acc.hi;
+                    res = acc.num / acc.den;
+                } else {
+                    n = clip_pass<LANES, false>(a, b, n, lo, hi, c_lo, c_hi);
+                    float s = 0.0f;
+                    for (int i = 0; i < n; i++) s += a.get(i);
+                    res = s / (float)n;
+                }
             }
         } else if (MODE == NL_ST_LINEAR_FIT && W) {
             // The weighted linear-fit pass (include/nlstack_wlinfit.h; no counterpart in the reference).  The
@@ -579,6 +591,8 @@ static const ExactEntry kExactTable[] = {
     {ExactVariant::Plain, NL_ST_LINEAR_FIT, false, "stack_exact_kernel<linearfit>", launch_exact<NL_ST_LINEAR_FIT, false>},
     {ExactVariant::Follow, NL_ST_SIGMA, false, "stack_exact_kernel<sigma,follow>", launch_exact<NL_ST_SIGMA, false, false, true>},
     {ExactVariant::Follow, NL_ST_WINSOR_SIGMA, false, "stack_exact_kernel<winsor,follow>", launch_exact<NL_ST_WINSOR_SIGMA, false, false, true>},
+    // (the weighted MAD-sigma pass, include/nlstack_wmad.h: two columns, as the plain MAD kernel)
+    {ExactVariant::Follow, NL_ST_MAD_SIGMA, false, "stack_exact_kernel<mad,follow>", launch_exact<NL_ST_MAD_SIGMA, false, false, true>},
     {ExactVariant::Maps, NL_ST_MEDIAN, false, "stack_exact_kernel<median,maps>", launch_exact<NL_ST_MEDIAN, false, true>},
     {ExactVariant::Maps, NL_ST_SIGMA, true, "stack_exact_kernel<sigma,weighted,maps>", launch_exact<NL_ST_SIGMA, true, true>},
     {ExactVariant::Maps, NL_ST_SIGMA, false, "stack_exact_kernel<sigma,maps>", launch_exact<NL_ST_SIGMA, false, true>},

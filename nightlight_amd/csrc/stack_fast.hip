@@ -36,6 +36,7 @@
 
 #include "fast_common.hpp"
 #include "launch_common.hpp"
+#include "wclip_common.hpp"
 
 namespace nl {
 
@@ -105,6 +106,51 @@ __global__ __launch_bounds__(256) void stack_median_fast_kernel(StackArgs p, Fas
     }
 }
 
+// The second read of the MAD kernels: the frames of the pixel at byte offset boff, in frame order, all loads first, into
+// v[0 .. N-1]; positions past the last frame repeat it.  Returns the frame count.
+// (frame count and pitch re-read through opaque registers: otherwise the scalar offsets and descriptors of the first
+// gather are kept alive across both sorts for re-use here)
+template <int NS>
+__device__ __forceinline__ int reread_frame_order(const StackArgs &p, unsigned boff, float (&v)[NS])
+{
+    int N2 = p.n_frames;
+    asm volatile("" : "+s"(N2));
+    int64_t frame_bytes = p.stride * (int64_t)sizeof(float);
+    asm volatile("" : "+s"(frame_bytes));
+    const int last = N2 - 1;
+    static_chunks<0, NS / 4, 4>([&](auto C) NL_INL {
+        constexpr int c0 = 4 * decltype(C)::value;
+        const int f0 = min(c0, last);
+        const char *gb = reinterpret_cast<const char *>(p.frames) + (int64_t)f0 * frame_bytes;
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(gb), 0, -1, 0x00020000);
+        static_range<0, 4>([&](auto U) NL_INL {
+            constexpr int k = c0 + decltype(U)::value;
+            const int soff = (min(k, last) - f0) * (int)frame_bytes;
+            v[k] = __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, (int)boff, soff, 0));
+        });
+    });
+    return N2;
+}
+
+// The weighted MAD-sigma pass (include/nlstack_wmad.h, an extension), register-resident: the frames of a pixel, re-read in
+// frame order into v[0 .. N2-1] (positions past N2 hold a repeated frame: no sample), go one by one through wclip_take
+// under the single round bd = (lo, hi), each with its own frame's weight.
+template <int NS>
+__device__ __forceinline__ void mad_follow_take(const float (&v)[NS], int N2, const float *weights, float2 bd, WclipAcc &acc)
+{
+    static_chunks<0, NS, 4>([&](auto K) NL_INL {
+        constexpr int k = decltype(K)::value;
+        // (the frame count and the weights' pointer go through opaque registers every 8 samples: otherwise the masks of
+        // all NS `k < N2` selects and all NS scalar loads are made in front of the first sample and spilled)
+        if constexpr ((k & 7) == 0) asm volatile("" : "+s"(N2), "+s"(weights));
+        const float x = (k < N2) ? v[k] : __builtin_nanf("");
+        wclip_take<0>(x, weights[min(k, N2 - 1)], nullptr, bd, acc);
+        // (pinned as the unweighted chains are: otherwise they are sunk below all compares; wclip_take's flags are
+        // integers, so no sample parks a lane mask in SGPRs)
+        asm volatile("" : "+v"(acc.lo), "+v"(acc.hi), "+v"(acc.num), "+v"(acc.den));
+    });
+}
+
 // StackMADSigma (stack.go:536-605), register resident.  The clip bounds come from two
 // medians (of the samples, and of their absolute deviations from it), both order
 // independent, so the bounds, every clip decision and both counters are exact without
@@ -119,7 +165,10 @@ __global__ __launch_bounds__(256) void stack_median_fast_kernel(StackArgs p, Fas
 // (Inf - Inf); what the reference's quickselect makes of those depends on where they sit
 // (for some inputs it runs off the array and panics).  Such a pixel goes to the exact
 // kernel, which follows the reference step by step where that is defined.
-template <int NS>
+// FOLLOW: the weighted MAD-sigma pass (include/nlstack_wmad.h, an extension) -- the same bounds, and the second read,
+// which is in frame order already, goes sample by sample through wclip_take with its frame's weight (p.weights is set):
+// counts as before, num / den instead of sum / kept.
+template <int NS, bool FOLLOW = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NS > 80 ? 3 : 1, 8)))   // (96: 190 VGPRs otherwise, since the 128-position merge)
 void stack_mad_fast_kernel(StackArgs p, FastArgs q)
 {
@@ -172,26 +221,18 @@ void stack_mad_fast_kernel(StackArgs p, FastArgs q)
     const float lo = median - t_lo, hi = median + t_hi;
 
     // second read, frame order: all loads first, into the column's registers (free again)
-    // (frame count and pitch re-read through opaque registers: otherwise the scalar offsets and
-    // descriptors of the first gather are kept alive across both sorts for re-use here)
-    int N2 = p.n_frames;
-    asm volatile("" : "+s"(N2));
-    int64_t frame_bytes = p.stride * (int64_t)sizeof(float);
-    asm volatile("" : "+s"(frame_bytes));
-    const int last = N2 - 1;
-    static_chunks<0, NS / 4, 4>([&](auto C) NL_INL {
-        constexpr int c0 = 4 * decltype(C)::value;
-        const int f0 = min(c0, last);
-        const char *gb = reinterpret_cast<const char *>(p.frames) + (int64_t)f0 * frame_bytes;
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(gb), 0, -1, 0x00020000);
-        static_range<0, 4>([&](auto U) NL_INL {
-            constexpr int k = c0 + decltype(U)::value;
-            const int soff = (min(k, last) - f0) * (int)frame_bytes;
-            v[k] = __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, (int)boff, soff, 0));
-        });
-    });
+    const int N2 = reread_frame_order<NS>(p, boff, v);
     // counts as floats (exact far beyond 128): integer sums would be re-associated into a tree,
     // which keeps one lane mask per sample alive
+    int c_lo, c_hi;
+    float res;
+    if constexpr (FOLLOW) {
+        WclipAcc acc;
+        mad_follow_take<NS>(v, N2, p.weights, make_float2(lo, hi), acc);
+        c_lo = acc.lo;
+        c_hi = acc.hi;
+        res = acc.num / acc.den;                             // no survivor: 0/0 = NaN
+    } else {
     float f_lo = 0.0f, f_hi = 0.0f, f_kept = 0.0f, sum = 0.0f;
     static_chunks<0, NS, 4>([&](auto K) NL_INL {
         constexpr int k = decltype(K)::value;
@@ -208,8 +249,10 @@ void stack_mad_fast_kernel(StackArgs p, FastArgs q)
         // sample's lane masks are parked in SGPRs until then)
         asm volatile("" : "+v"(f_lo), "+v"(f_hi), "+v"(f_kept), "+v"(sum));
     });
-    int c_lo = (int)f_lo, c_hi = (int)f_hi;
-    float res = sum / f_kept;                                // no survivor: 0/0 = NaN, as the reference
+    c_lo = (int)f_lo;
+    c_hi = (int)f_hi;
+    res = sum / f_kept;                                      // no survivor: 0/0 = NaN, as the reference
+    }
     if (n == 0) res = p.ref_loc;
     const bool to_exact = on && degenerate;
     if (on && !to_exact) NL_STORE_RESULT(&p.out[pix], res);
@@ -251,6 +294,9 @@ void stack_mad_fast_kernel(StackArgs p, FastArgs q)
 // stay in their registers for the clip and the mean (summed in sorted order: the reference sums
 // in the order its quickselects left -- summation-order rounding either way).  Pixels with fewer
 // than 114 samples go to q.gen_list, which stack_mad_fast_kernel<128> finishes.
+// FOLLOW (the weighted MAD-sigma pass, include/nlstack_wmad.h): the bounds from the same selection, then a second read
+// in frame order through wclip_take; its narrow pixels are finished by stack_mad_fast_kernel<128, true>.
+template <bool FOLLOW = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8)))
 void stack_mad_bitonic_kernel(StackArgs p, FastArgs q)
 {
@@ -301,6 +347,18 @@ void stack_mad_bitonic_kernel(StackArgs p, FastArgs q)
     const float sd = mad * 1.4826f;                          // stack.go:574
     const float t_lo = p.sig_lo * sd, t_hi = p.sig_hi * sd;
     const float lo = median - t_lo, hi = median + t_hi;
+    int c_lo, c_hi;
+    float res;
+    if constexpr (FOLLOW) {
+        // the sorted registers cannot be summed in frame order: the column is free now, the frames are read again
+        // (L2 / MALL resident) into it, as stack_mad_fast_kernel's second read does
+        const int N2 = reread_frame_order<NS>(p, boff, v);
+        WclipAcc acc;
+        mad_follow_take<NS>(v, N2, p.weights, make_float2(lo, hi), acc);
+        c_lo = acc.lo;
+        c_hi = acc.hi;
+        res = acc.num / acc.den;                             // no survivor: 0/0 = NaN
+    } else {
     float f_lo = 0.0f, f_hi = 0.0f, f_kept = 0.0f, sum = 0.0f;
     int nn = n;
     static_chunks<0, NS, 4>([&](auto K) NL_INL {
@@ -317,8 +375,10 @@ void stack_mad_bitonic_kernel(StackArgs p, FastArgs q)
         sum += keep ? x : 0.0f;
         asm volatile("" : "+v"(f_lo), "+v"(f_hi), "+v"(f_kept), "+v"(sum));
     });
-    int c_lo = (int)f_lo, c_hi = (int)f_hi;
-    float res = sum / f_kept;                                // no survivor: 0/0 = NaN, as the reference
+    c_lo = (int)f_lo;
+    c_hi = (int)f_hi;
+    res = sum / f_kept;                                      // no survivor: 0/0 = NaN, as the reference
+    }
     if (n == 0) res = p.ref_loc;
     const bool to_exact = on && degenerate && !narrow;
     if (on && !to_exact && !narrow) NL_STORE_RESULT(&p.out[pix], res);
@@ -384,6 +444,7 @@ int fast_supported(int mode, bool weighted, int n_frames, int64_t npix)
 
 constexpr char kMedianFastName[] = "stack_median_fast_kernel";
 constexpr char kMadFastName[] = "stack_mad_fast_kernel";
+constexpr char kMadBitonicName[] = "stack_mad_bitonic_kernel";
 constexpr char kSigmaFastName[] = "stack_sigma_fast_kernel";
 
 hipError_t launch_stack_median_fast(const StackArgs &args, const FastArgs &fargs, hipStream_t stream,
@@ -415,21 +476,28 @@ int mad_fast_supported(int mode, bool weighted, int n_frames, int64_t npix)
     return (mode == NL_ST_MAD_SIGMA && !weighted && n_frames >= 1 && n_frames <= 128 && npix < kFastMaxPixels) ? 1 : 0;
 }
 
-hipError_t launch_stack_mad_fast(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name)
+// follow: the FOLLOW instantiations (the weighted MAD-sigma pass, include/nlstack_wmad.h; args.weights must be set)
+hipError_t launch_stack_mad_fast(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name, bool follow)
 {
+    if (follow && !args.weights) return hipErrorInvalidValue;
     Launcher L(stream);
     const unsigned blocks = pixel_grid(args.npix);
-    if (args.n_frames >= 114 && fargs.gen_list) {
-        *name = "stack_mad_bitonic_kernel";
-        L(stack_mad_bitonic_kernel, blocks, 256, 0, args, whole_tile(fargs));
-        // the pixels with fewer than 114 samples (aligned frames' borders): two sorts, second read
-        L(stack_mad_fast_kernel<128>, std::min(blocks, kGenericGrid), 256, 0, args, over_generic_list(fargs));
-        return L.err;
-    }
-    with_class<8, 16, 32, 48, 64, 80, 96, 112, 128>(args.n_frames, [&](auto C) {
-        constexpr int NS = decltype(C)::value;
-        *name = kernel_name<kMadFastName, NS>();
-        L(stack_mad_fast_kernel<NS>, blocks, 256, 0, args, fargs);
+    with_bool(follow, [&](auto F) {
+        constexpr bool FOLLOW = decltype(F)::value;
+        if (args.n_frames >= 114 && fargs.gen_list) {
+            if constexpr (FOLLOW) *name = kernel_name<kMadBitonicName, true>();
+            else                  *name = "stack_mad_bitonic_kernel";
+            L(stack_mad_bitonic_kernel<FOLLOW>, blocks, 256, 0, args, whole_tile(fargs));
+            // the pixels with fewer than 114 samples (aligned frames' borders): two sorts, second read
+            L(stack_mad_fast_kernel<128, FOLLOW>, std::min(blocks, kGenericGrid), 256, 0, args, over_generic_list(fargs));
+            return;
+        }
+        with_class<8, 16, 32, 48, 64, 80, 96, 112, 128>(args.n_frames, [&](auto C) {
+            constexpr int NS = decltype(C)::value;
+            if constexpr (FOLLOW) *name = kernel_name<kMadFastName, NS, true>();
+            else                  *name = kernel_name<kMadFastName, NS>();
+            L(stack_mad_fast_kernel<NS, FOLLOW>, blocks, 256, 0, args, fargs);
+        });
     });
     return L.err;
 }

@@ -80,7 +80,11 @@ hipError_t launch_stack_median_ml(const StackArgs &args, hipStream_t stream, con
 // StackMADSigma (stack.go:536-605) for 129..512 frames, as stack_mad_fast_kernel: merged
 // column -> median; column := |x - median| -> bitonic merge -> MAD; second read of the
 // pixel's frames (every lane its own) for the clip counts and the mean of the survivors.
-template <int LPP>
+// RECORD (the weighted MAD-sigma pass, include/nlstack_wmad.h): the kernel stops behind the bounds and leaves the pixel's
+// one round, p.bounds[pix] = (lo, hi) with p.nrounds[pix] = 1 -- or 0 for a pixel without a finite median or without a
+// sample -- for stack_clip_weighted_kernel<PX, true>: no second read, no result, no list, no counters.  (The lanes of a
+// pixel interleave the frames in the second read; a frame-order fp32 sum would be a chain through them per frame.)
+template <int LPP, bool RECORD = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8)))
 void stack_mad_ml_kernel(StackArgs p, FastArgs q)
 {
@@ -116,6 +120,13 @@ void stack_mad_ml_kernel(StackArgs p, FastArgs q)
     const float sd = mad * 1.4826f;
     const float t_lo = p.sig_lo * sd, t_hi = p.sig_hi * sd;
     const float lo = median - t_lo, hi = median + t_hi;
+    if constexpr (RECORD) {
+        if (on && role == 0) {
+            p.bounds[(size_t)pix] = make_float2(lo, hi);
+            p.nrounds[(size_t)pix] = (n > 0 && !degenerate) ? 1 : 0;
+        }
+        return;
+    }
 
     // second read: lane role r takes frames r, r+LPP, ... again (clipped descriptors as in the gather)
     int N2 = p.n_frames;
@@ -168,12 +179,18 @@ void stack_mad_ml_kernel(StackArgs p, FastArgs q)
     }
 }
 
-hipError_t launch_stack_mad_ml(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name)
+hipError_t launch_stack_mad_ml(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name, bool record)
 {
+    if (record && (!args.bounds || !args.nrounds)) return hipErrorInvalidValue;
     Launcher L(stream);
     with_ml_lanes(args.n_frames, [&](auto LPP) {
-        *name = kernel_name<kMadMlName, decltype(LPP)::value>();
-        L(stack_mad_ml_kernel<decltype(LPP)::value>, pixel_grid(args.npix, LPP), 256, 0, args, fargs);
+        if (record) {
+            *name = kernel_name<kMadMlName, decltype(LPP)::value, true>();
+            L(stack_mad_ml_kernel<decltype(LPP)::value, true>, pixel_grid(args.npix, LPP), 256, 0, args, fargs);
+        } else {
+            *name = kernel_name<kMadMlName, decltype(LPP)::value>();
+            L(stack_mad_ml_kernel<decltype(LPP)::value>, pixel_grid(args.npix, LPP), 256, 0, args, fargs);
+        }
     });
     return L.err;
 }

@@ -148,7 +148,9 @@ hipError_t launch_stack_median_fast(const StackArgs &args, const FastArgs &fargs
                                     const char **name, hipEvent_t dominant_done);
 // dominant_done (optional) is recorded right after the first, dominant kernel
 int mad_fast_supported(int mode, bool weighted, int n_frames, int64_t npix);
-hipError_t launch_stack_mad_fast(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name);
+// follow: the FOLLOW instantiations of the same kernels (the weighted MAD-sigma pass, include/nlstack_wmad.h; args.weights set)
+hipError_t launch_stack_mad_fast(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name,
+                                 bool follow = false);
 // 249..256 / 505..512 frames: zonal sigma / winsorized sigma pass with the clipping rounds on LDS
 // columns (stack_fast_mlz.hip); hand-over lists as the other fast kernels
 // generic pass of the multi-lane sigma / winsor kernels over fargs.in_list, whole columns in LDS (stack_fast_mlg.hip)
@@ -193,7 +195,9 @@ hipError_t launch_stack_sigma_decide(const StackArgs &args, hipStream_t stream, 
 constexpr int kMlNS = 128;     // samples per lane of the multi-lane kernels
 int fast_ml_supported(int mode, bool weighted, int n_frames, int64_t npix);
 hipError_t launch_stack_median_ml(const StackArgs &args, hipStream_t stream, const char **name);
-hipError_t launch_stack_mad_ml(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name);
+// record: the RECORD instantiations (the weighted MAD-sigma pass): only args.bounds / args.nrounds are written, one round
+hipError_t launch_stack_mad_ml(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name,
+                               bool record = false);
 unsigned ml_generic_grid(int n_frames, unsigned gen_hint);      // workgroups of launch_stack_sigma_mlg behind launch_stack_sigma_mlz
 
 // ---- stack_exact_coop.hip (bit-exact sigma replay, one wave per pixel) ----
@@ -255,9 +259,13 @@ int decide_shallow_supported(int mode, int n_frames, int64_t npix);
 hipError_t launch_stack_sigma_decide_shallow(const StackArgs &args, hipStream_t stream, bool winsor, const char **name);
 // stack_clip_weighted.hip: one streaming read of the frames under the thresholds in args.bounds / args.nrounds, the
 // weights from args.weights; pixels without a complete record go to fargs.fb_list, for launch_stack_exact_follow
-hipError_t launch_stack_clip_weighted(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name);
+// one_round: the instantiations for which one recorded round is a complete record (the weighted MAD-sigma pass,
+// include/nlstack_wmad.h, behind launch_stack_mad_ml(record))
+hipError_t launch_stack_clip_weighted(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name,
+                                      bool one_round = false);
 // stack_exact.hip: the column kernel's <follow> instantiations (NL_ST_SIGMA / NL_ST_WINSOR_SIGMA; one column: plan
-// with weighted = false; args.weights must be set), over the tile or over args.list
+// with weighted = false; NL_ST_MAD_SIGMA, the weighted MAD-sigma pass: two columns; args.weights must be set), over the
+// tile or over args.list
 hipError_t launch_stack_exact_follow(int mode, const StackArgs &args, int lanes, int grid, size_t lds_bytes,
                                      hipStream_t stream, const char **name);
 

@@ -312,10 +312,14 @@ Result OpStack::Apply(const std::vector<ImagePtr> &f, Context *c)
         // (the other extension: sigma / winsorized clipping averages each survivor with ITS frame's weight, not with
         // the one the reference's quickselect left in its slot)
         const bool followFrames = WeightsFollowFrames && (mode == StSigma || mode == StWinsorSigma) && !weights.empty();
+        // (the same switch with MAD sigma, include/nlstack_wmad.h: without it weighted MAD sigma fails as in the reference)
+        const bool followMad = WeightsFollowFrames && mode == StMADSigma && !weights.empty();
         if (rc == NL_OK && weightedFit)
             rc = nl_group_run_linfit_weighted(h, SigmaLow, SigmaHigh, RefFrameLoc, Resident ? nullptr : data.data(), &clipLow, &clipHigh);
         else if (rc == NL_OK && followFrames)
             rc = nl_group_run_clip_weighted(h, mode, SigmaLow, SigmaHigh, RefFrameLoc, Resident ? nullptr : data.data(), &clipLow, &clipHigh);
+        else if (rc == NL_OK && followMad)
+            rc = nl_group_run_mad_weighted(h, SigmaLow, SigmaHigh, RefFrameLoc, Resident ? nullptr : data.data(), &clipLow, &clipHigh);
         else if (rc == NL_OK)
             rc = nl_group_run(h, mode, SigmaLow, SigmaHigh, RefFrameLoc, Resident ? nullptr : data.data(), &clipLow, &clipHigh);
         if (rc != NL_OK) { out.err = nl_last_error(); break; }

@@ -25,7 +25,8 @@ struct OpStack : Operator, OpBase {
     // not in the reference either (an EXTENSION, include/nlstack_wclip.h): when the mode resolves to sigma or winsorized
     // sigma clipping and the weighting is not none, average each survivor with its own frame's weight, instead of the
     // weight the reference's quickselect left in the survivor's slot (stack.go:487).  Parsed when present, emitted only
-    // when true.
+    // when true.  With MAD sigma and a weighting (include/nlstack_wmad.h) the same switch runs the MAD rejection and
+    // averages each survivor with its frame's weight; without it that combination fails as in the reference.
     bool WeightsFollowFrames = false; // json:"weightsFollowFrames"
     // not in the reference: a group of device handles the caller keeps across several Apply calls
     // (OpStackBatches).  When set, Apply stacks on it and leaves the result tile on the devices

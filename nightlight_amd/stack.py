@@ -236,6 +236,21 @@ class StackHandle:
         capi.check(self._lib.nl_stack_run_clip_weighted_async(self._h, int(mode), C.c_float(sigma_low),
                                                               C.c_float(sigma_high), C.c_float(ref_loc)))
 
+    def run_mad_weighted(self, sigma_low=2.75, sigma_high=2.75, ref_loc=0.0, out=None, fetch=True):
+        """One pass of weighted MAD-sigma stacking whose weights follow their frames (include/nlstack_wmad.h; an
+        EXTENSION: the reference panics on MAD sigma with weights, and run(ST_MAD_SIGMA) with weights raises
+        ERR_WEIGHTED_MAD): the reference's MAD-sigma rejection on the values alone, then the mean of the survivors
+        in frame order, each with its own frame's weight of set_weights.  Returns (result or None, clip_low,
+        clip_high) as run does; the counters are those of run(ST_MAD_SIGMA) without weights.  Without weights it
+        raises NlError (ERR_INVALID_ARG)."""
+        return _run_counted(self._lib.nl_stack_run_mad_weighted, self._h, _sigmas(sigma_low, sigma_high, ref_loc),
+                            self._result_array(out, fetch))
+
+    def run_mad_weighted_async(self, sigma_low=2.75, sigma_high=2.75, ref_loc=0.0):
+        """run_mad_weighted without the wait: finish() completes it."""
+        capi.check(self._lib.nl_stack_run_mad_weighted_async(self._h, C.c_float(sigma_low), C.c_float(sigma_high),
+                                                             C.c_float(ref_loc)))
+
     def coverage(self, out=None):
         """Whole-image uint16 map of how many active frames have a sample (not NaN) at each pixel: the tile's rows
         of `out` (made here, zero outside the tile, if not given).  No pass: the last result stays."""
@@ -747,6 +762,11 @@ class StackGroup:
         """StackHandle.run_clip_weighted over the tiles: (result or None, clip_low, clip_high)."""
         return _run_counted(self._lib.nl_group_run_clip_weighted, self._g,
                             (int(mode),) + _sigmas(sigma_low, sigma_high, ref_loc), self._result_array(download))
+
+    def run_mad_weighted(self, sigma_low=2.75, sigma_high=2.75, ref_loc=0.0, download=True):
+        """StackHandle.run_mad_weighted over the tiles: (result or None, clip_low, clip_high)."""
+        return _run_counted(self._lib.nl_group_run_mad_weighted, self._g, _sigmas(sigma_low, sigma_high, ref_loc),
+                            self._result_array(download))
 
     def coverage(self):
         """StackHandle.coverage over the tiles."""
