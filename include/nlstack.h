@@ -356,6 +356,11 @@ int nl_group_accumulate_finalize(nl_group_t *g, float weight_sum, float *out_hos
  * nl_stack_run_maps_deep, nl_group_run_maps_deep: declared in nlstack_deepmaps.h, which is part of this interface. */
 #include "nlstack_deepmaps.h"
 
+/* ---- the same maps from the MAD-sigma engines (1 ... 512 frames, unweighted), the median on its default kernels with
+ * zero maps, and the engines of nlstack_deepmaps.h for everything else ----
+ * nl_stack_run_maps_full, nl_group_run_maps_full: declared in nlstack_fullmaps.h, which is part of this interface. */
+#include "nlstack_fullmaps.h"
+
 /* ---- linear-fit rejection with a weighted mean of the survivors (an extension: the reference's fit takes no weights) ----
  * nl_stack_run_linfit_weighted, nl_stack_run_linfit_weighted_async, nl_group_run_linfit_weighted: declared in
  * nlstack_wlinfit.h, which is part of this interface. */

@@ -94,6 +94,10 @@ RESIDENTMAPS_EXPORTS = ["nl_stack_run_maps_resident", "nl_group_run_maps_residen
 # (129 ... 512 frames) sigma / winsorized stacks as well
 DEEPMAPS_EXPORTS = ["nl_stack_run_maps_deep", "nl_group_run_maps_deep"]
 
+# every symbol include/nlstack_fullmaps.h declares (likewise): the maps pass with the MAD-sigma engines (1 ... 512 frames)
+# and the median's default kernels as well
+FULLMAPS_EXPORTS = ["nl_stack_run_maps_full", "nl_group_run_maps_full"]
+
 # every symbol include/nlstack_wlinfit.h declares (likewise): the weighted linear-fit pass, an extension
 WLINFIT_EXPORTS = ["nl_stack_run_linfit_weighted", "nl_stack_run_linfit_weighted_async", "nl_group_run_linfit_weighted"]
 
@@ -289,7 +293,7 @@ def open_library(path):
     L.nl_group_last_mode.argtypes = [vp]
     _u16p = C.POINTER(C.c_uint16)
     _maps_args = [vp, C.c_int, C.c_float, C.c_float, C.c_float, _f32p, _i64p, _i64p, _u16p, _u16p]
-    for suffix in ("", "_fast", "_resident", "_deep"):
+    for suffix in ("", "_fast", "_resident", "_deep", "_full"):
         getattr(L, "nl_stack_run_maps" + suffix).argtypes = _maps_args
         getattr(L, "nl_group_run_maps" + suffix).argtypes = _maps_args
     _wlinfit_args = [vp, C.c_float, C.c_float, C.c_float, _f32p, _i64p, _i64p]

@@ -349,6 +349,14 @@ int nl_group_run_maps_deep(nl_group_t *g, int mode, float sigma_low, float sigma
                      {out_host, clip_low, clip_high, reject_low_host, reject_high_host});
 }
 
+int nl_group_run_maps_full(nl_group_t *g, int mode, float sigma_low, float sigma_high, float ref_loc,
+                           float *out_host, int64_t *clip_low, int64_t *clip_high, uint16_t *reject_low_host, uint16_t *reject_high_host)
+{
+    if (!g) return null_group();
+    return run_tiles(g, {PassKind::Default, MapsTier::Full, mode, sigma_low, sigma_high, ref_loc},
+                     {out_host, clip_low, clip_high, reject_low_host, reject_high_host});
+}
+
 // every tile counts on its own device and writes its own rows
 int nl_group_coverage(nl_group_t *g, uint16_t *coverage_host)
 {

@@ -60,6 +60,7 @@ enum class MapsTier {
     Fast,                 // nl_stack_run_maps_fast (include/nlstack_fastmaps.h): and the register-resident sigma / winsorized kernels, 2 ... 128 frames
     Resident,             // nl_stack_run_maps_resident (include/nlstack_residentmaps.h): and the linear fit's kernels and cascade
     Deep,                 // nl_stack_run_maps_deep (include/nlstack_deepmaps.h): and the LDS-column sigma / winsorized kernels, 129 ... 512 frames
+    Full,                 // nl_stack_run_maps_full (include/nlstack_fullmaps.h): and the MAD-sigma kernels, 1 ... 512 frames; the median on its default kernels
 };
 // the passes that run on an engine of their own instead of select_engine's (nlstack_pass.hip)
 enum class PassKind {

@@ -180,7 +180,9 @@ static bool fused_protocol_on()
 //   Column    (nl_stack_run_maps)           the one-pixel-per-lane column kernel, every mode but the mean;
 //   Fast      (nl_stack_run_maps_fast)      and run_sigma_maps on the register-resident sigma / winsorized kernels, 2 ... 128 frames;
 //   Resident  (nl_stack_run_maps_resident)  and run_listed's linear fit, on its own kernels and cascade;
-//   Deep      (nl_stack_run_maps_deep)      and run_sigma_maps on the LDS-column sigma / winsorized kernels, 129 ... 512 frames.
+//   Deep      (nl_stack_run_maps_deep)      and run_sigma_maps on the LDS-column sigma / winsorized kernels, 129 ... 512 frames;
+//   Full      (nl_stack_run_maps_full)      and run_listed's MAD sigma on its own kernels, 1 ... 512 frames; the median on its
+//                                           default kernels with the maps zeroed.
 // What no engine of its tier takes runs on the column kernel.  On every tier the pass takes part in none of what default
 // passes remember from one another: it takes and leaves no list-length hints, never runs the fused protocol, and leaves the
 // scratch sets as any other plain-protocol pass does; the linear fit drops the handle's weights as in every other
@@ -227,6 +229,14 @@ static Engine select_engine(const nl_stack *h, int mode, bool weighted, const nl
     if (a.reject_map && tier >= nl::MapsTier::Deep && fast && h->d_fb_list && h->d_gen_list && clip && !weighted &&
         nl::fast_ml_supported(mode, false, n, a.npix))
         return Engine::SigmaMaps;
+    if (a.reject_map && tier >= nl::MapsTier::Full && fast && h->d_fb_list && h->d_gen_list && mode == NL_ST_MAD_SIGMA && !weighted &&
+        (nl::mad_fast_supported(mode, false, n, a.npix) || nl::fast_ml_supported(mode, false, n, a.npix)))
+        return Engine::Listed;
+    // (the median rejects nothing: its default kernels, the maps zeroed)
+    if (a.reject_map && tier >= nl::MapsTier::Full && fast && mode == NL_ST_MEDIAN && nl::fast_supported(mode, weighted, n, a.npix))
+        return Engine::MedianRegisters;
+    if (a.reject_map && tier >= nl::MapsTier::Full && fast && mode == NL_ST_MEDIAN && nl::fast_ml_supported(mode, weighted, n, a.npix))
+        return Engine::MedianMultiLane;
     if (a.reject_map) return Engine::ExactColumns;      // a maps pass: the one engine that carries the per-pixel counts out of every mode
     if (fast && mode == NL_ST_MEDIAN && nl::fast_supported(mode, weighted, n, a.npix)) return Engine::MedianRegisters;
     if (fast && mode == NL_ST_MEDIAN && nl::fast_ml_supported(mode, weighted, n, a.npix)) return Engine::MedianMultiLane;
@@ -365,6 +375,8 @@ static int run_mean(nl_stack *h, const PassSetup &p, PassFacts *)
 // kernel to the full-sort one) or, 129 ... 512 frames, 2 or 4 lanes per pixel
 static int run_median(nl_stack *h, const PassSetup &p, bool multi_lane)
 {
+    // (a maps pass, MapsTier::Full: the median rejects nothing, as the mean)
+    if (p.maps()) NL_HIP(hipMemsetAsync(p.a.reject_map, 0, (size_t)p.a.npix * sizeof(unsigned), h->stream));
     if (!multi_lane) {
         NL_HIP(nl::launch_stack_median_fast(p.a, list_args(h, false, true), h->stream, &h->last_kernel, h->ev_dom1));
     } else {
@@ -387,6 +399,10 @@ static int run_median(nl_stack *h, const PassSetup &p, bool multi_lane)
 // Every word is first written by exactly one plain store of 1. or 3.; 2. only adds to words this pass wrote: no memset,
 // no stale word of an earlier pass.  Both kernels are bit-exact, so the result is the bit-exact one as well.  The stage
 // lengths stay in d_lf_count and the exact list's in the scratch set, with or without the map.
+// MAD sigma of a maps pass (MapsTier::Full, include/nlstack_fullmaps.h), likewise plain and on the one stream: the MAPS
+// instantiations of the dominant kernel (and, from 114 frames on, of the finisher of its hand-over list), where the lane
+// that stores a pixel's result stores its word as well; then 3. and 4.  Both medians are order independent, so the
+// counts need no guard: the only pixels left to 3. are those without a finite median.
 static int run_listed(nl_stack *h, const PassSetup &p, PassFacts *facts)
 {
     const nl::StackArgs &a = p.a;
@@ -394,8 +410,8 @@ static int run_listed(nl_stack *h, const PassSetup &p, PassFacts *facts)
         // counters exact (the bounds come from two medians); pixels with a non-finite median are replayed; 128 frames:
         // pixels with too few samples for the selection kernel go to the generic list
         const nl::FastArgs f = list_args(h, true, true);
-        if (a.n_frames <= 128) NL_HIP(nl::launch_stack_mad_fast(a, f, h->stream, &h->last_kernel));
-        else                   NL_HIP(nl::launch_stack_mad_ml(a, f, h->stream, &h->last_kernel));
+        if (a.n_frames <= 128) NL_HIP(nl::launch_stack_mad_fast(a, f, h->stream, &h->last_kernel, false, p.maps()));
+        else                   NL_HIP(nl::launch_stack_mad_ml(a, f, h->stream, &h->last_kernel, false, p.maps()));
         NL_HIP(hipEventRecord(h->ev_dom1, h->stream));
     } else {
         // bit-exact (sums run in sorted order; 129 ... 512 frames: 2 or 4 lanes per pixel, the sums chained through the
@@ -1057,7 +1073,8 @@ int nl_stack_run_mad_weighted(nl_stack_t *h, float sigma_low, float sigma_high, 
                     {out_host, clip_low, clip_high, nullptr, nullptr});
 }
 
-// the maps passes (include/nlstack_maps.h, nlstack_fastmaps.h, nlstack_residentmaps.h, nlstack_deepmaps.h): one tier each
+// the maps passes (include/nlstack_maps.h, nlstack_fastmaps.h, nlstack_residentmaps.h, nlstack_deepmaps.h, nlstack_fullmaps.h):
+// one tier each
 int nl_stack_run_maps(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc,
                       float *out_host, int64_t *clip_low, int64_t *clip_high, uint16_t *reject_low_host, uint16_t *reject_high_host)
 {
@@ -1083,6 +1100,13 @@ int nl_stack_run_maps_deep(nl_stack_t *h, int mode, float sigma_low, float sigma
                            float *out_host, int64_t *clip_low, int64_t *clip_high, uint16_t *reject_low_host, uint16_t *reject_high_host)
 {
     return run_pass(h, {PassKind::Default, MapsTier::Deep, mode, sigma_low, sigma_high, ref_loc},
+                    {out_host, clip_low, clip_high, reject_low_host, reject_high_host});
+}
+
+int nl_stack_run_maps_full(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc,
+                           float *out_host, int64_t *clip_low, int64_t *clip_high, uint16_t *reject_low_host, uint16_t *reject_high_host)
+{
+    return run_pass(h, {PassKind::Default, MapsTier::Full, mode, sigma_low, sigma_high, ref_loc},
                     {out_host, clip_low, clip_high, reject_low_host, reject_high_host});
 }
 

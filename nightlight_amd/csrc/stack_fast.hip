@@ -168,10 +168,14 @@ __device__ __forceinline__ void mad_follow_take(const float (&v)[NS], int N2, co
 // FOLLOW: the weighted MAD-sigma pass (include/nlstack_wmad.h, an extension) -- the same bounds, and the second read,
 // which is in frame order already, goes sample by sample through wclip_take with its frame's weight (p.weights is set):
 // counts as before, num / den instead of sum / kept.
-template <int NS, bool FOLLOW = false>
+// MAPS: the full maps pass (include/nlstack_fullmaps.h) -- the lane that stores a pixel's result also stores its two clip
+// counts, p.reject_map[pix] = c_lo | c_hi << 16 (a pixel without data: a zero word beside ref_loc; a pixel handed to the
+// exact list: nothing, the column kernel's MAPS replay stores its word).  No other instantiation touches reject_map.
+template <int NS, bool FOLLOW = false, bool MAPS = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NS > 80 ? 3 : 1, 8)))   // (96: 190 VGPRs otherwise, since the 128-position merge)
 void stack_mad_fast_kernel(StackArgs p, FastArgs q)
 {
+    static_assert(!(FOLLOW && MAPS), "the weighted MAD-sigma pass has no maps form");
     // q.in_list: the pixels stack_mad_bitonic_kernel handed over (the list's length is only known on
     // the device: fixed grid, grid-stride loop); otherwise the grid covers the tile
     const int64_t limit = q.in_list ? (int64_t)min(*q.in_count, q.in_capacity) : p.npix;
@@ -257,6 +261,9 @@ void stack_mad_fast_kernel(StackArgs p, FastArgs q)
     const bool to_exact = on && degenerate;
     if (on && !to_exact) NL_STORE_RESULT(&p.out[pix], res);
     if (!on || to_exact || n == 0) { c_lo = 0; c_hi = 0; }
+    if constexpr (MAPS) {
+        if (on && !to_exact) p.reject_map[pix] = (unsigned)c_lo | ((unsigned)c_hi << 16);
+    }
     c_lo_sum += c_lo;
     c_hi_sum += c_hi;
     const unsigned long long em = __ballot(to_exact);
@@ -296,10 +303,13 @@ void stack_mad_fast_kernel(StackArgs p, FastArgs q)
 // than 114 samples go to q.gen_list, which stack_mad_fast_kernel<128> finishes.
 // FOLLOW (the weighted MAD-sigma pass, include/nlstack_wmad.h): the bounds from the same selection, then a second read
 // in frame order through wclip_take; its narrow pixels are finished by stack_mad_fast_kernel<128, true>.
-template <bool FOLLOW = false>
+// MAPS (the full maps pass, as in stack_mad_fast_kernel): a pixel it finishes stores its word of p.reject_map, a narrow
+// pixel leaves it to stack_mad_fast_kernel<128, false, true>.
+template <bool FOLLOW = false, bool MAPS = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8)))
 void stack_mad_bitonic_kernel(StackArgs p, FastArgs q)
 {
+    static_assert(!(FOLLOW && MAPS), "the weighted MAD-sigma pass has no maps form");
     constexpr int NS = 128;
     const int64_t pix = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const bool on = pix < p.npix;
@@ -383,6 +393,9 @@ void stack_mad_bitonic_kernel(StackArgs p, FastArgs q)
     const bool to_exact = on && degenerate && !narrow;
     if (on && !to_exact && !narrow) NL_STORE_RESULT(&p.out[pix], res);
     if (!on || to_exact || narrow || n == 0) { c_lo = 0; c_hi = 0; }
+    if constexpr (MAPS) {
+        if (on && !to_exact && !narrow) p.reject_map[pix] = (unsigned)c_lo | ((unsigned)c_hi << 16);
+    }
     const unsigned long long em = __ballot(to_exact), gm = __ballot(narrow);
     if (em) {
         unsigned base = 0;
@@ -476,27 +489,50 @@ int mad_fast_supported(int mode, bool weighted, int n_frames, int64_t npix)
     return (mode == NL_ST_MAD_SIGMA && !weighted && n_frames >= 1 && n_frames <= 128 && npix < kFastMaxPixels) ? 1 : 0;
 }
 
+// "NAME<a, ..., maps>" / "NAME<maps>": the default pass's display name of a MAD kernel with "maps" as its last argument
+template <const char *BASE, auto... ARGS>
+static const char *mad_maps_kernel_name()
+{
+    static const std::string name = [] {
+        std::string s = BASE;
+        s += "<";
+        ((s += name_arg(ARGS), s += ", "), ...);
+        return s + "maps>";
+    }();
+    return name.c_str();
+}
+
 // follow: the FOLLOW instantiations (the weighted MAD-sigma pass, include/nlstack_wmad.h; args.weights must be set)
-hipError_t launch_stack_mad_fast(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name, bool follow)
+// maps: the MAPS instantiations (the full maps pass, include/nlstack_fullmaps.h; args.reject_map must be set)
+hipError_t launch_stack_mad_fast(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name, bool follow,
+                                 bool maps)
 {
     if (follow && !args.weights) return hipErrorInvalidValue;
+    if (maps && (!args.reject_map || follow)) return hipErrorInvalidValue;
     Launcher L(stream);
     const unsigned blocks = pixel_grid(args.npix);
-    with_bool(follow, [&](auto F) {
-        constexpr bool FOLLOW = decltype(F)::value;
+    // f(FOLLOW, MAPS): plain, follow or maps
+    auto with_form = [&](auto &&f) {
+        if (maps) f(std::false_type{}, std::true_type{});
+        else with_bool(follow, [&](auto F) { f(F, std::false_type{}); });
+    };
+    with_form([&](auto F, auto M) {
+        constexpr bool FOLLOW = decltype(F)::value, MAPS = decltype(M)::value;
         if (args.n_frames >= 114 && fargs.gen_list) {
-            if constexpr (FOLLOW) *name = kernel_name<kMadBitonicName, true>();
-            else                  *name = "stack_mad_bitonic_kernel";
-            L(stack_mad_bitonic_kernel<FOLLOW>, blocks, 256, 0, args, whole_tile(fargs));
+            if constexpr (MAPS)        *name = mad_maps_kernel_name<kMadBitonicName>();
+            else if constexpr (FOLLOW) *name = kernel_name<kMadBitonicName, true>();
+            else                       *name = "stack_mad_bitonic_kernel";
+            L(stack_mad_bitonic_kernel<FOLLOW, MAPS>, blocks, 256, 0, args, whole_tile(fargs));
             // the pixels with fewer than 114 samples (aligned frames' borders): two sorts, second read
-            L(stack_mad_fast_kernel<128, FOLLOW>, std::min(blocks, kGenericGrid), 256, 0, args, over_generic_list(fargs));
+            L(stack_mad_fast_kernel<128, FOLLOW, MAPS>, std::min(blocks, kGenericGrid), 256, 0, args, over_generic_list(fargs));
             return;
         }
         with_class<8, 16, 32, 48, 64, 80, 96, 112, 128>(args.n_frames, [&](auto C) {
             constexpr int NS = decltype(C)::value;
-            if constexpr (FOLLOW) *name = kernel_name<kMadFastName, NS, true>();
-            else                  *name = kernel_name<kMadFastName, NS>();
-            L(stack_mad_fast_kernel<NS, FOLLOW>, blocks, 256, 0, args, fargs);
+            if constexpr (MAPS)        *name = mad_maps_kernel_name<kMadFastName, NS>();
+            else if constexpr (FOLLOW) *name = kernel_name<kMadFastName, NS, true>();
+            else                       *name = kernel_name<kMadFastName, NS>();
+            L(stack_mad_fast_kernel<NS, FOLLOW, MAPS>, blocks, 256, 0, args, fargs);
         });
     });
     return L.err;

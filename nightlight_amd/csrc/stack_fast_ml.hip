@@ -84,10 +84,13 @@ hipError_t launch_stack_median_ml(const StackArgs &args, hipStream_t stream, con
 // one round, p.bounds[pix] = (lo, hi) with p.nrounds[pix] = 1 -- or 0 for a pixel without a finite median or without a
 // sample -- for stack_clip_weighted_kernel<PX, true>: no second read, no result, no list, no counters.  (The lanes of a
 // pixel interleave the frames in the second read; a frame-order fp32 sum would be a chain through them per frame.)
-template <int LPP, bool RECORD = false>
+// MAPS (the full maps pass, include/nlstack_fullmaps.h): the lane that stores a pixel's result also stores its two clip
+// counts, p.reject_map[pix] = c_lo | c_hi << 16 (zero beside ref_loc; nothing for a pixel of the exact list).
+template <int LPP, bool RECORD = false, bool MAPS = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8)))
 void stack_mad_ml_kernel(StackArgs p, FastArgs q)
 {
+    static_assert(!(RECORD && MAPS), "the record-only kernel stores no result and no map");
     constexpr int NS = kMlNS;
     const int lane = threadIdx.x & 63;
     const int role = threadIdx.x % LPP;
@@ -163,6 +166,9 @@ void stack_mad_ml_kernel(StackArgs p, FastArgs q)
     const bool to_exact = rep && degenerate;
     if (rep && !to_exact) NL_STORE_RESULT(&p.out[pix], res);
     if (!rep || to_exact || n == 0) { c_lo = 0; c_hi = 0; }
+    if constexpr (MAPS) {
+        if (rep && !to_exact) p.reject_map[pix] = (unsigned)c_lo | ((unsigned)c_hi << 16);
+    }
     wave_append(q.fb_list, q.fb_count, q.fb_capacity, to_exact, (unsigned)pix, lane);
     __shared__ int s_lo[4], s_hi[4];
 #pragma unroll
@@ -179,12 +185,20 @@ void stack_mad_ml_kernel(StackArgs p, FastArgs q)
     }
 }
 
-hipError_t launch_stack_mad_ml(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name, bool record)
+// maps: the MAPS instantiations (the full maps pass; args.reject_map must be set), named as the default pass's kernel
+// with "maps" as its last argument
+hipError_t launch_stack_mad_ml(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name, bool record,
+                               bool maps)
 {
     if (record && (!args.bounds || !args.nrounds)) return hipErrorInvalidValue;
+    if (maps && (!args.reject_map || record)) return hipErrorInvalidValue;
     Launcher L(stream);
     with_ml_lanes(args.n_frames, [&](auto LPP) {
-        if (record) {
+        if (maps) {
+            static const std::string maps_name = std::string(kMadMlName) + "<" + std::to_string(decltype(LPP)::value) + ", maps>";
+            *name = maps_name.c_str();
+            L(stack_mad_ml_kernel<decltype(LPP)::value, false, true>, pixel_grid(args.npix, LPP), 256, 0, args, fargs);
+        } else if (record) {
             *name = kernel_name<kMadMlName, decltype(LPP)::value, true>();
             L(stack_mad_ml_kernel<decltype(LPP)::value, true>, pixel_grid(args.npix, LPP), 256, 0, args, fargs);
         } else {

@@ -62,9 +62,9 @@ struct StackArgs {
     // decided: the replay computes its own bounds, as without these).  nullptr: off.
     float2 *bounds;
     unsigned char *nrounds;
-    // Maps pass (nl_stack_run_maps, nl_stack_run_maps_fast, nl_stack_run_maps_resident): [npix] words, the pixel's clipLow
+    // Maps pass (nl_stack_run_maps and the tiers above it): [npix] words, the pixel's clipLow
     // count | clipHigh count << 16.  Read by the MAPS instantiations only (stack_exact_kernel; stack_fast_maps_impl.hpp;
-    // stack_linfit_impl.hpp); nullptr everywhere else.
+    // stack_linfit_impl.hpp; the MAD kernels of stack_fast.hip / stack_fast_ml.hip); nullptr everywhere else.
     unsigned *reject_map;
 };
 
@@ -149,8 +149,10 @@ hipError_t launch_stack_median_fast(const StackArgs &args, const FastArgs &fargs
 // dominant_done (optional) is recorded right after the first, dominant kernel
 int mad_fast_supported(int mode, bool weighted, int n_frames, int64_t npix);
 // follow: the FOLLOW instantiations of the same kernels (the weighted MAD-sigma pass, include/nlstack_wmad.h; args.weights set)
+// maps: their MAPS instantiations (the full maps pass, include/nlstack_fullmaps.h; args.reject_map set, never with follow):
+// one more store per pixel, its two clip counts
 hipError_t launch_stack_mad_fast(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name,
-                                 bool follow = false);
+                                 bool follow = false, bool maps = false);
 // 249..256 / 505..512 frames: zonal sigma / winsorized sigma pass with the clipping rounds on LDS
 // columns (stack_fast_mlz.hip); hand-over lists as the other fast kernels
 // generic pass of the multi-lane sigma / winsor kernels over fargs.in_list, whole columns in LDS (stack_fast_mlg.hip)
@@ -196,8 +198,9 @@ constexpr int kMlNS = 128;     // samples per lane of the multi-lane kernels
 int fast_ml_supported(int mode, bool weighted, int n_frames, int64_t npix);
 hipError_t launch_stack_median_ml(const StackArgs &args, hipStream_t stream, const char **name);
 // record: the RECORD instantiations (the weighted MAD-sigma pass): only args.bounds / args.nrounds are written, one round
+// maps: the MAPS instantiations (the full maps pass; args.reject_map set, never with record)
 hipError_t launch_stack_mad_ml(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name,
-                               bool record = false);
+                               bool record = false, bool maps = false);
 unsigned ml_generic_grid(int n_frames, unsigned gen_hint);      // workgroups of launch_stack_sigma_mlg behind launch_stack_sigma_mlz
 
 // ---- stack_exact_coop.hip (bit-exact sigma replay, one wave per pixel) ----

@@ -208,6 +208,14 @@ class StackHandle:
         of run_maps_resident everywhere else.  Arguments and return value are those of run_maps."""
         return self._run_maps(self._lib.nl_stack_run_maps_deep, mode, sigma_low, sigma_high, ref_loc, out, reject_low, reject_high)
 
+    def run_maps_full(self, mode, sigma_low=2.75, sigma_high=2.75, ref_loc=0.0, out=None, reject_low=None,
+                      reject_high=None):
+        """run_maps_deep with MAD sigma and the median on their own engines as well (nl_stack_run_maps_full,
+        include/nlstack_fullmaps.h): unweighted MAD sigma of 1 ... 512 frames on the MAD kernels of the default pass --
+        the result is then the default pass's, bit for bit -- the median on its default kernels with zero maps, and
+        the pass of run_maps_deep everywhere else.  Arguments and return value are those of run_maps."""
+        return self._run_maps(self._lib.nl_stack_run_maps_full, mode, sigma_low, sigma_high, ref_loc, out, reject_low, reject_high)
+
     def run_linfit_weighted(self, sigma_low=2.75, sigma_high=2.75, ref_loc=0.0, out=None, fetch=True):
         """One pass of the weighted linear fit (include/nlstack_wlinfit.h; an EXTENSION, the reference's fit takes
         no weights): the reference's linear-fit rejection, then the mean of the survivors with the weights of
@@ -752,6 +760,10 @@ class StackGroup:
     def run_maps_deep(self, mode, sigma_low=2.75, sigma_high=2.75, ref_loc=0.0):
         """StackHandle.run_maps_deep over the tiles (nl_group_run_maps_deep): the return value of run_maps."""
         return self._run_maps(self._lib.nl_group_run_maps_deep, mode, sigma_low, sigma_high, ref_loc)
+
+    def run_maps_full(self, mode, sigma_low=2.75, sigma_high=2.75, ref_loc=0.0):
+        """StackHandle.run_maps_full over the tiles (nl_group_run_maps_full): the return value of run_maps."""
+        return self._run_maps(self._lib.nl_group_run_maps_full, mode, sigma_low, sigma_high, ref_loc)
 
     def run_linfit_weighted(self, sigma_low=2.75, sigma_high=2.75, ref_loc=0.0, download=True):
         """StackHandle.run_linfit_weighted over the tiles: (result or None, clip_low, clip_high)."""

@@ -45,6 +45,17 @@
         the column maps pass      nl_stack_run_maps, every host pointer NULL; in the first --column-reps repetitions only
       with the two hand-over list lengths of the deep maps pass.  A workload whose handle cannot be made (memory) is
       reported and skipped.  DIR receives the lines as deepmaps_probe.txt, workload by workload as they finish.
+
+  python tools/maps_probe.py --mad [--mad-frames 32,128,256,512 --width 4096 --height 4096 --sigma 3 --mad-reps 10
+                                    --median-frames 128 --out DIR]
+      The full maps pass (include/nlstack_fullmaps.h) beside the passes it sits next to.  Per depth ONE handle, and on it
+      3 warm-up runs and the median of --mad-reps, whole pass and dominant kernel, of MAD sigma through (the first two
+      interleaved, the third in a block of its own behind them):
+        the default pass          nl_stack_run (plain protocol already: its own yardstick)
+        the full maps pass        nl_stack_run_maps_full, every host pointer NULL
+        the column maps pass      nl_stack_run_maps, every host pointer NULL
+      and, at --median-frames, the same three for the median.  DIR (default: profiles/) receives the lines as
+      maps_probe_mad.txt, depth by depth as they finish.
 """
 import argparse
 import os
@@ -261,6 +272,54 @@ def deep(a):
                     default.med - default.med_dom))
 
 
+def mad(a):
+    import nightlight_amd as nl
+    from nightlight_amd import capi
+    L = capi.load()
+    warm, reps = 3, a.mad_reps
+    emit = Report(a.out or os.path.join(ROOT, "profiles"), "maps_probe_mad.txt")
+    emit("MAD sigma %.2f / %.2f and the median, frames of %d x %d resident; per depth one handle, %d repetitions "
+         "after %d warm-up runs, default and full maps pass interleaved; GPU time of the whole pass" % (a.sigma, a.sigma, a.width, a.height, reps, warm))
+    for n in [int(x) for x in a.mad_frames.split(",")]:
+        emit("-- %d frames" % n)
+        try:
+            st = nl.StackHandle(n, a.width, a.height)
+        except capi.NlError as e:
+            emit("no handle of %d frames: %s" % (n, e))
+            continue
+        with st:
+            st.fill_synthetic(seed=7)
+            default_pass, maps_pass = pass_fns(st, L, capi.ST_MAD_SIGMA, a.sigma)
+            # (the default MAD pass runs the plain protocol already: it is its own yardstick)
+            # (the pair that is compared runs interleaved; the column kernel, which holds the device for a hundred times
+            # as long, in a block of its own behind them: in between it shifts the passes next to it by 10 ... 20 %, either way)
+            t = measure(st, (("default pass", default_pass), ("full maps pass", maps_pass("nl_stack_run_maps_full"))),
+                        warm, reps, interleaved=True)
+            t.update(measure(st, (("column maps pass", maps_pass("nl_stack_run_maps")),), warm, reps))
+            for label, r in t.items():
+                tail = "; protocol %d" % r.protocol
+                if label != "column maps pass":
+                    tail += "; exact list %d, generic list %d" % (r.exact_list, r.generic_list)
+                emit("%-17s %-36s %s (%d runs)%s; dominant kernel median %.3f ms, min %.3f ms"
+                     % (label, r.kernel, stats(r.ms), len(r.ms), tail, r.med_dom, r.min_dom))
+            fm, default = t["full maps pass"], t["default pass"]
+            emit("full maps / default = %.4f (one more 4-byte store per %d bytes read: %.4f); column maps / full maps = %.1f"
+                 % (fm.med / default.med, 4 * n, 1.0 + 1.0 / n, t["column maps pass"].med / fm.med))
+            emit("dominant kernels, full maps / default = %.4f; behind the dominant kernel: %.3f ms (full maps), %.3f ms (default)"
+                 % (fm.med_dom / default.med_dom, fm.med - fm.med_dom, default.med - default.med_dom))
+            if n == a.median_frames:
+                default_pass, maps_pass = pass_fns(st, L, capi.ST_MEDIAN, a.sigma)
+                t = measure(st, (("default pass", default_pass), ("full maps pass", maps_pass("nl_stack_run_maps_full"))),
+                            warm, reps, interleaved=True)
+                t.update(measure(st, (("column maps pass", maps_pass("nl_stack_run_maps")),), warm, reps))
+                emit("-- %d frames, the median" % n)
+                for label, r in t.items():
+                    emit("%-17s %-36s %s (%d runs); protocol %d" % (label, r.kernel, stats(r.ms), len(r.ms), r.protocol))
+                emit("full maps / default = %.4f (one memset of %d bytes beside %d bytes read); column maps / full maps = %.1f"
+                     % (t["full maps pass"].med / t["default pass"].med, 4 * a.width * a.height, 4 * n * a.width * a.height,
+                        t["column maps pass"].med / t["full maps pass"].med))
+
+
 def column(a):
     import nightlight_amd as nl
     from nightlight_amd import capi
@@ -301,6 +360,10 @@ def main():
     ap.add_argument("--deep", action="store_true")
     ap.add_argument("--deep-workloads", default="512x4096x4096:2,256x4096x4096:2,512x4096x512:3")
     ap.add_argument("--column-reps", type=int, default=3)
+    ap.add_argument("--mad", action="store_true")
+    ap.add_argument("--mad-frames", default="32,128,256,512")
+    ap.add_argument("--mad-reps", type=int, default=10)
+    ap.add_argument("--median-frames", type=int, default=128)
     ap.add_argument("--frames", type=int, default=128)
     ap.add_argument("--width", type=int, default=4096)
     ap.add_argument("--height", type=int, default=4096)
@@ -309,7 +372,7 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    return (fastmaps if a.fastmaps else linfit if a.linfit else deep if a.deep else column)(a)
+    return (fastmaps if a.fastmaps else linfit if a.linfit else deep if a.deep else mad if a.mad else column)(a)
 
 
 if __name__ == "__main__":
