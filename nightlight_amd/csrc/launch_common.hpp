@@ -104,6 +104,20 @@ const char *kernel_name()
     return name.c_str();
 }
 
+// "BASE<a, b, ..., maps>" ("BASE<maps>" without arguments): the display name of a Form::Maps instantiation -- the default
+// pass's name of the same kernel with "maps" as its last argument
+template <const char *BASE, auto... ARGS>
+const char *maps_kernel_name()
+{
+    static const std::string name = [] {
+        std::string s = BASE;
+        s += "<";
+        ((s += name_arg(ARGS), s += ", "), ...);
+        return s + "maps>";
+    }();
+    return name.c_str();
+}
+
 // a FastArgs pass over the whole tile / over the generic list (the pixels the dominant kernel handed over)
 inline FastArgs whole_tile(FastArgs f)
 {

@@ -62,7 +62,7 @@ enum class MapsTier {
     Deep,                 // nl_stack_run_maps_deep (include/nlstack_deepmaps.h): and the LDS-column sigma / winsorized kernels, 129 ... 512 frames
     Full,                 // nl_stack_run_maps_full (include/nlstack_fullmaps.h): and the MAD-sigma kernels, 1 ... 512 frames; the median on its default kernels
 };
-// the passes that run on an engine of their own instead of select_engine's (nlstack_pass.hip)
+// the kinds of pass: select_engine (nlstack_pass.hip) gives every kind but Default an engine of its own
 enum class PassKind {
     Default,              // nl_stack_run_async and, with a tier, the nl_stack_run_maps* entries
     WeightedLinfit,       // nl_stack_run_linfit_weighted (include/nlstack_wlinfit.h): run_linfit_weighted; mode is NL_ST_LINEAR_FIT

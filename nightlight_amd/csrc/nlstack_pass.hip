@@ -1,5 +1,6 @@
 // nlstack_pass.hip -- one stack pass of the C ABI, and what runs passes: goal-seek, the stack of stacks.
 // run_async_impl sets a pass up, select_engine picks the engine that runs it; all pixel arithmetic runs in the kernels.
+#include <cassert>
 #include <mutex>
 
 #include "goal_seek.hpp"
@@ -186,8 +187,8 @@ static bool fused_protocol_on()
 // What no engine of its tier takes runs on the column kernel.  On every tier the pass takes part in none of what default
 // passes remember from one another: it takes and leaves no list-length hints, never runs the fused protocol, and leaves the
 // scratch sets as any other plain-protocol pass does; the linear fit drops the handle's weights as in every other
-// unweighted entry (stack.go:158).  One more engine with per-pixel counts is one predicate in select_engine and one
-// `maps` at its launch sites.
+// unweighted entry (stack.go:158).  One more engine with per-pixel counts is one rung of maps_engine and nl::Form::Maps
+// (stack_kernels.h) at its launch sites: the pass carries its form in PassSetup::form, and every launcher takes one.
 
 // the engines, in the order select_engine tries them
 enum class Engine {
@@ -200,6 +201,10 @@ enum class Engine {
     WeightedTile,         // bit-exact replay, 64 consecutive pixels per wave with their columns in LDS
     DenseReplay,          // bit-exact wave-per-pixel replay over the whole tile (behind a decision pass where there is one)
     ExactColumns,         // bit-exact, one pixel per lane with its column in LDS: every mode, any depth
+    // the extension passes (nl::PassKind), each on an engine of its own:
+    LinfitWeighted,       // PassKind::WeightedLinfit
+    ClipWeighted,         // PassKind::WeightedClip
+    MadWeighted,          // PassKind::WeightedMad
 };
 
 // what the prologue of the pass decided, for the engine
@@ -209,35 +214,54 @@ struct PassSetup {
     bool timed;               // the pass records its timing events (not with kDevUntimed)
     bool fused;               // fused protocol (fused_protocol_on; only the SigmaFast engine runs it)
     nl::StackArgs a;
-    nl::MapsTier tier = nl::MapsTier::None;
-    bool maps() const { return tier != nl::MapsTier::None; }      // a maps pass: a.reject_map is set
+    nl::Form form;            // of the pass's kernels: Maps behind a tier (a.reject_map is set), Follow for the weighted clip and
+                              // MAD-sigma passes (a.weights is set), else Plain
+    bool maps() const { return form == nl::Form::Maps; }
 };
 
-// Pure: allocates nothing, enqueues nothing.  The first engine whose condition holds runs the pass.  tier: the ladder above.
-static Engine select_engine(const nl_stack *h, int mode, bool weighted, const nl::StackArgs &a, nl::MapsTier tier)
+// The ladder of a maps pass (a.reject_map set, never the mean): the first rung whose condition holds; what no engine of the
+// tier takes runs on the one engine that carries the per-pixel counts out of every mode.  Default passes never come here.
+static Engine maps_engine(const nl_stack *h, int mode, bool weighted, const nl::StackArgs &a, nl::MapsTier tier)
 {
     const bool fast = !h->force_exact;
     const bool clip = mode == NL_ST_SIGMA || mode == NL_ST_WINSOR_SIGMA;
+    const bool listed = fast && h->d_fb_list, both_lists = listed && h->d_gen_list;
     const int n = a.n_frames;
-    if (mode == NL_ST_MEAN) return Engine::Mean;
-    if (a.reject_map && tier >= nl::MapsTier::Fast && fast && h->d_fb_list && h->d_gen_list && clip &&
-        nl::fast_supported(mode, weighted, n, a.npix))
-        return Engine::SigmaMaps;
-    if (a.reject_map && tier >= nl::MapsTier::Resident && fast && h->d_fb_list && mode == NL_ST_LINEAR_FIT &&
+    if (tier >= nl::MapsTier::Fast && both_lists && clip && nl::fast_supported(mode, weighted, n, a.npix)) return Engine::SigmaMaps;
+    if (tier >= nl::MapsTier::Resident && listed && mode == NL_ST_LINEAR_FIT &&
         (nl::linfit_fast_supported(mode, n, a.npix) || nl::linfit_ml_supported(mode, n, a.npix)))
         return Engine::Listed;
-    if (a.reject_map && tier >= nl::MapsTier::Deep && fast && h->d_fb_list && h->d_gen_list && clip && !weighted &&
-        nl::fast_ml_supported(mode, false, n, a.npix))
+    if (tier >= nl::MapsTier::Deep && both_lists && clip && !weighted && nl::fast_ml_supported(mode, false, n, a.npix))
         return Engine::SigmaMaps;
-    if (a.reject_map && tier >= nl::MapsTier::Full && fast && h->d_fb_list && h->d_gen_list && mode == NL_ST_MAD_SIGMA && !weighted &&
+    if (tier >= nl::MapsTier::Full && both_lists && mode == NL_ST_MAD_SIGMA && !weighted &&
         (nl::mad_fast_supported(mode, false, n, a.npix) || nl::fast_ml_supported(mode, false, n, a.npix)))
         return Engine::Listed;
     // (the median rejects nothing: its default kernels, the maps zeroed)
-    if (a.reject_map && tier >= nl::MapsTier::Full && fast && mode == NL_ST_MEDIAN && nl::fast_supported(mode, weighted, n, a.npix))
+    if (tier >= nl::MapsTier::Full && fast && mode == NL_ST_MEDIAN && nl::fast_supported(mode, weighted, n, a.npix))
         return Engine::MedianRegisters;
-    if (a.reject_map && tier >= nl::MapsTier::Full && fast && mode == NL_ST_MEDIAN && nl::fast_ml_supported(mode, weighted, n, a.npix))
+    if (tier >= nl::MapsTier::Full && fast && mode == NL_ST_MEDIAN && nl::fast_ml_supported(mode, weighted, n, a.npix))
         return Engine::MedianMultiLane;
-    if (a.reject_map) return Engine::ExactColumns;      // a maps pass: the one engine that carries the per-pixel counts out of every mode
+    return Engine::ExactColumns;
+}
+
+// Pure: allocates nothing, enqueues nothing.  An extension pass has its engine; a maps pass climbs maps_engine's ladder
+// (tier); for every other pass the first engine whose condition holds runs it.
+static Engine select_engine(const nl_stack *h, nl::PassKind kind, int mode, bool weighted, const nl::StackArgs &a, nl::MapsTier tier)
+{
+    const bool fast = !h->force_exact;
+    const int n = a.n_frames;
+    if (kind != PassKind::Default) {
+        // Until these kinds had engines of their own here, the pass asked the ladder below, dispatched past its answer and
+        // kept one thing of it: whether it was SigmaFast, which turns on hint loading, the fused protocol and its single
+        // start event.  It never was.  All three kinds run with the handle's weights (the entries refuse a handle without
+        // them), and with weights fast_supported and fast_ml_supported are 0 for sigma and winsorized sigma; for the
+        // linear fit and MAD sigma, which are no clip modes, they are 0 anyway: the SigmaFast rung cannot hold.
+        assert(weighted && !nl::fast_supported(mode, weighted, n, a.npix) && !nl::fast_ml_supported(mode, weighted, n, a.npix));
+        return kind == PassKind::WeightedLinfit ? Engine::LinfitWeighted
+               : kind == PassKind::WeightedClip ? Engine::ClipWeighted : Engine::MadWeighted;
+    }
+    if (mode == NL_ST_MEAN) return Engine::Mean;
+    if (a.reject_map) return maps_engine(h, mode, weighted, a, tier);
     if (fast && mode == NL_ST_MEDIAN && nl::fast_supported(mode, weighted, n, a.npix)) return Engine::MedianRegisters;
     if (fast && mode == NL_ST_MEDIAN && nl::fast_ml_supported(mode, weighted, n, a.npix)) return Engine::MedianMultiLane;
     if (fast && h->d_fb_list &&
@@ -275,28 +299,19 @@ static nl::FastArgs list_args(const nl_stack *h, bool exact_list, bool generic_l
     return f;
 }
 
-// The column kernel (stack_exact.hip): its plain instantiations, the MAPS ones, which also store each pixel's word of
-// a.reject_map, or the <follow> ones of the weighted clip pass (one column: planned with weighted = false)
-enum class Columns { Plain, Maps, Follow };
-
-static hipError_t launch_columns(Columns variant, int mode, bool weighted, const nl::StackArgs &a, int lanes, int grid, size_t lds,
-                                 hipStream_t stream, const char **name)
-{
-    if (variant == Columns::Follow) return nl::launch_stack_exact_follow(mode, a, lanes, grid, lds, stream, name);
-    return nl::launch_stack_exact(mode, weighted, a, lanes, grid, lds, stream, name, variant == Columns::Maps);
-}
-
 // how a pass of the plain protocol ends: the sharded clip counts (d_partial) -> the pass's totals (d_counters)
 static hipError_t reduce_clip_slots(nl_stack *h)
 {
     return nl::launch_reduce_counters(h->d_partial, nl::kClipSlots, h->d_counters, h->stream);
 }
 
-// ... over the exact list (d_fb_list), kListLanes pixels per wave
-static int replay_list(nl_stack *h, int mode, bool weighted, const nl::StackArgs &a, Columns variant = Columns::Plain)
+// The column kernel (stack_exact.hip) in the form of the pass -- Form::Follow: one column, planned with weighted = false --
+// over the exact list (d_fb_list), kListLanes pixels per wave
+static int replay_list(nl_stack *h, int mode, bool weighted, const nl::StackArgs &a, nl::Form form = nl::Form::Plain)
 {
     int lanes = 0;
     size_t lds = 0;
+    weighted = weighted && form != nl::Form::Follow;
     if (nl::exact_plan(mode, weighted, a.n_frames, a.n_pad, kListLanes, &lanes, &lds) != 0)
         return fail(NL_ERR_TOO_MANY_FRAMES, "%d frames do not fit the per-pixel LDS column (mode %d)", a.n_frames, mode);
     nl::StackArgs e = a;
@@ -304,24 +319,45 @@ static int replay_list(nl_stack *h, int mode, bool weighted, const nl::StackArgs
     e.list_count = h->d_fb_count;
     e.list_capacity = (unsigned)h->npix;
     const char *exact_name = "";
-    NL_HIP(launch_columns(variant, mode, weighted, e, lanes, kListGrid, lds, h->stream, &exact_name));
+    NL_HIP(nl::launch_stack_exact(mode, weighted, e, lanes, kListGrid, lds, h->stream, &exact_name, form));
     return NL_OK;
 }
 
 // ... over the whole tile, as the dominant kernel of the pass: ev_dom1 is recorded behind it
-static int columns_over_tile(nl_stack *h, int mode, bool weighted, nl::StackArgs a, Columns variant = Columns::Plain)
+static int columns_over_tile(nl_stack *h, int mode, bool weighted, nl::StackArgs a, nl::Form form = nl::Form::Plain)
 {
     int lanes = 0;
     size_t lds = 0;
+    weighted = weighted && form != nl::Form::Follow;
     if (nl::exact_plan(mode, weighted, a.n_frames, a.n_pad, 64, &lanes, &lds) != 0)
         return weighted && mode == NL_ST_LINEAR_FIT
                    ? fail(NL_ERR_TOO_MANY_FRAMES, "%d frames do not fit the per-pixel LDS columns of the weighted linear fit", a.n_frames)
                    : fail(NL_ERR_TOO_MANY_FRAMES, "%d frames do not fit the per-pixel LDS column (mode %d)", a.n_frames, mode);
     a.tiles = (a.npix + lanes - 1) / lanes;
     const int grid = (int)(a.tiles < (int64_t)h->max_grid ? a.tiles : (int64_t)h->max_grid);
-    NL_HIP(launch_columns(variant, mode, weighted, a, lanes, grid, lds, h->stream, &h->last_kernel));
+    NL_HIP(nl::launch_stack_exact(mode, weighted, a, lanes, grid, lds, h->stream, &h->last_kernel, form));
     NL_HIP(hipEventRecord(h->ev_dom1, h->stream));
     return NL_OK;
+}
+
+// How the engines of the plain protocol end: the column kernel in the pass's form over the exact list (`listed`: a dominant
+// kernel filled it) or over the whole tile, then the reduction of the sharded clip counts
+static int end_on_columns(nl_stack *h, const PassSetup &p, const nl::StackArgs &a, bool listed, PassFacts *facts)
+{
+    const int rc = listed ? replay_list(h, p.mode, p.weighted, a, p.form) : columns_over_tile(h, p.mode, p.weighted, a, p.form);
+    if (rc != NL_OK) return rc;
+    NL_HIP(reduce_clip_slots(h));
+    facts->has_counters = true;
+    return NL_OK;
+}
+
+// a.bounds / a.nrounds point at the handle's threshold record; false: there is none (ensure_bounds), `a` stays as it is
+static bool bounds_on_record(nl_stack *h, nl::StackArgs &a)
+{
+    if (!ensure_bounds(h)) return false;
+    a.bounds = h->d_bounds;
+    a.nrounds = h->d_nrounds;
+    return true;
 }
 
 // Grids of the wave-per-pixel list replays: one wave per workgroup, grid-stride over a list whose length is only known on
@@ -341,24 +377,16 @@ static void replay_grids(const nl_stack *h, int *grid0, int *grid1)
 
 // The decision pass of a weighted sigma / winsorized stack in front of the whole-tile replay: it leaves the clip bounds of
 // every round it can decide in a.bounds / a.nrounds.  33 ... 128 frames: the register-resident kernel; 129 ... 512: the
-// LDS-column kernel of the frame-count class (FastArgs::record_only: no outputs, lists or counters; a pixel it would hand
+// LDS-column kernel of the frame-count class (Form::Record: no outputs, lists or counters; a pixel it would hand
 // to the generic pass has no round on record).
 static int decision_pass(nl_stack *h, const PassSetup &p, nl::StackArgs &a)
 {
     if (!p.weighted || h->exact_flavour != 0 || p.mode == NL_ST_MEDIAN) return NL_OK;
     const char *ignored = "";
-    if (nl::decide_supported(p.mode, a.n_frames, a.npix) && ensure_bounds(h)) {
-        a.bounds = h->d_bounds;
-        a.nrounds = h->d_nrounds;
+    if (nl::decide_supported(p.mode, a.n_frames, a.npix) && bounds_on_record(h, a))
         NL_HIP(nl::launch_stack_sigma_decide(a, h->stream, p.mode == NL_ST_WINSOR_SIGMA, &ignored));
-    } else if (nl::decide_ml_supported(p.mode, a.n_frames, a.npix) && ensure_bounds(h)) {
-        a.bounds = h->d_bounds;
-        a.nrounds = h->d_nrounds;
-        nl::FastArgs f;
-        memset(&f, 0, sizeof f);
-        f.record_only = 1;
-        NL_HIP(nl::launch_stack_sigma_mlz(a, f, h->stream, &ignored, p.mode == NL_ST_WINSOR_SIGMA));
-    }
+    else if (nl::decide_ml_supported(p.mode, a.n_frames, a.npix) && bounds_on_record(h, a))
+        NL_HIP(nl::launch_stack_sigma_mlz(a, nl::FastArgs{}, h->stream, &ignored, p.mode == NL_ST_WINSOR_SIGMA, nl::Form::Record));
     return NL_OK;
 }
 
@@ -410,8 +438,8 @@ static int run_listed(nl_stack *h, const PassSetup &p, PassFacts *facts)
         // counters exact (the bounds come from two medians); pixels with a non-finite median are replayed; 128 frames:
         // pixels with too few samples for the selection kernel go to the generic list
         const nl::FastArgs f = list_args(h, true, true);
-        if (a.n_frames <= 128) NL_HIP(nl::launch_stack_mad_fast(a, f, h->stream, &h->last_kernel, false, p.maps()));
-        else                   NL_HIP(nl::launch_stack_mad_ml(a, f, h->stream, &h->last_kernel, false, p.maps()));
+        if (a.n_frames <= 128) NL_HIP(nl::launch_stack_mad_fast(a, f, h->stream, &h->last_kernel, p.form));
+        else                   NL_HIP(nl::launch_stack_mad_ml(a, f, h->stream, &h->last_kernel, p.form));
         NL_HIP(hipEventRecord(h->ev_dom1, h->stream));
     } else {
         // bit-exact (sums run in sorted order; 129 ... 512 frames: 2 or 4 lanes per pixel, the sums chained through the
@@ -421,16 +449,12 @@ static int run_listed(nl_stack *h, const PassSetup &p, PassFacts *facts)
         const nl::LinfitCascade *cas = linfit_cascade(h, &cascade);
         if (cas) NL_HIP(hipMemsetAsync(h->d_lf_count, 0, sizeof(unsigned) * nl::kLinfitCounters, h->stream));
         if (nl::linfit_ml_supported(p.mode, a.n_frames, a.npix))
-            NL_HIP(nl::launch_stack_linfit_ml(a, f, cas, h->stream, &h->last_kernel, h->ev_dom1, p.maps()));
+            NL_HIP(nl::launch_stack_linfit_ml(a, f, cas, h->stream, &h->last_kernel, h->ev_dom1, p.form));
         else
-            NL_HIP(nl::launch_stack_linfit_fast(a, f, cas, h->stream, &h->last_kernel, h->ev_dom1, p.maps()));
+            NL_HIP(nl::launch_stack_linfit_fast(a, f, cas, h->stream, &h->last_kernel, h->ev_dom1, p.form));
     }
-    const int rc = replay_list(h, p.mode, p.weighted, a, p.maps() ? Columns::Maps : Columns::Plain);
-    if (rc != NL_OK) return rc;
-    NL_HIP(reduce_clip_slots(h));
-    facts->has_counters = true;
     facts->used_fast = true;
-    return NL_OK;
+    return end_on_columns(h, p, a, true, facts);
 }
 
 // A winsorization cascade plan (kWinsorPlan*, NL_WCAS), the dominant kernel first, the last stage runs to the end:
@@ -532,10 +556,7 @@ static int run_sigma_fast(nl_stack *h, const PassSetup &p, PassFacts *facts)
     // replay of a pixel that turns undecidable later skips the winsorization loops of the decided rounds
     // (from 129 frames on: C3 tile 5.28 -> 5.14 ms; at 128 frames most undecidable pixels are undecidable in
     // their first round and the stores cost the dominant kernel 0.6 %)
-    if (winsor && a.n_frames > 128 && fused_protocol_on() && ensure_bounds(h)) {
-        a.bounds = h->d_bounds;
-        a.nrounds = h->d_nrounds;
-    }
+    if (winsor && a.n_frames > 128 && fused_protocol_on()) (void)bounds_on_record(h, a);
     // the wave-per-pixel replays of the exact list: the first of them to start stores 1 + the list's length in `snap`
     // (StackArgs::list_snap); part 0 is the list as the dominant part left it, part 1 the generic pass's additions
     unsigned *const snap = h->d_fb_count + 2;
@@ -567,14 +588,14 @@ static int run_sigma_fast(nl_stack *h, const PassSetup &p, PassFacts *facts)
     replay_blocks = replay_blocks < 64u ? 64u : replay_blocks > 768u ? 768u : replay_blocks;
     const hipEvent_t dominant_done = p.timed ? h->ev_dom1 : nullptr;
     const bool one_lane = a.n_frames <= 128;          // 129 ... 512 frames: 2 or 4 lanes per pixel, the LDS-column kernels
-    if (one_lane) NL_HIP(nl::launch_stack_sigma_fast_dominant(a, f, h->stream, &h->last_kernel, dominant_done, winsor));
+    if (one_lane) NL_HIP(nl::launch_stack_sigma_dominant(a, f, h->stream, &h->last_kernel, dominant_done, winsor));
     else          NL_HIP(nl::launch_stack_sigma_mlz(a, nl::whole_tile(f), h->stream, &h->last_kernel, winsor));
     if (!one_lane && dominant_done) NL_HIP(hipEventRecord(dominant_done, h->stream));
     if (coop && !tail_fused) {
         const int rc = fork_first_replay(h, mode, first, grid0, cascade);
         if (rc != NL_OK) return rc;
     }
-    if (one_lane) NL_HIP(nl::launch_stack_sigma_fast_generic(a, f, h->stream, winsor, tail_fused ? &first : nullptr, replay_blocks));
+    if (one_lane) NL_HIP(nl::launch_stack_sigma_generic(a, f, h->stream, winsor, nl::Form::Plain, tail_fused ? &first : nullptr, replay_blocks));
     else          NL_HIP(nl::launch_stack_sigma_mlg(a, nl::over_generic_list(nl::whole_tile(f)), nl::ml_generic_grid(a.n_frames, f.gen_hint), h->stream, winsor));
     if (coop) {
         const char *exact_name = "";
@@ -616,17 +637,13 @@ static int run_sigma_maps(nl_stack *h, const PassSetup &p, PassFacts *facts)
     if (winsor) (void)winsor_setup(h, a.n_frames, f, false);      // (the round cap of the generic pass, as run_sigma_fast sets it)
     const hipEvent_t dominant_done = p.timed ? h->ev_dom1 : nullptr;
     const bool one_lane = a.n_frames <= 128;          // 129 ... 512 frames: 2 or 4 lanes per pixel, the LDS-column kernels
-    if (one_lane) NL_HIP(nl::launch_stack_sigma_maps_dominant(a, f, h->stream, &h->last_kernel, dominant_done, winsor));
-    else          NL_HIP(nl::launch_stack_sigma_mlz(a, nl::whole_tile(f), h->stream, &h->last_kernel, winsor, true));
+    if (one_lane) NL_HIP(nl::launch_stack_sigma_dominant(a, f, h->stream, &h->last_kernel, dominant_done, winsor, p.form));
+    else          NL_HIP(nl::launch_stack_sigma_mlz(a, nl::whole_tile(f), h->stream, &h->last_kernel, winsor, p.form));
     if (!one_lane && dominant_done) NL_HIP(hipEventRecord(dominant_done, h->stream));
-    if (one_lane) NL_HIP(nl::launch_stack_sigma_maps_generic(a, f, h->stream, winsor));
-    else          NL_HIP(nl::launch_stack_sigma_mlg(a, nl::over_generic_list(nl::whole_tile(f)), nl::ml_generic_grid(a.n_frames, 0), h->stream, winsor, true));
-    const int rc = replay_list(h, p.mode, false, a, Columns::Maps);
-    if (rc != NL_OK) return rc;
-    NL_HIP(reduce_clip_slots(h));
-    facts->has_counters = true;
+    if (one_lane) NL_HIP(nl::launch_stack_sigma_generic(a, f, h->stream, winsor, p.form));
+    else          NL_HIP(nl::launch_stack_sigma_mlg(a, nl::over_generic_list(nl::whole_tile(f)), nl::ml_generic_grid(a.n_frames, 0), h->stream, winsor, p.form));
     facts->used_fast = true;
-    return NL_OK;
+    return end_on_columns(h, p, a, true, facts);        // (p.weighted is false: both rungs of this engine are unweighted kernels)
 }
 
 // Bit-exact replay over the whole tile, 64 consecutive pixels per wave with their columns in LDS, one pixel per lane:
@@ -670,11 +687,9 @@ static int run_dense_replay(nl_stack *h, const PassSetup &p, PassFacts *facts)
 // one pixel per lane with its column in LDS: every mode at any depth (nl_stack_set_exact(h, 1), and what no other engine takes)
 static int run_exact_columns(nl_stack *h, const PassSetup &p, PassFacts *facts)
 {
-    const int rc = columns_over_tile(h, p.mode, p.weighted, p.a, p.maps() ? Columns::Maps : Columns::Plain);
-    if (rc != NL_OK) return rc;
-    NL_HIP(reduce_clip_slots(h));
-    facts->has_counters = p.mode != NL_ST_MEDIAN;
-    return NL_OK;
+    const int rc = end_on_columns(h, p, p.a, false, facts);
+    facts->has_counters = p.mode != NL_ST_MEDIAN;           // (the median clips nothing)
+    return rc;
 }
 
 // The weighted linear-fit pass (include/nlstack_wlinfit.h, an extension): up to 128 frames the register-resident kernel
@@ -684,19 +699,13 @@ static int run_exact_columns(nl_stack *h, const PassSetup &p, PassFacts *facts)
 static int run_linfit_weighted(nl_stack *h, const PassSetup &p, PassFacts *facts)
 {
     const nl::StackArgs &a = p.a;
-    if (!h->force_exact && h->d_fb_list && nl::linfit_weighted_supported(a.n_frames, a.npix)) {
+    const bool listed = !h->force_exact && h->d_fb_list && nl::linfit_weighted_supported(a.n_frames, a.npix);
+    if (listed) {
         NL_HIP(nl::launch_stack_linfit_weighted(a, list_args(h, true, false), h->stream, &h->last_kernel));
         NL_HIP(hipEventRecord(h->ev_dom1, h->stream));
-        const int rc = replay_list(h, p.mode, true, a);
-        if (rc != NL_OK) return rc;
         facts->used_fast = true;
-    } else {
-        const int rc = columns_over_tile(h, p.mode, true, a);
-        if (rc != NL_OK) return rc;
     }
-    NL_HIP(reduce_clip_slots(h));
-    facts->has_counters = true;
-    return NL_OK;
+    return end_on_columns(h, p, a, listed, facts);          // (p.weighted: this pass keeps the weights)
 }
 
 // The weighted clip pass whose weights follow their frames (include/nlstack_wclip.h, an extension): sigma / winsorized
@@ -723,10 +732,8 @@ static int run_clip_weighted(nl_stack *h, const PassSetup &p, PassFacts *facts)
     if (clip_weighted_decided(h, p.mode, a)) {
         const int rc = decision_pass(h, p, a);
         if (rc != NL_OK) return rc;
-        if (!a.bounds && nl::decide_shallow_supported(p.mode, a.n_frames, a.npix) && ensure_bounds(h)) {
+        if (!a.bounds && nl::decide_shallow_supported(p.mode, a.n_frames, a.npix) && bounds_on_record(h, a)) {
             const char *ignored = "";
-            a.bounds = h->d_bounds;
-            a.nrounds = h->d_nrounds;
             NL_HIP(nl::launch_stack_sigma_decide_shallow(a, h->stream, p.mode == NL_ST_WINSOR_SIGMA, &ignored));
         }
         streamed = a.bounds != nullptr;
@@ -736,14 +743,10 @@ static int run_clip_weighted(nl_stack *h, const PassSetup &p, PassFacts *facts)
         NL_HIP(hipEventRecord(h->ev_dom1, h->stream));
         facts->used_fast = true;
     }
-    // (the <follow> column kernel computes its own bounds: one column, planned with weighted = false)
+    // (the <follow> column kernel computes its own bounds)
     a.bounds = nullptr;
     a.nrounds = nullptr;
-    const int rc = streamed ? replay_list(h, p.mode, false, a, Columns::Follow) : columns_over_tile(h, p.mode, false, a, Columns::Follow);
-    if (rc != NL_OK) return rc;
-    NL_HIP(reduce_clip_slots(h));
-    facts->has_counters = true;
-    return NL_OK;
+    return end_on_columns(h, p, a, streamed, facts);
 }
 
 // The weighted MAD-sigma pass (include/nlstack_wmad.h, an extension): StackMADSigma's rejection on the values alone, then
@@ -763,15 +766,11 @@ static int run_mad_weighted(nl_stack *h, const PassSetup &p, PassFacts *facts)
     const bool lists = !h->force_exact && h->d_fb_list != nullptr;
     bool listed = false;
     if (lists && nl::mad_fast_supported(p.mode, false, a.n_frames, a.npix)) {
-        NL_HIP(nl::launch_stack_mad_fast(a, list_args(h, true, true), h->stream, &h->last_kernel, true));
+        NL_HIP(nl::launch_stack_mad_fast(a, list_args(h, true, true), h->stream, &h->last_kernel, p.form));
         listed = true;
-    } else if (lists && nl::fast_ml_supported(p.mode, false, a.n_frames, a.npix) && ensure_bounds(h)) {
+    } else if (lists && nl::fast_ml_supported(p.mode, false, a.n_frames, a.npix) && bounds_on_record(h, a)) {
         const char *ignored = "";
-        a.bounds = h->d_bounds;
-        a.nrounds = h->d_nrounds;
-        nl::FastArgs none;
-        memset(&none, 0, sizeof none);
-        NL_HIP(nl::launch_stack_mad_ml(a, none, h->stream, &ignored, true));
+        NL_HIP(nl::launch_stack_mad_ml(a, nl::FastArgs{}, h->stream, &ignored, nl::Form::Record));
         NL_HIP(nl::launch_stack_clip_weighted(a, list_args(h, true, false), h->stream, &h->last_kernel, true));
         a.bounds = nullptr;
         a.nrounds = nullptr;
@@ -781,11 +780,7 @@ static int run_mad_weighted(nl_stack *h, const PassSetup &p, PassFacts *facts)
         NL_HIP(hipEventRecord(h->ev_dom1, h->stream));
         facts->used_fast = true;
     }
-    const int rc = listed ? replay_list(h, p.mode, false, a, Columns::Follow) : columns_over_tile(h, p.mode, false, a, Columns::Follow);
-    if (rc != NL_OK) return rc;
-    NL_HIP(reduce_clip_slots(h));
-    facts->has_counters = true;
-    return NL_OK;
+    return end_on_columns(h, p, a, listed, facts);
 }
 
 // A pass that fails half-way (a launch or an event call after the first kernel) must not hand control back with work in
@@ -822,15 +817,15 @@ static int run_async_impl(nl_stack_t *h, const nl::PassRequest &req)
     int mode = req.mode;
     const bool maps = tier != nl::MapsTier::None, wlinfit = req.kind == PassKind::WeightedLinfit, wclip = req.kind == PassKind::WeightedClip;
     const bool wmad = req.kind == PassKind::WeightedMad;
-    if (wmad && !h->has_weights)
-        return fail(NL_ERR_INVALID_ARG, "run_mad_weighted: the handle has no weights (nl_stack_set_weights); "
-                                        "the unweighted pass is nl_stack_run with NL_ST_MAD_SIGMA");
-    if (wclip && !h->has_weights)
-        return fail(NL_ERR_INVALID_ARG, "run_clip_weighted: the handle has no weights (nl_stack_set_weights); "
-                                        "the unweighted pass is nl_stack_run");
-    if (wlinfit && !h->has_weights)
-        return fail(NL_ERR_INVALID_ARG, "run_linfit_weighted: the handle has no weights (nl_stack_set_weights); "
-                                        "the unweighted fit is nl_stack_run with NL_ST_LINEAR_FIT");
+    // the extension passes take their weights from the handle: the entry's name, and where the unweighted pass is
+    static const struct { PassKind kind; const char *entry, *unweighted; } kNeedWeights[] = {
+        {PassKind::WeightedMad, "run_mad_weighted", "the unweighted pass is nl_stack_run with NL_ST_MAD_SIGMA"},
+        {PassKind::WeightedClip, "run_clip_weighted", "the unweighted pass is nl_stack_run"},
+        {PassKind::WeightedLinfit, "run_linfit_weighted", "the unweighted fit is nl_stack_run with NL_ST_LINEAR_FIT"},
+    };
+    for (const auto &e : kNeedWeights)
+        if (req.kind == e.kind && !h->has_weights)
+            return fail(NL_ERR_INVALID_ARG, "%s: the handle has no weights (nl_stack_set_weights); %s", e.entry, e.unweighted);
     if (mode < NL_ST_MEDIAN || mode > NL_ST_AUTO) return fail(NL_ERR_INVALID_MODE, "invalid stacking mode");
     if (mode == NL_ST_AUTO) mode = nl::auto_select_mode(h->n_frames);
     if (wclip && mode != NL_ST_SIGMA && mode != NL_ST_WINSOR_SIGMA)
@@ -881,7 +876,7 @@ static int run_async_impl(nl_stack_t *h, const nl::PassRequest &req)
     h->ring_timed[h->pass_seq % kTimingRing] = timed;
     if (timed) NL_HIP(hipEventRecord(h->ev_start, h->stream));
     const bool fused_on = fused_protocol_on();
-    const Engine engine = select_engine(h, mode, weighted, a, tier);
+    const Engine engine = select_engine(h, req.kind, mode, weighted, a, tier);
     const bool sigma_fast = engine == Engine::SigmaFast;
     // (only while the exact list is short -- the length the last finished pass reported: its replays add their
     // counts to ONE word, and thousands of workgroups doing that take longer than a reduction kernel)
@@ -914,13 +909,11 @@ static int run_async_impl(nl_stack_t *h, const nl::PassRequest &req)
     h->partial_clean = false;
     if (timed && !one_start) NL_HIP(hipEventRecord(h->ev_dom0, h->stream));
 
-    const PassSetup p{mode, weighted, timed, fused, a, tier};
+    const nl::Form form = maps ? nl::Form::Maps : (wclip || wmad) ? nl::Form::Follow : nl::Form::Plain;
+    const PassSetup p{mode, weighted, timed, fused, a, form};
     PassFacts facts;
     int rc = NL_OK;
-    if (wlinfit) rc = run_linfit_weighted(h, p, &facts);
-    else if (wclip) rc = run_clip_weighted(h, p, &facts);
-    else if (wmad) rc = run_mad_weighted(h, p, &facts);
-    else switch (engine) {
+    switch (engine) {
     case Engine::Mean:            rc = run_mean(h, p, &facts); break;
     case Engine::MedianRegisters: rc = run_median(h, p, false); break;
     case Engine::MedianMultiLane: rc = run_median(h, p, true); break;
@@ -930,6 +923,9 @@ static int run_async_impl(nl_stack_t *h, const nl::PassRequest &req)
     case Engine::WeightedTile:    rc = run_weighted_tile(h, p, &facts); break;
     case Engine::DenseReplay:     rc = run_dense_replay(h, p, &facts); break;
     case Engine::ExactColumns:    rc = run_exact_columns(h, p, &facts); break;
+    case Engine::LinfitWeighted:  rc = run_linfit_weighted(h, p, &facts); break;
+    case Engine::ClipWeighted:    rc = run_clip_weighted(h, p, &facts); break;
+    case Engine::MadWeighted:     rc = run_mad_weighted(h, p, &facts); break;
     }
     if (rc != NL_OK) return rc;
     NL_HIP(hipEventRecord(h->ev_stop, h->stream));

@@ -574,59 +574,49 @@ int exact_plan(int mode, bool weighted, int n_frames, int n_pad, int max_lanes, 
 
 // every instantiation of the column kernel a pass can ask for: plain, then <follow> (include/nlstack_wclip.h: one column,
 // plan with weighted = false), then MAPS (every pixel's two clip counts go to args.reject_map)
-enum class ExactVariant { Plain, Follow, Maps };
 struct ExactEntry {
-    ExactVariant variant; int mode; bool weighted; const char *name;
+    Form form; int mode; bool weighted; const char *name;
     hipError_t (*launch)(const StackArgs &, int, int, size_t, hipStream_t);
 };
 static const ExactEntry kExactTable[] = {
-    {ExactVariant::Plain, NL_ST_MEDIAN, false, "stack_exact_kernel<median>", launch_exact<NL_ST_MEDIAN, false>},
-    {ExactVariant::Plain, NL_ST_SIGMA, true, "stack_exact_kernel<sigma,weighted>", launch_exact<NL_ST_SIGMA, true>},
-    {ExactVariant::Plain, NL_ST_SIGMA, false, "stack_exact_kernel<sigma>", launch_exact<NL_ST_SIGMA, false>},
-    {ExactVariant::Plain, NL_ST_WINSOR_SIGMA, true, "stack_exact_kernel<winsor,weighted>", launch_exact<NL_ST_WINSOR_SIGMA, true>},
-    {ExactVariant::Plain, NL_ST_WINSOR_SIGMA, false, "stack_exact_kernel<winsor>", launch_exact<NL_ST_WINSOR_SIGMA, false>},
-    {ExactVariant::Plain, NL_ST_MAD_SIGMA, false, "stack_exact_kernel<mad>", launch_exact<NL_ST_MAD_SIGMA, false>},
+    {Form::Plain, NL_ST_MEDIAN, false, "stack_exact_kernel<median>", launch_exact<NL_ST_MEDIAN, false>},
+    {Form::Plain, NL_ST_SIGMA, true, "stack_exact_kernel<sigma,weighted>", launch_exact<NL_ST_SIGMA, true>},
+    {Form::Plain, NL_ST_SIGMA, false, "stack_exact_kernel<sigma>", launch_exact<NL_ST_SIGMA, false>},
+    {Form::Plain, NL_ST_WINSOR_SIGMA, true, "stack_exact_kernel<winsor,weighted>", launch_exact<NL_ST_WINSOR_SIGMA, true>},
+    {Form::Plain, NL_ST_WINSOR_SIGMA, false, "stack_exact_kernel<winsor>", launch_exact<NL_ST_WINSOR_SIGMA, false>},
+    {Form::Plain, NL_ST_MAD_SIGMA, false, "stack_exact_kernel<mad>", launch_exact<NL_ST_MAD_SIGMA, false>},
     // (the weighted linear-fit pass, include/nlstack_wlinfit.h: never a default pass)
-    {ExactVariant::Plain, NL_ST_LINEAR_FIT, true, "stack_exact_kernel<linfit,weighted>", launch_exact<NL_ST_LINEAR_FIT, true>},
-    {ExactVariant::Plain, NL_ST_LINEAR_FIT, false, "stack_exact_kernel<linearfit>", launch_exact<NL_ST_LINEAR_FIT, false>},
-    {ExactVariant::Follow, NL_ST_SIGMA, false, "stack_exact_kernel<sigma,follow>", launch_exact<NL_ST_SIGMA, false, false, true>},
-    {ExactVariant::Follow, NL_ST_WINSOR_SIGMA, false, "stack_exact_kernel<winsor,follow>", launch_exact<NL_ST_WINSOR_SIGMA, false, false, true>},
+    {Form::Plain, NL_ST_LINEAR_FIT, true, "stack_exact_kernel<linfit,weighted>", launch_exact<NL_ST_LINEAR_FIT, true>},
+    {Form::Plain, NL_ST_LINEAR_FIT, false, "stack_exact_kernel<linearfit>", launch_exact<NL_ST_LINEAR_FIT, false>},
+    {Form::Follow, NL_ST_SIGMA, false, "stack_exact_kernel<sigma,follow>", launch_exact<NL_ST_SIGMA, false, false, true>},
+    {Form::Follow, NL_ST_WINSOR_SIGMA, false, "stack_exact_kernel<winsor,follow>", launch_exact<NL_ST_WINSOR_SIGMA, false, false, true>},
     // (the weighted MAD-sigma pass, include/nlstack_wmad.h: two columns, as the plain MAD kernel)
-    {ExactVariant::Follow, NL_ST_MAD_SIGMA, false, "stack_exact_kernel<mad,follow>", launch_exact<NL_ST_MAD_SIGMA, false, false, true>},
-    {ExactVariant::Maps, NL_ST_MEDIAN, false, "stack_exact_kernel<median,maps>", launch_exact<NL_ST_MEDIAN, false, true>},
-    {ExactVariant::Maps, NL_ST_SIGMA, true, "stack_exact_kernel<sigma,weighted,maps>", launch_exact<NL_ST_SIGMA, true, true>},
-    {ExactVariant::Maps, NL_ST_SIGMA, false, "stack_exact_kernel<sigma,maps>", launch_exact<NL_ST_SIGMA, false, true>},
-    {ExactVariant::Maps, NL_ST_WINSOR_SIGMA, true, "stack_exact_kernel<winsor,weighted,maps>", launch_exact<NL_ST_WINSOR_SIGMA, true, true>},
-    {ExactVariant::Maps, NL_ST_WINSOR_SIGMA, false, "stack_exact_kernel<winsor,maps>", launch_exact<NL_ST_WINSOR_SIGMA, false, true>},
-    {ExactVariant::Maps, NL_ST_MAD_SIGMA, false, "stack_exact_kernel<mad,maps>", launch_exact<NL_ST_MAD_SIGMA, false, true>},
-    {ExactVariant::Maps, NL_ST_LINEAR_FIT, false, "stack_exact_kernel<linearfit,maps>", launch_exact<NL_ST_LINEAR_FIT, false, true>},
+    {Form::Follow, NL_ST_MAD_SIGMA, false, "stack_exact_kernel<mad,follow>", launch_exact<NL_ST_MAD_SIGMA, false, false, true>},
+    {Form::Maps, NL_ST_MEDIAN, false, "stack_exact_kernel<median,maps>", launch_exact<NL_ST_MEDIAN, false, true>},
+    {Form::Maps, NL_ST_SIGMA, true, "stack_exact_kernel<sigma,weighted,maps>", launch_exact<NL_ST_SIGMA, true, true>},
+    {Form::Maps, NL_ST_SIGMA, false, "stack_exact_kernel<sigma,maps>", launch_exact<NL_ST_SIGMA, false, true>},
+    {Form::Maps, NL_ST_WINSOR_SIGMA, true, "stack_exact_kernel<winsor,weighted,maps>", launch_exact<NL_ST_WINSOR_SIGMA, true, true>},
+    {Form::Maps, NL_ST_WINSOR_SIGMA, false, "stack_exact_kernel<winsor,maps>", launch_exact<NL_ST_WINSOR_SIGMA, false, true>},
+    {Form::Maps, NL_ST_MAD_SIGMA, false, "stack_exact_kernel<mad,maps>", launch_exact<NL_ST_MAD_SIGMA, false, true>},
+    {Form::Maps, NL_ST_LINEAR_FIT, false, "stack_exact_kernel<linearfit,maps>", launch_exact<NL_ST_LINEAR_FIT, false, true>},
 };
 
-static hipError_t launch_exact_variant(ExactVariant variant, int mode, bool weighted, const StackArgs &args, int lanes, int grid,
-                                       size_t lds_bytes, hipStream_t stream, const char **name)
+// Form::Maps: every pixel's two clip counts also go to args.reject_map; Form::Follow (sigma / winsorized: one column, plan
+// with weighted = false; MAD sigma, the weighted MAD-sigma pass: two columns): the weights come from args.weights
+hipError_t launch_stack_exact(int mode, bool weighted, const StackArgs &args, int lanes, int grid,
+                              size_t lds_bytes, hipStream_t stream, const char **name, Form form)
 {
+    // (the median and MAD sigma never weigh, a maps pass drops the linear fit's weights as every unweighted entry does,
+    // and the <follow> instantiations are keyed as unweighted)
+    if (mode == NL_ST_MEDIAN || mode == NL_ST_MAD_SIGMA || (form == Form::Maps && mode == NL_ST_LINEAR_FIT) || form == Form::Follow)
+        weighted = false;
+    if (!form_args_ok(form, args) || (mode == NL_ST_LINEAR_FIT && weighted && !args.weights)) return hipErrorInvalidValue;
     for (const ExactEntry &e : kExactTable)
-        if (e.variant == variant && e.mode == mode && e.weighted == weighted) {
+        if (e.form == form && e.mode == mode && e.weighted == weighted) {
             *name = e.name;
             return e.launch(args, lanes, grid, lds_bytes, stream);
         }
     return hipErrorInvalidValue;
-}
-
-hipError_t launch_stack_exact(int mode, bool weighted, const StackArgs &args, int lanes, int grid,
-                              size_t lds_bytes, hipStream_t stream, const char **name, bool maps)
-{
-    // (the median and MAD sigma never weigh, and a maps pass drops the linear fit's weights as every unweighted entry does)
-    if (mode == NL_ST_MEDIAN || mode == NL_ST_MAD_SIGMA || (maps && mode == NL_ST_LINEAR_FIT)) weighted = false;
-    if ((maps && !args.reject_map) || (mode == NL_ST_LINEAR_FIT && weighted && !args.weights)) return hipErrorInvalidValue;
-    return launch_exact_variant(maps ? ExactVariant::Maps : ExactVariant::Plain, mode, weighted, args, lanes, grid, lds_bytes, stream, name);
-}
-
-hipError_t launch_stack_exact_follow(int mode, const StackArgs &args, int lanes, int grid, size_t lds_bytes,
-                                     hipStream_t stream, const char **name)
-{
-    if (!args.weights) return hipErrorInvalidValue;
-    return launch_exact_variant(ExactVariant::Follow, mode, false, args, lanes, grid, lds_bytes, stream, name);
 }
 
 hipError_t launch_reduce_counters(unsigned long long *partial, int n_blocks,

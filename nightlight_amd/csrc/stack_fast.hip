@@ -489,37 +489,21 @@ int mad_fast_supported(int mode, bool weighted, int n_frames, int64_t npix)
     return (mode == NL_ST_MAD_SIGMA && !weighted && n_frames >= 1 && n_frames <= 128 && npix < kFastMaxPixels) ? 1 : 0;
 }
 
-// "NAME<a, ..., maps>" / "NAME<maps>": the default pass's display name of a MAD kernel with "maps" as its last argument
-template <const char *BASE, auto... ARGS>
-static const char *mad_maps_kernel_name()
+// Form::Follow: the weighted MAD-sigma pass (include/nlstack_wmad.h); Form::Maps: the full maps pass (include/nlstack_fullmaps.h)
+hipError_t launch_stack_mad_fast(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name, Form form)
 {
-    static const std::string name = [] {
-        std::string s = BASE;
-        s += "<";
-        ((s += name_arg(ARGS), s += ", "), ...);
-        return s + "maps>";
-    }();
-    return name.c_str();
-}
-
-// follow: the FOLLOW instantiations (the weighted MAD-sigma pass, include/nlstack_wmad.h; args.weights must be set)
-// maps: the MAPS instantiations (the full maps pass, include/nlstack_fullmaps.h; args.reject_map must be set)
-hipError_t launch_stack_mad_fast(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name, bool follow,
-                                 bool maps)
-{
-    if (follow && !args.weights) return hipErrorInvalidValue;
-    if (maps && (!args.reject_map || follow)) return hipErrorInvalidValue;
+    if (form == Form::Record || !form_args_ok(form, args)) return hipErrorInvalidValue;
     Launcher L(stream);
     const unsigned blocks = pixel_grid(args.npix);
     // f(FOLLOW, MAPS): plain, follow or maps
     auto with_form = [&](auto &&f) {
-        if (maps) f(std::false_type{}, std::true_type{});
-        else with_bool(follow, [&](auto F) { f(F, std::false_type{}); });
+        if (form == Form::Maps) f(std::false_type{}, std::true_type{});
+        else with_bool(form == Form::Follow, [&](auto F) { f(F, std::false_type{}); });
     };
     with_form([&](auto F, auto M) {
         constexpr bool FOLLOW = decltype(F)::value, MAPS = decltype(M)::value;
         if (args.n_frames >= 114 && fargs.gen_list) {
-            if constexpr (MAPS)        *name = mad_maps_kernel_name<kMadBitonicName>();
+            if constexpr (MAPS)        *name = maps_kernel_name<kMadBitonicName>();
             else if constexpr (FOLLOW) *name = kernel_name<kMadBitonicName, true>();
             else                       *name = "stack_mad_bitonic_kernel";
             L(stack_mad_bitonic_kernel<FOLLOW, MAPS>, blocks, 256, 0, args, whole_tile(fargs));
@@ -529,7 +513,7 @@ hipError_t launch_stack_mad_fast(const StackArgs &args, const FastArgs &fargs, h
         }
         with_class<8, 16, 32, 48, 64, 80, 96, 112, 128>(args.n_frames, [&](auto C) {
             constexpr int NS = decltype(C)::value;
-            if constexpr (MAPS)        *name = mad_maps_kernel_name<kMadFastName, NS>();
+            if constexpr (MAPS)        *name = maps_kernel_name<kMadFastName, NS>();
             else if constexpr (FOLLOW) *name = kernel_name<kMadFastName, NS, true>();
             else                       *name = kernel_name<kMadFastName, NS>();
             L(stack_mad_fast_kernel<NS, FOLLOW, MAPS>, blocks, 256, 0, args, fargs);
@@ -663,17 +647,31 @@ static hipError_t with_sigma_network(bool winsor, int n_frames, F &&f)
     });
 }
 
-hipError_t launch_stack_sigma_fast_dominant(const StackArgs &args, const FastArgs &fargs, hipStream_t stream,
-                                            const char **name, hipEvent_t dominant_done, bool winsor)
+// (stack_fast_maps_sigma.hip / stack_fast_maps_winsor.hip: the MAPS instantiations, units of their own for build parallelism)
+hipError_t sigma_maps_dominant(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name,
+                               hipEvent_t dominant_done, bool winsor);
+hipError_t sigma_maps_generic(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, bool winsor);
+
+hipError_t launch_stack_sigma_dominant(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name,
+                                       hipEvent_t dominant_done, bool winsor, Form form)
 {
+    // (the MAPS kernels have no continuation form: no cascade plan)
+    if ((form != Form::Plain && form != Form::Maps) || !form_args_ok(form, args) || (form == Form::Maps && fargs.cas_list[0]))
+        return hipErrorInvalidValue;
+    if (form == Form::Maps) return sigma_maps_dominant(args, fargs, stream, name, dominant_done, winsor);
     return with_sigma_network(winsor, args.n_frames, [&](auto C, auto W) {
         return launch_dominant<decltype(C)::value, decltype(W)::value>(args, fargs, stream, name, dominant_done);
     });
 }
 
-hipError_t launch_stack_sigma_fast_generic(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, bool winsor,
-                                           const StackArgs *first_replay, unsigned replay_blocks)
+hipError_t launch_stack_sigma_generic(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, bool winsor, Form form,
+                                      const StackArgs *first_replay, unsigned replay_blocks)
 {
+    // (no fused tail either: the generic part of a maps pass is a launch of its own, on a fixed grid)
+    if ((form != Form::Plain && form != Form::Maps) || !form_args_ok(form, args) ||
+        (form == Form::Maps && (first_replay || fargs.cas_list[0])))
+        return hipErrorInvalidValue;
+    if (form == Form::Maps) return sigma_maps_generic(args, fargs, stream, winsor);
     return with_sigma_network(winsor, args.n_frames, [&](auto C, auto W) {
         return launch_generic<decltype(C)::value, decltype(W)::value>(args, fargs, stream, first_replay, replay_blocks);
     });

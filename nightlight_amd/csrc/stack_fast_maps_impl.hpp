@@ -30,18 +30,6 @@ void stack_sigma_mlg_maps_kernel(StackArgs p, FastArgs q)
     mlg_body<1, WINSOR, true>(p, q, blockIdx.x, gridDim.x);
 }
 
-// the default pass's display name of the same instantiation with "maps" in the place of the last argument
-template <int NS, bool ZONAL, bool WINSOR, bool TIGHT>
-const char *maps_kernel_name()
-{
-    static const std::string name = [] {
-        std::string s = kernel_name<kSigmaFastMapsBase, NS, ZONAL, WINSOR, TIGHT, false, false>();
-        s.pop_back();
-        return s + ", maps>";
-    }();
-    return name.c_str();
-}
-
 // FastArgs of a kernel of the maps pass over the whole tile: both hand-over lists, no cascade, no budgets
 inline FastArgs maps_tile_args(const FastArgs &fargs)
 {
@@ -63,11 +51,11 @@ hipError_t launch_maps_dominant(const StackArgs &args, const FastArgs &fargs, hi
     if constexpr (NS >= kMapsZonalMinSize) {
         with_bool(args.n_frames == NS, [&](auto T) {
             constexpr bool TIGHT = decltype(T)::value;
-            *name = maps_kernel_name<NS, true, WINSOR, TIGHT>();
+            *name = maps_kernel_name<kSigmaFastMapsBase, NS, true, WINSOR, TIGHT, false, false>();
             L(stack_sigma_fast_kernel<NS, true, WINSOR, TIGHT, false, false, true>, tile_blocks, 256, 0, args, f);
         });
     } else {
-        *name = maps_kernel_name<NS, false, WINSOR, false>();
+        *name = maps_kernel_name<kSigmaFastMapsBase, NS, false, WINSOR, false, false, false>();
         L(stack_sigma_fast_kernel<NS, false, WINSOR, false, false, false, true>, tile_blocks, 256, 0, args, f);
     }
     L.record(dominant_done);
@@ -95,7 +83,7 @@ template <bool WINSOR>
 hipError_t maps_dominant(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name,
                          hipEvent_t dominant_done)
 {
-    if (!args.reject_map || args.n_frames < 2 || args.n_frames > 128) return hipErrorInvalidValue;
+    if (args.n_frames < 2 || args.n_frames > 128) return hipErrorInvalidValue;      // (args.reject_map: checked by the public launcher)
     return with_class<8, 16, 24, 32, 48, 64, 80, 96, 112, 128>(args.n_frames, [&](auto C) {
         return launch_maps_dominant<decltype(C)::value, WINSOR>(args, fargs, stream, name, dominant_done);
     });
@@ -104,7 +92,7 @@ hipError_t maps_dominant(const StackArgs &args, const FastArgs &fargs, hipStream
 template <bool WINSOR>
 hipError_t maps_generic(const StackArgs &args, const FastArgs &fargs, hipStream_t stream)
 {
-    if (!args.reject_map || args.n_frames < 2 || args.n_frames > 128) return hipErrorInvalidValue;
+    if (args.n_frames < 2 || args.n_frames > 128) return hipErrorInvalidValue;      // (args.reject_map: checked by the public launcher)
     return with_class<8, 16, 24, 32, 48, 64, 80, 96, 112, 128>(args.n_frames, [&](auto C) {
         return launch_maps_generic<decltype(C)::value, WINSOR>(args, fargs, stream);
     });

@@ -19,6 +19,7 @@
 // StackSigma: internal/ops/stack/stack.go:372-436.  HBM traffic: every sample is
 // read once; a wave instruction covers 64/LPP consecutive pixels of LPP frames.
 #include <cstdlib>
+#include <cstring>
 
 #include "fast_ml_common.hpp"
 #include "launch_common.hpp"
@@ -185,22 +186,21 @@ void stack_mad_ml_kernel(StackArgs p, FastArgs q)
     }
 }
 
-// maps: the MAPS instantiations (the full maps pass; args.reject_map must be set), named as the default pass's kernel
-// with "maps" as its last argument
-hipError_t launch_stack_mad_ml(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name, bool record,
-                               bool maps)
+// Form::Maps: the full maps pass, named as the default pass's kernel with "maps" as its last argument.  Form::Record: the
+// weighted MAD-sigma pass; the kernel writes no list, so it gets an all-zero FastArgs and `fargs` is not read
+hipError_t launch_stack_mad_ml(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name, Form form)
 {
-    if (record && (!args.bounds || !args.nrounds)) return hipErrorInvalidValue;
-    if (maps && (!args.reject_map || record)) return hipErrorInvalidValue;
+    if (form == Form::Follow || !form_args_ok(form, args)) return hipErrorInvalidValue;
     Launcher L(stream);
     with_ml_lanes(args.n_frames, [&](auto LPP) {
-        if (maps) {
-            static const std::string maps_name = std::string(kMadMlName) + "<" + std::to_string(decltype(LPP)::value) + ", maps>";
-            *name = maps_name.c_str();
+        if (form == Form::Maps) {
+            *name = maps_kernel_name<kMadMlName, decltype(LPP)::value>();
             L(stack_mad_ml_kernel<decltype(LPP)::value, false, true>, pixel_grid(args.npix, LPP), 256, 0, args, fargs);
-        } else if (record) {
+        } else if (form == Form::Record) {
+            FastArgs none;
+            memset(&none, 0, sizeof none);
             *name = kernel_name<kMadMlName, decltype(LPP)::value, true>();
-            L(stack_mad_ml_kernel<decltype(LPP)::value, true>, pixel_grid(args.npix, LPP), 256, 0, args, fargs);
+            L(stack_mad_ml_kernel<decltype(LPP)::value, true>, pixel_grid(args.npix, LPP), 256, 0, args, none);
         } else {
             *name = kernel_name<kMadMlName, decltype(LPP)::value>();
             L(stack_mad_ml_kernel<decltype(LPP)::value>, pixel_grid(args.npix, LPP), 256, 0, args, fargs);

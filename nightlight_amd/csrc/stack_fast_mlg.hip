@@ -58,9 +58,10 @@ void stack_sigma_mlg_kernel(StackArgs p, FastArgs q)
 static hipError_t launch_mlg_lanes_maps(const StackArgs &args, const FastArgs &fargs, unsigned grid, hipStream_t stream, bool winsor);
 
 hipError_t launch_stack_sigma_mlg(const StackArgs &args, const FastArgs &fargs, unsigned grid, hipStream_t stream,
-                                  bool winsor, bool maps)
+                                  bool winsor, Form form)
 {
-    if (maps) return launch_mlg_lanes_maps(args, fargs, grid, stream, winsor);
+    if ((form != Form::Plain && form != Form::Maps) || !form_args_ok(form, args)) return hipErrorInvalidValue;
+    if (form == Form::Maps) return launch_mlg_lanes_maps(args, fargs, grid, stream, winsor);
     Launcher L(stream);
     with_bool(winsor, [&](auto W) {
         constexpr bool WINSOR = decltype(W)::value;
@@ -89,7 +90,7 @@ void stack_sigma_mlg_lanes_maps_kernel(StackArgs p, FastArgs q)
 // its caller passes the grid without one, ml_generic_grid(n, 0)
 static hipError_t launch_mlg_lanes_maps(const StackArgs &args, const FastArgs &fargs, unsigned grid, hipStream_t stream, bool winsor)
 {
-    if (!args.reject_map || args.n_frames <= kMlNS || args.n_frames > 4 * kMlNS) return hipErrorInvalidValue;
+    if (args.n_frames <= kMlNS || args.n_frames > 4 * kMlNS) return hipErrorInvalidValue;
     Launcher L(stream);
     with_bool(winsor, [&](auto W) {
         with_ml_lanes(args.n_frames, [&](auto LPP) {

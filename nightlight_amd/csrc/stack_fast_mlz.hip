@@ -1,5 +1,7 @@
 // stack_fast_mlz.hip -- dispatch of the LDS-column sigma / winsor kernels (stack_fast_mlz_impl.hpp) over the
 // frame-count classes: NTOP = frames rounded up to a multiple of 16, 2 lanes per pixel up to 256 frames, else 4
+#include <string.h>
+
 #include "launch_common.hpp"
 
 namespace nl {
@@ -29,15 +31,23 @@ int decide_ml_supported(int mode, int n_frames, int64_t npix)
 }
 
 // the zonal launch over the whole tile (the generic pass over its hand-over list is stack_fast_mlg.hip); the part that
-// instantiates the class sets *name.  maps: the MAPS instantiation of the class -- every pixel the kernel decides gets its
-// word of args.reject_map beside its result; never a record-only pass
+// instantiates the class sets *name.  Form::Maps: the MAPS instantiation of the class -- every pixel the kernel decides gets
+// its word of args.reject_map beside its result.  Form::Record: the plain instantiation as a decision pass, which reads
+// FastArgs::record_only -- the kernel gets a FastArgs of its own, all bytes zero (cert_every too) but that field; `fargs`
+// is not read
 hipError_t launch_stack_sigma_mlz(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name,
-                                  bool winsor, bool maps)
+                                  bool winsor, Form form)
 {
-    if (maps && (!args.reject_map || fargs.record_only || !fast_mlz_supported(winsor ? NL_ST_WINSOR_SIGMA : NL_ST_SIGMA, false, args.n_frames)))
+    const bool maps = form == Form::Maps;
+    if (form == Form::Follow || !form_args_ok(form, args) ||
+        (maps && (fargs.record_only || !fast_mlz_supported(winsor ? NL_ST_WINSOR_SIGMA : NL_ST_SIGMA, false, args.n_frames))))
         return hipErrorInvalidValue;
     Launcher L(stream);
-    const FastArgs f = whole_tile(fargs);
+    FastArgs f = whole_tile(fargs);
+    if (form == Form::Record) {
+        memset(&f, 0, sizeof f);
+        f.record_only = 1;
+    }
     const int ntop = (args.n_frames + 15) / 16 * 16;
     const auto *const parts = maps ? kMapsParts : kParts;
     bool ok = false;

@@ -841,19 +841,6 @@ void stack_sigma_mlz_kernel(StackArgs p, FastArgs q)
 
 constexpr char kMlzName[] = "stack_sigma_mlz_kernel";
 
-// the default pass's display name of the same instantiation with "maps" as its last argument (maps_kernel_name,
-// stack_fast_maps_impl.hpp)
-template <int LPP, bool WINSOR, int NTOP>
-const char *mlz_maps_kernel_name()
-{
-    static const std::string name = [] {
-        std::string s = kernel_name<kMlzName, LPP, WINSOR, NTOP, 0>();
-        s.pop_back();
-        return s + ", maps>";
-    }();
-    return name.c_str();
-}
-
 // launches the kernel of frame-count class `ntop` if it is one of this translation unit's (consecutive multiples of 16);
 // MAPS: its MAPS instantiation (stack_fast_mlz_maps_*.hip).  A stack of 241 ... 255 or 497 ... 511 frames runs the class that
 // fills its lanes, whose columns take 15 missing samples -- and is up to 15 short already: at 497 frames every pixel with
@@ -868,7 +855,7 @@ static bool launch_mlz_classes(int ntop, bool winsor, const StackArgs &args, con
             constexpr bool WINSOR = decltype(W)::value;
             constexpr int NTOP = decltype(C)::value;
             using LY = MlzLayout<LPP, WINSOR, NTOP>;
-            if constexpr (MAPS) *name = mlz_maps_kernel_name<LPP, WINSOR, NTOP>();
+            if constexpr (MAPS) *name = maps_kernel_name<kMlzName, LPP, WINSOR, NTOP, 0>();
             else                *name = kernel_name<kMlzName, LPP, WINSOR, NTOP, 0>();
             if constexpr (MAPS && NTOP == kMlNS * LPP) {
                 if (args.n_frames < NTOP) {

@@ -109,11 +109,32 @@ struct FastArgs {
     unsigned in_region, in_regions, in_group;      // entries per input region, number of regions, regions per workgroup
     int pass_budget, round_cap;   // clipping passes a wave may run in this stage / winsorization rounds per pass (0 = no limit)
     int record_only = 0;          // LDS-column kernels as the DECISION pass of a weighted stack (129 ... 512 frames): no outputs, no
-                                  // lists, no counters -- only StackArgs::bounds / nrounds (0 rounds for a pixel they would hand over)
+                                  // lists, no counters -- only StackArgs::bounds / nrounds (0 rounds for a pixel they would hand over).
+                                  // Set by launch_stack_sigma_mlz for Form::Record, by nobody else
     int cert_first = 0, cert_every = 1;      // invariant-interval certificate of the winsorization loops (stack_fast_sigma_impl.hpp): first trial after this many rounds of a loop (0: off), then every so many
     int gen_round_cap = 0;        // generic pass of the one-lane winsorized kernels: winsorization rounds per clipping pass before a pixel
                                   // is handed to the exact replay instead (0: 100, the limit of every kernel)
 };
+
+// The FORM of a stack kernel: what an instantiation does beside, or instead of, its plain work.  Every launcher that
+// has forms takes one `Form form = Form::Plain` and returns hipErrorInvalidValue for a form it has no instantiation of,
+// or whose StackArgs fields are missing (form_args_ok).  On the device the forms are the bool template parameters MAPS,
+// FOLLOW and RECORD.
+//   Plain   the kernel as every default pass runs it;
+//   Maps    also store the pixel's two clip counts, clipLow | clipHigh << 16 (a maps pass): needs args.reject_map;
+//   Follow  weights follow their frames (the weighted clip and MAD-sigma passes): needs args.weights;
+//   Record  leave only the clip bounds, no outputs, lists or counters (a decision pass): needs args.bounds and
+//           args.nrounds.
+enum class Form { Plain, Maps, Follow, Record };
+inline bool form_args_ok(Form form, const StackArgs &args)
+{
+    switch (form) {
+    case Form::Maps:   return args.reject_map != nullptr;
+    case Form::Follow: return args.weights != nullptr;
+    case Form::Record: return args.bounds != nullptr && args.nrounds != nullptr;
+    default:           return true;
+    }
+}
 
 // sets what nl_last_error() returns on this thread (nlstack_api.hip)
 void set_last_error(const char *msg);
@@ -129,10 +150,11 @@ int stack_settle(nl_stack_t *h);
 // Picks lanes-per-wave and LDS bytes for the exact kernel; -1 if it cannot fit.
 int exact_plan(int mode, bool weighted, int n_frames, int n_pad, int max_lanes, int *lanes,
                size_t *lds_bytes);
-// maps: the MAPS instantiations -- every pixel's two clip counts also go to args.reject_map (the whole tile, or -- the
-// replay behind the other kernels of a maps pass -- the pixels of args.list)
+// Plain, Maps or Follow, over the whole tile or -- the replay behind the other kernels of a pass -- the pixels of args.list.
+// The median, MAD sigma and a Maps linear fit drop `weighted`.  Follow (the weighted clip pass, include/nlstack_wclip.h:
+// NL_ST_SIGMA / NL_ST_WINSOR_SIGMA, one column; the weighted MAD-sigma pass: two columns) ignores it: plan with weighted = false
 hipError_t launch_stack_exact(int mode, bool weighted, const StackArgs &args, int lanes, int grid,
-                              size_t lds_bytes, hipStream_t stream, const char **name, bool maps = false);
+                              size_t lds_bytes, hipStream_t stream, const char **name, Form form = Form::Plain);
 // list_counts (optional): {exact-list length, generic-list length} of the pass, left in counters[2] (low | high << 32)
 // zero_after: the kernel leaves the scratch set (kScratchWords words at `partial`) zeroed for the next pass
 hipError_t launch_reduce_counters(unsigned long long *partial, int n_blocks,
@@ -148,36 +170,31 @@ hipError_t launch_stack_median_fast(const StackArgs &args, const FastArgs &fargs
                                     const char **name, hipEvent_t dominant_done);
 // dominant_done (optional) is recorded right after the first, dominant kernel
 int mad_fast_supported(int mode, bool weighted, int n_frames, int64_t npix);
-// follow: the FOLLOW instantiations of the same kernels (the weighted MAD-sigma pass, include/nlstack_wmad.h; args.weights set)
-// maps: their MAPS instantiations (the full maps pass, include/nlstack_fullmaps.h; args.reject_map set, never with follow):
-// one more store per pixel, its two clip counts
+// Plain, Follow (the weighted MAD-sigma pass, include/nlstack_wmad.h) or Maps (the full maps pass, include/nlstack_fullmaps.h)
 hipError_t launch_stack_mad_fast(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name,
-                                 bool follow = false, bool maps = false);
+                                 Form form = Form::Plain);
 // 249..256 / 505..512 frames: zonal sigma / winsorized sigma pass with the clipping rounds on LDS
 // columns (stack_fast_mlz.hip); hand-over lists as the other fast kernels
 // generic pass of the multi-lane sigma / winsor kernels over fargs.in_list, whole columns in LDS (stack_fast_mlg.hip)
-// maps (both launches, 129 ... 512 frames, args.reject_map set: the two parts of a maps pass at that depth): the MAPS
-// instantiations (stack_fast_mlz_maps_{a,b,c,d}.hip, stack_fast_mlg.hip), one more store per pixel, its two clip counts
+// Maps (both launches, 129 ... 512 frames: the two parts of a maps pass at that depth): stack_fast_mlz_maps_{a,b,c,d}.hip,
+// stack_fast_mlg.hip.  launch_stack_sigma_mlz also takes Record (the decision pass of a weighted stack): the launcher then
+// passes the kernel a FastArgs of its own, all zero but record_only = 1, whatever `fargs` holds
 hipError_t launch_stack_sigma_mlg(const StackArgs &args, const FastArgs &fargs, unsigned grid, hipStream_t stream,
-                                  bool winsor, bool maps = false);
+                                  bool winsor, Form form = Form::Plain);
 int fast_mlz_supported(int mode, bool weighted, int n_frames);
 hipError_t launch_stack_sigma_mlz(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name,
-                                  bool winsor, bool maps = false);
+                                  bool winsor, Form form = Form::Plain);
 // sigma / winsorized clipping of 2 ... 128 frames, in the two parts a pass enqueues them.  Dominant part: the zonal kernel
 // (network size 8: the generic kernel over the whole tile), dominant_done (optional) recorded behind it, and for winsorized
 // stacks the continuation stages of the cascade.  Generic part: the pass over the generic list (network size 8: nothing);
 // with first_replay (tail_fused_supported) it shares ONE launch with the replay of the exact list as the dominant part left
 // it (stack_tail_fused.hip) -- *first_replay are that replay's arguments (list part 0), in replay_blocks workgroups
-hipError_t launch_stack_sigma_fast_dominant(const StackArgs &args, const FastArgs &fargs, hipStream_t stream,
-                                            const char **name, hipEvent_t dominant_done, bool winsor);
-hipError_t launch_stack_sigma_fast_generic(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, bool winsor,
-                                           const StackArgs *first_replay = nullptr, unsigned replay_blocks = 0);
-// ---- stack_fast_maps_sigma.hip / stack_fast_maps_winsor.hip: the two parts of a maps pass of 2 ... 128 frames,
-// args.reject_map set.  As the parts above with one more store per pixel, its two clip counts; no cascade, no fused
-// tail, no hints: the generic part runs a fixed grid ----
-hipError_t launch_stack_sigma_maps_dominant(const StackArgs &args, const FastArgs &fargs, hipStream_t stream,
-                                            const char **name, hipEvent_t dominant_done, bool winsor);
-hipError_t launch_stack_sigma_maps_generic(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, bool winsor);
+// Maps (stack_fast_maps_sigma.hip / stack_fast_maps_winsor.hip): as the parts above with one more store per pixel; no cascade
+// plan in fargs, no first_replay, no hints -- the generic part runs a fixed grid
+hipError_t launch_stack_sigma_dominant(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name,
+                                       hipEvent_t dominant_done, bool winsor, Form form = Form::Plain);
+hipError_t launch_stack_sigma_generic(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, bool winsor,
+                                      Form form = Form::Plain, const StackArgs *first_replay = nullptr, unsigned replay_blocks = 0);
 // ---- stack_tail_fused.hip: generic pass (one lane per pixel, LDS columns) + first replay in one grid; plain sigma, 65 ... 128 frames
 int tail_fused_supported(int mode, bool weighted, int n_frames);
 hipError_t launch_stack_sigma_tail(const StackArgs &generic, const FastArgs &fargs, unsigned gen_blocks,
@@ -190,17 +207,16 @@ constexpr int kBoundRounds = 8;
 // stacks (StackArgs::bounds / nrounds); 33 ... 128 frames (decide_supported); 129 ... 512 frames: the LDS-column kernel
 // of the frame-count class, record-only (decide_ml_supported) ----
 int decide_supported(int mode, int n_frames, int64_t npix);
-int decide_ml_supported(int mode, int n_frames, int64_t npix);      // 129 ... 512 frames: the LDS-column kernel of the class, FastArgs::record_only
+int decide_ml_supported(int mode, int n_frames, int64_t npix);      // 129 ... 512 frames: launch_stack_sigma_mlz, Form::Record
 hipError_t launch_stack_sigma_decide(const StackArgs &args, hipStream_t stream, bool winsor, const char **name);
 
 // ---- stack_fast_ml.hip (129..512 frames, 2 or 4 lanes per pixel) ----
 constexpr int kMlNS = 128;     // samples per lane of the multi-lane kernels
 int fast_ml_supported(int mode, bool weighted, int n_frames, int64_t npix);
 hipError_t launch_stack_median_ml(const StackArgs &args, hipStream_t stream, const char **name);
-// record: the RECORD instantiations (the weighted MAD-sigma pass): only args.bounds / args.nrounds are written, one round
-// maps: the MAPS instantiations (the full maps pass; args.reject_map set, never with record)
+// Plain, Maps (the full maps pass) or Record (the weighted MAD-sigma pass: one round per pixel, `fargs` is not read)
 hipError_t launch_stack_mad_ml(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name,
-                               bool record = false, bool maps = false);
+                               Form form = Form::Plain);
 unsigned ml_generic_grid(int n_frames, unsigned gen_hint);      // workgroups of launch_stack_sigma_mlg behind launch_stack_sigma_mlz
 
 // ---- stack_exact_coop.hip (bit-exact sigma replay, one wave per pixel) ----
@@ -241,13 +257,13 @@ constexpr int kLinfitCounters = 8;  // device list lengths of one pass (the bit-
 int linfit_fast_supported(int mode, int n_frames, int64_t npix);
 int linfit_ml_supported(int mode, int n_frames, int64_t npix);
 
-// maps (args.reject_map set): the MAPS instantiations of the same kernels (stack_linfit_maps.hip).  Same classes, cascade,
+// Form::Maps: the MAPS instantiations of the same kernels (stack_linfit_maps.hip).  Same classes, cascade,
 // quotas and grids; every lane that holds a pixel's two clip counts leaves them in args.reject_map (stage 0 stores,
 // continuation stages add: stack_linfit_impl.hpp)
 hipError_t launch_stack_linfit_fast(const StackArgs &args, const FastArgs &fargs, const LinfitCascade *cascade,
-                                    hipStream_t stream, const char **name, hipEvent_t dominant_done, bool maps = false);
+                                    hipStream_t stream, const char **name, hipEvent_t dominant_done, Form form = Form::Plain);
 hipError_t launch_stack_linfit_ml(const StackArgs &args, const FastArgs &fargs, const LinfitCascade *cascade,
-                                  hipStream_t stream, const char **name, hipEvent_t dominant_done, bool maps = false);
+                                  hipStream_t stream, const char **name, hipEvent_t dominant_done, Form form = Form::Plain);
 
 // ---- stack_linfit_weighted.hip (the weighted linear-fit pass, include/nlstack_wlinfit.h: register-resident fit, one
 // pixel per lane, up to 128 frames; args.weights must be set; pixels it cannot decide go to fargs.fb_list, for
@@ -261,16 +277,11 @@ hipError_t launch_stack_linfit_weighted(const StackArgs &args, const FastArgs &f
 int decide_shallow_supported(int mode, int n_frames, int64_t npix);
 hipError_t launch_stack_sigma_decide_shallow(const StackArgs &args, hipStream_t stream, bool winsor, const char **name);
 // stack_clip_weighted.hip: one streaming read of the frames under the thresholds in args.bounds / args.nrounds, the
-// weights from args.weights; pixels without a complete record go to fargs.fb_list, for launch_stack_exact_follow
+// weights from args.weights; pixels without a complete record go to fargs.fb_list, for launch_stack_exact(Form::Follow)
 // one_round: the instantiations for which one recorded round is a complete record (the weighted MAD-sigma pass,
-// include/nlstack_wmad.h, behind launch_stack_mad_ml(record))
+// include/nlstack_wmad.h, behind launch_stack_mad_ml(Form::Record))
 hipError_t launch_stack_clip_weighted(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name,
                                       bool one_round = false);
-// stack_exact.hip: the column kernel's <follow> instantiations (NL_ST_SIGMA / NL_ST_WINSOR_SIGMA; one column: plan
-// with weighted = false; NL_ST_MAD_SIGMA, the weighted MAD-sigma pass: two columns; args.weights must be set), over the
-// tile or over args.list
-hipError_t launch_stack_exact_follow(int mode, const StackArgs &args, int lanes, int grid, size_t lds_bytes,
-                                     hipStream_t stream, const char **name);
 
 // ---- stack_mean.hip ----
 hipError_t launch_stack_mean(bool weighted, const StackArgs &args, hipStream_t stream,

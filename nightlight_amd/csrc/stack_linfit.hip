@@ -21,17 +21,19 @@ hipError_t launch_linfit_fast_maps(const StackArgs &args, const FastArgs &fargs,
                                    hipStream_t stream, const char **name, hipEvent_t dominant_done);
 
 hipError_t launch_stack_linfit_ml(const StackArgs &args, const FastArgs &fargs, const LinfitCascade *cascade,
-                                  hipStream_t stream, const char **name, hipEvent_t dominant_done, bool maps)
+                                  hipStream_t stream, const char **name, hipEvent_t dominant_done, Form form)
 {
-    return maps ? launch_linfit_ml_maps(args, fargs, cascade, stream, name, dominant_done)
-                : launch_linfit_ml<false>(args, fargs, cascade, stream, name, dominant_done);
+    if ((form != Form::Plain && form != Form::Maps) || !form_args_ok(form, args)) return hipErrorInvalidValue;
+    return form == Form::Maps ? launch_linfit_ml_maps(args, fargs, cascade, stream, name, dominant_done)
+                              : launch_linfit_ml<false>(args, fargs, cascade, stream, name, dominant_done);
 }
 
 hipError_t launch_stack_linfit_fast(const StackArgs &args, const FastArgs &fargs, const LinfitCascade *cascade,
-                                    hipStream_t stream, const char **name, hipEvent_t dominant_done, bool maps)
+                                    hipStream_t stream, const char **name, hipEvent_t dominant_done, Form form)
 {
-    return maps ? launch_linfit_fast_maps(args, fargs, cascade, stream, name, dominant_done)
-                : launch_linfit_fast<false>(args, fargs, cascade, stream, name, dominant_done);
+    if ((form != Form::Plain && form != Form::Maps) || !form_args_ok(form, args)) return hipErrorInvalidValue;
+    return form == Form::Maps ? launch_linfit_fast_maps(args, fargs, cascade, stream, name, dominant_done)
+                              : launch_linfit_fast<false>(args, fargs, cascade, stream, name, dominant_done);
 }
 
 }  // namespace nl

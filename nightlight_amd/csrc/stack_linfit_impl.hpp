@@ -786,16 +786,8 @@ constexpr char kLinfitFastName[] = "stack_linfit_fast_kernel";
 template <const char *BASE, int A, bool MAPS>
 const char *linfit_kernel_name()
 {
-    if constexpr (!MAPS) {
-        return kernel_name<BASE, A, false>();
-    } else {
-        static const std::string name = [] {
-            std::string s = kernel_name<BASE, A, false>();
-            s.pop_back();
-            return s + ", maps>";
-        }();
-        return name.c_str();
-    }
+    if constexpr (MAPS) return maps_kernel_name<BASE, A, false>();
+    else                return kernel_name<BASE, A, false>();
 }
 
 // cascade->state must hold LPP entries per listed pixel (2 up to 256 frames, else 4)
@@ -803,7 +795,6 @@ template <bool MAPS>
 hipError_t launch_linfit_ml(const StackArgs &args, const FastArgs &fargs, const LinfitCascade *cascade,
                             hipStream_t stream, const char **name, hipEvent_t dominant_done)
 {
-    if (MAPS && !args.reject_map) return hipErrorInvalidValue;
     Launcher L(stream);
     with_ml_lanes(args.n_frames, [&](auto C) {
         constexpr int LPP = decltype(C)::value;
@@ -818,7 +809,6 @@ template <bool MAPS>
 hipError_t launch_linfit_fast(const StackArgs &args, const FastArgs &fargs, const LinfitCascade *cascade,
                               hipStream_t stream, const char **name, hipEvent_t dominant_done)
 {
-    if (MAPS && !args.reject_map) return hipErrorInvalidValue;
     Launcher L(stream);
     with_class<8, 16, 32, 48, 64, 96, 128>(args.n_frames, [&](auto C) {
         constexpr int NS = decltype(C)::value;
