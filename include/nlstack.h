@@ -378,6 +378,12 @@ int nl_group_accumulate_finalize(nl_group_t *g, float weight_sum, float *out_hos
  * which is part of this interface. */
 #include "nlstack_wmad.h"
 
+/* ---- the median and MAD sigma of 513 ... 2048 frames on register-resident engines (an extension of depth, not of
+ * semantics: the results are those of nl_stack_run; everything else falls through to nl_stack_run's pass) ----
+ * nl_stack_run_deepstack, nl_stack_run_deepstack_async, nl_group_run_deepstack: declared in nlstack_deepstack.h, which
+ * is part of this interface. */
+#include "nlstack_deepstack.h"
+
 /* ---- stack of stacks (StackIncremental / Finalize, stack.go:924-944) ----
  * acc += result_of_last_pass * weight (first != 0: acc = result*weight),
  * on the device; finalize multiplies by 1/weight_sum and downloads. */

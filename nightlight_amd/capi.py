@@ -109,6 +109,10 @@ WCLIP_EXPORTS = ["nl_stack_run_clip_weighted", "nl_stack_run_clip_weighted_async
 # an extension
 WMAD_EXPORTS = ["nl_stack_run_mad_weighted", "nl_stack_run_mad_weighted_async", "nl_group_run_mad_weighted"]
 
+# every symbol include/nlstack_deepstack.h declares (likewise): the median and MAD sigma of 513 ... 2048 frames on
+# register-resident engines, an extension of depth
+DEEPSTACK_EXPORTS = ["nl_stack_run_deepstack", "nl_stack_run_deepstack_async", "nl_group_run_deepstack"]
+
 # every symbol include/nlstack_align.h declares (likewise)
 ALIGN_EXPORTS = ["nl_aligner_create", "nl_aligner_destroy", "nl_aligner_info", "nl_aligner_match",
                  "nl_aligner_match_stars"]
@@ -307,6 +311,9 @@ def open_library(path):
     L.nl_stack_run_mad_weighted.argtypes = _wlinfit_args
     L.nl_group_run_mad_weighted.argtypes = _wlinfit_args
     L.nl_stack_run_mad_weighted_async.argtypes = [vp, C.c_float, C.c_float, C.c_float]
+    L.nl_stack_run_deepstack.argtypes = _wclip_args
+    L.nl_group_run_deepstack.argtypes = _wclip_args
+    L.nl_stack_run_deepstack_async.argtypes = [vp, C.c_int, C.c_float, C.c_float, C.c_float]
     L.nl_stack_coverage.argtypes = [vp, _u16p]
     L.nl_group_coverage.argtypes = [vp, _u16p]
     L.nl_stack_last_coverage_ms.argtypes = [vp]

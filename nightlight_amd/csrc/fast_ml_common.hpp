@@ -2,7 +2,8 @@
 // share one pixel, 128 samples per lane): DPP quad permutes and reductions, the cross-lane
 // bitonic merge, rank lookups, and the gather that ends with lane r holding the global sorted
 // ranks [128r, 128r+128).  Used by stack_fast_ml.hip (sigma / winsor / median) and
-// stack_linfit.hip (linear fit beyond 128 frames).
+// stack_linfit.hip (linear fit beyond 128 frames).  The median and MAD-sigma kernels of 513 ... 2048 frames
+// (stack_fast_ml_deep.hip) run the same blocks on 8 or 16 lanes per pixel: half a DPP row or a whole one.
 #pragma once
 #include "fast_common.hpp"
 
@@ -21,27 +22,67 @@ __device__ __forceinline__ int dpp_i(int x)
 constexpr int kSwap1 = 0xB1;   // quad_perm [1,0,3,2]: partner = lane ^ 1
 constexpr int kSwap2 = 0x4E;   // quad_perm [2,3,0,1]: partner = lane ^ 2
 constexpr int kMirror = 0x1B;  // quad_perm [3,2,1,0]: partner = 3 - lane
+// 8 and 16 lanes per pixel: partners within a row of 16 lanes
+constexpr int kMirror8 = 0x141;   // row_half_mirror: partner = 7 - lane within 8
+constexpr int kMirror16 = 0x140;  // row_mirror: partner = 15 - lane within 16
+constexpr int kSwap8 = 0x128;     // row_ror:8: partner = lane ^ 8
+// lane ^ 4 is no DPP control of this ISA: ds_swizzle_b32 in bit-mask mode, swizzle(SWAP,4) (and 0x1F, or 0, xor 4) --
+// one instruction of the LDS crossbar (no LDS memory) where DPP would take two bank-masked row shifts
+constexpr int kSwap4 = -4;
+constexpr int kSwizzleSwap4 = 0x101F;
+
+// the value of lane CTRL's partner: a DPP move, or the swizzle for kSwap4
+template <int CTRL>
+__device__ __forceinline__ float partner_f(float x)
+{
+    if constexpr (CTRL == kSwap4) return __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(x), kSwizzleSwap4));
+    else return dpp_f<CTRL>(x);
+}
+
+// 8 and 16 lanes per pixel: the lane's role computed anew from the lane's index in its wave (the lane counts divide 64 and
+// the workgroup), three VALU operations where it is called.  The 128 samples and the networks' temporaries leave no
+// register to spare between two uses of a role that lie a whole sort apart, and a value that cannot be kept is not spilled.
+__device__ __forceinline__ int fresh_lane()
+{
+    int l;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+    return l;
+}
+template <int LPP>
+__device__ __forceinline__ int fresh_role()
+{
+    static_assert(LPP == 8 || LPP == 16, "lanes per pixel");
+    return fresh_lane() & (LPP - 1);
+}
 
 // sums / ors over the LPP lanes of a pixel; every lane gets the same bits
 template <int LPP>
 __device__ __forceinline__ float quad_sum(float x)
 {
+    static_assert(LPP == 2 || LPP == 4 || LPP == 8 || LPP == 16, "lanes per pixel");
     x = x + dpp_f<kSwap1>(x);
-    if constexpr (LPP == 4) x = x + dpp_f<kSwap2>(x);
+    if constexpr (LPP >= 4) x = x + dpp_f<kSwap2>(x);
+    // (all four lanes of a quad hold the same bits now, so any lane of the other quad is a partner; likewise at 16)
+    if constexpr (LPP >= 8) x = x + dpp_f<kMirror8>(x);
+    if constexpr (LPP == 16) x = x + dpp_f<kMirror16>(x);
     return x;
 }
 template <int LPP>
 __device__ __forceinline__ int quad_sum(int x)
 {
     x = x + dpp_i<kSwap1>(x);
-    if constexpr (LPP == 4) x = x + dpp_i<kSwap2>(x);
+    if constexpr (LPP >= 4) x = x + dpp_i<kSwap2>(x);
+    if constexpr (LPP >= 8) x = x + dpp_i<kMirror8>(x);
+    if constexpr (LPP == 16) x = x + dpp_i<kMirror16>(x);
     return x;
 }
 template <int LPP>
 __device__ __forceinline__ int quad_or(int x)
 {
     x = x | dpp_i<kSwap1>(x);
-    if constexpr (LPP == 4) x = x | dpp_i<kSwap2>(x);
+    if constexpr (LPP >= 4) x = x | dpp_i<kSwap2>(x);
+    if constexpr (LPP >= 8) x = x | dpp_i<kMirror8>(x);
+    if constexpr (LPP == 16) x = x | dpp_i<kMirror16>(x);
     return x;
 }
 
@@ -109,15 +150,15 @@ __device__ __forceinline__ void cross_stage(float (&v)[NS], bool keep_min)
         static_chunks<0, NS / 2, 16>([&](auto I) NL_INL {
             constexpr int i = decltype(I)::value;
             constexpr int j = NS - 1 - i;
-            const float pj = dpp_f<CTRL>(v[j]);
-            const float pi = dpp_f<CTRL>(v[i]);
+            const float pj = partner_f<CTRL>(v[j]);
+            const float pi = partner_f<CTRL>(v[i]);
             v[i] = __builtin_amdgcn_fmed3f(v[i], pj, side);
             v[j] = __builtin_amdgcn_fmed3f(v[j], pi, side);
         });
     } else {
         static_chunks<0, NS, 32>([&](auto I) NL_INL {
             constexpr int i = decltype(I)::value;
-            const float pv = dpp_f<CTRL>(v[i]);
+            const float pv = partner_f<CTRL>(v[i]);
             v[i] = __builtin_amdgcn_fmed3f(v[i], pv, side);
         });
     }
@@ -158,12 +199,14 @@ template <int LPP, int NS, bool ENDS_ONLY, int KEEP = 16, int CH = 32, int NSL =
 __device__ __forceinline__ void ml_sort_merge(float (&v)[NS], int role)
 {
     sort_network<NSL, true, NS>(v);
+    if constexpr (LPP >= 8) role = fresh_role<LPP>();
     // ---- merge the LPP sorted runs: lane r ends up with ranks [r*NS, r*NS+NS) ----
     // (zonal: the final half-cleaners only order the ends of each lane, see half_clean_ends)
     static_assert(kZone + kPadMax <= KEEP, "zones must lie inside the sorted ends");
     cross_stage<NS, kSwap1, true>(v, (role & 1) == 0);
     // the in-lane half-cleaners run as 2-/3-input operations too (FusedBitonic, sort_tables.inc: the
     // 0-1 analysis over bitonic inputs fuses 30 % of the instructions away)
+    static_assert(LPP <= 4 || (NS == 128 && !ENDS_ONLY), "8 and 16 lanes per pixel: full sort of 128 samples per lane");
     if constexpr (NS == 128 && (KEEP == 16 || KEEP == 32)) {
         if constexpr (ENDS_ONLY && LPP == 2) run_network<FusedBitonic<NS, KEEP>, NS>(v);
         else                             run_network<FusedBitonic<NS, 0>, NS>(v);
@@ -172,6 +215,29 @@ __device__ __forceinline__ void ml_sort_merge(float (&v)[NS], int role)
             cross_stage<NS, kSwap1, false>(v, (role & 1) == 0);
             if constexpr (ENDS_ONLY) run_network<FusedBitonic<NS, KEEP>, NS>(v);
             else                 run_network<FusedBitonic<NS, 0>, NS>(v);
+        }
+        if constexpr (LPP >= 8) {
+            // two runs of 2 lanes -> one of 4, as above; then two of 4 -> one of 8: mirrored against lane 7 - r, half-cleaners
+            // at lane distance 2 and 1, the in-lane network
+            // (the role anew behind every in-lane network: fresh_role)
+            role = fresh_role<LPP>();
+            cross_stage<NS, kMirror, true>(v, (role & 2) == 0);
+            cross_stage<NS, kSwap1, false>(v, (role & 1) == 0);
+            run_network<FusedBitonic<NS, 0>, NS>(v);
+            role = fresh_role<LPP>();
+            cross_stage<NS, kMirror8, true>(v, (role & 4) == 0);
+            cross_stage<NS, kSwap2, false>(v, (role & 2) == 0);
+            cross_stage<NS, kSwap1, false>(v, (role & 1) == 0);
+            run_network<FusedBitonic<NS, 0>, NS>(v);
+        }
+        if constexpr (LPP == 16) {
+            // two runs of 8 lanes -> one of 16: mirrored against lane 15 - r, then distances 4, 2 and 1
+            role = fresh_role<LPP>();
+            cross_stage<NS, kMirror16, true>(v, (role & 8) == 0);
+            cross_stage<NS, kSwap4, false>(v, (role & 4) == 0);
+            cross_stage<NS, kSwap2, false>(v, (role & 2) == 0);
+            cross_stage<NS, kSwap1, false>(v, (role & 1) == 0);
+            run_network<FusedBitonic<NS, 0>, NS>(v);
         }
     } else {
         if constexpr (ENDS_ONLY && LPP == 2) half_clean_ends<NS, NS / 2, KEEP, CH>(v);
@@ -206,6 +272,8 @@ __device__ __forceinline__ int ml_gather_raw(const float *frames, int64_t stride
                                              int role, float (&v)[NS])
 {
     static_assert(KPAD0 <= NLOAD && NLOAD <= NS, "positions");
+    // (8 / 16 lanes per pixel serve 513 ... 1024 / 1025 ... 2048 frames: more than LPP * NS / 2, so the defaults' invariant
+    // -- only positions k >= NS / 2 can lack a frame -- holds; LPP * frame_bytes < 2^31 is deep_ml_supported's bound)
     constexpr bool CLASS = !(KPAD0 == NS / 2 && NLOAD == NS);
     int nan_cnt = 0;
     int spad = NS - NLOAD;                                   // positions of this lane without a frame

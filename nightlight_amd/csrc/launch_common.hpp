@@ -39,6 +39,14 @@ decltype(auto) with_ml_lanes(int n_frames, F &&f)
     return f(std::integral_constant<int, 4>{});
 }
 
+// 513 ... 2048 frames (include/nlstack_deepstack.h): LPP = 8 lanes per pixel up to 8 kMlNS frames, else 16
+template <class F>
+decltype(auto) with_deep_lanes(int n_frames, F &&f)
+{
+    if (n_frames <= 8 * kMlNS) return f(std::integral_constant<int, 8>{});
+    return f(std::integral_constant<int, 16>{});
+}
+
 // workgroups of `block` threads over npix pixels at lpp lanes per pixel
 inline unsigned pixel_grid(int64_t npix, int lpp = 1, int block = 256)
 {

@@ -316,6 +316,15 @@ int nl_group_run_mad_weighted(nl_group_t *g, float sigma_low, float sigma_high, 
                      {out_host, clip_low, clip_high, nullptr, nullptr});
 }
 
+// the deep pass (include/nlstack_deepstack.h)
+int nl_group_run_deepstack(nl_group_t *g, int mode, float sigma_low, float sigma_high, float ref_loc,
+                           float *out_host, int64_t *clip_low, int64_t *clip_high)
+{
+    if (!g) return null_group();
+    return run_tiles(g, {PassKind::DeepStack, MapsTier::None, mode, sigma_low, sigma_high, ref_loc},
+                     {out_host, clip_low, clip_high, nullptr, nullptr});
+}
+
 // the maps passes, one tier (nl::MapsTier) each
 int nl_group_run_maps(nl_group_t *g, int mode, float sigma_low, float sigma_high, float ref_loc,
                       float *out_host, int64_t *clip_low, int64_t *clip_high, uint16_t *reject_low_host, uint16_t *reject_high_host)

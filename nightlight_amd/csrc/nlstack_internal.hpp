@@ -68,6 +68,8 @@ enum class PassKind {
     WeightedLinfit,       // nl_stack_run_linfit_weighted (include/nlstack_wlinfit.h): run_linfit_weighted; mode is NL_ST_LINEAR_FIT
     WeightedClip,         // nl_stack_run_clip_weighted (include/nlstack_wclip.h): run_clip_weighted
     WeightedMad,          // nl_stack_run_mad_weighted (include/nlstack_wmad.h): run_mad_weighted; mode is NL_ST_MAD_SIGMA
+    DeepStack,            // nl_stack_run_deepstack (include/nlstack_deepstack.h): the median / MAD sigma of 513 ... 2048 frames on
+                          // 8 / 16 lanes per pixel (run_deep_median, run_deep_mad); everything else is the Default pass
 };
 // One stack pass as every pass entry of the handle and of the group asks for it, and where its results go; any output
 // may be null, the two maps are read by a maps pass only.

@@ -205,6 +205,8 @@ enum class Engine {
     LinfitWeighted,       // PassKind::WeightedLinfit
     ClipWeighted,         // PassKind::WeightedClip
     MadWeighted,          // PassKind::WeightedMad
+    DeepMedian,           // PassKind::DeepStack, the median of 513 ... 2048 frames: 8 or 16 lanes per pixel
+    DeepMad,              // PassKind::DeepStack, MAD sigma of 513 ... 2048 frames: the same, + bit-exact replay of its list
 };
 
 // what the prologue of the pass decided, for the engine
@@ -250,6 +252,15 @@ static Engine select_engine(const nl_stack *h, nl::PassKind kind, int mode, bool
 {
     const bool fast = !h->force_exact;
     const int n = a.n_frames;
+    if (kind == PassKind::DeepStack) {
+        // The deep pass (include/nlstack_deepstack.h): its two engines where they hold -- the median, and MAD sigma on a handle
+        // with an exact list -- and the ladder of the default pass, unchanged, for everything else: another mode or depth,
+        // nl_stack_set_exact, a stride beyond the gather's 31-bit offsets.
+        const bool deep = fast && a.npix <= a.stride && nl::deep_ml_supported(mode, weighted, n, a.stride);
+        if (deep && mode == NL_ST_MEDIAN) return Engine::DeepMedian;
+        if (deep && mode == NL_ST_MAD_SIGMA && h->d_fb_list) return Engine::DeepMad;
+        kind = PassKind::Default;
+    }
     if (kind != PassKind::Default) {
         // Until these kinds had engines of their own here, the pass asked the ladder below, dispatched past its answer and
         // kept one thing of it: whether it was SigmaFast, which turns on hint loading, the fused protocol and its single
@@ -783,6 +794,26 @@ static int run_mad_weighted(nl_stack *h, const PassSetup &p, PassFacts *facts)
     return end_on_columns(h, p, a, listed, facts);
 }
 
+// The deep pass (include/nlstack_deepstack.h, an extension of depth): the median and MAD sigma of 513 ... 2048 active frames
+// on the kernels of the 129 ... 512-frame engines with 8 or 16 lanes per pixel (stack_fast_ml_deep.hip).  Both rest on order
+// statistics alone: the median is bit-exact as Engine::MedianMultiLane's; MAD sigma runs as Engine::Listed's -- its kernel
+// the dominant one of a plain-protocol pass, the pixels without a finite median on the exact list for the column kernel,
+// then the reduction of the sharded clip counters.  No hints read or left, never the fused protocol.
+static int run_deep_median(nl_stack *h, const PassSetup &p)
+{
+    NL_HIP(nl::launch_stack_median_ml_deep(p.a, h->stream, &h->last_kernel));
+    NL_HIP(hipEventRecord(h->ev_dom1, h->stream));
+    return NL_OK;
+}
+
+static int run_deep_mad(nl_stack *h, const PassSetup &p, PassFacts *facts)
+{
+    NL_HIP(nl::launch_stack_mad_ml_deep(p.a, list_args(h, true, false), h->stream, &h->last_kernel));
+    NL_HIP(hipEventRecord(h->ev_dom1, h->stream));
+    facts->used_fast = true;
+    return end_on_columns(h, p, p.a, true, facts);
+}
+
 // A pass that fails half-way (a launch or an event call after the first kernel) must not hand control back with work in
 // flight on the handle's streams and its bookkeeping half-updated: whatever was enqueued is waited for, the scratch
 // sets count as dirty, no list lengths or hints are taken from the broken pass.  The error of the failing call is kept.
@@ -926,6 +957,8 @@ static int run_async_impl(nl_stack_t *h, const nl::PassRequest &req)
     case Engine::LinfitWeighted:  rc = run_linfit_weighted(h, p, &facts); break;
     case Engine::ClipWeighted:    rc = run_clip_weighted(h, p, &facts); break;
     case Engine::MadWeighted:     rc = run_mad_weighted(h, p, &facts); break;
+    case Engine::DeepMedian:      rc = run_deep_median(h, p); break;
+    case Engine::DeepMad:         rc = run_deep_mad(h, p, &facts); break;
     }
     if (rc != NL_OK) return rc;
     NL_HIP(hipEventRecord(h->ev_stop, h->stream));
@@ -1067,6 +1100,18 @@ int nl_stack_run_mad_weighted(nl_stack_t *h, float sigma_low, float sigma_high, 
 {
     return run_pass(h, {PassKind::WeightedMad, MapsTier::None, NL_ST_MAD_SIGMA, sigma_low, sigma_high, ref_loc},
                     {out_host, clip_low, clip_high, nullptr, nullptr});
+}
+
+// the deep pass (include/nlstack_deepstack.h)
+int nl_stack_run_deepstack_async(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc)
+{
+    return nl::stack_start(h, {PassKind::DeepStack, MapsTier::None, mode, sigma_low, sigma_high, ref_loc});
+}
+
+int nl_stack_run_deepstack(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc,
+                           float *out_host, int64_t *clip_low, int64_t *clip_high)
+{
+    return run_pass(h, {PassKind::DeepStack, MapsTier::None, mode, sigma_low, sigma_high, ref_loc}, {out_host, clip_low, clip_high, nullptr, nullptr});
 }
 
 // the maps passes (include/nlstack_maps.h, nlstack_fastmaps.h, nlstack_residentmaps.h, nlstack_deepmaps.h, nlstack_fullmaps.h):

@@ -219,6 +219,12 @@ hipError_t launch_stack_mad_ml(const StackArgs &args, const FastArgs &fargs, hip
                                Form form = Form::Plain);
 unsigned ml_generic_grid(int n_frames, unsigned gen_hint);      // workgroups of launch_stack_sigma_mlg behind launch_stack_sigma_mlz
 
+// the same two kernels on 8 / 16 lanes per pixel: the median and unweighted MAD sigma of 513 ... 2048 frames, plain form
+// (stack_fast_ml_deep.hip; include/nlstack_deepstack.h).  `stride`: floats between frames, LPP * stride * 4 < 2^31
+int deep_ml_supported(int mode, bool weighted, int n_frames, int64_t stride);
+hipError_t launch_stack_median_ml_deep(const StackArgs &args, hipStream_t stream, const char **name);
+hipError_t launch_stack_mad_ml_deep(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name);
+
 // ---- stack_exact_coop.hip (bit-exact sigma replay, one wave per pixel) ----
 int coop_supported(int mode, bool weighted, int n_frames);
 hipError_t launch_stack_median_coop(const StackArgs &args, int grid, hipStream_t stream, const char **name);

@@ -259,6 +259,20 @@ class StackHandle:
         capi.check(self._lib.nl_stack_run_mad_weighted_async(self._h, C.c_float(sigma_low), C.c_float(sigma_high),
                                                              C.c_float(ref_loc)))
 
+    def run_deepstack(self, mode, sigma_low=2.75, sigma_high=2.75, ref_loc=0.0, out=None, fetch=True):
+        """run for deep stacks (include/nlstack_deepstack.h; an extension of depth, not of semantics): the median and
+        unweighted MAD sigma of 513 ... 2048 active frames on register-resident kernels with 8 or 16 lanes per pixel
+        -- the median bit-equal to run(ST_MEDIAN), MAD sigma with run(ST_MAD_SIGMA)'s counters and the mean of the
+        same survivors -- and run's own pass for every other mode and depth.  Arguments and return value are those
+        of run."""
+        return _run_counted(self._lib.nl_stack_run_deepstack, self._h, (int(mode),) + _sigmas(sigma_low, sigma_high, ref_loc),
+                            self._result_array(out, fetch))
+
+    def run_deepstack_async(self, mode, sigma_low=2.75, sigma_high=2.75, ref_loc=0.0):
+        """run_deepstack without the wait: finish() completes it."""
+        capi.check(self._lib.nl_stack_run_deepstack_async(self._h, int(mode), C.c_float(sigma_low), C.c_float(sigma_high),
+                                                          C.c_float(ref_loc)))
+
     def coverage(self, out=None):
         """Whole-image uint16 map of how many active frames have a sample (not NaN) at each pixel: the tile's rows
         of `out` (made here, zero outside the tile, if not given).  No pass: the last result stays."""
@@ -778,6 +792,11 @@ class StackGroup:
     def run_mad_weighted(self, sigma_low=2.75, sigma_high=2.75, ref_loc=0.0, download=True):
         """StackHandle.run_mad_weighted over the tiles: (result or None, clip_low, clip_high)."""
         return _run_counted(self._lib.nl_group_run_mad_weighted, self._g, _sigmas(sigma_low, sigma_high, ref_loc),
+                            self._result_array(download))
+
+    def run_deepstack(self, mode, sigma_low=2.75, sigma_high=2.75, ref_loc=0.0, download=True):
+        """StackHandle.run_deepstack over the tiles: (result or None, clip_low, clip_high)."""
+        return _run_counted(self._lib.nl_group_run_deepstack, self._g, (int(mode),) + _sigmas(sigma_low, sigma_high, ref_loc),
                             self._result_array(download))
 
     def coverage(self):
