@@ -383,6 +383,8 @@ int nl_group_accumulate_finalize(nl_group_t *g, float weight_sum, float *out_hos
  * nl_stack_run_deepstack, nl_stack_run_deepstack_async, nl_group_run_deepstack: declared in nlstack_deepstack.h, which
  * is part of this interface. */
 #include "nlstack_deepstack.h"
+#include "nlstack_deepstackmaps.h"
+#include "nlstack_deepwmad.h"
 
 /* ---- stack of stacks (StackIncremental / Finalize, stack.go:924-944) ----
  * acc += result_of_last_pass * weight (first != 0: acc = result*weight),

@@ -113,6 +113,15 @@ WMAD_EXPORTS = ["nl_stack_run_mad_weighted", "nl_stack_run_mad_weighted_async", 
 # register-resident engines, an extension of depth
 DEEPSTACK_EXPORTS = ["nl_stack_run_deepstack", "nl_stack_run_deepstack_async", "nl_group_run_deepstack"]
 
+# every symbol include/nlstack_deepstackmaps.h declares (likewise): the maps pass with the engines of stacks beyond 512
+# frames as well -- MAD sigma and the median on 8 / 16 lanes per pixel, sigma / winsorized clipping on the wave-per-pixel replay
+DEEPSTACKMAPS_EXPORTS = ["nl_stack_run_maps_deepstack", "nl_group_run_maps_deepstack"]
+
+# every symbol include/nlstack_deepwmad.h declares (likewise): weighted MAD-sigma stacking of 513 ... 2048 frames on the
+# 8- / 16-lane engine, an extension of depth
+DEEPWMAD_EXPORTS = ["nl_stack_run_mad_weighted_deepstack", "nl_stack_run_mad_weighted_deepstack_async",
+                    "nl_group_run_mad_weighted_deepstack"]
+
 # every symbol include/nlstack_align.h declares (likewise)
 ALIGN_EXPORTS = ["nl_aligner_create", "nl_aligner_destroy", "nl_aligner_info", "nl_aligner_match",
                  "nl_aligner_match_stars"]
@@ -297,7 +306,7 @@ def open_library(path):
     L.nl_group_last_mode.argtypes = [vp]
     _u16p = C.POINTER(C.c_uint16)
     _maps_args = [vp, C.c_int, C.c_float, C.c_float, C.c_float, _f32p, _i64p, _i64p, _u16p, _u16p]
-    for suffix in ("", "_fast", "_resident", "_deep", "_full"):
+    for suffix in ("", "_fast", "_resident", "_deep", "_full", "_deepstack"):
         getattr(L, "nl_stack_run_maps" + suffix).argtypes = _maps_args
         getattr(L, "nl_group_run_maps" + suffix).argtypes = _maps_args
     _wlinfit_args = [vp, C.c_float, C.c_float, C.c_float, _f32p, _i64p, _i64p]
@@ -314,6 +323,9 @@ def open_library(path):
     L.nl_stack_run_deepstack.argtypes = _wclip_args
     L.nl_group_run_deepstack.argtypes = _wclip_args
     L.nl_stack_run_deepstack_async.argtypes = [vp, C.c_int, C.c_float, C.c_float, C.c_float]
+    L.nl_stack_run_mad_weighted_deepstack.argtypes = _wlinfit_args
+    L.nl_group_run_mad_weighted_deepstack.argtypes = _wlinfit_args
+    L.nl_stack_run_mad_weighted_deepstack_async.argtypes = [vp, C.c_float, C.c_float, C.c_float]
     L.nl_stack_coverage.argtypes = [vp, _u16p]
     L.nl_group_coverage.argtypes = [vp, _u16p]
     L.nl_stack_last_coverage_ms.argtypes = [vp]

@@ -325,6 +325,15 @@ int nl_group_run_deepstack(nl_group_t *g, int mode, float sigma_low, float sigma
                      {out_host, clip_low, clip_high, nullptr, nullptr});
 }
 
+// the deep weighted MAD-sigma pass (include/nlstack_deepwmad.h)
+int nl_group_run_mad_weighted_deepstack(nl_group_t *g, float sigma_low, float sigma_high, float ref_loc,
+                                        float *out_host, int64_t *clip_low, int64_t *clip_high)
+{
+    if (!g) return null_group();
+    return run_tiles(g, {PassKind::DeepWeightedMad, MapsTier::None, NL_ST_MAD_SIGMA, sigma_low, sigma_high, ref_loc},
+                     {out_host, clip_low, clip_high, nullptr, nullptr});
+}
+
 // the maps passes, one tier (nl::MapsTier) each
 int nl_group_run_maps(nl_group_t *g, int mode, float sigma_low, float sigma_high, float ref_loc,
                       float *out_host, int64_t *clip_low, int64_t *clip_high, uint16_t *reject_low_host, uint16_t *reject_high_host)
@@ -363,6 +372,14 @@ int nl_group_run_maps_full(nl_group_t *g, int mode, float sigma_low, float sigma
 {
     if (!g) return null_group();
     return run_tiles(g, {PassKind::Default, MapsTier::Full, mode, sigma_low, sigma_high, ref_loc},
+                     {out_host, clip_low, clip_high, reject_low_host, reject_high_host});
+}
+
+int nl_group_run_maps_deepstack(nl_group_t *g, int mode, float sigma_low, float sigma_high, float ref_loc,
+                                float *out_host, int64_t *clip_low, int64_t *clip_high, uint16_t *reject_low_host, uint16_t *reject_high_host)
+{
+    if (!g) return null_group();
+    return run_tiles(g, {PassKind::Default, MapsTier::DeepStack, mode, sigma_low, sigma_high, ref_loc},
                      {out_host, clip_low, clip_high, reject_low_host, reject_high_host});
 }
 

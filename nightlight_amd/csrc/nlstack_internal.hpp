@@ -61,6 +61,8 @@ enum class MapsTier {
     Resident,             // nl_stack_run_maps_resident (include/nlstack_residentmaps.h): and the linear fit's kernels and cascade
     Deep,                 // nl_stack_run_maps_deep (include/nlstack_deepmaps.h): and the LDS-column sigma / winsorized kernels, 129 ... 512 frames
     Full,                 // nl_stack_run_maps_full (include/nlstack_fullmaps.h): and the MAD-sigma kernels, 1 ... 512 frames; the median on its default kernels
+    DeepStack,            // nl_stack_run_maps_deepstack (include/nlstack_deepstackmaps.h): and MAD sigma / the median of 513 ... 2048 frames on
+                          // 8 / 16 lanes per pixel; sigma / winsorized clipping beyond 512 frames on the wave-per-pixel replay
 };
 // the kinds of pass: select_engine (nlstack_pass.hip) gives every kind but Default an engine of its own
 enum class PassKind {
@@ -70,6 +72,8 @@ enum class PassKind {
     WeightedMad,          // nl_stack_run_mad_weighted (include/nlstack_wmad.h): run_mad_weighted; mode is NL_ST_MAD_SIGMA
     DeepStack,            // nl_stack_run_deepstack (include/nlstack_deepstack.h): the median / MAD sigma of 513 ... 2048 frames on
                           // 8 / 16 lanes per pixel (run_deep_median, run_deep_mad); everything else is the Default pass
+    DeepWeightedMad,      // nl_stack_run_mad_weighted_deepstack (include/nlstack_deepwmad.h): WeightedMad of 513 ... 2048 frames on
+                          // run_deep_mad_weighted; everything else is the WeightedMad pass
 };
 // One stack pass as every pass entry of the handle and of the group asks for it, and where its results go; any output
 // may be null, the two maps are read by a maps pass only.

@@ -183,7 +183,10 @@ static bool fused_protocol_on()
 //   Resident  (nl_stack_run_maps_resident)  and run_listed's linear fit, on its own kernels and cascade;
 //   Deep      (nl_stack_run_maps_deep)      and run_sigma_maps on the LDS-column sigma / winsorized kernels, 129 ... 512 frames;
 //   Full      (nl_stack_run_maps_full)      and run_listed's MAD sigma on its own kernels, 1 ... 512 frames; the median on its
-//                                           default kernels with the maps zeroed.
+//                                           default kernels with the maps zeroed;
+//   DeepStack (nl_stack_run_maps_deepstack) and, beyond 512 frames: run_deep_mad's MAD sigma and run_deep_median's median on 8 / 16
+//                                           lanes per pixel (513 ... 2048 frames), run_dense_replay's sigma / winsorized clipping on
+//                                           the wave-per-pixel replay over the whole tile.
 // What no engine of its tier takes runs on the column kernel.  On every tier the pass takes part in none of what default
 // passes remember from one another: it takes and leaves no list-length hints, never runs the fused protocol, and leaves the
 // scratch sets as any other plain-protocol pass does; the linear fit drops the handle's weights as in every other
@@ -207,6 +210,7 @@ enum class Engine {
     MadWeighted,          // PassKind::WeightedMad
     DeepMedian,           // PassKind::DeepStack, the median of 513 ... 2048 frames: 8 or 16 lanes per pixel
     DeepMad,              // PassKind::DeepStack, MAD sigma of 513 ... 2048 frames: the same, + bit-exact replay of its list
+    DeepMadWeighted,      // PassKind::DeepWeightedMad: the same kernel record-only, the streaming kernel of the weighted clip pass
 };
 
 // what the prologue of the pass decided, for the engine
@@ -220,6 +224,13 @@ struct PassSetup {
                               // MAD-sigma passes (a.weights is set), else Plain
     bool maps() const { return form == nl::Form::Maps; }
 };
+
+// the depth conditions of the 8- / 16-lane engines (PassKind::DeepStack, PassKind::DeepWeightedMad, MapsTier::DeepStack): not forced exact, a tile
+// within its stride, and -- with `weighted` = false: the kernels are the unweighted ones -- deep_ml_supported
+static bool deep_conditions(const nl_stack *h, int mode, bool weighted, const nl::StackArgs &a)
+{
+    return !h->force_exact && a.npix <= a.stride && nl::deep_ml_supported(mode, weighted, a.n_frames, a.stride);
+}
 
 // The ladder of a maps pass (a.reject_map set, never the mean): the first rung whose condition holds; what no engine of the
 // tier takes runs on the one engine that carries the per-pixel counts out of every mode.  Default passes never come here.
@@ -243,6 +254,13 @@ static Engine maps_engine(const nl_stack *h, int mode, bool weighted, const nl::
         return Engine::MedianRegisters;
     if (tier >= nl::MapsTier::Full && fast && mode == NL_ST_MEDIAN && nl::fast_ml_supported(mode, weighted, n, a.npix))
         return Engine::MedianMultiLane;
+    // beyond 512 frames (include/nlstack_deepstackmaps.h): the engines of the deep pass, and the replay nl_stack_run runs there
+    if (tier >= nl::MapsTier::DeepStack && !weighted && deep_conditions(h, mode, false, a)) {
+        if (mode == NL_ST_MAD_SIGMA && h->d_fb_list) return Engine::DeepMad;
+        if (mode == NL_ST_MEDIAN) return Engine::DeepMedian;
+    }
+    if (tier >= nl::MapsTier::DeepStack && fast && clip && !weighted && n > 512 && nl::coop_supported(mode, false, n))
+        return Engine::DenseReplay;
     return Engine::ExactColumns;
 }
 
@@ -256,10 +274,18 @@ static Engine select_engine(const nl_stack *h, nl::PassKind kind, int mode, bool
         // The deep pass (include/nlstack_deepstack.h): its two engines where they hold -- the median, and MAD sigma on a handle
         // with an exact list -- and the ladder of the default pass, unchanged, for everything else: another mode or depth,
         // nl_stack_set_exact, a stride beyond the gather's 31-bit offsets.
-        const bool deep = fast && a.npix <= a.stride && nl::deep_ml_supported(mode, weighted, n, a.stride);
+        const bool deep = deep_conditions(h, mode, weighted, a);
         if (deep && mode == NL_ST_MEDIAN) return Engine::DeepMedian;
         if (deep && mode == NL_ST_MAD_SIGMA && h->d_fb_list) return Engine::DeepMad;
         kind = PassKind::Default;
+    }
+    if (kind == PassKind::DeepWeightedMad) {
+        // The deep weighted MAD-sigma pass (include/nlstack_deepwmad.h): its engine where the depth conditions hold on a handle
+        // with an exact list (the engine itself falls back to run_mad_weighted where the threshold record cannot be had),
+        // and PassKind::WeightedMad's, unchanged, for everything else.
+        // (the streaming kernel's exact list holds 32-bit pixel indices: launch_stack_clip_weighted's bound)
+        if (deep_conditions(h, mode, false, a) && h->d_fb_list && a.npix < nl::kFastMaxPixels) return Engine::DeepMadWeighted;
+        kind = PassKind::WeightedMad;
     }
     if (kind != PassKind::Default) {
         // Until these kinds had engines of their own here, the pass asked the ladder below, dispatched past its answer and
@@ -687,8 +713,9 @@ static int run_dense_replay(nl_stack *h, const PassSetup &p, PassFacts *facts)
     const int64_t items = a.npix / per_item;
     const int64_t most = 262144;
     const int g = dense_grid(items, most, h->width, per_item);
+    // (a maps pass, MapsTier::DeepStack: unweighted sigma / winsorized clipping beyond 512 frames, the MAPS form of the replay)
     if (p.mode == NL_ST_MEDIAN) NL_HIP(nl::launch_stack_median_coop(a, (int)g, h->stream, &h->last_kernel));
-    else                        NL_HIP(nl::launch_stack_sigma_coop(p.mode, a, (int)g, h->stream, &h->last_kernel));
+    else                        NL_HIP(nl::launch_stack_sigma_coop(p.mode, a, (int)g, h->stream, &h->last_kernel, p.form));
     NL_HIP(hipEventRecord(h->ev_dom1, h->stream));
     NL_HIP(reduce_clip_slots(h));
     facts->has_counters = p.mode != NL_ST_MEDIAN;
@@ -799,8 +826,12 @@ static int run_mad_weighted(nl_stack *h, const PassSetup &p, PassFacts *facts)
 // statistics alone: the median is bit-exact as Engine::MedianMultiLane's; MAD sigma runs as Engine::Listed's -- its kernel
 // the dominant one of a plain-protocol pass, the pixels without a finite median on the exact list for the column kernel,
 // then the reduction of the sharded clip counters.  No hints read or left, never the fused protocol.
+// A maps pass (MapsTier::DeepStack, include/nlstack_deepstackmaps.h) runs both: the median behind a memset of the map, as
+// run_median; MAD sigma in Form::Maps -- the lane that stores a pixel's result stores its word, and the column kernel's
+// <mad,maps> replay writes the words of the exact list, as run_listed does for the Full tier.
 static int run_deep_median(nl_stack *h, const PassSetup &p)
 {
+    if (p.maps()) NL_HIP(hipMemsetAsync(p.a.reject_map, 0, (size_t)p.a.npix * sizeof(unsigned), h->stream));
     NL_HIP(nl::launch_stack_median_ml_deep(p.a, h->stream, &h->last_kernel));
     NL_HIP(hipEventRecord(h->ev_dom1, h->stream));
     return NL_OK;
@@ -808,10 +839,29 @@ static int run_deep_median(nl_stack *h, const PassSetup &p)
 
 static int run_deep_mad(nl_stack *h, const PassSetup &p, PassFacts *facts)
 {
-    NL_HIP(nl::launch_stack_mad_ml_deep(p.a, list_args(h, true, false), h->stream, &h->last_kernel));
+    NL_HIP(nl::launch_stack_mad_ml_deep(p.a, list_args(h, true, false), h->stream, &h->last_kernel, p.form));
     NL_HIP(hipEventRecord(h->ev_dom1, h->stream));
     facts->used_fast = true;
     return end_on_columns(h, p, p.a, true, facts);
+}
+
+// The deep weighted MAD-sigma pass (include/nlstack_deepwmad.h): run_mad_weighted's 129 ... 512 branch with the 8- / 16-lane
+// kernel -- record-only, it leaves (lo, hi) per pixel in h->d_bounds; the streaming kernel of the weighted clip pass reads
+// the frames once under them and hands pixels without a finite median or without a sample to the exact list; then the
+// column kernel's <mad,follow> instantiation over that list and the reduction.  Where the threshold record cannot be had
+// (ensure_bounds) the pass is run_mad_weighted's.
+static int run_deep_mad_weighted(nl_stack *h, const PassSetup &p, PassFacts *facts)
+{
+    nl::StackArgs a = p.a;
+    if (!bounds_on_record(h, a)) return run_mad_weighted(h, p, facts);
+    const char *ignored = "";
+    NL_HIP(nl::launch_stack_mad_ml_deep(a, nl::FastArgs{}, h->stream, &ignored, nl::Form::Record));
+    NL_HIP(nl::launch_stack_clip_weighted(a, list_args(h, true, false), h->stream, &h->last_kernel, true));
+    a.bounds = nullptr;
+    a.nrounds = nullptr;
+    NL_HIP(hipEventRecord(h->ev_dom1, h->stream));
+    facts->used_fast = true;
+    return end_on_columns(h, p, a, true, facts);
 }
 
 // A pass that fails half-way (a launch or an event call after the first kernel) must not hand control back with work in
@@ -847,10 +897,11 @@ static int run_async_impl(nl_stack_t *h, const nl::PassRequest &req)
     const float sigma_low = req.sigma_low, sigma_high = req.sigma_high, ref_loc = req.ref_loc;
     int mode = req.mode;
     const bool maps = tier != nl::MapsTier::None, wlinfit = req.kind == PassKind::WeightedLinfit, wclip = req.kind == PassKind::WeightedClip;
-    const bool wmad = req.kind == PassKind::WeightedMad;
+    const bool wmad = req.kind == PassKind::WeightedMad || req.kind == PassKind::DeepWeightedMad;
     // the extension passes take their weights from the handle: the entry's name, and where the unweighted pass is
     static const struct { PassKind kind; const char *entry, *unweighted; } kNeedWeights[] = {
         {PassKind::WeightedMad, "run_mad_weighted", "the unweighted pass is nl_stack_run with NL_ST_MAD_SIGMA"},
+        {PassKind::DeepWeightedMad, "run_mad_weighted", "the unweighted pass is nl_stack_run with NL_ST_MAD_SIGMA"},
         {PassKind::WeightedClip, "run_clip_weighted", "the unweighted pass is nl_stack_run"},
         {PassKind::WeightedLinfit, "run_linfit_weighted", "the unweighted fit is nl_stack_run with NL_ST_LINEAR_FIT"},
     };
@@ -959,6 +1010,7 @@ static int run_async_impl(nl_stack_t *h, const nl::PassRequest &req)
     case Engine::MadWeighted:     rc = run_mad_weighted(h, p, &facts); break;
     case Engine::DeepMedian:      rc = run_deep_median(h, p); break;
     case Engine::DeepMad:         rc = run_deep_mad(h, p, &facts); break;
+    case Engine::DeepMadWeighted: rc = run_deep_mad_weighted(h, p, &facts); break;
     }
     if (rc != NL_OK) return rc;
     NL_HIP(hipEventRecord(h->ev_stop, h->stream));
@@ -1114,8 +1166,21 @@ int nl_stack_run_deepstack(nl_stack_t *h, int mode, float sigma_low, float sigma
     return run_pass(h, {PassKind::DeepStack, MapsTier::None, mode, sigma_low, sigma_high, ref_loc}, {out_host, clip_low, clip_high, nullptr, nullptr});
 }
 
-// the maps passes (include/nlstack_maps.h, nlstack_fastmaps.h, nlstack_residentmaps.h, nlstack_deepmaps.h, nlstack_fullmaps.h):
-// one tier each
+// the deep weighted MAD-sigma pass (include/nlstack_deepwmad.h)
+int nl_stack_run_mad_weighted_deepstack_async(nl_stack_t *h, float sigma_low, float sigma_high, float ref_loc)
+{
+    return nl::stack_start(h, {PassKind::DeepWeightedMad, MapsTier::None, NL_ST_MAD_SIGMA, sigma_low, sigma_high, ref_loc});
+}
+
+int nl_stack_run_mad_weighted_deepstack(nl_stack_t *h, float sigma_low, float sigma_high, float ref_loc,
+                                        float *out_host, int64_t *clip_low, int64_t *clip_high)
+{
+    return run_pass(h, {PassKind::DeepWeightedMad, MapsTier::None, NL_ST_MAD_SIGMA, sigma_low, sigma_high, ref_loc},
+                    {out_host, clip_low, clip_high, nullptr, nullptr});
+}
+
+// the maps passes (include/nlstack_maps.h, nlstack_fastmaps.h, nlstack_residentmaps.h, nlstack_deepmaps.h, nlstack_fullmaps.h,
+// nlstack_deepstackmaps.h): one tier each
 int nl_stack_run_maps(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc,
                       float *out_host, int64_t *clip_low, int64_t *clip_high, uint16_t *reject_low_host, uint16_t *reject_high_host)
 {
@@ -1148,6 +1213,13 @@ int nl_stack_run_maps_full(nl_stack_t *h, int mode, float sigma_low, float sigma
                            float *out_host, int64_t *clip_low, int64_t *clip_high, uint16_t *reject_low_host, uint16_t *reject_high_host)
 {
     return run_pass(h, {PassKind::Default, MapsTier::Full, mode, sigma_low, sigma_high, ref_loc},
+                    {out_host, clip_low, clip_high, reject_low_host, reject_high_host});
+}
+
+int nl_stack_run_maps_deepstack(nl_stack_t *h, int mode, float sigma_low, float sigma_high, float ref_loc,
+                                float *out_host, int64_t *clip_low, int64_t *clip_high, uint16_t *reject_low_host, uint16_t *reject_high_host)
+{
+    return run_pass(h, {PassKind::Default, MapsTier::DeepStack, mode, sigma_low, sigma_high, ref_loc},
                     {out_host, clip_low, clip_high, reject_low_host, reject_high_host});
 }
 

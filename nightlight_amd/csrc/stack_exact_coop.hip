@@ -40,11 +40,11 @@ __device__ unsigned long long nl_probe_cycles[8];
 #include "launch_common.hpp"
 namespace nl {
 
-template <bool WINSOR, bool W, int GROUP, int PF = 2>
+template <bool WINSOR, bool W, int GROUP, int PF = 2, bool MAPS = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PF <= 2 ? 8 : 5, 8))) void stack_sigma_coop_kernel(StackArgs p)
 {
     extern __shared__ float a[];
-    coop_body<WINSOR, W, GROUP, PF>(p, a, blockIdx.x, gridDim.x);
+    coop_body<WINSOR, W, GROUP, PF, MAPS>(p, a, blockIdx.x, gridDim.x);
 }
 
 // StackMedian (stack.go:274-303) beyond the register kernels' 512 frames: gather and the
@@ -114,8 +114,29 @@ static void launch_coop(Launcher &L, const StackArgs &args, int grid, size_t lds
     L(stack_sigma_coop_kernel<WINSOR, W, GROUP, PF>, grid, 64, lds, args);
 }
 
-hipError_t launch_stack_sigma_coop(int mode, const StackArgs &args, int grid, hipStream_t stream, const char **name)
+// Form::Maps (include/nlstack_deepstackmaps.h): {sigma, winsorized} x {1, 4 pixels per work item}, two chunks in registers
+// (the PF = 8 variants serve up to 512 frames, where the maps passes have engines of their own)
+template <bool WINSOR, int GROUP>
+static void launch_coop_maps(Launcher &L, const StackArgs &args, int grid, size_t lds, const char **name)
 {
+    *name = maps_kernel_name<kSigmaCoopName, WINSOR, false, GROUP, 2>();
+    L(stack_sigma_coop_kernel<WINSOR, false, GROUP, 2, true>, grid, 64, lds, args);
+}
+
+hipError_t launch_stack_sigma_coop(int mode, const StackArgs &args, int grid, hipStream_t stream, const char **name, Form form)
+{
+    if (form == Form::Follow || form == Form::Record || !form_args_ok(form, args)) return hipErrorInvalidValue;
+    if (form == Form::Maps) {
+        if (args.weights || args.list) return hipErrorInvalidValue;      // the whole-tile, unweighted replay only
+        const size_t lds = (size_t)args.n_frames * sizeof(float) * coop_columns(mode, false);
+        const bool group4 = coop_group(args) == 4;
+        Launcher L(stream);
+        with_bool(mode == NL_ST_WINSOR_SIGMA, [&](auto WS) {
+            if (group4) launch_coop_maps<decltype(WS)::value, 4>(L, args, grid, lds, name);
+            else        launch_coop_maps<decltype(WS)::value, 1>(L, args, grid, lds, name);
+        });
+        return L.err;
+    }
     // (measured, profiles/r05_wsigma512_pf8_*, r05_wwinsor512_*: with PF = 8 a weighted sigma replay of 512 frames fetches
     // 1.45 x the algorithmic bytes instead of 13.7 x and takes 35.8 instead of 34.6 ms per 1024 x 4096 pixels -- it is bound by
     // the issue of the partition passes, not by its fetches; the winsorized replay, whose loops wait on memory between

@@ -356,7 +356,11 @@ __device__ float coop_select_median(float *a, unsigned short *lpos, unsigned sho
 // winsorized replays only, see launch_stack_sigma_coop.
 // The kernel's body, workgroup `block` of `nblocks` with its LDS columns at `a`: stack_sigma_coop_kernel (stack_exact_coop.hip) is the whole grid;
 // stack_tail_fused.hip runs it in the upper part of a grid whose lower workgroups are the generic pass.
-template <bool WINSOR, bool W, int GROUP, int PF = 2>
+// MAPS (the deep-stack maps pass, include/nlstack_deepstackmaps.h: the whole-tile, unweighted replay only): lane 0 stores the
+// pixel's two clip counts, p.reject_map[pix] = low | high << 16, beside its result -- the pixel's own increments of the
+// wave's running counts; a pixel without a sample gets ref_loc and a zero word; with GROUP = 4 each of the four pixels
+// of a work item gets its own word.
+template <bool WINSOR, bool W, int GROUP, int PF = 2, bool MAPS = false>
 __device__ __forceinline__ void coop_body(const StackArgs &p, float *a, const unsigned block, const unsigned nblocks)
 {
     float *wz = a + p.n_frames;                   // winsorized copy (WINSOR only)
@@ -397,6 +401,7 @@ __device__ __forceinline__ void coop_body(const StackArgs &p, float *a, const un
     // The first 128 frames of a pixel are gathered up front (two loads in flight), its decided rounds and their
     // bounds come with them (lane r holds round r), the weights of those frames sit in registers.
     static_assert(PF == 2 || GROUP == 4, "deep register prefetch is for the whole-tile replays");
+    static_assert(!MAPS || !W, "the maps form is the unweighted replay's");
     const bool dense = p.list == nullptr;
     float wreg[PF] = {};
     if constexpr (W) {
@@ -462,6 +467,8 @@ __device__ __forceinline__ void coop_body(const StackArgs &p, float *a, const un
 
         NL_T(0);
         float res = p.ref_loc;
+        // (MAPS: the pixel's counts are the increments of the running counts; at most 65 535 each, so their low words do)
+        [[maybe_unused]] const unsigned lo_before = (unsigned)c_lo, hi_before = (unsigned)c_hi;
         // StackArgs::bounds (weighted stacks with a decision pass; list replays of winsorized passes): the clip
         // bounds of this pixel's first `decided` rounds are on record -- those rounds only permute (the quickselect of
         // QSelectMedian) and clip.  An unweighted result is the mean of the LAST round, which is never on record.
@@ -590,6 +597,9 @@ __device__ __forceinline__ void coop_body(const StackArgs &p, float *a, const un
             }
         }
         if (lane == 0) p.out[pix] = res;
+        if constexpr (MAPS) {
+            if (lane == 0) p.reject_map[pix] = ((unsigned)c_lo - lo_before) | (((unsigned)c_hi - hi_before) << 16);
+        }
         NL_T(4);
       }
     }

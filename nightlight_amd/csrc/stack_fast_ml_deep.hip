@@ -14,8 +14,11 @@
 // Per sample the cross-lane work is 2 instructions per stage (partner move + med3): 1 / 3 / 6 / 10 cross-lane stages
 // on 2 / 4 / 8 / 16 lanes for the median, 1 / 2 / 3 / 4 more for the MAD kernel.
 //
-// No non-temporal loads (they pay only where a wave reads whole 128-byte lines: two lanes per pixel), plain form only: no
-// MAPS or RECORD instantiation exists for these lane counts.
+// No non-temporal loads (they pay only where a wave reads whole 128-byte lines: two lanes per pixel).  The MAD kernel also
+// runs in its MAPS and RECORD forms here (include/nlstack_deepstackmaps.h, include/nlstack_deepwmad.h): what they need behind
+// the sorts -- pixel, role, `on` -- is computed anew like everything else (DeepThread::renew), so they spill as little.
+#include <cstring>
+
 #include "launch_common.hpp"
 #include "stack_fast_ml_impl.hpp"
 
@@ -31,12 +34,25 @@ hipError_t launch_stack_median_ml_deep(const StackArgs &args, hipStream_t stream
     return L.err;
 }
 
-hipError_t launch_stack_mad_ml_deep(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name)
+// Form::Maps (include/nlstack_deepstackmaps.h): named as the plain kernel with "maps" as its last argument.  Form::Record
+// (include/nlstack_deepwmad.h): the kernel writes no list, so it gets an all-zero FastArgs and `fargs` is not read
+hipError_t launch_stack_mad_ml_deep(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name, Form form)
 {
+    if (form == Form::Follow || !form_args_ok(form, args)) return hipErrorInvalidValue;
     Launcher L(stream);
     with_deep_lanes(args.n_frames, [&](auto LPP) {
-        *name = kernel_name<kMadMlName, decltype(LPP)::value>();
-        L(stack_mad_ml_kernel<decltype(LPP)::value>, pixel_grid(args.npix, LPP), 256, 0, args, fargs);
+        if (form == Form::Maps) {
+            *name = maps_kernel_name<kMadMlName, decltype(LPP)::value>();
+            L(stack_mad_ml_kernel<decltype(LPP)::value, false, true>, pixel_grid(args.npix, LPP), 256, 0, args, fargs);
+        } else if (form == Form::Record) {
+            FastArgs none;
+            memset(&none, 0, sizeof none);
+            *name = kernel_name<kMadMlName, decltype(LPP)::value, true>();
+            L(stack_mad_ml_kernel<decltype(LPP)::value, true>, pixel_grid(args.npix, LPP), 256, 0, args, none);
+        } else {
+            *name = kernel_name<kMadMlName, decltype(LPP)::value>();
+            L(stack_mad_ml_kernel<decltype(LPP)::value>, pixel_grid(args.npix, LPP), 256, 0, args, fargs);
+        }
     });
     return L.err;
 }

@@ -71,12 +71,13 @@ void stack_median_ml_kernel(StackArgs p)
 // pixel interleave the frames in the second read; a frame-order fp32 sum would be a chain through them per frame.)
 // MAPS (the full maps pass, include/nlstack_fullmaps.h): the lane that stores a pixel's result also stores its two clip
 // counts, p.reject_map[pix] = c_lo | c_hi << 16 (zero beside ref_loc; nothing for a pixel of the exact list).
+// Both forms exist at every lane count: 8 and 16 lanes serve include/nlstack_deepwmad.h (RECORD) and
+// include/nlstack_deepstackmaps.h (MAPS), and take pixel, role and `on` anew behind the sorts as the plain form does.
 template <int LPP, bool RECORD = false, bool MAPS = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8)))
 void stack_mad_ml_kernel(StackArgs p, FastArgs q)
 {
     static_assert(!(RECORD && MAPS), "the record-only kernel stores no result and no map");
-    static_assert(LPP <= 4 || !(RECORD || MAPS), "8 and 16 lanes per pixel: the plain form only");
     constexpr int NS = kMlNS;
     int lane = threadIdx.x & 63;
     int role = threadIdx.x % LPP;
@@ -138,6 +139,7 @@ void stack_mad_ml_kernel(StackArgs p, FastArgs q)
     const float t_lo = p.sig_lo * sd, t_hi = p.sig_hi * sd;
     const float lo = median - t_lo, hi = median + t_hi;
     if constexpr (RECORD) {
+        if constexpr (LPP >= 8) me.template renew<LPP>(role, pix, on, p.npix);
         if (on && role == 0) {
             p.bounds[(size_t)pix] = make_float2(lo, hi);
             p.nrounds[(size_t)pix] = (n > 0 && !degenerate) ? 1 : 0;

@@ -64,7 +64,8 @@ struct StackArgs {
     unsigned char *nrounds;
     // Maps pass (nl_stack_run_maps and the tiers above it): [npix] words, the pixel's clipLow
     // count | clipHigh count << 16.  Read by the MAPS instantiations only (stack_exact_kernel; stack_fast_maps_impl.hpp;
-    // stack_linfit_impl.hpp; the MAD kernels of stack_fast.hip / stack_fast_ml.hip); nullptr everywhere else.
+    // stack_linfit_impl.hpp; the MAD kernels of stack_fast.hip / stack_fast_ml.hip / stack_fast_ml_deep.hip; coop_body);
+    // nullptr everywhere else.
     unsigned *reject_map;
 };
 
@@ -219,16 +220,20 @@ hipError_t launch_stack_mad_ml(const StackArgs &args, const FastArgs &fargs, hip
                                Form form = Form::Plain);
 unsigned ml_generic_grid(int n_frames, unsigned gen_hint);      // workgroups of launch_stack_sigma_mlg behind launch_stack_sigma_mlz
 
-// the same two kernels on 8 / 16 lanes per pixel: the median and unweighted MAD sigma of 513 ... 2048 frames, plain form
+// the same two kernels on 8 / 16 lanes per pixel: the median and unweighted MAD sigma of 513 ... 2048 frames
 // (stack_fast_ml_deep.hip; include/nlstack_deepstack.h).  `stride`: floats between frames, LPP * stride * 4 < 2^31
+// The MAD kernel: Plain, Maps (include/nlstack_deepstackmaps.h) or Record (include/nlstack_deepwmad.h), as launch_stack_mad_ml
 int deep_ml_supported(int mode, bool weighted, int n_frames, int64_t stride);
 hipError_t launch_stack_median_ml_deep(const StackArgs &args, hipStream_t stream, const char **name);
-hipError_t launch_stack_mad_ml_deep(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name);
+hipError_t launch_stack_mad_ml_deep(const StackArgs &args, const FastArgs &fargs, hipStream_t stream, const char **name,
+                                    Form form = Form::Plain);
 
 // ---- stack_exact_coop.hip (bit-exact sigma replay, one wave per pixel) ----
 int coop_supported(int mode, bool weighted, int n_frames);
 hipError_t launch_stack_median_coop(const StackArgs &args, int grid, hipStream_t stream, const char **name);
-hipError_t launch_stack_sigma_coop(int mode, const StackArgs &args, int grid, hipStream_t stream, const char **name);
+// Plain, or Maps (include/nlstack_deepstackmaps.h): the whole-tile, unweighted replay only -- refused with weights or a list
+hipError_t launch_stack_sigma_coop(int mode, const StackArgs &args, int grid, hipStream_t stream, const char **name,
+                                   Form form = Form::Plain);
 int coop_group(const StackArgs &args);      // pixels per work item of that launch (4: whole-tile replay with aligned 16-byte loads)
 
 // ---- stack_exact_tile.hip (bit-exact sigma / winsorized clipping over whole tiles: one wave = 64

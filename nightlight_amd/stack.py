@@ -216,6 +216,16 @@ class StackHandle:
         the pass of run_maps_deep everywhere else.  Arguments and return value are those of run_maps."""
         return self._run_maps(self._lib.nl_stack_run_maps_full, mode, sigma_low, sigma_high, ref_loc, out, reject_low, reject_high)
 
+    def run_maps_deepstack(self, mode, sigma_low=2.75, sigma_high=2.75, ref_loc=0.0, out=None, reject_low=None,
+                           reject_high=None):
+        """run_maps_full with the stacks beyond 512 frames on engines of their own as well (nl_stack_run_maps_deepstack,
+        include/nlstack_deepstackmaps.h): unweighted MAD sigma of 513 ... 2048 frames on the 8- / 16-lane kernel of
+        run_deepstack -- the result is then run_deepstack's, bit for bit, the maps run_maps' -- the median on its deep
+        kernel with zero maps, unweighted sigma / winsorized clipping beyond 512 frames on the wave-per-pixel replay
+        (result and maps are run_maps'), and the pass of run_maps_full everywhere else.  Arguments and return value are
+        those of run_maps."""
+        return self._run_maps(self._lib.nl_stack_run_maps_deepstack, mode, sigma_low, sigma_high, ref_loc, out, reject_low, reject_high)
+
     def run_linfit_weighted(self, sigma_low=2.75, sigma_high=2.75, ref_loc=0.0, out=None, fetch=True):
         """One pass of the weighted linear fit (include/nlstack_wlinfit.h; an EXTENSION, the reference's fit takes
         no weights): the reference's linear-fit rejection, then the mean of the survivors with the weights of
@@ -258,6 +268,19 @@ class StackHandle:
         """run_mad_weighted without the wait: finish() completes it."""
         capi.check(self._lib.nl_stack_run_mad_weighted_async(self._h, C.c_float(sigma_low), C.c_float(sigma_high),
                                                              C.c_float(ref_loc)))
+
+    def run_mad_weighted_deepstack(self, sigma_low=2.75, sigma_high=2.75, ref_loc=0.0, out=None, fetch=True):
+        """run_mad_weighted for deep stacks (include/nlstack_deepwmad.h; an extension of depth, not of semantics):
+        513 ... 2048 active frames on the 8- / 16-lane MAD kernel, record only, and the streaming kernel of the weighted
+        passes -- bit-equal to run_mad_weighted, the same counters -- and run_mad_weighted's own pass at every other
+        depth.  Arguments and return value are those of run_mad_weighted."""
+        return _run_counted(self._lib.nl_stack_run_mad_weighted_deepstack, self._h, _sigmas(sigma_low, sigma_high, ref_loc),
+                            self._result_array(out, fetch))
+
+    def run_mad_weighted_deepstack_async(self, sigma_low=2.75, sigma_high=2.75, ref_loc=0.0):
+        """run_mad_weighted_deepstack without the wait: finish() completes it."""
+        capi.check(self._lib.nl_stack_run_mad_weighted_deepstack_async(self._h, C.c_float(sigma_low), C.c_float(sigma_high),
+                                                                       C.c_float(ref_loc)))
 
     def run_deepstack(self, mode, sigma_low=2.75, sigma_high=2.75, ref_loc=0.0, out=None, fetch=True):
         """run for deep stacks (include/nlstack_deepstack.h; an extension of depth, not of semantics): the median and
@@ -779,6 +802,10 @@ class StackGroup:
         """StackHandle.run_maps_full over the tiles (nl_group_run_maps_full): the return value of run_maps."""
         return self._run_maps(self._lib.nl_group_run_maps_full, mode, sigma_low, sigma_high, ref_loc)
 
+    def run_maps_deepstack(self, mode, sigma_low=2.75, sigma_high=2.75, ref_loc=0.0):
+        """StackHandle.run_maps_deepstack over the tiles (nl_group_run_maps_deepstack): the return value of run_maps."""
+        return self._run_maps(self._lib.nl_group_run_maps_deepstack, mode, sigma_low, sigma_high, ref_loc)
+
     def run_linfit_weighted(self, sigma_low=2.75, sigma_high=2.75, ref_loc=0.0, download=True):
         """StackHandle.run_linfit_weighted over the tiles: (result or None, clip_low, clip_high)."""
         return _run_counted(self._lib.nl_group_run_linfit_weighted, self._g, _sigmas(sigma_low, sigma_high, ref_loc),
@@ -792,6 +819,11 @@ class StackGroup:
     def run_mad_weighted(self, sigma_low=2.75, sigma_high=2.75, ref_loc=0.0, download=True):
         """StackHandle.run_mad_weighted over the tiles: (result or None, clip_low, clip_high)."""
         return _run_counted(self._lib.nl_group_run_mad_weighted, self._g, _sigmas(sigma_low, sigma_high, ref_loc),
+                            self._result_array(download))
+
+    def run_mad_weighted_deepstack(self, sigma_low=2.75, sigma_high=2.75, ref_loc=0.0, download=True):
+        """StackHandle.run_mad_weighted_deepstack over the tiles: (result or None, clip_low, clip_high)."""
+        return _run_counted(self._lib.nl_group_run_mad_weighted_deepstack, self._g, _sigmas(sigma_low, sigma_high, ref_loc),
                             self._result_array(download))
 
     def run_deepstack(self, mode, sigma_low=2.75, sigma_high=2.75, ref_loc=0.0, download=True):

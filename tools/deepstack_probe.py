@@ -16,6 +16,19 @@ lanes per pixel) beside the pass of nl_stack_run, whose kernels beyond 512 frame
         timeout -k 10 120 python tools/deepstack_probe.py --frames 512 --out DIR && \
         timeout -k 10 300 python tools/deepstack_probe.py --frames 1024 --out DIR --append && \
         timeout -k 10 420 python tools/deepstack_probe.py --frames 2048 --out DIR --append
+
+  python tools/deepstack_probe.py --maps [--modes mad,sigma,winsor] ...
+      The maps pass beyond 512 frames (include/nlstack_deepstackmaps.h), same protocol.  Per frame count and mode:
+        run_maps_full       the column kernel: what every maps tier below this one runs there
+        run_maps_deepstack  the new pass
+        run_deepstack (MAD sigma) / run (sigma, winsorized)   the plain pass beside it, the MAPS kernel's twin
+      and the two ratios, whether maps, totals and result bits agree.  The column pass runs in a block of its own, first.
+  python tools/deepstack_probe.py --weighted ...
+      The weighted MAD-sigma pass (include/nlstack_deepwmad.h): run_mad_weighted (the column kernel beyond 512 frames),
+      run_mad_weighted_deepstack, and run_deepstack's unweighted MAD pass beside them; weights 1 / (1 + 3 s_k),
+      s_k = (1237 k mod 4099) / 4098.
+      Both append to DIR/deepstack_probe.txt with --append; the blocks of profiles/deepstack_probe.txt behind the first were
+      made so, one process and one time limit per frame count.
 """
 import argparse
 import os
@@ -37,6 +50,9 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--out", default=None)
     ap.add_argument("--append", action="store_true")
+    ap.add_argument("--maps", action="store_true")
+    ap.add_argument("--weighted", action="store_true")
+    ap.add_argument("--modes", default="mad,sigma,winsor")
     a = ap.parse_args()
     import nightlight_amd as nl
     from nightlight_amd import capi
@@ -55,7 +71,68 @@ def main():
         emit("a tile of %d rows of %d x %d, sigma %.2f / %.2f; up to %d runs after one warm-up run"
              % (a.rows, a.width, a.height, a.sigma, a.sigma, a.reps))
     px = a.width * a.rows
-    for frames in [int(x) for x in a.frames.split(",")]:
+
+    def timed(st, call):
+        """(median ms of the pass, of its dominant kernel, minimum, runs, what the last run returned)"""
+        got = call()                                                                       # warm-up
+        first = st.pass_times(0)[0]
+        reps = max(2, min(a.reps, int(10000.0 / max(first, 1e-3))))
+        ms = []
+        for _ in range(reps):
+            got = call()
+            ms.append(st.pass_times(0))
+        return float(np.median([m[0] for m in ms])), float(np.median([m[1] for m in ms])), min(m[0] for m in ms), reps, got
+
+    def line(st, ename, mname, t, frames):
+        emit("  %-26s %-10s %-44s pass median %.3f ms, min %.3f ms; dominant kernel %.3f ms; %d runs; %.2f ps per sample; "
+             "handed over %d pixels" % (ename, mname, st.last_kernel_name, t[0], t[2], t[1], t[3],
+                                        1e9 * t[0] / (float(px) * frames), st.last_fallback_pixels))
+
+    if a.maps or a.weighted:
+        modes = {"mad": (capi.ST_MAD_SIGMA, "MAD sigma"), "sigma": (capi.ST_SIGMA, "sigma"),
+                 "winsor": (capi.ST_WINSOR_SIGMA, "winsorized")}
+        for frames in [int(x) for x in a.frames.split(",")]:
+            with nl.StackHandle(frames, a.width, a.height, row0=0, rows=a.rows) as st:
+                st.fill_synthetic(seed=7)
+                sig = (a.sigma, a.sigma, 0.0)
+                if a.maps:
+                    emit("%d frames (%.1f GiB), maps passes:" % (frames, frames * px * 4 / 2.0 ** 30))
+                    for mode, mname in [modes[m] for m in a.modes.split(",")]:
+                        col = timed(st, lambda: st.run_maps_full(mode, *sig))
+                        line(st, "run_maps_full", mname, col, frames)
+                        new = timed(st, lambda: st.run_maps_deepstack(mode, *sig))
+                        line(st, "run_maps_deepstack", mname, new, frames)
+                        plain_entry = st.run_deepstack if mode == capi.ST_MAD_SIGMA else st.run
+                        twin = timed(st, lambda: plain_entry(mode, *sig))
+                        line(st, "run_deepstack" if mode == capi.ST_MAD_SIGMA else "run", mname, twin, frames)
+                        c, n, t = col[4], new[4], twin[4]
+                        emit("  %s: run_maps_full / run_maps_deepstack = %.1f; run_maps_deepstack / its plain twin = %.3f; "
+                             "maps equal: %s; totals equal: %s (%d / %d); result bits equal the column pass's: %s, the twin's: %s"
+                             % (mname, col[0] / new[0], new[0] / twin[0],
+                                np.array_equal(c[3], n[3]) and np.array_equal(c[4], n[4]), (c[1], c[2]) == (n[1], n[2]) == (t[1], t[2]),
+                                n[1], n[2], np.array_equal(c[0].view(np.uint32), n[0].view(np.uint32)),
+                                np.array_equal(t[0].view(np.uint32), n[0].view(np.uint32))))
+                if a.weighted:
+                    emit("%d frames (%.1f GiB), weighted MAD sigma:" % (frames, frames * px * 4 / 2.0 ** 30))
+                    k = np.arange(frames, dtype=np.int64)
+                    weights = (1.0 / (1.0 + 3.0 * ((1237 * k) % 4099) / 4098.0)).astype(np.float32)
+                    st.set_weights(weights)
+                    col = timed(st, lambda: st.run_mad_weighted(*sig))
+                    line(st, "run_mad_weighted", "MAD sigma", col, frames)
+                    new = timed(st, lambda: st.run_mad_weighted_deepstack(*sig))
+                    line(st, "run_mad_weighted_deepstack", "MAD sigma", new, frames)
+                    st.set_weights(None)
+                    twin = timed(st, lambda: st.run_deepstack(capi.ST_MAD_SIGMA, *sig))
+                    line(st, "run_deepstack", "MAD sigma", twin, frames)
+                    c, n, t = col[4], new[4], twin[4]
+                    emit("  weighted MAD sigma: run_mad_weighted / run_mad_weighted_deepstack = %.1f; run_mad_weighted_deepstack / "
+                         "run_deepstack = %.3f; totals equal: %s (%d / %d); result bits equal run_mad_weighted's: %s"
+                         % (col[0] / new[0], new[0] / twin[0], (c[1], c[2]) == (n[1], n[2]) == (t[1], t[2]), n[1], n[2],
+                            np.array_equal(c[0].view(np.uint32), n[0].view(np.uint32))))
+        frames_list = []
+    else:
+        frames_list = [int(x) for x in a.frames.split(",")]
+    for frames in frames_list:
         with nl.StackHandle(frames, a.width, a.height, row0=0, rows=a.rows) as st:
             st.fill_synthetic(seed=7)
             emit("%d frames (%.1f GiB):" % (frames, frames * px * 4 / 2.0 ** 30))
