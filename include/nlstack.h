@@ -726,6 +726,11 @@ int nl_stack_project_tile_paths(nl_stack_t *dst, nl_stack_t *src, int src_idx, c
  * nl_resample_lanczos3_table are declared in nlstack_resample.h, which is part of this interface. */
 #include "nlstack_resample.h"
 
+/* Drizzle integration of resident frames onto a finer output grid (AN EXTENSION: the reference has no drizzle):
+ * nl_drizzle_geometry, nl_stack_frame_drizzle_from, nl_stack_drizzle_finalize, nl_stack_frame_reject_against and
+ * nl_stack_drizzle_tile_paths are declared in nlstack_drizzle.h, which is part of this interface. */
+#include "nlstack_drizzle.h"
+
 /* ---- OpGaussianBlur / OpUnsharpMask / OpHSLUnsharpMask's UnsharpMask ----
  * (internal/ops/stretch/stretch.go:339-424, internal/ops/stretch/usm.go, internal/ops/hsl/hsl.go:538-551)
  * The two passes of GaussFilter2D (usm.go:118-122): Convolve1DX (usm.go:85-98) into a scratch frame of the

@@ -133,6 +133,13 @@ RESAMPLE_EXPORTS = ["nl_resample_lanczos3_table", "nl_stack_frame_resample_from"
 RS_BILINEAR, RS_BICUBIC, RS_LANCZOS3 = range(3)
 RS_PHASES = 1024
 
+# every symbol include/nlstack_drizzle.h declares (likewise): drizzle integration of resident frames onto a finer output
+# grid and the rejection step in front of it, an extension
+DRIZZLE_EXPORTS = ["nl_drizzle_geometry", "nl_stack_frame_drizzle_from", "nl_stack_drizzle_finalize",
+                   "nl_stack_frame_reject_against", "nl_stack_drizzle_tile_paths"]
+DZ_TURBO, DZ_POINT = range(2)
+DZ_MAX_RADIUS = 3
+
 # nl_star_t = star.Star (findstars.go:30-37), 24 bytes
 STAR_DTYPE = np.dtype([("index", "<i4"), ("value", "<f4"), ("x", "<f4"), ("y", "<f4"), ("mass", "<f4"),
                        ("hfr", "<f4")])
@@ -444,6 +451,12 @@ def open_library(path):
     L.nl_stack_frame_resample_from.argtypes = [vp, C.c_int, vp, C.c_int, _f32p, C.c_float, C.c_int, C.c_int]
     L.nl_group_frame_resample_from.argtypes = [vp, C.c_int, vp, C.c_int, _f32p, C.c_float, C.c_int, C.c_int]
     L.nl_stack_resample_tile_paths.argtypes = [vp, vp, C.c_int, _f32p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.nl_drizzle_geometry.argtypes = [_f32p, C.c_float, C.c_float, _f32p, _f32p, _f32p, _intp]
+    L.nl_stack_frame_drizzle_from.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, _f32p, C.c_float, C.c_float, C.c_float,
+                                              C.c_int, C.c_int]
+    L.nl_stack_drizzle_finalize.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float]
+    L.nl_stack_frame_reject_against.argtypes = [vp, C.c_int, C.c_int, C.c_float, C.c_float, _i64p, _i64p]
+    L.nl_stack_drizzle_tile_paths.argtypes = [vp, vp, C.c_int, _f32p, C.c_float, C.c_float, _i64p, _i64p]
     _planes = C.POINTER(C.c_int)
     # stars, n_stars, block, border, skip_bright, skip_dim, shadows, highlights, loc, scale, report
     _balance_args = [vp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, Rgb, Rgb, _f32p, _f32p, C.POINTER(RgbBalance)]

@@ -1,0 +1,232 @@
+// drizzle.hip -- drizzle integration of a resident, unresampled frame onto an output grid of another scale, for
+// nl_stack_frame_drizzle_from, and the two elementwise steps around it: nl_stack_drizzle_finalize's quotient and
+// nl_stack_frame_reject_against's blot-and-compare.  AN EXTENSION: the reference has no drizzle;
+// include/nlstack_drizzle.h carries the definition these kernels compute bit for bit.
+//
+// The gather form: one output pixel per work item, which walks the (2R + 1)^2 source pixels around its own rounded
+// source position in a fixed order and adds the overlap of each one's drop with itself.  No atomics, so the planes are
+// deterministic, and a frame is laid down in one pass over the output.
+//
+// The structure is project.hip's.  A workgroup owns a kProjTileW x kProjTileH tile of the output; wave w makes rows w,
+// w + 4, ... of it, lane l the columns l, l + 64, l + 128, l + 192 of a row, so every load and store of the two planes
+// covers 256 contiguous bytes per wave.  From the four corners of its tile (drizzle.hpp) the workgroup computes the
+// candidate box of the tile; it stages the box in LDS (each source byte fetched once, 16 bytes per lane where the
+// source's width allows) when the box is within kDzLdsFloats, else every candidate comes from global memory.  On a
+// finer output grid the box is small: 256 x 16 output pixels at scale 2 are 128 x 8 source pixels plus the window.
+//
+// Most candidates of a window fail the overlap test.  Nothing branches on that: a candidate that is outside the
+// source, or whose drop misses the pixel, reads element 0 (always there) and carries a NaN as its weight, which the
+// sums drop by a select as they drop a pixel without data (weight is finite, so no real candidate has one); the
+// (2R + 1)^2 loads of a pixel are independent and in flight together, and no mask outlives its candidate.  A pixel
+// whose whole window misses the source skips the loop.
+//
+// Bit-exact: coordinates, overlaps and sums in the header's operand order, no FMA (-ffp-contract=off).
+#include <math.h>
+
+#include "drizzle.hpp"
+#include "frame_common.hpp"
+#include "launch_common.hpp"
+
+namespace nl {
+
+namespace {
+
+// rows of the tile for this wave, four pixels per lane and row.  mem = the box in LDS (origin org_x, org_y, pitch
+// b.pitch) or the source itself (origin 0, 0, pitch src_w).
+template <int R, bool POINT, class Index>
+__device__ __forceinline__ void drizzle_rows(const float *__restrict__ mem, int org_x, int org_y, Index pitch, int src_w,
+                                             int src_h, float *__restrict__ sum, float *__restrict__ wgt, int dst_w,
+                                             int row0, int c0, int r_first, int r_end, const DzGeom &q, float weight,
+                                             bool first)
+{
+    const int lane = threadIdx.x & 63;
+    // xc in [-R, src_w - 1 + R] or the window misses the source (the bound may round up: every candidate is tested)
+    const float x_last = fminf((float)src_w + (float)R, 2147483520.0f), y_last = fminf((float)src_h + (float)R, 2147483520.0f);
+    for (int r = r_first + (int)(threadIdx.x >> 6); r < r_end; r += 4) {
+        const float py = (float)(row0 + r);
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int col = c0 + lane + 64 * k;
+            if (col >= dst_w) continue;
+            const float px = (float)col;
+            const float X = proj_x(q.g, px, py), Y = proj_y(q.g, px, py);
+            const float xc = floorf(X + 0.5f), yc = floorf(Y + 0.5f);
+            const int64_t at = (int64_t)r * dst_w + col;
+            float s = 0.0f, t = 0.0f;
+            if (!first) { s = sum[at]; t = wgt[at]; }
+            // (a NaN fails every comparison: no candidates)
+            if (xc >= -(float)R && xc <= x_last && yc >= -(float)R && yc <= y_last) {
+                const int xi = (int)xc, yi = (int)yc;
+                float v[2 * R + 1][2 * R + 1], wa[2 * R + 1][2 * R + 1];
+#pragma unroll
+                for (int dj = 0; dj <= 2 * R; dj++) {
+                    const int j = yi + dj - R;
+                    const float fj = (float)j;
+#pragma unroll
+                    for (int di = 0; di <= 2 * R; di++) {
+                        const int i = xi + di - R;
+                        const float fi = (float)i;
+                        const float u = proj_x(q.f, fi, fj), vv = proj_y(q.f, fi, fj);
+                        bool ok = (unsigned)i < (unsigned)src_w && (unsigned)j < (unsigned)src_h;
+                        if constexpr (POINT) {
+                            ok = ok && floorf(u + 0.5f) == px && floorf(vv + 0.5f) == py;
+                            wa[dj][di] = ok ? weight : __builtin_nanf("");
+                        } else {
+                            float lo = u - q.hw, e = px - 0.5f;
+                            if (e > lo) lo = e;
+                            float hi = u + q.hw;
+                            e = px + 0.5f;
+                            if (e < hi) hi = e;
+                            const float ox = hi - lo;
+                            lo = vv - q.hw;
+                            e = py - 0.5f;
+                            if (e > lo) lo = e;
+                            hi = vv + q.hw;
+                            e = py + 0.5f;
+                            if (e < hi) hi = e;
+                            const float oy = hi - lo;
+                            ok = ok && ox > 0.0f && oy > 0.0f;
+                            const float ar = ox * oy;
+                            wa[dj][di] = ok ? weight * ar : __builtin_nanf("");
+                        }
+                        const Index p = ok ? (Index)(j - org_y) * pitch + (Index)(i - org_x) : (Index)0;
+                        v[dj][di] = mem[p];
+                    }
+                }
+#pragma unroll
+                for (int dj = 0; dj <= 2 * R; dj++) {
+#pragma unroll
+                    for (int di = 0; di <= 2 * R; di++) {
+                        const float x = v[dj][di];
+                        const bool ok = x == x && wa[dj][di] == wa[dj][di]; // NaN = no data; a NaN weight = no candidate
+                        const float sn = s + x * wa[dj][di], tn = t + wa[dj][di];
+                        s = ok ? sn : s;
+                        t = ok ? tn : t;
+                    }
+                }
+            }
+            sum[at] = s;
+            wgt[at] = t;
+        }
+    }
+}
+
+// flags: bit 0 = the source allows 16-byte loads, bit 1 = tiles may stage their box, bit 2 = first
+template <int R, bool POINT>
+__global__ __launch_bounds__(256) void drizzle_tile_kernel(const float *__restrict__ src, int src_w, int src_h,
+                                                           float *__restrict__ sum, float *__restrict__ wgt, int dst_w,
+                                                           int row0, int rows, DzGeom q, float weight, unsigned flags)
+{
+    __shared__ float lds[kDzLdsFloats];
+    const int c0 = blockIdx.x * kProjTileW, r0 = blockIdx.y * kProjTileH;
+    const int c1 = min(c0 + kProjTileW, dst_w) - 1, r_end = min(r0 + kProjTileH, rows);
+    const bool vec = flags & 1u, first = flags & 4u;
+    ProjBox b = {0, 0, 0, 0, 0};
+    const bool staged = (flags & 2u) && dz_tile_box(q.g, R, src_w, src_h, c0, c1, row0 + r0, row0 + r_end - 1, vec, b);
+    if (staged) {                                                            // (uniform over the workgroup)
+        if (vec) stage_box<true>(src, src_w, b, lds);
+        else stage_box<false>(src, src_w, b, lds);
+        __syncthreads();
+        drizzle_rows<R, POINT, int>(lds, b.x0, b.y0, b.pitch, src_w, src_h, sum, wgt, dst_w, row0, c0, r0, r_end, q, weight, first);
+    } else {
+        drizzle_rows<R, POINT, int64_t>(src, 0, 0, src_w, src_w, src_h, sum, wgt, dst_w, row0, c0, r0, r_end, q, weight, first);
+    }
+}
+
+// bits 0 / 1 of the kernel's flags (project.hip's rule; the geometry's coefficients are finite)
+unsigned tile_flags(const float *src, int src_w, unsigned switches)
+{
+    const bool vec = (src_w & 3) == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0;
+    return (vec ? 1u : 0u) | (!(switches & kProjDirectOnly) ? 2u : 0u);
+}
+
+__global__ __launch_bounds__(256) void drizzle_finalize_kernel(const float *sum, const float *wgt, float *out, int64_t n,
+                                                                float min_weight, float empty)
+{
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const float s = sum[i], w = wgt[i];
+        out[i] = w > min_weight ? s / w : empty;                             // (a NaN weight: empty)
+    }
+}
+
+__global__ __launch_bounds__(256) void reject_against_kernel(float *frame, const float *model, int64_t n,
+                                                              float low, float high, unsigned long long *counts)
+{
+    unsigned n_low = 0, n_high = 0;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const float d = frame[i] - model[i];
+        const bool is_low = d < -low, is_high = !is_low && d > high;         // (a NaN on either side: neither)
+        if (is_low || is_high) frame[i] = __builtin_nanf("");
+        n_low += is_low ? 1u : 0u;
+        n_high += is_high ? 1u : 0u;
+    }
+    __shared__ unsigned s_low[4], s_high[4];
+    n_low = wave_sum(n_low);
+    n_high = wave_sum(n_high);
+    if ((threadIdx.x & 63) == 0) { s_low[threadIdx.x >> 6] = n_low; s_high[threadIdx.x >> 6] = n_high; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        counts[2 * (size_t)blockIdx.x + 0] = (unsigned long long)sum_in_order<4>(s_low);
+        counts[2 * (size_t)blockIdx.x + 1] = (unsigned long long)sum_in_order<4>(s_high);
+    }
+}
+
+unsigned stream_grid(int64_t n)
+{
+    const int64_t g = (n + 255) / 256;
+    return (unsigned)(g > 256 * 32 ? 256 * 32 : (g < 1 ? 1 : g));
+}
+
+}  // namespace
+
+hipError_t launch_drizzle(const float *src, int src_w, int src_h, float *sum, float *wgt, int dst_w, int row0, int rows,
+                          const DzGeom &geom, float weight, bool first, bool point, unsigned switches, hipStream_t stream)
+{
+    const dim3 grid((unsigned)((dst_w + kProjTileW - 1) / kProjTileW), (unsigned)((rows + kProjTileH - 1) / kProjTileH));
+    const unsigned flags = tile_flags(src, src_w, switches) | (first ? 4u : 0u);
+    Launcher L(stream);
+    with_class<1, 2, 3>(geom.radius, [&](auto R) {
+        with_bool(point, [&](auto P) {
+            L(drizzle_tile_kernel<decltype(R)::value, decltype(P)::value>, grid, 256, 0, src, src_w, src_h, sum, wgt, dst_w,
+              row0, rows, geom, weight, flags);
+        });
+    });
+    return L.err;
+}
+
+void drizzle_tile_paths(const float *src, int src_w, int src_h, int dst_w, int row0, int rows, const DzGeom &geom,
+                        unsigned switches, int64_t *staged, int64_t *direct)
+{
+    const unsigned flags = tile_flags(src, src_w, switches);
+    int64_t n_staged = 0, n_direct = 0;
+    for (int r0 = 0; r0 < rows; r0 += kProjTileH)
+        for (int c0 = 0; c0 < dst_w; c0 += kProjTileW) {
+            const int c1 = (c0 + kProjTileW < dst_w ? c0 + kProjTileW : dst_w) - 1;
+            const int r_end = r0 + kProjTileH < rows ? r0 + kProjTileH : rows;
+            ProjBox b;
+            if ((flags & 2u) && dz_tile_box(geom.g, geom.radius, src_w, src_h, c0, c1, row0 + r0, row0 + r_end - 1, flags & 1u, b))
+                n_staged++;
+            else
+                n_direct++;
+        }
+    *staged = n_staged;
+    *direct = n_direct;
+}
+
+hipError_t launch_drizzle_finalize(const float *sum, const float *wgt, float *out, int64_t n, float min_weight, float empty,
+                                   hipStream_t stream)
+{
+    Launcher L(stream);
+    L(drizzle_finalize_kernel, stream_grid(n), 256, 0, sum, wgt, out, n, min_weight, empty);
+    return L.err;
+}
+
+hipError_t launch_reject_against(float *frame, const float *model, int64_t n, float low, float high,
+                                 unsigned long long *counts, int blocks, hipStream_t stream)
+{
+    Launcher L(stream);
+    L(reject_against_kernel, (unsigned)blocks, 256, 0, frame, model, n, low, high, counts);
+    return L.err;
+}
+
+}  // namespace nl

@@ -1,0 +1,91 @@
+// drizzle.hpp -- what drizzle.hip's kernels, its launchers and the entries (nlstack_drizzle.hip) share: the geometry of
+// include/nlstack_drizzle.h as the kernel takes it, the candidate box of an output tile -- the one piece of arithmetic
+// host and device both run (the same fp32 operations, no contraction on either side, so drizzle_tile_paths() counts
+// exactly the tiles the kernel stages) -- and the launchers.  ProjInv, ProjBox, stage_box and the tile shape are
+// project.hpp's.
+#pragma once
+#include <math.h>
+#include <stdint.h>
+
+#include <hip/hip_runtime.h>
+
+#include "project.hpp"
+
+namespace nl {
+
+constexpr int kDzLdsFloats = 8192;        // 32 KiB: five workgroups (20 waves) share a CU's 160 KiB
+constexpr int kDzMaxRadius = 3;           // NL_DZ_MAX_RADIUS
+
+// nl_drizzle_geometry's results: f = source -> output pixel, g = output -> source pixel, hw = half the drop's side in
+// output pixels, radius = R of the candidate window
+struct DzGeom {
+    ProjInv f, g;
+    float hw;
+    int radius;
+};
+
+// floor(v + 0.5f) as an int where it matters: anything below -8 is -8 (its window of radius <= 3 ends in front of
+// column 0 either way), anything above 2^31 - 128 is that (behind every source, and +- 3 stays an int); v is no NaN
+__host__ __device__ inline int dz_round_clamped(float v)
+{
+    const float f = floorf(v + 0.5f);
+    return (int)(f < -8.0f ? -8.0f : (f > 2147483520.0f ? 2147483520.0f : f));
+}
+
+// The candidate box of the output tile of columns [c0, c1] and image rows [r0, r1] (inclusive): every source pixel in
+// the window of radius R around the rounded source position of a pixel of the tile.  False when the tile takes its
+// candidates from global memory instead: a coordinate that is NaN at a corner, a box beyond the LDS budget, or no
+// candidate in the source at all (then nothing is read either way).
+//
+// The four corners are enough, with no margin, by project.hpp's argument: X = fl(fl(fl(a*px) + fl(b*py)) + c) is
+// monotone in px for a fixed py and in py for a fixed px, rounding included, and so are fl(X + 0.5f) and its floor;
+// the smallest and the largest xc over the rectangle are taken at corners.  Same for yc.
+//
+// Unlike proj_tile_box a candidate needs no 2x2 footprint: the box reaches the source's last column and row, and one
+// pixel of it is enough.
+__host__ __device__ inline bool dz_tile_box(const ProjInv &g, int radius, int src_w, int src_h, int c0, int c1, int r0,
+                                            int r1, bool vec, ProjBox &b)
+{
+    const float px0 = (float)c0, px1 = (float)c1, py0 = (float)r0, py1 = (float)r1;
+    const float x00 = proj_x(g, px0, py0), x10 = proj_x(g, px1, py0), x01 = proj_x(g, px0, py1), x11 = proj_x(g, px1, py1);
+    const float y00 = proj_y(g, px0, py0), y10 = proj_y(g, px1, py0), y01 = proj_y(g, px0, py1), y11 = proj_y(g, px1, py1);
+    if (x00 != x00 || x10 != x10 || x01 != x01 || x11 != x11 || y00 != y00 || y10 != y10 || y01 != y01 || y11 != y11)
+        return false;
+    const float xmin = fminf(fminf(x00, x10), fminf(x01, x11)), xmax = fmaxf(fmaxf(x00, x10), fmaxf(x01, x11));
+    const float ymin = fminf(fminf(y00, y10), fminf(y01, y11)), ymax = fmaxf(fmaxf(y00, y10), fmaxf(y01, y11));
+    int x0 = dz_round_clamped(xmin) - radius, x1 = dz_round_clamped(xmax) + radius;
+    int y0 = dz_round_clamped(ymin) - radius, y1 = dz_round_clamped(ymax) + radius;
+    if (x0 < 0) x0 = 0;
+    if (y0 < 0) y0 = 0;
+    if (x1 > src_w - 1) x1 = src_w - 1;
+    if (y1 > src_h - 1) y1 = src_h - 1;
+    if (x1 < x0 || y1 < y0) return false;                  // no candidate in the source
+    if (vec) {                                             // whole 16-byte groups of a row (src_w is a multiple of 4)
+        x0 &= ~3;
+        x1 |= 3;
+    }
+    b.x0 = x0;
+    b.y0 = y0;
+    b.w = x1 - x0 + 1;
+    b.h = y1 - y0 + 1;
+    b.pitch = b.w | 1;                                     // odd, as proj_tile_box: a quarter turn spreads over the banks
+    return (int64_t)b.pitch * b.h <= kDzLdsFloats;
+}
+
+// ---- drizzle.hip ----
+// nl_stack_frame_drizzle_from's kernel: the rows [row0, row0 + rows) of a dst_w wide output grid; sum / wgt = the two
+// planes of those rows; point = NL_DZ_POINT; switches: kProjDirectOnly of project.hpp
+hipError_t launch_drizzle(const float *src, int src_w, int src_h, float *sum, float *wgt, int dst_w, int row0, int rows,
+                          const DzGeom &geom, float weight, bool first, bool point, unsigned switches, hipStream_t stream);
+// how many tiles of that launch stage their candidate box in LDS, how many read global memory (host arithmetic)
+void drizzle_tile_paths(const float *src, int src_w, int src_h, int dst_w, int row0, int rows, const DzGeom &geom,
+                        unsigned switches, int64_t *staged, int64_t *direct);
+// out[i] = wgt[i] > min_weight ? sum[i] / wgt[i] : empty (any aliasing)
+hipError_t launch_drizzle_finalize(const float *sum, const float *wgt, float *out, int64_t n, float min_weight, float empty,
+                                   hipStream_t stream);
+// nl_stack_frame_reject_against's kernel over n pixels on `blocks` workgroups: counts[2 * b] / [2 * b + 1] = the
+// pixels workgroup b took out low / high
+hipError_t launch_reject_against(float *frame, const float *model, int64_t n, float low, float high,
+                                 unsigned long long *counts, int blocks, hipStream_t stream);
+
+}  // namespace nl

@@ -1,0 +1,153 @@
+// nlstack_drizzle.hip -- the entries of include/nlstack_drizzle.h (AN EXTENSION: the reference has no drizzle): the
+// geometry, laying a resident frame onto the two planes of a finer output grid, the quotient of the planes, and the
+// rejection of a frame's outliers against a model.  One of the units of the frame steps (nlstack_frame_common.hpp);
+// kernels in drizzle.hip.
+#include <math.h>
+
+#include "drizzle.hpp"
+#include "nlstack_frame_common.hpp"
+
+namespace {
+
+// The definition's geometry in double, rounded to fp32 once; what needs no handle of a drizzle call's arguments.
+int drizzle_geometry(const char *who, const float *trans, float scale, float pixfrac, nl::DzGeom *out)
+{
+    if (!trans) return fail(NL_ERR_INVALID_ARG, "%s: null transform", who);
+    if (!isfinite(scale) || !(scale > 0.0f)) return fail(NL_ERR_INVALID_ARG, "%s: scale %g (a finite number > 0)", who, scale);
+    if (!(pixfrac > 0.0f && pixfrac <= 1.0f)) return fail(NL_ERR_INVALID_ARG, "%s: pixfrac %g (0 < pixfrac <= 1)", who, pixfrac);
+    float unused[6];
+    if (const int rc = invert_transform(trans, unused); rc != NL_OK) return rc;       // the reference's Invert test
+    const double a = trans[0], b = trans[1], c = trans[2], d = trans[3], e = trans[4], f = trans[5];
+    const double S = scale, p = pixfrac;
+    const double Fa = S * a, Fb = S * b, Fc = S * (c + 0.5) - 0.5, Fd = S * d, Fe = S * e, Ff = S * (f + 0.5) - 0.5;
+    const double det = Fa * Fe - Fb * Fd;
+    const double Ga = Fe / det, Gb = -Fb / det, Gd = -Fd / det, Ge = Fa / det;
+    const double Gc = -(Ga * Fc + Gb * Ff), Gf = -(Gd * Fc + Ge * Ff);
+    const double hw = 0.5 * p * sqrt(fabs(det));
+    const double reach = 0.5 + hw;
+    const double span = fmax((fabs(Ga) + fabs(Gb)) * reach, (fabs(Gd) + fabs(Ge)) * reach) + 0.5 + 1.0 / 64;
+    const nl::DzGeom g = {{(float)Fa, (float)Fb, (float)Fc, (float)Fd, (float)Fe, (float)Ff},
+                          {(float)Ga, (float)Gb, (float)Gc, (float)Gd, (float)Ge, (float)Gf}, (float)hw, 0};
+    const float all[13] = {g.f.a, g.f.b, g.f.c, g.f.d, g.f.e, g.f.f, g.g.a, g.g.b, g.g.c, g.g.d, g.g.e, g.g.f, g.hw};
+    for (float v : all)
+        if (!isfinite(v)) return fail(NL_ERR_INVALID_ARG, "%s: a coefficient of the geometry is not finite", who);
+    const double R = ceil(span);
+    if (!(R <= (double)NL_DZ_MAX_RADIUS))
+        return fail(NL_ERR_INVALID_ARG, "%s: window radius %.0f beyond NL_DZ_MAX_RADIUS %d (the output grid is too coarse for this frame)",
+                    who, R, NL_DZ_MAX_RADIUS);
+    *out = g;
+    out->radius = (int)R;
+    return NL_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int nl_drizzle_geometry(const float trans[6], float scale, float pixfrac, float src_to_out[6], float out_to_src[6],
+                        float *half_width, int *radius)
+{
+    if (!trans || !src_to_out || !out_to_src || !half_width || !radius)
+        return fail(NL_ERR_INVALID_ARG, "drizzle_geometry: null argument");
+    nl::DzGeom g;
+    const int rc = drizzle_geometry("drizzle_geometry", trans, scale, pixfrac, &g);
+    if (rc != NL_OK) return rc;
+    const float F[6] = {g.f.a, g.f.b, g.f.c, g.f.d, g.f.e, g.f.f}, G[6] = {g.g.a, g.g.b, g.g.c, g.g.d, g.g.e, g.g.f};
+    memcpy(src_to_out, F, sizeof F);
+    memcpy(out_to_src, G, sizeof G);
+    *half_width = g.hw;
+    *radius = g.radius;
+    return NL_OK;
+}
+
+int nl_stack_frame_drizzle_from(nl_stack_t *dst, int sum_idx, int wgt_idx, nl_stack_t *src, int src_idx,
+                                const float trans[6], float scale, float pixfrac, float weight, int first, int kernel)
+{
+    const char *who = "frame_drizzle_from";
+    // in front of any device work: what needs no handle
+    if (!trans) return fail(NL_ERR_INVALID_ARG, "%s: null transform", who);
+    if (kernel != NL_DZ_TURBO && kernel != NL_DZ_POINT)
+        return fail(NL_ERR_INVALID_ARG, "%s: unknown kernel %d (NL_DZ_TURBO 0, NL_DZ_POINT 1)", who, kernel);
+    if (!isfinite(weight) || !(weight > 0.0f)) return fail(NL_ERR_INVALID_ARG, "%s: weight %g (a finite number > 0)", who, weight);
+    nl::DzGeom geom;
+    int rc = drizzle_geometry(who, trans, scale, pixfrac, &geom);
+    if (rc != NL_OK) return rc;
+    if (!dst || !src) return fail(NL_ERR_INVALID_ARG, "%s: null handle", who);
+    NL_CHECK_HANDLE(src);
+    NL_CHECK_HANDLE(dst);
+    if (src->device != dst->device)
+        return fail(NL_ERR_INVALID_ARG, "%s: source on device %d, destination on device %d", who, src->device, dst->device);
+    if (sum_idx == wgt_idx) return fail(NL_ERR_INVALID_ARG, "%s: slot %d is both the sum and the weight plane", who, sum_idx);
+    float *s = nullptr, *d_sum = nullptr, *d_wgt = nullptr;
+    rc = resident_target(src, src_idx, "frame_drizzle_from (source)", false, &s);
+    if (rc == NL_OK) rc = resident_target(dst, sum_idx, "frame_drizzle_from (sum plane)", false, &d_sum);
+    if (rc == NL_OK) rc = resident_target(dst, wgt_idx, "frame_drizzle_from (weight plane)", false, &d_wgt);
+    if (rc == NL_OK) rc = need_whole_image(src, "frame_drizzle_from (source)", "a drizzle reads any row of the source");
+    if (rc == NL_OK) rc = need_int32_pixels(src->npix, who, "source frame");
+    if (rc == NL_OK) rc = need_int32_pixels(dst->npix, who, "destination tile");
+    if (rc != NL_OK) return rc;
+    if (dst->d_frames != dst->d_frames_owned)
+        return fail(NL_ERR_INVALID_ARG, "%s: the destination's frames are attached, not owned", who);
+    if (s == d_sum || s == d_wgt)
+        return fail(NL_ERR_INVALID_ARG, "%s: slot %d of one handle is source and destination (a drizzle cannot run in place)", who, src_idx);
+    if (src != dst && (rc = nl_stack_order_stream_after(src, dst->stream)) != NL_OK) return rc;
+    NL_HIP(hipSetDevice(dst->device));
+    NL_HIP(nl::launch_drizzle(s, src->width, src->height, d_sum, d_wgt, dst->width, dst->row0, dst->rows, geom, weight,
+                              first != 0, kernel == NL_DZ_POINT, project_switches(dst), dst->stream));
+    NL_HIP(hipStreamSynchronize(dst->stream));                 // the caller may overwrite the source slot at once
+    return NL_OK;
+}
+
+int nl_stack_drizzle_tile_paths(nl_stack_t *dst, nl_stack_t *src, int src_idx, const float trans[6], float scale,
+                                float pixfrac, int64_t *staged, int64_t *direct)
+{
+    if (!dst || !src || !trans || !staged || !direct) return fail(NL_ERR_INVALID_ARG, "drizzle_tile_paths: null argument");
+    nl::DzGeom geom;
+    const int rc = drizzle_geometry("drizzle_tile_paths", trans, scale, pixfrac, &geom);
+    if (rc != NL_OK) return rc;
+    if (src_idx < 0 || src_idx >= src->n_frames)               // (a host query: no device, no stream is touched)
+        return fail(NL_ERR_INVALID_ARG, "drizzle_tile_paths: bad index %d", src_idx);
+    const float *s = src->d_frames + (int64_t)src_idx * src->fstride;
+    nl::drizzle_tile_paths(s, src->width, src->height, dst->width, dst->row0, dst->rows, geom, project_switches(dst),
+                           staged, direct);
+    return NL_OK;
+}
+
+int nl_stack_drizzle_finalize(nl_stack_t *h, int sum_idx, int wgt_idx, int out_idx, float min_weight, float empty)
+{
+    float *d_sum = nullptr, *d_wgt = nullptr, *d_out = nullptr;
+    int rc = resident_entry(h, sum_idx, "drizzle_finalize (sum plane)", false, &d_sum);
+    if (rc == NL_OK) rc = resident_target(h, wgt_idx, "drizzle_finalize (weight plane)", false, &d_wgt);
+    if (rc == NL_OK) rc = resident_target(h, out_idx, "drizzle_finalize (result)", false, &d_out);
+    if (rc != NL_OK) return rc;
+    NL_HIP(nl::launch_drizzle_finalize(d_sum, d_wgt, d_out, h->npix, min_weight, empty, h->stream));
+    NL_HIP(hipStreamSynchronize(h->stream));
+    return NL_OK;
+}
+
+int nl_stack_frame_reject_against(nl_stack_t *h, int idx, int model_idx, float low, float high, int64_t *n_low,
+                                  int64_t *n_high)
+{
+    if (!(low >= 0.0f) || !(high >= 0.0f))                     // (in front of the handle; a NaN fails the comparison)
+        return fail(NL_ERR_INVALID_ARG, "frame_reject_against: low %g, high %g (absolute thresholds >= 0)", low, high);
+    float *d = nullptr, *m = nullptr;
+    int rc = resident_entry(h, idx, "frame_reject_against", false, &d);
+    if (rc == NL_OK) rc = resident_target(h, model_idx, "frame_reject_against (model)", false, &m);
+    if (rc != NL_OK) return rc;
+    // two words per workgroup in the statistics' partials (kStatBlocks x 3 doubles)
+    unsigned long long *counts = reinterpret_cast<unsigned long long *>(h->d_stat_partial);
+    NL_HIP(nl::launch_reject_against(d, m, h->npix, low, high, counts, kStatBlocks, h->stream));
+    std::vector<unsigned long long> part(2 * (size_t)kStatBlocks);
+    NL_HIP(hipMemcpyAsync(part.data(), counts, sizeof(unsigned long long) * part.size(), hipMemcpyDeviceToHost, h->stream));
+    NL_HIP(hipStreamSynchronize(h->stream));
+    int64_t lo = 0, hi = 0;
+    for (int b = 0; b < kStatBlocks; b++) {
+        lo += (int64_t)part[2 * (size_t)b];
+        hi += (int64_t)part[2 * (size_t)b + 1];
+    }
+    if (n_low) *n_low = lo;
+    if (n_high) *n_high = hi;
+    return NL_OK;
+}
+
+}  // extern "C"

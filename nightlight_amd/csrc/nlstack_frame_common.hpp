@@ -1,5 +1,5 @@
-// nlstack_frame_common.hpp -- what the four units of the frame steps (nlstack_frame.hip, nlstack_frame_pre.hip,
-// nlstack_frame_stretch.hip, nlstack_frame_rgb.hip) ask of a handle before they launch, and the plumbing around their
+// nlstack_frame_common.hpp -- what the units of the frame steps (nlstack_frame.hip, nlstack_frame_pre.hip,
+// nlstack_frame_stretch.hip, nlstack_frame_rgb.hip, nlstack_drizzle.hip) ask of a handle before they launch, and the plumbing around their
 // launches, each written once.  Defined in nlstack_frame.hip unless a template.  Private like nlstack_internal.hpp.
 #pragma once
 

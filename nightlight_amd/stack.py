@@ -678,6 +678,39 @@ class StackHandle:
                                                           C.byref(staged), C.byref(direct)))
         return int(staged.value), int(direct.value)
 
+    def frame_drizzle_from(self, sum_idx, wgt_idx, src, src_idx, trans, scale, pixfrac=1.0, weight=1.0, first=False,
+                           kernel=capi.DZ_TURBO):
+        """Drizzle: lays the unresampled resident slot src_idx of the whole-image handle `src` through the forward
+        transform `trans` (source -> reference pixel) onto this handle's planes sum_idx (flux) and wgt_idx (weight),
+        whose grid has `scale` pixels per reference pixel; every source pixel is a drop of `pixfrac` times its side
+        (include/nlstack_drizzle.h; an EXTENSION, the reference has no drizzle).  first starts the planes, otherwise
+        the frame is added to them.  kernel: capi.DZ_TURBO (axis-aligned drop) or DZ_POINT."""
+        t = np.ascontiguousarray(trans, dtype=np.float32).reshape(6)
+        capi.check(self._lib.nl_stack_frame_drizzle_from(self._h, int(sum_idx), int(wgt_idx), src._h, int(src_idx),
+                                                         capi.fptr(t), float(scale), float(pixfrac), float(weight),
+                                                         int(bool(first)), int(kernel)))
+
+    def drizzle_finalize(self, sum_idx, wgt_idx, out_idx, min_weight=0.0, empty=float("nan")):
+        """Slot out_idx = sum / weight where the weight exceeds min_weight, else `empty`; the slots may alias."""
+        capi.check(self._lib.nl_stack_drizzle_finalize(self._h, int(sum_idx), int(wgt_idx), int(out_idx),
+                                                       float(min_weight), float(empty)))
+
+    def frame_reject_against(self, idx, model_idx, low, high):
+        """(n_low, n_high): the pixels of slot idx more than `low` below or `high` above the model in slot model_idx
+        become NaN (absolute thresholds >= 0), which a drizzle skips; everything else keeps its bits."""
+        n_low, n_high = C.c_int64(0), C.c_int64(0)
+        capi.check(self._lib.nl_stack_frame_reject_against(self._h, int(idx), int(model_idx), float(low), float(high),
+                                                           C.byref(n_low), C.byref(n_high)))
+        return int(n_low.value), int(n_high.value)
+
+    def drizzle_tile_paths(self, src, src_idx, trans, scale, pixfrac=1.0):
+        """project_tile_paths for frame_drizzle_from(., ., src, src_idx, trans, scale, pixfrac) (developer query)."""
+        t = np.ascontiguousarray(trans, dtype=np.float32).reshape(6)
+        staged, direct = C.c_int64(0), C.c_int64(0)
+        capi.check(self._lib.nl_stack_drizzle_tile_paths(self._h, src._h, int(src_idx), capi.fptr(t), float(scale),
+                                                         float(pixfrac), C.byref(staged), C.byref(direct)))
+        return int(staged.value), int(direct.value)
+
     def download_result_fits(self):
         raw = np.empty(self.tile_pixels * 4, np.uint8)
         capi.check(self._lib.nl_stack_download_result_fits(self._h, raw.ctypes.data_as(C.c_void_p)))
@@ -1253,6 +1286,17 @@ def lanczos3_table():
     table = np.empty((capi.RS_PHASES, 6), np.float32)
     capi.check(capi.load().nl_resample_lanczos3_table(capi.fptr(table)))
     return table
+
+
+def drizzle_geometry(trans, scale, pixfrac=1.0):
+    """(src_to_out, out_to_src, half_width, radius) of a drizzle of the forward transform `trans` onto a grid of
+    `scale` pixels per reference pixel with drops of `pixfrac` (include/nlstack_drizzle.h; host only, no device)."""
+    t = np.ascontiguousarray(trans, dtype=np.float32).reshape(6)
+    f, g = np.empty(6, np.float32), np.empty(6, np.float32)
+    hw, radius = C.c_float(0.0), C.c_int(0)
+    capi.check(capi.load().nl_drizzle_geometry(capi.fptr(t), float(scale), float(pixfrac), capi.fptr(f), capi.fptr(g),
+                                               C.byref(hw), C.byref(radius)))
+    return f, g, np.float32(hw.value), int(radius.value)
 
 
 def blur_tap_paths(n_taps):
