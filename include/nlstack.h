@@ -731,6 +731,11 @@ int nl_stack_project_tile_paths(nl_stack_t *dst, nl_stack_t *src, int src_idx, c
  * nl_stack_drizzle_tile_paths are declared in nlstack_drizzle.h, which is part of this interface. */
 #include "nlstack_drizzle.h"
 
+/* CFA drizzle: a raw Bayer mosaic laid onto one colour plane with no debayer in front (AN EXTENSION):
+ * nl_drizzle_cfa_transform, nl_stack_frame_drizzle_cfa_from, nl_stack_frame_reject_against_cfa and
+ * nl_stack_frame_badpixel_cfa are declared in nlstack_cfadrizzle.h, which is part of this interface. */
+#include "nlstack_cfadrizzle.h"
+
 /* ---- OpGaussianBlur / OpUnsharpMask / OpHSLUnsharpMask's UnsharpMask ----
  * (internal/ops/stretch/stretch.go:339-424, internal/ops/stretch/usm.go, internal/ops/hsl/hsl.go:538-551)
  * The two passes of GaussFilter2D (usm.go:118-122): Convolve1DX (usm.go:85-98) into a scratch frame of the

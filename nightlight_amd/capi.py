@@ -140,6 +140,11 @@ DRIZZLE_EXPORTS = ["nl_drizzle_geometry", "nl_stack_frame_drizzle_from", "nl_sta
 DZ_TURBO, DZ_POINT = range(2)
 DZ_MAX_RADIUS = 3
 
+# every symbol include/nlstack_cfadrizzle.h declares (likewise): CFA drizzle -- a raw Bayer mosaic laid onto one colour
+# plane with no debayer in front -- and the resident rejection and bad-pixel steps of a mosaic, an extension
+CFADRIZZLE_EXPORTS = ["nl_drizzle_cfa_transform", "nl_stack_frame_drizzle_cfa_from", "nl_stack_frame_reject_against_cfa",
+                      "nl_stack_frame_badpixel_cfa"]
+
 # nl_star_t = star.Star (findstars.go:30-37), 24 bytes
 STAR_DTYPE = np.dtype([("index", "<i4"), ("value", "<f4"), ("x", "<f4"), ("y", "<f4"), ("mass", "<f4"),
                        ("hfr", "<f4")])
@@ -457,6 +462,11 @@ def open_library(path):
     L.nl_stack_drizzle_finalize.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float]
     L.nl_stack_frame_reject_against.argtypes = [vp, C.c_int, C.c_int, C.c_float, C.c_float, _i64p, _i64p]
     L.nl_stack_drizzle_tile_paths.argtypes = [vp, vp, C.c_int, _f32p, C.c_float, C.c_float, _i64p, _i64p]
+    L.nl_drizzle_cfa_transform.argtypes = [_f32p, C.c_char_p, _f32p]
+    L.nl_stack_frame_drizzle_cfa_from.argtypes = L.nl_stack_frame_drizzle_from.argtypes + [C.c_char_p, C.c_char_p]
+    L.nl_stack_frame_reject_against_cfa.argtypes = [vp, C.c_int, C.c_int, C.c_char_p, C.c_char_p, C.c_float, C.c_float,
+                                                    _i64p, _i64p]
+    L.nl_stack_frame_badpixel_cfa.argtypes = [vp, C.c_int, C.c_char_p, C.c_char_p, C.c_float, C.c_float, _i64p, _f32p]
     _planes = C.POINTER(C.c_int)
     # stars, n_stars, block, border, skip_bright, skip_dim, shadows, highlights, loc, scale, report
     _balance_args = [vp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, Rgb, Rgb, _f32p, _f32p, C.POINTER(RgbBalance)]

@@ -66,29 +66,8 @@ __device__ __forceinline__ void drizzle_rows(const float *__restrict__ mem, int 
                     for (int di = 0; di <= 2 * R; di++) {
                         const int i = xi + di - R;
                         const float fi = (float)i;
-                        const float u = proj_x(q.f, fi, fj), vv = proj_y(q.f, fi, fj);
                         bool ok = (unsigned)i < (unsigned)src_w && (unsigned)j < (unsigned)src_h;
-                        if constexpr (POINT) {
-                            ok = ok && floorf(u + 0.5f) == px && floorf(vv + 0.5f) == py;
-                            wa[dj][di] = ok ? weight : __builtin_nanf("");
-                        } else {
-                            float lo = u - q.hw, e = px - 0.5f;
-                            if (e > lo) lo = e;
-                            float hi = u + q.hw;
-                            e = px + 0.5f;
-                            if (e < hi) hi = e;
-                            const float ox = hi - lo;
-                            lo = vv - q.hw;
-                            e = py - 0.5f;
-                            if (e > lo) lo = e;
-                            hi = vv + q.hw;
-                            e = py + 0.5f;
-                            if (e < hi) hi = e;
-                            const float oy = hi - lo;
-                            ok = ok && ox > 0.0f && oy > 0.0f;
-                            const float ar = ox * oy;
-                            wa[dj][di] = ok ? weight * ar : __builtin_nanf("");
-                        }
+                        wa[dj][di] = dz_candidate_weight<POINT>(q, fi, fj, px, py, weight, ok);
                         const Index p = ok ? (Index)(j - org_y) * pitch + (Index)(i - org_x) : (Index)0;
                         v[dj][di] = mem[p];
                     }
@@ -131,13 +110,6 @@ __global__ __launch_bounds__(256) void drizzle_tile_kernel(const float *__restri
     } else {
         drizzle_rows<R, POINT, int64_t>(src, 0, 0, src_w, src_w, src_h, sum, wgt, dst_w, row0, c0, r0, r_end, q, weight, first);
     }
-}
-
-// bits 0 / 1 of the kernel's flags (project.hip's rule; the geometry's coefficients are finite)
-unsigned tile_flags(const float *src, int src_w, unsigned switches)
-{
-    const bool vec = (src_w & 3) == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0;
-    return (vec ? 1u : 0u) | (!(switches & kProjDirectOnly) ? 2u : 0u);
 }
 
 __global__ __launch_bounds__(256) void drizzle_finalize_kernel(const float *sum, const float *wgt, float *out, int64_t n,
@@ -183,7 +155,7 @@ hipError_t launch_drizzle(const float *src, int src_w, int src_h, float *sum, fl
                           const DzGeom &geom, float weight, bool first, bool point, unsigned switches, hipStream_t stream)
 {
     const dim3 grid((unsigned)((dst_w + kProjTileW - 1) / kProjTileW), (unsigned)((rows + kProjTileH - 1) / kProjTileH));
-    const unsigned flags = tile_flags(src, src_w, switches) | (first ? 4u : 0u);
+    const unsigned flags = dz_tile_flags(src, src_w, switches) | (first ? 4u : 0u);
     Launcher L(stream);
     with_class<1, 2, 3>(geom.radius, [&](auto R) {
         with_bool(point, [&](auto P) {
@@ -197,7 +169,7 @@ hipError_t launch_drizzle(const float *src, int src_w, int src_h, float *sum, fl
 void drizzle_tile_paths(const float *src, int src_w, int src_h, int dst_w, int row0, int rows, const DzGeom &geom,
                         unsigned switches, int64_t *staged, int64_t *direct)
 {
-    const unsigned flags = tile_flags(src, src_w, switches);
+    const unsigned flags = dz_tile_flags(src, src_w, switches);
     int64_t n_staged = 0, n_direct = 0;
     for (int r0 = 0; r0 < rows; r0 += kProjTileH)
         for (int c0 = 0; c0 < dst_w; c0 += kProjTileW) {

@@ -1,4 +1,4 @@
-// drizzle.hpp -- what drizzle.hip's kernels, its launchers and the entries (nlstack_drizzle.hip) share: the geometry of
+// drizzle.hpp -- what the kernels of drizzle.hip and drizzle_cfa.hip, their launchers and the entries (nlstack_drizzle.hip) share: the geometry of
 // include/nlstack_drizzle.h as the kernel takes it, the candidate box of an output tile -- the one piece of arithmetic
 // host and device both run (the same fp32 operations, no contraction on either side, so drizzle_tile_paths() counts
 // exactly the tiles the kernel stages) -- and the launchers.  ProjInv, ProjBox, stage_box and the tile shape are
@@ -9,6 +9,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "bayer.hpp"
 #include "project.hpp"
 
 namespace nl {
@@ -71,6 +72,79 @@ __host__ __device__ inline bool dz_tile_box(const ProjInv &g, int radius, int sr
     b.pitch = b.w | 1;                                     // odd, as proj_tile_box: a quarter turn spreads over the banks
     return (int64_t)b.pitch * b.h <= kDzLdsFloats;
 }
+
+// One candidate of the definition, what drizzle.hip's and drizzle_cfa.hip's walks share: the weight wa that source
+// pixel (fi, fj) lays onto output pixel (px, py), in the header's operand order.  ok comes in as "a pixel the walk
+// takes" (inside the source; of the channel) and leaves as "a candidate": a NaN weight marks the ones that are not.
+template <bool POINT>
+__device__ __forceinline__ float dz_candidate_weight(const DzGeom &q, float fi, float fj, float px, float py, float weight,
+                                                     bool &ok)
+{
+    const float u = proj_x(q.f, fi, fj), vv = proj_y(q.f, fi, fj);
+    if constexpr (POINT) {
+        ok = ok && floorf(u + 0.5f) == px && floorf(vv + 0.5f) == py;
+        return ok ? weight : __builtin_nanf("");
+    } else {
+        float lo = u - q.hw, e = px - 0.5f;
+        if (e > lo) lo = e;
+        float hi = u + q.hw;
+        e = px + 0.5f;
+        if (e < hi) hi = e;
+        const float ox = hi - lo;
+        lo = vv - q.hw;
+        e = py - 0.5f;
+        if (e > lo) lo = e;
+        hi = vv + q.hw;
+        e = py + 0.5f;
+        if (e < hi) hi = e;
+        const float oy = hi - lo;
+        ok = ok && ox > 0.0f && oy > 0.0f;
+        const float ar = ox * oy;
+        return ok ? weight * ar : __builtin_nanf("");
+    }
+}
+
+// bits 0 / 1 of the tile kernels' flags (project.hip's rule; the geometry's coefficients are finite): the source allows
+// 16-byte loads, tiles may stage their box
+inline unsigned dz_tile_flags(const float *src, int src_w, unsigned switches)
+{
+    const bool vec = (src_w & 3) == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0;
+    return (vec ? 1u : 0u) | (!(switches & kProjDirectOnly) ? 2u : 0u);
+}
+
+// The pixels of one channel of a raw mosaic (include/nlstack_cfadrizzle.h): (i, j) with i >= xo, j >= yo and, for R and
+// B, i of parity par_x and j of parity par_y; for G, i + j of parity par_x.  Parities are taken with & 1, which holds
+// for the negative window starts of a frame partly outside the grid as well (two's complement); % would not.
+struct DzChannel {
+    int xo, yo;            // getOffsets (debayer.go:26-37)
+    int green;             // 1 for G
+    int par_x, par_y;
+};
+
+// channel: bayer.hpp's BayerChannel
+inline DzChannel dz_channel(int channel, int xo, int yo)
+{
+    if (channel == kBayerG) return {xo, yo, 1, (xo + yo + 1) & 1, 0};
+    const int b = channel == kBayerB ? 1 : 0;
+    return {xo, yo, 0, (xo + b) & 1, (yo + b) & 1};
+}
+
+__host__ __device__ inline bool dz_channel_has(const DzChannel &c, int i, int j)
+{
+    const bool par = c.green ? ((i + j) & 1) == c.par_x : ((i & 1) == c.par_x && (j & 1) == c.par_y);
+    return i >= c.xo && j >= c.yo && par;
+}
+
+// ---- drizzle_cfa.hip ----
+// nl_stack_frame_drizzle_cfa_from's kernel: launch_drizzle over the pixels of channel ch of the mosaic src only, the
+// strided walk of the window
+hipError_t launch_drizzle_cfa(const float *src, int src_w, int src_h, float *sum, float *wgt, int dst_w, int row0, int rows,
+                              const DzGeom &geom, float weight, bool first, bool point, const DzChannel &ch,
+                              unsigned switches, hipStream_t stream);
+// nl_stack_frame_reject_against_cfa's kernel: launch_reject_against on the channel's pixels of the rows [row0, row0 +
+// rows) of a width wide mosaic
+hipError_t launch_reject_against_cfa(float *frame, const float *model, int width, int row0, int rows, const DzChannel &ch,
+                                     float low, float high, unsigned long long *counts, int blocks, hipStream_t stream);
 
 // ---- drizzle.hip ----
 // nl_stack_frame_drizzle_from's kernel: the rows [row0, row0 + rows) of a dst_w wide output grid; sum / wgt = the two

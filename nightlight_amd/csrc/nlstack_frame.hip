@@ -7,6 +7,7 @@
 
 #include <algorithm>
 
+#include "bayer.hpp"
 #include "nlstack_frame_common.hpp"
 
 namespace {
@@ -111,6 +112,30 @@ int nl::need_whole_frame(const nl_stack_t *h, const char *who, const char *why)
 {
     const int rc = need_whole_image(h, who, why);
     return rc == NL_OK ? need_int32_pixels(h->npix, who) : rc;
+}
+
+// getOffsets (debayer.go:26-37)
+int nl::cfa_offsets(const char *cfa, int *xo, int *yo)
+{
+    const std::string c = cfa;
+    if (c == "RGGB" || c == "rggb") { *xo = 0; *yo = 0; }
+    else if (c == "GRBG" || c == "grbg") { *xo = 1; *yo = 0; }
+    else if (c == "GBRG" || c == "gbrg") { *xo = 0; *yo = 1; }
+    else if (c == "BGGR" || c == "bggr") { *xo = 1; *yo = 1; }
+    else return fail(NL_ERR_INVALID_ARG, "Unknown CFA value %s", cfa);
+    return NL_OK;
+}
+
+int nl::cfa_names(const char *channel, const char *cfa, int *ch, int *xo, int *yo)
+{
+    if (const int rc = cfa_offsets(cfa, xo, yo); rc != NL_OK) return rc;
+    // the channel switch of CosmeticCorrectionBayer / DebayerBilinear (badpixels_bayer.go:36-45, debayer.go:47-59)
+    const std::string c = channel;
+    if (c == "R" || c == "r") *ch = nl::kBayerR;
+    else if (c == "G" || c == "g") *ch = nl::kBayerG;
+    else if (c == "B" || c == "b") *ch = nl::kBayerB;
+    else return fail(NL_ERR_INVALID_ARG, "Unknown debayering value %s", channel);
+    return NL_OK;
 }
 
 int nl::check_capacity(const char *who, int capacity, const void *ptr)

@@ -21,6 +21,11 @@ int need_whole_frame(const nl_stack_t *h, const char *who, const char *why);
 int check_capacity(const char *who, int capacity, const void *ptr);
 int check_stars(const char *who, const nl_star_t *stars, int n_stars);
 int export_check(const char *who, float gamma, int bits, const void *out_host);
+// The names of the colour-camera entries (neither null): the CFA, then the channel, as the reference checks them --
+// "Unknown CFA value <cfa>", "Unknown debayering value <channel>".  (*xo, *yo) = getOffsets (debayer.go:26-37); *ch =
+// bayer.hpp's BayerChannel (kBayerR / kBayerG / kBayerB)
+int cfa_offsets(const char *cfa, int *xo, int *yo);
+int cfa_names(const char *channel, const char *cfa, int *ch, int *xo, int *yo);
 
 // What a reduction enqueued on h->stream leaves in h->d_stat_partial; each waits for the stream.  The kStatBlocks
 // per-block fp64 sums added from block 0 on (the order is part of the result's bits):
@@ -56,6 +61,6 @@ int export_impl(nl_stack_t *h, const float *gray, const Planes *rgb, float min, 
 
 }  // namespace nl
 
-using nl::check_capacity, nl::check_stars, nl::export_check, nl::export_impl, nl::frame_stats_impl, nl::host_frames_run,
+using nl::cfa_names, nl::cfa_offsets, nl::check_capacity, nl::check_stars, nl::export_check, nl::export_impl, nl::frame_stats_impl, nl::host_frames_run,
     nl::min_mean_max_from_partials, nl::need_int32_pixels, nl::need_whole_frame, nl::need_whole_image, nl::resident_entry, nl::resident_target,
     nl::sum_stat_partials;

@@ -193,36 +193,11 @@ int nl_preprocess_frame(const nl_calib_t *c, int frame_id, const float *in_host,
 
 // ---- OpBadPixel, Bayer branch, and OpDebayer (internal/ops/pre/preprocess.go:180-251; kernels in bayer.hip) -------
 
-// getOffsets (debayer.go:26-37)
-static int cfa_offsets(const char *cfa, int *xo, int *yo)
-{
-    const std::string c = cfa;
-    if (c == "RGGB" || c == "rggb") { *xo = 0; *yo = 0; }
-    else if (c == "GRBG" || c == "grbg") { *xo = 1; *yo = 0; }
-    else if (c == "GBRG" || c == "gbrg") { *xo = 0; *yo = 1; }
-    else if (c == "BGGR" || c == "bggr") { *xo = 1; *yo = 1; }
-    else return fail(NL_ERR_INVALID_ARG, "Unknown CFA value %s", cfa);
-    return NL_OK;
-}
-
-// the channel switch of CosmeticCorrectionBayer / DebayerBilinear (badpixels_bayer.go:36-45, debayer.go:47-59)
-static int cfa_channel(const char *channel, int *ch)
-{
-    const std::string c = channel;
-    if (c == "R" || c == "r") *ch = nl::kBayerR;
-    else if (c == "G" || c == "g") *ch = nl::kBayerG;
-    else if (c == "B" || c == "b") *ch = nl::kBayerB;
-    else return fail(NL_ERR_INVALID_ARG, "Unknown debayering value %s", channel);
-    return NL_OK;
-}
-
-// the CFA, then the channel, as the reference checks them; the output shape of DebayerBilinear (debayer.go:65-66)
+// the names (cfa_names of nlstack_frame_common.hpp), then the output shape of DebayerBilinear (debayer.go:65-66)
 static int cfa_parse(const char *channel, const char *cfa, int width, int height, int *ch, int *xo, int *yo,
                      int *out_w, int *out_h)
 {
-    int rc = cfa_offsets(cfa, xo, yo);
-    if (rc == NL_OK) rc = cfa_channel(channel, ch);
-    if (rc != NL_OK) return rc;
+    if (const int rc = cfa_names(channel, cfa, ch, xo, yo); rc != NL_OK) return rc;
     *out_w = (width - *xo) & ~1;
     *out_h = (height - *yo) & ~1;
     if ((int64_t)*out_w * *out_h == 0)        // (the reference divides by the width 0 at preprocess.go:245)

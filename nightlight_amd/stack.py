@@ -711,6 +711,34 @@ class StackHandle:
                                                          float(pixfrac), C.byref(staged), C.byref(direct)))
         return int(staged.value), int(direct.value)
 
+    def frame_drizzle_cfa_from(self, sum_idx, wgt_idx, src, src_idx, trans, scale, channel, cfa="RGGB", pixfrac=1.0,
+                               weight=1.0, first=False, kernel=capi.DZ_TURBO):
+        """CFA drizzle: frame_drizzle_from for the pixels of `channel` ("R", "G", "B") of the raw `cfa` mosaic in slot
+        src_idx of the whole-image handle `src`, no debayer in front; `trans` maps mosaic pixels to reference pixels
+        (drizzle_cfa_transform).  The planes equal those of frame_drizzle_from on a copy of the mosaic whose other
+        pixels are NaN (include/nlstack_cfadrizzle.h; an EXTENSION)."""
+        t = np.ascontiguousarray(trans, dtype=np.float32).reshape(6)
+        capi.check(self._lib.nl_stack_frame_drizzle_cfa_from(self._h, int(sum_idx), int(wgt_idx), src._h, int(src_idx),
+                                                             capi.fptr(t), float(scale), float(pixfrac), float(weight),
+                                                             int(bool(first)), int(kernel), _cstr(channel), _cstr(cfa)))
+
+    def frame_reject_against_cfa(self, idx, model_idx, channel, cfa, low, high):
+        """(n_low, n_high): frame_reject_against on the pixels of `channel` of the `cfa` mosaic in slot idx; every
+        other pixel keeps its bits and counts nowhere."""
+        n_low, n_high = C.c_int64(0), C.c_int64(0)
+        capi.check(self._lib.nl_stack_frame_reject_against_cfa(self._h, int(idx), int(model_idx), _cstr(channel),
+                                                               _cstr(cfa), float(low), float(high), C.byref(n_low),
+                                                               C.byref(n_high)))
+        return int(n_low.value), int(n_high.value)
+
+    def frame_badpixel_cfa(self, idx, channel, cfa="RGGB", sigma_low=3.0, sigma_high=5.0):
+        """CosmeticCorrectionBayer for one channel in place on the resident mosaic in slot idx of a whole-image
+        handle: upload_frame_cfa's bad-pixel step without the debayer.  Returns (removed, (delta_mean, delta_std))."""
+        removed, stats = C.c_int64(0), (C.c_float * 2)()
+        capi.check(self._lib.nl_stack_frame_badpixel_cfa(self._h, int(idx), _cstr(channel), _cstr(cfa),
+                                                         float(sigma_low), float(sigma_high), C.byref(removed), stats))
+        return int(removed.value), (np.float32(stats[0]), np.float32(stats[1]))
+
     def download_result_fits(self):
         raw = np.empty(self.tile_pixels * 4, np.uint8)
         capi.check(self._lib.nl_stack_download_result_fits(self._h, raw.ctypes.data_as(C.c_void_p)))
@@ -1297,6 +1325,16 @@ def drizzle_geometry(trans, scale, pixfrac=1.0):
     capi.check(capi.load().nl_drizzle_geometry(capi.fptr(t), float(scale), float(pixfrac), capi.fptr(f), capi.fptr(g),
                                                C.byref(hw), C.byref(radius)))
     return f, g, np.float32(hw.value), int(radius.value)
+
+
+def drizzle_cfa_transform(trans_debayered, cfa):
+    """The forward transform of the raw `cfa` mosaic that belongs to `trans_debayered`, a transform estimated on a
+    plane debayered from it: plane pixel (x, y) is mosaic pixel (x + xo, y + yo) (include/nlstack_cfadrizzle.h; host
+    only, no device)."""
+    t = np.ascontiguousarray(trans_debayered, dtype=np.float32).reshape(6)
+    out = np.empty(6, np.float32)
+    capi.check(capi.load().nl_drizzle_cfa_transform(capi.fptr(t), _cstr(cfa), capi.fptr(out)))
+    return out
 
 
 def blur_tap_paths(n_taps):
