@@ -736,6 +736,11 @@ int nl_stack_project_tile_paths(nl_stack_t *dst, nl_stack_t *src, int src_idx, c
  * nl_stack_frame_badpixel_cfa are declared in nlstack_cfadrizzle.h, which is part of this interface. */
 #include "nlstack_cfadrizzle.h"
 
+/* Square drizzle: the exact overlap of a rotated drop with an output pixel, mono and CFA (AN EXTENSION):
+ * nl_drizzle_square_geometry, nl_stack_frame_drizzle_square_from, nl_stack_frame_drizzle_square_cfa_from and
+ * nl_stack_drizzle_square_tile_paths are declared in nlstack_sqdrizzle.h, which is part of this interface. */
+#include "nlstack_sqdrizzle.h"
+
 /* ---- OpGaussianBlur / OpUnsharpMask / OpHSLUnsharpMask's UnsharpMask ----
  * (internal/ops/stretch/stretch.go:339-424, internal/ops/stretch/usm.go, internal/ops/hsl/hsl.go:538-551)
  * The two passes of GaussFilter2D (usm.go:118-122): Convolve1DX (usm.go:85-98) into a scratch frame of the

@@ -11,7 +11,7 @@ from .capi import (CHROMA_FOR_HUES, CHROMA_GAMMA, CHROMA_NEUTRALIZE, DZ_MAX_RADI
                    TONE_SCALE_OFFSET, TONE_SHIFT_BLACK, WEIGHT_EXPOSURE, WEIGHT_INVERSE_HFR,
                    WEIGHT_INVERSE_NOISE, WEIGHT_NONE, device_count)
 from .stack import (Aligner, Calibration, StackGroup, StackHandle, back_extract, bin_nxn, bin_shape, blur_tap_paths,  # noqa: F401
-                    convolve_separable, debayer_shape, drizzle_cfa_transform, drizzle_geometry, deband_horiz, deband_vert, export_gray, export_rgb, find_stars, fits_padded_bytes,
+                    convolve_separable, debayer_shape, drizzle_cfa_transform, drizzle_geometry, drizzle_square_geometry, deband_horiz, deband_vert, export_gray, export_rgb, find_stars, fits_padded_bytes,
                     fits_parse_header, fits_write_header, gaussian_blur, gaussian_kernel_1d, lanczos3_table, location_scale, locscale_seeds,
                     median_filter_3x3,
                     median_filter_mask, preprocess_frame, preprocess_frame_cfa, rgb_balance, rgb_balance_coeffs,

@@ -145,6 +145,11 @@ DZ_MAX_RADIUS = 3
 CFADRIZZLE_EXPORTS = ["nl_drizzle_cfa_transform", "nl_stack_frame_drizzle_cfa_from", "nl_stack_frame_reject_against_cfa",
                       "nl_stack_frame_badpixel_cfa"]
 
+# every symbol include/nlstack_sqdrizzle.h declares (likewise): the square drizzle kernel -- the exact overlap of a
+# rotated drop with an output pixel -- for mono frames and for one channel of a mosaic, an extension
+SQDRIZZLE_EXPORTS = ["nl_drizzle_square_geometry", "nl_stack_frame_drizzle_square_from",
+                     "nl_stack_frame_drizzle_square_cfa_from", "nl_stack_drizzle_square_tile_paths"]
+
 # nl_star_t = star.Star (findstars.go:30-37), 24 bytes
 STAR_DTYPE = np.dtype([("index", "<i4"), ("value", "<f4"), ("x", "<f4"), ("y", "<f4"), ("mass", "<f4"),
                        ("hfr", "<f4")])
@@ -464,6 +469,10 @@ def open_library(path):
     L.nl_stack_drizzle_tile_paths.argtypes = [vp, vp, C.c_int, _f32p, C.c_float, C.c_float, _i64p, _i64p]
     L.nl_drizzle_cfa_transform.argtypes = [_f32p, C.c_char_p, _f32p]
     L.nl_stack_frame_drizzle_cfa_from.argtypes = L.nl_stack_frame_drizzle_from.argtypes + [C.c_char_p, C.c_char_p]
+    L.nl_drizzle_square_geometry.argtypes = [_f32p, C.c_float, C.c_float, _f32p, _f32p, _f32p, _f32p, _intp]
+    L.nl_stack_frame_drizzle_square_from.argtypes = L.nl_stack_frame_drizzle_from.argtypes[:-1]
+    L.nl_stack_frame_drizzle_square_cfa_from.argtypes = L.nl_stack_frame_drizzle_square_from.argtypes + [C.c_char_p, C.c_char_p]
+    L.nl_stack_drizzle_square_tile_paths.argtypes = L.nl_stack_drizzle_tile_paths.argtypes
     L.nl_stack_frame_reject_against_cfa.argtypes = [vp, C.c_int, C.c_int, C.c_char_p, C.c_char_p, C.c_float, C.c_float,
                                                     _i64p, _i64p]
     L.nl_stack_frame_badpixel_cfa.argtypes = [vp, C.c_int, C.c_char_p, C.c_char_p, C.c_float, C.c_float, _i64p, _f32p]

@@ -7,7 +7,8 @@
 // source position in a fixed order and adds the overlap of each one's drop with itself.  No atomics, so the planes are
 // deterministic, and a frame is laid down in one pass over the output.
 //
-// The structure is project.hip's.  A workgroup owns a kProjTileW x kProjTileH tile of the output; wave w makes rows w,
+// The structure is project.hip's (the walk itself is written once, in drizzle_walk.hpp, for this unit, drizzle_cfa.hip
+// and drizzle_square.hip; this unit gives it the weight of a NL_DZ_TURBO / NL_DZ_POINT candidate).  A workgroup owns a kProjTileW x kProjTileH tile of the output; wave w makes rows w,
 // w + 4, ... of it, lane l the columns l, l + 64, l + 128, l + 192 of a row, so every load and store of the two planes
 // covers 256 contiguous bytes per wave.  From the four corners of its tile (drizzle.hpp) the workgroup computes the
 // candidate box of the tile; it stages the box in LDS (each source byte fetched once, 16 bytes per lane where the
@@ -24,6 +25,7 @@
 #include <math.h>
 
 #include "drizzle.hpp"
+#include "drizzle_walk.hpp"
 #include "frame_common.hpp"
 #include "launch_common.hpp"
 
@@ -31,85 +33,14 @@ namespace nl {
 
 namespace {
 
-// rows of the tile for this wave, four pixels per lane and row.  mem = the box in LDS (origin org_x, org_y, pitch
-// b.pitch) or the source itself (origin 0, 0, pitch src_w).
-template <int R, bool POINT, class Index>
-__device__ __forceinline__ void drizzle_rows(const float *__restrict__ mem, int org_x, int org_y, Index pitch, int src_w,
-                                             int src_h, float *__restrict__ sum, float *__restrict__ wgt, int dst_w,
-                                             int row0, int c0, int r_first, int r_end, const DzGeom &q, float weight,
-                                             bool first)
-{
-    const int lane = threadIdx.x & 63;
-    // xc in [-R, src_w - 1 + R] or the window misses the source (the bound may round up: every candidate is tested)
-    const float x_last = fminf((float)src_w + (float)R, 2147483520.0f), y_last = fminf((float)src_h + (float)R, 2147483520.0f);
-    for (int r = r_first + (int)(threadIdx.x >> 6); r < r_end; r += 4) {
-        const float py = (float)(row0 + r);
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const int col = c0 + lane + 64 * k;
-            if (col >= dst_w) continue;
-            const float px = (float)col;
-            const float X = proj_x(q.g, px, py), Y = proj_y(q.g, px, py);
-            const float xc = floorf(X + 0.5f), yc = floorf(Y + 0.5f);
-            const int64_t at = (int64_t)r * dst_w + col;
-            float s = 0.0f, t = 0.0f;
-            if (!first) { s = sum[at]; t = wgt[at]; }
-            // (a NaN fails every comparison: no candidates)
-            if (xc >= -(float)R && xc <= x_last && yc >= -(float)R && yc <= y_last) {
-                const int xi = (int)xc, yi = (int)yc;
-                float v[2 * R + 1][2 * R + 1], wa[2 * R + 1][2 * R + 1];
-#pragma unroll
-                for (int dj = 0; dj <= 2 * R; dj++) {
-                    const int j = yi + dj - R;
-                    const float fj = (float)j;
-#pragma unroll
-                    for (int di = 0; di <= 2 * R; di++) {
-                        const int i = xi + di - R;
-                        const float fi = (float)i;
-                        bool ok = (unsigned)i < (unsigned)src_w && (unsigned)j < (unsigned)src_h;
-                        wa[dj][di] = dz_candidate_weight<POINT>(q, fi, fj, px, py, weight, ok);
-                        const Index p = ok ? (Index)(j - org_y) * pitch + (Index)(i - org_x) : (Index)0;
-                        v[dj][di] = mem[p];
-                    }
-                }
-#pragma unroll
-                for (int dj = 0; dj <= 2 * R; dj++) {
-#pragma unroll
-                    for (int di = 0; di <= 2 * R; di++) {
-                        const float x = v[dj][di];
-                        const bool ok = x == x && wa[dj][di] == wa[dj][di]; // NaN = no data; a NaN weight = no candidate
-                        const float sn = s + x * wa[dj][di], tn = t + wa[dj][di];
-                        s = ok ? sn : s;
-                        t = ok ? tn : t;
-                    }
-                }
-            }
-            sum[at] = s;
-            wgt[at] = t;
-        }
-    }
-}
-
-// flags: bit 0 = the source allows 16-byte loads, bit 1 = tiles may stage their box, bit 2 = first
+// flags: drizzle_walk.hpp's drizzle_tile
 template <int R, bool POINT>
 __global__ __launch_bounds__(256) void drizzle_tile_kernel(const float *__restrict__ src, int src_w, int src_h,
                                                            float *__restrict__ sum, float *__restrict__ wgt, int dst_w,
                                                            int row0, int rows, DzGeom q, float weight, unsigned flags)
 {
     __shared__ float lds[kDzLdsFloats];
-    const int c0 = blockIdx.x * kProjTileW, r0 = blockIdx.y * kProjTileH;
-    const int c1 = min(c0 + kProjTileW, dst_w) - 1, r_end = min(r0 + kProjTileH, rows);
-    const bool vec = flags & 1u, first = flags & 4u;
-    ProjBox b = {0, 0, 0, 0, 0};
-    const bool staged = (flags & 2u) && dz_tile_box(q.g, R, src_w, src_h, c0, c1, row0 + r0, row0 + r_end - 1, vec, b);
-    if (staged) {                                                            // (uniform over the workgroup)
-        if (vec) stage_box<true>(src, src_w, b, lds);
-        else stage_box<false>(src, src_w, b, lds);
-        __syncthreads();
-        drizzle_rows<R, POINT, int>(lds, b.x0, b.y0, b.pitch, src_w, src_h, sum, wgt, dst_w, row0, c0, r0, r_end, q, weight, first);
-    } else {
-        drizzle_rows<R, POINT, int64_t>(src, 0, 0, src_w, src_w, src_h, sum, wgt, dst_w, row0, c0, r0, r_end, q, weight, first);
-    }
+    drizzle_tile<R>(lds, src, src_w, src_h, sum, wgt, dst_w, row0, rows, q.g, DzDrop<POINT>{q, weight}, flags);
 }
 
 __global__ __launch_bounds__(256) void drizzle_finalize_kernel(const float *sum, const float *wgt, float *out, int64_t n,

@@ -1,4 +1,4 @@
-// drizzle.hpp -- what the kernels of drizzle.hip and drizzle_cfa.hip, their launchers and the entries (nlstack_drizzle.hip) share: the geometry of
+// drizzle.hpp -- what the kernels of drizzle.hip, drizzle_cfa.hip and drizzle_square.hip, their launchers and the entries (nlstack_drizzle.hip) share: the geometry of
 // include/nlstack_drizzle.h as the kernel takes it, the candidate box of an output tile -- the one piece of arithmetic
 // host and device both run (the same fp32 operations, no contraction on either side, so drizzle_tile_paths() counts
 // exactly the tiles the kernel stages) -- and the launchers.  ProjInv, ProjBox, stage_box and the tile shape are
@@ -23,6 +23,15 @@ struct DzGeom {
     ProjInv f, g;
     float hw;
     int radius;
+};
+
+// what nl_drizzle_square_geometry adds (include/nlstack_sqdrizzle.h): the corners of a drop relative to its centre, in
+// output pixels and in the order that makes the edge sum positive, and the half-sides of the drop's bounding box.  It
+// travels beside DzGeom (whose radius is then the square R), so that the kernels of drizzle.hip and drizzle_cfa.hip keep
+// their arguments.
+struct DzSquare {
+    float cx[4], cy[4];
+    float bx, by;
 };
 
 // floor(v + 0.5f) as an int where it matters: anything below -8 is -8 (its window of radius <= 3 ends in front of
@@ -145,6 +154,19 @@ hipError_t launch_drizzle_cfa(const float *src, int src_w, int src_h, float *sum
 // rows) of a width wide mosaic
 hipError_t launch_reject_against_cfa(float *frame, const float *model, int width, int row0, int rows, const DzChannel &ch,
                                      float low, float high, unsigned long long *counts, int blocks, hipStream_t stream);
+
+// ---- drizzle_square.hip ----
+// nl_stack_frame_drizzle_square_from's kernel: launch_drizzle with the exact overlap of the rotated drop as a
+// candidate's area.  switches: kProjDirectOnly, and kDzSquareEveryCandidate (developer switch 262144 of
+// nl_stack_set_dev_flags) = the four edges of every candidate are evaluated, none skipped wave by wave; the same bits
+constexpr unsigned kDzSquareEveryCandidate = 4u;
+hipError_t launch_drizzle_square(const float *src, int src_w, int src_h, float *sum, float *wgt, int dst_w, int row0,
+                                 int rows, const DzGeom &geom, const DzSquare &sq, float weight, bool first,
+                                 unsigned switches, hipStream_t stream);
+// nl_stack_frame_drizzle_square_cfa_from's: launch_drizzle_cfa likewise
+hipError_t launch_drizzle_square_cfa(const float *src, int src_w, int src_h, float *sum, float *wgt, int dst_w, int row0,
+                                     int rows, const DzGeom &geom, const DzSquare &sq, float weight, bool first,
+                                     const DzChannel &ch, unsigned switches, hipStream_t stream);
 
 // ---- drizzle.hip ----
 // nl_stack_frame_drizzle_from's kernel: the rows [row0, row0 + rows) of a dst_w wide output grid; sum / wgt = the two

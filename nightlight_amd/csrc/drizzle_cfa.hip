@@ -4,7 +4,7 @@
 // candidate that is not a pixel of the channel is skipped -- which these kernels compute bit for bit.
 //
 // A sibling of drizzle.hip's tile kernel in a unit of its own, so that the six mono instantiations keep their code
-// (DESIGN.md section 6u's table).  The tile shape, the candidate box, its staging in LDS (the whole box, all colours:
+// (DESIGN.md section 6u's table).  The walk described below is drizzle_walk.hpp's drizzle_cfa_rows.  The tile shape, the candidate box, its staging in LDS (the whole box, all colours:
 // drizzle_tile_paths() answers for this kernel too) and a candidate's arithmetic (dz_candidate_weight) are drizzle.hpp's.
 //
 // The strided window.  A work item does not test the (2R + 1)^2 pixels of its window for their colour: it walks the
@@ -18,6 +18,7 @@
 #include <math.h>
 
 #include "drizzle.hpp"
+#include "drizzle_walk.hpp"
 #include "frame_common.hpp"
 #include "launch_common.hpp"
 
@@ -25,70 +26,7 @@ namespace nl {
 
 namespace {
 
-// drizzle.hip's drizzle_rows over the channel's positions of each window
-template <int R, bool POINT, bool GREEN, class Index>
-__device__ __forceinline__ void drizzle_cfa_rows(const float *__restrict__ mem, int org_x, int org_y, Index pitch, int src_w,
-                                                 int src_h, float *__restrict__ sum, float *__restrict__ wgt, int dst_w,
-                                                 int row0, int c0, int r_first, int r_end, const DzGeom &q, float weight,
-                                                 bool first, const DzChannel &ch)
-{
-    constexpr int NR = GREEN ? 2 * R + 1 : R + 1, NC = R + 1;
-    const int lane = threadIdx.x & 63;
-    const float x_last = fminf((float)src_w + (float)R, 2147483520.0f), y_last = fminf((float)src_h + (float)R, 2147483520.0f);
-    for (int r = r_first + (int)(threadIdx.x >> 6); r < r_end; r += 4) {
-        const float py = (float)(row0 + r);
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const int col = c0 + lane + 64 * k;
-            if (col >= dst_w) continue;
-            const float px = (float)col;
-            const float X = proj_x(q.g, px, py), Y = proj_y(q.g, px, py);
-            const float xc = floorf(X + 0.5f), yc = floorf(Y + 0.5f);
-            const int64_t at = (int64_t)r * dst_w + col;
-            float s = 0.0f, t = 0.0f;
-            if (!first) { s = sum[at]; t = wgt[at]; }
-            if (xc >= -(float)R && xc <= x_last && yc >= -(float)R && yc <= y_last) {
-                const int xi = (int)xc, yi = (int)yc;
-                const int wx = xi - R, wy = yi - R, x_end = xi + R, y_end = yi + R;      // (x_end + 1 stays an int)
-                // the first row / column of the channel's parity at or behind the window's start
-                const int j_first = GREEN ? wy : wy + ((wy ^ ch.par_y) & 1);
-                const int i_sparse = wx + ((wx ^ ch.par_x) & 1);
-                float v[NR][NC], wa[NR][NC];
-#pragma unroll
-                for (int dj = 0; dj < NR; dj++) {
-                    const int j = GREEN ? j_first + dj : j_first + 2 * dj;
-                    const float fj = (float)j;
-                    const int i_first = GREEN ? wx + ((wx ^ j ^ ch.par_x) & 1) : i_sparse;
-                    const bool row_ok = (GREEN || j <= y_end) && j >= ch.yo && j < src_h;
-#pragma unroll
-                    for (int di = 0; di < NC; di++) {
-                        const int i = i_first + 2 * di;
-                        const float fi = (float)i;
-                        bool ok = row_ok && i <= x_end && i >= ch.xo && i < src_w;
-                        wa[dj][di] = dz_candidate_weight<POINT>(q, fi, fj, px, py, weight, ok);
-                        const Index p = ok ? (Index)(j - org_y) * pitch + (Index)(i - org_x) : (Index)0;
-                        v[dj][di] = mem[p];
-                    }
-                }
-#pragma unroll
-                for (int dj = 0; dj < NR; dj++) {
-#pragma unroll
-                    for (int di = 0; di < NC; di++) {
-                        const float x = v[dj][di];
-                        const bool ok = x == x && wa[dj][di] == wa[dj][di]; // NaN = no data; a NaN weight = no candidate
-                        const float sn = s + x * wa[dj][di], tn = t + wa[dj][di];
-                        s = ok ? sn : s;
-                        t = ok ? tn : t;
-                    }
-                }
-            }
-            sum[at] = s;
-            wgt[at] = t;
-        }
-    }
-}
-
-// flags: drizzle_tile_kernel's
+// flags: drizzle_walk.hpp's drizzle_tile
 template <int R, bool POINT, bool GREEN>
 __global__ __launch_bounds__(256) void drizzle_cfa_tile_kernel(const float *__restrict__ src, int src_w, int src_h,
                                                                float *__restrict__ sum, float *__restrict__ wgt, int dst_w,
@@ -96,21 +34,8 @@ __global__ __launch_bounds__(256) void drizzle_cfa_tile_kernel(const float *__re
                                                                DzChannel ch)
 {
     __shared__ float lds[kDzLdsFloats];
-    const int c0 = blockIdx.x * kProjTileW, r0 = blockIdx.y * kProjTileH;
-    const int c1 = min(c0 + kProjTileW, dst_w) - 1, r_end = min(r0 + kProjTileH, rows);
-    const bool vec = flags & 1u, first = flags & 4u;
-    ProjBox b = {0, 0, 0, 0, 0};
-    const bool staged = (flags & 2u) && dz_tile_box(q.g, R, src_w, src_h, c0, c1, row0 + r0, row0 + r_end - 1, vec, b);
-    if (staged) {                                                            // (uniform over the workgroup)
-        if (vec) stage_box<true>(src, src_w, b, lds);
-        else stage_box<false>(src, src_w, b, lds);
-        __syncthreads();
-        drizzle_cfa_rows<R, POINT, GREEN, int>(lds, b.x0, b.y0, b.pitch, src_w, src_h, sum, wgt, dst_w, row0, c0, r0, r_end, q,
-                                               weight, first, ch);
-    } else {
-        drizzle_cfa_rows<R, POINT, GREEN, int64_t>(src, 0, 0, src_w, src_w, src_h, sum, wgt, dst_w, row0, c0, r0, r_end, q,
-                                                   weight, first, ch);
-    }
+    drizzle_cfa_tile<R, DzDrop<POINT>, GREEN>(lds, src, src_w, src_h, sum, wgt, dst_w, row0, rows, q.g, DzDrop<POINT>{q, weight},
+                                              flags, ch);
 }
 
 // nl_stack_frame_reject_against's test on one pixel, and its counting: the wave sums, then the four wave values in

@@ -1,8 +1,10 @@
 // nlstack_drizzle.hip -- the entries of include/nlstack_drizzle.h (AN EXTENSION: the reference has no drizzle): the
 // geometry, laying a resident frame onto the two planes of a finer output grid, the quotient of the planes, and the
-// rejection of a frame's outliers against a model; and of include/nlstack_cfadrizzle.h (AN EXTENSION too): the same for
-// one channel of a raw Bayer mosaic, the mosaic's transform and CosmeticCorrectionBayer in place on a resident mosaic.
-// One of the units of the frame steps (nlstack_frame_common.hpp); kernels in drizzle.hip, drizzle_cfa.hip and bayer.hip.
+// rejection of a frame's outliers against a model; of include/nlstack_cfadrizzle.h (AN EXTENSION too): the same for
+// one channel of a raw Bayer mosaic, the mosaic's transform and CosmeticCorrectionBayer in place on a resident mosaic;
+// and of include/nlstack_sqdrizzle.h (AN EXTENSION too): the square kernel of both, the same checks under its names.
+// One of the units of the frame steps (nlstack_frame_common.hpp); kernels in drizzle.hip, drizzle_cfa.hip,
+// drizzle_square.hip and bayer.hip.
 #include <math.h>
 
 #include "bayer.hpp"
@@ -11,8 +13,10 @@
 
 namespace {
 
-// The definition's geometry in double, rounded to fp32 once; what needs no handle of a drizzle call's arguments.
-int drizzle_geometry(const char *who, const float *trans, float scale, float pixfrac, nl::DzGeom *out)
+// The definition's geometry in double, rounded to fp32 once; what needs no handle of a drizzle call's arguments.  With
+// sq the geometry of include/nlstack_sqdrizzle.h: the corners and the bounding box of the drop as well, and its R.
+int drizzle_geometry(const char *who, const float *trans, float scale, float pixfrac, nl::DzGeom *out,
+                     nl::DzSquare *sq = nullptr)
 {
     if (!trans) return fail(NL_ERR_INVALID_ARG, "%s: null transform", who);
     if (!isfinite(scale) || !(scale > 0.0f)) return fail(NL_ERR_INVALID_ARG, "%s: scale %g (a finite number > 0)", who, scale);
@@ -27,10 +31,26 @@ int drizzle_geometry(const char *who, const float *trans, float scale, float pix
     const double Gc = -(Ga * Fc + Gb * Ff), Gf = -(Gd * Fc + Ge * Ff);
     const double hw = 0.5 * p * sqrt(fabs(det));
     const double reach = 0.5 + hw;
-    const double span = fmax((fabs(Ga) + fabs(Gb)) * reach, (fabs(Gd) + fabs(Ge)) * reach) + 0.5 + 1.0 / 64;
+    double span = fmax((fabs(Ga) + fabs(Gb)) * reach, (fabs(Gd) + fabs(Ge)) * reach) + 0.5 + 1.0 / 64;
+    nl::DzSquare corners = {{0, 0, 0, 0}, {0, 0, 0, 0}, 0, 0};
+    if (sq) {
+        const double h = 0.5 * p, ox[4] = {-h, -h, h, h}, oy[4] = {-h, h, h, -h};
+        for (int k = 0; k < 4; k++) {
+            const int from = det < 0 ? 3 - k : k;              // (either orientation: a positive edge sum)
+            corners.cx[k] = (float)(Fa * ox[from] + Fb * oy[from]);
+            corners.cy[k] = (float)(Fd * ox[from] + Fe * oy[from]);
+        }
+        const double bx = h * (fabs(Fa) + fabs(Fb)), by = h * (fabs(Fd) + fabs(Fe));
+        const double reach_x = 0.5 + bx, reach_y = 0.5 + by;
+        corners.bx = (float)bx;
+        corners.by = (float)by;
+        span = fmax(fabs(Ga) * reach_x + fabs(Gb) * reach_y, fabs(Gd) * reach_x + fabs(Ge) * reach_y) + 0.5 + 1.0 / 64;
+    }
     const nl::DzGeom g = {{(float)Fa, (float)Fb, (float)Fc, (float)Fd, (float)Fe, (float)Ff},
                           {(float)Ga, (float)Gb, (float)Gc, (float)Gd, (float)Ge, (float)Gf}, (float)hw, 0};
-    const float all[13] = {g.f.a, g.f.b, g.f.c, g.f.d, g.f.e, g.f.f, g.g.a, g.g.b, g.g.c, g.g.d, g.g.e, g.g.f, g.hw};
+    const float all[23] = {g.f.a, g.f.b, g.f.c, g.f.d, g.f.e, g.f.f, g.g.a, g.g.b, g.g.c, g.g.d, g.g.e, g.g.f, g.hw,
+                           corners.cx[0], corners.cx[1], corners.cx[2], corners.cx[3], corners.cy[0], corners.cy[1],
+                           corners.cy[2], corners.cy[3], corners.bx, corners.by};
     for (float v : all)
         if (!isfinite(v)) return fail(NL_ERR_INVALID_ARG, "%s: a coefficient of the geometry is not finite", who);
     const double R = ceil(span);
@@ -39,6 +59,7 @@ int drizzle_geometry(const char *who, const float *trans, float scale, float pix
                     who, R, NL_DZ_MAX_RADIUS);
     *out = g;
     out->radius = (int)R;
+    if (sq) *sq = corners;
     return NL_OK;
 }
 
@@ -58,23 +79,31 @@ int channel_of(const char *who, const char *channel, const char *cfa, nl::DzChan
 struct DzWho { const char *who, *source, *sum, *wgt; };
 #define NL_DZ_WHO(name) {name, name " (source)", name " (sum plane)", name " (weight plane)"}
 
+// developer switches of the square drizzle as launch_drizzle_square takes them
+unsigned square_switches(const nl_stack *h)
+{
+    return project_switches(h) | ((h->dev_flags & kDevSquareEveryCandidate) ? nl::kDzSquareEveryCandidate : 0u);
+}
+
 // nl_stack_frame_drizzle_from and, with cfa_form, nl_stack_frame_drizzle_cfa_from: the same checks in the same order
-// under the entry's own name, the names of the CFA form behind the kernel and the weight
+// under the entry's own name, the names of the CFA form behind the kernel and the weight; with square the two
+// square entries, which have no kernel to check
 int drizzle_from(const DzWho &names, nl_stack_t *dst, int sum_idx, int wgt_idx, nl_stack_t *src, int src_idx,
                  const float *trans, float scale, float pixfrac, float weight, int first, int kernel, bool cfa_form,
-                 const char *channel, const char *cfa)
+                 const char *channel, const char *cfa, bool square = false)
 {
     const char *who = names.who;
     // in front of any device work: what needs no handle
     if (!trans) return fail(NL_ERR_INVALID_ARG, "%s: null transform", who);
-    if (kernel != NL_DZ_TURBO && kernel != NL_DZ_POINT)
+    if (!square && kernel != NL_DZ_TURBO && kernel != NL_DZ_POINT)
         return fail(NL_ERR_INVALID_ARG, "%s: unknown kernel %d (NL_DZ_TURBO 0, NL_DZ_POINT 1)", who, kernel);
     if (!isfinite(weight) || !(weight > 0.0f)) return fail(NL_ERR_INVALID_ARG, "%s: weight %g (a finite number > 0)", who, weight);
     nl::DzChannel ch = {0, 0, 0, 0, 0};
     int rc = cfa_form ? channel_of(who, channel, cfa, &ch) : NL_OK;
     if (rc != NL_OK) return rc;
     nl::DzGeom geom;
-    rc = drizzle_geometry(who, trans, scale, pixfrac, &geom);
+    nl::DzSquare sq;
+    rc = drizzle_geometry(who, trans, scale, pixfrac, &geom, square ? &sq : nullptr);
     if (rc != NL_OK) return rc;
     if (!dst || !src) return fail(NL_ERR_INVALID_ARG, "%s: null handle", who);
     NL_CHECK_HANDLE(src);
@@ -96,13 +125,36 @@ int drizzle_from(const DzWho &names, nl_stack_t *dst, int sum_idx, int wgt_idx, 
         return fail(NL_ERR_INVALID_ARG, "%s: slot %d of one handle is source and destination (a drizzle cannot run in place)", who, src_idx);
     if (src != dst && (rc = nl_stack_order_stream_after(src, dst->stream)) != NL_OK) return rc;
     NL_HIP(hipSetDevice(dst->device));
-    if (cfa_form)
+    if (square && cfa_form)
+        NL_HIP(nl::launch_drizzle_square_cfa(s, src->width, src->height, d_sum, d_wgt, dst->width, dst->row0, dst->rows, geom,
+                                             sq, weight, first != 0, ch, square_switches(dst), dst->stream));
+    else if (square)
+        NL_HIP(nl::launch_drizzle_square(s, src->width, src->height, d_sum, d_wgt, dst->width, dst->row0, dst->rows, geom, sq,
+                                         weight, first != 0, square_switches(dst), dst->stream));
+    else if (cfa_form)
         NL_HIP(nl::launch_drizzle_cfa(s, src->width, src->height, d_sum, d_wgt, dst->width, dst->row0, dst->rows, geom, weight,
                                       first != 0, kernel == NL_DZ_POINT, ch, project_switches(dst), dst->stream));
     else
         NL_HIP(nl::launch_drizzle(s, src->width, src->height, d_sum, d_wgt, dst->width, dst->row0, dst->rows, geom, weight,
                                   first != 0, kernel == NL_DZ_POINT, project_switches(dst), dst->stream));
     NL_HIP(hipStreamSynchronize(dst->stream));                 // the caller may overwrite the source slot at once
+    return NL_OK;
+}
+
+// nl_stack_drizzle_tile_paths and, with square, nl_stack_drizzle_square_tile_paths (the window of the square R)
+int tile_paths(const char *who, nl_stack_t *dst, nl_stack_t *src, int src_idx, const float *trans, float scale, float pixfrac,
+               int64_t *staged, int64_t *direct, bool square)
+{
+    if (!dst || !src || !trans || !staged || !direct) return fail(NL_ERR_INVALID_ARG, "%s: null argument", who);
+    nl::DzGeom geom;
+    nl::DzSquare sq;
+    const int rc = drizzle_geometry(who, trans, scale, pixfrac, &geom, square ? &sq : nullptr);
+    if (rc != NL_OK) return rc;
+    if (src_idx < 0 || src_idx >= src->n_frames)               // (a host query: no device, no stream is touched)
+        return fail(NL_ERR_INVALID_ARG, "%s: bad index %d", who, src_idx);
+    const float *s = src->d_frames + (int64_t)src_idx * src->fstride;
+    nl::drizzle_tile_paths(s, src->width, src->height, dst->width, dst->row0, dst->rows, geom, project_switches(dst),
+                           staged, direct);
     return NL_OK;
 }
 
@@ -160,16 +212,7 @@ int nl_stack_frame_drizzle_cfa_from(nl_stack_t *dst, int sum_idx, int wgt_idx, n
 int nl_stack_drizzle_tile_paths(nl_stack_t *dst, nl_stack_t *src, int src_idx, const float trans[6], float scale,
                                 float pixfrac, int64_t *staged, int64_t *direct)
 {
-    if (!dst || !src || !trans || !staged || !direct) return fail(NL_ERR_INVALID_ARG, "drizzle_tile_paths: null argument");
-    nl::DzGeom geom;
-    const int rc = drizzle_geometry("drizzle_tile_paths", trans, scale, pixfrac, &geom);
-    if (rc != NL_OK) return rc;
-    if (src_idx < 0 || src_idx >= src->n_frames)               // (a host query: no device, no stream is touched)
-        return fail(NL_ERR_INVALID_ARG, "drizzle_tile_paths: bad index %d", src_idx);
-    const float *s = src->d_frames + (int64_t)src_idx * src->fstride;
-    nl::drizzle_tile_paths(s, src->width, src->height, dst->width, dst->row0, dst->rows, geom, project_switches(dst),
-                           staged, direct);
-    return NL_OK;
+    return tile_paths("drizzle_tile_paths", dst, src, src_idx, trans, scale, pixfrac, staged, direct, false);
 }
 
 int nl_stack_drizzle_finalize(nl_stack_t *h, int sum_idx, int wgt_idx, int out_idx, float min_weight, float empty)
@@ -214,6 +257,49 @@ int nl_stack_frame_reject_against_cfa(nl_stack_t *h, int idx, int model_idx, con
     unsigned long long *counts = reinterpret_cast<unsigned long long *>(h->d_stat_partial);
     NL_HIP(nl::launch_reject_against_cfa(d, m, h->width, h->row0, h->rows, ch, low, high, counts, kStatBlocks, h->stream));
     return reject_counts(h, counts, n_low, n_high);
+}
+
+int nl_drizzle_square_geometry(const float trans[6], float scale, float pixfrac, float src_to_out[6], float out_to_src[6],
+                               float corners[8], float box_half[2], int *radius)
+{
+    if (!trans || !src_to_out || !out_to_src || !corners || !box_half || !radius)
+        return fail(NL_ERR_INVALID_ARG, "drizzle_square_geometry: null argument");
+    nl::DzGeom g;
+    nl::DzSquare sq;
+    const int rc = drizzle_geometry("drizzle_square_geometry", trans, scale, pixfrac, &g, &sq);
+    if (rc != NL_OK) return rc;
+    const float F[6] = {g.f.a, g.f.b, g.f.c, g.f.d, g.f.e, g.f.f}, G[6] = {g.g.a, g.g.b, g.g.c, g.g.d, g.g.e, g.g.f};
+    memcpy(src_to_out, F, sizeof F);
+    memcpy(out_to_src, G, sizeof G);
+    for (int k = 0; k < 4; k++) {
+        corners[2 * k] = sq.cx[k];
+        corners[2 * k + 1] = sq.cy[k];
+    }
+    box_half[0] = sq.bx;
+    box_half[1] = sq.by;
+    *radius = g.radius;
+    return NL_OK;
+}
+
+int nl_stack_frame_drizzle_square_from(nl_stack_t *dst, int sum_idx, int wgt_idx, nl_stack_t *src, int src_idx,
+                                       const float trans[6], float scale, float pixfrac, float weight, int first)
+{
+    return drizzle_from(NL_DZ_WHO("frame_drizzle_square_from"), dst, sum_idx, wgt_idx, src, src_idx, trans, scale, pixfrac,
+                        weight, first, 0, false, nullptr, nullptr, true);
+}
+
+int nl_stack_frame_drizzle_square_cfa_from(nl_stack_t *dst, int sum_idx, int wgt_idx, nl_stack_t *src, int src_idx,
+                                           const float trans[6], float scale, float pixfrac, float weight, int first,
+                                           const char *channel, const char *cfa)
+{
+    return drizzle_from(NL_DZ_WHO("frame_drizzle_square_cfa_from"), dst, sum_idx, wgt_idx, src, src_idx, trans, scale, pixfrac,
+                        weight, first, 0, true, channel, cfa, true);
+}
+
+int nl_stack_drizzle_square_tile_paths(nl_stack_t *dst, nl_stack_t *src, int src_idx, const float trans[6], float scale,
+                                       float pixfrac, int64_t *staged, int64_t *direct)
+{
+    return tile_paths("drizzle_square_tile_paths", dst, src, src_idx, trans, scale, pixfrac, staged, direct, true);
 }
 
 int nl_drizzle_cfa_transform(const float trans_debayered[6], const char *cfa, float trans_raw[6])

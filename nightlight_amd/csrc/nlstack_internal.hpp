@@ -253,6 +253,7 @@ struct nl_stack {
 constexpr unsigned kDevProjectDirect = 32768u;       // no tile stages its source box in LDS
 constexpr unsigned kDevProjectPlainStores = 65536u;  // plain instead of nontemporal result stores
 constexpr unsigned kDevColourDirect = 131072u;       // the darkest-block means stage no strip in LDS
+constexpr unsigned kDevSquareEveryCandidate = 262144u;  // the square drizzle evaluates the edges of every candidate
 inline unsigned project_switches(const nl_stack *h)
 {
     return ((h->dev_flags & kDevProjectDirect) ? nl::kProjDirectOnly : 0u) |

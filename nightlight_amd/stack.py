@@ -722,6 +722,34 @@ class StackHandle:
                                                              capi.fptr(t), float(scale), float(pixfrac), float(weight),
                                                              int(bool(first)), int(kernel), _cstr(channel), _cstr(cfa)))
 
+    def frame_drizzle_square_from(self, sum_idx, wgt_idx, src, src_idx, trans, scale, pixfrac=1.0, weight=1.0,
+                                  first=False):
+        """frame_drizzle_from with the square kernel: a drop is the image of the shrunken pixel under the transform (a
+        rotated square) and lays its flux down by the exact area of its overlap with each output pixel, under any
+        rotation (include/nlstack_sqdrizzle.h; an EXTENSION)."""
+        t = np.ascontiguousarray(trans, dtype=np.float32).reshape(6)
+        capi.check(self._lib.nl_stack_frame_drizzle_square_from(self._h, int(sum_idx), int(wgt_idx), src._h, int(src_idx),
+                                                                capi.fptr(t), float(scale), float(pixfrac), float(weight),
+                                                                int(bool(first))))
+
+    def frame_drizzle_square_cfa_from(self, sum_idx, wgt_idx, src, src_idx, trans, scale, channel, cfa="RGGB", pixfrac=1.0,
+                                      weight=1.0, first=False):
+        """frame_drizzle_cfa_from with the square kernel: the planes equal those of frame_drizzle_square_from on a copy
+        of the mosaic whose other pixels are NaN (include/nlstack_sqdrizzle.h; an EXTENSION)."""
+        t = np.ascontiguousarray(trans, dtype=np.float32).reshape(6)
+        capi.check(self._lib.nl_stack_frame_drizzle_square_cfa_from(self._h, int(sum_idx), int(wgt_idx), src._h,
+                                                                    int(src_idx), capi.fptr(t), float(scale),
+                                                                    float(pixfrac), float(weight), int(bool(first)),
+                                                                    _cstr(channel), _cstr(cfa)))
+
+    def drizzle_square_tile_paths(self, src, src_idx, trans, scale, pixfrac=1.0):
+        """drizzle_tile_paths for the two square entries: the window of the square radius (developer query)."""
+        t = np.ascontiguousarray(trans, dtype=np.float32).reshape(6)
+        staged, direct = C.c_int64(0), C.c_int64(0)
+        capi.check(self._lib.nl_stack_drizzle_square_tile_paths(self._h, src._h, int(src_idx), capi.fptr(t), float(scale),
+                                                                float(pixfrac), C.byref(staged), C.byref(direct)))
+        return int(staged.value), int(direct.value)
+
     def frame_reject_against_cfa(self, idx, model_idx, channel, cfa, low, high):
         """(n_low, n_high): frame_reject_against on the pixels of `channel` of the `cfa` mosaic in slot idx; every
         other pixel keeps its bits and counts nowhere."""
@@ -1325,6 +1353,19 @@ def drizzle_geometry(trans, scale, pixfrac=1.0):
     capi.check(capi.load().nl_drizzle_geometry(capi.fptr(t), float(scale), float(pixfrac), capi.fptr(f), capi.fptr(g),
                                                C.byref(hw), C.byref(radius)))
     return f, g, np.float32(hw.value), int(radius.value)
+
+
+def drizzle_square_geometry(trans, scale, pixfrac=1.0):
+    """(src_to_out, out_to_src, corners, box_half, radius) of a square drizzle: corners is float32 (4, 2), the corners
+    of a drop relative to its centre in output pixels in the order the kernel walks them; box_half = (bx, by), the
+    half-sides of the drop's bounding box (include/nlstack_sqdrizzle.h; host only, no device)."""
+    t = np.ascontiguousarray(trans, dtype=np.float32).reshape(6)
+    f, g = np.empty(6, np.float32), np.empty(6, np.float32)
+    corners, box = np.empty(8, np.float32), np.empty(2, np.float32)
+    radius = C.c_int(0)
+    capi.check(capi.load().nl_drizzle_square_geometry(capi.fptr(t), float(scale), float(pixfrac), capi.fptr(f), capi.fptr(g),
+                                                      capi.fptr(corners), capi.fptr(box), C.byref(radius)))
+    return f, g, corners.reshape(4, 2), box, int(radius.value)
 
 
 def drizzle_cfa_transform(trans_debayered, cfa):
